@@ -135,6 +135,10 @@ def parse(argv=None):
                          "layered batch pass per step inside the timed region")
     ap.add_argument("--profile-steps", type=int, default=0,
                     help="batches measured per-stage with HIP events (0 = the same batches as the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame set of the last timed step (what render_frames hands its "
+                         "caller) as DIR/<name>.npy in float32: whole, or a fixed seeded sample of pixel positions shared by "
+                         "every array when the whole set would exceed 60 MiB (single process only)")
     return ap.parse_args(argv)
 
 
@@ -472,6 +476,38 @@ class StubEngine:
 # --------------------------------------------------------------------------------------------------------------------
 # worker
 
+DUMP_BYTES = 60 * 2**20        # --dump-outputs: data bytes in all (the .npy headers add a few hundred bytes)
+DUMP_SEED = 0
+
+
+def dump_outputs(frames: dict, out_dir, budget: int = DUMP_BYTES, seed: int = DUMP_SEED) -> dict:
+    """Writes every [B, C, H, W] array of a frame set as out_dir/<name>.npy in float32.  When the whole set is larger than
+    `budget` bytes, each array keeps the same pixel positions -- a sorted sample drawn from default_rng(seed), a function of
+    (H, W, budget, channels in all) only -- as [B, C, n] instead of [B, C, H, W], so that two builds run with the same
+    arguments compare output for output.  Returns {name: shape written} and the sample size (None: whole arrays)."""
+    import torch
+    arrays = {k: v for k, v in frames.items() if isinstance(v, torch.Tensor) and v.dim() == 4}
+    if not arrays:
+        raise ValueError("dump_outputs: the frame set holds no [B, C, H, W] array")
+    H, W = next(iter(arrays.values())).shape[-2:]
+    bytes_per_pixel = 4 * sum(v.shape[0] * v.shape[1] for v in arrays.values())
+    n = min(H * W, budget // bytes_per_pixel)
+    if n < 1:
+        raise ValueError(f"dump_outputs: one pixel of every array takes {bytes_per_pixel} bytes, more than {budget}")
+    idx = None
+    if n < H * W:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(seed).choice(H * W, size=n, replace=False)))
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    written = {}
+    for name, t in arrays.items():
+        a = t if idx is None else t.flatten(2).index_select(2, idx.to(t.device))
+        a = a.to(torch.float32).cpu().numpy()
+        np.save(out / f"{name}.npy", a)
+        written[name] = list(a.shape)
+    return {"arrays": written, "sampled_pixels": None if idx is None else int(n)}
+
+
 def _checksums(local):
     """Per-tensor byte sums (int64) of a packed batch -- what the gather check compares across ranks."""
     import torch
@@ -539,6 +575,15 @@ def run_worker(args):
         else:
             dist.init_process_group("gloo")
         world = dist.get_world_size()              # the size actually initialised is what the line reports
+
+    def barrier():
+        """dist.barrier() first asks torch for the machine's accelerator, which starts the HIP runtime: on a GPU box every
+        stub rank would then hold the GPU open.  A rank without a device synchronises with an all-reduce of one CPU value."""
+        if dev.type == "cpu":
+            dist.all_reduce(torch.zeros(1))
+        else:
+            dist.barrier()
+
     devices = [None]
     me = {"rank": rank, "device": str(dev)}
     if dev.type == "cuda":
@@ -669,14 +714,14 @@ def run_worker(args):
         rank's own elapsed seconds between the two barriers' inner synchronisations)."""
         eng.sync()
         if use_dist:
-            dist.barrier()
+            barrier()
         eng.sync()
         t0 = time.perf_counter()
         run_steps(first, count, gather)
         eng.sync()
         own = time.perf_counter() - t0             # this rank's own work, before it waits for the others
         if use_dist:
-            dist.barrier()
+            barrier()
         eng.sync()
         el = time.perf_counter() - t0
         per_rank = [own]
@@ -703,6 +748,11 @@ def run_worker(args):
     repeats = max(1, args.repeats)
     gstat.update(host_s=0.0, wire_s=0.0, batches=0)
     runs = [timed(args.warmup, args.steps, gather_on) for _ in range(repeats)]
+    dumped = None
+    if args.dump_outputs:                          # before anything else renders into the frame sets
+        last = args.warmup + args.steps - 1
+        dumped = dump_outputs(eng.frames if args.sync_steps else eng.frame_sets[last % n_slots], args.dump_outputs)
+        dumped.update(dir=str(args.dump_outputs), step=last)
     gather_host_s, gather_wire_s = gstat["host_s"] / repeats, gstat["wire_s"] / repeats
     order = sorted(range(repeats), key=lambda r: runs[r][0])
     med = order[(repeats - 1) // 2]                # the median repeat (lower middle for an even count)
@@ -756,7 +806,7 @@ def run_worker(args):
             raise SystemExit("bench.py: gathered frames differ from what the ranks sent (gather check failed)")
 
     if rank != 0:
-        dist.barrier()
+        barrier()
         dist.destroy_process_group()
         return 0
 
@@ -774,6 +824,8 @@ def run_worker(args):
         "per_rank_s": {"min": round(min(per_rank), 6), "max": round(max(per_rank), 6), "rank0": round(per_rank[0], 6),
                        "all": [round(x, 6) for x in per_rank]},
     }
+    if dumped is not None:
+        line["dumped_outputs"] = dumped
     launcher = ("self: python bench.py --gpus N started torch.distributed.run as a child process"
                 if os.environ.get("PGR_BENCH_LAUNCHER") == "self" else
                 ("external torchrun (WORLD_SIZE in the environment)" if env_world else "single process"))
@@ -809,14 +861,14 @@ def run_worker(args):
                             "distributed": dist_info, "gather": gather_info})
         emit(line)
         if use_dist:
-            dist.barrier()
+            barrier()
             dist.destroy_process_group()
         return 0
 
     _finish_real_line(args, eng, line, value, world, dist_info, gather_info, rehearsal)
     emit(line)
     if use_dist:
-        dist.barrier()
+        barrier()
         dist.destroy_process_group()
     return 0
 
@@ -1258,6 +1310,10 @@ def run_cpu_only(args):
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parse(argv)
+    if args.dump_outputs and (max(args.gpus or 1, int(os.environ.get("WORLD_SIZE") or 1)) > 1 or args.force_dist
+                              or args.stub_renderer or args.facade or args.cpu_only):
+        raise SystemExit("--dump-outputs writes the frames of the single-process product path: not with --gpus N > 1, "
+                         "--force-dist, --stub-renderer, --facade or --cpu-only")
     if args.cpu_only:
         if "--workload" not in " ".join(argv):
             args.workload = "c1"

@@ -166,6 +166,66 @@ def test_dynamic_sequence_two_ranks_rehearsal(gpu_device):
     assert line["config"]["objects"] == 20
 
 
+def test_dump_outputs_writes_whole_or_one_shared_pixel_sample(tmp_path):
+    """bench.dump_outputs: every [B, C, H, W] array of a frame set as float32 .npy -- whole when it fits, else the same seeded
+    pixel positions in every array, within the byte budget, and the same positions on every call."""
+    import numpy as np
+    import torch
+    import bench
+    B, H, W = 2, 8, 10
+    pix = torch.arange(H * W, dtype=torch.float32).view(1, 1, H, W)
+    frames = {"color": pix.repeat(B, 3, 1, 1) + 1000 * torch.arange(3).view(1, 3, 1, 1),
+              "depth": pix.repeat(B, 1, 1, 1) * 0.5,
+              "masks": (pix.repeat(B, 2, 1, 1) % 2).to(torch.uint8),
+              "records": torch.zeros((B, 16), dtype=torch.uint8)}                 # not image-shaped: not an output array
+    whole = bench.dump_outputs(frames, tmp_path / "whole")
+    assert whole["sampled_pixels"] is None and sorted(whole["arrays"]) == ["color", "depth", "masks"]
+    for k in whole["arrays"]:
+        a = np.load(tmp_path / "whole" / f"{k}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, frames[k].float().numpy())
+    budget = 4 * B * (3 + 1 + 2) * 20 + 7                                           # room for 20 of the 80 pixels
+    for d in ("s1", "s2"):
+        got = bench.dump_outputs(frames, tmp_path / d, budget=budget)
+        assert got["sampled_pixels"] == 20 and got["arrays"]["color"] == [B, 3, 20]
+    assert sum(f.stat().st_size - 128 for f in (tmp_path / "s1").glob("*.npy")) <= budget     # (128: the .npy header)
+    c, dep, m = (np.load(tmp_path / "s1" / f"{k}.npy") for k in ("color", "depth", "masks"))
+    at = c[0, 0].astype(np.int64)                                                  # the sampled pixel positions
+    assert len(set(at.tolist())) == 20 and np.all(np.diff(at) > 0)
+    assert np.array_equal(c[1, 2], at + 2000) and np.array_equal(dep[1, 0], at * 0.5) and np.array_equal(m[0, 1], at % 2)
+    for k in ("color", "depth", "masks"):
+        assert np.array_equal(np.load(tmp_path / "s1" / f"{k}.npy"), np.load(tmp_path / "s2" / f"{k}.npy"))
+
+
+def test_dump_outputs_is_refused_off_the_single_process_path(tmp_path):
+    p, line = _run([sys.executable, "bench.py", "--stub-renderer", "--steps", "1", "--dump-outputs", str(tmp_path)])
+    assert p.returncode != 0 and line is None and "--dump-outputs" in p.stderr
+    assert not any(tmp_path.iterdir())
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_last_timed_step_and_reproducible(gpu_device, tmp_path):
+    """bench.py --dump-outputs on the product path: two runs whose last timed step is the same batch (step 2: warm-up 1 +
+    2 steps, and no warm-up + 3 steps) dump the same frames, bit for bit; the sample stays within the budget."""
+    import numpy as np
+    lines = {}
+    for tag, warmup, steps in (("a", "1", "2"), ("b", "0", "3")):
+        p, line = _run([sys.executable, "bench.py", "--scale", "0.03", "--steps", steps, "--warmup", warmup, "--batch", "4",
+                        "--views", "16", "--repeats", "2", "--no-drop-in", "--no-cpu-baseline",
+                        "--dump-outputs", str(tmp_path / tag)], timeout=900)
+        assert p.returncode == 0, p.stderr[-3000:]
+        assert line["steps"] == int(steps) and line["ms_per_step"] > 0
+        lines[tag] = line["dumped_outputs"]
+    a, b = lines["a"], lines["b"]
+    assert a["step"] == b["step"] == 2 and a["arrays"] == b["arrays"] and a["sampled_pixels"] == b["sampled_pixels"]
+    assert sorted(a["arrays"]) == ["color", "depth", "masks", "seg", "seg_depth"] and a["arrays"]["color"][:2] == [4, 3]
+    files = sorted((tmp_path / "a").glob("*.npy"))
+    assert [f.stem for f in files] == sorted(a["arrays"]) and sum(f.stat().st_size for f in files) <= 64 * 10**6
+    for f in files:
+        x, y = np.load(f), np.load(tmp_path / "b" / f.name)
+        assert x.dtype == np.float32 and np.isfinite(x).all() and np.array_equal(x, y), f.name
+    assert np.load(tmp_path / "a" / "color.npy").max() > 0                          # something was rendered
+
+
 def test_cpu_only_line_for_config_0():
     """BASELINE.json configs[0] (10 k-Gaussian cube, 256x256, CPU rasterizer: plumbing, no GPU): `bench.py --cpu-only` times
     the oracle alone and says so; no HIP device is touched."""

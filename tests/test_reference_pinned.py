@@ -70,11 +70,20 @@ def test_gaussian_model_getters_merge_mask_and_xyz_poses_equal_the_reference_cla
     from pegasus_amd.gaussian_model import build_rotation
     g = np.load(GOLD / "gs_model.npz")
     a, b = _model(g, "a"), _model(g, "b")
-    for name in ("get_xyz", "get_scaling", "get_rotation", "get_opacity", "get_features"):
+    for name in ("get_xyz", "get_rotation", "get_features"):
         np.testing.assert_array_equal(getattr(a, name).numpy(), g["a." + name], err_msg=name)     # same torch ops: bit-equal
+    # exp / sigmoid: the reference's activations, bit-equal to them on this host.  torch's CPU exp is MKL's vector maths,
+    # whose code path depends on the CPU it runs on (with MKL_CBWR=COMPATIBLE, 12 of the 771 recorded scales come out one
+    # ulp away), so against the recorded values: within one ulp
+    for name, act, raw in (("get_scaling", torch.exp, a._scaling), ("get_opacity", torch.sigmoid, a._opacity)):
+        np.testing.assert_array_equal(getattr(a, name).numpy(), act(raw).numpy(), err_msg=name)
+        np.testing.assert_array_max_ulp(getattr(a, name).numpy(), g["a." + name], maxulp=1)
     assert tuple(a.get_features.shape) == (257, 16, 3) and tuple(a.get_opacity.shape) == (257, 1)
-    np.testing.assert_array_equal(a.get_covariance().numpy(), g["a.get_covariance_1"])
-    np.testing.assert_array_equal(a.get_covariance(1.7).numpy(), g["a.get_covariance_1.7"])
+    # the covariance from the reference's own scales: bit-equal on every host
+    cov = _model(g, "a")
+    cov.scaling_activation = lambda s: torch.from_numpy(g["a.get_scaling"])
+    np.testing.assert_array_equal(cov.get_covariance().numpy(), g["a.get_covariance_1"])
+    np.testing.assert_array_equal(cov.get_covariance(1.7).numpy(), g["a.get_covariance_1.7"])
     # merge: once into a deep copy (the frame loop's order, pegasus.py:255-264: in-place append), once into a plain model
     for m in (copy.deepcopy(a), _model(g, "a")):
         m.merge_gaussians(b)
@@ -87,10 +96,19 @@ def test_gaussian_model_getters_merge_mask_and_xyz_poses_equal_the_reference_cla
     np.testing.assert_array_equal(m.max_radii2D.numpy(), g["masked.max_radii2D"])
     R, t, T = (torch.from_numpy(g[k]) for k in ("R", "t", "T"))
     m = _model(g, "a"); m.apply_translation_on_xyz(t); np.testing.assert_array_equal(m._xyz.numpy(), g["translated._xyz"])
-    m = _model(g, "a"); m.apply_rotation_on_xyz(R); np.testing.assert_array_equal(m._xyz.numpy(), g["rotated_about_mean._xyz"])
-    m = _model(g, "a"); m.apply_rotation_on_xyz(R, origin=True)
-    np.testing.assert_array_equal(m._xyz.numpy(), g["rotated_about_origin._xyz"])
-    m = _model(g, "a"); m.apply_transformation_on_xyz(T); np.testing.assert_array_equal(m._xyz.numpy(), g["transformed._xyz"])
+    # rotations: the reference's expressions, bit-equal on this host.  R @ xyz is torch's sgemm, MKL again, so against the
+    # recorded values: within two float32 epsilons of the largest coordinate
+    x = torch.from_numpy(g["a_xyz"])
+    c = torch.mean(x, 0)
+    for key, pose, want in (("rotated_about_mean._xyz", lambda m: m.apply_rotation_on_xyz(R), (R @ (x - c).T).T + c),
+                            ("rotated_about_origin._xyz", lambda m: m.apply_rotation_on_xyz(R, origin=True), (R @ x.T).T),
+                            ("transformed._xyz", lambda m: m.apply_transformation_on_xyz(T),
+                             (T[:3, :3] @ (x - c).T).T + c + T[:3, 3])):
+        m = _model(g, "a")
+        pose(m)
+        np.testing.assert_array_equal(m._xyz.numpy(), want.numpy(), err_msg=key)
+        np.testing.assert_allclose(m._xyz.numpy(), g[key], rtol=0, atol=2 * np.finfo(np.float32).eps * np.abs(g[key]).max(),
+                                   err_msg=key)
     # the splat quaternions the reference gets through scipy: R @ build_rotation(q), as a quaternion, sign free
     from scipy.spatial.transform import Rotation as Rot
     Rq = (R @ build_rotation(torch.from_numpy(g["a_rotation"]))).numpy()
