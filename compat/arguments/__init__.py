@@ -1,5 +1,6 @@
 """Argument groups PEGASUS re-uses by appending to sys.argv (pegasus.py:152-154): only the fields the render
-path reads are kept (sh_degree, source/model paths, white_background, data_device; the three pipeline flags)."""
+path reads are kept (sh_degree, source/model paths, white_background, data_device; the three pipeline flags), and the
+3DGS optimisation fields pegasus_amd.train.training reads."""
 from argparse import ArgumentParser, Namespace
 
 
@@ -53,6 +54,23 @@ class PipelineParams(ParamGroup):
 class OptimizationParams(ParamGroup):
     def __init__(self, parser):
         self.iterations = 30_000
+        # the 3DGS optimisation fields with their usual defaults (pegasus_amd.train.OPTIMIZATION_DEFAULTS)
+        self.position_lr_init = 0.00016
+        self.position_lr_final = 0.0000016
+        self.position_lr_delay_mult = 0.01
+        self.position_lr_max_steps = 30_000
+        self.feature_lr = 0.0025
+        self.opacity_lr = 0.05
+        self.scaling_lr = 0.005
+        self.rotation_lr = 0.001
+        self.percent_dense = 0.01
+        self.lambda_dssim = 0.2
+        self.densification_interval = 100
+        self.opacity_reset_interval = 3000
+        self.densify_from_iter = 500
+        self.densify_until_iter = 15_000
+        self.densify_grad_threshold = 0.0002
+        self.random_background = False
         super().__init__(parser, "Optimization Parameters")
 
 

@@ -440,6 +440,39 @@ int32_t pgr_frame_record_layout(int32_t width, int32_t height, int32_t k, PgrRec
 int32_t pgr_pack_records(const float *color_b3hw, const float *depth_bhw, const uint8_t *masks_bkhw, int32_t n_images,
                          int32_t k, int32_t width, int32_t height, uint8_t *records, int64_t record_stride, void *stream);
 
+/* ---- training step (pegasus_amd/train_ops.py) ----------------------------------------------------------------------------
+ * Fused 3DGS image loss over x, y [3,H,W] fp32 (x: the render, y: the ground truth):
+ *   loss = (1 - lambda) mean|x - y| + lambda (1 - mean SSIM(x, y))
+ * SSIM with an 11x11 Gaussian window (sigma 1.5, normalised), one window per channel, zero padding 5, C1 = 0.01^2,
+ * C2 = 0.03^2; means over all 3 H W values.  out3 (device, 3 floats) = {loss, mean |x - y|, mean SSIM}; grad (device
+ * [3,H,W], may be NULL for the value only) = dloss/dx, with sign(0) = 0 for the L1 term.  Deterministic: the sums run in a
+ * fixed order, without atomics.  workspace >= pgr_image_loss_workspace_bytes(height, width). */
+size_t pgr_image_loss_workspace_bytes(int32_t height, int32_t width);
+int32_t pgr_image_loss(const float *x, const float *y, int32_t height, int32_t width, double lambda_dssim, float *out3,
+                       float *grad, void *workspace, size_t workspace_bytes, void *stream);
+
+/* One Adam step over up to PGR_ADAM_MAX_GROUPS parameter groups in one launch, with torch.optim.Adam's single-tensor
+ * arithmetic (no weight decay, no amsgrad).  The table is HOST memory, read during the call; every pointer in it is a
+ * device fp32 array of n elements.  step is the step count AFTER this update (1 on the first step); the bias corrections
+ * are formed on the host in double, as torch forms them.  Groups with n = 0 are skipped. */
+#define PGR_ADAM_MAX_GROUPS 16
+typedef struct PgrAdamGroup {
+    float *param;
+    const float *grad;
+    float *exp_avg;
+    float *exp_avg_sq;
+    int64_t n;
+    double lr;
+    int64_t step;
+} PgrAdamGroup;
+int32_t pgr_adam_step(const PgrAdamGroup *groups, int32_t n_groups, double beta1, double beta2, double eps, void *stream);
+
+/* Densification statistics of one render, for every Gaussian i with radii[i] > 0:
+ *   grad_accum[i] += || viewspace_grad[i, 0:2] ||,  denom[i] += 1,  max_radii2d[i] = max(max_radii2d[i], radii[i])
+ * viewspace_grad: [n, grad_stride] fp32 (the screen-space gradient of render()'s "viewspace_points"). */
+int32_t pgr_densify_stats(int32_t n, const float *viewspace_grad, int32_t grad_stride, const int32_t *radii,
+                          float *grad_accum, float *denom, float *max_radii2d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,6 +96,14 @@ class PgrWorkspaceView(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("splats", "rects", "gauss_sorted", "ranges", "num_instances")]
 
 
+class PgrAdamGroup(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("n", C.c_int64), ("lr", C.c_double), ("step", C.c_int64)]
+
+
+PGR_ADAM_MAX_GROUPS = 16
+
+
 # every symbol include/pegasus_raster.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "pgr_abi_version": (C.c_int32, []),
@@ -160,6 +168,12 @@ SYMBOLS = {
                                        C.c_void_p]),
     "pgr_pack_frames": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pgr_image_loss_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "pgr_image_loss": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pgr_adam_step": (C.c_int32, [C.POINTER(PgrAdamGroup), C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p]),
+    "pgr_densify_stats": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
 }
 
 _lib = None

@@ -1,0 +1,350 @@
+"""COLMAP sparse models (``<source>/sparse/0/{cameras,images,points3D}.{bin,txt}``) read into what the trainer needs:
+cameras with their ground-truth images, the initial point cloud and the camera extent -- the upstream 3DGS scene reader's
+conventions, written for this package (no plyfile / cv2: PLY through ply_io, images through PIL).
+
+Conventions (the ones pegasus_amd.cameras.Camera uses):
+  R = qvec2rotmat(qvec)^T   (camera-to-world rotation),   T = tvec   (world-to-camera translation)
+  FoVx = focal2fov(fx, width), FoVy = focal2fov(fy, height)
+Only PINHOLE and SIMPLE_PINHOLE cameras are supported: the rasterizer has no distortion model."""
+from __future__ import annotations
+
+import os
+import struct
+from dataclasses import dataclass
+from pathlib import Path
+
+import numpy as np
+
+from .graphics import focal2fov, getWorld2View2
+from .ply_io import read_ply_vertices, write_ply_vertices
+
+# model id -> (name, number of parameters) of every COLMAP camera model (COLMAP src/colmap/sensor/models.h)
+CAMERA_MODELS = {0: ("SIMPLE_PINHOLE", 3), 1: ("PINHOLE", 4), 2: ("SIMPLE_RADIAL", 4), 3: ("RADIAL", 5),
+                 4: ("OPENCV", 8), 5: ("OPENCV_FISHEYE", 8), 6: ("FULL_OPENCV", 12), 7: ("FOV", 5),
+                 8: ("SIMPLE_RADIAL_FISHEYE", 4), 9: ("RADIAL_FISHEYE", 5), 10: ("THIN_PRISM_FISHEYE", 12)}
+SUPPORTED_MODELS = ("PINHOLE", "SIMPLE_PINHOLE")
+LLFF_HOLD = 8                                   # eval: every 8th image (sorted by name) is a test camera
+
+
+class UnsupportedCameraModel(ValueError):
+    pass
+
+
+@dataclass
+class ColmapCamera:
+    id: int
+    model: str
+    width: int
+    height: int
+    params: np.ndarray
+
+    @property
+    def focal(self):
+        """(fx, fy)"""
+        if self.model == "SIMPLE_PINHOLE":
+            return float(self.params[0]), float(self.params[0])
+        if self.model == "PINHOLE":
+            return float(self.params[0]), float(self.params[1])
+        raise UnsupportedCameraModel(f"COLMAP camera {self.id}: model {self.model} is not supported (only "
+                                     f"{' / '.join(SUPPORTED_MODELS)}: undistort the images first)")
+
+
+@dataclass
+class ColmapImage:
+    id: int
+    qvec: np.ndarray                            # w, x, y, z (world-to-camera)
+    tvec: np.ndarray
+    camera_id: int
+    name: str
+
+
+def qvec2rotmat(q):
+    w, x, y, z = (float(v) for v in q)
+    return np.array([[1 - 2 * y * y - 2 * z * z, 2 * x * y - 2 * w * z, 2 * z * x + 2 * w * y],
+                     [2 * x * y + 2 * w * z, 1 - 2 * x * x - 2 * z * z, 2 * y * z - 2 * w * x],
+                     [2 * z * x - 2 * w * y, 2 * y * z + 2 * w * x, 1 - 2 * x * x - 2 * y * y]])
+
+
+def rotmat2qvec(R):
+    """Unit quaternion (w, x, y, z), w >= 0, of a rotation matrix (the inverse of qvec2rotmat)."""
+    m = np.asarray(R, dtype=np.float64)
+    tr = m[0, 0] + m[1, 1] + m[2, 2]
+    if tr > 0:
+        s = 2.0 * np.sqrt(tr + 1.0)
+        q = [0.25 * s, (m[2, 1] - m[1, 2]) / s, (m[0, 2] - m[2, 0]) / s, (m[1, 0] - m[0, 1]) / s]
+    elif m[0, 0] > m[1, 1] and m[0, 0] > m[2, 2]:
+        s = 2.0 * np.sqrt(1.0 + m[0, 0] - m[1, 1] - m[2, 2])
+        q = [(m[2, 1] - m[1, 2]) / s, 0.25 * s, (m[0, 1] + m[1, 0]) / s, (m[0, 2] + m[2, 0]) / s]
+    elif m[1, 1] > m[2, 2]:
+        s = 2.0 * np.sqrt(1.0 + m[1, 1] - m[0, 0] - m[2, 2])
+        q = [(m[0, 2] - m[2, 0]) / s, (m[0, 1] + m[1, 0]) / s, 0.25 * s, (m[1, 2] + m[2, 1]) / s]
+    else:
+        s = 2.0 * np.sqrt(1.0 + m[2, 2] - m[0, 0] - m[1, 1])
+        q = [(m[1, 0] - m[0, 1]) / s, (m[0, 2] + m[2, 0]) / s, (m[1, 2] + m[2, 1]) / s, 0.25 * s]
+    q = np.asarray(q) / np.linalg.norm(q)
+    return -q if q[0] < 0 else q
+
+
+def _check_model(cam: ColmapCamera) -> ColmapCamera:
+    if cam.model not in SUPPORTED_MODELS:
+        raise UnsupportedCameraModel(f"COLMAP camera {cam.id}: model {cam.model} is not supported (only "
+                                     f"{' / '.join(SUPPORTED_MODELS)}: undistort the images first)")
+    return cam
+
+
+def _lines(path):
+    for line in Path(path).read_text().splitlines():
+        line = line.strip()
+        if line and not line.startswith("#"):
+            yield line
+
+
+# ---- text -----------------------------------------------------------------------------------------------------------------
+def read_cameras_text(path) -> dict:
+    cams = {}
+    for line in _lines(path):
+        tok = line.split()
+        cam = ColmapCamera(int(tok[0]), tok[1], int(tok[2]), int(tok[3]), np.array([float(v) for v in tok[4:]]))
+        cams[cam.id] = _check_model(cam)
+    return cams
+
+
+def read_images_text(path) -> dict:
+    imgs = {}
+    raw = [ln.strip() for ln in Path(path).read_text().splitlines() if not ln.strip().startswith("#")]
+    # two lines per image: the pose line and the (possibly empty) 2D point line
+    i = 0
+    while i < len(raw):
+        if not raw[i]:
+            i += 1
+            continue
+        tok = raw[i].split()
+        img = ColmapImage(int(tok[0]), np.array([float(v) for v in tok[1:5]]), np.array([float(v) for v in tok[5:8]]),
+                          int(tok[8]), " ".join(tok[9:]))
+        imgs[img.id] = img
+        i += 2
+    return imgs
+
+
+def read_points3D_text(path):
+    """(xyz [N,3] float64, rgb [N,3] uint8)"""
+    xyz, rgb = [], []
+    for line in _lines(path):
+        tok = line.split()
+        xyz.append([float(v) for v in tok[1:4]])
+        rgb.append([int(v) for v in tok[4:7]])
+    return np.array(xyz, dtype=np.float64).reshape(-1, 3), np.array(rgb, dtype=np.uint8).reshape(-1, 3)
+
+
+# ---- binary (little endian) -----------------------------------------------------------------------------------------------
+class _Reader:
+    def __init__(self, path):
+        self.data, self.off = Path(path).read_bytes(), 0
+
+    def read(self, fmt):
+        vals = struct.unpack_from("<" + fmt, self.data, self.off)
+        self.off += struct.calcsize("<" + fmt)
+        return vals
+
+    def cstring(self):
+        end = self.data.index(b"\x00", self.off)
+        s = self.data[self.off:end].decode("utf-8")
+        self.off = end + 1
+        return s
+
+
+def read_cameras_binary(path) -> dict:
+    r, cams = _Reader(path), {}
+    (n,) = r.read("Q")
+    for _ in range(n):
+        cam_id, model_id, w, h = r.read("iiQQ")
+        if model_id not in CAMERA_MODELS:
+            raise UnsupportedCameraModel(f"COLMAP camera {cam_id}: unknown model id {model_id}")
+        name, n_params = CAMERA_MODELS[model_id]
+        params = np.array(r.read("d" * n_params))
+        cams[cam_id] = _check_model(ColmapCamera(cam_id, name, int(w), int(h), params))
+    return cams
+
+
+def read_images_binary(path) -> dict:
+    r, imgs = _Reader(path), {}
+    (n,) = r.read("Q")
+    for _ in range(n):
+        vals = r.read("idddddddi")
+        name = r.cstring()
+        (n2d,) = r.read("Q")
+        r.off += n2d * 24                        # (x, y, point3D_id) per 2D point: not needed here
+        imgs[vals[0]] = ColmapImage(vals[0], np.array(vals[1:5]), np.array(vals[5:8]), vals[8], name)
+    return imgs
+
+
+def read_points3D_binary(path):
+    r = _Reader(path)
+    (n,) = r.read("Q")
+    xyz, rgb = np.empty((n, 3)), np.empty((n, 3), dtype=np.uint8)
+    for i in range(n):
+        vals = r.read("QdddBBBd")
+        xyz[i], rgb[i] = vals[1:4], vals[4:7]
+        (track,) = r.read("Q")
+        r.off += track * 8
+    return xyz, rgb
+
+
+# ---- writers (test fixtures, synthetic datasets) --------------------------------------------------------------------------
+_MODEL_IDS = {name: mid for mid, (name, _) in CAMERA_MODELS.items()}
+
+
+def write_colmap_model(sparse_dir, cameras, images, xyz, rgb, binary=True) -> None:
+    """Writes cameras / images / points3D (.bin or .txt).  cameras: {id: ColmapCamera}; images: {id: ColmapImage};
+    xyz [N,3], rgb [N,3] uint8.  2D points and tracks are written empty."""
+    d = Path(sparse_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    if binary:
+        b = struct.pack("<Q", len(cameras))
+        for c in cameras.values():
+            b += struct.pack("<iiQQ", c.id, _MODEL_IDS[c.model], c.width, c.height)
+            b += struct.pack("<" + "d" * len(c.params), *map(float, c.params))
+        (d / "cameras.bin").write_bytes(b)
+        b = struct.pack("<Q", len(images))
+        for im in images.values():
+            b += struct.pack("<idddddddi", im.id, *map(float, im.qvec), *map(float, im.tvec), im.camera_id)
+            b += im.name.encode("utf-8") + b"\x00" + struct.pack("<Q", 0)
+        (d / "images.bin").write_bytes(b)
+        b = struct.pack("<Q", len(xyz))
+        for i, (p, c) in enumerate(zip(np.asarray(xyz, dtype=np.float64), np.asarray(rgb, dtype=np.uint8))):
+            b += struct.pack("<QdddBBBdQ", i + 1, *map(float, p), *map(int, c), 0.0, 0)
+        (d / "points3D.bin").write_bytes(b)
+    else:
+        (d / "cameras.txt").write_text("# Camera list\n" + "".join(
+            f"{c.id} {c.model} {c.width} {c.height} {' '.join(repr(float(v)) for v in c.params)}\n"
+            for c in cameras.values()))
+        (d / "images.txt").write_text("# Image list\n" + "".join(
+            f"{im.id} {' '.join(repr(float(v)) for v in im.qvec)} {' '.join(repr(float(v)) for v in im.tvec)} "
+            f"{im.camera_id} {im.name}\n\n" for im in images.values()))
+        (d / "points3D.txt").write_text("# 3D point list\n" + "".join(
+            f"{i + 1} {' '.join(repr(float(v)) for v in p)} {' '.join(str(int(v)) for v in c)} 0.0\n"
+            for i, (p, c) in enumerate(zip(np.asarray(xyz, dtype=np.float64), np.asarray(rgb, dtype=np.uint8)))))
+
+
+# ---- the scene ------------------------------------------------------------------------------------------------------------
+def _sparse_dir(source_path) -> Path:
+    d = Path(source_path) / "sparse" / "0"
+    return d if d.is_dir() else Path(source_path) / "sparse"
+
+
+def read_model(source_path):
+    """(cameras, images) of ``source_path``'s sparse model, binary preferred."""
+    d = _sparse_dir(source_path)
+    if (d / "images.bin").exists() and (d / "cameras.bin").exists():
+        return read_cameras_binary(d / "cameras.bin"), read_images_binary(d / "images.bin")
+    if (d / "images.txt").exists() and (d / "cameras.txt").exists():
+        return read_cameras_text(d / "cameras.txt"), read_images_text(d / "images.txt")
+    raise FileNotFoundError(f"no COLMAP model (cameras / images .bin or .txt) under {d}")
+
+
+class PointCloud:
+    def __init__(self, points, colors):
+        self.points, self.colors = np.asarray(points, dtype=np.float32), np.asarray(colors, dtype=np.float32)
+
+
+def fetch_point_cloud(source_path) -> PointCloud:
+    """The initial point cloud, cached as ``sparse/0/points3D.ply`` (x, y, z, normals, red / green / blue in 0..255)."""
+    d = _sparse_dir(source_path)
+    ply = d / "points3D.ply"
+    if not ply.exists():
+        if (d / "points3D.bin").exists():
+            xyz, rgb = read_points3D_binary(d / "points3D.bin")
+        elif (d / "points3D.txt").exists():
+            xyz, rgb = read_points3D_text(d / "points3D.txt")
+        else:
+            raise FileNotFoundError(f"no points3D.bin / .txt / .ply under {d}")
+        store_ply(ply, xyz, rgb)
+    return read_point_cloud_ply(ply)
+
+
+def store_ply(path, xyz, rgb) -> None:
+    xyz = np.asarray(xyz, dtype=np.float64)
+    rgb = np.asarray(rgb)
+    write_ply_vertices(path, {"x": xyz[:, 0], "y": xyz[:, 1], "z": xyz[:, 2], "nx": np.zeros(len(xyz)),
+                              "ny": np.zeros(len(xyz)), "nz": np.zeros(len(xyz)), "red": rgb[:, 0],
+                              "green": rgb[:, 1], "blue": rgb[:, 2]})
+
+
+def read_point_cloud_ply(path) -> PointCloud:
+    v = read_ply_vertices(path)
+    pts = np.stack([v["x"], v["y"], v["z"]], axis=1)
+    cols = np.stack([v["red"], v["green"], v["blue"]], axis=1).astype(np.float32) / 255.0
+    return PointCloud(pts, cols)
+
+
+@dataclass
+class CameraInfo:
+    uid: int
+    R: np.ndarray
+    T: np.ndarray
+    FoVx: float
+    FoVy: float
+    image_path: str
+    image_name: str
+    width: int
+    height: int
+
+
+def camera_infos(source_path, images_dir="images") -> list:
+    """One CameraInfo per registered image, sorted by image name."""
+    cams, imgs = read_model(source_path)
+    out = []
+    for im in imgs.values():
+        cam = cams[im.camera_id]
+        fx, fy = cam.focal
+        out.append(CameraInfo(uid=im.id, R=np.transpose(qvec2rotmat(im.qvec)), T=np.asarray(im.tvec, dtype=np.float64),
+                              FoVx=focal2fov(fx, cam.width), FoVy=focal2fov(fy, cam.height),
+                              image_path=os.path.join(source_path, images_dir, im.name),
+                              image_name=os.path.splitext(os.path.basename(im.name))[0], width=cam.width,
+                              height=cam.height))
+    return sorted(out, key=lambda c: c.image_name)
+
+
+def split_train_test(infos, eval_split: bool):
+    if not eval_split:
+        return list(infos), []
+    return ([c for i, c in enumerate(infos) if i % LLFF_HOLD != 0], [c for i, c in enumerate(infos) if i % LLFF_HOLD == 0])
+
+
+def camera_extent(infos) -> float:
+    """1.1 x the largest distance of a camera centre from the mean centre (upstream getNerfppNorm's radius)."""
+    centres = np.stack([np.linalg.inv(getWorld2View2(c.R, c.T))[:3, 3] for c in infos])
+    return float(1.1 * np.linalg.norm(centres - centres.mean(0), axis=1).max())
+
+
+def _target_size(w, h, resolution, scale=1.0):
+    if resolution in (1, 2, 4, 8):
+        return round(w / (scale * resolution)), round(h / (scale * resolution))
+    if resolution == -1:
+        f = w / 1600 if w > 1600 else 1.0               # large images come down to 1600 pixels across
+    else:
+        f = w / resolution
+    f *= scale
+    return int(w / f), int(h / f)
+
+
+def load_camera(info: CameraInfo, resolution=-1, white_background=False, data_device="cuda"):
+    """Camera with its ground-truth image ([3,H,W] in 0..1, resized per ``resolution``; an alpha channel composites the
+    image over the training background: white with ``white_background``, else black)."""
+    import torch
+    from PIL import Image
+
+    from .cameras import Camera
+    with Image.open(info.image_path) as im:
+        im = im.convert("RGBA") if im.mode in ("RGBA", "LA", "P") else im.convert("RGB")
+        size = _target_size(im.width, im.height, resolution)
+        if size != (im.width, im.height):
+            im = im.resize(size, Image.BICUBIC)
+        a = np.asarray(im, dtype=np.float32) / 255.0
+    rgb = a[..., :3]
+    if a.shape[-1] == 4:
+        bg = 1.0 if white_background else 0.0
+        rgb = rgb * a[..., 3:4] + bg * (1.0 - a[..., 3:4])
+    image = torch.from_numpy(np.ascontiguousarray(rgb.transpose(2, 0, 1)))
+    return Camera(colmap_id=info.uid, R=info.R, T=info.T, FoVx=info.FoVx, FoVy=info.FoVy, image=image, gt_alpha_mask=None,
+                  image_name=info.image_name, uid=info.uid, data_device=data_device)

@@ -1,7 +1,8 @@
 """``GaussianModel`` for the render path: the parameter container PEGASUS composes scenes with
 (/root/reference/src/gs/gaussian_model.py).  Same attribute names, getters (activations), PLY layout,
-``merge_gaussians`` / ``mask_points`` and pose methods; training (optimizer, densification) is out of scope
-for this build and raises.
+``merge_gaussians`` / ``mask_points`` and pose methods, and the training half: optimizer set-up (FusedAdam, one
+pgr_adam_step launch per step), learning-rate schedule, densification statistics, clone / split / prune with the
+optimizer state kept in step, and capture / restore for checkpoints (reference :71-104,165-191,226-229,290-458).
 
 The pose methods run on the device: ``apply_transformation`` is one pgr_compose_object launch instead of the
 reference's GPU -> CPU -> scipy/e3nn -> GPU round trip (gaussian_model.py:499-546)."""
@@ -11,6 +12,7 @@ import copy
 
 import numpy as np
 import torch
+from torch import nn
 
 from . import compose, pose_queue
 from .ply_io import read_ply_vertices, write_ply_vertices
@@ -73,6 +75,8 @@ class GaussianModel:
         self._xyz = self._features_dc = self._features_rest = self._scaling = self._rotation = self._opacity = e
         self.max_radii2D = self.xyz_gradient_accum = self.denom = e
         self.optimizer = None
+        self.percent_dense = 0
+        self.spatial_lr_scale = 0
         self.scaling_activation, self.scaling_inverse_activation = torch.exp, torch.log
         self.opacity_activation, self.inverse_opacity_activation = torch.sigmoid, inverse_sigmoid
         self.rotation_activation = torch.nn.functional.normalize
@@ -389,8 +393,184 @@ class GaussianModel:
         self._opacity = torch.log(opac / (1 - opac))          # inverse_sigmoid
         self.max_radii2D = torch.zeros((pts.shape[0],), device=dev)
 
-    # ---- training loop: not part of this build (the differentiable rasterizer it would call is: pgr_backward)
-    def training_setup(self, *a, **k):
-        raise NotImplementedError("the training loop (optimizer, densification) is out of scope: SURVEY.md section 8f row 4")
+    # ---- training (reference :165-191,226-229,290-458): the optimizer holds the six row attributes as nn.Parameters;
+    # every densify / prune step rebuilds them and carries their Adam moments along (new rows start at zero moments)
+    _PARAM_NAMES = (("xyz", "_xyz"), ("f_dc", "_features_dc"), ("f_rest", "_features_rest"), ("opacity", "_opacity"),
+                    ("scaling", "_scaling"), ("rotation", "_rotation"))
 
-    densify_and_prune = training_setup
+    def _set_params(self, tensors: dict) -> None:
+        for name, attr in self._PARAM_NAMES:
+            if name in tensors:
+                setattr(self, attr, tensors[name])
+
+    def training_setup(self, training_args):
+        from .train_ops import FusedAdam, get_expon_lr_func
+        arg = lambda k, d: getattr(training_args, k, d)
+        self.percent_dense = arg("percent_dense", 0.01)
+        n = int(self.get_xyz.shape[0])
+        dev = self._xyz.device
+        self.xyz_gradient_accum = torch.zeros((n, 1), device=dev)
+        self.denom = torch.zeros((n, 1), device=dev)
+        if self.max_radii2D.shape != (n,):
+            self.max_radii2D = torch.zeros((n,), device=dev)
+        # the parameters get storage of their own: never a view into the row buffers of merge_gaussians / deepcopy (which a
+        # later append could write) and never shared with another model
+        for _, attr in self._PARAM_NAMES:
+            setattr(self, attr, nn.Parameter(getattr(self, attr).detach().clone().contiguous().requires_grad_(True)))
+        self.__dict__.pop("_rows", None)
+        lr_init = arg("position_lr_init", 0.00016)
+        feature_lr = arg("feature_lr", 0.0025)
+        lrs = {"xyz": lr_init * self.spatial_lr_scale, "f_dc": feature_lr, "f_rest": feature_lr / 20.0,
+               "opacity": arg("opacity_lr", 0.05), "scaling": arg("scaling_lr", 0.005), "rotation": arg("rotation_lr", 0.001)}
+        groups = [{"params": [getattr(self, attr)], "lr": lrs[name], "name": name} for name, attr in self._PARAM_NAMES]
+        self.optimizer = FusedAdam(groups, lr=0.0, eps=1e-15)
+        self.xyz_scheduler_args = get_expon_lr_func(lr_init=lr_init * self.spatial_lr_scale,
+                                                    lr_final=arg("position_lr_final", 0.0000016) * self.spatial_lr_scale,
+                                                    lr_delay_mult=arg("position_lr_delay_mult", 0.01),
+                                                    max_steps=arg("position_lr_max_steps", 30_000))
+
+    def update_learning_rate(self, iteration):
+        """Position learning rate of ``iteration`` (the other groups keep theirs); returns it."""
+        for group in self.optimizer.param_groups:
+            if group["name"] == "xyz":
+                lr = self.xyz_scheduler_args(iteration)
+                group["lr"] = lr
+                return lr
+
+    def capture(self):
+        return (self.active_sh_degree, self._xyz, self._features_dc, self._features_rest, self._scaling, self._rotation,
+                self._opacity, self.max_radii2D, self.xyz_gradient_accum, self.denom, self.optimizer.state_dict(),
+                self.spatial_lr_scale)
+
+    def restore(self, model_args, training_args):
+        (self.active_sh_degree, xyz, f_dc, f_rest, scaling, rotation, opacity, max_radii2D, xyz_gradient_accum, denom,
+         opt_dict, self.spatial_lr_scale) = model_args
+        self._xyz, self._features_dc, self._features_rest = xyz, f_dc, f_rest
+        self._scaling, self._rotation, self._opacity = scaling, rotation, opacity
+        self.max_radii2D = max_radii2D
+        self.training_setup(training_args)
+        self.xyz_gradient_accum = xyz_gradient_accum
+        self.denom = denom
+        self.optimizer.load_state_dict(opt_dict)
+
+    def replace_tensor_to_optimizer(self, tensor, name):
+        """Puts ``tensor`` in place of the parameter of group ``name``, with zeroed Adam moments; returns {name: param}."""
+        out = {}
+        for group in self.optimizer.param_groups:
+            if group["name"] != name:
+                continue
+            old = group["params"][0]
+            st = self.optimizer.state.pop(old, None)
+            new = nn.Parameter(tensor.detach().contiguous().requires_grad_(True))
+            group["params"][0] = new
+            if st is not None:
+                st["exp_avg"] = torch.zeros_like(new)
+                st["exp_avg_sq"] = torch.zeros_like(new)
+                self.optimizer.state[new] = st
+            out[name] = new
+        return out
+
+    def _rebuild_params(self, rows_of):
+        """Replaces every group's parameter p with nn.Parameter(rows_of(p, 0.0)) and its moments m with rows_of(m, 0.0):
+        the one place where densification edits the optimizer."""
+        out = {}
+        for group in self.optimizer.param_groups:
+            old = group["params"][0]
+            st = self.optimizer.state.pop(old, None)
+            new = nn.Parameter(rows_of(group["name"], old.detach()).contiguous().requires_grad_(True))
+            group["params"][0] = new
+            if st is not None:
+                st["exp_avg"] = rows_of(group["name"], st["exp_avg"], moment=True).contiguous()
+                st["exp_avg_sq"] = rows_of(group["name"], st["exp_avg_sq"], moment=True).contiguous()
+                self.optimizer.state[new] = st
+            out[group["name"]] = new
+        return out
+
+    def _prune_optimizer(self, mask):
+        return self._rebuild_params(lambda name, t, moment=False: t[mask])
+
+    def prune_points(self, mask):
+        """Drops the rows where ``mask`` is True from the parameters, their Adam moments and the statistics."""
+        valid = ~mask
+        self._set_params(self._prune_optimizer(valid))
+        self.xyz_gradient_accum = self.xyz_gradient_accum[valid]
+        self.denom = self.denom[valid]
+        self.max_radii2D = self.max_radii2D[valid]
+
+    def cat_tensors_to_optimizer(self, tensors_dict):
+        """Appends tensors_dict[name] to each group's parameter; the new rows start with zero Adam moments."""
+        def rows_of(name, t, moment=False):
+            ext = tensors_dict[name].detach()
+            return torch.cat((t, torch.zeros_like(ext) if moment else ext), dim=0)
+        return self._rebuild_params(rows_of)
+
+    def densification_postfix(self, new_xyz, new_features_dc, new_features_rest, new_opacities, new_scaling,
+                              new_rotation):
+        self._set_params(self.cat_tensors_to_optimizer({
+            "xyz": new_xyz, "f_dc": new_features_dc, "f_rest": new_features_rest, "opacity": new_opacities,
+            "scaling": new_scaling, "rotation": new_rotation}))
+        n, dev = int(self.get_xyz.shape[0]), self._xyz.device
+        self.xyz_gradient_accum = torch.zeros((n, 1), device=dev)
+        self.denom = torch.zeros((n, 1), device=dev)
+        self.max_radii2D = torch.zeros((n,), device=dev)
+
+    def densify_and_split(self, grads, grad_threshold, scene_extent, N=2):
+        """Gaussians with a large view-space gradient AND a large extent are replaced by N samples drawn from them, each
+        with its scale divided by 0.8 N."""
+        n_init = int(self.get_xyz.shape[0])
+        padded = torch.zeros((n_init,), device=self._xyz.device)
+        padded[:grads.shape[0]] = grads.squeeze()
+        scaling = self.get_scaling
+        selected = (padded >= grad_threshold) & (torch.max(scaling, dim=1).values > self.percent_dense * scene_extent)
+        stds = scaling[selected].repeat(N, 1)
+        samples = torch.normal(mean=torch.zeros((stds.shape[0], 3), device=stds.device), std=stds)
+        rots = build_rotation(self._rotation[selected]).repeat(N, 1, 1)
+        new_xyz = torch.bmm(rots, samples.unsqueeze(-1)).squeeze(-1) + self.get_xyz[selected].repeat(N, 1)
+        new_scaling = self.scaling_inverse_activation(scaling[selected].repeat(N, 1) / (0.8 * N))
+        self.densification_postfix(new_xyz, self._features_dc[selected].repeat(N, 1, 1),
+                                   self._features_rest[selected].repeat(N, 1, 1), self._opacity[selected].repeat(N, 1),
+                                   new_scaling, self._rotation[selected].repeat(N, 1))
+        prune = torch.cat((selected, torch.zeros(N * int(selected.sum()), device=selected.device, dtype=torch.bool)))
+        self.prune_points(prune)
+
+    def densify_and_clone(self, grads, grad_threshold, scene_extent):
+        """Gaussians with a large view-space gradient and a small extent get an identical copy."""
+        selected = (torch.norm(grads, dim=-1) >= grad_threshold) & \
+                   (torch.max(self.get_scaling, dim=1).values <= self.percent_dense * scene_extent)
+        self.densification_postfix(self._xyz[selected], self._features_dc[selected], self._features_rest[selected],
+                                   self._opacity[selected], self._scaling[selected], self._rotation[selected])
+
+    def densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size):
+        grads = self.xyz_gradient_accum / self.denom
+        grads[grads.isnan()] = 0.0
+        self.densify_and_clone(grads, max_grad, extent)
+        self.densify_and_split(grads, max_grad, extent)
+        self.prune_by(min_opacity, extent, max_screen_size)
+
+    def prune_by(self, min_opacity, extent, max_screen_size=None):
+        """Drops transparent Gaussians and, with ``max_screen_size``, those larger than it on screen (max_radii2D) or
+        larger than a tenth of the scene in the world.  (Called by densify_and_prune right after densification_postfix,
+        which zeroes max_radii2D, as upstream does: there only the world-size test can fire.)"""
+        prune = (self.get_opacity < min_opacity).squeeze(1)
+        if max_screen_size:
+            big_on_screen = self.max_radii2D > max_screen_size
+            big_in_world = self.get_scaling.max(dim=1).values > 0.1 * extent
+            prune = prune | big_on_screen | big_in_world
+        self.prune_points(prune)
+
+    def reset_opacity(self):
+        opacities_new = inverse_sigmoid(torch.min(self.get_opacity, torch.ones_like(self.get_opacity) * 0.01))
+        self._opacity = self.replace_tensor_to_optimizer(opacities_new, "opacity")["opacity"]
+
+    def add_densification_stats(self, viewspace_point_tensor, update_filter):
+        """Reference form (a visibility mask): accumulates the screen-space gradient norm and the visit count."""
+        g = viewspace_point_tensor.grad[update_filter, :2]
+        self.xyz_gradient_accum[update_filter] += torch.norm(g, dim=-1, keepdim=True)
+        self.denom[update_filter] += 1
+
+    def add_render_stats(self, viewspace_point_tensor, radii):
+        """add_densification_stats and the max_radii2D update of one render in one pgr_densify_stats launch (what the
+        trainer calls: every Gaussian with radii > 0 counts)."""
+        from .train_ops import densify_stats
+        densify_stats(viewspace_point_tensor.grad.contiguous(), radii.to(torch.int32).contiguous(),
+                      self.xyz_gradient_accum, self.denom, self.max_radii2D)

@@ -1,0 +1,261 @@
+"""``training(dataset, opt, pipe, testing_iterations, saving_iterations, checkpoint_iterations, checkpoint, debug_from)``:
+the 3DGS optimisation loop that PEGASUS's reconstruction scripts reach through train_gaussian_splatting_wrapper
+(/root/reference/src/gs/gs_training.py:7,46), on this package's kernels:
+
+    render (pgr_forward)  ->  ImageLoss (pgr_image_loss)  ->  backward (pgr_backward)  ->  densification statistics
+    (pgr_densify_stats)  ->  densify / prune / opacity reset on their schedule (torch)  ->  FusedAdam (pgr_adam_step)
+
+It reads a COLMAP dataset (pegasus_amd.colmap_io) and writes the model layout ``Scene(args, gaussians,
+load_iteration=-1)`` opens: cfg_args, cameras.json, input.ply, point_cloud/iteration_N/point_cloud.ply, chkpntN.pth.
+
+    python -m pegasus_amd.train -s <colmap dir> -m <output dir> [--iterations N] [--eval] ...
+"""
+from __future__ import annotations
+
+import json
+import math
+import os
+import random
+import shutil
+import sys
+from argparse import ArgumentParser, Namespace
+
+import torch
+
+from . import colmap_io
+from .gaussian_model import GaussianModel
+from .scene import camera_to_JSON, searchForMaxIteration
+
+# the 3DGS optimisation parameters and their defaults (compat/arguments OptimizationParams carries the same fields);
+# training() reads every one with getattr(opt, name, default), so an options object that lacks a field still works
+OPTIMIZATION_DEFAULTS = dict(
+    iterations=30_000, position_lr_init=0.00016, position_lr_final=0.0000016, position_lr_delay_mult=0.01,
+    position_lr_max_steps=30_000, feature_lr=0.0025, opacity_lr=0.05, scaling_lr=0.005, rotation_lr=0.001,
+    percent_dense=0.01, lambda_dssim=0.2, densification_interval=100, opacity_reset_interval=3000,
+    densify_from_iter=500, densify_until_iter=15_000, densify_grad_threshold=0.0002, random_background=False)
+MODEL_DEFAULTS = dict(sh_degree=3, source_path="", model_path="", images="images", resolution=-1,
+                      white_background=False, data_device="cuda", eval=False)
+MIN_OPACITY = 0.005                      # densify_and_prune's opacity floor
+SCREEN_SIZE_LIMIT = 20                   # pixels: the screen-radius prune once the first opacity reset has happened
+
+
+class _Options:
+    """getattr(source, name, default) for every field of ``defaults``."""
+
+    def __init__(self, source, defaults):
+        for k, v in defaults.items():
+            setattr(self, k, getattr(source, k, v) if source is not None else v)
+
+
+class TrainingScene:
+    """The dataset side of a training run: COLMAP cameras with their images, the train / test split, the camera extent,
+    and the model directory (input.ply, cameras.json, point_cloud/iteration_N)."""
+
+    def __init__(self, args, gaussians: GaussianModel, load_iteration=None, shuffle=True):
+        self.model_path = args.model_path
+        self.gaussians = gaussians
+        self.loaded_iter = None
+        if load_iteration:
+            pc = os.path.join(self.model_path, "point_cloud")
+            self.loaded_iter = searchForMaxIteration(pc) if load_iteration == -1 else load_iteration
+        infos = colmap_io.camera_infos(args.source_path, args.images)
+        train, test = colmap_io.split_train_test(infos, bool(args.eval))
+        self.cameras_extent = colmap_io.camera_extent(train if train else infos)
+        pcd = colmap_io.fetch_point_cloud(args.source_path)
+        if not self.loaded_iter:
+            os.makedirs(self.model_path, exist_ok=True)
+            shutil.copyfile(os.path.join(colmap_io._sparse_dir(args.source_path), "points3D.ply"),
+                            os.path.join(self.model_path, "input.ply"))
+            json_cams = [camera_to_JSON(i, _JsonCamera(c)) for i, c in enumerate(test + train)]
+            with open(os.path.join(self.model_path, "cameras.json"), "w") as f:
+                json.dump(json_cams, f)
+        if shuffle:
+            random.shuffle(train)
+            random.shuffle(test)
+        load = lambda c: colmap_io.load_camera(c, args.resolution, args.white_background, args.data_device)
+        self.train_cameras = [load(c) for c in train]
+        self.test_cameras = [load(c) for c in test]
+        if self.loaded_iter:
+            gaussians.load_ply(os.path.join(self.model_path, "point_cloud", f"iteration_{self.loaded_iter}",
+                                            "point_cloud.ply"))
+        else:
+            gaussians.create_from_pcd(pcd, self.cameras_extent)
+
+    def save(self, iteration):
+        self.gaussians.save_ply(os.path.join(self.model_path, "point_cloud", f"iteration_{iteration}", "point_cloud.ply"))
+
+    def getTrainCameras(self, scale=1.0):
+        return self.train_cameras
+
+    def getTestCameras(self, scale=1.0):
+        return self.test_cameras
+
+
+class _JsonCamera:
+    """A CameraInfo seen through the attributes scene.camera_to_JSON reads (the dataset's own image size)."""
+
+    def __init__(self, info):
+        self.R, self.T, self.FoVx, self.FoVy = info.R, info.T, info.FoVx, info.FoVy
+        self.image_name, self.image_width, self.image_height = info.image_name, info.width, info.height
+
+
+def psnr(img, gt) -> float:
+    mse = torch.mean((img.float() - gt.float()) ** 2).item()
+    return float("inf") if mse == 0.0 else 20.0 * math.log10(1.0 / math.sqrt(mse))
+
+
+def evaluate(cameras, gaussians, pipe, background) -> tuple:
+    """(mean L1, mean PSNR) of no-grad renders of ``cameras`` against their images (renders clamped to 0..1)."""
+    from .gaussian_renderer import render
+    from .train_ops import l1_loss
+    l1s, psnrs = [], []
+    with torch.no_grad():
+        for cam in cameras:
+            image = torch.clamp(render(cam, gaussians, pipe, background)["render"], 0.0, 1.0)
+            gt = torch.clamp(cam.original_image.to(image.device), 0.0, 1.0)
+            l1s.append(float(l1_loss(image, gt).item()))
+            psnrs.append(psnr(image, gt))
+    return (sum(l1s) / len(l1s), sum(psnrs) / len(psnrs)) if cameras else (float("nan"), float("nan"))
+
+
+def training_report(iteration, scene, gaussians, pipe, background, quiet=False) -> dict:
+    train = scene.getTrainCameras()
+    configs = {"test": scene.getTestCameras(), "train": [train[i % len(train)] for i in range(5, 30, 5)] if train else []}
+    out = {}
+    for name, cams in configs.items():
+        if cams:
+            l1, p = evaluate(cams, gaussians, pipe, background)
+            out[name] = {"l1": l1, "psnr": p}
+            if not quiet:
+                print(f"\n[ITER {iteration}] Evaluating {name}: L1 {l1} PSNR {p}")
+    return out
+
+
+def _gui_step(iteration, gaussians, pipe, background, opt, dataset):
+    """Serves the remote viewer while one is connected (upstream's loop; nothing happens without a connection)."""
+    from . import network_gui
+    from .gaussian_renderer import render
+    if network_gui.conn is None:
+        network_gui.try_connect()
+    while network_gui.conn is not None:
+        try:
+            cam, do_training, pipe.convert_SHs_python, pipe.compute_cov3D_python, keep_alive, scaling = network_gui.receive()
+            net_image_bytes = None
+            if cam is not None:
+                with torch.no_grad():
+                    img = render(cam, gaussians, pipe, background, scaling)["render"]
+                net_image_bytes = memoryview((torch.clamp(img, 0, 1.0) * 255).byte().permute(1, 2, 0).contiguous().cpu()
+                                             .numpy())
+            network_gui.send(net_image_bytes, dataset.source_path)
+            if do_training and ((iteration < int(opt.iterations)) or not keep_alive):
+                break
+        except Exception:
+            network_gui.conn = None
+
+
+def training(dataset, opt, pipe, testing_iterations, saving_iterations, checkpoint_iterations, checkpoint, debug_from,
+             quiet=False):
+    """Trains a Gaussian model on ``dataset.source_path`` (COLMAP) into ``dataset.model_path``.  Returns
+    {"reports": {iteration: {"test"/"train": {"l1", "psnr"}}}, "num_gaussians": N, "model": GaussianModel}."""
+    from . import network_gui
+    from .gaussian_renderer import render
+    from .train_ops import ImageLoss
+    opt = _Options(opt, OPTIMIZATION_DEFAULTS)
+    dataset = _Options(dataset, MODEL_DEFAULTS)
+    testing_iterations, saving_iterations = set(testing_iterations or ()), set(saving_iterations or ())
+    checkpoint_iterations = set(checkpoint_iterations or ())
+    os.makedirs(dataset.model_path, exist_ok=True)
+    with open(os.path.join(dataset.model_path, "cfg_args"), "w") as f:
+        f.write(str(Namespace(**vars(dataset))))
+    gaussians = GaussianModel(dataset.sh_degree, device=dataset.data_device)
+    scene = TrainingScene(dataset, gaussians)
+    gaussians.training_setup(opt)
+    first_iter = 0
+    if checkpoint:
+        model_params, first_iter = torch.load(checkpoint, weights_only=False)
+        gaussians.restore(model_params, opt)
+    dev = gaussians._xyz.device
+    background = torch.tensor([1, 1, 1] if dataset.white_background else [0, 0, 0], dtype=torch.float32, device=dev)
+    iterations = int(opt.iterations)
+    stack = None
+    reports = {}
+    for iteration in range(first_iter + 1, iterations + 1):
+        if network_gui.conn is not None or network_gui._listener is not None:
+            _gui_step(iteration, gaussians, pipe, background, opt, dataset)
+        gaussians.update_learning_rate(iteration)
+        if iteration % 1000 == 0:
+            gaussians.oneupSHdegree()
+        if not stack:
+            stack = scene.getTrainCameras().copy()
+        cam = stack.pop(random.randint(0, len(stack) - 1))
+        if iteration - 1 == debug_from:
+            pipe.debug = True
+        bg = torch.rand(3, device=dev) if opt.random_background else background
+        pkg = render(cam, gaussians, pipe, bg)
+        image, viewspace, radii = pkg["render"], pkg["viewspace_points"], pkg["radii"]
+        loss = ImageLoss.apply(image, cam.original_image, float(opt.lambda_dssim))
+        loss.backward()
+        with torch.no_grad():
+            if iteration in testing_iterations:
+                reports[iteration] = training_report(iteration, scene, gaussians, pipe, background, quiet)
+            if iteration in saving_iterations:
+                if not quiet:
+                    print(f"\n[ITER {iteration}] Saving Gaussians")
+                scene.save(iteration)
+            if iteration < opt.densify_until_iter:
+                gaussians.add_render_stats(viewspace, radii)
+                if iteration > opt.densify_from_iter and iteration % opt.densification_interval == 0:
+                    size_threshold = SCREEN_SIZE_LIMIT if iteration > opt.opacity_reset_interval else None
+                    gaussians.densify_and_prune(opt.densify_grad_threshold, MIN_OPACITY, scene.cameras_extent,
+                                                size_threshold)
+                if iteration % opt.opacity_reset_interval == 0 or (dataset.white_background and
+                                                                   iteration == opt.densify_from_iter):
+                    gaussians.reset_opacity()
+            if iteration < iterations:
+                gaussians.optimizer.step()
+                gaussians.optimizer.zero_grad(set_to_none=True)
+            if iteration in checkpoint_iterations:
+                if not quiet:
+                    print(f"\n[ITER {iteration}] Saving Checkpoint")
+                torch.save((gaussians.capture(), iteration),
+                           os.path.join(dataset.model_path, f"chkpnt{iteration}.pth"))
+    return {"reports": reports, "num_gaussians": int(gaussians.get_xyz.shape[0]), "model": gaussians}
+
+
+def _parser() -> ArgumentParser:
+    p = ArgumentParser(description="Train a 3D Gaussian splatting model on a COLMAP dataset")
+    short = {"source_path": "-s", "model_path": "-m", "images": "-i", "resolution": "-r", "white_background": "-w"}
+    for k, v in {**MODEL_DEFAULTS, **OPTIMIZATION_DEFAULTS,
+                 **dict(convert_SHs_python=False, compute_cov3D_python=False, debug=False)}.items():
+        flags = ["--" + k] + ([short[k]] if k in short else [])
+        if isinstance(v, bool):
+            p.add_argument(*flags, action="store_true", default=v)
+        else:
+            p.add_argument(*flags, type=type(v), default=v)
+    p.add_argument("--debug_from", type=int, default=-1)
+    p.add_argument("--test_iterations", nargs="+", type=int, default=[7_000, 30_000])
+    p.add_argument("--save_iterations", nargs="+", type=int, default=[7_000, 30_000])
+    p.add_argument("--checkpoint_iterations", nargs="+", type=int, default=[])
+    p.add_argument("--start_checkpoint", type=str, default=None)
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--quiet", action="store_true")
+    return p
+
+
+def main(argv=None) -> int:
+    args = _parser().parse_args(argv)
+    if not args.source_path or not args.model_path:
+        print("both -s <colmap dir> and -m <output dir> are required", file=sys.stderr)
+        return 2
+    args.save_iterations = list(args.save_iterations) + [args.iterations]
+    random.seed(args.seed)
+    torch.manual_seed(args.seed)
+    print("Optimizing " + args.model_path)
+    training(args, args, args, args.test_iterations, args.save_iterations, args.checkpoint_iterations,
+             args.start_checkpoint, args.debug_from, quiet=args.quiet)
+    print("\nTraining complete.")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,0 +1,176 @@
+"""Median ms per 3DGS training iteration at 800x800 on the C2 object (150 k Gaussians) and the C3 scene (2 M), split into
+forward / loss / backward / stats / optimizer with HIP events, plus two same-box A/B pairs:
+    loss:      pgr_image_loss (value + gradient, one call)  vs  the torch conv2d form of the same loss + its backward
+    optimizer: FusedAdam (one pgr_adam_step launch)         vs  torch.optim.Adam(foreach=True)
+Inputs are random (targets, gradients); every stage is warmed up first; each number is the median of 5 repeats.
+
+    python scripts/train_step_bench.py [--iters 20] [--warmup 5] [--repeats 5] [--scenes c2 c3] [--json out.json]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import statistics
+import sys
+from pathlib import Path
+from types import SimpleNamespace
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+STAGES = ("forward", "loss", "backward", "stats", "optimizer")
+
+
+def torch_loss(x, y, lam=0.2):
+    g = torch.tensor([math.exp(-((k - 5) ** 2) / (2 * 1.5 ** 2)) for k in range(11)], device=x.device)
+    g = g / g.sum()
+    w = (g[:, None] @ g[None, :]).expand(3, 1, 11, 11).contiguous()
+    blur = lambda t: F.conv2d(t[None], w, padding=5, groups=3)[0]
+    mx, my = blur(x), blur(y)
+    sxx, syy, sxy = blur(x * x) - mx * mx, blur(y * y) - my * my, blur(x * y) - mx * my
+    C1, C2 = 0.01 ** 2, 0.03 ** 2
+    s = ((2 * mx * my + C1) * (2 * sxy + C2)) / ((mx * mx + my * my + C1) * (sxx + syy + C2))
+    return (1 - lam) * (x - y).abs().mean() + lam * (1 - s.mean())
+
+
+def model_and_cameras(name, dev):
+    from pegasus_amd import scenes
+    from pegasus_amd.cameras import Camera
+    from pegasus_amd.gaussian_model import GaussianModel
+    from pegasus_amd.train import OPTIMIZATION_DEFAULTS, _Options
+    cloud, views = scenes.scene_c2() if name == "c2" else scenes.scene_c3(n_views=16)
+    m = GaussianModel.from_arrays(cloud.xyz, cloud.features_dc, cloud.features_rest, cloud.opacity, cloud.scaling,
+                                  cloud.rotation, sh_degree=3, device=dev)
+    m.spatial_lr_scale = 1.0
+    m.training_setup(_Options(None, OPTIMIZATION_DEFAULTS))
+    gen = torch.Generator().manual_seed(0)
+    cams = [Camera(colmap_id=i, R=v.R_c2w, T=v.t_w2c, FoVx=v.fovx, FoVy=v.fovy,
+                   image=torch.rand((3, v.height, v.width), generator=gen), gt_alpha_mask=None, image_name=str(i), uid=i,
+                   data_device=str(dev)) for i, v in enumerate(views[:8])]
+    return m, cams
+
+
+def train_steps(m, cams, iters, dev):
+    """Per-stage event times (ms) of ``iters`` iterations, summed per stage."""
+    from pegasus_amd.gaussian_renderer import render
+    from pegasus_amd.train_ops import ImageLoss
+    pipe = SimpleNamespace(convert_SHs_python=False, compute_cov3D_python=False, debug=False)
+    bg = torch.zeros(3, device=dev)
+    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(len(STAGES) + 1)] for _ in range(iters)]
+    for i in range(iters):
+        cam = cams[i % len(cams)]
+        e = ev[i]
+        e[0].record()
+        pkg = render(cam, m, pipe, bg)
+        e[1].record()
+        loss = ImageLoss.apply(pkg["render"], cam.original_image, 0.2)
+        e[2].record()
+        loss.backward()
+        e[3].record()
+        with torch.no_grad():
+            m.add_render_stats(pkg["viewspace_points"], pkg["radii"])
+            e[4].record()
+            m.optimizer.step()
+            m.optimizer.zero_grad(set_to_none=True)
+        e[5].record()
+    torch.cuda.synchronize()
+    per = {s: sum(e[k].elapsed_time(e[k + 1]) for e in ev) / iters for k, s in enumerate(STAGES)}
+    per["total"] = sum(e[0].elapsed_time(e[-1]) for e in ev) / iters
+    return per
+
+
+def time_loop(fn, iters):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def loss_ab(dev, iters, warmup, repeats):
+    from pegasus_amd.train_ops import ImageLoss
+    gen = torch.Generator().manual_seed(1)
+    x0 = torch.rand((3, 800, 800), generator=gen).to(dev)
+    y = torch.rand((3, 800, 800), generator=gen).to(dev)
+
+    def ours():
+        x = x0.clone().requires_grad_(True)
+        ImageLoss.apply(x, y, 0.2).backward()
+
+    def theirs():
+        x = x0.clone().requires_grad_(True)
+        torch_loss(x, y).backward()
+    out = {}
+    for name, fn in (("pgr_image_loss", ours), ("torch_conv2d", theirs)):
+        time_loop(fn, warmup)
+    res = {"pgr_image_loss": [], "torch_conv2d": []}
+    for _ in range(repeats):                                 # alternate the two in every repeat
+        for name, fn in (("pgr_image_loss", ours), ("torch_conv2d", theirs)):
+            res[name].append(time_loop(fn, iters))
+    for k, v in res.items():
+        out[k] = statistics.median(v)
+    return out
+
+
+def adam_ab(m, dev, iters, warmup, repeats):
+    from pegasus_amd.train_ops import FusedAdam
+    gen = torch.Generator().manual_seed(2)
+    shapes = [t.shape for _, t in ((n, getattr(m, a)) for n, a in m._PARAM_NAMES)]
+    lrs = [g["lr"] for g in m.optimizer.param_groups]
+
+    def make(cls, **kw):
+        ps = [torch.nn.Parameter(torch.randn(s, generator=gen).to(dev)) for s in shapes]
+        for p in ps:
+            p.grad = torch.randn(p.shape, generator=gen).to(dev)
+        return cls([{"params": [p], "lr": lr} for p, lr in zip(ps, lrs)], lr=0.0, eps=1e-15, **kw)
+    fused, ref = make(FusedAdam), make(torch.optim.Adam, foreach=True)
+    for o in (fused, ref):
+        time_loop(o.step, warmup)
+    res = {"FusedAdam": [], "torch_Adam_foreach": []}
+    for _ in range(repeats):
+        for name, o in (("FusedAdam", fused), ("torch_Adam_foreach", ref)):
+            res[name].append(time_loop(o.step, iters))
+    out = {k: statistics.median(v) for k, v in res.items()}
+    out["floats"] = sum(math.prod(s) for s in shapes)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--scenes", nargs="+", default=["c2", "c3"])
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("train_step_bench.py needs a HIP device (no CPU timing)")
+    dev = torch.device("cuda:0")
+    report = {"device": torch.cuda.get_device_name(0), "iters": a.iters, "repeats": a.repeats, "size": "800x800"}
+    report["loss_ab_ms"] = loss_ab(dev, a.iters, a.warmup, a.repeats)
+    print("loss A/B (value + gradient, 800x800):", json.dumps(report["loss_ab_ms"]), flush=True)
+    for name in a.scenes:
+        m, cams = model_and_cameras(name, dev)
+        train_steps(m, cams, a.warmup, dev)
+        reps = [train_steps(m, cams, a.iters, dev) for _ in range(a.repeats)]
+        med = {k: statistics.median(r[k] for r in reps) for k in reps[0]}
+        report[name] = {"gaussians": int(m.get_xyz.shape[0]), "ms_per_iter": med,
+                        "adam_ab_ms": adam_ab(m, dev, a.iters, a.warmup, a.repeats)}
+        print(name, json.dumps(report[name]), flush=True)
+        del m, cams
+        torch.cuda.empty_cache()
+    line = json.dumps(report)
+    print(line)
+    if a.json:
+        Path(a.json).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.json).write_text(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
