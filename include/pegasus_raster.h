@@ -379,7 +379,7 @@ size_t pgr_knn_workspace_bytes(int32_t n);
 int32_t pgr_knn_mean_dist2(int32_t n, const float *xyz, float *out, void *workspace, size_t workspace_bytes,
                            void *stream);
 
-/* Gradients returned by pgr_backward (device pointers, any may be NULL = not wanted). */
+/* Gradients returned by pgr_backward / pgr_backward_batch (device pointers, any may be NULL = not wanted). */
 typedef struct PgrGradOutputs {
     float *means2d;              /* [n,3] screen-space mean, NDC-scaled (what viewspace_points.grad receives) */
     float *means3d;              /* [n,3] */
@@ -399,6 +399,30 @@ int32_t pgr_backward(const PgrScene *scene, const PgrCamera *camera, const float
                      const float *grad_depth, const float *final_T, const uint32_t *n_contrib,
                      const int32_t *radii, void *workspace, size_t workspace_bytes, int64_t max_instances,
                      const PgrGradOutputs *grads, float *grad_rows, void *stream);
+
+/* Backward of a pgr_forward_batch call: the gradients of a loss over all n_views images at once.  `workspace` must be exactly
+ * as that call left it (same n, image size, max_instances_per_view and n_views); `cameras` are the forward's (only the image
+ * size is read: the packed cameras live in the workspace).  `views` is a HOST array of n_views entries, one per view.
+ * Every gradient in `grads` is the SUM over the views, except means2d, which is [n_views, n, 3] view-major: each view's own
+ * screen-space gradient (densification gathers its statistics per view).  Two launches do the work: the compositor backward
+ * of every (view, tile) list in the forward's interleaved work order, and one thread per Gaussian looping over the views in
+ * order (cov3D -> scale / rotation once, on the summed cov3D gradient; no atomics across views).
+ * `scratch`: device memory of pgr_backward_batch_scratch_bytes(n, n_views) bytes -- per-view accumulator rows of 48 bytes
+ * per Gaussian (48 n n_views: 768 MB for 8 views of 2 M Gaussians) and a small table.
+ * PGR_ERR_INVALID_ARGUMENT (before anything is enqueued): shs_rest, NULL cameras / views / grads, n_views <= 0, mixed image
+ * sizes, a view without grad_color / final_T / n_contrib (or radii, n > 0), scratch NULL or smaller than required.  Posed,
+ * semantic and layered batches have no backward. */
+typedef struct PgrBackwardView {
+    const float *grad_color;     /* [3,H,W] required */
+    const float *grad_depth;     /* [1,H,W] or NULL */
+    const float *final_T;        /* [H,W]   the forward's */
+    const uint32_t *n_contrib;   /* [H,W]   the forward's */
+    const int32_t *radii;        /* [n]     the forward's (required) */
+} PgrBackwardView;
+size_t pgr_backward_batch_scratch_bytes(int32_t n, int32_t n_views);
+int32_t pgr_backward_batch(const PgrScene *scene, int32_t n_views, const PgrCamera *cameras, const PgrBackwardView *views,
+                           void *workspace, size_t workspace_bytes, int64_t max_instances_per_view,
+                           const PgrGradOutputs *grads, void *scratch, size_t scratch_bytes, void *stream);
 
 /* present[i] = 1 iff Gaussian i passes the near-plane test of `viewmatrix` (device [16]). */
 int32_t pgr_mark_visible(int32_t n, const float *means3d, const float *viewmatrix, uint8_t *present,

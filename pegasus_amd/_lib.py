@@ -92,6 +92,10 @@ class PgrGradOutputs(C.Structure):
                                           "rotations")]
 
 
+class PgrBackwardView(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("grad_color", "grad_depth", "final_T", "n_contrib", "radii")]
+
+
 class PgrWorkspaceView(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("splats", "rects", "gauss_sorted", "ranges", "num_instances")]
 
@@ -149,6 +153,10 @@ SYMBOLS = {
     "pgr_backward": (C.c_int32, [C.POINTER(PgrScene), C.POINTER(PgrCamera), C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.POINTER(PgrGradOutputs),
                                  C.c_void_p, C.c_void_p]),
+    "pgr_backward_batch_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "pgr_backward_batch": (C.c_int32, [C.POINTER(PgrScene), C.c_int32, C.POINTER(PgrCamera), C.POINTER(PgrBackwardView),
+                                       C.c_void_p, C.c_size_t, C.c_int64, C.POINTER(PgrGradOutputs), C.c_void_p,
+                                       C.c_size_t, C.c_void_p]),
     "pgr_compose_object": (C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                        C.POINTER(PgrObjectPose), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                        C.c_void_p]),

@@ -8,6 +8,10 @@
 //       atomic on the Gaussian's row.
 //   preprocess_backward_kernel      one thread per Gaussian: conic -> cov2D -> (cov3D, view-space mean) ->
 //       scale / rotation; projection; SH -> coefficients and view direction.
+//   composite_backward_batch_kernel, preprocess_backward_batch_kernel  the backward of a pgr_forward_batch call
+//       (pgr_backward_batch): the same block walk for every (view, tile) item of the forward's interleaved work order in
+//       one launch, into per-view rows [n_views, n, GRAD_ROW]; then one thread per Gaussian over the views in order,
+//       summing in registers, cov3D -> scale / rotation once.
 #pragma once
 #include <type_traits>
 #include "composite.hip.h"
@@ -31,13 +35,12 @@ constexpr int GRAD_ROW = 12;
 // of colour and depth -- is a prefix product and four prefix sums over the four lanes of a quad (two quad_perm steps
 // each); everything else is per entry.  The ten partials are summed over the block's 16 pixels (two row shifts, then a
 // 640-byte LDS transpose that also lines the 4 x 10 totals up for ONE atomic instruction).
-__global__ __launch_bounds__(WAVE) void composite_backward_block_kernel(
+// The walk of one block (`item` = 4 * tile + quarter of the view, block = blockIdx.x & 3 inside the quarter); the single-view
+// and the batch kernel below differ only in where the view's lists, camera and images come from.
+__device__ __forceinline__ void composite_backward_block(
     const CameraDev* __restrict__ camp, const uint2* __restrict__ ranges, const uint32_t* __restrict__ gauss_sorted,
     const float4* __restrict__ splats, const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
-    const float* __restrict__ g_color, const float* __restrict__ g_depth, float* __restrict__ g_rows,
-    const uint32_t* __restrict__ work_order) {
-    const uint32_t item = work_order ? work_order[blockIdx.x >> 2] : (blockIdx.x >> 2);
-    if (item == INVALID_ITEM) return;
+    const float* __restrict__ g_color, const float* __restrict__ g_depth, float* __restrict__ g_rows, uint32_t item) {
     const CameraDev& cam = *camp;
     const int W = cam.width, H = cam.height;
     const int tile = (int)(item >> 2), quarter = (int)(item & 3), sub = (int)(blockIdx.x & 3);
@@ -210,6 +213,59 @@ __global__ __launch_bounds__(WAVE) void composite_backward_block_kernel(
     }
 }
 
+__global__ __launch_bounds__(WAVE) void composite_backward_block_kernel(
+    const CameraDev* __restrict__ camp, const uint2* __restrict__ ranges, const uint32_t* __restrict__ gauss_sorted,
+    const float4* __restrict__ splats, const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
+    const float* __restrict__ g_color, const float* __restrict__ g_depth, float* __restrict__ g_rows,
+    const uint32_t* __restrict__ work_order) {
+    const uint32_t item = work_order ? work_order[blockIdx.x >> 2] : (blockIdx.x >> 2);
+    if (item == INVALID_ITEM) return;
+    composite_backward_block(camp, ranges, gauss_sorted, splats, final_T, n_contrib, g_color, g_depth, g_rows, item);
+}
+
+// ---- batch backward (pgr_backward_batch): the backward of a pgr_forward_batch call -------------------------------------
+// One entry per view, in device memory (written by backward_table_kernel from the launch arguments), read through the
+// scalar cache: the forward's lists and packed camera in the workspace, the view's image gradients and forward outputs, and
+// the view's own rows of the [n_views, n, GRAD_ROW] accumulator (screen-space partials: they cannot be summed over views).
+struct alignas(16) BwdViewDev {
+    const CameraDev* cam;
+    const uint2* ranges;
+    const uint32_t* gauss_sorted;
+    const float4* splats;
+    const uint32_t* counters;    // [1] != 0: the forward overflowed this view (it was not composited; nothing to walk)
+    const float* g_color;        // [3,H,W]
+    const float* g_depth;        // [H,W] or NULL
+    const float* final_T;        // [H,W]
+    const uint32_t* n_contrib;   // [H,W]
+    const int32_t* radii;        // [n]
+    float* rows;                 // [n, GRAD_ROW]
+};
+constexpr int BWD_TABLE_CHUNK = 16;            // views per table launch (kernel arguments: 16 x 96 bytes)
+struct BwdTableChunk { BwdViewDev v[BWD_TABLE_CHUNK]; };
+__global__ __launch_bounds__(64) void backward_table_kernel(BwdTableChunk chunk, int count, BwdViewDev* __restrict__ out) {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(chunk.v);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(out);
+    const int words = count * (int)(sizeof(BwdViewDev) / 4);
+    for (int k = threadIdx.x; k < words; k += blockDim.x) dst[k] = src[k];
+}
+
+// The compositor backward of EVERY view in one launch: the forward's interleaved work order (item = view * items_per_view +
+// 4 * tile + quarter, as composite_quarter_kernel reads it), so no view waits on its own slowest tile -- the single-view
+// launch lasts as long as its longest wave.
+__global__ __launch_bounds__(WAVE) void composite_backward_batch_kernel(const BwdViewDev* __restrict__ views,
+                                                                        uint32_t n_views, uint32_t items_per_view,
+                                                                        const uint32_t* __restrict__ work_order) {
+    uint32_t item = work_order[blockIdx.x >> 2];
+    if (item == INVALID_ITEM) return;
+    const uint32_t view = item / items_per_view;
+    if (view >= n_views) return;
+    item -= view * items_per_view;
+    const BwdViewDev& bv = views[view];
+    if (bv.counters[1]) return;
+    composite_backward_block(bv.cam, bv.ranges, bv.gauss_sorted, bv.splats, bv.final_T, bv.n_contrib, bv.g_color, bv.g_depth,
+                             bv.rows, item);
+}
+
 struct GradOut {
     float* means2d;    // [n,3] or NULL
     float* means3d;    // [n,3] or NULL
@@ -260,6 +316,131 @@ __device__ __forceinline__ void sh_basis_grad(float x, float y, float z, float b
     }
 }
 
+// 3D covariance of Gaussian i as the forward formed it (recomputed from scale / rotation, or the precomputed one)
+__device__ __forceinline__ void load_cov3d(const PgrScene& sc, int i, float cov[6]) {
+    if (sc.cov3d_precomp) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) cov[k] = sc.cov3d_precomp[6 * (size_t)i + k];
+    } else {
+        const float4 q = reinterpret_cast<const float4*>(sc.rotations)[i];
+        cov3d_from_scale_rot(sc.scales[3 * i], sc.scales[3 * i + 1], sc.scales[3 * i + 2], sc.scale_modifier, q, cov);
+    }
+}
+
+// One view's geometry chain for a Gaussian the view rendered: the compositor's row -> NDC-scaled screen gradient (gndc, set),
+// conic -> cov2D -> the six cov3D partials (gS, set) and the view-space / projected position -> mean gradient (ADDED to gp).
+__device__ __forceinline__ void view_geometry_backward(const CameraDev& cam, const float* row, const float p[3],
+                                                       const float cov[6], float gp[3], float gS[6], float gndc[2]) {
+    const float* vm = cam.view;
+    const float* pm = cam.proj;
+    // ---- screen position
+    gndc[0] = row[0] * 0.5f * (float)cam.width;
+    gndc[1] = row[1] * 0.5f * (float)cam.height;
+    {
+        const float hx = pm[0] * p[0] + pm[4] * p[1] + pm[8] * p[2] + pm[12];
+        const float hy = pm[1] * p[0] + pm[5] * p[1] + pm[9] * p[2] + pm[13];
+        const float hw = pm[3] * p[0] + pm[7] * p[1] + pm[11] * p[2] + pm[15];
+        const float mw = 1.0f / (hw + 0.0000001f);
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            gp[k] += gndc[0] * (pm[4 * k + 0] * mw - hx * mw * mw * pm[4 * k + 3]) +
+                     gndc[1] * (pm[4 * k + 1] * mw - hy * mw * mw * pm[4 * k + 3]);
+    }
+    // ---- view-space position
+    float t[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) t[r] = vm[r] * p[0] + vm[4 + r] * p[1] + vm[8 + r] * p[2] + vm[12 + r];
+    float gt[3] = {0.f, 0.f, row[9]};
+
+    // ---- 3D covariance
+    const float S3[3][3] = {{cov[0], cov[1], cov[2]}, {cov[1], cov[3], cov[4]}, {cov[2], cov[4], cov[5]}};
+    const float fx = cam.focal_x, fy = cam.focal_y;
+    const float limx = 1.3f * cam.tanfovx, limy = 1.3f * cam.tanfovy;
+    const float txtz = t[0] / t[2], tytz = t[1] / t[2];
+    const float cx = fminf(limx, fmaxf(-limx, txtz)) * t[2], cy = fminf(limy, fmaxf(-limy, tytz)) * t[2];
+    const float xmul = (txtz < -limx || txtz > limx) ? 0.f : 1.f, ymul = (tytz < -limy || tytz > limy) ? 0.f : 1.f;
+    const float j00 = fx / t[2], j02 = -fx * cx / (t[2] * t[2]), j11 = fy / t[2], j12 = -fy * cy / (t[2] * t[2]);
+    float T0[3], T1[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        T0[k] = j00 * vm[4 * k + 0] + j02 * vm[4 * k + 2];
+        T1[k] = j11 * vm[4 * k + 1] + j12 * vm[4 * k + 2];
+    }
+    float a = 0.f, b = 0.f, c = 0.f;
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+            a += T0[r] * S3[r][s] * T0[s];
+            b += T0[r] * S3[r][s] * T1[s];
+            c += T1[r] * S3[r][s] * T1[s];
+        }
+    a += LOWPASS; c += LOWPASS;
+    const float det = a * c - b * b, d2 = 1.0f / (det * det);
+    const float gA = row[2], gB = row[3], gCc = row[4];
+    const float ga = d2 * (-c * c * gA + b * c * gB - b * b * gCc);
+    const float gb = d2 * (2 * b * c * gA - (det + 2 * b * b) * gB + 2 * a * b * gCc);
+    const float gc = d2 * (-b * b * gA + a * b * gB - a * a * gCc);
+    gS[0] = ga * T0[0] * T0[0] + gb * T0[0] * T1[0] + gc * T1[0] * T1[0];
+    gS[3] = ga * T0[1] * T0[1] + gb * T0[1] * T1[1] + gc * T1[1] * T1[1];
+    gS[5] = ga * T0[2] * T0[2] + gb * T0[2] * T1[2] + gc * T1[2] * T1[2];
+    gS[1] = 2 * ga * T0[0] * T0[1] + gb * (T0[0] * T1[1] + T0[1] * T1[0]) + 2 * gc * T1[0] * T1[1];
+    gS[2] = 2 * ga * T0[0] * T0[2] + gb * (T0[0] * T1[2] + T0[2] * T1[0]) + 2 * gc * T1[0] * T1[2];
+    gS[4] = 2 * ga * T0[1] * T0[2] + gb * (T0[1] * T1[2] + T0[2] * T1[1]) + 2 * gc * T1[1] * T1[2];
+    float gj00 = 0.f, gj02 = 0.f, gj11 = 0.f, gj12 = 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+        for (int s = 0; s < 3; ++s) { s0 += S3[k][s] * T0[s]; s1 += S3[k][s] * T1[s]; }
+        const float gT0 = 2 * ga * s0 + gb * s1, gT1 = 2 * gc * s1 + gb * s0;
+        gj00 += gT0 * vm[4 * k + 0]; gj02 += gT0 * vm[4 * k + 2];
+        gj11 += gT1 * vm[4 * k + 1]; gj12 += gT1 * vm[4 * k + 2];
+    }
+    const float tz2 = 1.0f / (t[2] * t[2]), tz3 = tz2 / t[2];
+    gt[0] += xmul * -fx * tz2 * gj02;
+    gt[1] += ymul * -fy * tz2 * gj12;
+    gt[2] += -fx * tz2 * gj00 - fy * tz2 * gj11 + 2 * fx * cx * tz3 * gj02 + 2 * fy * cy * tz3 * gj12;
+    if (xmul == 0.f) gt[2] += -fx * tz2 * gj02 * (cx / t[2]);
+    if (ymul == 0.f) gt[2] += -fy * tz2 * gj12 * (cy / t[2]);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) gp[k] += vm[4 * k + 0] * gt[0] + vm[4 * k + 1] * gt[1] + vm[4 * k + 2] * gt[2];
+}
+
+// cov3D = (R S)(R S)^T -> scale and rotation (gS: the six partials of cov3D; linear in them)
+__device__ __forceinline__ void scale_rot_backward(const PgrScene& sc, int i, const float gS[6], float gs[3], float gq[4]) {
+    const float4 q4 = reinterpret_cast<const float4*>(sc.rotations)[i];
+    const float r = q4.x, x = q4.y, y = q4.z, z = q4.w;
+    const float R[3][3] = {{1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y)},
+                           {2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x)},
+                           {2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)}};
+    const float s[3] = {sc.scale_modifier * sc.scales[3 * i], sc.scale_modifier * sc.scales[3 * i + 1],
+                        sc.scale_modifier * sc.scales[3 * i + 2]};
+    const float Gf[3][3] = {{gS[0], 0.5f * gS[1], 0.5f * gS[2]}, {0.5f * gS[1], gS[3], 0.5f * gS[4]},
+                            {0.5f * gS[2], 0.5f * gS[4], gS[5]}};
+    float gR[3][3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        float accs = 0.f;
+#pragma unroll
+        for (int a_ = 0; a_ < 3; ++a_) {
+            float gM = 0.f;
+#pragma unroll
+            for (int m = 0; m < 3; ++m) gM += 2 * Gf[a_][m] * R[m][k] * s[k];
+            accs += gM * R[a_][k];
+            gR[a_][k] = gM * s[k];
+        }
+        gs[k] = accs * sc.scale_modifier;
+    }
+    gq[0] = 2 * (-z * gR[0][1] + y * gR[0][2] + z * gR[1][0] - x * gR[1][2] - y * gR[2][0] + x * gR[2][1]);
+    gq[1] = 2 * (y * gR[0][1] + z * gR[0][2] + y * gR[1][0] - 2 * x * gR[1][1] - r * gR[1][2] + z * gR[2][0] +
+                 r * gR[2][1] - 2 * x * gR[2][2]);
+    gq[2] = 2 * (-2 * y * gR[0][0] + x * gR[0][1] + r * gR[0][2] + x * gR[1][0] + z * gR[1][2] - r * gR[2][0] +
+                 z * gR[2][1] - 2 * y * gR[2][2]);
+    gq[3] = 2 * (-2 * z * gR[0][0] - r * gR[0][1] + x * gR[0][2] + r * gR[1][0] - 2 * z * gR[1][1] + y * gR[1][2] +
+                 x * gR[2][0] + y * gR[2][1]);
+}
+
 template <int DEG>
 __global__ __launch_bounds__(256) void preprocess_backward_kernel(PgrScene sc, const CameraDev* __restrict__ camp,
                                                                   const int32_t* __restrict__ radii,
@@ -278,92 +459,13 @@ __global__ __launch_bounds__(256) void preprocess_backward_kernel(PgrScene sc, c
     float gcol[3] = {0.f, 0.f, 0.f};
     float gop = 0.f;
     const float p[3] = {sc.means3d[3 * i], sc.means3d[3 * i + 1], sc.means3d[3 * i + 2]};
-    const float* vm = cam.view;
-    const float* pm = cam.proj;
 
     if (live) {
         gop = row[5];
         gcol[0] = row[6]; gcol[1] = row[7]; gcol[2] = row[8];
-        // ---- screen position
-        gndc[0] = row[0] * 0.5f * (float)cam.width;
-        gndc[1] = row[1] * 0.5f * (float)cam.height;
-        {
-            const float hx = pm[0] * p[0] + pm[4] * p[1] + pm[8] * p[2] + pm[12];
-            const float hy = pm[1] * p[0] + pm[5] * p[1] + pm[9] * p[2] + pm[13];
-            const float hw = pm[3] * p[0] + pm[7] * p[1] + pm[11] * p[2] + pm[15];
-            const float mw = 1.0f / (hw + 0.0000001f);
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                gp[k] += gndc[0] * (pm[4 * k + 0] * mw - hx * mw * mw * pm[4 * k + 3]) +
-                         gndc[1] * (pm[4 * k + 1] * mw - hy * mw * mw * pm[4 * k + 3]);
-        }
-        // ---- view-space position
-        float t[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) t[r] = vm[r] * p[0] + vm[4 + r] * p[1] + vm[8 + r] * p[2] + vm[12 + r];
-        float gt[3] = {0.f, 0.f, row[9]};
-
-        // ---- 3D covariance (recomputed)
         float cov[6];
-        if (sc.cov3d_precomp) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) cov[k] = sc.cov3d_precomp[6 * (size_t)i + k];
-        } else {
-            const float4 q = reinterpret_cast<const float4*>(sc.rotations)[i];
-            cov3d_from_scale_rot(sc.scales[3 * i], sc.scales[3 * i + 1], sc.scales[3 * i + 2], sc.scale_modifier, q, cov);
-        }
-        const float S3[3][3] = {{cov[0], cov[1], cov[2]}, {cov[1], cov[3], cov[4]}, {cov[2], cov[4], cov[5]}};
-        const float fx = cam.focal_x, fy = cam.focal_y;
-        const float limx = 1.3f * cam.tanfovx, limy = 1.3f * cam.tanfovy;
-        const float txtz = t[0] / t[2], tytz = t[1] / t[2];
-        const float cx = fminf(limx, fmaxf(-limx, txtz)) * t[2], cy = fminf(limy, fmaxf(-limy, tytz)) * t[2];
-        const float xmul = (txtz < -limx || txtz > limx) ? 0.f : 1.f, ymul = (tytz < -limy || tytz > limy) ? 0.f : 1.f;
-        const float j00 = fx / t[2], j02 = -fx * cx / (t[2] * t[2]), j11 = fy / t[2], j12 = -fy * cy / (t[2] * t[2]);
-        float T0[3], T1[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            T0[k] = j00 * vm[4 * k + 0] + j02 * vm[4 * k + 2];
-            T1[k] = j11 * vm[4 * k + 1] + j12 * vm[4 * k + 2];
-        }
-        float a = 0.f, b = 0.f, c = 0.f;
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int s = 0; s < 3; ++s) {
-                a += T0[r] * S3[r][s] * T0[s];
-                b += T0[r] * S3[r][s] * T1[s];
-                c += T1[r] * S3[r][s] * T1[s];
-            }
-        a += LOWPASS; c += LOWPASS;
-        const float det = a * c - b * b, d2 = 1.0f / (det * det);
-        const float gA = row[2], gB = row[3], gCc = row[4];
-        const float ga = d2 * (-c * c * gA + b * c * gB - b * b * gCc);
-        const float gb = d2 * (2 * b * c * gA - (det + 2 * b * b) * gB + 2 * a * b * gCc);
-        const float gc = d2 * (-b * b * gA + a * b * gB - a * a * gCc);
-        gS[0] = ga * T0[0] * T0[0] + gb * T0[0] * T1[0] + gc * T1[0] * T1[0];
-        gS[3] = ga * T0[1] * T0[1] + gb * T0[1] * T1[1] + gc * T1[1] * T1[1];
-        gS[5] = ga * T0[2] * T0[2] + gb * T0[2] * T1[2] + gc * T1[2] * T1[2];
-        gS[1] = 2 * ga * T0[0] * T0[1] + gb * (T0[0] * T1[1] + T0[1] * T1[0]) + 2 * gc * T1[0] * T1[1];
-        gS[2] = 2 * ga * T0[0] * T0[2] + gb * (T0[0] * T1[2] + T0[2] * T1[0]) + 2 * gc * T1[0] * T1[2];
-        gS[4] = 2 * ga * T0[1] * T0[2] + gb * (T0[1] * T1[2] + T0[2] * T1[1]) + 2 * gc * T1[1] * T1[2];
-        float gj00 = 0.f, gj02 = 0.f, gj11 = 0.f, gj12 = 0.f;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-            for (int s = 0; s < 3; ++s) { s0 += S3[k][s] * T0[s]; s1 += S3[k][s] * T1[s]; }
-            const float gT0 = 2 * ga * s0 + gb * s1, gT1 = 2 * gc * s1 + gb * s0;
-            gj00 += gT0 * vm[4 * k + 0]; gj02 += gT0 * vm[4 * k + 2];
-            gj11 += gT1 * vm[4 * k + 1]; gj12 += gT1 * vm[4 * k + 2];
-        }
-        const float tz2 = 1.0f / (t[2] * t[2]), tz3 = tz2 / t[2];
-        gt[0] += xmul * -fx * tz2 * gj02;
-        gt[1] += ymul * -fy * tz2 * gj12;
-        gt[2] += -fx * tz2 * gj00 - fy * tz2 * gj11 + 2 * fx * cx * tz3 * gj02 + 2 * fy * cy * tz3 * gj12;
-        if (xmul == 0.f) gt[2] += -fx * tz2 * gj02 * (cx / t[2]);
-        if (ymul == 0.f) gt[2] += -fy * tz2 * gj12 * (cy / t[2]);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) gp[k] += vm[4 * k + 0] * gt[0] + vm[4 * k + 1] * gt[1] + vm[4 * k + 2] * gt[2];
+        load_cov3d(sc, i, cov);
+        view_geometry_backward(cam, row, p, cov, gp, gS, gndc);
 
         // ---- colour: SH coefficients and the view direction
         if (sc.shs) {
@@ -446,41 +548,132 @@ __global__ __launch_bounds__(256) void preprocess_backward_kernel(PgrScene sc, c
     if (o.scales || o.rotations) {
         float gs[3] = {0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f};
         if (live && sc.scales && sc.rotations) {
-            const float4 q4 = reinterpret_cast<const float4*>(sc.rotations)[i];
-            const float r = q4.x, x = q4.y, y = q4.z, z = q4.w;
-            const float R[3][3] = {{1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y)},
-                                   {2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x)},
-                                   {2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)}};
-            const float s[3] = {sc.scale_modifier * sc.scales[3 * i], sc.scale_modifier * sc.scales[3 * i + 1],
-                                sc.scale_modifier * sc.scales[3 * i + 2]};
-            const float Gf[3][3] = {{gS[0], 0.5f * gS[1], 0.5f * gS[2]}, {0.5f * gS[1], gS[3], 0.5f * gS[4]},
-                                    {0.5f * gS[2], 0.5f * gS[4], gS[5]}};
-            float gR[3][3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                float accs = 0.f;
-#pragma unroll
-                for (int a_ = 0; a_ < 3; ++a_) {
-                    float gM = 0.f;
-#pragma unroll
-                    for (int m = 0; m < 3; ++m) gM += 2 * Gf[a_][m] * R[m][k] * s[k];
-                    accs += gM * R[a_][k];
-                    gR[a_][k] = gM * s[k];
-                }
-                gs[k] = accs * sc.scale_modifier;
-            }
-            gq[0] = 2 * (-z * gR[0][1] + y * gR[0][2] + z * gR[1][0] - x * gR[1][2] - y * gR[2][0] + x * gR[2][1]);
-            gq[1] = 2 * (y * gR[0][1] + z * gR[0][2] + y * gR[1][0] - 2 * x * gR[1][1] - r * gR[1][2] + z * gR[2][0] +
-                         r * gR[2][1] - 2 * x * gR[2][2]);
-            gq[2] = 2 * (-2 * y * gR[0][0] + x * gR[0][1] + r * gR[0][2] + x * gR[1][0] + z * gR[1][2] - r * gR[2][0] +
-                         z * gR[2][1] - 2 * y * gR[2][2]);
-            gq[3] = 2 * (-2 * z * gR[0][0] - r * gR[0][1] + x * gR[0][2] + r * gR[1][0] - 2 * z * gR[1][1] + y * gR[1][2] +
-                         x * gR[2][0] + y * gR[2][1]);
+            scale_rot_backward(sc, i, gS, gs, gq);
         }
         if (o.scales) { o.scales[3 * i] = gs[0]; o.scales[3 * i + 1] = gs[1]; o.scales[3 * i + 2] = gs[2]; }
         if (o.rotations) reinterpret_cast<float4*>(o.rotations)[i] = make_float4(gq[0], gq[1], gq[2], gq[3]);
     }
     if (o.means2d) { o.means2d[3 * i] = gndc[0]; o.means2d[3 * i + 1] = gndc[1]; o.means2d[3 * i + 2] = 0.f; }
+    if (o.means3d) { o.means3d[3 * i] = gp[0]; o.means3d[3 * i + 1] = gp[1]; o.means3d[3 * i + 2] = gp[2]; }
+    if (o.opacities) o.opacities[i] = gop;
+    if (o.colors) { o.colors[3 * i] = gcol[0]; o.colors[3 * i + 1] = gcol[1]; o.colors[3 * i + 2] = gcol[2]; }
+    if (o.cov3d) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) o.cov3d[6 * (size_t)i + k] = gS[k];
+    }
+}
+
+// Per-Gaussian backward of a batch: one thread per Gaussian walks the views in a fixed order (0 .. n_views-1), as the forward
+// preprocess walks them, and sums in registers what each view that rendered the Gaussian contributes: mean, the six cov3D
+// partials, opacity, rgb and the (DEG+1)^2 x 3 SH coefficients.  means2d[v] (the screen-space gradient densification reads
+// per view) is written per view; the cov3D -> scale / rotation chain is linear in the cov3D gradient and runs ONCE, on the
+// sum.  Every output is written exactly once, no atomics.
+template <int DEG>
+__global__ __launch_bounds__(256) void preprocess_backward_batch_kernel(PgrScene sc, const BwdViewDev* __restrict__ views,
+                                                                        int n_views, GradOut o) {
+    constexpr int NC = (DEG + 1) * (DEG + 1);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= sc.n) return;
+    const bool sh_quads = sc.shs && sc.sh_stride == 16 && (reinterpret_cast<uintptr_t>(sc.shs) & 15u) == 0 &&
+                          (!o.shs || (reinterpret_cast<uintptr_t>(o.shs) & 15u) == 0);
+    const float p[3] = {sc.means3d[3 * i], sc.means3d[3 * i + 1], sc.means3d[3 * i + 2]};
+    float gp[3] = {0.f, 0.f, 0.f}, gS[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, gcol[3] = {0.f, 0.f, 0.f}, gop = 0.f;
+    float shv[3 * NC], gsh[3 * NC];      // the active coefficients (k, channel) and their summed gradients
+#pragma unroll
+    for (int k = 0; k < 3 * NC; ++k) { shv[k] = 0.f; gsh[k] = 0.f; }
+    bool any = false;
+    float cov[6];
+    for (int v = 0; v < n_views; ++v) {
+        const BwdViewDev& bv = views[v];
+        const bool live = bv.radii[i] > 0 && !bv.counters[1];
+        float gndc[2] = {0.f, 0.f};
+        if (live) {
+            if (!any) {      // per-Gaussian inputs, read once, at the first view that rendered the Gaussian
+                any = true;
+                load_cov3d(sc, i, cov);
+                if (sc.shs) {
+                    const float* sh = sc.shs + (size_t)i * sc.sh_stride * 3;
+                    if (sh_quads) {
+#pragma unroll
+                        for (int q = 0; q < (3 * NC + 3) / 4; ++q) {
+                            const float4 x = reinterpret_cast<const float4*>(sh)[q];
+                            const float e[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+                            for (int c = 0; c < 4; ++c)
+                                if (4 * q + c < 3 * NC) shv[4 * q + c] = e[c];
+                        }
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < 3 * NC; ++k) shv[k] = sh[k];
+                    }
+                }
+            }
+            const CameraDev& cam = *bv.cam;
+            const float* row = bv.rows + (size_t)i * GRAD_ROW;
+            gop += row[5];
+            const float gc[3] = {row[6], row[7], row[8]};
+#pragma unroll
+            for (int c = 0; c < 3; ++c) gcol[c] += gc[c];
+            float gpv[3] = {0.f, 0.f, 0.f}, gSv[6];
+            view_geometry_backward(cam, row, p, cov, gpv, gSv, gndc);
+            if (sc.shs) {
+                const float d[3] = {p[0] - cam.campos[0], p[1] - cam.campos[1], p[2] - cam.campos[2]};
+                const float len = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+                const float u[3] = {d[0] / len, d[1] / len, d[2] / len};
+                float bb[16], bx[16], by[16], bz[16];
+                sh_basis_grad<DEG>(u[0], u[1], u[2], bb, bx, by, bz);
+                float gu[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) {
+                    float accv = 0.f;
+#pragma unroll
+                    for (int k = 0; k < NC; ++k) accv += bb[k] * shv[3 * k + ch];
+                    const float g = (accv + 0.5f < 0.0f) ? 0.f : gc[ch];
+#pragma unroll
+                    for (int k = 0; k < NC; ++k) {
+                        gsh[3 * k + ch] += bb[k] * g;
+                        gu[0] += g * shv[3 * k + ch] * bx[k];
+                        gu[1] += g * shv[3 * k + ch] * by[k];
+                        gu[2] += g * shv[3 * k + ch] * bz[k];
+                    }
+                }
+                const float dot = u[0] * gu[0] + u[1] * gu[1] + u[2] * gu[2];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) gpv[k] += (gu[k] - u[k] * dot) / len;
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) gp[k] += gpv[k];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) gS[k] += gSv[k];
+        }
+        if (o.means2d) {
+            float* m2 = o.means2d + ((size_t)v * sc.n + i) * 3;
+            m2[0] = gndc[0]; m2[1] = gndc[1]; m2[2] = 0.f;
+        }
+    }
+    if (o.shs) {     // coefficients above the active degree (and every coefficient of an unseen Gaussian) receive zero
+        if (sh_quads) {
+            float4* dst = reinterpret_cast<float4*>(o.shs + (size_t)i * 48);
+#pragma unroll
+            for (int q = 0; q < 12; ++q) {
+                float e[4];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) e[c] = 4 * q + c < 3 * NC ? gsh[4 * q + c] : 0.f;
+                dst[q] = make_float4(e[0], e[1], e[2], e[3]);
+            }
+        } else {
+            float* dst = o.shs + (size_t)i * sc.sh_stride * 3;
+#pragma unroll
+            for (int k = 0; k < 3 * NC; ++k) dst[k] = gsh[k];
+            for (int k = 3 * NC; k < sc.sh_stride * 3; ++k) dst[k] = 0.f;
+        }
+    }
+    if (o.scales || o.rotations) {
+        float gs[3] = {0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f};
+        if (any && sc.scales && sc.rotations) scale_rot_backward(sc, i, gS, gs, gq);
+        if (o.scales) { o.scales[3 * i] = gs[0]; o.scales[3 * i + 1] = gs[1]; o.scales[3 * i + 2] = gs[2]; }
+        if (o.rotations) reinterpret_cast<float4*>(o.rotations)[i] = make_float4(gq[0], gq[1], gq[2], gq[3]);
+    }
     if (o.means3d) { o.means3d[3 * i] = gp[0]; o.means3d[3 * i + 1] = gp[1]; o.means3d[3 * i + 2] = gp[2]; }
     if (o.opacities) o.opacities[i] = gop;
     if (o.colors) { o.colors[3 * i] = gcol[0]; o.colors[3 * i + 1] = gcol[1]; o.colors[3 * i + 2] = gcol[2]; }

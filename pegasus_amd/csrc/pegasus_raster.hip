@@ -744,6 +744,69 @@ int32_t pgr_backward(const PgrScene* scene, const PgrCamera* cam, const float* g
     return hip_ok(hipGetLastError(), "backward launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
 }
 
+size_t pgr_backward_batch_scratch_bytes(int32_t n, int32_t n_views) {
+    if (n < 0 || n_views <= 0) return 0;
+    return align_up((size_t)n_views * (size_t)n * GRAD_ROW * sizeof(float)) + align_up((size_t)n_views * sizeof(BwdViewDev));
+}
+
+int32_t pgr_backward_batch(const PgrScene* scene, int32_t n_views, const PgrCamera* cameras, const PgrBackwardView* views,
+                           void* workspace, size_t workspace_bytes, int64_t max_instances_per_view,
+                           const PgrGradOutputs* grads, void* scratch, size_t scratch_bytes, void* stream_v) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    // every check before the first enqueue
+    if (int rc = check_scene(scene)) return rc;
+    if (scene->shs_rest) return PGR_ERR_INVALID_ARGUMENT;      // the SH gradient is one [n,sh_stride,3] array
+    if (n_views <= 0 || !cameras || !views || !grads) return PGR_ERR_INVALID_ARGUMENT;
+    if (max_instances_per_view < 0 || max_instances_per_view > 0x7fffffffLL) return PGR_ERR_INVALID_ARGUMENT;
+    const int N = scene->n, W = cameras[0].image_width, H = cameras[0].image_height;
+    if (W <= 0 || H <= 0) return PGR_ERR_INVALID_ARGUMENT;
+    for (int v = 0; v < n_views; ++v) {
+        if (cameras[v].image_width != W || cameras[v].image_height != H) return PGR_ERR_INVALID_ARGUMENT;
+        if (!views[v].grad_color || !views[v].final_T || !views[v].n_contrib) return PGR_ERR_INVALID_ARGUMENT;
+        if (N > 0 && !views[v].radii) return PGR_ERR_INVALID_ARGUMENT;
+    }
+    if (N == 0) return PGR_OK;
+    if (!workspace || !scratch || scratch_bytes < pgr_backward_batch_scratch_bytes(N, n_views)) return PGR_ERR_INVALID_ARGUMENT;
+    const Layout L = make_layout(N, W, H, max_instances_per_view);
+    const BatchLayout B = make_batch_layout(L, n_views, (size_t)N);
+    if (workspace_bytes < B.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    char* ws = static_cast<char*>(workspace);
+    const CameraDev* cams_dev = reinterpret_cast<const CameraDev*>(ws + B.cams);
+    const uint32_t* status_dev = reinterpret_cast<const uint32_t*>(ws + B.status);
+    const size_t rows_bytes = (size_t)n_views * (size_t)N * GRAD_ROW * sizeof(float);
+    float* rows = static_cast<float*>(scratch);
+    auto* table = reinterpret_cast<BwdViewDev*>(static_cast<char*>(scratch) + align_up(rows_bytes));
+    // the per-view table: the forward's slices of the workspace + the caller's per-view arrays, into the scratch from the
+    // launch arguments (no host staging that would have to outlive the call)
+    for (int v0 = 0; v0 < n_views; v0 += BWD_TABLE_CHUNK) {
+        const int cnt = std::min(BWD_TABLE_CHUNK, n_views - v0);
+        BwdTableChunk chunk;
+        memset(&chunk, 0, sizeof(chunk));
+        for (int k = 0; k < cnt; ++k) {
+            const int v = v0 + k;
+            const ViewWs vw = carve(ws + B.views + (size_t)v * B.per_view, L);
+            const PgrBackwardView& bv = views[v];
+            chunk.v[k] = BwdViewDev{cams_dev + v, vw.ranges, vw.gauss_sorted, vw.splats, status_dev + 2 * v, bv.grad_color,
+                                    bv.grad_depth, bv.final_T, bv.n_contrib, bv.radii, rows + (size_t)v * N * GRAD_ROW};
+        }
+        backward_table_kernel<<<1, 64, 0, stream>>>(chunk, cnt, table + v0);
+    }
+    if (!hip_ok(hipMemsetAsync(rows, 0, rows_bytes, stream), "memset grad rows")) return PGR_ERR_LAUNCH_FAILURE;
+    // the forward's interleaved work order is still in the workspace: every (view, tile, quarter) item, four blocks each
+    composite_backward_batch_kernel<<<4u * (uint32_t)B.order_slots, WAVE, 0, stream>>>(
+        table, (uint32_t)n_views, ITEMS_PER_TILE * (uint32_t)L.tiles, reinterpret_cast<const uint32_t*>(ws + B.work_order));
+    const GradOut go{grads->means2d, grads->means3d, grads->opacities, grads->colors, grads->shs, grads->cov3d,
+                     grads->scales, grads->rotations};
+    const int blocks = (N + 255) / 256;
+    switch (scene->shs ? scene->sh_degree : 0) {
+        case 0: preprocess_backward_batch_kernel<0><<<blocks, 256, 0, stream>>>(*scene, table, n_views, go); break;
+        case 1: preprocess_backward_batch_kernel<1><<<blocks, 256, 0, stream>>>(*scene, table, n_views, go); break;
+        case 2: preprocess_backward_batch_kernel<2><<<blocks, 256, 0, stream>>>(*scene, table, n_views, go); break;
+        default: preprocess_backward_batch_kernel<3><<<blocks, 256, 0, stream>>>(*scene, table, n_views, go); break;
+    }
+    return hip_ok(hipGetLastError(), "backward batch launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
 int32_t pgr_compose_object(int32_t n, const float* xyz, const float* rot, const float* f_rest, int32_t n_rest,
                            int32_t in_rest_stride, const PgrObjectPose* pose, float* out_xyz, float* out_rot,
                            float* out_rest, int32_t out_rest_stride, void* stream_v) {

@@ -26,7 +26,8 @@ from torch import nn
 from .. import _lib, rasterizer
 from ..rasterizer import dev_f32 as _dev_f32, _ptr
 
-__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "last_forward_info"]
+__all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "rasterize_gaussians_batch",
+           "last_forward_info"]
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -188,6 +189,142 @@ class _RasterizeGaussians(torch.autograd.Function):
         # means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings
         return (g["means3d"], g["means2d"], g.get("shs"), g.get("colors"), g["opacities"].view(ctx.op_shape),
                 g.get("scales"), g.get("rotations"), g.get("cov3d"), None)
+
+
+def _scene_struct(t, n, sh_degree, scale_modifier):
+    return _lib.PgrScene(n=n, means3d=_ptr(t["means3D"]), opacities=_ptr(t["op"]), scales=_ptr(t["scales"]),
+                         rotations=_ptr(t["rot"]), cov3d_precomp=_ptr(t["cov"]), shs=_ptr(t["sh"]),
+                         colors_precomp=_ptr(t["colors"]), sh_degree=int(sh_degree),
+                         sh_stride=int(t["sh"].shape[1]) if t["sh"] is not None else 0,
+                         scale_modifier=float(scale_modifier))
+
+
+_SCENE_KEYS = ("means3D", "sh", "colors", "op", "scales", "rot", "cov")
+
+
+class _RasterizeGaussiansBatch(torch.autograd.Function):
+    """Differentiable rasterization of V views of one scene in ONE pgr_forward_batch call, and its backward in one
+    pgr_backward_batch call (training over several cameras per step).  Outputs color [V,3,H,W], radii [V,n] (not
+    differentiable), depth [V,1,H,W].  Gradients of the scene inputs are summed over the views; ``means2D`` is [V,n,3] and
+    receives every view's own screen-space gradient.
+
+    The contract of _RasterizeGaussians: the call owns its workspace, retries an instance overflow with a grown capacity, and
+    saves every tensor the backward re-reads, so an in-place edit of an input between forward and backward raises."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings):
+        L = _lib.lib()
+        settings = tuple(settings)
+        V = len(settings)
+        if V == 0:
+            raise ValueError("rasterize_gaussians_batch: no views")
+        rs0 = settings[0]
+        H, W = int(rs0.image_height), int(rs0.image_width)
+        for rs in settings[1:]:
+            if (int(rs.image_height), int(rs.image_width)) != (H, W):
+                raise ValueError("rasterize_gaussians_batch: every view of a batch must have the same image size")
+            if int(rs.sh_degree) != int(rs0.sh_degree) or float(rs.scale_modifier) != float(rs0.scale_modifier):
+                raise ValueError("rasterize_gaussians_batch: sh_degree and scale_modifier must be the same for every view")
+        device = means3D.device
+        if device.type != "cuda":
+            raise RuntimeError("rasterize_gaussians_batch needs tensors on a HIP device (torch device 'cuda'); "
+                               "there is no CPU path")
+        n = int(means3D.shape[0])
+        t = {k: _dev_f32(v, device) for k, v in dict(means3D=means3D, sh=sh, colors=colors_precomp, op=opacities,
+                                                     scales=scales, rot=rotations, cov=cov3Ds_precomp).items()}
+        scene = _scene_struct(t, n, rs0.sh_degree, rs0.scale_modifier)
+        cam_t = [[_dev_f32(x, device) for x in (rs.viewmatrix, rs.projmatrix, rs.campos, rs.bg)] for rs in settings]
+        cams = (_lib.PgrCamera * V)(*[
+            _lib.PgrCamera(image_width=W, image_height=H, tanfovx=float(rs.tanfovx), tanfovy=float(rs.tanfovy),
+                           viewmatrix=_ptr(c[0]), projmatrix=_ptr(c[1]), campos=_ptr(c[2]), bg=_ptr(c[3]))
+            for rs, c in zip(settings, cam_t)])
+        color = torch.empty((V, 3, H, W), dtype=torch.float32, device=device)
+        depth = torch.empty((V, 1, H, W), dtype=torch.float32, device=device)
+        radii = torch.empty((V, n), dtype=torch.int32, device=device)
+        final_T = torch.empty((V, H, W), dtype=torch.float32, device=device)
+        n_contrib = torch.empty((V, H, W), dtype=torch.int32, device=device)
+        outs = (_lib.PgrOutputs * V)(*[
+            _lib.PgrOutputs(color=_ptr(color[v]), depth=_ptr(depth[v]), radii=_ptr(radii[v]), final_T=_ptr(final_T[v]),
+                            n_contrib=_ptr(n_contrib[v])) for v in range(V)])
+        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        max_inst = max(1 << 18, 4 * n)
+        need = (C.c_int64 * V)()
+        with torch.cuda.device(device):
+            for _attempt in range(3):
+                ws = torch.empty(L.pgr_batch_workspace_bytes(n, W, H, max_inst, V), dtype=torch.uint8, device=device)
+                status = L.pgr_forward_batch(C.byref(scene), V, cams, outs, C.c_void_p(ws.data_ptr()), ws.numel(),
+                                             max_inst, need, stream)
+                if status != _lib.PGR_ERR_INSTANCE_OVERFLOW:
+                    break
+                max_inst = rasterizer.grown_capacity(max(need), 1.25)
+            _lib.check(status, "pgr_forward_batch")
+        ctx.hw, ctx.V, ctx.n, ctx.max_inst = (H, W), V, n, max_inst
+        ctx.sh_degree, ctx.scale_modifier = int(rs0.sh_degree), float(rs0.scale_modifier)
+        ctx.present = tuple(k for k in _SCENE_KEYS if t[k] is not None)
+        ctx.op_shape = tuple(opacities.shape)
+        ctx.save_for_backward(*(t[k] for k in ctx.present), ws, radii, final_T, n_contrib)
+        ctx.mark_non_differentiable(radii)
+        return color, radii, depth
+
+    @staticmethod
+    def backward(ctx, grad_color, _grad_radii, grad_depth):
+        L = _lib.lib()
+        V, n, (H, W) = ctx.V, ctx.n, ctx.hw
+        saved = ctx.saved_tensors          # raises if an input was modified in place since the forward
+        k = len(ctx.present)
+        t = dict.fromkeys(_SCENE_KEYS)
+        t.update(zip(ctx.present, saved[:k]))
+        ws, radii, final_T, n_contrib = saved[k:]
+        device = ws.device
+        # preprocess_backward_batch_kernel writes every element of every gradient it is handed: no zero fill, except for
+        # an empty scene, where nothing runs
+        alloc = torch.empty if n > 0 else torch.zeros
+        z = lambda *shape: alloc(shape, dtype=torch.float32, device=device)
+        g = dict(means2d=z(V, n, 3), means3d=z(n, 3), opacities=z(n, 1))
+        if t["sh"] is not None:
+            g["shs"] = z(*t["sh"].shape)
+        else:
+            g["colors"] = z(n, 3)
+        if t["cov"] is not None:
+            g["cov3d"] = z(n, 6)
+        else:
+            g["scales"], g["rotations"] = z(n, 3), z(n, 4)
+        grads = _lib.PgrGradOutputs(**{key: _ptr(v) for key, v in g.items()})
+        scene = _scene_struct(t, n, ctx.sh_degree, ctx.scale_modifier)
+        cams = (_lib.PgrCamera * V)(*[_lib.PgrCamera(image_width=W, image_height=H) for _ in range(V)])
+        gc = grad_color.contiguous().float()
+        gd = None if grad_depth is None else grad_depth.contiguous().float()
+        views = (_lib.PgrBackwardView * V)(*[
+            _lib.PgrBackwardView(grad_color=_ptr(gc[v]), grad_depth=None if gd is None else _ptr(gd[v]),
+                                 final_T=_ptr(final_T[v]), n_contrib=_ptr(n_contrib[v]), radii=_ptr(radii[v]))
+            for v in range(V)])
+        scratch = torch.empty(max(1, L.pgr_backward_batch_scratch_bytes(n, V)), dtype=torch.uint8, device=device)
+        with torch.cuda.device(device):
+            _lib.check(L.pgr_backward_batch(C.byref(scene), V, cams, views, C.c_void_p(ws.data_ptr()), ws.numel(),
+                                            ctx.max_inst, C.byref(grads), C.c_void_p(scratch.data_ptr()), scratch.numel(),
+                                            C.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
+                       "pgr_backward_batch")
+        # means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings
+        return (g["means3d"], g["means2d"], g.get("shs"), g.get("colors"), g["opacities"].view(ctx.op_shape),
+                g.get("scales"), g.get("rotations"), g.get("cov3d"), None)
+
+
+def rasterize_gaussians_batch(means3D, means2D, opacities, raster_settings, shs=None, colors_precomp=None, scales=None,
+                              rotations=None, cov3D_precomp=None):
+    """Differentiable render of V views of one scene: ``raster_settings`` is a sequence of V
+    GaussianRasterizationSettings with one image size.  Returns (color [V,3,H,W], radii [V,n] int32, depth [V,1,H,W]).
+    ``means2D`` (or None) is [V,n,3]; its .grad receives each view's screen-space gradient.  Every other input's gradient
+    is the sum over the views."""
+    if (shs is None) == (colors_precomp is None):
+        raise ValueError("rasterize_gaussians_batch: provide exactly one of shs and colors_precomp")
+    if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+            ((scales is not None or rotations is not None) and cov3D_precomp is not None):
+        raise ValueError("rasterize_gaussians_batch: provide exactly one of a scale/rotation pair and cov3D_precomp")
+    settings = tuple(raster_settings)
+    if means2D is None:
+        means2D = torch.zeros((len(settings), int(means3D.shape[0]), 3), dtype=torch.float32, device=means3D.device)
+    return _RasterizeGaussiansBatch.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                          cov3D_precomp, settings)
 
 
 class GaussianRasterizer(nn.Module):

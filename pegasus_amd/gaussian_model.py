@@ -574,3 +574,15 @@ class GaussianModel:
         from .train_ops import densify_stats
         densify_stats(viewspace_point_tensor.grad.contiguous(), radii.to(torch.int32).contiguous(),
                       self.xyz_gradient_accum, self.denom, self.max_radii2D)
+
+    def add_batch_render_stats(self, viewspace_point_tensor, radii, grad_scale=1.0):
+        """add_render_stats for every view of a render_batch: ``viewspace_point_tensor`` [V,N,3] whose .grad holds each
+        view's screen-space gradient, ``radii`` [V,N]; one pgr_densify_stats launch per view, in view order.  The gradients
+        are multiplied by ``grad_scale`` first: a loss that is the MEAN of V per-view losses passes V, so that each view
+        counts with its own loss's gradient and densify_grad_threshold keeps its single-view meaning."""
+        from .train_ops import densify_stats
+        grad = viewspace_point_tensor.grad
+        radii = radii.to(torch.int32)
+        for v in range(int(grad.shape[0])):
+            g = grad[v] * grad_scale if grad_scale != 1.0 else grad[v]
+            densify_stats(g.contiguous(), radii[v].contiguous(), self.xyz_gradient_accum, self.denom, self.max_radii2D)

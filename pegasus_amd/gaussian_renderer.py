@@ -15,7 +15,8 @@ import weakref
 
 import torch
 
-from .diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians
+from .diff_gaussian_rasterization import (GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians,
+                                          rasterize_gaussians_batch)
 from .sh_utils import sh_basis
 
 # ---- activated parameters of a model, kept while the model does not change ------------------------------------------------
@@ -171,4 +172,36 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
             inputs.get("scales"), inputs.get("rotations"), inputs.get("cov3D_precomp"), settings,
             after_enqueue=lambda r: extra.__setitem__("vis", r["radii"] > 0), sh_rest=inputs.get("shs_rest"))
         return {"render": image, "depth": depth, "viewspace_points": probe, "visibility_filter": extra["vis"], "radii": radii}
+    return {"render": image, "depth": depth, "viewspace_points": probe, "visibility_filter": radii > 0, "radii": radii}
+
+
+def render_batch(cameras, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None):
+    """Render ``pc`` from V cameras of one image size in one differentiable call (pgr_forward_batch; backward
+    pgr_backward_batch): the training path's several views per optimiser step.  ``bg_color`` is [3] (every view) or [V,3]
+    (one background per view).  Returns "render" [V,3,H,W], "depth" [V,1,H,W], "viewspace_points" [V,N,3] (a leaf whose
+    .grad receives each view's own screen-space gradient when autograd is on), "visibility_filter" [V,N] (radii > 0) and
+    "radii" [V,N].  Colours come from the kernel-evaluated SH (or ``override_color``, shared by every view);
+    pipe.compute_cov3D_python is honoured.  pipe.convert_SHs_python is refused: its colours differ per view."""
+    cameras = list(cameras)
+    V = len(cameras)
+    if V == 0:
+        raise ValueError("render_batch: no cameras")
+    if getattr(pipe, "convert_SHs_python", False):
+        raise ValueError("render_batch: pipe.convert_SHs_python evaluates colours per view on the host; a batch takes the "
+                         "kernel-evaluated SH")
+    size = (int(cameras[0].image_height), int(cameras[0].image_width))
+    if any((int(c.image_height), int(c.image_width)) != size for c in cameras):
+        raise ValueError("render_batch: every camera of a batch must have the same image size")
+    if bg_color.dim() == 2:
+        if tuple(bg_color.shape) != (V, 3):
+            raise ValueError(f"render_batch: bg_color must be [3] or [{V},3], got {tuple(bg_color.shape)}")
+        bgs = [bg_color[v] for v in range(V)]
+    else:
+        bgs = [bg_color] * V
+    xyz = pc.get_xyz
+    probe = torch.zeros((V,) + tuple(xyz.shape), dtype=xyz.dtype, device=xyz.device, requires_grad=torch.is_grad_enabled())
+    settings = [_view(cam, pc, pipe, bg, scaling_modifier) for cam, bg in zip(cameras, bgs)]
+    colour = dict(colors_precomp=override_color) if override_color is not None else dict(shs=kept_activation(pc, "get_features"))
+    image, radii, depth = rasterize_gaussians_batch(xyz, probe, kept_activation(pc, "get_opacity"), settings, **colour,
+                                                    **_geometry(pc, pipe, scaling_modifier))
     return {"render": image, "depth": depth, "viewspace_points": probe, "visibility_filter": radii > 0, "radii": radii}

@@ -8,7 +8,10 @@ the 3DGS optimisation loop that PEGASUS's reconstruction scripts reach through t
 It reads a COLMAP dataset (pegasus_amd.colmap_io) and writes the model layout ``Scene(args, gaussians,
 load_iteration=-1)`` opens: cfg_args, cameras.json, input.ply, point_cloud/iteration_N/point_cloud.ply, chkpntN.pth.
 
-    python -m pegasus_amd.train -s <colmap dir> -m <output dir> [--iterations N] [--eval] ...
+    python -m pegasus_amd.train -s <colmap dir> -m <output dir> [--iterations N] [--eval] [--batch_size B] ...
+
+With --batch_size B > 1 a step renders B views in one render_batch (pgr_forward_batch / pgr_backward_batch) and the Adam
+step, which touches every parameter whatever the number of views, is paid once per B views.
 """
 from __future__ import annotations
 
@@ -153,13 +156,54 @@ def _gui_step(iteration, gaussians, pipe, background, opt, dataset):
             network_gui.conn = None
 
 
+def _pick_cameras(stack, train_cameras, k):
+    """k distinct cameras popped at random from ``stack``; a stack that runs short is emptied, then refilled from
+    ``train_cameras`` without the cameras already picked.  Returns (cameras, stack)."""
+    if k > len(train_cameras):
+        raise ValueError(f"batch_size {k} is larger than the {len(train_cameras)} training cameras")
+    cams = []
+    while len(cams) < k:
+        if not stack:
+            stack = [c for c in train_cameras if all(c is not d for d in cams)]
+        cams.append(stack.pop(random.randint(0, len(stack) - 1)))
+    return cams, stack
+
+
+def train_step_batch(gaussians, cams, pipe, bg, lambda_dssim):
+    """The forward and backward of one multi-view step: the B cameras in one render_batch, the loss = the mean of the B
+    per-view image losses, loss.backward().  Returns (loss, render_batch's dict).  Each view's screen-space gradient in
+    ``viewspace_points.grad`` then carries a factor 1/B: GaussianModel.add_batch_render_stats(..., grad_scale=B) undoes it."""
+    from .gaussian_renderer import render_batch
+    from .train_ops import ImageLoss
+    pkg = render_batch(cams, gaussians, pipe, bg)
+    image = pkg["render"]
+    loss = sum(ImageLoss.apply(image[v], cam.original_image, float(lambda_dssim)) for v, cam in enumerate(cams)) / len(cams)
+    loss.backward()
+    return loss, pkg
+
+
 def training(dataset, opt, pipe, testing_iterations, saving_iterations, checkpoint_iterations, checkpoint, debug_from,
-             quiet=False):
+             quiet=False, batch_size=None):
     """Trains a Gaussian model on ``dataset.source_path`` (COLMAP) into ``dataset.model_path``.  Returns
-    {"reports": {iteration: {"test"/"train": {"l1", "psnr"}}}, "num_gaussians": N, "model": GaussianModel}."""
+    {"reports": {iteration: {"test"/"train": {"l1", "psnr"}}}, "num_gaussians": N, "model": GaussianModel}.
+
+    ``batch_size`` (default: ``opt.batch_size`` if the options carry one, else 1) views per optimiser step.  With B > 1
+    each step renders B distinct training cameras in one render_batch (one random background per view with
+    random_background), the loss is the mean of the B per-view losses, and the densification statistics take each view's
+    own loss gradient.  Every schedule -- learning rate, SH degree, densify / opacity reset, test / save / checkpoint
+    iterations and ``iterations`` itself -- keeps counting OPTIMISER STEPS: a run with B views per step sees B times as many
+    images; divide ``--iterations`` (and the schedules) by B for the same number of images.  Nothing is rescaled here."""
     from . import network_gui
     from .gaussian_renderer import render
     from .train_ops import ImageLoss
+    if batch_size is None:
+        batch_size = getattr(opt, "batch_size", 1)
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+    if batch_size > 1 and getattr(pipe, "convert_SHs_python", False):
+        raise ValueError("batch_size > 1 renders through render_batch, which takes the kernel-evaluated SH: "
+                         "convert_SHs_python is not supported with it")
     opt = _Options(opt, OPTIMIZATION_DEFAULTS)
     dataset = _Options(dataset, MODEL_DEFAULTS)
     testing_iterations, saving_iterations = set(testing_iterations or ()), set(saving_iterations or ())
@@ -185,16 +229,24 @@ def training(dataset, opt, pipe, testing_iterations, saving_iterations, checkpoi
         gaussians.update_learning_rate(iteration)
         if iteration % 1000 == 0:
             gaussians.oneupSHdegree()
-        if not stack:
-            stack = scene.getTrainCameras().copy()
-        cam = stack.pop(random.randint(0, len(stack) - 1))
-        if iteration - 1 == debug_from:
-            pipe.debug = True
-        bg = torch.rand(3, device=dev) if opt.random_background else background
-        pkg = render(cam, gaussians, pipe, bg)
-        image, viewspace, radii = pkg["render"], pkg["viewspace_points"], pkg["radii"]
-        loss = ImageLoss.apply(image, cam.original_image, float(opt.lambda_dssim))
-        loss.backward()
+        if batch_size == 1:
+            if not stack:
+                stack = scene.getTrainCameras().copy()
+            cam = stack.pop(random.randint(0, len(stack) - 1))
+            if iteration - 1 == debug_from:
+                pipe.debug = True
+            bg = torch.rand(3, device=dev) if opt.random_background else background
+            pkg = render(cam, gaussians, pipe, bg)
+            image, viewspace, radii = pkg["render"], pkg["viewspace_points"], pkg["radii"]
+            loss = ImageLoss.apply(image, cam.original_image, float(opt.lambda_dssim))
+            loss.backward()
+        else:
+            cams, stack = _pick_cameras(stack or [], scene.getTrainCameras(), batch_size)
+            if iteration - 1 == debug_from:
+                pipe.debug = True
+            bg = torch.rand((batch_size, 3), device=dev) if opt.random_background else background
+            loss, pkg = train_step_batch(gaussians, cams, pipe, bg, opt.lambda_dssim)
+            viewspace, radii = pkg["viewspace_points"], pkg["radii"]
         with torch.no_grad():
             if iteration in testing_iterations:
                 reports[iteration] = training_report(iteration, scene, gaussians, pipe, background, quiet)
@@ -203,7 +255,10 @@ def training(dataset, opt, pipe, testing_iterations, saving_iterations, checkpoi
                     print(f"\n[ITER {iteration}] Saving Gaussians")
                 scene.save(iteration)
             if iteration < opt.densify_until_iter:
-                gaussians.add_render_stats(viewspace, radii)
+                if batch_size == 1:
+                    gaussians.add_render_stats(viewspace, radii)
+                else:
+                    gaussians.add_batch_render_stats(viewspace, radii, grad_scale=batch_size)
                 if iteration > opt.densify_from_iter and iteration % opt.densification_interval == 0:
                     size_threshold = SCREEN_SIZE_LIMIT if iteration > opt.opacity_reset_interval else None
                     gaussians.densify_and_prune(opt.densify_grad_threshold, MIN_OPACITY, scene.cameras_extent,
@@ -238,6 +293,8 @@ def _parser() -> ArgumentParser:
     p.add_argument("--checkpoint_iterations", nargs="+", type=int, default=[])
     p.add_argument("--start_checkpoint", type=str, default=None)
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--batch_size", type=int, default=1,
+                   help="views per optimiser step (schedules and --iterations count steps, not views)")
     p.add_argument("--quiet", action="store_true")
     return p
 
@@ -252,7 +309,7 @@ def main(argv=None) -> int:
     torch.manual_seed(args.seed)
     print("Optimizing " + args.model_path)
     training(args, args, args, args.test_iterations, args.save_iterations, args.checkpoint_iterations,
-             args.start_checkpoint, args.debug_from, quiet=args.quiet)
+             args.start_checkpoint, args.debug_from, quiet=args.quiet, batch_size=args.batch_size)
     print("\nTraining complete.")
     return 0
 

@@ -3,8 +3,12 @@ forward / loss / backward / stats / optimizer with HIP events, plus two same-box
     loss:      pgr_image_loss (value + gradient, one call)  vs  the torch conv2d form of the same loss + its backward
     optimizer: FusedAdam (one pgr_adam_step launch)         vs  torch.optim.Adam(foreach=True)
 Inputs are random (targets, gradients); every stage is warmed up first; each number is the median of 5 repeats.
+--batch B ... adds multi-view steps (render_batch: B views per optimiser step, one pgr_forward_batch and one
+pgr_backward_batch) with the same stage split, per step and per view; "backward" is the HIP-event time of loss.backward(),
+i.e. of the backward kernels.  B = 1 is the single-view loop above (the default, whose output is unchanged).
 
-    python scripts/train_step_bench.py [--iters 20] [--warmup 5] [--repeats 5] [--scenes c2 c3] [--json out.json]
+    python scripts/train_step_bench.py [--iters 20] [--warmup 5] [--repeats 5] [--scenes c2 c3] [--batch 1 2 4 8]
+                                       [--json out.json]
 """
 from __future__ import annotations
 
@@ -83,6 +87,35 @@ def train_steps(m, cams, iters, dev):
     return per
 
 
+def train_steps_batch(m, cams, B, iters, dev):
+    """train_steps with B views per optimiser step (render_batch; loss = the mean of the B per-view losses)."""
+    from pegasus_amd.gaussian_renderer import render_batch
+    from pegasus_amd.train_ops import ImageLoss
+    pipe = SimpleNamespace(convert_SHs_python=False, compute_cov3D_python=False, debug=False)
+    bg = torch.zeros(3, device=dev)
+    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(len(STAGES) + 1)] for _ in range(iters)]
+    for i in range(iters):
+        batch = [cams[(i * B + k) % len(cams)] for k in range(B)]
+        e = ev[i]
+        e[0].record()
+        pkg = render_batch(batch, m, pipe, bg)
+        e[1].record()
+        loss = sum(ImageLoss.apply(pkg["render"][k], c.original_image, 0.2) for k, c in enumerate(batch)) / B
+        e[2].record()
+        loss.backward()
+        e[3].record()
+        with torch.no_grad():
+            m.add_batch_render_stats(pkg["viewspace_points"], pkg["radii"], grad_scale=B)
+            e[4].record()
+            m.optimizer.step()
+            m.optimizer.zero_grad(set_to_none=True)
+        e[5].record()
+    torch.cuda.synchronize()
+    per = {s: sum(e[k].elapsed_time(e[k + 1]) for e in ev) / iters for k, s in enumerate(STAGES)}
+    per["total"] = sum(e[0].elapsed_time(e[-1]) for e in ev) / iters
+    return per
+
+
 def time_loop(fn, iters):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
@@ -147,6 +180,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--scenes", nargs="+", default=["c2", "c3"])
+    ap.add_argument("--batch", nargs="+", type=int, default=[1], help="views per optimiser step (1: the single-view loop)")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -163,6 +197,14 @@ def main():
         report[name] = {"gaussians": int(m.get_xyz.shape[0]), "ms_per_iter": med,
                         "adam_ab_ms": adam_ab(m, dev, a.iters, a.warmup, a.repeats)}
         print(name, json.dumps(report[name]), flush=True)
+        for B in (b for b in a.batch if b > 1):
+            train_steps_batch(m, cams, B, a.warmup, dev)
+            reps = [train_steps_batch(m, cams, B, a.iters, dev) for _ in range(a.repeats)]
+            step = {k: statistics.median(r[k] for r in reps) for k in reps[0]}
+            report[name].setdefault("batch", {})[str(B)] = {"ms_per_step": step,
+                                                              "ms_per_view": {k: v / B for k, v in step.items()}}
+            print(f"{name} B={B}", json.dumps(report[name]["batch"][str(B)]), flush=True)
+            torch.cuda.empty_cache()
         del m, cams
         torch.cuda.empty_cache()
     line = json.dumps(report)
