@@ -58,16 +58,29 @@ def quat_R(q):
                      [2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)]])
 
 
-def dense_forward(means3d, opacities, scales, rotations, shs, sh_degree, width, height, tanfovx, tanfovy, viewmatrix,
-                  projmatrix, campos, bg, scale_modifier=1.0):
-    f = lambda a: np.asarray(a, dtype=np.float64)
+def dense_forward(means3d, opacities, scales=None, rotations=None, shs=None, sh_degree=0, *, width, height, tanfovx,
+                  tanfovy, viewmatrix, projmatrix, campos, bg, scale_modifier=1.0, cov3d_precomp=None, colors_precomp=None,
+                  return_decisions=False):
+    """(colour [3,H,W], depth [H,W]) in float64; with ``return_decisions`` also a dict of every discrete decision the
+    image function took -- which Gaussians were projected (t_z > 0.2, det != 0, a tile rectangle) and their tile
+    rectangles, which view-space coordinates hit the 1.3*tanfov clamp, which colour channels hit max(., 0), and per pixel
+    the set of blended entries, the entries whose alpha hit the 0.99 clamp and the entry at which T < 1e-4 stopped the
+    pixel.  Two calls with equal decisions lie on one smooth piece of the model (compare with ``same_decisions``): a
+    finite difference across a kink is a sample to discard, not a gradient.
+
+    ``cov3d_precomp`` [n,6] replaces scales / rotations: the upper triangle (xx, xy, xz, yy, yz, zz) of the symmetric
+    3D covariance, each off-diagonal stored ONCE (a change of the stored xy moves both Sigma_xy and Sigma_yx).
+    ``colors_precomp`` [n,3] replaces the SH colour (no clamp at 0)."""
+    f = lambda a: None if a is None else np.asarray(a, dtype=np.float64)
     means3d, opacities, scales, rotations, shs = f(means3d), f(opacities).reshape(-1), f(scales), f(rotations), f(shs)
+    cov3d_precomp, colors_precomp = f(cov3d_precomp), f(colors_precomp)
     vm, pm, campos, bg = f(viewmatrix).reshape(4, 4), f(projmatrix).reshape(4, 4), f(campos), f(bg)
     W, H = width, height
     fx, fy = W / (2 * tanfovx), H / (2 * tanfovy)
     gx, gy = (W + 15) // 16, (H + 15) // 16
     n = means3d.shape[0]
     recs = []
+    dec = dict(projected=[], clamp_xy=[], rgb_neg=[])
     for i in range(n):
         p = np.append(means3d[i], 1.0)
         t = p @ vm[:, :3]                 # row-vector convention: vm is stored transposed
@@ -75,9 +88,13 @@ def dense_forward(means3d, opacities, scales, rotations, shs, sh_degree, width, 
             continue
         h = p @ pm
         ndc = h[:2] / (h[3] + 1e-7)
-        R = quat_R(rotations[i])
-        M = R * (scale_modifier * scales[i])[None, :]
-        S3 = M @ M.T
+        if cov3d_precomp is not None:
+            c6 = cov3d_precomp[i]
+            S3 = np.array([[c6[0], c6[1], c6[2]], [c6[1], c6[3], c6[4]], [c6[2], c6[4], c6[5]]])
+        else:
+            R = quat_R(rotations[i])
+            M = R * (scale_modifier * scales[i])[None, :]
+            S3 = M @ M.T
         cx = min(1.3 * tanfovx, max(-1.3 * tanfovx, t[0] / t[2])) * t[2]
         cy = min(1.3 * tanfovy, max(-1.3 * tanfovy, t[1] / t[2])) * t[2]
         J = np.array([[fx / t[2], 0, -fx * cx / t[2] ** 2], [0, fy / t[2], -fy * cy / t[2] ** 2]])
@@ -97,14 +114,22 @@ def dense_forward(means3d, opacities, scales, rotations, shs, sh_degree, width, 
         maxx, maxy = ct((pix[0] + radius + 15) / 16, gx), ct((pix[1] + radius + 15) / 16, gy)
         if maxx <= minx or maxy <= miny:
             continue
-        d = means3d[i] - campos
-        d = d / np.linalg.norm(d)
-        b = real_sh_basis(sh_degree, d)
-        rgb = np.maximum(b @ shs[i, :b.shape[0]] + 0.5, 0.0)
+        if colors_precomp is not None:
+            rgb = colors_precomp[i]
+        else:
+            d = means3d[i] - campos
+            d = d / np.linalg.norm(d)
+            b = real_sh_basis(sh_degree, d)
+            raw = b @ shs[i, :b.shape[0]] + 0.5
+            rgb = np.maximum(raw, 0.0)
+            dec["rgb_neg"].append((i, *(bool(x) for x in raw < 0)))
+        dec["projected"].append((i, minx, miny, maxx, maxy))
+        dec["clamp_xy"].append((i, bool(abs(t[0] / t[2]) > 1.3 * tanfovx), bool(abs(t[1] / t[2]) > 1.3 * tanfovy)))
         recs.append((t[2], i, pix, conic, opacities[i], rgb, (minx, miny, maxx, maxy)))
     recs.sort(key=lambda r: (np.float32(r[0]), r[1]))
     ys, xs = np.mgrid[0:H, 0:W].astype(np.float64)
     T = np.ones((H, W)); C = np.zeros((3, H, W)); D = np.zeros((H, W)); done = np.zeros((H, W), bool)
+    blended, clamped, stop_at = [], [], np.full((H, W), -1)
     for z, i, pix, conic, op, rgb, (minx, miny, maxx, maxy) in recs:
         inrect = (xs >= 16 * minx) & (xs < 16 * maxx) & (ys >= 16 * miny) & (ys < 16 * maxy)
         dx, dy = pix[0] - xs, pix[1] - ys
@@ -119,4 +144,25 @@ def dense_forward(means3d, opacities, scales, rotations, shs, sh_degree, width, 
         C += rgb[:, None, None] * w
         D += z * w
         T = np.where(blend, test_T, T)
-    return C + T * bg[:, None, None], D
+        if return_decisions:
+            blended.append(np.packbits(blend))
+            clamped.append(np.packbits(blend & (op * np.exp(np.minimum(power, 0)) > 0.99)))
+            stop_at[stop] = i
+    if not return_decisions:
+        return C + T * bg[:, None, None], D
+    dec.update(order=[r[1] for r in recs], blended=blended, clamped=clamped, stop_at=stop_at)
+    return C + T * bg[:, None, None], D, dec
+
+
+def same_decisions(a, b):
+    """Whether two ``dense_forward(..., return_decisions=True)`` calls took every discrete decision alike."""
+    if a.keys() != b.keys():
+        return False
+    for k in a:
+        x, y = a[k], b[k]
+        if isinstance(x, np.ndarray):
+            if not np.array_equal(x, y):
+                return False
+        elif len(x) != len(y) or any(not np.array_equal(u, v) for u, v in zip(x, y)):
+            return False
+    return True

@@ -99,3 +99,36 @@ def assert_images_match(g, o, tol=1e-4, max_ambig_frac=5e-4):
         ad = np.abs(g["out_depth"][0] - o["out_depth"][0])[amb].max()
         at = np.abs(g["final_T"] - o["final_T"])[amb].max()
         assert ac <= 0.02 * cmax and ad <= 0.02 * zmax and at <= 0.02, f"flagged pixels differ by more than one entry: {ac} {ad} {at}"
+
+
+def grad_ratio(got, ref, rel=1e-3, floor=1e-5):
+    """Per-element error of a gradient against its reference, in units of the bound rel*|ref| + floor*max|ref|:
+    (worst ratio, flat index of the worst element).  A ratio <= 1 passes.  Where the whole group is 0 the bound is 0 and
+    only an exact 0 passes."""
+    got = np.asarray(got, np.float64).reshape(-1)
+    ref = np.asarray(ref, np.float64).reshape(-1)
+    if got.size == 0:
+        return 0.0, -1
+    err = np.abs(got - ref)
+    bound = rel * np.abs(ref) + floor * np.abs(ref).max()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(err == 0, 0.0, err / bound)
+    ratio = np.where(np.isnan(ratio), np.inf, ratio)
+    k = int(ratio.argmax())
+    return float(ratio[k]), k
+
+
+def assert_grads_match(got: dict, ref: dict, tag="", rel=1e-3, floor=1e-5, bounds=None):
+    """Every gradient group of ``got`` against ``ref``, per element (grad_ratio).  ``bounds`` may raise the allowed ratio
+    of a named group (a documented rounding mechanism, at most 10x its measured worst).  Returns {group: worst ratio}."""
+    worst = {}
+    for k in got:
+        g, r = np.asarray(got[k]), np.asarray(ref[k])
+        assert g.shape == r.shape, (tag, k, g.shape, r.shape)
+        assert np.isfinite(g).all(), (tag, k, "non-finite gradient")
+        ratio, i = grad_ratio(g, r, rel, floor)
+        worst[k] = ratio
+        limit = (bounds or {}).get(k, 1.0)
+        assert ratio <= limit, (f"{tag} {k}: worst element {np.unravel_index(i, g.shape)} got {g.reshape(-1)[i]!r} "
+                                f"ref {r.reshape(-1)[i]!r} ratio {ratio:.3g} > {limit}")
+    return worst
