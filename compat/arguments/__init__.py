@@ -40,6 +40,7 @@ class ModelParams(ParamGroup):
         self._white_background = False
         self.data_device = "cuda"
         self.eval = False
+        self.masks = ""                # per-image object masks: a directory, "alpha" or "" (pegasus_amd.train.MASK_DEFAULTS)
         super().__init__(parser, "Loading Parameters", sentinel)
 
 
@@ -71,6 +72,7 @@ class OptimizationParams(ParamGroup):
         self.densify_until_iter = 15_000
         self.densify_grad_threshold = 0.0002
         self.random_background = False
+        self.lambda_alpha = 0.5        # weight of mean|alpha - mask| when training from masks
         super().__init__(parser, "Optimization Parameters")
 
 

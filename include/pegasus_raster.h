@@ -400,6 +400,16 @@ int32_t pgr_backward(const PgrScene *scene, const PgrCamera *camera, const float
                      const int32_t *radii, void *workspace, size_t workspace_bytes, int64_t max_instances,
                      const PgrGradOutputs *grads, float *grad_rows, void *stream);
 
+/* pgr_backward with the gradient of the accumulated opacity: grad_alpha = dL/dalpha [1,H,W] or NULL, alpha = 1 - final_T
+ * (what the forward's final_T output leaves behind).  For every blended entry i of a pixel, dalpha/dalpha_i =
+ * final_T / (1 - alpha_i), under the colour term's conventions (the 0.99 clamp passes the gradient straight through, the
+ * T < 1e-4 stop and n_contrib bound the walk).  grad_alpha = NULL reads nothing and gives exactly pgr_backward's results
+ * (pgr_backward is this call with NULL). */
+int32_t pgr_backward_ex(const PgrScene *scene, const PgrCamera *camera, const float *grad_color,
+                        const float *grad_depth, const float *grad_alpha, const float *final_T,
+                        const uint32_t *n_contrib, const int32_t *radii, void *workspace, size_t workspace_bytes,
+                        int64_t max_instances, const PgrGradOutputs *grads, float *grad_rows, void *stream);
+
 /* Backward of a pgr_forward_batch call: the gradients of a loss over all n_views images at once.  `workspace` must be exactly
  * as that call left it (same n, image size, max_instances_per_view and n_views); `cameras` are the forward's (only the image
  * size is read: the packed cameras live in the workspace).  `views` is a HOST array of n_views entries, one per view.
@@ -423,6 +433,13 @@ size_t pgr_backward_batch_scratch_bytes(int32_t n, int32_t n_views);
 int32_t pgr_backward_batch(const PgrScene *scene, int32_t n_views, const PgrCamera *cameras, const PgrBackwardView *views,
                            void *workspace, size_t workspace_bytes, int64_t max_instances_per_view,
                            const PgrGradOutputs *grads, void *scratch, size_t scratch_bytes, void *stream);
+/* pgr_backward_batch with the per-view gradient of the accumulated opacity (see pgr_backward_ex): grad_alpha is a HOST
+ * array of n_views device pointers ([1,H,W] each), any of which may be NULL; the whole array may be NULL (pgr_backward_batch
+ * is this call with NULL). */
+int32_t pgr_backward_batch_ex(const PgrScene *scene, int32_t n_views, const PgrCamera *cameras,
+                              const PgrBackwardView *views, const float *const *grad_alpha, void *workspace,
+                              size_t workspace_bytes, int64_t max_instances_per_view, const PgrGradOutputs *grads,
+                              void *scratch, size_t scratch_bytes, void *stream);
 
 /* present[i] = 1 iff Gaussian i passes the near-plane test of `viewmatrix` (device [16]). */
 int32_t pgr_mark_visible(int32_t n, const float *means3d, const float *viewmatrix, uint8_t *present,
@@ -474,6 +491,20 @@ int32_t pgr_pack_records(const float *color_b3hw, const float *depth_bhw, const 
 size_t pgr_image_loss_workspace_bytes(int32_t height, int32_t width);
 int32_t pgr_image_loss(const float *x, const float *y, int32_t height, int32_t width, double lambda_dssim, float *out3,
                        float *grad, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The image loss against a MASKED target, plus an opacity term (training an object from per-image masks):
+ *   y' = y m + bg (1 - m)                                  (formed on the fly; no [3,H,W] target is written)
+ *   loss = (1 - lambda) mean|x - y'| + lambda (1 - mean SSIM(x, y')) + lambda_alpha mean|a - m|
+ * mask m [H,W] in 0..1, bg [3] (the step's background, device), alpha a [H,W] (the render's 1 - final_T), all device fp32.
+ * out4 (device, 4 floats) = {loss, mean |x - y'|, mean SSIM, mean |a - m| (0 without alpha)}; grad = dloss/dx [3,H,W] or
+ * NULL; grad_alpha = dloss/da [H,W] or NULL (sign(0) = 0).  mask = NULL is pgr_image_loss (bit for bit, out4[3] = 0).
+ * PGR_ERR_INVALID_ARGUMENT before anything is enqueued: a mask without bg, alpha without a mask, lambda_alpha < 0,
+ * lambda_alpha > 0 without alpha, grad_alpha without alpha (and pgr_image_loss's own checks).  Deterministic, like
+ * pgr_image_loss.  workspace >= pgr_image_loss_masked_workspace_bytes(height, width). */
+size_t pgr_image_loss_masked_workspace_bytes(int32_t height, int32_t width);
+int32_t pgr_image_loss_masked(const float *x, const float *y, const float *mask, const float *bg, const float *alpha,
+                              int32_t height, int32_t width, double lambda_dssim, double lambda_alpha, float *out4,
+                              float *grad, float *grad_alpha, void *workspace, size_t workspace_bytes, void *stream);
 
 /* One Adam step over up to PGR_ADAM_MAX_GROUPS parameter groups in one launch, with torch.optim.Adam's single-tensor
  * arithmetic (no weight decay, no amsgrad).  The table is HOST memory, read during the call; every pointer in it is a

@@ -153,10 +153,16 @@ SYMBOLS = {
     "pgr_backward": (C.c_int32, [C.POINTER(PgrScene), C.POINTER(PgrCamera), C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.POINTER(PgrGradOutputs),
                                  C.c_void_p, C.c_void_p]),
+    "pgr_backward_ex": (C.c_int32, [C.POINTER(PgrScene), C.POINTER(PgrCamera), C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64,
+                                    C.POINTER(PgrGradOutputs), C.c_void_p, C.c_void_p]),
     "pgr_backward_batch_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "pgr_backward_batch": (C.c_int32, [C.POINTER(PgrScene), C.c_int32, C.POINTER(PgrCamera), C.POINTER(PgrBackwardView),
                                        C.c_void_p, C.c_size_t, C.c_int64, C.POINTER(PgrGradOutputs), C.c_void_p,
                                        C.c_size_t, C.c_void_p]),
+    "pgr_backward_batch_ex": (C.c_int32, [C.POINTER(PgrScene), C.c_int32, C.POINTER(PgrCamera),
+                                          C.POINTER(PgrBackwardView), C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t,
+                                          C.c_int64, C.POINTER(PgrGradOutputs), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pgr_compose_object": (C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                        C.POINTER(PgrObjectPose), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                        C.c_void_p]),
@@ -179,6 +185,10 @@ SYMBOLS = {
     "pgr_image_loss_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "pgr_image_loss": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pgr_image_loss_masked_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "pgr_image_loss_masked": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                          C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_size_t, C.c_void_p]),
     "pgr_adam_step": (C.c_int32, [C.POINTER(PgrAdamGroup), C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p]),
     "pgr_densify_stats": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),

@@ -15,9 +15,12 @@ from . import graphics as G
 
 class Camera(nn.Module):
     def __init__(self, colmap_id, R, T, FoVx, FoVy, image, gt_alpha_mask, image_name, uid,
-                 trans=np.array([0.0, 0.0, 0.0]), scale=1.0, data_device="cuda", image_width=None, image_height=None):
+                 trans=np.array([0.0, 0.0, 0.0]), scale=1.0, data_device="cuda", image_width=None, image_height=None,
+                 gt_mask=None):
         """``image=None`` with ``image_width`` / ``image_height``: a render-only camera (no ground-truth image is kept:
-        the reference's own cameras are built around ``torch.empty((3, H, W))`` placeholders, pegasus_setup.py:130-140)."""
+        the reference's own cameras are built around ``torch.empty((3, H, W))`` placeholders, pegasus_setup.py:130-140).
+        ``gt_mask``: the object mask [1,H,W] in 0..1 the trainer supervises alpha with (kept as ``gt_mask`` on
+        ``data_device``; unlike ``gt_alpha_mask`` it does not touch the image)."""
         super().__init__()
         self.uid = uid
         self.colmap_id = colmap_id
@@ -43,6 +46,7 @@ class Camera(nn.Module):
             self.image_height = self.original_image.shape[1]
             if gt_alpha_mask is not None:
                 self.original_image *= gt_alpha_mask.to(self.data_device)
+        self.gt_mask = None if gt_mask is None else gt_mask.to(torch.float32).clamp(0.0, 1.0).to(self.data_device)
         self.zfar = G.ZFAR
         self.znear = G.ZNEAR
         self.trans = trans

@@ -328,9 +328,39 @@ def _target_size(w, h, resolution, scale=1.0):
     return int(w / f), int(h / f)
 
 
-def load_camera(info: CameraInfo, resolution=-1, white_background=False, data_device="cuda"):
+MASK_EXTENSIONS = (".png", ".jpg", ".jpeg", ".PNG", ".JPG", ".JPEG")
+
+
+def mask_path(masks_dir, image_name: str) -> str:
+    """The mask file of an image in a mask directory: the file with the image's stem and a png or jpg extension (the
+    layout of PEGASUS's object reconstruction: one mask per image, named like it).  Raises FileNotFoundError naming the
+    image when there is none."""
+    stem = os.path.splitext(os.path.basename(image_name))[0]
+    for ext in MASK_EXTENSIONS:
+        p = os.path.join(masks_dir, stem + ext)
+        if os.path.isfile(p):
+            return p
+    raise FileNotFoundError(f"no mask for image {image_name!r} in {masks_dir} (looked for {stem}.png / {stem}.jpg)")
+
+
+def load_mask(path, size) -> np.ndarray:
+    """A mask file as float32 [H,W] in 0..1: greyscale / 255, resized (bilinear) to ``size`` = (W, H)."""
+    from PIL import Image
+    with Image.open(path) as m:
+        m = m.convert("L")
+        if m.size != tuple(size):
+            m = m.resize(tuple(size), Image.BILINEAR)
+        return np.clip(np.asarray(m, dtype=np.float32) / 255.0, 0.0, 1.0)
+
+
+def load_camera(info: CameraInfo, resolution=-1, white_background=False, data_device="cuda", masks=""):
     """Camera with its ground-truth image ([3,H,W] in 0..1, resized per ``resolution``; an alpha channel composites the
-    image over the training background: white with ``white_background``, else black)."""
+    image over the training background: white with ``white_background``, else black).
+
+    ``masks``: a per-image object mask for alpha supervision, kept as ``camera.gt_mask`` [1,H,W].  A directory (the mask
+    of each image is the file with its stem, png or jpg, read as greyscale / 255, resized bilinearly to the image's training
+    size), or ``"alpha"`` (the image's own alpha channel).  With masks the RGB is NOT composited: the trainer composites the
+    target over each step's background.  An image without a mask raises an error that names it.  ``""``: no masks."""
     import torch
     from PIL import Image
 
@@ -342,9 +372,17 @@ def load_camera(info: CameraInfo, resolution=-1, white_background=False, data_de
             im = im.resize(size, Image.BICUBIC)
         a = np.asarray(im, dtype=np.float32) / 255.0
     rgb = a[..., :3]
-    if a.shape[-1] == 4:
+    mask = None
+    if masks == "alpha":
+        if a.shape[-1] != 4:
+            raise ValueError(f"masks='alpha' but image {info.image_name!r} ({info.image_path}) has no alpha channel")
+        mask = np.clip(a[..., 3], 0.0, 1.0)
+    elif masks:
+        mask = load_mask(mask_path(masks, info.image_name), size)
+    elif a.shape[-1] == 4:
         bg = 1.0 if white_background else 0.0
         rgb = rgb * a[..., 3:4] + bg * (1.0 - a[..., 3:4])
     image = torch.from_numpy(np.ascontiguousarray(rgb.transpose(2, 0, 1)))
+    gt_mask = None if mask is None else torch.from_numpy(np.ascontiguousarray(mask))[None]
     return Camera(colmap_id=info.uid, R=info.R, T=info.T, FoVx=info.FoVx, FoVy=info.FoVy, image=image, gt_alpha_mask=None,
-                  image_name=info.image_name, uid=info.uid, data_device=data_device)
+                  image_name=info.image_name, uid=info.uid, data_device=data_device, gt_mask=gt_mask)

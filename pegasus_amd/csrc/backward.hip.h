@@ -5,7 +5,8 @@
 //
 //   composite_backward_block_kernel  one wave per 4x4-pixel block, four list entries per step (below): the ten
 //       per-Gaussian partial gradients of an entry are summed over the block's pixels and land as one 10-lane float
-//       atomic on the Gaussian's row.
+//       atomic on the Gaussian's row.  An optional dL/dalpha [H,W] (alpha = 1 - final_T, the accumulated opacity) adds
+//       g_alpha T_final / (1 - alpha_i) to the opacity-side gradient of every blended entry i (pgr_backward_ex).
 //   preprocess_backward_kernel      one thread per Gaussian: conic -> cov2D -> (cov3D, view-space mean) ->
 //       scale / rotation; projection; SH -> coefficients and view direction.
 //   composite_backward_batch_kernel, preprocess_backward_batch_kernel  the backward of a pgr_forward_batch call
@@ -37,10 +38,15 @@ constexpr int GRAD_ROW = 12;
 // 640-byte LDS transpose that also lines the 4 x 10 totals up for ONE atomic instruction).
 // The walk of one block (`item` = 4 * tile + quarter of the view, block = blockIdx.x & 3 inside the quarter); the single-view
 // and the batch kernel below differ only in where the view's lists, camera and images come from.
+// ALPHA: the walk takes a dL/dalpha image (g_alpha, which may still be NULL).  The alpha term keeps one more register live
+// over the walk, and at 73 VGPRs the batch kernel drops from 7 to 6 waves per SIMD, so the launches without one use the
+// ALPHA = false instance: the walk as it was before the term existed, instruction for instruction.
+template <bool ALPHA>
 __device__ __forceinline__ void composite_backward_block(
     const CameraDev* __restrict__ camp, const uint2* __restrict__ ranges, const uint32_t* __restrict__ gauss_sorted,
     const float4* __restrict__ splats, const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
-    const float* __restrict__ g_color, const float* __restrict__ g_depth, float* __restrict__ g_rows, uint32_t item) {
+    const float* __restrict__ g_color, const float* __restrict__ g_depth, const float* __restrict__ g_alpha,
+    float* __restrict__ g_rows, uint32_t item) {
     const CameraDev& cam = *camp;
     const int W = cam.width, H = cam.height;
     const int tile = (int)(item >> 2), quarter = (int)(item & 3), sub = (int)(blockIdx.x & 3);
@@ -63,6 +69,8 @@ __device__ __forceinline__ void composite_backward_block(
         S[c] = T * cam.bg[c];
     }
     const float gD = (inside && g_depth) ? g_depth[pix] : 0.0f;
+    // alpha = 1 - T_final, dalpha/dalpha_i = T_final / (1 - alpha_i): the FORWARD's final T (the walk overwrites T) times r
+    const float gAT = (ALPHA && inside && g_alpha) ? g_alpha[pix] * T : 0.0f;
     float SD = 0.0f;
     uint32_t n_used = last;
 #pragma unroll
@@ -167,6 +175,7 @@ __device__ __forceinline__ void composite_backward_block(
                     acc[6 + c] = w * gC[c];
                 }
                 dL_dalpha += gD * (Tin * z - (SD + (cinc[3] - cin[3])) * r);
+                if constexpr (ALPHA) dL_dalpha += gAT * r;
                 acc[9] = w * gD;
                 acc[5] = G * dL_dalpha;
                 const float dLp = G * op * dL_dalpha;    // dL/dpower
@@ -213,14 +222,16 @@ __device__ __forceinline__ void composite_backward_block(
     }
 }
 
+template <bool ALPHA>
 __global__ __launch_bounds__(WAVE) void composite_backward_block_kernel(
     const CameraDev* __restrict__ camp, const uint2* __restrict__ ranges, const uint32_t* __restrict__ gauss_sorted,
     const float4* __restrict__ splats, const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
-    const float* __restrict__ g_color, const float* __restrict__ g_depth, float* __restrict__ g_rows,
-    const uint32_t* __restrict__ work_order) {
+    const float* __restrict__ g_color, const float* __restrict__ g_depth, const float* __restrict__ g_alpha,
+    float* __restrict__ g_rows, const uint32_t* __restrict__ work_order) {
     const uint32_t item = work_order ? work_order[blockIdx.x >> 2] : (blockIdx.x >> 2);
     if (item == INVALID_ITEM) return;
-    composite_backward_block(camp, ranges, gauss_sorted, splats, final_T, n_contrib, g_color, g_depth, g_rows, item);
+    composite_backward_block<ALPHA>(camp, ranges, gauss_sorted, splats, final_T, n_contrib, g_color, g_depth, g_alpha,
+                                    g_rows, item);
 }
 
 // ---- batch backward (pgr_backward_batch): the backward of a pgr_forward_batch call -------------------------------------
@@ -239,7 +250,9 @@ struct alignas(16) BwdViewDev {
     const uint32_t* n_contrib;   // [H,W]
     const int32_t* radii;        // [n]
     float* rows;                 // [n, GRAD_ROW]
+    const float* g_alpha;        // [H,W] or NULL: dL/dalpha, alpha = 1 - final_T
 };
+static_assert(sizeof(BwdViewDev) == 96, "BWD_TABLE_CHUNK sizes the table launch's kernel arguments by 96-byte entries");
 constexpr int BWD_TABLE_CHUNK = 16;            // views per table launch (kernel arguments: 16 x 96 bytes)
 struct BwdTableChunk { BwdViewDev v[BWD_TABLE_CHUNK]; };
 __global__ __launch_bounds__(64) void backward_table_kernel(BwdTableChunk chunk, int count, BwdViewDev* __restrict__ out) {
@@ -252,6 +265,7 @@ __global__ __launch_bounds__(64) void backward_table_kernel(BwdTableChunk chunk,
 // The compositor backward of EVERY view in one launch: the forward's interleaved work order (item = view * items_per_view +
 // 4 * tile + quarter, as composite_quarter_kernel reads it), so no view waits on its own slowest tile -- the single-view
 // launch lasts as long as its longest wave.
+template <bool ALPHA>
 __global__ __launch_bounds__(WAVE) void composite_backward_batch_kernel(const BwdViewDev* __restrict__ views,
                                                                         uint32_t n_views, uint32_t items_per_view,
                                                                         const uint32_t* __restrict__ work_order) {
@@ -262,8 +276,8 @@ __global__ __launch_bounds__(WAVE) void composite_backward_batch_kernel(const Bw
     item -= view * items_per_view;
     const BwdViewDev& bv = views[view];
     if (bv.counters[1]) return;
-    composite_backward_block(bv.cam, bv.ranges, bv.gauss_sorted, bv.splats, bv.final_T, bv.n_contrib, bv.g_color, bv.g_depth,
-                             bv.rows, item);
+    composite_backward_block<ALPHA>(bv.cam, bv.ranges, bv.gauss_sorted, bv.splats, bv.final_T, bv.n_contrib, bv.g_color,
+                                    bv.g_depth, bv.g_alpha, bv.rows, item);
 }
 
 struct GradOut {

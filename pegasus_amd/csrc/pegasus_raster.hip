@@ -712,6 +712,14 @@ int32_t pgr_backward(const PgrScene* scene, const PgrCamera* cam, const float* g
                      const float* final_T, const uint32_t* n_contrib, const int32_t* radii, void* workspace,
                      size_t workspace_bytes, int64_t max_instances, const PgrGradOutputs* grads, float* grad_rows,
                      void* stream_v) {
+    return pgr_backward_ex(scene, cam, grad_color, grad_depth, nullptr, final_T, n_contrib, radii, workspace,
+                           workspace_bytes, max_instances, grads, grad_rows, stream_v);
+}
+
+int32_t pgr_backward_ex(const PgrScene* scene, const PgrCamera* cam, const float* grad_color, const float* grad_depth,
+                        const float* grad_alpha, const float* final_T, const uint32_t* n_contrib, const int32_t* radii,
+                        void* workspace, size_t workspace_bytes, int64_t max_instances, const PgrGradOutputs* grads,
+                        float* grad_rows, void* stream_v) {
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     if (int rc = check_scene(scene)) return rc;
     if (scene->shs_rest) return PGR_ERR_INVALID_ARGUMENT;      // the SH gradient is one [n,sh_stride,3] array
@@ -729,8 +737,10 @@ int32_t pgr_backward(const PgrScene* scene, const PgrCamera* cam, const float* g
     if (!hip_ok(hipMemsetAsync(grad_rows, 0, (size_t)N * GRAD_ROW * sizeof(float), stream), "memset grad rows"))
         return PGR_ERR_LAUNCH_FAILURE;
     // the forward's work order is still in the workspace (one view: item = 4 * tile + quarter)
-    composite_backward_block_kernel<<<4u * (uint32_t)B.order_slots, WAVE, 0, stream>>>(
-        camd, vw.ranges, vw.gauss_sorted, vw.splats, final_T, n_contrib, grad_color, grad_depth, grad_rows,
+    // (the instance without the alpha term when there is no dL/dalpha: backward.hip.h, composite_backward_block)
+    auto* walk = grad_alpha ? composite_backward_block_kernel<true> : composite_backward_block_kernel<false>;
+    walk<<<4u * (uint32_t)B.order_slots, WAVE, 0, stream>>>(
+        camd, vw.ranges, vw.gauss_sorted, vw.splats, final_T, n_contrib, grad_color, grad_depth, grad_alpha, grad_rows,
         reinterpret_cast<const uint32_t*>(ws + B.work_order));
     const GradOut go{grads->means2d, grads->means3d, grads->opacities, grads->colors, grads->shs, grads->cov3d,
                      grads->scales, grads->rotations};
@@ -752,6 +762,14 @@ size_t pgr_backward_batch_scratch_bytes(int32_t n, int32_t n_views) {
 int32_t pgr_backward_batch(const PgrScene* scene, int32_t n_views, const PgrCamera* cameras, const PgrBackwardView* views,
                            void* workspace, size_t workspace_bytes, int64_t max_instances_per_view,
                            const PgrGradOutputs* grads, void* scratch, size_t scratch_bytes, void* stream_v) {
+    return pgr_backward_batch_ex(scene, n_views, cameras, views, nullptr, workspace, workspace_bytes,
+                                 max_instances_per_view, grads, scratch, scratch_bytes, stream_v);
+}
+
+int32_t pgr_backward_batch_ex(const PgrScene* scene, int32_t n_views, const PgrCamera* cameras,
+                              const PgrBackwardView* views, const float* const* grad_alpha, void* workspace,
+                              size_t workspace_bytes, int64_t max_instances_per_view, const PgrGradOutputs* grads,
+                              void* scratch, size_t scratch_bytes, void* stream_v) {
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     // every check before the first enqueue
     if (int rc = check_scene(scene)) return rc;
@@ -787,13 +805,17 @@ int32_t pgr_backward_batch(const PgrScene* scene, int32_t n_views, const PgrCame
             const ViewWs vw = carve(ws + B.views + (size_t)v * B.per_view, L);
             const PgrBackwardView& bv = views[v];
             chunk.v[k] = BwdViewDev{cams_dev + v, vw.ranges, vw.gauss_sorted, vw.splats, status_dev + 2 * v, bv.grad_color,
-                                    bv.grad_depth, bv.final_T, bv.n_contrib, bv.radii, rows + (size_t)v * N * GRAD_ROW};
+                                    bv.grad_depth, bv.final_T, bv.n_contrib, bv.radii, rows + (size_t)v * N * GRAD_ROW,
+                                    grad_alpha ? grad_alpha[v] : nullptr};
         }
         backward_table_kernel<<<1, 64, 0, stream>>>(chunk, cnt, table + v0);
     }
     if (!hip_ok(hipMemsetAsync(rows, 0, rows_bytes, stream), "memset grad rows")) return PGR_ERR_LAUNCH_FAILURE;
     // the forward's interleaved work order is still in the workspace: every (view, tile, quarter) item, four blocks each
-    composite_backward_batch_kernel<<<4u * (uint32_t)B.order_slots, WAVE, 0, stream>>>(
+    bool any_alpha = false;
+    for (int v = 0; grad_alpha && v < n_views; ++v) any_alpha = any_alpha || grad_alpha[v];
+    auto* walk = any_alpha ? composite_backward_batch_kernel<true> : composite_backward_batch_kernel<false>;
+    walk<<<4u * (uint32_t)B.order_slots, WAVE, 0, stream>>>(
         table, (uint32_t)n_views, ITEMS_PER_TILE * (uint32_t)L.tiles, reinterpret_cast<const uint32_t*>(ws + B.work_order));
     const GradOut go{grads->means2d, grads->means3d, grads->opacities, grads->colors, grads->shs, grads->cov3d,
                      grads->scales, grads->rotations};
@@ -1054,7 +1076,7 @@ int32_t pgr_knn_mean_dist2(int32_t n, const float* xyz, float* out, void* worksp
 
 // ---- training step: fused L1 + D-SSIM loss, Adam over all parameter groups, densification statistics (train.hip.h) ------
 namespace {
-struct LossLayout { size_t a, b, c, partial, total; int tiles_x, tiles_y; };
+struct LossLayout { size_t a, b, c, partial, total, partial_a, total_masked; int tiles_x, tiles_y; };
 LossLayout loss_layout(int32_t height, int32_t width) {
     LossLayout L{};
     L.tiles_x = (width + LOSS_TILE - 1) / LOSS_TILE;
@@ -1067,6 +1089,8 @@ LossLayout loss_layout(int32_t height, int32_t width) {
     L.c = take(map);
     L.partial = take((size_t)3 * L.tiles_x * L.tiles_y * 2 * sizeof(double));
     L.total = off;
+    L.partial_a = take((size_t)L.tiles_x * L.tiles_y * sizeof(double));      // the masked loss's alpha partials
+    L.total_masked = off;
     return L;
 }
 LossWindow ssim_window() {
@@ -1076,6 +1100,11 @@ LossWindow ssim_window() {
     for (int k = 0; k <= 2 * LOSS_R; ++k) w.w[k] = (float)(g[k] / sum);
     return w;
 }
+// the three launches of pgr_image_loss / pgr_image_loss_masked (arguments checked by the callers)
+int32_t image_loss_launch(const LossLayout& L, const float* x, const float* y, const float* mask, const float* bg,
+                          const float* alpha, int32_t height, int32_t width, double lambda_dssim, double lambda_alpha,
+                          float* out3, float* out_a, float* grad, float* grad_alpha, void* workspace,
+                          hipStream_t stream);
 }  // namespace
 
 size_t pgr_image_loss_workspace_bytes(int32_t height, int32_t width) {
@@ -1089,7 +1118,33 @@ int32_t pgr_image_loss(const float* x, const float* y, int32_t height, int32_t w
     if ((int64_t)height * width > (int64_t)1 << 28) return PGR_ERR_INVALID_ARGUMENT;
     const LossLayout L = loss_layout(height, width);
     if (workspace_bytes < L.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    return image_loss_launch(L, x, y, nullptr, nullptr, nullptr, height, width, lambda_dssim, 0.0, out3, nullptr, grad,
+                             nullptr, workspace, static_cast<hipStream_t>(stream_v));
+}
+
+size_t pgr_image_loss_masked_workspace_bytes(int32_t height, int32_t width) {
+    return (height <= 0 || width <= 0) ? 0 : loss_layout(height, width).total_masked;
+}
+
+int32_t pgr_image_loss_masked(const float* x, const float* y, const float* mask, const float* bg, const float* alpha,
+                              int32_t height, int32_t width, double lambda_dssim, double lambda_alpha, float* out4,
+                              float* grad, float* grad_alpha, void* workspace, size_t workspace_bytes, void* stream_v) {
+    if (height <= 0 || width <= 0 || !x || !y || !out4 || !workspace) return PGR_ERR_INVALID_ARGUMENT;
+    if (!(lambda_dssim >= 0.0 && lambda_dssim <= 1.0) || !(lambda_alpha >= 0.0)) return PGR_ERR_INVALID_ARGUMENT;
+    if ((int64_t)height * width > (int64_t)1 << 28) return PGR_ERR_INVALID_ARGUMENT;
+    if ((mask && !bg) || (alpha && !mask) || (lambda_alpha > 0.0 && !alpha) || (grad_alpha && !alpha))
+        return PGR_ERR_INVALID_ARGUMENT;
+    const LossLayout L = loss_layout(height, width);
+    if (workspace_bytes < L.total_masked) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    return image_loss_launch(L, x, y, mask, bg, alpha, height, width, lambda_dssim, lambda_alpha, out4, out4 + 3, grad,
+                             grad_alpha, workspace, static_cast<hipStream_t>(stream_v));
+}
+
+namespace {
+int32_t image_loss_launch(const LossLayout& L, const float* x, const float* y, const float* mask, const float* bg,
+                          const float* alpha, int32_t height, int32_t width, double lambda_dssim, double lambda_alpha,
+                          float* out3, float* out_a, float* grad, float* grad_alpha, void* workspace,
+                          hipStream_t stream) {
     char* ws = static_cast<char*>(workspace);
     auto* A = reinterpret_cast<float*>(ws + L.a);
     auto* B = reinterpret_cast<float*>(ws + L.b);
@@ -1099,13 +1154,18 @@ int32_t pgr_image_loss(const float* x, const float* y, int32_t height, int32_t w
     const dim3 grid(L.tiles_x, L.tiles_y, 3);
     const int n_blocks = 3 * L.tiles_x * L.tiles_y;
     const double n_values = 3.0 * (double)height * (double)width;
-    loss_ssim_kernel<<<grid, 256, 0, stream>>>(x, y, height, width, win, A, B, Cm, partial);
+    const double n_pix = (double)height * (double)width;
+    auto* partial_a = alpha ? reinterpret_cast<double*>(ws + L.partial_a) : nullptr;
+    loss_ssim_kernel<<<grid, 256, 0, stream>>>(x, y, height, width, win, A, B, Cm, partial, mask, bg, alpha,
+                                               (float)(lambda_alpha / n_pix), grad_alpha, partial_a);
     if (grad)
         loss_grad_kernel<<<grid, 256, 0, stream>>>(x, y, height, width, win, A, B, Cm, (float)(-lambda_dssim / n_values),
-                                                   (float)((1.0 - lambda_dssim) / n_values), grad);
-    loss_reduce_kernel<<<1, 256, 0, stream>>>(partial, n_blocks, 1.0 / n_values, lambda_dssim, out3);
+                                                   (float)((1.0 - lambda_dssim) / n_values), grad, mask, bg);
+    loss_reduce_kernel<<<1, 256, 0, stream>>>(partial, n_blocks, 1.0 / n_values, lambda_dssim, out3, partial_a,
+                                              L.tiles_x * L.tiles_y, 1.0 / n_pix, lambda_alpha, out_a);
     return hip_ok(hipGetLastError(), "image loss launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
 }
+}  // namespace
 
 int32_t pgr_adam_step(const PgrAdamGroup* groups, int32_t n_groups, double beta1, double beta2, double eps,
                       void* stream_v) {

@@ -1,5 +1,6 @@
 // train.hip.h -- the per-iteration kernels of a 3DGS training step that are not the rasterizer itself:
 //   pgr_image_loss     fused L1 + D-SSIM over a [3,H,W] image: the value and dloss/dx in one call (three launches)
+//   pgr_image_loss_masked  the same kernels against a masked target, plus an alpha term (below)
 //   pgr_adam_step      torch.optim.Adam's single-tensor arithmetic for every parameter group in one launch
 //   pgr_densify_stats  the densification statistics of one render (gradient norm, visit count, largest screen radius)
 //
@@ -11,6 +12,11 @@
 // Pass A blurs the five moment maps of a 16x16 tile from a 26x26 halo in LDS and stores A, B, C and one partial sum per
 // workgroup; pass B blurs A, B, C the same way and writes the gradient; pass C sums the partials in a fixed order
 // (doubles, no atomics: the loss value is the same on every run).
+//
+// Masked form (pgr_image_loss_masked): with a mask m [H,W], a background bg [3] and the rendered alpha a [H,W], the target
+// is y' = y m + bg (1 - m), formed where y is read (the halo load, and the gradient pass), so no [3,H,W] target is
+// written; loss += lambda_a mean|a - m|, whose gradient sign(a - m) lambda_a / (H W) pass A writes, and whose sum is one
+// more partial per channel-0 workgroup, reduced in pass C in a fixed order.  A NULL mask is the unmasked path unchanged.
 //
 // The partials are written so that x == y gives s == 1, A == 0 and 2x blur(B) + y blur(C) == 0 exactly (every term pair
 // is formed by the same operations up to exact factors of two): the loss and gradient of identical images are zero.
@@ -27,13 +33,22 @@ constexpr float SSIM_C2 = 0.03f * 0.03f;
 
 struct LossWindow { float w[2 * LOSS_R + 1]; };
 
-// loads the 26x26 halo of `src` (channel plane, zero outside the image) around the tile at (tx0, ty0)
+// the masked loss target y' = y m + bg (1 - m) of one value
+__device__ __forceinline__ float masked_target(float y, float m, float bg) { return fmaf(y, m, bg * (1.0f - m)); }
+
+// loads the 26x26 halo of `src` (channel plane, zero outside the image) around the tile at (tx0, ty0); with a mask
+// [H,W], the masked target of src over the background value bg
 __device__ __forceinline__ void loss_load_halo(float (*dst)[LOSS_HALO + 1], const float* __restrict__ src, int H, int W,
-                                               int tx0, int ty0) {
+                                               int tx0, int ty0, const float* __restrict__ mask = nullptr,
+                                               float bg = 0.0f) {
     for (int i = threadIdx.x; i < LOSS_HALO * LOSS_HALO; i += blockDim.x) {
         const int r = i / LOSS_HALO, q = i - r * LOSS_HALO;
         const int gy = ty0 - LOSS_R + r, gx = tx0 - LOSS_R + q;
-        dst[r][q] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? gload(src + (size_t)gy * W + gx) : 0.0f;
+        const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
+        const size_t o = in ? (size_t)gy * W + gx : 0;
+        float v = in ? gload(src + o) : 0.0f;
+        if (mask && in) v = masked_target(v, gload(mask + o), bg);
+        dst[r][q] = v;
     }
 }
 
@@ -47,18 +62,22 @@ __device__ double block_sum_256(double v, double* red) {
     return red[0];
 }
 
-// grid (tiles_x, tiles_y, 3), 256 threads
+// grid (tiles_x, tiles_y, 3), 256 threads.  mask / bg: the masked target (NULL: y); alpha: the alpha term, summed by the
+// channel-0 workgroups into partial_a[tile] (grad_alpha, if not NULL, = coef_a sign(a - m)).
 __global__ __launch_bounds__(256) void loss_ssim_kernel(const float* __restrict__ x, const float* __restrict__ y, int H,
                                                         int W, LossWindow win, float* __restrict__ mapA,
                                                         float* __restrict__ mapB, float* __restrict__ mapC,
-                                                        double* __restrict__ partial) {
+                                                        double* __restrict__ partial, const float* __restrict__ mask,
+                                                        const float* __restrict__ bg, const float* __restrict__ alpha,
+                                                        float coef_a, float* __restrict__ grad_alpha,
+                                                        double* __restrict__ partial_a) {
     __shared__ float sx[LOSS_HALO][LOSS_HALO + 1], sy[LOSS_HALO][LOSS_HALO + 1];
     __shared__ float hb[5][LOSS_HALO][LOSS_TILE + 1];
     __shared__ double red[256];
     const int c = blockIdx.z, tx0 = blockIdx.x * LOSS_TILE, ty0 = blockIdx.y * LOSS_TILE;
     const size_t plane = (size_t)H * W;
     loss_load_halo(sx, x + c * plane, H, W, tx0, ty0);
-    loss_load_halo(sy, y + c * plane, H, W, tx0, ty0);
+    loss_load_halo(sy, y + c * plane, H, W, tx0, ty0, mask, mask ? bg[c] : 0.0f);
     __syncthreads();
     // horizontal pass: 26 rows x 16 columns of the five moment maps
     for (int i = threadIdx.x; i < LOSS_HALO * LOSS_TILE; i += blockDim.x) {
@@ -115,13 +134,26 @@ __global__ __launch_bounds__(256) void loss_ssim_kernel(const float* __restrict_
         partial[2 * bid] = l1_total;
         partial[2 * bid + 1] = s_total;
     }
+    if (alpha && c == 0) {                 // (uniform over the workgroup)
+        double a_sum = 0.0;
+        if (gy < H && gx < W) {
+            const size_t o = (size_t)gy * W + gx;
+            const float d = gload(alpha + o) - gload(mask + o);
+            a_sum = (double)fabsf(d);
+            if (grad_alpha) gstore(grad_alpha + o, coef_a * (d > 0.f ? 1.0f : (d < 0.f ? -1.0f : 0.0f)));
+        }
+        __syncthreads();
+        const double a_total = block_sum_256(a_sum, red);
+        if (threadIdx.x == 0) partial_a[blockIdx.y * gridDim.x + blockIdx.x] = a_total;
+    }
 }
 
 // grid (tiles_x, tiles_y, 3), 256 threads: grad = coef_s (blur(A) + 2x blur(B) + y blur(C)) + coef_l1 sign(x - y)
 __global__ __launch_bounds__(256) void loss_grad_kernel(const float* __restrict__ x, const float* __restrict__ y, int H,
                                                         int W, LossWindow win, const float* __restrict__ mapA,
                                                         const float* __restrict__ mapB, const float* __restrict__ mapC,
-                                                        float coef_s, float coef_l1, float* __restrict__ grad) {
+                                                        float coef_s, float coef_l1, float* __restrict__ grad,
+                                                        const float* __restrict__ mask, const float* __restrict__ bg) {
     __shared__ float sm[3][LOSS_HALO][LOSS_HALO + 1];
     __shared__ float hb[3][LOSS_HALO][LOSS_TILE + 1];
     const int c = blockIdx.z, tx0 = blockIdx.x * LOSS_TILE, ty0 = blockIdx.y * LOSS_TILE;
@@ -155,16 +187,21 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(const float* __restrict_
         bC = fmaf(w, hb[2][ly + k][lx], bC);
     }
     const size_t o = c * plane + (size_t)gy * W + gx;
-    const float xv = gload(x + o), yv = gload(y + o);
+    const float xv = gload(x + o);
+    float yv = gload(y + o);
+    if (mask) yv = masked_target(yv, gload(mask + (size_t)gy * W + gx), bg[c]);
     const float d = xv - yv;
     const float sgn = d > 0.f ? 1.0f : (d < 0.f ? -1.0f : 0.0f);
     const float g_ssim = (bA + (2.0f * xv) * bB) + yv * bC;
     gstore(grad + o, coef_s * g_ssim + coef_l1 * sgn);
 }
 
-// one workgroup of 256: the partials in a fixed order -> out[0] loss, out[1] mean |x-y|, out[2] mean SSIM
+// one workgroup of 256: the partials in a fixed order -> out[0] loss, out[1] mean |x-y|, out[2] mean SSIM; with partial_a
+// (n_a tiles) out[0] += lambda_a mean|a-m| and out_a = mean|a-m|; out_a without partial_a: 0
 __global__ __launch_bounds__(256) void loss_reduce_kernel(const double* __restrict__ partial, int n_blocks, double inv_n,
-                                                          double lambda, float* __restrict__ out) {
+                                                          double lambda, float* __restrict__ out,
+                                                          const double* __restrict__ partial_a, int n_a, double inv_hw,
+                                                          double lambda_a, float* __restrict__ out_a) {
     __shared__ double red[256];
     double a = 0.0, b = 0.0;
     for (int i = threadIdx.x; i < n_blocks; i += blockDim.x) {
@@ -174,10 +211,20 @@ __global__ __launch_bounds__(256) void loss_reduce_kernel(const double* __restri
     const double l1 = block_sum_256(a, red) * inv_n;
     __syncthreads();
     const double ss = block_sum_256(b, red) * inv_n;
+    double loss = (1.0 - lambda) * l1 + lambda * (1.0 - ss);
+    double am = 0.0;
+    if (partial_a) {
+        double s = 0.0;
+        for (int i = threadIdx.x; i < n_a; i += blockDim.x) s += partial_a[i];
+        __syncthreads();
+        am = block_sum_256(s, red) * inv_hw;
+        loss += lambda_a * am;
+    }
     if (threadIdx.x == 0) {
-        out[0] = (float)((1.0 - lambda) * l1 + lambda * (1.0 - ss));
+        out[0] = (float)loss;
         out[1] = (float)l1;
         out[2] = (float)ss;
+        if (out_a) *out_a = (float)am;
     }
 }
 

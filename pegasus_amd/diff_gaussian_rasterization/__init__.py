@@ -7,8 +7,8 @@ Same surface as the module the reference installs from its (absent) submodule
     GaussianRasterizationSettings(image_height, image_width, tanfovx, tanfovy, bg, scale_modifier,
                                   viewmatrix, projmatrix, sh_degree, campos, prefiltered, debug)
     GaussianRasterizer(raster_settings)(means3D, means2D, opacities, shs=None, colors_precomp=None,
-                                        scales=None, rotations=None, cov3D_precomp=None)
-        -> (color[3,H,W], radii[N] int32, depth[1,H,W])
+                                        scales=None, rotations=None, cov3D_precomp=None, return_alpha=False)
+        -> (color[3,H,W], radii[N] int32, depth[1,H,W])  (+ alpha[1,H,W] = 1 - final_T with return_alpha)
     GaussianRasterizer.markVisible(positions) -> bool[N]
 
 The compute is libpegasus_raster.so (hand-written HIP for gfx950) reached through its C ABI
@@ -27,7 +27,7 @@ from .. import _lib, rasterizer
 from ..rasterizer import dev_f32 as _dev_f32, _ptr
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "rasterize_gaussians_batch",
-           "last_forward_info"]
+           "last_forward_info", "alpha_from_final_T"]
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -47,6 +47,11 @@ class GaussianRasterizationSettings(NamedTuple):
 
 def last_forward_info() -> dict:
     return rasterizer.last_forward_info()
+
+
+def alpha_from_final_T(final_T: torch.Tensor) -> torch.Tensor:
+    """The accumulated opacity of a render, [..., 1, H, W] from the forward's final transmittance [..., H, W]."""
+    return (1.0 - final_T).unsqueeze(-3)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -95,11 +100,14 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     Every tensor the backward re-reads goes through ``ctx.save_for_backward``: an in-place update of means, scales,
     rotations, opacities or SH between forward and backward trips autograd's version-counter check instead of
-    silently pairing new parameter values with the forward's lists, final_T and n_contrib."""
+    silently pairing new parameter values with the forward's lists, final_T and n_contrib.
+
+    With ``return_alpha`` a fourth output, alpha [1,H,W] = 1 - final_T, is differentiable: its gradient reaches
+    pgr_backward_ex as grad_alpha (NULL when it got none)."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings):
+                raster_settings, return_alpha=False):
         L = _lib.lib()
         rs = raster_settings
         device = means3D.device
@@ -143,10 +151,14 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.op_shape = tuple(opacities.shape)
         ctx.save_for_backward(*(t[k] for k in ctx.present), ws, radii, final_T, n_contrib)
         ctx.mark_non_differentiable(radii)
+        if return_alpha:
+            # an output without a gradient then comes to backward as None (no zero image, no load of one)
+            ctx.set_materialize_grads(False)
+            return color, radii, depth, alpha_from_final_T(final_T)
         return color, radii, depth
 
     @staticmethod
-    def backward(ctx, grad_color, _grad_radii, grad_depth):
+    def backward(ctx, grad_color, _grad_radii, grad_depth, grad_alpha=None):
         L = _lib.lib()
         rs, n = ctx.rs, ctx.n
         saved = ctx.saved_tensors          # raises if an input was modified in place since the forward
@@ -178,17 +190,19 @@ class _RasterizeGaussians(torch.autograd.Function):
         cam = _lib.PgrCamera(image_width=W, image_height=H, tanfovx=float(rs.tanfovx), tanfovy=float(rs.tanfovy),
                              viewmatrix=_ptr(t["view"]), projmatrix=_ptr(t["proj"]), campos=_ptr(t["campos"]),
                              bg=_ptr(t["bg"]))
-        gc = grad_color.contiguous().float()
+        gc = (torch.zeros((3, H, W), dtype=torch.float32, device=device) if grad_color is None
+              else grad_color.contiguous().float())
         gd = None if grad_depth is None else grad_depth.contiguous().float()
+        ga = None if grad_alpha is None else grad_alpha.contiguous().float()
         rows = torch.empty((n, 12), dtype=torch.float32, device=device)
         with torch.cuda.device(device):
-            _lib.check(L.pgr_backward(C.byref(scene), C.byref(cam), _ptr(gc), _ptr(gd), _ptr(final_T), _ptr(n_contrib),
-                                      _ptr(radii), C.c_void_p(ws.data_ptr()), ws.numel(), ctx.max_inst,
-                                      C.byref(grads), _ptr(rows),
-                                      C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "pgr_backward")
-        # means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings
+            _lib.check(L.pgr_backward_ex(C.byref(scene), C.byref(cam), _ptr(gc), _ptr(gd), _ptr(ga), _ptr(final_T),
+                                         _ptr(n_contrib), _ptr(radii), C.c_void_p(ws.data_ptr()), ws.numel(), ctx.max_inst,
+                                         C.byref(grads), _ptr(rows),
+                                         C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "pgr_backward_ex")
+        # means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, return_alpha
         return (g["means3d"], g["means2d"], g.get("shs"), g.get("colors"), g["opacities"].view(ctx.op_shape),
-                g.get("scales"), g.get("rotations"), g.get("cov3d"), None)
+                g.get("scales"), g.get("rotations"), g.get("cov3d"), None, None)
 
 
 def _scene_struct(t, n, sh_degree, scale_modifier):
@@ -209,10 +223,12 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
     receives every view's own screen-space gradient.
 
     The contract of _RasterizeGaussians: the call owns its workspace, retries an instance overflow with a grown capacity, and
-    saves every tensor the backward re-reads, so an in-place edit of an input between forward and backward raises."""
+    saves every tensor the backward re-reads, so an in-place edit of an input between forward and backward raises.
+    With ``return_alpha`` a fourth output, alpha [V,1,H,W] = 1 - final_T, is differentiable (pgr_backward_batch_ex)."""
 
     @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings):
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings,
+                return_alpha=False):
         L = _lib.lib()
         settings = tuple(settings)
         V = len(settings)
@@ -264,10 +280,13 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         ctx.op_shape = tuple(opacities.shape)
         ctx.save_for_backward(*(t[k] for k in ctx.present), ws, radii, final_T, n_contrib)
         ctx.mark_non_differentiable(radii)
+        if return_alpha:
+            ctx.set_materialize_grads(False)
+            return color, radii, depth, alpha_from_final_T(final_T)
         return color, radii, depth
 
     @staticmethod
-    def backward(ctx, grad_color, _grad_radii, grad_depth):
+    def backward(ctx, grad_color, _grad_radii, grad_depth, grad_alpha=None):
         L = _lib.lib()
         V, n, (H, W) = ctx.V, ctx.n, ctx.hw
         saved = ctx.saved_tensors          # raises if an input was modified in place since the forward
@@ -292,27 +311,31 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         grads = _lib.PgrGradOutputs(**{key: _ptr(v) for key, v in g.items()})
         scene = _scene_struct(t, n, ctx.sh_degree, ctx.scale_modifier)
         cams = (_lib.PgrCamera * V)(*[_lib.PgrCamera(image_width=W, image_height=H) for _ in range(V)])
-        gc = grad_color.contiguous().float()
+        gc = (torch.zeros((V, 3, H, W), dtype=torch.float32, device=device) if grad_color is None
+              else grad_color.contiguous().float())
         gd = None if grad_depth is None else grad_depth.contiguous().float()
+        ga = None if grad_alpha is None else grad_alpha.contiguous().float()
+        alpha_ptrs = None if ga is None else (C.c_void_p * V)(*[ga[v].data_ptr() for v in range(V)])
         views = (_lib.PgrBackwardView * V)(*[
             _lib.PgrBackwardView(grad_color=_ptr(gc[v]), grad_depth=None if gd is None else _ptr(gd[v]),
                                  final_T=_ptr(final_T[v]), n_contrib=_ptr(n_contrib[v]), radii=_ptr(radii[v]))
             for v in range(V)])
         scratch = torch.empty(max(1, L.pgr_backward_batch_scratch_bytes(n, V)), dtype=torch.uint8, device=device)
         with torch.cuda.device(device):
-            _lib.check(L.pgr_backward_batch(C.byref(scene), V, cams, views, C.c_void_p(ws.data_ptr()), ws.numel(),
-                                            ctx.max_inst, C.byref(grads), C.c_void_p(scratch.data_ptr()), scratch.numel(),
-                                            C.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
-                       "pgr_backward_batch")
-        # means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings
+            _lib.check(L.pgr_backward_batch_ex(C.byref(scene), V, cams, views, alpha_ptrs, C.c_void_p(ws.data_ptr()),
+                                               ws.numel(), ctx.max_inst, C.byref(grads), C.c_void_p(scratch.data_ptr()),
+                                               scratch.numel(), C.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
+                       "pgr_backward_batch_ex")
+        # means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, return_alpha
         return (g["means3d"], g["means2d"], g.get("shs"), g.get("colors"), g["opacities"].view(ctx.op_shape),
-                g.get("scales"), g.get("rotations"), g.get("cov3d"), None)
+                g.get("scales"), g.get("rotations"), g.get("cov3d"), None, None)
 
 
 def rasterize_gaussians_batch(means3D, means2D, opacities, raster_settings, shs=None, colors_precomp=None, scales=None,
-                              rotations=None, cov3D_precomp=None):
+                              rotations=None, cov3D_precomp=None, return_alpha=False):
     """Differentiable render of V views of one scene: ``raster_settings`` is a sequence of V
-    GaussianRasterizationSettings with one image size.  Returns (color [V,3,H,W], radii [V,n] int32, depth [V,1,H,W]).
+    GaussianRasterizationSettings with one image size.  Returns (color [V,3,H,W], radii [V,n] int32, depth [V,1,H,W]), and
+    with ``return_alpha`` also alpha [V,1,H,W] = 1 - final_T (differentiable).
     ``means2D`` (or None) is [V,n,3]; its .grad receives each view's screen-space gradient.  Every other input's gradient
     is the sum over the views."""
     if (shs is None) == (colors_precomp is None):
@@ -324,7 +347,7 @@ def rasterize_gaussians_batch(means3D, means2D, opacities, raster_settings, shs=
     if means2D is None:
         means2D = torch.zeros((len(settings), int(means3D.shape[0]), 3), dtype=torch.float32, device=means3D.device)
     return _RasterizeGaussiansBatch.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                          cov3D_precomp, settings)
+                                          cov3D_precomp, settings, bool(return_alpha))
 
 
 class GaussianRasterizer(nn.Module):
@@ -351,7 +374,9 @@ class GaussianRasterizer(nn.Module):
             return present.bool()
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None):
+                cov3D_precomp=None, return_alpha=False):
+        """(color, radii, depth), or (color, radii, depth, alpha) with ``return_alpha``: alpha [1,H,W] = 1 - final_T, the
+        accumulated opacity, differentiable like the colour."""
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
@@ -362,7 +387,12 @@ class GaussianRasterizer(nn.Module):
             if means2D is None:
                 means2D = torch.zeros_like(means3D, requires_grad=False)
             return _RasterizeGaussians.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                             cov3D_precomp, self.raster_settings)
+                                             cov3D_precomp, self.raster_settings, bool(return_alpha))
         with torch.no_grad():
+            if return_alpha:
+                color, radii, depth, final_T, _ = rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities,
+                                                                      scales, rotations, cov3D_precomp,
+                                                                      self.raster_settings, want_aux=True)
+                return color, radii, depth, alpha_from_final_T(final_T)
             return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                        cov3D_precomp, self.raster_settings)

@@ -15,8 +15,8 @@ import weakref
 
 import torch
 
-from .diff_gaussian_rasterization import (GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians,
-                                          rasterize_gaussians_batch)
+from .diff_gaussian_rasterization import (GaussianRasterizationSettings, GaussianRasterizer, alpha_from_final_T,
+                                          rasterize_gaussians, rasterize_gaussians_batch)
 from .sh_utils import sh_basis
 
 # ---- activated parameters of a model, kept while the model does not change ------------------------------------------------
@@ -140,8 +140,11 @@ def _colour(pc, pipe, cam, override_color) -> dict:
     return dict(colors_precomp=(rgb + 0.5).clamp_min(0.0))
 
 
-def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None):
-    """Render the scene ``pc`` (a GaussianModel) from ``viewpoint_camera``.  ``bg_color`` must be on the GPU."""
+def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
+           return_alpha=False):
+    """Render the scene ``pc`` (a GaussianModel) from ``viewpoint_camera``.  ``bg_color`` must be on the GPU.
+    ``return_alpha``: the dict also holds "alpha" [1,H,W] = 1 - final_T, the accumulated opacity (differentiable when
+    autograd is on; training against object masks)."""
     xyz = pc.get_xyz
     # "viewspace_points": a zero tensor shaped like the means whose .grad receives the screen-space (NDC-scaled) gradient
     # of the 2D means -- training-style callers read it for densification.  A leaf that asks for a gradient only when
@@ -160,28 +163,38 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     inputs = dict(means3D=xyz, means2D=probe, opacities=kept_activation(pc, "get_opacity"),
                   **_colour(pc, pipe, viewpoint_camera, override_color), **_geometry(pc, pipe, scaling_modifier))
     if torch.is_grad_enabled():
-        image, radii, depth = GaussianRasterizer(raster_settings=settings)(**inputs)
+        out = GaussianRasterizer(raster_settings=settings)(**inputs, return_alpha=return_alpha)
+        image, radii, depth = out[:3]
     else:
         # the render loops (torch.no_grad(), pegasus.py:248): straight to the forward, without building an nn.Module per call
         # and going through its __call__ machinery (0.571 -> 0.553 ms per call on the 2 M-Gaussian scene: a single view
         # leaves the GPU idle between its kernels, so host microseconds are wall-clock microseconds)
         # "visibility_filter" is queued behind the compositor before the host waits for the call's status
         extra = {}
-        image, radii, depth = rasterize_gaussians(
+        out = rasterize_gaussians(
             inputs["means3D"], inputs["means2D"], inputs.get("shs"), inputs.get("colors_precomp"), inputs["opacities"],
-            inputs.get("scales"), inputs.get("rotations"), inputs.get("cov3D_precomp"), settings,
+            inputs.get("scales"), inputs.get("rotations"), inputs.get("cov3D_precomp"), settings, want_aux=return_alpha,
             after_enqueue=lambda r: extra.__setitem__("vis", r["radii"] > 0), sh_rest=inputs.get("shs_rest"))
-        return {"render": image, "depth": depth, "viewspace_points": probe, "visibility_filter": extra["vis"], "radii": radii}
-    return {"render": image, "depth": depth, "viewspace_points": probe, "visibility_filter": radii > 0, "radii": radii}
+        image, radii, depth = out[:3]
+        pkg = {"render": image, "depth": depth, "viewspace_points": probe, "visibility_filter": extra["vis"], "radii": radii}
+        if return_alpha:
+            pkg["alpha"] = alpha_from_final_T(out[3])
+        return pkg
+    pkg = {"render": image, "depth": depth, "viewspace_points": probe, "visibility_filter": radii > 0, "radii": radii}
+    if return_alpha:
+        pkg["alpha"] = out[3]
+    return pkg
 
 
-def render_batch(cameras, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None):
+def render_batch(cameras, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
+                 return_alpha=False):
     """Render ``pc`` from V cameras of one image size in one differentiable call (pgr_forward_batch; backward
     pgr_backward_batch): the training path's several views per optimiser step.  ``bg_color`` is [3] (every view) or [V,3]
     (one background per view).  Returns "render" [V,3,H,W], "depth" [V,1,H,W], "viewspace_points" [V,N,3] (a leaf whose
     .grad receives each view's own screen-space gradient when autograd is on), "visibility_filter" [V,N] (radii > 0) and
     "radii" [V,N].  Colours come from the kernel-evaluated SH (or ``override_color``, shared by every view);
-    pipe.compute_cov3D_python is honoured.  pipe.convert_SHs_python is refused: its colours differ per view."""
+    pipe.compute_cov3D_python is honoured.  pipe.convert_SHs_python is refused: its colours differ per view.
+    ``return_alpha``: also "alpha" [V,1,H,W] = 1 - final_T (differentiable)."""
     cameras = list(cameras)
     V = len(cameras)
     if V == 0:
@@ -202,6 +215,10 @@ def render_batch(cameras, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0
     probe = torch.zeros((V,) + tuple(xyz.shape), dtype=xyz.dtype, device=xyz.device, requires_grad=torch.is_grad_enabled())
     settings = [_view(cam, pc, pipe, bg, scaling_modifier) for cam, bg in zip(cameras, bgs)]
     colour = dict(colors_precomp=override_color) if override_color is not None else dict(shs=kept_activation(pc, "get_features"))
-    image, radii, depth = rasterize_gaussians_batch(xyz, probe, kept_activation(pc, "get_opacity"), settings, **colour,
-                                                    **_geometry(pc, pipe, scaling_modifier))
-    return {"render": image, "depth": depth, "viewspace_points": probe, "visibility_filter": radii > 0, "radii": radii}
+    out = rasterize_gaussians_batch(xyz, probe, kept_activation(pc, "get_opacity"), settings, **colour,
+                                    **_geometry(pc, pipe, scaling_modifier), return_alpha=return_alpha)
+    image, radii, depth = out[:3]
+    pkg = {"render": image, "depth": depth, "viewspace_points": probe, "visibility_filter": radii > 0, "radii": radii}
+    if return_alpha:
+        pkg["alpha"] = out[3]
+    return pkg

@@ -8,7 +8,12 @@ the 3DGS optimisation loop that PEGASUS's reconstruction scripts reach through t
 It reads a COLMAP dataset (pegasus_amd.colmap_io) and writes the model layout ``Scene(args, gaussians,
 load_iteration=-1)`` opens: cfg_args, cameras.json, input.ply, point_cloud/iteration_N/point_cloud.ply, chkpntN.pth.
 
-    python -m pegasus_amd.train -s <colmap dir> -m <output dir> [--iterations N] [--eval] [--batch_size B] ...
+    python -m pegasus_amd.train -s <colmap dir> -m <output dir> [--iterations N] [--eval] [--batch_size B]
+                                [--masks <mask dir> | --masks alpha] [--lambda_alpha L] ...
+
+With --masks (an object trained from per-image masks, as PEGASUS's reconstruction scripts do) every step renders the
+accumulated opacity too and takes MaskedImageLoss (pgr_image_loss_masked): the target is the image inside the mask over
+the step's own background, plus lambda_alpha mean|alpha - mask|, whose gradient reaches the backward as dL/dalpha.
 
 With --batch_size B > 1 a step renders B views in one render_batch (pgr_forward_batch / pgr_backward_batch) and the Adam
 step, which touches every parameter whatever the number of views, is paid once per B views.
@@ -38,6 +43,8 @@ OPTIMIZATION_DEFAULTS = dict(
     densify_from_iter=500, densify_until_iter=15_000, densify_grad_threshold=0.0002, random_background=False)
 MODEL_DEFAULTS = dict(sh_degree=3, source_path="", model_path="", images="images", resolution=-1,
                       white_background=False, data_device="cuda", eval=False)
+# training from object masks (dataset.masks, opt.lambda_alpha; compat/arguments ModelParams / OptimizationParams carry them)
+MASK_DEFAULTS = dict(masks="", lambda_alpha=0.5)
 MIN_OPACITY = 0.005                      # densify_and_prune's opacity floor
 SCREEN_SIZE_LIMIT = 20                   # pixels: the screen-radius prune once the first opacity reset has happened
 
@@ -75,7 +82,8 @@ class TrainingScene:
         if shuffle:
             random.shuffle(train)
             random.shuffle(test)
-        load = lambda c: colmap_io.load_camera(c, args.resolution, args.white_background, args.data_device)
+        masks = getattr(args, "masks", MASK_DEFAULTS["masks"]) or ""
+        load = lambda c: colmap_io.load_camera(c, args.resolution, args.white_background, args.data_device, masks=masks)
         self.train_cameras = [load(c) for c in train]
         self.test_cameras = [load(c) for c in test]
         if self.loaded_iter:
@@ -107,6 +115,29 @@ def psnr(img, gt) -> float:
     return float("inf") if mse == 0.0 else 20.0 * math.log10(1.0 / math.sqrt(mse))
 
 
+def evaluate_masked(cameras, gaussians, pipe, background) -> tuple:
+    """(mean L1, mean PSNR, mean alpha L1, mean silhouette IoU) of no-grad renders of cameras that carry ``gt_mask``: the
+    target is the image inside the mask composited over ``background``; alpha L1 = mean|alpha - mask|, IoU of alpha > 0.5
+    against mask > 0.5."""
+    from .gaussian_renderer import render
+    from .train_ops import l1_loss
+    acc = [[], [], [], []]
+    with torch.no_grad():
+        for cam in cameras:
+            pkg = render(cam, gaussians, pipe, background, return_alpha=True)
+            image = torch.clamp(pkg["render"], 0.0, 1.0)
+            m = cam.gt_mask.to(image.device)
+            gt = torch.clamp(cam.original_image.to(image.device) * m + background.reshape(3, 1, 1) * (1.0 - m), 0.0, 1.0)
+            alpha = pkg["alpha"]
+            acc[0].append(float(l1_loss(image, gt).item()))
+            acc[1].append(psnr(image, gt))
+            acc[2].append(float(torch.mean(torch.abs(alpha - m)).item()))
+            a, g = alpha > 0.5, m > 0.5
+            union = int((a | g).sum().item())
+            acc[3].append(1.0 if union == 0 else int((a & g).sum().item()) / union)
+    return tuple(sum(v) / len(v) for v in acc) if cameras else (float("nan"),) * 4
+
+
 def evaluate(cameras, gaussians, pipe, background) -> tuple:
     """(mean L1, mean PSNR) of no-grad renders of ``cameras`` against their images (renders clamped to 0..1)."""
     from .gaussian_renderer import render
@@ -126,7 +157,12 @@ def training_report(iteration, scene, gaussians, pipe, background, quiet=False) 
     configs = {"test": scene.getTestCameras(), "train": [train[i % len(train)] for i in range(5, 30, 5)] if train else []}
     out = {}
     for name, cams in configs.items():
-        if cams:
+        if cams and all(getattr(c, "gt_mask", None) is not None for c in cams):
+            l1, p, al1, iou = evaluate_masked(cams, gaussians, pipe, background)
+            out[name] = {"l1": l1, "psnr": p, "alpha_l1": al1, "iou": iou}
+            if not quiet:
+                print(f"\n[ITER {iteration}] Evaluating {name}: L1 {l1} PSNR {p} alpha L1 {al1} IoU {iou}")
+        elif cams:
             l1, p = evaluate(cams, gaussians, pipe, background)
             out[name] = {"l1": l1, "psnr": p}
             if not quiet:
@@ -169,12 +205,22 @@ def _pick_cameras(stack, train_cameras, k):
     return cams, stack
 
 
-def train_step_batch(gaussians, cams, pipe, bg, lambda_dssim):
+def train_step_batch(gaussians, cams, pipe, bg, lambda_dssim, lambda_alpha=None):
     """The forward and backward of one multi-view step: the B cameras in one render_batch, the loss = the mean of the B
     per-view image losses, loss.backward().  Returns (loss, render_batch's dict).  Each view's screen-space gradient in
-    ``viewspace_points.grad`` then carries a factor 1/B: GaussianModel.add_batch_render_stats(..., grad_scale=B) undoes it."""
+    ``viewspace_points.grad`` then carries a factor 1/B: GaussianModel.add_batch_render_stats(..., grad_scale=B) undoes it.
+    ``lambda_alpha`` (not None): the cameras carry ``gt_mask`` and each view takes MaskedImageLoss against its own
+    background (``bg`` [3] or [B,3])."""
     from .gaussian_renderer import render_batch
-    from .train_ops import ImageLoss
+    from .train_ops import ImageLoss, MaskedImageLoss
+    if lambda_alpha is not None:
+        pkg = render_batch(cams, gaussians, pipe, bg, return_alpha=True)
+        image, alpha = pkg["render"], pkg["alpha"]
+        bgs = [bg[v] if bg.dim() == 2 else bg for v in range(len(cams))]
+        loss = sum(MaskedImageLoss.apply(image[v], alpha[v], cam.original_image, cam.gt_mask, bgs[v], float(lambda_dssim),
+                                         float(lambda_alpha)) for v, cam in enumerate(cams)) / len(cams)
+        loss.backward()
+        return loss, pkg
     pkg = render_batch(cams, gaussians, pipe, bg)
     image = pkg["render"]
     loss = sum(ImageLoss.apply(image[v], cam.original_image, float(lambda_dssim)) for v, cam in enumerate(cams)) / len(cams)
@@ -195,7 +241,7 @@ def training(dataset, opt, pipe, testing_iterations, saving_iterations, checkpoi
     images; divide ``--iterations`` (and the schedules) by B for the same number of images.  Nothing is rescaled here."""
     from . import network_gui
     from .gaussian_renderer import render
-    from .train_ops import ImageLoss
+    from .train_ops import ImageLoss, MaskedImageLoss
     if batch_size is None:
         batch_size = getattr(opt, "batch_size", 1)
     batch_size = int(batch_size)
@@ -204,8 +250,14 @@ def training(dataset, opt, pipe, testing_iterations, saving_iterations, checkpoi
     if batch_size > 1 and getattr(pipe, "convert_SHs_python", False):
         raise ValueError("batch_size > 1 renders through render_batch, which takes the kernel-evaluated SH: "
                          "convert_SHs_python is not supported with it")
+    masked = _Options(dataset, {"masks": MASK_DEFAULTS["masks"]}).masks or ""
+    lambda_alpha = float(_Options(opt, {"lambda_alpha": MASK_DEFAULTS["lambda_alpha"]}).lambda_alpha)
+    if lambda_alpha < 0.0:
+        raise ValueError(f"lambda_alpha must be >= 0, got {lambda_alpha}")
     opt = _Options(opt, OPTIMIZATION_DEFAULTS)
     dataset = _Options(dataset, MODEL_DEFAULTS)
+    if masked:
+        dataset.masks = masked          # (cfg_args and TrainingScene; an unmasked run writes what it wrote before)
     testing_iterations, saving_iterations = set(testing_iterations or ()), set(saving_iterations or ())
     checkpoint_iterations = set(checkpoint_iterations or ())
     os.makedirs(dataset.model_path, exist_ok=True)
@@ -236,16 +288,21 @@ def training(dataset, opt, pipe, testing_iterations, saving_iterations, checkpoi
             if iteration - 1 == debug_from:
                 pipe.debug = True
             bg = torch.rand(3, device=dev) if opt.random_background else background
-            pkg = render(cam, gaussians, pipe, bg)
+            pkg = render(cam, gaussians, pipe, bg, return_alpha=bool(masked))
             image, viewspace, radii = pkg["render"], pkg["viewspace_points"], pkg["radii"]
-            loss = ImageLoss.apply(image, cam.original_image, float(opt.lambda_dssim))
+            if masked:
+                loss = MaskedImageLoss.apply(image, pkg["alpha"], cam.original_image, cam.gt_mask, bg,
+                                             float(opt.lambda_dssim), lambda_alpha)
+            else:
+                loss = ImageLoss.apply(image, cam.original_image, float(opt.lambda_dssim))
             loss.backward()
         else:
             cams, stack = _pick_cameras(stack or [], scene.getTrainCameras(), batch_size)
             if iteration - 1 == debug_from:
                 pipe.debug = True
             bg = torch.rand((batch_size, 3), device=dev) if opt.random_background else background
-            loss, pkg = train_step_batch(gaussians, cams, pipe, bg, opt.lambda_dssim)
+            loss, pkg = train_step_batch(gaussians, cams, pipe, bg, opt.lambda_dssim,
+                                         lambda_alpha if masked else None)
             viewspace, radii = pkg["viewspace_points"], pkg["radii"]
         with torch.no_grad():
             if iteration in testing_iterations:
@@ -280,7 +337,7 @@ def training(dataset, opt, pipe, testing_iterations, saving_iterations, checkpoi
 def _parser() -> ArgumentParser:
     p = ArgumentParser(description="Train a 3D Gaussian splatting model on a COLMAP dataset")
     short = {"source_path": "-s", "model_path": "-m", "images": "-i", "resolution": "-r", "white_background": "-w"}
-    for k, v in {**MODEL_DEFAULTS, **OPTIMIZATION_DEFAULTS,
+    for k, v in {**MODEL_DEFAULTS, **OPTIMIZATION_DEFAULTS, **MASK_DEFAULTS,
                  **dict(convert_SHs_python=False, compute_cov3D_python=False, debug=False)}.items():
         flags = ["--" + k] + ([short[k]] if k in short else [])
         if isinstance(v, bool):

@@ -2,6 +2,9 @@
 
     ImageLoss / image_loss(x, y, lambda_dssim)   (1 - l) mean|x-y| + l (1 - mean SSIM), an autograd Function over
                                                  pgr_image_loss (value and dloss/dx in one call); l1_loss, ssim helpers
+    MaskedImageLoss / masked_image_loss(x, alpha, y, mask, bg, lambda_dssim, lambda_alpha)
+                                                 the same loss against y m + bg (1 - m), plus lambda_alpha mean|alpha - m|:
+                                                 pgr_image_loss_masked, differentiable in x and alpha
     FusedAdam                                    a torch.optim.Optimizer whose step() is ONE pgr_adam_step launch for all
                                                  parameter groups, with torch.optim.Adam's state layout and arithmetic
     densify_stats(...)                           pgr_densify_stats: the densification statistics of one render
@@ -15,7 +18,8 @@ import torch
 
 from . import _lib
 
-__all__ = ["ImageLoss", "image_loss", "image_loss_terms", "l1_loss", "ssim", "FusedAdam", "densify_stats"]
+__all__ = ["ImageLoss", "image_loss", "image_loss_terms", "MaskedImageLoss", "masked_image_loss", "masked_image_loss_terms",
+           "l1_loss", "ssim", "FusedAdam", "densify_stats"]
 
 
 def _stream(device) -> C.c_void_p:
@@ -69,6 +73,75 @@ class ImageLoss(torch.autograd.Function):
 
 def image_loss(x, y, lambda_dssim: float = 0.2):
     return ImageLoss.apply(x, y, float(lambda_dssim))
+
+
+def _plane(t: torch.Tensor, what: str, H: int, W: int, device) -> torch.Tensor:
+    """A [H,W] / [1,H,W] map as the kernels read it: fp32, contiguous, [H,W]."""
+    if not isinstance(t, torch.Tensor) or t.numel() != H * W or t.dim() not in (2, 3) or tuple(t.shape[-2:]) != (H, W):
+        raise ValueError(f"{what}: expected a [H,W] or [1,H,W] tensor with H, W = {H}, {W}, got {getattr(t, 'shape', type(t))}")
+    if t.device != device:
+        raise ValueError(f"{what} is on {t.device}, the image on {device}")
+    return t.detach().to(torch.float32).reshape(H, W).contiguous()
+
+
+def masked_image_loss_terms(x, alpha, y, mask, bg, lambda_dssim: float, lambda_alpha: float, want_grad: bool = True,
+                            want_grad_alpha: bool = True):
+    """(out, grad, grad_alpha) of pgr_image_loss_masked: out = device tensor [loss, mean |x-y'|, mean SSIM(x,y'),
+    mean |alpha-m|] with y' = y mask + bg (1 - mask); grad = dloss/dx [3,H,W], grad_alpha = dloss/dalpha [1,H,W] (None when
+    not wanted).  ``alpha`` may be None when lambda_alpha = 0; ``mask`` None is the unmasked loss."""
+    xc, yc = _image(x, "x"), _image(y, "y")
+    if xc.shape != yc.shape or xc.device != yc.device:
+        raise ValueError(f"image loss: x {tuple(xc.shape)} on {xc.device} vs y {tuple(yc.shape)} on {yc.device}")
+    _, H, W = xc.shape
+    dev = xc.device
+    mc = None if mask is None else _plane(mask, "mask", H, W, dev)
+    ac = None if alpha is None else _plane(alpha, "alpha", H, W, dev)
+    bc = None
+    if bg is not None:
+        if not isinstance(bg, torch.Tensor) or bg.numel() != 3 or bg.device != dev:
+            raise ValueError(f"bg: expected 3 values on {dev}, got {getattr(bg, 'shape', type(bg))}")
+        bc = bg.detach().to(torch.float32).reshape(3).contiguous()
+    L = _lib.lib()
+    out = torch.empty(4, dtype=torch.float32, device=dev)
+    grad = torch.empty_like(xc) if want_grad else None
+    grad_a = torch.empty((1, H, W), dtype=torch.float32, device=dev) if (want_grad_alpha and ac is not None) else None
+    ws = torch.empty(L.pgr_image_loss_masked_workspace_bytes(H, W), dtype=torch.uint8, device=dev)
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    with torch.cuda.device(dev):
+        _lib.check(L.pgr_image_loss_masked(p(xc), p(yc), p(mc), p(bc), p(ac), H, W, float(lambda_dssim), float(lambda_alpha),
+                                           p(out), p(grad), p(grad_a), p(ws), ws.numel(), _stream(dev)),
+                   "pgr_image_loss_masked")
+    return out, grad, grad_a
+
+
+class MaskedImageLoss(torch.autograd.Function):
+    """loss = (1 - lambda_dssim) mean|x - y'| + lambda_dssim (1 - mean SSIM(x, y')) + lambda_alpha mean|alpha - mask|,
+    y' = y mask + bg (1 - mask): the image loss of an object trained from a mask, against the step's own background.
+    x [3,H,W] (the render), alpha [1,H,W] (the render's accumulated opacity; None if lambda_alpha = 0), y [3,H,W], mask
+    [1,H,W] or [H,W] in 0..1, bg [3].  Differentiable in x and alpha; like ImageLoss the gradients are final in the forward
+    pass.  ``ctx.terms`` holds [loss, l1, ssim, alpha_l1]."""
+
+    @staticmethod
+    def forward(ctx, x, alpha, y, mask, bg, lambda_dssim=0.2, lambda_alpha=0.5):
+        out, grad, grad_a = masked_image_loss_terms(x, alpha, y, mask, bg, lambda_dssim, lambda_alpha,
+                                                    want_grad=ctx.needs_input_grad[0],
+                                                    want_grad_alpha=alpha is not None and ctx.needs_input_grad[1])
+        ctx.save_for_backward(*(t for t in (grad, grad_a) if t is not None))
+        ctx.has = (grad is not None, grad_a is not None)
+        ctx.alpha_shape = None if alpha is None else tuple(alpha.shape)
+        ctx.terms = out
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        saved = list(ctx.saved_tensors)
+        gx = saved.pop(0) * grad_output if ctx.has[0] else None
+        ga = (saved.pop(0) * grad_output).view(ctx.alpha_shape) if ctx.has[1] else None
+        return gx, ga, None, None, None, None, None
+
+
+def masked_image_loss(x, alpha, y, mask, bg, lambda_dssim: float = 0.2, lambda_alpha: float = 0.5):
+    return MaskedImageLoss.apply(x, alpha, y, mask, bg, float(lambda_dssim), float(lambda_alpha))
 
 
 def l1_loss(x, y):

@@ -6,9 +6,12 @@ Inputs are random (targets, gradients); every stage is warmed up first; each num
 --batch B ... adds multi-view steps (render_batch: B views per optimiser step, one pgr_forward_batch and one
 pgr_backward_batch) with the same stage split, per step and per view; "backward" is the HIP-event time of loss.backward(),
 i.e. of the backward kernels.  B = 1 is the single-view loop above (the default, whose output is unchanged).
+--masks adds, beside every plain step, the same step trained from object masks (a seeded synthetic soft mask per camera):
+render with return_alpha, MaskedImageLoss (pgr_image_loss_masked) against the step's background, backward with dL/dalpha
+(pgr_backward_ex / pgr_backward_batch_ex); reported as "masked" next to the plain numbers.
 
     python scripts/train_step_bench.py [--iters 20] [--warmup 5] [--repeats 5] [--scenes c2 c3] [--batch 1 2 4 8]
-                                       [--json out.json]
+                                       [--masks] [--json out.json]
 """
 from __future__ import annotations
 
@@ -58,10 +61,22 @@ def model_and_cameras(name, dev):
     return m, cams
 
 
-def train_steps(m, cams, iters, dev):
+def add_masks(cams, dev):
+    """A seeded soft elliptical mask per camera (the object in the middle of the frame, a 12-pixel soft edge)."""
+    gen = torch.Generator().manual_seed(3)
+    for cam in cams:
+        H, W = cam.image_height, cam.image_width
+        c = torch.rand(4, generator=gen)
+        ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing="ij")
+        cx, cy, rx, ry = W * (0.4 + 0.2 * c[0]), H * (0.4 + 0.2 * c[1]), W * (0.2 + 0.15 * c[2]), H * (0.2 + 0.15 * c[3])
+        r = torch.sqrt(((xs - cx) / rx) ** 2 + ((ys - cy) / ry) ** 2)
+        cam.gt_mask = torch.clamp((1.0 - r) * min(rx, ry) / 12.0 + 0.5, 0.0, 1.0)[None].to(dev)
+
+
+def train_steps(m, cams, iters, dev, masked=False):
     """Per-stage event times (ms) of ``iters`` iterations, summed per stage."""
     from pegasus_amd.gaussian_renderer import render
-    from pegasus_amd.train_ops import ImageLoss
+    from pegasus_amd.train_ops import ImageLoss, MaskedImageLoss
     pipe = SimpleNamespace(convert_SHs_python=False, compute_cov3D_python=False, debug=False)
     bg = torch.zeros(3, device=dev)
     ev = [[torch.cuda.Event(enable_timing=True) for _ in range(len(STAGES) + 1)] for _ in range(iters)]
@@ -69,9 +84,12 @@ def train_steps(m, cams, iters, dev):
         cam = cams[i % len(cams)]
         e = ev[i]
         e[0].record()
-        pkg = render(cam, m, pipe, bg)
+        pkg = render(cam, m, pipe, bg, return_alpha=masked)
         e[1].record()
-        loss = ImageLoss.apply(pkg["render"], cam.original_image, 0.2)
+        if masked:
+            loss = MaskedImageLoss.apply(pkg["render"], pkg["alpha"], cam.original_image, cam.gt_mask, bg, 0.2, 0.5)
+        else:
+            loss = ImageLoss.apply(pkg["render"], cam.original_image, 0.2)
         e[2].record()
         loss.backward()
         e[3].record()
@@ -87,10 +105,10 @@ def train_steps(m, cams, iters, dev):
     return per
 
 
-def train_steps_batch(m, cams, B, iters, dev):
+def train_steps_batch(m, cams, B, iters, dev, masked=False):
     """train_steps with B views per optimiser step (render_batch; loss = the mean of the B per-view losses)."""
     from pegasus_amd.gaussian_renderer import render_batch
-    from pegasus_amd.train_ops import ImageLoss
+    from pegasus_amd.train_ops import ImageLoss, MaskedImageLoss
     pipe = SimpleNamespace(convert_SHs_python=False, compute_cov3D_python=False, debug=False)
     bg = torch.zeros(3, device=dev)
     ev = [[torch.cuda.Event(enable_timing=True) for _ in range(len(STAGES) + 1)] for _ in range(iters)]
@@ -98,9 +116,13 @@ def train_steps_batch(m, cams, B, iters, dev):
         batch = [cams[(i * B + k) % len(cams)] for k in range(B)]
         e = ev[i]
         e[0].record()
-        pkg = render_batch(batch, m, pipe, bg)
+        pkg = render_batch(batch, m, pipe, bg, return_alpha=masked)
         e[1].record()
-        loss = sum(ImageLoss.apply(pkg["render"][k], c.original_image, 0.2) for k, c in enumerate(batch)) / B
+        if masked:
+            loss = sum(MaskedImageLoss.apply(pkg["render"][k], pkg["alpha"][k], c.original_image, c.gt_mask, bg, 0.2, 0.5)
+                       for k, c in enumerate(batch)) / B
+        else:
+            loss = sum(ImageLoss.apply(pkg["render"][k], c.original_image, 0.2) for k, c in enumerate(batch)) / B
         e[2].record()
         loss.backward()
         e[3].record()
@@ -181,6 +203,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--scenes", nargs="+", default=["c2", "c3"])
     ap.add_argument("--batch", nargs="+", type=int, default=[1], help="views per optimiser step (1: the single-view loop)")
+    ap.add_argument("--masks", action="store_true", help="also time the masked step (alpha + MaskedImageLoss)")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -191,11 +214,17 @@ def main():
     print("loss A/B (value + gradient, 800x800):", json.dumps(report["loss_ab_ms"]), flush=True)
     for name in a.scenes:
         m, cams = model_and_cameras(name, dev)
+        if a.masks:
+            add_masks(cams, dev)
         train_steps(m, cams, a.warmup, dev)
         reps = [train_steps(m, cams, a.iters, dev) for _ in range(a.repeats)]
         med = {k: statistics.median(r[k] for r in reps) for k in reps[0]}
         report[name] = {"gaussians": int(m.get_xyz.shape[0]), "ms_per_iter": med,
                         "adam_ab_ms": adam_ab(m, dev, a.iters, a.warmup, a.repeats)}
+        if a.masks:
+            train_steps(m, cams, a.warmup, dev, masked=True)
+            reps = [train_steps(m, cams, a.iters, dev, masked=True) for _ in range(a.repeats)]
+            report[name]["masked"] = {"ms_per_iter": {k: statistics.median(r[k] for r in reps) for k in reps[0]}}
         print(name, json.dumps(report[name]), flush=True)
         for B in (b for b in a.batch if b > 1):
             train_steps_batch(m, cams, B, a.warmup, dev)
@@ -203,6 +232,11 @@ def main():
             step = {k: statistics.median(r[k] for r in reps) for k in reps[0]}
             report[name].setdefault("batch", {})[str(B)] = {"ms_per_step": step,
                                                               "ms_per_view": {k: v / B for k, v in step.items()}}
+            if a.masks:
+                train_steps_batch(m, cams, B, a.warmup, dev, masked=True)
+                reps = [train_steps_batch(m, cams, B, a.iters, dev, masked=True) for _ in range(a.repeats)]
+                step = {k: statistics.median(r[k] for r in reps) for k in reps[0]}
+                report[name]["batch"][str(B)]["masked"] = {"ms_per_step": step}
             print(f"{name} B={B}", json.dumps(report[name]["batch"][str(B)]), flush=True)
             torch.cuda.empty_cache()
         del m, cams
