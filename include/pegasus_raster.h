@@ -394,7 +394,9 @@ typedef struct PgrGradOutputs {
 /* Backward of ONE view rendered by pgr_forward into `workspace` (which must be untouched since, with the same
  * n / image size / max_instances), given dL/dcolor [3,H,W] and optionally dL/ddepth [1,H,W], and the forward's
  * final_T / n_contrib outputs.  Replaces _C.rasterize_gaussians_backward of the reference's extension (used by
- * training only: /root/reference/src/gs/gs_training.py:7,46).  `grad_rows` is scratch of n*12 floats. */
+ * training only: /root/reference/src/gs/gs_training.py:7,46).  `grad_rows` is scratch of n*12 floats.  It is the
+ * one-view case of pgr_backward_batch (same kernels, same results), with `grad_rows` as its rows; its one per-view table
+ * entry is written into the workspace's `tables` region, which only the forward reads (and the next forward rewrites). */
 int32_t pgr_backward(const PgrScene *scene, const PgrCamera *camera, const float *grad_color,
                      const float *grad_depth, const float *final_T, const uint32_t *n_contrib,
                      const int32_t *radii, void *workspace, size_t workspace_bytes, int64_t max_instances,

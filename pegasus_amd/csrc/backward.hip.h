@@ -3,16 +3,16 @@
 // of alpha is not differentiated, the screen-space mean gradient is NDC-scaled (pixel gradient * W/2, H/2),
 // colours clamped at 0 and clamped view-space coordinates pass no gradient.
 //
-//   composite_backward_block_kernel  one wave per 4x4-pixel block, four list entries per step (below): the ten
-//       per-Gaussian partial gradients of an entry are summed over the block's pixels and land as one 10-lane float
-//       atomic on the Gaussian's row.  An optional dL/dalpha [H,W] (alpha = 1 - final_T, the accumulated opacity) adds
-//       g_alpha T_final / (1 - alpha_i) to the opacity-side gradient of every blended entry i (pgr_backward_ex).
-//   preprocess_backward_kernel      one thread per Gaussian: conic -> cov2D -> (cov3D, view-space mean) ->
-//       scale / rotation; projection; SH -> coefficients and view direction.
-//   composite_backward_batch_kernel, preprocess_backward_batch_kernel  the backward of a pgr_forward_batch call
-//       (pgr_backward_batch): the same block walk for every (view, tile) item of the forward's interleaved work order in
-//       one launch, into per-view rows [n_views, n, GRAD_ROW]; then one thread per Gaussian over the views in order,
-//       summing in registers, cov3D -> scale / rotation once.
+// Both entries (pgr_backward_ex: one view, pgr_backward_batch_ex: a pgr_forward_batch call) run the same two kernels on a
+// table of per-view entries; a one-view call runs their ONE instances (n_views pinned to 1, view 0).
+//   composite_backward_batch_kernel  one wave per 4x4-pixel block, four list entries per step (below), for every
+//       (view, tile) item of the forward's interleaved work order in one launch, into per-view rows [n_views, n, GRAD_ROW]:
+//       the ten per-Gaussian partial gradients of an entry are summed over the block's pixels and land as one 10-lane
+//       float atomic on the Gaussian's row.  An optional dL/dalpha [H,W] (alpha = 1 - final_T, the accumulated opacity)
+//       adds g_alpha T_final / (1 - alpha_i) to the opacity-side gradient of every blended entry i.
+//   preprocess_backward_batch_kernel  one thread per Gaussian over the views in order, summing in registers: conic ->
+//       cov2D -> (cov3D, view-space mean); projection; SH -> coefficients and view direction; cov3D -> scale / rotation
+//       once, on the sum.
 #pragma once
 #include <type_traits>
 #include "composite.hip.h"
@@ -36,11 +36,12 @@ constexpr int GRAD_ROW = 12;
 // of colour and depth -- is a prefix product and four prefix sums over the four lanes of a quad (two quad_perm steps
 // each); everything else is per entry.  The ten partials are summed over the block's 16 pixels (two row shifts, then a
 // 640-byte LDS transpose that also lines the 4 x 10 totals up for ONE atomic instruction).
-// The walk of one block (`item` = 4 * tile + quarter of the view, block = blockIdx.x & 3 inside the quarter); the single-view
-// and the batch kernel below differ only in where the view's lists, camera and images come from.
+// The walk of one block (`item` = 4 * tile + quarter of the view, block = blockIdx.x & 3 inside the quarter).  The view's
+// images are read as global memory (gload): through the table's generic pointers a load is a flat one, and the 64-bit
+// per-lane addresses cost the walk two VGPRs.
 // ALPHA: the walk takes a dL/dalpha image (g_alpha, which may still be NULL).  The alpha term keeps one more register live
-// over the walk, and at 73 VGPRs the batch kernel drops from 7 to 6 waves per SIMD, so the launches without one use the
-// ALPHA = false instance: the walk as it was before the term existed, instruction for instruction.
+// over the walk, so the launches without one use the ALPHA = false instance: the walk as it was before the term existed,
+// instruction for instruction.
 template <bool ALPHA>
 __device__ __forceinline__ void composite_backward_block(
     const CameraDev* __restrict__ camp, const uint2* __restrict__ ranges, const uint32_t* __restrict__ gauss_sorted,
@@ -58,19 +59,19 @@ __device__ __forceinline__ void composite_backward_block(
     const bool inside = px < W && py < H;
     const size_t P = (size_t)W * H;
     const size_t pix = inside ? (size_t)py * W + px : 0;
-    const uint2 range = ranges[tile];
+    const uint2 range = gload(ranges + tile);
 
-    const uint32_t last = inside ? n_contrib[pix] : 0u;
-    float T = inside ? final_T[pix] : 0.0f;        // per-pixel state, the same in the four lanes of a pixel
+    const uint32_t last = inside ? gload(n_contrib + pix) : 0u;
+    float T = inside ? gload(final_T + pix) : 0.0f;        // per-pixel state, the same in the four lanes of a pixel
     float S[3], gC[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        gC[c] = inside ? g_color[c * P + pix] : 0.0f;
+        gC[c] = inside ? gload(g_color + c * P + pix) : 0.0f;
         S[c] = T * cam.bg[c];
     }
-    const float gD = (inside && g_depth) ? g_depth[pix] : 0.0f;
+    const float gD = (inside && g_depth) ? gload(g_depth + pix) : 0.0f;
     // alpha = 1 - T_final, dalpha/dalpha_i = T_final / (1 - alpha_i): the FORWARD's final T (the walk overwrites T) times r
-    const float gAT = (ALPHA && inside && g_alpha) ? g_alpha[pix] * T : 0.0f;
+    const float gAT = (ALPHA && inside && g_alpha) ? gload(g_alpha + pix) * T : 0.0f;
     float SD = 0.0f;
     uint32_t n_used = last;
 #pragma unroll
@@ -222,24 +223,13 @@ __device__ __forceinline__ void composite_backward_block(
     }
 }
 
-template <bool ALPHA>
-__global__ __launch_bounds__(WAVE) void composite_backward_block_kernel(
-    const CameraDev* __restrict__ camp, const uint2* __restrict__ ranges, const uint32_t* __restrict__ gauss_sorted,
-    const float4* __restrict__ splats, const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
-    const float* __restrict__ g_color, const float* __restrict__ g_depth, const float* __restrict__ g_alpha,
-    float* __restrict__ g_rows, const uint32_t* __restrict__ work_order) {
-    const uint32_t item = work_order ? work_order[blockIdx.x >> 2] : (blockIdx.x >> 2);
-    if (item == INVALID_ITEM) return;
-    composite_backward_block<ALPHA>(camp, ranges, gauss_sorted, splats, final_T, n_contrib, g_color, g_depth, g_alpha,
-                                    g_rows, item);
-}
-
 // ---- batch backward (pgr_backward_batch): the backward of a pgr_forward_batch call -------------------------------------
 // One entry per view, in device memory (written by backward_table_kernel from the launch arguments), read through the
-// scalar cache: the forward's lists and packed camera in the workspace, the view's image gradients and forward outputs, and
-// the view's own rows of the [n_views, n, GRAD_ROW] accumulator (screen-space partials: they cannot be summed over views).
+// scalar cache: the forward's lists in the workspace, the view's image gradients and forward outputs, and the view's own
+// rows of the [n_views, n, GRAD_ROW] accumulator (screen-space partials: they cannot be summed over views).  The packed
+// cameras are a kernel argument instead (the workspace's array, one per view): a camera reached through a pointer loaded
+// from the table is read with per-lane flat loads into VGPRs, one through the argument with scalar loads.
 struct alignas(16) BwdViewDev {
-    const CameraDev* cam;
     const uint2* ranges;
     const uint32_t* gauss_sorted;
     const float4* splats;
@@ -264,19 +254,21 @@ __global__ __launch_bounds__(64) void backward_table_kernel(BwdTableChunk chunk,
 
 // The compositor backward of EVERY view in one launch: the forward's interleaved work order (item = view * items_per_view +
 // 4 * tile + quarter, as composite_quarter_kernel reads it), so no view waits on its own slowest tile -- the single-view
-// launch lasts as long as its longest wave.
-template <bool ALPHA>
+// launch lasts as long as its longest wave.  ONE: the instance for a one-view call (n_views = 1, view 0).
+template <bool ALPHA, bool ONE>
 __global__ __launch_bounds__(WAVE) void composite_backward_batch_kernel(const BwdViewDev* __restrict__ views,
-                                                                        uint32_t n_views, uint32_t items_per_view,
+                                                                        const CameraDev* __restrict__ cams, uint32_t n_views,
+                                                                        uint32_t items_per_view,
                                                                         const uint32_t* __restrict__ work_order) {
+    if (ONE) n_views = 1;
     uint32_t item = work_order[blockIdx.x >> 2];
     if (item == INVALID_ITEM) return;
-    const uint32_t view = item / items_per_view;
+    const uint32_t view = ONE ? 0u : item / items_per_view;
     if (view >= n_views) return;
     item -= view * items_per_view;
     const BwdViewDev& bv = views[view];
-    if (bv.counters[1]) return;
-    composite_backward_block<ALPHA>(bv.cam, bv.ranges, bv.gauss_sorted, bv.splats, bv.final_T, bv.n_contrib, bv.g_color,
+    if (gload(bv.counters + 1)) return;
+    composite_backward_block<ALPHA>(cams + view, bv.ranges, bv.gauss_sorted, bv.splats, bv.final_T, bv.n_contrib, bv.g_color,
                                     bv.g_depth, bv.g_alpha, bv.rows, item);
 }
 
@@ -455,136 +447,18 @@ __device__ __forceinline__ void scale_rot_backward(const PgrScene& sc, int i, co
                  x * gR[2][0] + y * gR[2][1]);
 }
 
-template <int DEG>
-__global__ __launch_bounds__(256) void preprocess_backward_kernel(PgrScene sc, const CameraDev* __restrict__ camp,
-                                                                  const int32_t* __restrict__ radii,
-                                                                  const float* __restrict__ g_rows, GradOut o) {
-    const CameraDev& cam = *camp;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= sc.n) return;
-    const bool live = radii[i] > 0;
-    // SH coefficients (and their gradients) as twelve aligned quads per Gaussian
-    const bool sh_quads = sc.shs && sc.sh_stride == 16 && (reinterpret_cast<uintptr_t>(sc.shs) & 15u) == 0 &&
-                          (!o.shs || (reinterpret_cast<uintptr_t>(o.shs) & 15u) == 0);
-    const float* row = g_rows + (size_t)i * GRAD_ROW;
-    float gp[3] = {0.f, 0.f, 0.f};
-    float gS[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    float gndc[2] = {0.f, 0.f};
-    float gcol[3] = {0.f, 0.f, 0.f};
-    float gop = 0.f;
-    const float p[3] = {sc.means3d[3 * i], sc.means3d[3 * i + 1], sc.means3d[3 * i + 2]};
-
-    if (live) {
-        gop = row[5];
-        gcol[0] = row[6]; gcol[1] = row[7]; gcol[2] = row[8];
-        float cov[6];
-        load_cov3d(sc, i, cov);
-        view_geometry_backward(cam, row, p, cov, gp, gS, gndc);
-
-        // ---- colour: SH coefficients and the view direction
-        if (sc.shs) {
-            float d[3] = {p[0] - cam.campos[0], p[1] - cam.campos[1], p[2] - cam.campos[2]};
-            const float len = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-            const float u[3] = {d[0] / len, d[1] / len, d[2] / len};
-            float bb[16], bx[16], by[16], bz[16];
-            sh_basis_grad<DEG>(u[0], u[1], u[2], bb, bx, by, bz);
-            constexpr int NC = (DEG + 1) * (DEG + 1);
-            const float* sh = sc.shs + (size_t)i * sc.sh_stride * 3;
-            float gu[3] = {0.f, 0.f, 0.f};
-            if (sh_quads) {
-                // the common layout (16 coefficients x rgb = twelve aligned quads per Gaussian): coefficients in and
-                // gradients out as 16-byte accesses -- the scalar form is 48 four-byte loads (three times over) and 48
-                // four-byte stores per thread, each touching 64 different cache lines per instruction
-                float shv[48], outv[48];
-#pragma unroll
-                for (int q = 0; q < 12; ++q) {
-                    const float4 v = reinterpret_cast<const float4*>(sh)[q];
-                    shv[4 * q] = v.x; shv[4 * q + 1] = v.y; shv[4 * q + 2] = v.z; shv[4 * q + 3] = v.w;
-                }
-#pragma unroll
-                for (int k = 0; k < 48; ++k) outv[k] = 0.f;
-#pragma unroll
-                for (int ch = 0; ch < 3; ++ch) {
-                    float accv = 0.f;
-#pragma unroll
-                    for (int k = 0; k < NC; ++k) accv += bb[k] * shv[3 * k + ch];
-                    const float g = (accv + 0.5f < 0.0f) ? 0.f : gcol[ch];
-#pragma unroll
-                    for (int k = 0; k < NC; ++k) {
-                        outv[3 * k + ch] = bb[k] * g;
-                        gu[0] += g * shv[3 * k + ch] * bx[k];
-                        gu[1] += g * shv[3 * k + ch] * by[k];
-                        gu[2] += g * shv[3 * k + ch] * bz[k];
-                    }
-                }
-                if (o.shs) {
-                    float4* dst = reinterpret_cast<float4*>(o.shs + (size_t)i * 48);
-#pragma unroll
-                    for (int q = 0; q < 12; ++q) dst[q] = make_float4(outv[4 * q], outv[4 * q + 1], outv[4 * q + 2], outv[4 * q + 3]);
-                }
-            } else {
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-                float accv = 0.f;
-#pragma unroll
-                for (int k = 0; k < NC; ++k) accv += bb[k] * sh[3 * k + ch];
-                const float g = (accv + 0.5f < 0.0f) ? 0.f : gcol[ch];
-#pragma unroll
-                for (int k = 0; k < NC; ++k) {
-                    if (o.shs) o.shs[((size_t)i * sc.sh_stride + k) * 3 + ch] = bb[k] * g;
-                    gu[0] += g * sh[3 * k + ch] * bx[k];
-                    gu[1] += g * sh[3 * k + ch] * by[k];
-                    gu[2] += g * sh[3 * k + ch] * bz[k];
-                }
-            }
-            }
-            const float dot = u[0] * gu[0] + u[1] * gu[1] + u[2] * gu[2];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) gp[k] += (gu[k] - u[k] * dot) / len;
-        }
-    } else if (o.shs) {
-        if (sh_quads) {
-            float4* dst = reinterpret_cast<float4*>(o.shs + (size_t)i * 48);
-#pragma unroll
-            for (int q = 0; q < 12; ++q) dst[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-        } else {
-            const int nf = sc.sh_stride * 3;
-            for (int k = 0; k < nf; ++k) o.shs[(size_t)i * nf + k] = 0.f;
-        }
-    }
-    if (live && o.shs && !sh_quads) {   // coefficients above the active degree receive no gradient
-        constexpr int NC = (DEG + 1) * (DEG + 1);
-        for (int k = NC; k < sc.sh_stride; ++k)
-            for (int ch = 0; ch < 3; ++ch) o.shs[((size_t)i * sc.sh_stride + k) * 3 + ch] = 0.f;
-    }
-
-    // ---- cov3D -> scale, rotation
-    if (o.scales || o.rotations) {
-        float gs[3] = {0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f};
-        if (live && sc.scales && sc.rotations) {
-            scale_rot_backward(sc, i, gS, gs, gq);
-        }
-        if (o.scales) { o.scales[3 * i] = gs[0]; o.scales[3 * i + 1] = gs[1]; o.scales[3 * i + 2] = gs[2]; }
-        if (o.rotations) reinterpret_cast<float4*>(o.rotations)[i] = make_float4(gq[0], gq[1], gq[2], gq[3]);
-    }
-    if (o.means2d) { o.means2d[3 * i] = gndc[0]; o.means2d[3 * i + 1] = gndc[1]; o.means2d[3 * i + 2] = 0.f; }
-    if (o.means3d) { o.means3d[3 * i] = gp[0]; o.means3d[3 * i + 1] = gp[1]; o.means3d[3 * i + 2] = gp[2]; }
-    if (o.opacities) o.opacities[i] = gop;
-    if (o.colors) { o.colors[3 * i] = gcol[0]; o.colors[3 * i + 1] = gcol[1]; o.colors[3 * i + 2] = gcol[2]; }
-    if (o.cov3d) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) o.cov3d[6 * (size_t)i + k] = gS[k];
-    }
-}
-
-// Per-Gaussian backward of a batch: one thread per Gaussian walks the views in a fixed order (0 .. n_views-1), as the forward
+// Per-Gaussian backward: one thread per Gaussian walks the views in a fixed order (0 .. n_views-1), as the forward
 // preprocess walks them, and sums in registers what each view that rendered the Gaussian contributes: mean, the six cov3D
 // partials, opacity, rgb and the (DEG+1)^2 x 3 SH coefficients.  means2d[v] (the screen-space gradient densification reads
 // per view) is written per view; the cov3D -> scale / rotation chain is linear in the cov3D gradient and runs ONCE, on the
 // sum.  Every output is written exactly once, no atomics.
-template <int DEG>
-__global__ __launch_bounds__(256) void preprocess_backward_batch_kernel(PgrScene sc, const BwdViewDev* __restrict__ views,
-                                                                        int n_views, GradOut o) {
+// Registers: cov3D and the active SH coefficients are loaded where they are first used, and colour / opacity summed after
+// the SH step, so that none of them is live across the geometry chain.  ONE: the one-view instance (pgr_backward_ex); at
+// DEG 0-1 it is bounded to 8 waves per SIMD (64 VGPRs, no spills) -- left alone the scheduler stops at 65-66.
+template <int DEG, bool ONE>
+__global__ __launch_bounds__(256, ONE && DEG < 2 ? 8 : 1) void preprocess_backward_batch_kernel(
+    PgrScene sc, const BwdViewDev* __restrict__ views, const CameraDev* __restrict__ cams, int n_views, GradOut o) {
+    if (ONE) n_views = 1;
     constexpr int NC = (DEG + 1) * (DEG + 1);
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= sc.n) return;
@@ -599,13 +473,17 @@ __global__ __launch_bounds__(256) void preprocess_backward_batch_kernel(PgrScene
     float cov[6];
     for (int v = 0; v < n_views; ++v) {
         const BwdViewDev& bv = views[v];
-        const bool live = bv.radii[i] > 0 && !bv.counters[1];
+        const bool live = gload(bv.radii + i) > 0 && !gload(bv.counters + 1);
         float gndc[2] = {0.f, 0.f};
         if (live) {
-            if (!any) {      // per-Gaussian inputs, read once, at the first view that rendered the Gaussian
-                any = true;
-                load_cov3d(sc, i, cov);
-                if (sc.shs) {
+            if (!any) load_cov3d(sc, i, cov);      // per-Gaussian inputs: read once, at the first view that rendered it
+            const CameraDev& cam = cams[v];
+            const float* row = bv.rows + (size_t)i * GRAD_ROW;
+            const float gc[3] = {row[6], row[7], row[8]};
+            float gpv[3] = {0.f, 0.f, 0.f}, gSv[6];
+            view_geometry_backward(cam, row, p, cov, gpv, gSv, gndc);
+            if (sc.shs) {
+                if (!any) {      // the active coefficients, loaded where they are first used
                     const float* sh = sc.shs + (size_t)i * sc.sh_stride * 3;
                     if (sh_quads) {
 #pragma unroll
@@ -621,16 +499,6 @@ __global__ __launch_bounds__(256) void preprocess_backward_batch_kernel(PgrScene
                         for (int k = 0; k < 3 * NC; ++k) shv[k] = sh[k];
                     }
                 }
-            }
-            const CameraDev& cam = *bv.cam;
-            const float* row = bv.rows + (size_t)i * GRAD_ROW;
-            gop += row[5];
-            const float gc[3] = {row[6], row[7], row[8]};
-#pragma unroll
-            for (int c = 0; c < 3; ++c) gcol[c] += gc[c];
-            float gpv[3] = {0.f, 0.f, 0.f}, gSv[6];
-            view_geometry_backward(cam, row, p, cov, gpv, gSv, gndc);
-            if (sc.shs) {
                 const float d[3] = {p[0] - cam.campos[0], p[1] - cam.campos[1], p[2] - cam.campos[2]};
                 const float len = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
                 const float u[3] = {d[0] / len, d[1] / len, d[2] / len};
@@ -659,6 +527,10 @@ __global__ __launch_bounds__(256) void preprocess_backward_batch_kernel(PgrScene
             for (int k = 0; k < 3; ++k) gp[k] += gpv[k];
 #pragma unroll
             for (int k = 0; k < 6; ++k) gS[k] += gSv[k];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) gcol[c] += gc[c];
+            gop += row[5];
+            any = true;
         }
         if (o.means2d) {
             float* m2 = o.means2d + ((size_t)v * sc.n + i) * 3;

@@ -518,6 +518,56 @@ static int32_t forward_batch_impl(const PgrScene* scene, int n_views, const PgrC
     return overflow ? PGR_ERR_INSTANCE_OVERFLOW : PGR_OK;
 }
 
+// Both backward entries after their checks: the per-view table into `table` from the launch arguments (no host staging that
+// would have to outlive the call), `rows` [n_views, n, GRAD_ROW] cleared, the walk of every (view, tile, quarter) item of the
+// forward's work order, then one thread per Gaussian over the views.  One view runs the kernels' ONE instances.
+static int32_t backward_impl(const PgrScene* scene, int n_views, const PgrBackwardView* views,
+                             const float* const* grad_alpha, char* ws, const Layout& L, const BatchLayout& B,
+                             const PgrGradOutputs* grads, float* rows, BwdViewDev* table, hipStream_t stream) {
+    const int N = scene->n;
+    const CameraDev* cams_dev = reinterpret_cast<const CameraDev*>(ws + B.cams);
+    const uint32_t* status_dev = reinterpret_cast<const uint32_t*>(ws + B.status);
+    for (int v0 = 0; v0 < n_views; v0 += BWD_TABLE_CHUNK) {
+        const int cnt = std::min(BWD_TABLE_CHUNK, n_views - v0);
+        BwdTableChunk chunk;
+        memset(&chunk, 0, sizeof(chunk));
+        for (int k = 0; k < cnt; ++k) {
+            const int v = v0 + k;
+            const ViewWs vw = carve(ws + B.views + (size_t)v * B.per_view, L);
+            const PgrBackwardView& bv = views[v];
+            chunk.v[k] = BwdViewDev{vw.ranges, vw.gauss_sorted, vw.splats, status_dev + 2 * v, bv.grad_color, bv.grad_depth,
+                                    bv.final_T, bv.n_contrib, bv.radii, rows + (size_t)v * N * GRAD_ROW,
+                                    grad_alpha ? grad_alpha[v] : nullptr};
+        }
+        backward_table_kernel<<<1, 64, 0, stream>>>(chunk, cnt, table + v0);
+    }
+    if (!hip_ok(hipMemsetAsync(rows, 0, (size_t)n_views * N * GRAD_ROW * sizeof(float), stream), "memset grad rows"))
+        return PGR_ERR_LAUNCH_FAILURE;
+    bool any_alpha = false;
+    for (int v = 0; grad_alpha && v < n_views; ++v) any_alpha = any_alpha || grad_alpha[v];
+    // (the instance without the alpha term when there is no dL/dalpha: backward.hip.h, composite_backward_block)
+    const bool one = n_views == 1;
+    auto* walk = any_alpha ? (one ? composite_backward_batch_kernel<true, true> : composite_backward_batch_kernel<true, false>)
+                           : (one ? composite_backward_batch_kernel<false, true> : composite_backward_batch_kernel<false, false>);
+    walk<<<4u * (uint32_t)B.order_slots, WAVE, 0, stream>>>(table, cams_dev, (uint32_t)n_views, ITEMS_PER_TILE * (uint32_t)L.tiles,
+                                                          reinterpret_cast<const uint32_t*>(ws + B.work_order));
+    const GradOut go{grads->means2d, grads->means3d, grads->opacities, grads->colors, grads->shs, grads->cov3d,
+                     grads->scales, grads->rotations};
+    constexpr decltype(&preprocess_backward_batch_kernel<0, false>) pres[4][2] = {
+        {preprocess_backward_batch_kernel<0, false>, preprocess_backward_batch_kernel<0, true>},
+        {preprocess_backward_batch_kernel<1, false>, preprocess_backward_batch_kernel<1, true>},
+        {preprocess_backward_batch_kernel<2, false>, preprocess_backward_batch_kernel<2, true>},
+        {preprocess_backward_batch_kernel<3, false>, preprocess_backward_batch_kernel<3, true>}};
+    auto* pre = pres[scene->shs ? scene->sh_degree : 0][one];
+    pre<<<(N + 255) / 256, 256, 0, stream>>>(*scene, table, cams_dev, n_views, go);
+    return hip_ok(hipGetLastError(), "backward launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+// The one-view table entry lives in the forward's `tables` region, which the backward never reads and the next forward
+// rewrites; at one view that region holds a ViewEntry, a BinView and a PreOut.
+static_assert(sizeof(BwdViewDev) <= sizeof(ViewEntry) + sizeof(BinView) + sizeof(PreOut),
+              "pgr_backward_ex writes its BwdViewDev into the one-view tables region");
+
 }  // namespace pgr
 
 using namespace pgr;
@@ -720,38 +770,20 @@ int32_t pgr_backward_ex(const PgrScene* scene, const PgrCamera* cam, const float
                         const float* grad_alpha, const float* final_T, const uint32_t* n_contrib, const int32_t* radii,
                         void* workspace, size_t workspace_bytes, int64_t max_instances, const PgrGradOutputs* grads,
                         float* grad_rows, void* stream_v) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
     if (int rc = check_scene(scene)) return rc;
     if (scene->shs_rest) return PGR_ERR_INVALID_ARGUMENT;      // the SH gradient is one [n,sh_stride,3] array
     if (!cam || !grads || !grad_color || !final_T || !n_contrib || cam->image_width <= 0 || cam->image_height <= 0)
         return PGR_ERR_INVALID_ARGUMENT;
-    const int N = scene->n, W = cam->image_width, H = cam->image_height;
+    const int N = scene->n;
     if (N == 0) return PGR_OK;
     if (!workspace || !grad_rows || !radii) return PGR_ERR_INVALID_ARGUMENT;
-    const Layout L = make_layout(N, W, H, max_instances);
+    const Layout L = make_layout(N, cam->image_width, cam->image_height, max_instances);
     const BatchLayout B = make_batch_layout(L, 1, (size_t)N);
     if (workspace_bytes < B.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
     char* ws = static_cast<char*>(workspace);
-    const ViewWs vw = carve(ws + B.views, L);
-    const CameraDev* camd = reinterpret_cast<const CameraDev*>(ws + B.cams);
-    if (!hip_ok(hipMemsetAsync(grad_rows, 0, (size_t)N * GRAD_ROW * sizeof(float), stream), "memset grad rows"))
-        return PGR_ERR_LAUNCH_FAILURE;
-    // the forward's work order is still in the workspace (one view: item = 4 * tile + quarter)
-    // (the instance without the alpha term when there is no dL/dalpha: backward.hip.h, composite_backward_block)
-    auto* walk = grad_alpha ? composite_backward_block_kernel<true> : composite_backward_block_kernel<false>;
-    walk<<<4u * (uint32_t)B.order_slots, WAVE, 0, stream>>>(
-        camd, vw.ranges, vw.gauss_sorted, vw.splats, final_T, n_contrib, grad_color, grad_depth, grad_alpha, grad_rows,
-        reinterpret_cast<const uint32_t*>(ws + B.work_order));
-    const GradOut go{grads->means2d, grads->means3d, grads->opacities, grads->colors, grads->shs, grads->cov3d,
-                     grads->scales, grads->rotations};
-    const int blocks = (N + 255) / 256;
-    switch (scene->shs ? scene->sh_degree : 0) {
-        case 0: preprocess_backward_kernel<0><<<blocks, 256, 0, stream>>>(*scene, camd, radii, grad_rows, go); break;
-        case 1: preprocess_backward_kernel<1><<<blocks, 256, 0, stream>>>(*scene, camd, radii, grad_rows, go); break;
-        case 2: preprocess_backward_kernel<2><<<blocks, 256, 0, stream>>>(*scene, camd, radii, grad_rows, go); break;
-        default: preprocess_backward_kernel<3><<<blocks, 256, 0, stream>>>(*scene, camd, radii, grad_rows, go); break;
-    }
-    return hip_ok(hipGetLastError(), "backward launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+    const PgrBackwardView view{grad_color, grad_depth, final_T, n_contrib, radii};
+    return backward_impl(scene, 1, &view, &grad_alpha, ws, L, B, grads, grad_rows,
+                         reinterpret_cast<BwdViewDev*>(ws + B.tables), static_cast<hipStream_t>(stream_v));
 }
 
 size_t pgr_backward_batch_scratch_bytes(int32_t n, int32_t n_views) {
@@ -770,7 +802,6 @@ int32_t pgr_backward_batch_ex(const PgrScene* scene, int32_t n_views, const PgrC
                               const PgrBackwardView* views, const float* const* grad_alpha, void* workspace,
                               size_t workspace_bytes, int64_t max_instances_per_view, const PgrGradOutputs* grads,
                               void* scratch, size_t scratch_bytes, void* stream_v) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
     // every check before the first enqueue
     if (int rc = check_scene(scene)) return rc;
     if (scene->shs_rest) return PGR_ERR_INVALID_ARGUMENT;      // the SH gradient is one [n,sh_stride,3] array
@@ -788,45 +819,10 @@ int32_t pgr_backward_batch_ex(const PgrScene* scene, int32_t n_views, const PgrC
     const Layout L = make_layout(N, W, H, max_instances_per_view);
     const BatchLayout B = make_batch_layout(L, n_views, (size_t)N);
     if (workspace_bytes < B.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
-    char* ws = static_cast<char*>(workspace);
-    const CameraDev* cams_dev = reinterpret_cast<const CameraDev*>(ws + B.cams);
-    const uint32_t* status_dev = reinterpret_cast<const uint32_t*>(ws + B.status);
     const size_t rows_bytes = (size_t)n_views * (size_t)N * GRAD_ROW * sizeof(float);
-    float* rows = static_cast<float*>(scratch);
     auto* table = reinterpret_cast<BwdViewDev*>(static_cast<char*>(scratch) + align_up(rows_bytes));
-    // the per-view table: the forward's slices of the workspace + the caller's per-view arrays, into the scratch from the
-    // launch arguments (no host staging that would have to outlive the call)
-    for (int v0 = 0; v0 < n_views; v0 += BWD_TABLE_CHUNK) {
-        const int cnt = std::min(BWD_TABLE_CHUNK, n_views - v0);
-        BwdTableChunk chunk;
-        memset(&chunk, 0, sizeof(chunk));
-        for (int k = 0; k < cnt; ++k) {
-            const int v = v0 + k;
-            const ViewWs vw = carve(ws + B.views + (size_t)v * B.per_view, L);
-            const PgrBackwardView& bv = views[v];
-            chunk.v[k] = BwdViewDev{cams_dev + v, vw.ranges, vw.gauss_sorted, vw.splats, status_dev + 2 * v, bv.grad_color,
-                                    bv.grad_depth, bv.final_T, bv.n_contrib, bv.radii, rows + (size_t)v * N * GRAD_ROW,
-                                    grad_alpha ? grad_alpha[v] : nullptr};
-        }
-        backward_table_kernel<<<1, 64, 0, stream>>>(chunk, cnt, table + v0);
-    }
-    if (!hip_ok(hipMemsetAsync(rows, 0, rows_bytes, stream), "memset grad rows")) return PGR_ERR_LAUNCH_FAILURE;
-    // the forward's interleaved work order is still in the workspace: every (view, tile, quarter) item, four blocks each
-    bool any_alpha = false;
-    for (int v = 0; grad_alpha && v < n_views; ++v) any_alpha = any_alpha || grad_alpha[v];
-    auto* walk = any_alpha ? composite_backward_batch_kernel<true> : composite_backward_batch_kernel<false>;
-    walk<<<4u * (uint32_t)B.order_slots, WAVE, 0, stream>>>(
-        table, (uint32_t)n_views, ITEMS_PER_TILE * (uint32_t)L.tiles, reinterpret_cast<const uint32_t*>(ws + B.work_order));
-    const GradOut go{grads->means2d, grads->means3d, grads->opacities, grads->colors, grads->shs, grads->cov3d,
-                     grads->scales, grads->rotations};
-    const int blocks = (N + 255) / 256;
-    switch (scene->shs ? scene->sh_degree : 0) {
-        case 0: preprocess_backward_batch_kernel<0><<<blocks, 256, 0, stream>>>(*scene, table, n_views, go); break;
-        case 1: preprocess_backward_batch_kernel<1><<<blocks, 256, 0, stream>>>(*scene, table, n_views, go); break;
-        case 2: preprocess_backward_batch_kernel<2><<<blocks, 256, 0, stream>>>(*scene, table, n_views, go); break;
-        default: preprocess_backward_batch_kernel<3><<<blocks, 256, 0, stream>>>(*scene, table, n_views, go); break;
-    }
-    return hip_ok(hipGetLastError(), "backward batch launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+    return backward_impl(scene, n_views, views, grad_alpha, static_cast<char*>(workspace), L, B, grads,
+                         static_cast<float*>(scratch), table, static_cast<hipStream_t>(stream_v));
 }
 
 int32_t pgr_compose_object(int32_t n, const float* xyz, const float* rot, const float* f_rest, int32_t n_rest,

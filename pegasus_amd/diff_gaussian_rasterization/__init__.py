@@ -91,120 +91,6 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     return r["color"], r["radii"], r["depth"]
 
 
-_TENSOR_KEYS = ("means3D", "sh", "colors", "op", "scales", "rot", "cov", "bg", "view", "proj", "campos")
-
-
-class _RasterizeGaussians(torch.autograd.Function):
-    """Differentiable single-view rasterization (training path).  The forward keeps its own workspace (the
-    backward walks the same per-tile lists), so it does not share the pooled scratch of the no-grad path.
-
-    Every tensor the backward re-reads goes through ``ctx.save_for_backward``: an in-place update of means, scales,
-    rotations, opacities or SH between forward and backward trips autograd's version-counter check instead of
-    silently pairing new parameter values with the forward's lists, final_T and n_contrib.
-
-    With ``return_alpha`` a fourth output, alpha [1,H,W] = 1 - final_T, is differentiable: its gradient reaches
-    pgr_backward_ex as grad_alpha (NULL when it got none)."""
-
-    @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, return_alpha=False):
-        L = _lib.lib()
-        rs = raster_settings
-        device = means3D.device
-        if device.type != "cuda":
-            raise RuntimeError("GaussianRasterizer needs tensors on a HIP device (torch device 'cuda'); "
-                               "there is no CPU path")
-        H, W, n = int(rs.image_height), int(rs.image_width), int(means3D.shape[0])
-        t = {k: _dev_f32(v, device) for k, v in dict(means3D=means3D, sh=sh, colors=colors_precomp, op=opacities,
-                                                     scales=scales, rot=rotations, cov=cov3Ds_precomp, bg=rs.bg,
-                                                     view=rs.viewmatrix, proj=rs.projmatrix, campos=rs.campos).items()}
-        scene = _lib.PgrScene(n=n, means3d=_ptr(t["means3D"]), opacities=_ptr(t["op"]), scales=_ptr(t["scales"]),
-                              rotations=_ptr(t["rot"]), cov3d_precomp=_ptr(t["cov"]), shs=_ptr(t["sh"]),
-                              colors_precomp=_ptr(t["colors"]), sh_degree=int(rs.sh_degree),
-                              sh_stride=int(t["sh"].shape[1]) if t["sh"] is not None else 0,
-                              scale_modifier=float(rs.scale_modifier))
-        cam = _lib.PgrCamera(image_width=W, image_height=H, tanfovx=float(rs.tanfovx), tanfovy=float(rs.tanfovy),
-                             viewmatrix=_ptr(t["view"]), projmatrix=_ptr(t["proj"]), campos=_ptr(t["campos"]),
-                             bg=_ptr(t["bg"]))
-        color = torch.empty((3, H, W), dtype=torch.float32, device=device)
-        depth = torch.empty((1, H, W), dtype=torch.float32, device=device)
-        radii = torch.empty((n,), dtype=torch.int32, device=device)
-        final_T = torch.empty((H, W), dtype=torch.float32, device=device)
-        n_contrib = torch.empty((H, W), dtype=torch.int32, device=device)
-        outs = _lib.PgrOutputs(color=_ptr(color), depth=_ptr(depth), radii=_ptr(radii), final_T=_ptr(final_T),
-                               n_contrib=_ptr(n_contrib))
-        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        max_inst = max(1 << 18, 4 * n)
-        need = C.c_int64(0)
-        with torch.cuda.device(device):
-            for _attempt in range(3):
-                ws = torch.empty(L.pgr_workspace_bytes(n, W, H, max_inst), dtype=torch.uint8, device=device)
-                status = L.pgr_forward(C.byref(scene), C.byref(cam), C.byref(outs), C.c_void_p(ws.data_ptr()),
-                                       ws.numel(), max_inst, C.byref(need), stream)
-                if status != _lib.PGR_ERR_INSTANCE_OVERFLOW:
-                    break
-                max_inst = rasterizer.grown_capacity(need.value, 1.25)
-            _lib.check(status, "pgr_forward")
-        ctx.rs, ctx.max_inst, ctx.n = rs, max_inst, n
-        # non-tensor state stays on ctx; tensors (inputs as the kernels read them + the forward's own buffers) are saved
-        ctx.present = tuple(k for k in _TENSOR_KEYS if t[k] is not None)
-        ctx.op_shape = tuple(opacities.shape)
-        ctx.save_for_backward(*(t[k] for k in ctx.present), ws, radii, final_T, n_contrib)
-        ctx.mark_non_differentiable(radii)
-        if return_alpha:
-            # an output without a gradient then comes to backward as None (no zero image, no load of one)
-            ctx.set_materialize_grads(False)
-            return color, radii, depth, alpha_from_final_T(final_T)
-        return color, radii, depth
-
-    @staticmethod
-    def backward(ctx, grad_color, _grad_radii, grad_depth, grad_alpha=None):
-        L = _lib.lib()
-        rs, n = ctx.rs, ctx.n
-        saved = ctx.saved_tensors          # raises if an input was modified in place since the forward
-        k = len(ctx.present)
-        t = dict.fromkeys(_TENSOR_KEYS)
-        t.update(zip(ctx.present, saved[:k]))
-        ws, radii, final_T, n_contrib = saved[k:]
-        device = ws.device
-        H, W = int(rs.image_height), int(rs.image_width)
-        # preprocess_backward_kernel writes every element of every gradient it is handed (zeros for culled Gaussians): no
-        # zero fill (384 MB for the SH gradient of a 2 M-Gaussian scene) -- except for an empty scene, where nothing runs
-        alloc = torch.empty if n > 0 else torch.zeros
-        z = lambda *shape: alloc(shape, dtype=torch.float32, device=device)
-        g = dict(means2d=z(n, 3), means3d=z(n, 3), opacities=z(n, 1))
-        if t["sh"] is not None:
-            g["shs"] = z(*t["sh"].shape)
-        else:
-            g["colors"] = z(n, 3)
-        if t["cov"] is not None:
-            g["cov3d"] = z(n, 6)
-        else:
-            g["scales"], g["rotations"] = z(n, 3), z(n, 4)
-        grads = _lib.PgrGradOutputs(**{k: _ptr(v) for k, v in g.items()})
-        scene = _lib.PgrScene(n=n, means3d=_ptr(t["means3D"]), opacities=_ptr(t["op"]), scales=_ptr(t["scales"]),
-                              rotations=_ptr(t["rot"]), cov3d_precomp=_ptr(t["cov"]), shs=_ptr(t["sh"]),
-                              colors_precomp=_ptr(t["colors"]), sh_degree=int(rs.sh_degree),
-                              sh_stride=int(t["sh"].shape[1]) if t["sh"] is not None else 0,
-                              scale_modifier=float(rs.scale_modifier))
-        cam = _lib.PgrCamera(image_width=W, image_height=H, tanfovx=float(rs.tanfovx), tanfovy=float(rs.tanfovy),
-                             viewmatrix=_ptr(t["view"]), projmatrix=_ptr(t["proj"]), campos=_ptr(t["campos"]),
-                             bg=_ptr(t["bg"]))
-        gc = (torch.zeros((3, H, W), dtype=torch.float32, device=device) if grad_color is None
-              else grad_color.contiguous().float())
-        gd = None if grad_depth is None else grad_depth.contiguous().float()
-        ga = None if grad_alpha is None else grad_alpha.contiguous().float()
-        rows = torch.empty((n, 12), dtype=torch.float32, device=device)
-        with torch.cuda.device(device):
-            _lib.check(L.pgr_backward_ex(C.byref(scene), C.byref(cam), _ptr(gc), _ptr(gd), _ptr(ga), _ptr(final_T),
-                                         _ptr(n_contrib), _ptr(radii), C.c_void_p(ws.data_ptr()), ws.numel(), ctx.max_inst,
-                                         C.byref(grads), _ptr(rows),
-                                         C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "pgr_backward_ex")
-        # means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, return_alpha
-        return (g["means3d"], g["means2d"], g.get("shs"), g.get("colors"), g["opacities"].view(ctx.op_shape),
-                g.get("scales"), g.get("rotations"), g.get("cov3d"), None, None)
-
-
 def _scene_struct(t, n, sh_degree, scale_modifier):
     return _lib.PgrScene(n=n, means3d=_ptr(t["means3D"]), opacities=_ptr(t["op"]), scales=_ptr(t["scales"]),
                          rotations=_ptr(t["rot"]), cov3d_precomp=_ptr(t["cov"]), shs=_ptr(t["sh"]),
@@ -216,18 +102,25 @@ def _scene_struct(t, n, sh_degree, scale_modifier):
 _SCENE_KEYS = ("means3D", "sh", "colors", "op", "scales", "rot", "cov")
 
 
-class _RasterizeGaussiansBatch(torch.autograd.Function):
-    """Differentiable rasterization of V views of one scene in ONE pgr_forward_batch call, and its backward in one
-    pgr_backward_batch call (training over several cameras per step).  Outputs color [V,3,H,W], radii [V,n] (not
-    differentiable), depth [V,1,H,W].  Gradients of the scene inputs are summed over the views; ``means2D`` is [V,n,3] and
-    receives every view's own screen-space gradient.
+class _RasterizeGaussians(torch.autograd.Function):
+    """Differentiable rasterization of V views of one scene (training path): ``settings`` is a tuple of V
+    GaussianRasterizationSettings with one image size.  Outputs color [V,3,H,W], radii [V,n] (not differentiable), depth
+    [V,1,H,W]; gradients of the scene inputs are summed over the views, and ``means2D`` [V,n,3] receives every view's own
+    screen-space gradient.  ``single`` (the drop-in GaussianRasterizer: V = 1) drops the view axis of every output and of
+    ``means2D`` and goes through pgr_forward / pgr_backward_ex; otherwise one pgr_forward_batch call and its
+    pgr_backward_batch_ex.
 
-    The contract of _RasterizeGaussians: the call owns its workspace, retries an instance overflow with a grown capacity, and
-    saves every tensor the backward re-reads, so an in-place edit of an input between forward and backward raises.
-    With ``return_alpha`` a fourth output, alpha [V,1,H,W] = 1 - final_T, is differentiable (pgr_backward_batch_ex)."""
+    The call keeps its own workspace (the backward walks the same per-tile lists), so it does not share the pooled scratch
+    of the no-grad path, and retries an instance overflow with a grown capacity.  Every tensor the backward re-reads goes
+    through ``ctx.save_for_backward``: an in-place update of means, scales, rotations, opacities or SH between forward and
+    backward trips autograd's version-counter check instead of silently pairing new parameter values with the forward's
+    lists, final_T and n_contrib.  The cameras are not re-read: the backward takes the packed ones from the workspace.
+
+    With ``return_alpha`` a fourth output, alpha [V,1,H,W] = 1 - final_T, is differentiable: its gradient reaches the
+    backward as grad_alpha (NULL when it got none)."""
 
     @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings,
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, single,
                 return_alpha=False):
         L = _lib.lib()
         settings = tuple(settings)
@@ -243,8 +136,8 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
                 raise ValueError("rasterize_gaussians_batch: sh_degree and scale_modifier must be the same for every view")
         device = means3D.device
         if device.type != "cuda":
-            raise RuntimeError("rasterize_gaussians_batch needs tensors on a HIP device (torch device 'cuda'); "
-                               "there is no CPU path")
+            raise RuntimeError(("GaussianRasterizer" if single else "rasterize_gaussians_batch") +
+                               " needs tensors on a HIP device (torch device 'cuda'); there is no CPU path")
         n = int(means3D.shape[0])
         t = {k: _dev_f32(v, device) for k, v in dict(means3D=means3D, sh=sh, colors=colors_precomp, op=opacities,
                                                      scales=scales, rot=rotations, cov=cov3Ds_precomp).items()}
@@ -254,33 +147,41 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
             _lib.PgrCamera(image_width=W, image_height=H, tanfovx=float(rs.tanfovx), tanfovy=float(rs.tanfovy),
                            viewmatrix=_ptr(c[0]), projmatrix=_ptr(c[1]), campos=_ptr(c[2]), bg=_ptr(c[3]))
             for rs, c in zip(settings, cam_t)])
-        color = torch.empty((V, 3, H, W), dtype=torch.float32, device=device)
-        depth = torch.empty((V, 1, H, W), dtype=torch.float32, device=device)
-        radii = torch.empty((V, n), dtype=torch.int32, device=device)
-        final_T = torch.empty((V, H, W), dtype=torch.float32, device=device)
-        n_contrib = torch.empty((V, H, W), dtype=torch.int32, device=device)
+        lead = () if single else (V,)
+        per_view = (lambda x: (x,)) if single else (lambda x: x.unbind(0))
+        color = torch.empty(lead + (3, H, W), dtype=torch.float32, device=device)
+        depth = torch.empty(lead + (1, H, W), dtype=torch.float32, device=device)
+        radii = torch.empty(lead + (n,), dtype=torch.int32, device=device)
+        final_T = torch.empty(lead + (H, W), dtype=torch.float32, device=device)
+        n_contrib = torch.empty(lead + (H, W), dtype=torch.int32, device=device)
         outs = (_lib.PgrOutputs * V)(*[
-            _lib.PgrOutputs(color=_ptr(color[v]), depth=_ptr(depth[v]), radii=_ptr(radii[v]), final_T=_ptr(final_T[v]),
-                            n_contrib=_ptr(n_contrib[v])) for v in range(V)])
+            _lib.PgrOutputs(color=_ptr(c), depth=_ptr(d), radii=_ptr(r), final_T=_ptr(ft), n_contrib=_ptr(nc))
+            for c, d, r, ft, nc in zip(*map(per_view, (color, depth, radii, final_T, n_contrib)))])
         stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
         max_inst = max(1 << 18, 4 * n)
         need = (C.c_int64 * V)()
         with torch.cuda.device(device):
             for _attempt in range(3):
                 ws = torch.empty(L.pgr_batch_workspace_bytes(n, W, H, max_inst, V), dtype=torch.uint8, device=device)
-                status = L.pgr_forward_batch(C.byref(scene), V, cams, outs, C.c_void_p(ws.data_ptr()), ws.numel(),
-                                             max_inst, need, stream)
+                if single:
+                    status = L.pgr_forward(C.byref(scene), cams, outs, C.c_void_p(ws.data_ptr()), ws.numel(), max_inst,
+                                           need, stream)
+                else:
+                    status = L.pgr_forward_batch(C.byref(scene), V, cams, outs, C.c_void_p(ws.data_ptr()), ws.numel(),
+                                                 max_inst, need, stream)
                 if status != _lib.PGR_ERR_INSTANCE_OVERFLOW:
                     break
                 max_inst = rasterizer.grown_capacity(max(need), 1.25)
-            _lib.check(status, "pgr_forward_batch")
-        ctx.hw, ctx.V, ctx.n, ctx.max_inst = (H, W), V, n, max_inst
+            _lib.check(status, "pgr_forward" if single else "pgr_forward_batch")
+        ctx.hw, ctx.V, ctx.n, ctx.max_inst, ctx.single = (H, W), V, n, max_inst, single
         ctx.sh_degree, ctx.scale_modifier = int(rs0.sh_degree), float(rs0.scale_modifier)
+        # non-tensor state stays on ctx; tensors (inputs as the kernels read them + the forward's own buffers) are saved
         ctx.present = tuple(k for k in _SCENE_KEYS if t[k] is not None)
         ctx.op_shape = tuple(opacities.shape)
         ctx.save_for_backward(*(t[k] for k in ctx.present), ws, radii, final_T, n_contrib)
         ctx.mark_non_differentiable(radii)
         if return_alpha:
+            # an output without a gradient then comes to backward as None (no zero image, no load of one)
             ctx.set_materialize_grads(False)
             return color, radii, depth, alpha_from_final_T(final_T)
         return color, radii, depth
@@ -288,18 +189,20 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_color, _grad_radii, grad_depth, grad_alpha=None):
         L = _lib.lib()
-        V, n, (H, W) = ctx.V, ctx.n, ctx.hw
+        V, n, (H, W), single = ctx.V, ctx.n, ctx.hw, ctx.single
         saved = ctx.saved_tensors          # raises if an input was modified in place since the forward
         k = len(ctx.present)
         t = dict.fromkeys(_SCENE_KEYS)
         t.update(zip(ctx.present, saved[:k]))
         ws, radii, final_T, n_contrib = saved[k:]
         device = ws.device
-        # preprocess_backward_batch_kernel writes every element of every gradient it is handed: no zero fill, except for
-        # an empty scene, where nothing runs
+        lead = () if single else (V,)
+        # preprocess_backward_batch_kernel writes every element of every gradient it is handed (zeros for culled
+        # Gaussians): no zero fill (384 MB for the SH gradient of a 2 M-Gaussian scene) -- except for an empty scene,
+        # where nothing runs
         alloc = torch.empty if n > 0 else torch.zeros
         z = lambda *shape: alloc(shape, dtype=torch.float32, device=device)
-        g = dict(means2d=z(V, n, 3), means3d=z(n, 3), opacities=z(n, 1))
+        g = dict(means2d=z(*lead, n, 3), means3d=z(n, 3), opacities=z(n, 1))
         if t["sh"] is not None:
             g["shs"] = z(*t["sh"].shape)
         else:
@@ -311,24 +214,31 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         grads = _lib.PgrGradOutputs(**{key: _ptr(v) for key, v in g.items()})
         scene = _scene_struct(t, n, ctx.sh_degree, ctx.scale_modifier)
         cams = (_lib.PgrCamera * V)(*[_lib.PgrCamera(image_width=W, image_height=H) for _ in range(V)])
-        gc = (torch.zeros((V, 3, H, W), dtype=torch.float32, device=device) if grad_color is None
+        gc = (torch.zeros(lead + (3, H, W), dtype=torch.float32, device=device) if grad_color is None
               else grad_color.contiguous().float())
         gd = None if grad_depth is None else grad_depth.contiguous().float()
         ga = None if grad_alpha is None else grad_alpha.contiguous().float()
-        alpha_ptrs = None if ga is None else (C.c_void_p * V)(*[ga[v].data_ptr() for v in range(V)])
-        views = (_lib.PgrBackwardView * V)(*[
-            _lib.PgrBackwardView(grad_color=_ptr(gc[v]), grad_depth=None if gd is None else _ptr(gd[v]),
-                                 final_T=_ptr(final_T[v]), n_contrib=_ptr(n_contrib[v]), radii=_ptr(radii[v]))
-            for v in range(V)])
-        scratch = torch.empty(max(1, L.pgr_backward_batch_scratch_bytes(n, V)), dtype=torch.uint8, device=device)
+        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
         with torch.cuda.device(device):
-            _lib.check(L.pgr_backward_batch_ex(C.byref(scene), V, cams, views, alpha_ptrs, C.c_void_p(ws.data_ptr()),
-                                               ws.numel(), ctx.max_inst, C.byref(grads), C.c_void_p(scratch.data_ptr()),
-                                               scratch.numel(), C.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
-                       "pgr_backward_batch_ex")
-        # means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, return_alpha
+            if single:
+                rows = torch.empty((n, 12), dtype=torch.float32, device=device)
+                _lib.check(L.pgr_backward_ex(C.byref(scene), cams, _ptr(gc), _ptr(gd), _ptr(ga), _ptr(final_T),
+                                             _ptr(n_contrib), _ptr(radii), C.c_void_p(ws.data_ptr()), ws.numel(),
+                                             ctx.max_inst, C.byref(grads), _ptr(rows), stream), "pgr_backward_ex")
+            else:
+                alpha_ptrs = None if ga is None else (C.c_void_p * V)(*[ga[v].data_ptr() for v in range(V)])
+                views = (_lib.PgrBackwardView * V)(*[
+                    _lib.PgrBackwardView(grad_color=_ptr(gc[v]), grad_depth=None if gd is None else _ptr(gd[v]),
+                                         final_T=_ptr(final_T[v]), n_contrib=_ptr(n_contrib[v]), radii=_ptr(radii[v]))
+                    for v in range(V)])
+                scratch = torch.empty(max(1, L.pgr_backward_batch_scratch_bytes(n, V)), dtype=torch.uint8, device=device)
+                _lib.check(L.pgr_backward_batch_ex(C.byref(scene), V, cams, views, alpha_ptrs, C.c_void_p(ws.data_ptr()),
+                                                   ws.numel(), ctx.max_inst, C.byref(grads),
+                                                   C.c_void_p(scratch.data_ptr()), scratch.numel(), stream),
+                           "pgr_backward_batch_ex")
+        # means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, single, return_alpha
         return (g["means3d"], g["means2d"], g.get("shs"), g.get("colors"), g["opacities"].view(ctx.op_shape),
-                g.get("scales"), g.get("rotations"), g.get("cov3d"), None, None)
+                g.get("scales"), g.get("rotations"), g.get("cov3d"), None, None, None)
 
 
 def rasterize_gaussians_batch(means3D, means2D, opacities, raster_settings, shs=None, colors_precomp=None, scales=None,
@@ -346,8 +256,8 @@ def rasterize_gaussians_batch(means3D, means2D, opacities, raster_settings, shs=
     settings = tuple(raster_settings)
     if means2D is None:
         means2D = torch.zeros((len(settings), int(means3D.shape[0]), 3), dtype=torch.float32, device=means3D.device)
-    return _RasterizeGaussiansBatch.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                          cov3D_precomp, settings, bool(return_alpha))
+    return _RasterizeGaussians.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
+                                     settings, False, bool(return_alpha))
 
 
 class GaussianRasterizer(nn.Module):
@@ -387,7 +297,7 @@ class GaussianRasterizer(nn.Module):
             if means2D is None:
                 means2D = torch.zeros_like(means3D, requires_grad=False)
             return _RasterizeGaussians.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                             cov3D_precomp, self.raster_settings, bool(return_alpha))
+                                             cov3D_precomp, (self.raster_settings,), True, bool(return_alpha))
         with torch.no_grad():
             if return_alpha:
                 color, radii, depth, final_T, _ = rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities,

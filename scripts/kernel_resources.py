@@ -21,5 +21,5 @@ for b in re.split(r"remark: [^\n]*Function Name: ", txt)[1:]:
     def g(k):
         m = re.search(re.escape(k) + r": (\d+)", b)
         return m.group(1) if m else "?"
-    print(f"{d[:84]:84s} vgpr {g('VGPRs'):>3} agpr {g('AGPRs'):>3} spill {g('VGPR Spill'):>3} scratch {g('ScratchSize [bytes/lane]'):>4} "
+    print(f"{d[:84]:84s} vgpr {g('VGPRs'):>3} agpr {g('AGPRs'):>3} spill {g('VGPRs Spill'):>3} scratch {g('ScratchSize [bytes/lane]'):>4} "
           f"occ {g('Occupancy [waves/SIMD]'):>2} lds {g('LDS Size [bytes/block]'):>6}")
