@@ -14,10 +14,12 @@ One "step" = one batch of B = 32 cameras of the synthetic merged scene (BASELINE
 2.0 M Gaussians, 800x800) through the rasterizer hot path.  Views shard across ranks (view v -> rank v mod N, scene
 replicated: SURVEY.md section 8e), weak scaling: every rank renders K batches of its own shard.  For N > 1 the path's ONE
 collective -- the gather of every finished batch to rank 0, in the reference's on-disk precision -- runs inside the timed
-region by default (asynchronous, one gather in flight beside the next batch); the render-only rate is timed in a second
-K-step pass and reported beside it.  Rank 0 prints ONE JSON line.
+region by default (asynchronous, one gather in flight beside the next batch), and one more batch checks afterwards that
+rank 0 received what every rank sent.  Rank 0 prints ONE JSON line.
 
-The JSON line also carries
+A plain run does only what that line's headline needs: set-up, warm-up, the timed steps, --dump-outputs when given, the
+line.  With --full it also measures, outside the timed region (each one None in a plain line):
+  gather.views_per_s_render_only -- N > 1: the render-only rate, timed in a second K-step pass
   roofline      -- the dominant kernel's algorithmic bytes / its average duration measured live with HIP events on the
                    launch stream (pgr_forward_batch_profiled), against 8 TB/s HBM peak; `valu` prices the compositor's
                    pixel-Gaussian evaluations against the chip's VALU lane rate
@@ -76,8 +78,11 @@ def parse(argv=None):
                          "side workload, never as the headline")
     ap.add_argument("--batch", type=int, default=32,
                     help="views per step (one batch call); 16 default steps x 32 = the 512 views of configs[2], each once")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-drop-in", action="store_true", help="skip the per-camera render() sample (drop_in)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: per-stage timing and roofline, "
+                         "the CPU baseline and the drop-in sample (N = 1), the render-only rate (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle timing (cpu_baseline)")
+    ap.add_argument("--no-drop-in", action="store_true", help="--full: skip the per-camera render() sample (drop_in)")
     ap.add_argument("--facade", action="store_true",
                     help="only the drop-in path: frames/s of PEGASUS's per-camera loop through the four render wrappers "
                          "and the latency of one render() call, on a larger sample")
@@ -134,7 +139,7 @@ def parse(argv=None):
                          "the K per-object silhouette masks (/root/reference/pegasus.py:491, src/gs/render.py:36-65), as one "
                          "layered batch pass per step inside the timed region")
     ap.add_argument("--profile-steps", type=int, default=0,
-                    help="batches measured per-stage with HIP events (0 = the same batches as the timed steps)")
+                    help="--full: batches measured per-stage with HIP events (0 = the same batches as the timed steps)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the frame set of the last timed step (what render_frames hands its "
                          "caller) as DIR/<name>.npy in float32: whole, or a fixed seeded sample of pixel positions shared by "
@@ -733,7 +738,7 @@ def run_worker(args):
             dist.all_gather_object(per_rank, own)
         return el, per_rank
 
-    probe = ClockProbe(dev) if (not eng.stub and world == 1) else None
+    probe = ClockProbe(dev) if (args.full and not eng.stub and world == 1) else None
     clock = {}
     eng.probe, eng.clock = probe, clock
     eng.settle(run_steps)
@@ -757,7 +762,7 @@ def run_worker(args):
     order = sorted(range(repeats), key=lambda r: runs[r][0])
     med = order[(repeats - 1) // 2]                # the median repeat (lower middle for an even count)
     elapsed, per_rank = runs[med]
-    elapsed_render_only = timed(args.warmup, args.steps, False)[0] if gather_on else None
+    elapsed_render_only = timed(args.warmup, args.steps, False)[0] if gather_on and args.full else None
 
     # ---- gather check (N > 1, outside the timed region): one more batch through the same pack + gather; rank 0 compares
     # the byte sums of what it RECEIVED from every rank with the sums those ranks computed on what they SENT
@@ -844,7 +849,7 @@ def run_worker(args):
                         if direct else "pgr_pack_records into the send buffer after the batch"),
             "bytes_per_rank_and_batch": fg.bytes_per_rank_and_batch,
             "views_per_s_with_gather": round(value, 3),
-            "views_per_s_render_only": round(total_views / elapsed_render_only, 3),
+            "views_per_s_render_only": round(total_views / elapsed_render_only, 3) if elapsed_render_only else None,
             "inbound_to_root_gb_per_s": round(fg.bytes_per_rank_and_batch * (world - 1) * args.steps / elapsed / 1e9, 2),
             # rank 0's own per-batch overhead: host time to enqueue the pack kernel and start the collective (there is no
             # assembly step: nothing is reordered or copied on arrival), mean over the repeats; and, apart from it, the host
@@ -873,9 +878,9 @@ def run_worker(args):
     return 0
 
 
-def _finish_real_line(args, eng, line, value, world, dist_info, gather_info, rehearsal):
-    """Rank 0, product path: per-view statistics, per-stage HIP-event timing of whole batches, roofline, CPU baseline and
-    the drop-in sample -- all outside the timed region."""
+def _side_measurements(args, eng, value, world):
+    """--full, rank 0, product path: per-view statistics, per-stage HIP-event timing of whole batches, roofline, CPU baseline
+    and the drop-in sample -- all outside the timed region."""
     import torch
     from pegasus_amd import _lib, rasterizer
     fr, B, W, H = eng.fr, eng.B, eng.W, eng.H
@@ -1059,7 +1064,13 @@ def _finish_real_line(args, eng, line, value, world, dist_info, gather_info, reh
         if isinstance(drop_in, dict) and "error" not in drop_in:
             drop_in["dynamic"] = ({k: dyn[k] for k in ("mode", "frames_per_s", "ms_per_frame", "frames_per_s_all_data_points",
                                                        "ms_per_part", "passes_ms_per_frame")} if "error" not in dyn else dyn)
+    return {"roofline": roofline, "cpu_baseline": cpu, "drop_in": drop_in}
 
+
+def _finish_real_line(args, eng, line, value, world, dist_info, gather_info, rehearsal):
+    """Rank 0, product path: what the run rendered (metric, config) and, with --full, the side measurements."""
+    fr, B, W, H, N = eng.fr, eng.B, eng.W, eng.H, eng.cloud.n
+    with_masks = eng.with_masks
     N_label = f"{N / 1e6:.2g}M"
     line.update(
         metric=(f"rendered views/sec (RGB+depth+mask) on {N_label}-Gaussian scene @{W}x{H}" if with_masks else
@@ -1080,7 +1091,9 @@ def _finish_real_line(args, eng, line, value, world, dist_info, gather_info, reh
                 "data_points": (["rgb", "depth", "seg_vis", "sem_seg"] + (["seg_sil"] if eng.with_sil else [])) if with_masks
                                else ["rgb", "depth"],
                 "parallelism": f"view-shard x{world}", "distributed": dist_info, "gather": gather_info},
-        roofline=roofline, cpu_baseline=cpu, drop_in=drop_in)
+        roofline=None, cpu_baseline=None, drop_in=None)
+    if args.full:
+        line.update(_side_measurements(args, eng, value, world))
     if rehearsal:
         line["rehearsal"] = ("NOT a result: ranks share devices, the gather runs on gloo through host memory, or a one-rank "
                              "process group was forced; only the launch, sharding, collective and gather logic is exercised")

@@ -7,7 +7,7 @@ REPO=$PWD
 name=${1:-pmc_lds}; shift
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-BENCH_FLAGS="--steps 16 --warmup 1 --repeats 1 --no-cpu-baseline --no-drop-in --profile-steps 1 --sync-steps $*"
+BENCH_FLAGS="--full --steps 16 --warmup 1 --repeats 1 --no-cpu-baseline --no-drop-in --profile-steps 1 --sync-steps $*"
 d=/tmp/pmc_lds_$name
 rm -rf $d
 ( cd /tmp && timeout 600 rocprofv3 --pmc SQ_LDS_ADDR_CONFLICT SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_INSTS_LDS_ATOMIC SQ_LDS_ATOMIC_RETURN SQ_LDS_UNALIGNED_STALL GRBM_GUI_ACTIVE -d $d -- python3 $REPO/bench.py $BENCH_FLAGS > /tmp/pmc_lds_$name.log 2>&1 )

@@ -11,20 +11,20 @@ cp gpurun_out/r06_pmc.json profiles/pmc.json; cp gpurun_out/r06_pmc_c5.json prof
 cp gpurun_out/r06_pmc.json profiles/r06_pmc.json; cp gpurun_out/r06_pmc_c5.json profiles/r06_pmc_c5.json
 python scripts/issue_model.py profiles/r06_pmc.json profiles/r06_pmc_c5.json > ${P}_issue_model.log 2>&1
 cp profiles/r06_issue_model.txt profiles/issue_model.json gpurun_out/
-python bench.py > ${P}_bench_default.json 2> ${P}_bench_default.err
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline > ${P}_bench_steps20_warmup5.json 2>/dev/null
-python bench.py --data-points all --no-cpu-baseline --no-drop-in > ${P}_bench_all_data_points.json 2>/dev/null
-python bench.py --workload c5 --dynamic --views 200 --no-drop-in > ${P}_bench_c5_dynamic.json 2>/dev/null
-python bench.py --workload c5 --views 200 --no-drop-in --no-cpu-baseline > ${P}_bench_c5_static.json 2>/dev/null
-python bench.py --dynamic --no-drop-in --no-cpu-baseline > ${P}_bench_c3_dynamic.json 2>/dev/null
-python bench.py --workload c2 --views 64 --no-drop-in --no-cpu-baseline > ${P}_bench_c2.json 2>/dev/null
-python bench.py --views 4096 --steps 128 --repeats 3 --no-drop-in --no-cpu-baseline > ${P}_bench_c4_4096views_1gpu.json 2>/dev/null
-python bench.py --workload c5 --dynamic --views 200 --batch 40 --steps 5 --no-drop-in --no-cpu-baseline > ${P}_bench_c5_dynamic_200steps_1gpu.json 2>/dev/null
+python bench.py --full > ${P}_bench_default.json 2> ${P}_bench_default.err
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > ${P}_bench_steps20_warmup5.json 2>/dev/null
+python bench.py --full --data-points all --no-cpu-baseline --no-drop-in > ${P}_bench_all_data_points.json 2>/dev/null
+python bench.py --full --workload c5 --dynamic --views 200 --no-drop-in > ${P}_bench_c5_dynamic.json 2>/dev/null
+python bench.py --full --workload c5 --views 200 --no-drop-in --no-cpu-baseline > ${P}_bench_c5_static.json 2>/dev/null
+python bench.py --full --dynamic --no-drop-in --no-cpu-baseline > ${P}_bench_c3_dynamic.json 2>/dev/null
+python bench.py --full --workload c2 --views 64 --no-drop-in --no-cpu-baseline > ${P}_bench_c2.json 2>/dev/null
+python bench.py --full --views 4096 --steps 128 --repeats 3 --no-drop-in --no-cpu-baseline > ${P}_bench_c4_4096views_1gpu.json 2>/dev/null
+python bench.py --full --workload c5 --dynamic --views 200 --batch 40 --steps 5 --no-drop-in --no-cpu-baseline > ${P}_bench_c5_dynamic_200steps_1gpu.json 2>/dev/null
 python bench.py --facade > ${P}_bench_facade.json 2>/dev/null
-python bench.py --width 640 --height 480 --objects 6 --data-points all --no-cpu-baseline > ${P}_bench_ref_default_640x480.json 2>/dev/null
-python bench.py --gpus 2 --share-devices --backend gloo --steps 6 --warmup 2 --no-drop-in > ${P}_bench_rehearsal_2ranks_1gpu.json 2>/dev/null
-python bench.py --force-dist --backend nccl --no-drop-in --no-cpu-baseline > ${P}_bench_rccl_1rank_forced.json 2>/dev/null
-python bench.py --force-dist --backend nccl --full-outputs --no-drop-in --no-cpu-baseline > ${P}_bench_rccl_1rank_forced_full_outputs.json 2>/dev/null
+python bench.py --full --width 640 --height 480 --objects 6 --data-points all --no-cpu-baseline > ${P}_bench_ref_default_640x480.json 2>/dev/null
+python bench.py --full --gpus 2 --share-devices --backend gloo --steps 6 --warmup 2 --no-drop-in > ${P}_bench_rehearsal_2ranks_1gpu.json 2>/dev/null
+python bench.py --full --force-dist --backend nccl --no-drop-in --no-cpu-baseline > ${P}_bench_rccl_1rank_forced.json 2>/dev/null
+python bench.py --full --force-dist --backend nccl --full-outputs --no-drop-in --no-cpu-baseline > ${P}_bench_rccl_1rank_forced_full_outputs.json 2>/dev/null
 bash scripts/trace_run.sh r06 --no-drop-in > /dev/null 2>&1
 bash scripts/trace_run.sh r06_sync --no-drop-in --sync-steps > /dev/null 2>&1
 bash scripts/trace_run.sh r06_c5_sync --no-drop-in --sync-steps --workload c5 --views 200 > /dev/null 2>&1

@@ -3,6 +3,7 @@
 cd "$(dirname "$0")/.."
 REPO=$PWD
 name=$1; shift
+set -- --full "$@"
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 d=/tmp/trace_$name

@@ -31,7 +31,8 @@ def _run(cmd, env=None, timeout=300):
 
 
 def test_gpus_2_launches_two_ranks_by_itself_and_gathers():
-    p, line = _run([sys.executable, "bench.py", "--gpus", "2", "--stub-renderer", "--steps", "3", "--warmup", "1", "--batch", "4"])
+    p, line = _run([sys.executable, "bench.py", "--gpus", "2", "--stub-renderer", "--steps", "3", "--warmup", "1", "--batch", "4",
+                    "--full"])
     assert p.returncode == 0, p.stderr[-2000:]
     assert len([l for l in p.stdout.splitlines() if l.startswith("{")]) == 1          # ONE line, from rank 0
     assert [l for l in p.stdout.splitlines() if l.strip()] == [l for l in p.stdout.splitlines() if l.startswith("{")], \
@@ -53,6 +54,16 @@ def test_gpus_2_launches_two_ranks_by_itself_and_gathers():
     pr = line["per_rank_s"]
     assert len(pr["all"]) == 2 and pr["min"] <= pr["rank0"] <= pr["max"] + 1e-9 and pr["max"] * 1e3 <= line["ms_per_step"] * 3 + 1e-3
     assert g["rank0_gather_host_ms_per_step"] >= 0
+
+
+def test_plain_run_leaves_the_render_only_pass_to_full():
+    """Without --full an N-rank run still gathers inside the timed region and checks what arrived, but times no second,
+    render-only pass."""
+    p, line = _run([sys.executable, "bench.py", "--gpus", "2", "--stub-renderer", "--steps", "2", "--warmup", "1", "--batch", "3"])
+    assert p.returncode == 0, p.stderr[-2000:]
+    g = line["config"]["gather"]
+    assert g["check"] == "ok" and g["views_per_s_with_gather"] == line["value"] > 0
+    assert g["views_per_s_render_only"] is None
 
 
 import pytest as _pytest
@@ -115,7 +126,7 @@ def test_real_renderer_two_ranks_on_one_device_rehearsal(gpu_device):
     RCCL refuses two ranks on one device), small scene.  Checks the launcher, per-rank sharding, pack + gather + the
     received-bytes check, and that the line is flagged as a rehearsal."""
     p, line = _run([sys.executable, "bench.py", "--gpus", "2", "--share-devices", "--backend", "gloo", "--scale", "0.03",
-                    "--steps", "2", "--warmup", "1", "--batch", "4", "--views", "8", "--slots", "2", "--no-drop-in"], timeout=900)
+                    "--steps", "2", "--warmup", "1", "--batch", "4", "--views", "8", "--slots", "2", "--no-drop-in", "--full"], timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     assert line["n_gpus"] == 2 and "rehearsal" in line and line["config"]["distributed"]["backend"] == "gloo"
     g = line["config"]["gather"]
@@ -126,11 +137,24 @@ def test_real_renderer_two_ranks_on_one_device_rehearsal(gpu_device):
 
 
 @pytest.mark.gpu
+def test_plain_line_is_the_headline_only(gpu_device):
+    """A plain single-GPU run prints the headline and what it rendered; the side measurements are --full's (None here)."""
+    p, line = _run([sys.executable, "bench.py", "--scale", "0.03", "--steps", "2", "--warmup", "1", "--batch", "4",
+                    "--views", "8", "--repeats", "2"], timeout=900)
+    assert p.returncode == 0, p.stderr[-3000:]
+    assert line["metric"].startswith("rendered views/sec (RGB+depth+mask)") and line["unit"] == "views/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f32" and line["steps"] == 2 and line["warmup"] == 1
+    assert line["value"] > 0 and abs(line["ms_per_step"] * 2 * line["value"] / 1e3 - 2 * 4) < 0.05
+    assert line["config"]["objects"] == 8 and line["config"]["views_per_step"] == 4
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["drop_in"] is None
+
+
+@pytest.mark.gpu
 def test_dynamic_sequence_bench_line(gpu_device):
     """bench.py --dynamic (configs[4] as SURVEY.md section 8d writes it: poses from the reference's trajectory fixture) at a
     small scale: runs, names the sequence, and carries the posed CPU baseline."""
     p, line = _run([sys.executable, "bench.py", "--workload", "c5", "--dynamic", "--scale", "0.02", "--steps", "2", "--warmup", "1",
-                    "--batch", "4", "--views", "200", "--no-drop-in", "--cpu-budget-s", "2"], timeout=900)
+                    "--batch", "4", "--views", "200", "--no-drop-in", "--cpu-budget-s", "2", "--full"], timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     assert "simulation_steps.json" in line["config"]["sequence"] and line["config"]["objects"] == 20
     assert line["cpu_baseline"]["value"] > 0 and line["value"] > 0
@@ -142,7 +166,7 @@ def test_one_rank_process_group_on_rccl(gpu_device):
     RCCL initialisation in this environment, all_gather_object / barrier / all_reduce of the timing protocol, the asynchronous
     gather of uint8 and 16-bit-as-bytes frames and its check -- every collective call the N-rank run makes, with N = 1."""
     p, line = _run([sys.executable, "bench.py", "--force-dist", "--backend", "nccl", "--scale", "0.03", "--steps", "2", "--warmup", "1",
-                    "--batch", "4", "--views", "8", "--slots", "2", "--no-drop-in", "--no-cpu-baseline"], timeout=900)
+                    "--batch", "4", "--views", "8", "--slots", "2", "--no-drop-in", "--no-cpu-baseline", "--full"], timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     d = line["config"]["distributed"]
     assert d["backend"] == "nccl (RCCL)" and d["world_size"] == 1 and line["n_gpus"] == 1 and "rehearsal" in line
