@@ -443,6 +443,41 @@ int32_t pgr_backward_batch_ex(const PgrScene *scene, int32_t n_views, const PgrC
                               size_t workspace_bytes, int64_t max_instances_per_view, const PgrGradOutputs *grads,
                               void *scratch, size_t scratch_bytes, void *stream);
 
+/* Camera gradients: the exact partials of the loss with respect to the 35 camera numbers the forward reads per view --
+ * viewmatrix [16] and projmatrix [16] (PgrCamera's transposed storage) and campos [3] -- each treated as an independent
+ * input (a caller that ties them together, e.g. through a pose, composes them).  With p = (x, y, z, 1) per Gaussian the
+ * view rendered (radii > 0, no overflow): viewmatrix through the view-space position t_r = sum_k p_k vm[4k+r] (depth, the
+ * Jacobian, the 1.3 tanfov clamp) and the Jacobian product T = J W; projmatrix through the projected screen position;
+ * campos through the SH view direction (0 with colors_precomp).  vm[4k+3] and pm[4k+2] are never read: exactly 0.
+ * Discrete decisions (near cull, radius, tile rectangle, sort order) have no gradient.
+ * The outputs are WRITTEN (not accumulated), on the stream, by two launches behind the scene backward: one thread per
+ * Gaussian over the views, summed per workgroup in a fixed order into `cam_scratch`, then one workgroup per view summing
+ * its partials in a fixed order (deterministic; no float atomics). */
+typedef struct PgrCameraGrad {   /* device pointers, any NULL = not wanted; WRITTEN, not accumulated */
+    float *viewmatrix;           /* [16] same storage as PgrCamera::viewmatrix */
+    float *projmatrix;           /* [16] */
+    float *campos;               /* [3]  */
+} PgrCameraGrad;
+/* Device scratch of the camera kernels: 140 bytes per view and 256 Gaussians (0 for n < 0 or n_views <= 0). */
+size_t pgr_camera_grad_scratch_bytes(int32_t n, int32_t n_views);
+/* pgr_backward_ex plus the camera gradient of its view.  The scene gradients are exactly pgr_backward_ex's.
+ * PGR_ERR_INVALID_ARGUMENT before anything is enqueued: camera_grad NULL, cam_scratch NULL or smaller than
+ * pgr_camera_grad_scratch_bytes(n, 1), and every case pgr_backward_ex refuses. */
+int32_t pgr_backward_camera(const PgrScene *scene, const PgrCamera *camera, const float *grad_color,
+                            const float *grad_depth, const float *grad_alpha, const float *final_T,
+                            const uint32_t *n_contrib, const int32_t *radii, void *workspace, size_t workspace_bytes,
+                            int64_t max_instances, const PgrGradOutputs *grads, float *grad_rows,
+                            const PgrCameraGrad *camera_grad, void *cam_scratch, size_t cam_scratch_bytes, void *stream);
+/* pgr_backward_batch_ex plus every view's camera gradient: camera_grads is a HOST array of n_views entries (the outputs
+ * reach the device 16 views per launch, as the batch backward's table does).  The scene gradients are exactly
+ * pgr_backward_batch_ex's.  PGR_ERR_INVALID_ARGUMENT before anything is enqueued: camera_grads NULL, cam_scratch NULL or
+ * smaller than pgr_camera_grad_scratch_bytes(n, n_views), and every case pgr_backward_batch_ex refuses. */
+int32_t pgr_backward_batch_camera(const PgrScene *scene, int32_t n_views, const PgrCamera *cameras,
+                                  const PgrBackwardView *views, const float *const *grad_alpha, void *workspace,
+                                  size_t workspace_bytes, int64_t max_instances_per_view, const PgrGradOutputs *grads,
+                                  void *scratch, size_t scratch_bytes, const PgrCameraGrad *camera_grads,
+                                  void *cam_scratch, size_t cam_scratch_bytes, void *stream);
+
 /* present[i] = 1 iff Gaussian i passes the near-plane test of `viewmatrix` (device [16]). */
 int32_t pgr_mark_visible(int32_t n, const float *means3d, const float *viewmatrix, uint8_t *present,
                          void *stream);

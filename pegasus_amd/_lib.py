@@ -96,6 +96,10 @@ class PgrBackwardView(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("grad_color", "grad_depth", "final_T", "n_contrib", "radii")]
 
 
+class PgrCameraGrad(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("viewmatrix", "projmatrix", "campos")]
+
+
 class PgrWorkspaceView(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("splats", "rects", "gauss_sorted", "ranges", "num_instances")]
 
@@ -163,6 +167,15 @@ SYMBOLS = {
     "pgr_backward_batch_ex": (C.c_int32, [C.POINTER(PgrScene), C.c_int32, C.POINTER(PgrCamera),
                                           C.POINTER(PgrBackwardView), C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t,
                                           C.c_int64, C.POINTER(PgrGradOutputs), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pgr_camera_grad_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "pgr_backward_camera": (C.c_int32, [C.POINTER(PgrScene), C.POINTER(PgrCamera), C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64,
+                                        C.POINTER(PgrGradOutputs), C.c_void_p, C.POINTER(PgrCameraGrad), C.c_void_p,
+                                        C.c_size_t, C.c_void_p]),
+    "pgr_backward_batch_camera": (C.c_int32, [C.POINTER(PgrScene), C.c_int32, C.POINTER(PgrCamera),
+                                              C.POINTER(PgrBackwardView), C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t,
+                                              C.c_int64, C.POINTER(PgrGradOutputs), C.c_void_p, C.c_size_t,
+                                              C.POINTER(PgrCameraGrad), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pgr_compose_object": (C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                        C.POINTER(PgrObjectPose), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                        C.c_void_p]),

@@ -322,6 +322,54 @@ __device__ __forceinline__ void sh_basis_grad(float x, float y, float z, float b
     }
 }
 
+// The (DEG+1)^2 x 3 active SH coefficients of Gaussian i into shv (16-byte quads where the rows allow: sh_quads)
+template <int DEG>
+__device__ __forceinline__ void load_sh_active(const PgrScene& sc, int i, bool sh_quads, float* shv) {
+    constexpr int NC = (DEG + 1) * (DEG + 1);
+    const float* sh = sc.shs + (size_t)i * sc.sh_stride * 3;
+    if (sh_quads) {
+#pragma unroll
+        for (int q = 0; q < (3 * NC + 3) / 4; ++q) {
+            const float4 x = reinterpret_cast<const float4*>(sh)[q];
+            const float e[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (4 * q + c < 3 * NC) shv[4 * q + c] = e[c];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3 * NC; ++k) shv[k] = sh[k];
+    }
+}
+
+// The SH step of one view: the rgb gradient gc (zero on a channel clamped at 0) -> coefficients (ADDED to gsh) and the
+// unit view direction u (gu, set).  The direction u = (p - campos) / |p - campos| passes (gu - u (u . gu)) / |p - campos|
+// on to the mean, and its negative to campos.
+// load_sh_active and sh_backward are the camera kernel's.  preprocess_backward_batch_kernel keeps the same steps written
+// out in its body: called there, either helper changes how that kernel is scheduled (its ISA differs), and the existing
+// instances are held to the code they compiled to.
+template <int DEG>
+__device__ __forceinline__ void sh_backward(const float* shv, const float gc[3], const float u[3], float* gsh, float gu[3]) {
+    constexpr int NC = (DEG + 1) * (DEG + 1);
+    float bb[16], bx[16], by[16], bz[16];
+    sh_basis_grad<DEG>(u[0], u[1], u[2], bb, bx, by, bz);
+    gu[0] = 0.f; gu[1] = 0.f; gu[2] = 0.f;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        float accv = 0.f;
+#pragma unroll
+        for (int k = 0; k < NC; ++k) accv += bb[k] * shv[3 * k + ch];
+        const float g = (accv + 0.5f < 0.0f) ? 0.f : gc[ch];
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            gsh[3 * k + ch] += bb[k] * g;
+            gu[0] += g * shv[3 * k + ch] * bx[k];
+            gu[1] += g * shv[3 * k + ch] * by[k];
+            gu[2] += g * shv[3 * k + ch] * bz[k];
+        }
+    }
+}
+
 // 3D covariance of Gaussian i as the forward formed it (recomputed from scale / rotation, or the precomputed one)
 __device__ __forceinline__ void load_cov3d(const PgrScene& sc, int i, float cov[6]) {
     if (sc.cov3d_precomp) {
@@ -335,8 +383,16 @@ __device__ __forceinline__ void load_cov3d(const PgrScene& sc, int i, float cov[
 
 // One view's geometry chain for a Gaussian the view rendered: the compositor's row -> NDC-scaled screen gradient (gndc, set),
 // conic -> cov2D -> the six cov3D partials (gS, set) and the view-space / projected position -> mean gradient (ADDED to gp).
+// CAM (camera_backward_kernel): also the partials of the 32 matrix entries the forward reads, ADDED to gcam[0..31]
+// (viewmatrix [0..15], projmatrix [16..31], both in PgrCamera's transposed storage), from the same intermediate terms:
+//   the projection  h = p pm (row vector p = (x, y, z, 1)), ndc = h.xy / (h.w + 1e-7): dL/dpm[4k+c] = dL/dh_c p_k;
+//   the view space  t_r = p . vm[4k+r]: dL/dvm[4k+r] += gt_r p_k (gt: the full view-space gradient, depth and clamps in);
+//   the Jacobian    T = J W, W[r][k] = vm[4k+r]: dL/dvm[4k+0] += gT0_k j00, [4k+1] += gT1_k j11, [4k+2] += gT0_k j02 + gT1_k j12.
+// vm[4k+3] and pm[4k+2] are never read and receive nothing.  The CAM = false instance is the chain as it was before.
+template <bool CAM = false>
 __device__ __forceinline__ void view_geometry_backward(const CameraDev& cam, const float* row, const float p[3],
-                                                       const float cov[6], float gp[3], float gS[6], float gndc[2]) {
+                                                       const float cov[6], float gp[3], float gS[6], float gndc[2],
+                                                       float* gcam = nullptr) {
     const float* vm = cam.view;
     const float* pm = cam.proj;
     // ---- screen position
@@ -351,6 +407,16 @@ __device__ __forceinline__ void view_geometry_backward(const CameraDev& cam, con
         for (int k = 0; k < 3; ++k)
             gp[k] += gndc[0] * (pm[4 * k + 0] * mw - hx * mw * mw * pm[4 * k + 3]) +
                      gndc[1] * (pm[4 * k + 1] * mw - hy * mw * mw * pm[4 * k + 3]);
+        if constexpr (CAM) {
+            const float ghx = gndc[0] * mw, ghy = gndc[1] * mw, ghw = -(gndc[0] * hx + gndc[1] * hy) * mw * mw;
+            const float ph[4] = {p[0], p[1], p[2], 1.0f};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                gcam[16 + 4 * k + 0] += ghx * ph[k];
+                gcam[16 + 4 * k + 1] += ghy * ph[k];
+                gcam[16 + 4 * k + 3] += ghw * ph[k];
+            }
+        }
     }
     // ---- view-space position
     float t[3];
@@ -402,6 +468,11 @@ __device__ __forceinline__ void view_geometry_backward(const CameraDev& cam, con
         const float gT0 = 2 * ga * s0 + gb * s1, gT1 = 2 * gc * s1 + gb * s0;
         gj00 += gT0 * vm[4 * k + 0]; gj02 += gT0 * vm[4 * k + 2];
         gj11 += gT1 * vm[4 * k + 1]; gj12 += gT1 * vm[4 * k + 2];
+        if constexpr (CAM) {
+            gcam[4 * k + 0] += gT0 * j00;
+            gcam[4 * k + 1] += gT1 * j11;
+            gcam[4 * k + 2] += gT0 * j02 + gT1 * j12;
+        }
     }
     const float tz2 = 1.0f / (t[2] * t[2]), tz3 = tz2 / t[2];
     gt[0] += xmul * -fx * tz2 * gj02;
@@ -411,6 +482,13 @@ __device__ __forceinline__ void view_geometry_backward(const CameraDev& cam, con
     if (ymul == 0.f) gt[2] += -fy * tz2 * gj12 * (cy / t[2]);
 #pragma unroll
     for (int k = 0; k < 3; ++k) gp[k] += vm[4 * k + 0] * gt[0] + vm[4 * k + 1] * gt[1] + vm[4 * k + 2] * gt[2];
+    if constexpr (CAM) {
+        const float ph[4] = {p[0], p[1], p[2], 1.0f};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int r = 0; r < 3; ++r) gcam[4 * k + r] += gt[r] * ph[k];
+    }
 }
 
 // cov3D = (R S)(R S)^T -> scale and rotation (gS: the six partials of cov3D; linear in them)
@@ -566,6 +644,132 @@ __global__ __launch_bounds__(256, ONE && DEG < 2 ? 8 : 1) void preprocess_backwa
     if (o.cov3d) {
 #pragma unroll
         for (int k = 0; k < 6; ++k) o.cov3d[6 * (size_t)i + k] = gS[k];
+    }
+}
+
+// ---- camera backward (pgr_backward_camera / pgr_backward_batch_camera) -------------------------------------------------
+// The exact partials of the loss with respect to the 35 camera numbers the forward reads per view (viewmatrix [16],
+// projmatrix [16], campos [3]; treated as independent inputs), after the two launches above and from their rows:
+//   camera_backward_kernel      one thread per Gaussian over the views in order, as preprocess_backward_batch_kernel: the
+//       view's geometry chain (view_geometry_backward<true>) and SH step (sh_backward: dL/dcampos = -(gu - u (u . gu)) / len)
+//       of every Gaussian the view rendered, summed over the workgroup in a fixed order -- within each row of 16 lanes by
+//       DPP shifts, the 16 row totals through LDS -- into one CAM_GRAD-float partial per (view, workgroup);
+//   camera_grad_finish_kernel   one workgroup per view: the view's partials summed in a fixed order, WRITTEN to the caller's
+//       outputs.  No float atomics: every workgroup adding into one 35-float row would serialise on it.
+// Discrete decisions (near cull, radius and tile rectangle, sort order) have no gradient; Gaussians a view did not render
+// (radii 0) or a view that overflowed contribute nothing.
+constexpr int CAM_GRAD = 35;
+constexpr int CAM_BLOCK = 256;                 // threads per workgroup of both kernels: 16 rows of 16 lanes
+
+template <int CTRL>
+__device__ __forceinline__ float dpp_shift(float v) {      // row_shr / bound_ctrl: lanes shifted in from outside the row read 0
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
+}
+
+// Sum of g[k] over the CAM_BLOCK threads of the workgroup, returned to thread k (k < CAM_GRAD); every thread must call it.
+// Inclusive scans over each row of 16 lanes (row_shr 1, 2, 4, 8: lane 15 ends with the row's sum), the 16 row sums through
+// LDS, added in row order.  Deterministic: the same inputs give the same bits.
+__device__ __forceinline__ float camera_block_sum(const float g[CAM_GRAD], float* s_red) {
+    const int t = threadIdx.x, row = t >> 4;
+#pragma unroll
+    for (int k = 0; k < CAM_GRAD; ++k) {
+        float v = g[k];
+        v += dpp_shift<0x111>(v);
+        v += dpp_shift<0x112>(v);
+        v += dpp_shift<0x114>(v);
+        v += dpp_shift<0x118>(v);
+        if ((t & 15) == 15) s_red[row * CAM_GRAD + k] = v;
+    }
+    __syncthreads();
+    float tot = 0.f;
+    if (t < CAM_GRAD) {
+#pragma unroll
+        for (int r = 0; r < CAM_BLOCK / 16; ++r) tot += s_red[r * CAM_GRAD + t];
+    }
+    __syncthreads();      // s_red is rewritten by the next call
+    return tot;
+}
+
+// partials [n_views, gridDim.x, CAM_GRAD]: every (view, workgroup) entry is written.  ONE: the one-view instance.
+template <int DEG, bool ONE>
+__global__ __launch_bounds__(CAM_BLOCK) void camera_backward_kernel(PgrScene sc, const BwdViewDev* __restrict__ views,
+                                                                    const CameraDev* __restrict__ cams, int n_views,
+                                                                    float* __restrict__ partials) {
+    if (ONE) n_views = 1;
+    constexpr int NC = (DEG + 1) * (DEG + 1);
+    __shared__ float s_red[(CAM_BLOCK / 16) * CAM_GRAD];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool real = i < sc.n;          // (threads past the end take part in the sums with zeros)
+    const bool sh_quads = sc.shs && sc.sh_stride == 16 && (reinterpret_cast<uintptr_t>(sc.shs) & 15u) == 0;
+    float p[3] = {0.f, 0.f, 0.f};
+    if (real) { p[0] = sc.means3d[3 * i]; p[1] = sc.means3d[3 * i + 1]; p[2] = sc.means3d[3 * i + 2]; }
+    float cov[6], shv[3 * NC];
+#pragma unroll
+    for (int k = 0; k < 3 * NC; ++k) shv[k] = 0.f;
+    bool have = false;
+    for (int v = 0; v < n_views; ++v) {
+        const BwdViewDev& bv = views[v];
+        float g[CAM_GRAD];
+#pragma unroll
+        for (int k = 0; k < CAM_GRAD; ++k) g[k] = 0.f;
+        if (real && gload(bv.radii + i) > 0 && !gload(bv.counters + 1)) {
+            if (!have) {
+                load_cov3d(sc, i, cov);
+                if (sc.shs) load_sh_active<DEG>(sc, i, sh_quads, shv);
+                have = true;
+            }
+            const CameraDev& cam = cams[v];
+            const float* row = bv.rows + (size_t)i * GRAD_ROW;
+            float gp[3] = {0.f, 0.f, 0.f}, gS[6], gndc[2];
+            view_geometry_backward<true>(cam, row, p, cov, gp, gS, gndc, g);
+            if (sc.shs) {
+                const float gc[3] = {row[6], row[7], row[8]};
+                const float d[3] = {p[0] - cam.campos[0], p[1] - cam.campos[1], p[2] - cam.campos[2]};
+                const float len = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+                const float u[3] = {d[0] / len, d[1] / len, d[2] / len};
+                float gsh[3 * NC], gu[3];
+#pragma unroll
+                for (int k = 0; k < 3 * NC; ++k) gsh[k] = 0.f;
+                sh_backward<DEG>(shv, gc, u, gsh, gu);
+                const float dot = u[0] * gu[0] + u[1] * gu[1] + u[2] * gu[2];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) g[32 + k] = -(gu[k] - u[k] * dot) / len;
+            }
+        }
+        const float tot = camera_block_sum(g, s_red);
+        if (threadIdx.x < CAM_GRAD) partials[((size_t)v * gridDim.x + blockIdx.x) * CAM_GRAD + threadIdx.x] = tot;
+    }
+}
+
+// The caller's outputs of up to BWD_TABLE_CHUNK views per launch (kernel arguments), any NULL = not wanted
+struct CamGradChunk {
+    float* view[BWD_TABLE_CHUNK];
+    float* proj[BWD_TABLE_CHUNK];
+    float* campos[BWD_TABLE_CHUNK];
+};
+
+// One workgroup per view of the chunk (view v0 + blockIdx.x): its n_parts partials summed, thread b taking the partials
+// b, b + CAM_BLOCK, ... in order, then camera_block_sum.
+__global__ __launch_bounds__(CAM_BLOCK) void camera_grad_finish_kernel(const float* __restrict__ partials, int n_parts,
+                                                                       int v0, CamGradChunk out) {
+    __shared__ float s_red[(CAM_BLOCK / 16) * CAM_GRAD];
+    const int vl = blockIdx.x;
+    const float* src = partials + (size_t)(v0 + vl) * n_parts * CAM_GRAD;
+    float g[CAM_GRAD];
+#pragma unroll
+    for (int k = 0; k < CAM_GRAD; ++k) g[k] = 0.f;
+    for (int b = threadIdx.x; b < n_parts; b += CAM_BLOCK) {
+#pragma unroll
+        for (int k = 0; k < CAM_GRAD; ++k) g[k] += gload(src + (size_t)b * CAM_GRAD + k);
+    }
+    const float tot = camera_block_sum(g, s_red);
+    const int t = threadIdx.x;
+    if (t < 16) {
+        if (out.view[vl]) out.view[vl][t] = tot;
+    } else if (t < 32) {
+        if (out.proj[vl]) out.proj[vl][t - 16] = tot;
+    } else if (t < CAM_GRAD) {
+        if (out.campos[vl]) out.campos[vl][t - 32] = tot;
     }
 }
 

@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "backward.hip.h"
@@ -563,6 +564,46 @@ static int32_t backward_impl(const PgrScene* scene, int n_views, const PgrBackwa
     return hip_ok(hipGetLastError(), "backward launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
 }
 
+// The camera kernels behind a finished backward_impl: `table` and the packed cameras as it left them, the outputs of up to
+// BWD_TABLE_CHUNK views per finishing launch (kernel arguments).  An empty scene writes zeros.
+static size_t camera_scratch_bytes(int32_t n, int32_t n_views) {
+    return align_up((size_t)n_views * (size_t)((n + CAM_BLOCK - 1) / CAM_BLOCK) * CAM_GRAD * sizeof(float) + 1);
+}
+
+static int32_t camera_backward_impl(const PgrScene* scene, int n_views, const PgrCameraGrad* cg, const BwdViewDev* table,
+                                    const CameraDev* cams_dev, float* partials, hipStream_t stream) {
+    const int N = scene->n;
+    if (N == 0) {
+        for (int v = 0; v < n_views; ++v) {
+            const std::pair<float*, size_t> outs[3] = {{cg[v].viewmatrix, 16}, {cg[v].projmatrix, 16}, {cg[v].campos, 3}};
+            for (const auto& o : outs)
+                if (o.first && !hip_ok(hipMemsetAsync(o.first, 0, o.second * sizeof(float), stream), "memset camera grad"))
+                    return PGR_ERR_LAUNCH_FAILURE;
+        }
+        return PGR_OK;
+    }
+    const int blocks = (N + CAM_BLOCK - 1) / CAM_BLOCK;
+    const bool one = n_views == 1;
+    constexpr decltype(&camera_backward_kernel<0, false>) cks[4][2] = {
+        {camera_backward_kernel<0, false>, camera_backward_kernel<0, true>},
+        {camera_backward_kernel<1, false>, camera_backward_kernel<1, true>},
+        {camera_backward_kernel<2, false>, camera_backward_kernel<2, true>},
+        {camera_backward_kernel<3, false>, camera_backward_kernel<3, true>}};
+    cks[scene->shs ? scene->sh_degree : 0][one]<<<blocks, CAM_BLOCK, 0, stream>>>(*scene, table, cams_dev, n_views, partials);
+    for (int v0 = 0; v0 < n_views; v0 += BWD_TABLE_CHUNK) {
+        const int cnt = std::min(BWD_TABLE_CHUNK, n_views - v0);
+        CamGradChunk chunk;
+        memset(&chunk, 0, sizeof(chunk));
+        for (int k = 0; k < cnt; ++k) {
+            chunk.view[k] = cg[v0 + k].viewmatrix;
+            chunk.proj[k] = cg[v0 + k].projmatrix;
+            chunk.campos[k] = cg[v0 + k].campos;
+        }
+        camera_grad_finish_kernel<<<cnt, CAM_BLOCK, 0, stream>>>(partials, blocks, v0, chunk);
+    }
+    return hip_ok(hipGetLastError(), "camera backward launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
 // The one-view table entry lives in the forward's `tables` region, which the backward never reads and the next forward
 // rewrites; at one view that region holds a ViewEntry, a BinView and a PreOut.
 static_assert(sizeof(BwdViewDev) <= sizeof(ViewEntry) + sizeof(BinView) + sizeof(PreOut),
@@ -823,6 +864,51 @@ int32_t pgr_backward_batch_ex(const PgrScene* scene, int32_t n_views, const PgrC
     auto* table = reinterpret_cast<BwdViewDev*>(static_cast<char*>(scratch) + align_up(rows_bytes));
     return backward_impl(scene, n_views, views, grad_alpha, static_cast<char*>(workspace), L, B, grads,
                          static_cast<float*>(scratch), table, static_cast<hipStream_t>(stream_v));
+}
+
+size_t pgr_camera_grad_scratch_bytes(int32_t n, int32_t n_views) {
+    if (n < 0 || n_views <= 0) return 0;
+    return camera_scratch_bytes(n, n_views);
+}
+
+int32_t pgr_backward_camera(const PgrScene* scene, const PgrCamera* cam, const float* grad_color, const float* grad_depth,
+                            const float* grad_alpha, const float* final_T, const uint32_t* n_contrib, const int32_t* radii,
+                            void* workspace, size_t workspace_bytes, int64_t max_instances, const PgrGradOutputs* grads,
+                            float* grad_rows, const PgrCameraGrad* camera_grad, void* cam_scratch, size_t cam_scratch_bytes,
+                            void* stream_v) {
+    if (!camera_grad || !scene || scene->n < 0 || !cam_scratch || cam_scratch_bytes < camera_scratch_bytes(scene->n, 1))
+        return PGR_ERR_INVALID_ARGUMENT;
+    const int32_t rc = pgr_backward_ex(scene, cam, grad_color, grad_depth, grad_alpha, final_T, n_contrib, radii, workspace,
+                                       workspace_bytes, max_instances, grads, grad_rows, stream_v);
+    if (rc != PGR_OK) return rc;
+    const int N = scene->n;
+    const Layout L = make_layout(N, cam->image_width, cam->image_height, max_instances);
+    const BatchLayout B = make_batch_layout(L, 1, (size_t)N);
+    char* ws = static_cast<char*>(workspace);
+    return camera_backward_impl(scene, 1, camera_grad, reinterpret_cast<const BwdViewDev*>(ws + B.tables),
+                                reinterpret_cast<const CameraDev*>(ws + B.cams), static_cast<float*>(cam_scratch),
+                                static_cast<hipStream_t>(stream_v));
+}
+
+int32_t pgr_backward_batch_camera(const PgrScene* scene, int32_t n_views, const PgrCamera* cameras,
+                                  const PgrBackwardView* views, const float* const* grad_alpha, void* workspace,
+                                  size_t workspace_bytes, int64_t max_instances_per_view, const PgrGradOutputs* grads,
+                                  void* scratch, size_t scratch_bytes, const PgrCameraGrad* camera_grads, void* cam_scratch,
+                                  size_t cam_scratch_bytes, void* stream_v) {
+    if (!camera_grads || !scene || scene->n < 0 || n_views <= 0 || !cam_scratch ||
+        cam_scratch_bytes < camera_scratch_bytes(scene->n, n_views))
+        return PGR_ERR_INVALID_ARGUMENT;
+    const int32_t rc = pgr_backward_batch_ex(scene, n_views, cameras, views, grad_alpha, workspace, workspace_bytes,
+                                             max_instances_per_view, grads, scratch, scratch_bytes, stream_v);
+    if (rc != PGR_OK) return rc;
+    const int N = scene->n;
+    const Layout L = make_layout(N, cameras[0].image_width, cameras[0].image_height, max_instances_per_view);
+    const BatchLayout B = make_batch_layout(L, n_views, (size_t)N);
+    const size_t rows_bytes = (size_t)n_views * (size_t)N * GRAD_ROW * sizeof(float);
+    return camera_backward_impl(scene, n_views, camera_grads,
+                                reinterpret_cast<const BwdViewDev*>(static_cast<char*>(scratch) + align_up(rows_bytes)),
+                                reinterpret_cast<const CameraDev*>(static_cast<char*>(workspace) + B.cams),
+                                static_cast<float*>(cam_scratch), static_cast<hipStream_t>(stream_v));
 }
 
 int32_t pgr_compose_object(int32_t n, const float* xyz, const float* rot, const float* f_rest, int32_t n_rest,

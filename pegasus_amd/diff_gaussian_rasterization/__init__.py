@@ -11,6 +11,14 @@ Same surface as the module the reference installs from its (absent) submodule
         -> (color[3,H,W], radii[N] int32, depth[1,H,W])  (+ alpha[1,H,W] = 1 - final_T with return_alpha)
     GaussianRasterizer.markVisible(positions) -> bool[N]
 
+Camera gradients: the viewmatrix, projmatrix and campos tensors of the settings are differentiable inputs too.  When
+autograd is on and any of them requires grad, the render takes the differentiable path even if no scene tensor does (a
+frozen model rendered from a camera being refined), and their .grad receives the exact partial of the loss with respect
+to each of their entries, each treated as an independent input (pgr_backward_camera / pgr_backward_batch_camera;
+entries the forward never reads -- viewmatrix[4k+3], projmatrix[4k+2] -- get 0, campos gets 0 with colors_precomp).
+A camera built from a pose (pegasus_amd.camera_pose.PosedCamera) passes them on to the pose through torch.  Without a
+camera tensor that requires grad the call and its launches are those of a scene-only backward.
+
 The compute is libpegasus_raster.so (hand-written HIP for gfx950) reached through its C ABI
 (include/pegasus_raster.h); tensors are passed as raw device pointers, work is enqueued on
 torch's current stream, and memory comes from torch's caching allocator.  No CPU fallback.
@@ -117,11 +125,15 @@ class _RasterizeGaussians(torch.autograd.Function):
     lists, final_T and n_contrib.  The cameras are not re-read: the backward takes the packed ones from the workspace.
 
     With ``return_alpha`` a fourth output, alpha [V,1,H,W] = 1 - final_T, is differentiable: its gradient reaches the
-    backward as grad_alpha (NULL when it got none)."""
+    backward as grad_alpha (NULL when it got none).
+
+    ``cam_inputs``: empty, or the 3 V tensors (viewmatrix, projmatrix, campos of every view, None allowed) passed when one of
+    them requires grad (``_camera_inputs``).  They are the tensors ``settings`` holds, handed to ``apply`` so that autograd
+    tracks them; the backward then goes through the camera entries and returns their gradients shaped like them."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, single,
-                return_alpha=False):
+                return_alpha=False, *cam_inputs):
         L = _lib.lib()
         settings = tuple(settings)
         V = len(settings)
@@ -175,6 +187,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             _lib.check(status, "pgr_forward" if single else "pgr_forward_batch")
         ctx.hw, ctx.V, ctx.n, ctx.max_inst, ctx.single = (H, W), V, n, max_inst, single
         ctx.sh_degree, ctx.scale_modifier = int(rs0.sh_degree), float(rs0.scale_modifier)
+        ctx.cam_meta = tuple(None if x is None else (tuple(x.shape), x.dtype) for x in cam_inputs)
         # non-tensor state stays on ctx; tensors (inputs as the kernels read them + the forward's own buffers) are saved
         ctx.present = tuple(k for k in _SCENE_KEYS if t[k] is not None)
         ctx.op_shape = tuple(opacities.shape)
@@ -219,8 +232,24 @@ class _RasterizeGaussians(torch.autograd.Function):
         gd = None if grad_depth is None else grad_depth.contiguous().float()
         ga = None if grad_alpha is None else grad_alpha.contiguous().float()
         stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        # camera gradients: [V, 35] written by the camera kernels (only the wanted ones get a pointer)
+        want_cam = [m is not None and ctx.needs_input_grad[11 + j] for j, m in enumerate(ctx.cam_meta)]
+        cam_g = cam_structs = cam_scratch = None
+        if any(want_cam):
+            cam_g = torch.empty((V, 35), dtype=torch.float32, device=device)
+            sl = ((0, 16), (16, 32), (32, 35))
+            cam_structs = (_lib.PgrCameraGrad * V)(*[_lib.PgrCameraGrad(*[
+                _ptr(cam_g[v, a:b]) if want_cam[3 * v + c] else None for c, (a, b) in enumerate(sl)]) for v in range(V)])
+            cam_scratch = torch.empty(L.pgr_camera_grad_scratch_bytes(n, V), dtype=torch.uint8, device=device)
         with torch.cuda.device(device):
-            if single:
+            if single and cam_g is not None:
+                rows = torch.empty((n, 12), dtype=torch.float32, device=device)
+                _lib.check(L.pgr_backward_camera(C.byref(scene), cams, _ptr(gc), _ptr(gd), _ptr(ga), _ptr(final_T),
+                                                 _ptr(n_contrib), _ptr(radii), C.c_void_p(ws.data_ptr()), ws.numel(),
+                                                 ctx.max_inst, C.byref(grads), _ptr(rows), cam_structs,
+                                                 C.c_void_p(cam_scratch.data_ptr()), cam_scratch.numel(), stream),
+                           "pgr_backward_camera")
+            elif single:
                 rows = torch.empty((n, 12), dtype=torch.float32, device=device)
                 _lib.check(L.pgr_backward_ex(C.byref(scene), cams, _ptr(gc), _ptr(gd), _ptr(ga), _ptr(final_T),
                                              _ptr(n_contrib), _ptr(radii), C.c_void_p(ws.data_ptr()), ws.numel(),
@@ -232,13 +261,33 @@ class _RasterizeGaussians(torch.autograd.Function):
                                          final_T=_ptr(final_T[v]), n_contrib=_ptr(n_contrib[v]), radii=_ptr(radii[v]))
                     for v in range(V)])
                 scratch = torch.empty(max(1, L.pgr_backward_batch_scratch_bytes(n, V)), dtype=torch.uint8, device=device)
-                _lib.check(L.pgr_backward_batch_ex(C.byref(scene), V, cams, views, alpha_ptrs, C.c_void_p(ws.data_ptr()),
-                                                   ws.numel(), ctx.max_inst, C.byref(grads),
-                                                   C.c_void_p(scratch.data_ptr()), scratch.numel(), stream),
-                           "pgr_backward_batch_ex")
-        # means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, single, return_alpha
+                if cam_g is not None:
+                    _lib.check(L.pgr_backward_batch_camera(C.byref(scene), V, cams, views, alpha_ptrs,
+                                                           C.c_void_p(ws.data_ptr()), ws.numel(), ctx.max_inst,
+                                                           C.byref(grads), C.c_void_p(scratch.data_ptr()), scratch.numel(),
+                                                           cam_structs, C.c_void_p(cam_scratch.data_ptr()),
+                                                           cam_scratch.numel(), stream), "pgr_backward_batch_camera")
+                else:
+                        _lib.check(L.pgr_backward_batch_ex(C.byref(scene), V, cams, views, alpha_ptrs,
+                                                       C.c_void_p(ws.data_ptr()), ws.numel(), ctx.max_inst, C.byref(grads),
+                                                       C.c_void_p(scratch.data_ptr()), scratch.numel(), stream),
+                               "pgr_backward_batch_ex")
+        sl = ((0, 16), (16, 32), (32, 35))
+        cam_out = tuple(cam_g[j // 3, sl[j % 3][0]:sl[j % 3][1]].reshape(m[0]).to(m[1]) if want_cam[j] else None
+                        for j, m in enumerate(ctx.cam_meta))
+        # means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, single, return_alpha,
+        # then the camera tensors
         return (g["means3d"], g["means2d"], g.get("shs"), g.get("colors"), g["opacities"].view(ctx.op_shape),
-                g.get("scales"), g.get("rotations"), g.get("cov3d"), None, None, None)
+                g.get("scales"), g.get("rotations"), g.get("cov3d"), None, None, None) + cam_out
+
+
+def _camera_inputs(settings) -> tuple:
+    """The camera tensors of ``settings`` as extra ``_RasterizeGaussians`` inputs: all 3 V of them (viewmatrix, projmatrix,
+    campos per view) when autograd is on and one of them requires grad, else none (the scene-only call)."""
+    cams = tuple(x for rs in settings for x in (rs.viewmatrix, rs.projmatrix, rs.campos))
+    if torch.is_grad_enabled() and any(isinstance(x, torch.Tensor) and x.requires_grad for x in cams):
+        return tuple(x if isinstance(x, torch.Tensor) else None for x in cams)
+    return ()
 
 
 def rasterize_gaussians_batch(means3D, means2D, opacities, raster_settings, shs=None, colors_precomp=None, scales=None,
@@ -247,7 +296,8 @@ def rasterize_gaussians_batch(means3D, means2D, opacities, raster_settings, shs=
     GaussianRasterizationSettings with one image size.  Returns (color [V,3,H,W], radii [V,n] int32, depth [V,1,H,W]), and
     with ``return_alpha`` also alpha [V,1,H,W] = 1 - final_T (differentiable).
     ``means2D`` (or None) is [V,n,3]; its .grad receives each view's screen-space gradient.  Every other input's gradient
-    is the sum over the views."""
+    is the sum over the views.  A view's viewmatrix / projmatrix / campos that requires grad receives that view's camera
+    gradient."""
     if (shs is None) == (colors_precomp is None):
         raise ValueError("rasterize_gaussians_batch: provide exactly one of shs and colors_precomp")
     if ((scales is None or rotations is None) and cov3D_precomp is None) or \
@@ -257,7 +307,7 @@ def rasterize_gaussians_batch(means3D, means2D, opacities, raster_settings, shs=
     if means2D is None:
         means2D = torch.zeros((len(settings), int(means3D.shape[0]), 3), dtype=torch.float32, device=means3D.device)
     return _RasterizeGaussians.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                     settings, False, bool(return_alpha))
+                                     settings, False, bool(return_alpha), *_camera_inputs(settings))
 
 
 class GaussianRasterizer(nn.Module):
@@ -293,11 +343,12 @@ class GaussianRasterizer(nn.Module):
                 ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
         inputs = (means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp)
-        if torch.is_grad_enabled() and any(x is not None and x.requires_grad for x in inputs):
+        cams = _camera_inputs((self.raster_settings,))
+        if cams or (torch.is_grad_enabled() and any(x is not None and x.requires_grad for x in inputs)):
             if means2D is None:
                 means2D = torch.zeros_like(means3D, requires_grad=False)
             return _RasterizeGaussians.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                             cov3D_precomp, (self.raster_settings,), True, bool(return_alpha))
+                                             cov3D_precomp, (self.raster_settings,), True, bool(return_alpha), *cams)
         with torch.no_grad():
             if return_alpha:
                 color, radii, depth, final_T, _ = rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities,

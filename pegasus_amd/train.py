@@ -17,6 +17,12 @@ the step's own background, plus lambda_alpha mean|alpha - mask|, whose gradient 
 
 With --batch_size B > 1 a step renders B views in one render_batch (pgr_forward_batch / pgr_backward_batch) and the Adam
 step, which touches every parameter whatever the number of views, is paid once per B views.
+
+With --pose_lr > 0 the training cameras' poses are refined with the Gaussians (scans whose registration is slightly off):
+every training camera gets a pose correction (pegasus_amd.camera_pose.PosedCamera), a 6-vector that the camera gradient
+of the rasterizer (pgr_backward_camera) reaches through torch, updated by its own Adam (rotation lr pose_lr, translation lr
+pose_lr x cameras_extent) with the Gaussian optimiser's step.  The train report renders the refined cameras, test cameras
+keep their poses, every save writes cameras_refined.json and every checkpoint the corrections to chkpntN_poses.pth.
 """
 from __future__ import annotations
 
@@ -45,6 +51,8 @@ MODEL_DEFAULTS = dict(sh_degree=3, source_path="", model_path="", images="images
                       white_background=False, data_device="cuda", eval=False)
 # training from object masks (dataset.masks, opt.lambda_alpha; compat/arguments ModelParams / OptimizationParams carry them)
 MASK_DEFAULTS = dict(masks="", lambda_alpha=0.5)
+# camera pose refinement while training (opt.pose_lr; 0 = off)
+POSE_DEFAULTS = dict(pose_lr=0.0)
 MIN_OPACITY = 0.005                      # densify_and_prune's opacity floor
 SCREEN_SIZE_LIMIT = 20                   # pixels: the screen-radius prune once the first opacity reset has happened
 
@@ -152,8 +160,9 @@ def evaluate(cameras, gaussians, pipe, background) -> tuple:
     return (sum(l1s) / len(l1s), sum(psnrs) / len(psnrs)) if cameras else (float("nan"), float("nan"))
 
 
-def training_report(iteration, scene, gaussians, pipe, background, quiet=False) -> dict:
-    train = scene.getTrainCameras()
+def training_report(iteration, scene, gaussians, pipe, background, quiet=False, train_cameras=None) -> dict:
+    """``train_cameras``: the training cameras to evaluate (default: the scene's; pose refinement passes its refined ones)."""
+    train = scene.getTrainCameras() if train_cameras is None else train_cameras
     configs = {"test": scene.getTestCameras(), "train": [train[i % len(train)] for i in range(5, 30, 5)] if train else []}
     out = {}
     for name, cams in configs.items():
@@ -228,6 +237,44 @@ def train_step_batch(gaussians, cams, pipe, bg, lambda_dssim, lambda_alpha=None)
     return loss, pkg
 
 
+class PoseRefinement:
+    """The pose corrections of the training cameras (``--pose_lr``): a zero 6-vector leaf per camera, stored in units that
+    give one Adam learning rate the two step sizes (rotation pose_lr, translation pose_lr x extent), and the PosedCamera
+    each step renders through."""
+
+    def __init__(self, cameras, pose_lr: float, extent: float, device):
+        from .camera_pose import PosedCamera
+        self.cameras = list(cameras)
+        self.scale = torch.tensor([1.0, 1.0, 1.0, extent, extent, extent], dtype=torch.float32, device=device)
+        self.leaves = [torch.zeros(6, dtype=torch.float32, device=device, requires_grad=True) for _ in self.cameras]
+        self.posed = {id(c): PosedCamera(c, torch.zeros(6, device=device)) for c in self.cameras}
+        self._leaf = {id(c): u for c, u in zip(self.cameras, self.leaves)}
+        self.optimizer = torch.optim.Adam(self.leaves, lr=float(pose_lr))
+
+    def view(self, cam):
+        """``cam`` through its current correction (differentiable in it)."""
+        p = self.posed[id(cam)]
+        p.delta = self._leaf[id(cam)] * self.scale
+        return p
+
+    def deltas(self):
+        return {c.image_name: (u.detach() * self.scale).cpu() for c, u in zip(self.cameras, self.leaves)}
+
+    def refined(self):
+        """Plain Cameras of the refined poses (no gradient)."""
+        from .camera_pose import PosedCamera
+        return [PosedCamera(c, (u.detach() * self.scale)).refined() for c, u in zip(self.cameras, self.leaves)]
+
+    def write_json(self, path):
+        cams = self.refined()
+        with open(path, "w") as f:
+            json.dump([camera_to_JSON(i, c) for i, c in enumerate(cams)], f)
+
+    def step(self):
+        self.optimizer.step()
+        self.optimizer.zero_grad(set_to_none=True)
+
+
 def training(dataset, opt, pipe, testing_iterations, saving_iterations, checkpoint_iterations, checkpoint, debug_from,
              quiet=False, batch_size=None):
     """Trains a Gaussian model on ``dataset.source_path`` (COLMAP) into ``dataset.model_path``.  Returns
@@ -252,6 +299,9 @@ def training(dataset, opt, pipe, testing_iterations, saving_iterations, checkpoi
                          "convert_SHs_python is not supported with it")
     masked = _Options(dataset, {"masks": MASK_DEFAULTS["masks"]}).masks or ""
     lambda_alpha = float(_Options(opt, {"lambda_alpha": MASK_DEFAULTS["lambda_alpha"]}).lambda_alpha)
+    pose_lr = float(_Options(opt, POSE_DEFAULTS).pose_lr)
+    if pose_lr < 0.0:
+        raise ValueError(f"pose_lr must be >= 0, got {pose_lr}")
     if lambda_alpha < 0.0:
         raise ValueError(f"lambda_alpha must be >= 0, got {lambda_alpha}")
     opt = _Options(opt, OPTIMIZATION_DEFAULTS)
@@ -272,6 +322,8 @@ def training(dataset, opt, pipe, testing_iterations, saving_iterations, checkpoi
         gaussians.restore(model_params, opt)
     dev = gaussians._xyz.device
     background = torch.tensor([1, 1, 1] if dataset.white_background else [0, 0, 0], dtype=torch.float32, device=dev)
+    poses = PoseRefinement(scene.getTrainCameras(), pose_lr, scene.cameras_extent, dev) if pose_lr > 0.0 else None
+    posed = (lambda c: c) if poses is None else poses.view
     iterations = int(opt.iterations)
     stack = None
     reports = {}
@@ -288,7 +340,7 @@ def training(dataset, opt, pipe, testing_iterations, saving_iterations, checkpoi
             if iteration - 1 == debug_from:
                 pipe.debug = True
             bg = torch.rand(3, device=dev) if opt.random_background else background
-            pkg = render(cam, gaussians, pipe, bg, return_alpha=bool(masked))
+            pkg = render(posed(cam), gaussians, pipe, bg, return_alpha=bool(masked))
             image, viewspace, radii = pkg["render"], pkg["viewspace_points"], pkg["radii"]
             if masked:
                 loss = MaskedImageLoss.apply(image, pkg["alpha"], cam.original_image, cam.gt_mask, bg,
@@ -301,16 +353,19 @@ def training(dataset, opt, pipe, testing_iterations, saving_iterations, checkpoi
             if iteration - 1 == debug_from:
                 pipe.debug = True
             bg = torch.rand((batch_size, 3), device=dev) if opt.random_background else background
-            loss, pkg = train_step_batch(gaussians, cams, pipe, bg, opt.lambda_dssim,
+            loss, pkg = train_step_batch(gaussians, [posed(c) for c in cams], pipe, bg, opt.lambda_dssim,
                                          lambda_alpha if masked else None)
             viewspace, radii = pkg["viewspace_points"], pkg["radii"]
         with torch.no_grad():
             if iteration in testing_iterations:
-                reports[iteration] = training_report(iteration, scene, gaussians, pipe, background, quiet)
+                reports[iteration] = training_report(iteration, scene, gaussians, pipe, background, quiet,
+                                                     None if poses is None else poses.refined())
             if iteration in saving_iterations:
                 if not quiet:
                     print(f"\n[ITER {iteration}] Saving Gaussians")
                 scene.save(iteration)
+                if poses is not None:
+                    poses.write_json(os.path.join(dataset.model_path, "cameras_refined.json"))
             if iteration < opt.densify_until_iter:
                 if batch_size == 1:
                     gaussians.add_render_stats(viewspace, radii)
@@ -326,18 +381,25 @@ def training(dataset, opt, pipe, testing_iterations, saving_iterations, checkpoi
             if iteration < iterations:
                 gaussians.optimizer.step()
                 gaussians.optimizer.zero_grad(set_to_none=True)
+                if poses is not None:
+                    poses.step()
             if iteration in checkpoint_iterations:
                 if not quiet:
                     print(f"\n[ITER {iteration}] Saving Checkpoint")
                 torch.save((gaussians.capture(), iteration),
                            os.path.join(dataset.model_path, f"chkpnt{iteration}.pth"))
-    return {"reports": reports, "num_gaussians": int(gaussians.get_xyz.shape[0]), "model": gaussians}
+                if poses is not None:
+                    torch.save(poses.deltas(), os.path.join(dataset.model_path, f"chkpnt{iteration}_poses.pth"))
+    out = {"reports": reports, "num_gaussians": int(gaussians.get_xyz.shape[0]), "model": gaussians}
+    if poses is not None:
+        out["refined_cameras"] = poses.refined()
+    return out
 
 
 def _parser() -> ArgumentParser:
     p = ArgumentParser(description="Train a 3D Gaussian splatting model on a COLMAP dataset")
     short = {"source_path": "-s", "model_path": "-m", "images": "-i", "resolution": "-r", "white_background": "-w"}
-    for k, v in {**MODEL_DEFAULTS, **OPTIMIZATION_DEFAULTS, **MASK_DEFAULTS,
+    for k, v in {**MODEL_DEFAULTS, **OPTIMIZATION_DEFAULTS, **MASK_DEFAULTS, **POSE_DEFAULTS,
                  **dict(convert_SHs_python=False, compute_cov3D_python=False, debug=False)}.items():
         flags = ["--" + k] + ([short[k]] if k in short else [])
         if isinstance(v, bool):
