@@ -233,17 +233,29 @@ __global__ __launch_bounds__(256) void batch_header_kernel(uint32_t* __restrict_
         for (int i = threadIdx.x; i < table_words; i += blockDim.x) gstore(tables_out + i, tables.w[i]);
 }
 
+// What an entry adds to the plain batch call; every field is optional.
+struct ForwardOptions {
+    hipEvent_t* ev = nullptr;             // PGR_NUM_STAGES+1 events recorded at the stage boundaries (profiling entry)
+    // NULL = synchronous call (tables staged from pageable memory, stream synchronised at the end, num_instances
+    // filled).  Non-NULL = pinned host memory of host_scratch_bytes(n_views): nothing blocks, the status words land in
+    // its tail when the stream reaches them (pgr_batch_status reads them).
+    void* host_scratch = nullptr;
+    const PgrSemantic* semantic = nullptr;
+    const PgrPosedObjects* posed = nullptr;
+    const PgrLayers* layers = nullptr;
+    hipEvent_t status_event = nullptr;    // recorded behind the tile scan, which stores the status words itself
+};
+
 // The whole hot path for a batch of views of ONE scene.  All views share the image size.
-// ev: optional PGR_NUM_STAGES+1 events recorded at the stage boundaries (profiling entry point only).
-// host_scratch: NULL = synchronous call (tables staged from pageable memory, stream synchronised at the end,
-// num_instances filled).  Non-NULL = pinned host memory of host_scratch_bytes(n_views): nothing blocks, the
-// status words land in its tail when the stream reaches them (pgr_batch_status reads them).
 static int32_t forward_batch_impl(const PgrScene* scene, int n_views, const PgrCamera* cams, const PgrOutputs* outs,
                                   void* workspace, size_t workspace_bytes, int64_t max_instances,
-                                  int64_t* num_instances, hipStream_t stream, hipEvent_t* ev,
-                                  void* host_scratch = nullptr, const PgrSemantic* semantic = nullptr,
-                                  const PgrPosedObjects* posed = nullptr, const PgrLayers* layers = nullptr,
-                                  hipEvent_t status_event = nullptr) {
+                                  int64_t* num_instances, hipStream_t stream, const ForwardOptions& opt = {}) {
+    hipEvent_t* const ev = opt.ev;
+    void* const host_scratch = opt.host_scratch;
+    const PgrSemantic* const semantic = opt.semantic;
+    const PgrPosedObjects* const posed = opt.posed;
+    const PgrLayers* const layers = opt.layers;
+    const hipEvent_t status_event = opt.status_event;
     auto mark = [&](int k) { if (ev) (void)hipEventRecord(ev[k], stream); };
     // every argument check happens here, before the first enqueue: an early return below this block would leave work
     // on the stream that still reads the (pageable) table staging of the synchronous path
@@ -666,57 +678,73 @@ int32_t pgr_forward(const PgrScene* scene, const PgrCamera* cam, const PgrOutput
                     size_t workspace_bytes, int64_t max_instances, int64_t* num_instances, void* stream_v) {
     if (scene && scene->n > 0 && out && !out->radii) return PGR_ERR_INVALID_ARGUMENT;
     return forward_batch_impl(scene, 1, cam, out, workspace, workspace_bytes, max_instances, num_instances,
-                              static_cast<hipStream_t>(stream_v), nullptr);
+                              static_cast<hipStream_t>(stream_v));
 }
 
 int32_t pgr_forward_batch(const PgrScene* scene, int32_t n_views, const PgrCamera* cameras, const PgrOutputs* outs,
                           void* workspace, size_t workspace_bytes, int64_t max_instances_per_view,
                           int64_t* num_instances, void* stream_v) {
     return forward_batch_impl(scene, n_views, cameras, outs, workspace, workspace_bytes, max_instances_per_view,
-                              num_instances, static_cast<hipStream_t>(stream_v), nullptr);
+                              num_instances, static_cast<hipStream_t>(stream_v));
 }
 
 size_t pgr_host_scratch_bytes(int32_t n_views) { return n_views > 0 ? host_scratch_bytes(n_views) : 0; }
 
+// The asynchronous entries after their own checks: the pinned host scratch must hold host_scratch_bytes(n_views), and an
+// empty scene, which launches nothing, gets its status words (all zero) written here.
+static int32_t forward_async(const PgrScene* scene, int32_t n_views, const PgrCamera* cameras, const PgrOutputs* outs,
+                             void* workspace, size_t workspace_bytes, int64_t max_instances_per_view,
+                             size_t host_scratch_size, void* stream_v, const ForwardOptions& opt) {
+    if (!opt.host_scratch || n_views <= 0 || host_scratch_size < host_scratch_bytes(n_views)) return PGR_ERR_INVALID_ARGUMENT;
+    if (scene && scene->n == 0) memset(opt.host_scratch, 0, host_scratch_bytes(n_views));
+    return forward_batch_impl(scene, n_views, cameras, outs, workspace, workspace_bytes, max_instances_per_view, nullptr,
+                              static_cast<hipStream_t>(stream_v), opt);
+}
+
 int32_t pgr_forward_batch_async(const PgrScene* scene, int32_t n_views, const PgrCamera* cameras, const PgrOutputs* outs,
                                 void* workspace, size_t workspace_bytes, int64_t max_instances_per_view,
                                 void* host_scratch, size_t host_scratch_size, void* stream_v) {
-    if (!host_scratch || n_views <= 0 || host_scratch_size < host_scratch_bytes(n_views)) return PGR_ERR_INVALID_ARGUMENT;
-    if (scene && scene->n == 0) memset(static_cast<char*>(host_scratch), 0, host_scratch_bytes(n_views));
-    return forward_batch_impl(scene, n_views, cameras, outs, workspace, workspace_bytes, max_instances_per_view, nullptr,
-                              static_cast<hipStream_t>(stream_v), nullptr, host_scratch);
+    ForwardOptions opt;
+    opt.host_scratch = host_scratch;
+    return forward_async(scene, n_views, cameras, outs, workspace, workspace_bytes, max_instances_per_view,
+                         host_scratch_size, stream_v, opt);
 }
 
 int32_t pgr_forward_frames_async(const PgrScene* scene, const PgrSemantic* semantic, int32_t n_views,
                                  const PgrCamera* cameras, const PgrOutputs* outs, void* workspace,
                                  size_t workspace_bytes, int64_t max_instances_per_view, void* host_scratch,
                                  size_t host_scratch_size, void* stream_v) {
-    if (!host_scratch || n_views <= 0 || host_scratch_size < host_scratch_bytes(n_views)) return PGR_ERR_INVALID_ARGUMENT;
-    if (scene && scene->n == 0) memset(static_cast<char*>(host_scratch), 0, host_scratch_bytes(n_views));
-    return forward_batch_impl(scene, n_views, cameras, outs, workspace, workspace_bytes, max_instances_per_view, nullptr,
-                              static_cast<hipStream_t>(stream_v), nullptr, host_scratch, semantic);
+    ForwardOptions opt;
+    opt.host_scratch = host_scratch;
+    opt.semantic = semantic;
+    return forward_async(scene, n_views, cameras, outs, workspace, workspace_bytes, max_instances_per_view,
+                         host_scratch_size, stream_v, opt);
 }
 
 int32_t pgr_forward_posed_async(const PgrScene* scene, const PgrSemantic* semantic, const PgrPosedObjects* posed,
                                 int32_t n_views, const PgrCamera* cameras, const PgrOutputs* outs, void* workspace,
                                 size_t workspace_bytes, int64_t max_instances_per_view, void* host_scratch,
                                 size_t host_scratch_size, void* stream_v) {
-    if (!host_scratch || n_views <= 0 || host_scratch_size < host_scratch_bytes(n_views)) return PGR_ERR_INVALID_ARGUMENT;
-    if (scene && scene->n == 0) memset(static_cast<char*>(host_scratch), 0, host_scratch_bytes(n_views));
-    return forward_batch_impl(scene, n_views, cameras, outs, workspace, workspace_bytes, max_instances_per_view, nullptr,
-                              static_cast<hipStream_t>(stream_v), nullptr, host_scratch, semantic, posed);
+    ForwardOptions opt;
+    opt.host_scratch = host_scratch;
+    opt.semantic = semantic;
+    opt.posed = posed;
+    return forward_async(scene, n_views, cameras, outs, workspace, workspace_bytes, max_instances_per_view,
+                         host_scratch_size, stream_v, opt);
 }
 
 int32_t pgr_forward_posed_early_status(const PgrScene* scene, const PgrSemantic* semantic, const PgrPosedObjects* posed,
                                        int32_t n_views, const PgrCamera* cameras, const PgrOutputs* outs, void* workspace,
                                        size_t workspace_bytes, int64_t max_instances_per_view, void* host_scratch,
                                        size_t host_scratch_size, void* stream_v, void* status_event) {
-    if (!host_scratch || !status_event || n_views <= 0 || host_scratch_size < host_scratch_bytes(n_views))
-        return PGR_ERR_INVALID_ARGUMENT;
-    if (scene && scene->n == 0) memset(static_cast<char*>(host_scratch), 0, host_scratch_bytes(n_views));
-    return forward_batch_impl(scene, n_views, cameras, outs, workspace, workspace_bytes, max_instances_per_view, nullptr,
-                              static_cast<hipStream_t>(stream_v), nullptr, host_scratch, semantic, posed, nullptr,
-                              static_cast<hipEvent_t>(status_event));
+    if (!status_event) return PGR_ERR_INVALID_ARGUMENT;
+    ForwardOptions opt;
+    opt.host_scratch = host_scratch;
+    opt.semantic = semantic;
+    opt.posed = posed;
+    opt.status_event = static_cast<hipEvent_t>(status_event);
+    return forward_async(scene, n_views, cameras, outs, workspace, workspace_bytes, max_instances_per_view,
+                         host_scratch_size, stream_v, opt);
 }
 
 size_t pgr_layers_workspace_bytes(int32_t n, int32_t width, int32_t height, int64_t max_instances, int32_t n_views,
@@ -731,11 +759,13 @@ int32_t pgr_forward_layers_async(const PgrScene* scene, const PgrLayers* layers,
                                  int32_t n_views, const PgrCamera* cameras, const PgrOutputs* outs, void* workspace,
                                  size_t workspace_bytes, int64_t max_instances_per_view, void* host_scratch,
                                  size_t host_scratch_size, void* stream_v) {
-    if (!layers || !host_scratch || n_views <= 0 || host_scratch_size < host_scratch_bytes(n_views))
-        return PGR_ERR_INVALID_ARGUMENT;
-    if (scene && scene->n == 0) memset(static_cast<char*>(host_scratch), 0, host_scratch_bytes(n_views));
-    return forward_batch_impl(scene, n_views, cameras, outs, workspace, workspace_bytes, max_instances_per_view, nullptr,
-                              static_cast<hipStream_t>(stream_v), nullptr, host_scratch, nullptr, posed, layers);
+    if (!layers) return PGR_ERR_INVALID_ARGUMENT;
+    ForwardOptions opt;
+    opt.host_scratch = host_scratch;
+    opt.posed = posed;
+    opt.layers = layers;
+    return forward_async(scene, n_views, cameras, outs, workspace, workspace_bytes, max_instances_per_view,
+                         host_scratch_size, stream_v, opt);
 }
 
 size_t pgr_scene_cache_bytes(int32_t n) { return n < 0 ? 0 : align_up((size_t)n * 4) + align_up((size_t)n); }
@@ -788,8 +818,11 @@ int32_t pgr_forward_batch_profiled(const PgrScene* scene, const PgrSemantic* sem
     for (auto& e : ev)
         if (!hip_ok(hipEventCreate(&e), "hipEventCreate")) return PGR_ERR_LAUNCH_FAILURE;
     for (int k = 0; k < PGR_NUM_STAGES; ++k) stage_ms[k] = 0.f;
+    ForwardOptions opt;
+    opt.ev = ev;
+    opt.semantic = semantic;
     int32_t rc = forward_batch_impl(scene, n_views, cameras, outs, workspace, workspace_bytes, max_instances_per_view,
-                                    num_instances, stream, ev, nullptr, semantic);
+                                    num_instances, stream, opt);
     if (rc == PGR_OK && scene->n > 0) {
         for (int k = 0; rc == PGR_OK && k < PGR_NUM_STAGES; ++k)
             if (!hip_ok(hipEventElapsedTime(&stage_ms[k], ev[k], ev[k + 1]), "hipEventElapsedTime"))

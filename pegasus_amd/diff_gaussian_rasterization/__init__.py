@@ -32,7 +32,7 @@ import torch
 from torch import nn
 
 from .. import _lib, rasterizer
-from ..rasterizer import dev_f32 as _dev_f32, _ptr
+from ..rasterizer import _ptr, _until_fits, camera_structs, dev_f32 as _dev_f32, scene_struct
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "rasterize_gaussians_batch",
            "last_forward_info", "alpha_from_final_T"]
@@ -84,30 +84,18 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     pb = rasterizer.forward_views(means3D, opacities, [view], shs=sh, colors_precomp=colors_precomp, scales=scales,
                                   rotations=rotations, cov3D_precomp=cov3Ds_precomp, sh_degree=rs.sh_degree,
                                   scale_modifier=rs.scale_modifier, want_radii=True, want_aux=want_aux,
-                                  async_slot=("single-view", 0), early_status=True, shs_rest=sh_rest)
-    if isinstance(pb, list):            # (an empty view list cannot happen here; an empty SCENE still returns a handle)
-        r = pb[0]
-    else:
-        pb.record_info = True
-        if after_enqueue is not None:
-            after_enqueue(pb.results[0])
-        r = pb.wait()[0]
-        if after_enqueue is not None and getattr(pb, "_was_redone", False):
-            after_enqueue(r)
+                                  async_slot=("single-view", 0), early_status=True, shs_rest=sh_rest, record_info=True)
+    if after_enqueue is not None:
+        after_enqueue(pb.results[0])
+    r = pb.wait()[0]
+    if after_enqueue is not None and pb.redone:
+        after_enqueue(r)
     if want_aux:
         return r["color"], r["radii"], r["depth"], r["final_T"], r["n_contrib"]
     return r["color"], r["radii"], r["depth"]
 
 
-def _scene_struct(t, n, sh_degree, scale_modifier):
-    return _lib.PgrScene(n=n, means3d=_ptr(t["means3D"]), opacities=_ptr(t["op"]), scales=_ptr(t["scales"]),
-                         rotations=_ptr(t["rot"]), cov3d_precomp=_ptr(t["cov"]), shs=_ptr(t["sh"]),
-                         colors_precomp=_ptr(t["colors"]), sh_degree=int(sh_degree),
-                         sh_stride=int(t["sh"].shape[1]) if t["sh"] is not None else 0,
-                         scale_modifier=float(scale_modifier))
-
-
-_SCENE_KEYS = ("means3D", "sh", "colors", "op", "scales", "rot", "cov")
+_SCENE_KEYS = ("means3D", "opacities", "shs", "colors_precomp", "scales", "rotations", "cov3D_precomp")
 
 
 class _RasterizeGaussians(torch.autograd.Function):
@@ -151,14 +139,10 @@ class _RasterizeGaussians(torch.autograd.Function):
             raise RuntimeError(("GaussianRasterizer" if single else "rasterize_gaussians_batch") +
                                " needs tensors on a HIP device (torch device 'cuda'); there is no CPU path")
         n = int(means3D.shape[0])
-        t = {k: _dev_f32(v, device) for k, v in dict(means3D=means3D, sh=sh, colors=colors_precomp, op=opacities,
-                                                     scales=scales, rot=rotations, cov=cov3Ds_precomp).items()}
-        scene = _scene_struct(t, n, rs0.sh_degree, rs0.scale_modifier)
-        cam_t = [[_dev_f32(x, device) for x in (rs.viewmatrix, rs.projmatrix, rs.campos, rs.bg)] for rs in settings]
-        cams = (_lib.PgrCamera * V)(*[
-            _lib.PgrCamera(image_width=W, image_height=H, tanfovx=float(rs.tanfovx), tanfovy=float(rs.tanfovy),
-                           viewmatrix=_ptr(c[0]), projmatrix=_ptr(c[1]), campos=_ptr(c[2]), bg=_ptr(c[3]))
-            for rs, c in zip(settings, cam_t)])
+        t = {k: _dev_f32(v, device) for k, v in zip(_SCENE_KEYS, (means3D, opacities, sh, colors_precomp, scales, rotations,
+                                                                  cov3Ds_precomp))}
+        scene = scene_struct(n, sh_degree=rs0.sh_degree, scale_modifier=rs0.scale_modifier, **t)
+        cams, _cam_tensors = camera_structs(settings, device)
         lead = () if single else (V,)
         per_view = (lambda x: (x,)) if single else (lambda x: x.unbind(0))
         color = torch.empty(lead + (3, H, W), dtype=torch.float32, device=device)
@@ -170,20 +154,16 @@ class _RasterizeGaussians(torch.autograd.Function):
             _lib.PgrOutputs(color=_ptr(c), depth=_ptr(d), radii=_ptr(r), final_T=_ptr(ft), n_contrib=_ptr(nc))
             for c, d, r, ft, nc in zip(*map(per_view, (color, depth, radii, final_T, n_contrib)))])
         stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        max_inst = max(1 << 18, 4 * n)
         need = (C.c_int64 * V)()
+        ws = None
+
+        def run(capacity):
+            nonlocal ws
+            ws = torch.empty(L.pgr_batch_workspace_bytes(n, W, H, capacity, V), dtype=torch.uint8, device=device)
+            args = (cams, outs, C.c_void_p(ws.data_ptr()), ws.numel(), capacity, need, stream)
+            return (L.pgr_forward(C.byref(scene), *args) if single else L.pgr_forward_batch(C.byref(scene), V, *args)), need
         with torch.cuda.device(device):
-            for _attempt in range(3):
-                ws = torch.empty(L.pgr_batch_workspace_bytes(n, W, H, max_inst, V), dtype=torch.uint8, device=device)
-                if single:
-                    status = L.pgr_forward(C.byref(scene), cams, outs, C.c_void_p(ws.data_ptr()), ws.numel(), max_inst,
-                                           need, stream)
-                else:
-                    status = L.pgr_forward_batch(C.byref(scene), V, cams, outs, C.c_void_p(ws.data_ptr()), ws.numel(),
-                                                 max_inst, need, stream)
-                if status != _lib.PGR_ERR_INSTANCE_OVERFLOW:
-                    break
-                max_inst = rasterizer.grown_capacity(max(need), 1.25)
+            status, _, max_inst = _until_fits(run, max(1 << 18, 4 * n), 1.25)
             _lib.check(status, "pgr_forward" if single else "pgr_forward_batch")
         ctx.hw, ctx.V, ctx.n, ctx.max_inst, ctx.single = (H, W), V, n, max_inst, single
         ctx.sh_degree, ctx.scale_modifier = int(rs0.sh_degree), float(rs0.scale_modifier)
@@ -205,8 +185,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         V, n, (H, W), single = ctx.V, ctx.n, ctx.hw, ctx.single
         saved = ctx.saved_tensors          # raises if an input was modified in place since the forward
         k = len(ctx.present)
-        t = dict.fromkeys(_SCENE_KEYS)
-        t.update(zip(ctx.present, saved[:k]))
+        t = dict(zip(ctx.present, saved[:k]))
         ws, radii, final_T, n_contrib = saved[k:]
         device = ws.device
         lead = () if single else (V,)
@@ -216,16 +195,16 @@ class _RasterizeGaussians(torch.autograd.Function):
         alloc = torch.empty if n > 0 else torch.zeros
         z = lambda *shape: alloc(shape, dtype=torch.float32, device=device)
         g = dict(means2d=z(*lead, n, 3), means3d=z(n, 3), opacities=z(n, 1))
-        if t["sh"] is not None:
-            g["shs"] = z(*t["sh"].shape)
+        if "shs" in t:
+            g["shs"] = z(*t["shs"].shape)
         else:
             g["colors"] = z(n, 3)
-        if t["cov"] is not None:
+        if "cov3D_precomp" in t:
             g["cov3d"] = z(n, 6)
         else:
             g["scales"], g["rotations"] = z(n, 3), z(n, 4)
         grads = _lib.PgrGradOutputs(**{key: _ptr(v) for key, v in g.items()})
-        scene = _scene_struct(t, n, ctx.sh_degree, ctx.scale_modifier)
+        scene = scene_struct(n, sh_degree=ctx.sh_degree, scale_modifier=ctx.scale_modifier, **t)
         cams = (_lib.PgrCamera * V)(*[_lib.PgrCamera(image_width=W, image_height=H) for _ in range(V)])
         gc = (torch.zeros(lead + (3, H, W), dtype=torch.float32, device=device) if grad_color is None
               else grad_color.contiguous().float())

@@ -249,10 +249,9 @@ class FrameRenderer:
             def wait(self_inner):
                 h1.wait()
                 if h2 is not None:
-                    before = h2.results
                     h2.wait()
                     ev_masks.synchronize()
-                    if h2.results is not before:      # semantic pass was re-rendered after an overflow: redo masks
+                    if h2.redone:      # semantic pass was re-rendered after an overflow: redo masks
                         M.color_masks(frames["seg"][:B], renderer.colors, M.MASK_THRESHOLD, out=frames["masks"][:B])
                         torch.cuda.current_stream(dev).synchronize()
                 return frames
@@ -315,7 +314,6 @@ class FrameRenderer:
                                 rotations=self.obj["rotations"], sh_degree=0, want_radii=False, posed=posed,
                                 tie_index=self.obj_tie_index, tie_inv=self.obj_tie_inv, outputs=outs,
                                 async_slot=("silhouette", slot), layers=layers)
-        h._args = (specs, posed, layers)
         if not wait:
             return out[:, :self.K], h
         h.wait()
@@ -362,7 +360,7 @@ class FrameRenderer:
         for p in pending:
             if p is not None:
                 p.wait()
-                redo = redo or getattr(p, "_was_redone", False)
+                redo = redo or p.redone
         if redo:            # an instance overflow re-rendered a pass after its masks were taken: start over (sized now)
             return self.render_silhouettes_per_object(specs, out, poses)
         return out[:, :self.K]

@@ -139,41 +139,106 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
-class PendingBatch:
-    """Handle of an asynchronous forward_views call: ``wait()`` blocks until the batch has finished on its
-    stream, checks the overflow flags (re-rendering synchronously with a larger capacity if needed) and
-    returns the list of result dicts."""
+def scene_struct(n: int, means3D=None, opacities=None, *, shs=None, shs_rest=None, colors_precomp=None, scales=None,
+                 rotations=None, cov3D_precomp=None, sh_degree=0, scale_modifier=1.0, tie_index=None,
+                 tie_inv=None) -> _lib.PgrScene:
+    """The PgrScene of one call's tensors, as the kernels read them (dev_f32).  An absent tensor is a NULL pointer; the SH
+    stride counts the coefficients of ``shs`` and ``shs_rest`` together, and ``tie_inv`` is passed only with ``tie_index``."""
+    return _lib.PgrScene(
+        n=int(n), means3d=_ptr(means3D), opacities=_ptr(opacities), scales=_ptr(scales), rotations=_ptr(rotations),
+        cov3d_precomp=_ptr(cov3D_precomp), shs=_ptr(shs), colors_precomp=_ptr(colors_precomp), sh_degree=int(sh_degree),
+        sh_stride=0 if shs is None else int(shs.shape[1]) + (0 if shs_rest is None else int(shs_rest.shape[1])),
+        scale_modifier=float(scale_modifier), tie_index=_ptr(tie_index),
+        tie_inv=None if tie_index is None else _ptr(tie_inv), shs_rest=_ptr(shs_rest))
 
-    def __init__(self, results, event, scratch, nv, key, max_inst, redo):
-        self.results, self._event, self._scratch, self._nv = results, event, scratch, nv
-        self._key, self._max_inst, self._redo = key, max_inst, redo
+
+def camera_structs(views, device):
+    """The PgrCamera array of ``views`` (ViewSpecs or GaussianRasterizationSettings) and the converted camera tensors it
+    points to, which must stay alive as long as the call that reads them."""
+    cams = (_lib.PgrCamera * len(views))()
+    keep = []
+    for i, v in enumerate(views):
+        bg, vm, pm, cp = (dev_f32(t, device) for t in (v.bg, v.viewmatrix, v.projmatrix, v.campos))
+        keep.append((bg, vm, pm, cp))
+        cams[i] = _lib.PgrCamera(image_width=int(v.image_width), image_height=int(v.image_height), tanfovx=float(v.tanfovx),
+                                 tanfovy=float(v.tanfovy), viewmatrix=_ptr(vm), projmatrix=_ptr(pm), campos=_ptr(cp),
+                                 bg=_ptr(bg), depth_mode=int(getattr(v, "depth_mode", 0)))
+    return cams, keep
+
+
+def _until_fits(run, capacity: int, factor: float, attempts: int = 3):
+    """The instance-overflow retry of every forward call.  ``run(capacity)`` renders once at that per-view capacity and
+    returns (status, per-view instance counts); after PGR_ERR_INSTANCE_OVERFLOW the next attempt runs at
+    grown_capacity(largest count, factor).  Returns (status, counts, the capacity that held).  Raises grown_capacity's
+    per-view-limit error, or RuntimeError when ``attempts`` attempts all overflowed."""
+    for _attempt in range(attempts):
+        status, need = run(capacity)
+        if status != _lib.PGR_ERR_INSTANCE_OVERFLOW:
+            return status, need, capacity
+        capacity = grown_capacity(max(need), factor)
+    raise RuntimeError("instance capacity did not converge")
+
+
+def _learn(key, capacity: int, peak: Optional[int] = None) -> int:
+    """Raises the learned capacity of ``key`` (capacity_hints()) to ``capacity``.  Given the ``peak`` count of a call that
+    ran at ``capacity``, a peak above 80 % of it asks for grown_capacity(peak, 1.6) instead: few, large steps, since every
+    growth reallocates the multi-GB workspace.  Returns the capacity asked for."""
+    if peak is not None and peak > 0.8 * capacity:
+        capacity = grown_capacity(peak, 1.6)
+    _WS.capacity_hint[key] = max(_WS.capacity_hint.get(key, 0), capacity)
+    return capacity
+
+
+def _batch_status(scratch: torch.Tensor, nv: int):
+    """(status, per-view instance counts) of the asynchronous call whose pinned host scratch is ``scratch``."""
+    need = (C.c_int64 * nv)()
+    status = _lib.lib().pgr_batch_status(C.c_void_p(scratch.data_ptr()), nv, need)
+    return status, [int(x) for x in need]
+
+
+def _remember(key, need, used: int, ws: torch.Tensor, max_instances: Optional[int] = None) -> None:
+    """Fills last_forward_info() for a call of scene shape ``key`` that ran at capacity ``used`` in ``ws``."""
+    _LAST_INFO.clear()
+    _LAST_INFO.update(num_instances=[int(x) for x in need], max_instances=int(used if max_instances is None else max_instances),
+                      used_max_instances=int(used), n=int(key[1]), width=int(key[2]), height=int(key[3]),
+                      n_views=len(need), workspace=ws, workspace_bytes=int(ws.numel()))
+
+
+class PendingBatch:
+    """Handle of an asynchronous forward_views call: ``wait()`` blocks until the batch's status words are final, checks
+    the overflow flags -- after an overflow ``redo()`` renders the batch again at a grown capacity and ``redone`` is True
+    -- and returns the list of result dicts.  ``keep`` holds every tensor the enqueued call reads until then."""
+
+    def __init__(self, results, event, scratch, workspace, key, capacity, redo, keep, record_info=False):
+        self.results = results
         self.num_instances = None
-        self.record_info = False     # True: wait() fills last_forward_info() like a synchronous call (single-view drop-in)
+        self.redone = False
+        self._event, self._scratch, self._workspace = event, scratch, workspace
+        self._key, self._capacity, self._redo, self._keep = key, capacity, redo, keep
+        self._record_info = record_info      # wait() fills last_forward_info() like a synchronous call (single-view drop-in)
+
+    @property
+    def _was_redone(self) -> bool:
+        """The earlier name of ``redone``, still read by code written against it."""
+        return self.redone
 
     def wait(self):
-        if self._event is not None:
-            self._event.synchronize()
-            need = (C.c_int64 * self._nv)()
-            status = _lib.lib().pgr_batch_status(C.c_void_p(self._scratch.data_ptr()), self._nv, need)
-            self.num_instances = [int(x) for x in need]
-            peak = max(self.num_instances)
-            if peak > 0.8 * self._max_inst and peak <= MAX_INSTANCES:
-                _WS.capacity_hint[self._key] = max(_WS.capacity_hint.get(self._key, 0), grown_capacity(peak, 1.6))   # few, large steps:
-                # every growth reallocates the multi-GB workspace (tens of ms)
-            self._event = None
-            if self.record_info and status != _lib.PGR_ERR_INSTANCE_OVERFLOW:
-                ws = self._keep[1]
-                _LAST_INFO.clear()
-                _LAST_INFO.update(num_instances=self.num_instances, max_instances=int(self._max_inst),
-                                  used_max_instances=int(self._max_inst), n=int(self._key[1]), width=int(self._key[2]),
-                                  height=int(self._key[3]), n_views=self._nv, workspace=ws, workspace_bytes=int(ws.numel()))
-            if status == _lib.PGR_ERR_INSTANCE_OVERFLOW:
-                self._was_redone = True
-                _WS.capacity_hint[self._key] = max(_WS.capacity_hint.get(self._key, 0), grown_capacity(peak, 1.6))   # raises beyond MAX_INSTANCES
-                self.results = self._redo()          # synchronous path grows the workspace and retries
-            else:
-                _lib.check(status, "pgr_forward_batch_async")
-            self._redo = None
+        if self._event is None:
+            return self.results
+        self._event.synchronize()
+        self._event = None
+        status, self.num_instances = _batch_status(self._scratch, len(self.results))
+        peak = max(self.num_instances)
+        if peak > 0.8 * self._capacity:      # only a crowded batch teaches the learned capacity something
+            _learn(self._key, self._capacity, peak)
+        redo, self._redo = self._redo, None
+        if status == _lib.PGR_ERR_INSTANCE_OVERFLOW:
+            self.redone = True
+            self.results = redo()
+        else:
+            _lib.check(status, "pgr_batch_status")
+            if self._record_info:
+                _remember(self._key, self.num_instances, self._capacity, self._workspace)
         return self.results
 
 
@@ -181,7 +246,8 @@ def forward_views(means3D, opacities, views: Sequence[ViewSpec], *, shs=None, co
                   rotations=None, cov3D_precomp=None, sh_degree=0, scale_modifier=1.0, want_radii=True,
                   want_aux=False, stage_ms: Optional[list] = None, outputs: Optional[list] = None,
                   async_slot=None, semantic: Optional[dict] = None, posed: Optional[dict] = None, tie_index=None,
-                  tie_inv=None, layers: Optional[dict] = None, early_status: bool = False, shs_rest=None):
+                  tie_inv=None, layers: Optional[dict] = None, early_status: bool = False, shs_rest=None,
+                  record_info: bool = False):
     """Renders ``len(views)`` views of one scene.  Returns a list of dicts with keys
     color[3,H,W], depth[1,H,W], radii[N] (or None), and final_T / n_contrib when ``want_aux``.
 
@@ -189,14 +255,18 @@ def forward_views(means3D, opacities, views: Sequence[ViewSpec], *, shs=None, co
     milliseconds (whole batch) measured with HIP events on the launch stream.
     ``outputs``: optional pre-allocated list of dicts (same keys) to render into.
     ``async_slot``: not None -> enqueue on torch's CURRENT stream without synchronising and return a
-    PendingBatch; the slot names the workspace / pinned scratch to use (one batch in flight per slot).
+    PendingBatch; the slot names the workspace / pinned scratch to use (one batch in flight per slot).  After an instance
+    overflow its wait() renders the batch again: a layered call on the same slot, any other as the synchronous call does.
+    A synchronous call with ``semantic`` or ``posed`` (and no ``stage_ms``) is an asynchronous one on the "sync-fused" slot,
+    waited for; any other goes through pgr_forward_batch (or pgr_forward_batch_profiled) on the pooled workspace.
+    ``record_info`` (with ``async_slot``): PendingBatch.wait() fills last_forward_info() like a synchronous call.
     ``shs_rest``: the SH coefficients as the model stores them -- ``shs`` = _features_dc [N,1,3], ``shs_rest`` = _features_rest
     [N,K-1,3] (PgrScene::shs_rest) -- instead of their concatenation; results are bit-identical.
     ``early_status`` (with ``async_slot``, not layered): PendingBatch.wait() returns as soon as the call's status words are
     final -- behind the tile scan, pgr_forward_posed_early_status -- instead of at the end of the call; the outputs are
     complete in stream order (whatever the caller queues on the current stream, or fetches with .cpu(), comes after them).
     ``semantic``: dict(object_id int32[N], colors float32[K,3], n_env, k) -> the fused objects-only semantic
-    render is written to r["sem_color"] (and r["sem_depth"]) of every view (pgr_forward_frames_async).
+    render is written to r["sem_color"] (and r["sem_depth"]) of every view (pgr_forward_posed_async).
     ``semantic`` may also carry ``mask_colors`` float32[K,3] (+ ``mask_threshold``): every output dict with a ``sem_masks``
     uint8[K,H,W] tensor then receives the K colour-distance masks of the semantic image from the compositor's epilogue
     (bit for bit what color_masks() computes from ``sem_color``), and ``object_id_u8`` (scene_prepare()).
@@ -219,45 +289,34 @@ def forward_views(means3D, opacities, views: Sequence[ViewSpec], *, shs=None, co
     if nv == 0:
         return []
     H, W = int(views[0].image_height), int(views[0].image_width)
+    if any(int(v.image_height) != H or int(v.image_width) != W for v in views):
+        raise ValueError("all views of a batch must share the image size")
+    if posed is not None and stage_ms is not None:
+        raise ValueError("the profiling entry point does not take posed objects")
+    if layers is not None and (async_slot is None or semantic is not None or stage_ms is not None):
+        raise ValueError("a layered call is asynchronous (async_slot) and takes no semantic descriptor")
+    if async_slot is not None:
+        stage_ms = None          # the asynchronous entries are not profiled, nor is the synchronous retry of an overflow
+    fused = (semantic is not None or posed is not None) and stage_ms is None
     n = int(means3D.shape[0])
-    means3D_in, opacities_in = means3D, opacities      # (an empty scene converts to None = NULL pointers: re-entrant calls get the originals)
-    means3D = dev_f32(means3D, device)
-    opacities = dev_f32(opacities, device)
-    shs = dev_f32(shs, device)
-    shs_rest = dev_f32(shs_rest, device)
+    shs, shs_rest = dev_f32(shs, device), dev_f32(shs_rest, device)
     if shs_rest is not None:
         if shs is None or shs.dim() != 3 or shs.shape[1] != 1 or shs_rest.dim() != 3 or shs_rest.shape[0] != shs.shape[0]:
             raise ValueError("shs_rest goes with shs = [N,1,3] (the first coefficient) and is [N,K-1,3]")
         if shs_rest.shape[1] == 0:
             shs_rest = None                        # nothing but the first coefficient: the plain layout with stride 1
-    colors_precomp = dev_f32(colors_precomp, device)
-    scales = dev_f32(scales, device)
-    rotations = dev_f32(rotations, device)
-    cov3D_precomp = dev_f32(cov3D_precomp, device)
+    tensors = dict(means3D=means3D, opacities=opacities, colors_precomp=colors_precomp, scales=scales, rotations=rotations,
+                   cov3D_precomp=cov3D_precomp)
+    tensors = {k: dev_f32(t, device) for k, t in tensors.items()}
+    tensors.update(shs=shs, shs_rest=shs_rest, tie_index=tie_index, tie_inv=tie_inv)
+    scene = C.byref(scene_struct(n, sh_degree=sh_degree, scale_modifier=scale_modifier, **tensors))
+    cams, cam_tensors = camera_structs(views, device)
 
-    scene = _lib.PgrScene(
-        n=n, means3d=_ptr(means3D), opacities=_ptr(opacities), scales=_ptr(scales), rotations=_ptr(rotations),
-        cov3d_precomp=_ptr(cov3D_precomp), shs=_ptr(shs), colors_precomp=_ptr(colors_precomp),
-        sh_degree=int(sh_degree),
-        sh_stride=(int(shs.shape[1]) + (int(shs_rest.shape[1]) if shs_rest is not None else 0)) if shs is not None else 0,
-        scale_modifier=float(scale_modifier), tie_index=_ptr(tie_index), tie_inv=_ptr(tie_inv) if tie_index is not None else None,
-        shs_rest=_ptr(shs_rest))
-
-    cams = (_lib.PgrCamera * nv)()
-    outs = (_lib.PgrOutputs * nv)()
-    keep = []
-    results: List[dict] = []
-    for i, v in enumerate(views):
-        if int(v.image_height) != H or int(v.image_width) != W:
-            raise ValueError("all views of a batch must share the image size")
-        bg, vm, pm, cp = (dev_f32(t, device) for t in (v.bg, v.viewmatrix, v.projmatrix, v.campos))
-        keep.append((bg, vm, pm, cp))
-        cams[i] = _lib.PgrCamera(image_width=W, image_height=H, tanfovx=float(v.tanfovx), tanfovy=float(v.tanfovy),
-                                 viewmatrix=_ptr(vm), projmatrix=_ptr(pm), campos=_ptr(cp), bg=_ptr(bg),
-                                 depth_mode=int(getattr(v, "depth_mode", 0)))
-        if outputs is not None:
-            r = outputs[i]
-        else:
+    if outputs is not None:
+        results = list(outputs[:nv])
+    else:
+        results = []
+        for _ in range(nv):
             r = dict(color=torch.empty((3, H, W), dtype=torch.float32, device=device),
                      depth=torch.empty((1, H, W), dtype=torch.float32, device=device),
                      radii=torch.empty((n,), dtype=torch.int32, device=device) if want_radii else None)
@@ -267,151 +326,118 @@ def forward_views(means3D, opacities, views: Sequence[ViewSpec], *, shs=None, co
             if semantic is not None:
                 r["sem_color"] = torch.empty((3, H, W), dtype=torch.float32, device=device)
                 r["sem_depth"] = torch.empty((1, H, W), dtype=torch.float32, device=device)
-        outs[i] = _lib.PgrOutputs(color=_ptr(r.get("color")), depth=_ptr(r.get("depth")), radii=_ptr(r.get("radii")),
-                                  final_T=_ptr(r.get("final_T")), n_contrib=_ptr(r.get("n_contrib")),
-                                  sem_color=_ptr(r.get("sem_color")) if semantic is not None else None,
-                                  sem_depth=_ptr(r.get("sem_depth")) if semantic is not None else None,
-                                  sem_masks=_ptr(r.get("sem_masks")) if (semantic is not None or layers is not None) else None,
-                                  record=_ptr(r.get("record")) if layers is None else None)
-        results.append(r)
+            results.append(r)
+    outs = (_lib.PgrOutputs * nv)(*[
+        _lib.PgrOutputs(color=_ptr(r.get("color")), depth=_ptr(r.get("depth")), radii=_ptr(r.get("radii")),
+                        final_T=_ptr(r.get("final_T")), n_contrib=_ptr(r.get("n_contrib")),
+                        sem_color=_ptr(r.get("sem_color")) if semantic is not None else None,
+                        sem_depth=_ptr(r.get("sem_depth")) if semantic is not None else None,
+                        sem_masks=_ptr(r.get("sem_masks")) if (semantic is not None or layers is not None) else None,
+                        record=_ptr(r.get("record")) if layers is None else None)
+        for r in results])
 
-    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    key = (device, n, W, H)
-    max_inst = _WS.capacity_hint.get(key, max(1 << 20, 6 * n))
-    sem_struct = posed_struct = None
+    sem = posed_ref = poses = layers_ref = None
     if posed is not None:
-        if stage_ms is not None:
-            raise ValueError("the profiling entry point does not take posed objects")
         poses = dev_f32(posed["poses"], device)
         if poses.dim() != 3 or poses.shape[0] != nv or poses.shape[2] != _lib.PGR_POSE_STRIDE:
             raise ValueError("posed['poses'] must be [n_views, K, 20]")
-        keep.append(poses)
-        posed_struct = _lib.PgrPosedObjects(object_id=_ptr(posed["object_id"]), poses=_ptr(poses),
-                                            k_objects=int(poses.shape[1]))
+        posed_ref = C.byref(_lib.PgrPosedObjects(object_id=_ptr(posed["object_id"]), poses=_ptr(poses),
+                                                 k_objects=int(poses.shape[1])))
     if semantic is not None:
-        sem_struct = _lib.PgrSemantic(object_id=_ptr(semantic["object_id"]), colors=_ptr(semantic["colors"]),
-                                      n_env=int(semantic["n_env"]), k_objects=int(semantic["k"]),
-                                      object_id_u8=_ptr(semantic.get("object_id_u8")),
-                                      mask_colors=_ptr(semantic.get("mask_colors")),
-                                      mask_threshold=float(semantic.get("mask_threshold", 0.1)))
-    layers_struct = None
+        sem = C.byref(_lib.PgrSemantic(object_id=_ptr(semantic["object_id"]), colors=_ptr(semantic["colors"]),
+                                       n_env=int(semantic["n_env"]), k_objects=int(semantic["k"]),
+                                       object_id_u8=_ptr(semantic.get("object_id_u8")),
+                                       mask_colors=_ptr(semantic.get("mask_colors")),
+                                       mask_threshold=float(semantic.get("mask_threshold", 0.1))))
+    key = (device, n, W, H)
     if layers is not None:
-        if async_slot is None or semantic is not None or stage_ms is not None:
-            raise ValueError("a layered call is asynchronous (async_slot) and takes no semantic descriptor")
-        layers_struct = _lib.PgrLayers(layer_id=_ptr(layers["layer_id"]), n_layers=int(layers["n_layers"]),
-                                       mask_colors=_ptr(layers["mask_colors"]),
-                                       mask_threshold=float(layers.get("mask_threshold", 0.1)))
-        key = (device, n, W, H, "layers", int(layers["n_layers"]))
-        max_inst = _WS.capacity_hint.get(key, max(1 << 20, 6 * n))
-    if semantic is not None or posed is not None:
-        if async_slot is None and stage_ms is None:      # synchronous fused call: enqueue asynchronously, wait, retry on overflow
-            kw = dict(shs=shs, shs_rest=shs_rest, colors_precomp=colors_precomp, scales=scales, rotations=rotations,
-                      cov3D_precomp=cov3D_precomp, sh_degree=sh_degree, scale_modifier=scale_modifier,
-                      want_radii=want_radii, want_aux=want_aux, outputs=results, semantic=semantic, posed=posed,
-                      tie_index=tie_index, tie_inv=tie_inv)
-            for _attempt in range(3):
-                pb = forward_views(means3D_in, opacities_in, views, async_slot="sync-fused", **kw)
-                pb._redo = None
-                pb._event.synchronize()
-                need = (C.c_int64 * nv)()
-                status = L.pgr_batch_status(C.c_void_p(pb._scratch.data_ptr()), nv, need)
-                if status != _lib.PGR_ERR_INSTANCE_OVERFLOW:
-                    _lib.check(status, "pgr_forward_frames_async")
-                    _LAST_INFO.clear()
-                    _LAST_INFO.update(num_instances=[int(x) for x in need], max_instances=int(pb._max_inst),
-                                      used_max_instances=int(pb._max_inst), n=n, width=W, height=H, n_views=nv,
-                                      workspace=pb._keep[1], workspace_bytes=int(pb._keep[1].numel()))
-                    return results
-                _WS.capacity_hint[key] = grown_capacity(max(need), 1.6)
-            raise RuntimeError("instance capacity did not converge")
-    if async_slot is not None:
+        n_layers = int(layers["n_layers"])
+        layers_ref = C.byref(_lib.PgrLayers(layer_id=_ptr(layers["layer_id"]), n_layers=n_layers,
+                                            mask_colors=_ptr(layers["mask_colors"]),
+                                            mask_threshold=float(layers.get("mask_threshold", 0.1))))
+        key += ("layers", n_layers)
+    default_capacity = max(1 << 20, 6 * n)
+    ws = None          # the workspace of the latest attempt
+
+    def workspace(slot, capacity):
+        nbytes = (L.pgr_batch_workspace_bytes(n, W, H, capacity, nv) if layers is None else
+                  L.pgr_layers_workspace_bytes(n, W, H, capacity, nv, n_layers))
+        if nbytes == 0:
+            raise ValueError("pgr_batch_workspace_bytes: invalid sizes")
+        return _WS.get(device, nbytes, slot=slot)
+
+    def enqueue(slot, capacity, early=False):
+        """One asynchronous attempt on ``slot``'s workspace and pinned scratch: (scratch, event behind the status words)."""
+        nonlocal ws
+        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
         with torch.cuda.device(device):
-            if layers_struct is not None:
-                nbytes = L.pgr_layers_workspace_bytes(n, W, H, max_inst, nv, layers_struct.n_layers)
-            else:
-                nbytes = L.pgr_batch_workspace_bytes(n, W, H, max_inst, nv)
-            ws = _WS.get(device, nbytes, slot=("async", async_slot))
-            sb = L.pgr_host_scratch_bytes(nv)
-            scratch = _WS.pinned(async_slot, sb)
-            if layers_struct is not None:
-                _lib.check(L.pgr_forward_layers_async(C.byref(scene), C.byref(layers_struct),
-                                                      C.byref(posed_struct) if posed_struct else None, nv,
-                                                      cams, outs, C.c_void_p(ws.data_ptr()), ws.numel(), max_inst,
-                                                      C.c_void_p(scratch.data_ptr()), scratch.numel(), stream),
-                           "pgr_forward_layers_async")
-            elif early_status:
-                ev = _WS.status_event(device, async_slot)
-                _lib.check(L.pgr_forward_posed_early_status(C.byref(scene), C.byref(sem_struct) if sem_struct else None,
-                                                            C.byref(posed_struct) if posed_struct else None, nv,
-                                                            cams, outs, C.c_void_p(ws.data_ptr()), ws.numel(), max_inst,
-                                                            C.c_void_p(scratch.data_ptr()), scratch.numel(), stream,
-                                                            C.c_void_p(ev.cuda_event)),
+            ws = workspace(("async", slot), capacity)
+            scratch = _WS.pinned(slot, L.pgr_host_scratch_bytes(nv))
+            args = (nv, cams, outs, C.c_void_p(ws.data_ptr()), ws.numel(), capacity, C.c_void_p(scratch.data_ptr()),
+                    scratch.numel(), stream)
+            if layers is not None:
+                _lib.check(L.pgr_forward_layers_async(scene, layers_ref, posed_ref, *args), "pgr_forward_layers_async")
+            elif early:
+                event = _WS.status_event(device, slot)
+                _lib.check(L.pgr_forward_posed_early_status(scene, sem, posed_ref, *args, C.c_void_p(event.cuda_event)),
                            "pgr_forward_posed_early_status")
+                return scratch, event
             else:
-                _lib.check(L.pgr_forward_posed_async(C.byref(scene), C.byref(sem_struct) if sem_struct else None,
-                                                     C.byref(posed_struct) if posed_struct else None, nv,
-                                                     cams, outs, C.c_void_p(ws.data_ptr()), ws.numel(), max_inst,
-                                                     C.c_void_p(scratch.data_ptr()), scratch.numel(), stream),
-                           "pgr_forward_posed_async")
-            if not (early_status and layers_struct is None):
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(device))
-        kw = dict(shs=shs, shs_rest=shs_rest, colors_precomp=colors_precomp, scales=scales, rotations=rotations,
-                  cov3D_precomp=cov3D_precomp, sh_degree=sh_degree, scale_modifier=scale_modifier,
-                  want_radii=want_radii, want_aux=want_aux, outputs=results, semantic=semantic, posed=posed,
-                  tie_index=tie_index, tie_inv=tie_inv)
-        if layers is not None:          # a layered call is asynchronous only: the retry after an overflow is one too
-            def redo():
-                # bounded like the fused path: every attempt runs at the capacity the device asked for (a view that needs
-                # more than MAX_INSTANCES raises from grown_capacity instead of overflowing for ever)
-                for _attempt in range(3):
-                    pb2 = forward_views(means3D_in, opacities_in, views, async_slot=async_slot, layers=layers, **kw)
-                    pb2._redo = None
-                    pb2._event.synchronize()
-                    need2 = (C.c_int64 * nv)()
-                    status2 = L.pgr_batch_status(C.c_void_p(pb2._scratch.data_ptr()), nv, need2)
-                    if status2 != _lib.PGR_ERR_INSTANCE_OVERFLOW:
-                        _lib.check(status2, "pgr_forward_layers_async")
-                        return pb2.results
-                    _WS.capacity_hint[key] = grown_capacity(max(need2), 1.6)
-                raise RuntimeError("instance capacity did not converge")
-        else:
-            redo = lambda: forward_views(means3D_in, opacities_in, views, **kw)
-        pb = PendingBatch(results, ev, scratch, nv, key, max_inst, redo)
-        pb._keep = (keep, ws, cams, outs, scene)
-        return pb
-    need = (C.c_int64 * nv)()
-    ms = (C.c_float * _lib.PGR_NUM_STAGES)()
-    with torch.cuda.device(device):
-        for _attempt in range(3):
-            nbytes = L.pgr_batch_workspace_bytes(n, W, H, max_inst, nv)
-            if nbytes == 0:
-                raise ValueError("pgr_batch_workspace_bytes: invalid sizes")
-            ws = _WS.get(device, nbytes)
+                _lib.check(L.pgr_forward_posed_async(scene, sem, posed_ref, *args), "pgr_forward_posed_async")
+            event = torch.cuda.Event()
+            event.record(torch.cuda.current_stream(device))
+        return scratch, event
+
+    def waited_on(slot):
+        """Asynchronous attempts on ``slot``, each waited for, until the capacity holds; a grown capacity is learned."""
+        def run(capacity):
+            scratch, event = enqueue(slot, capacity)
+            event.synchronize()
+            return _batch_status(scratch, nv)
+        start = _WS.capacity_hint.get(key, default_capacity)
+        status, need, capacity = _until_fits(run, start, 1.6)
+        _lib.check(status, "pgr_batch_status")
+        if capacity != start:
+            _learn(key, capacity)
+        return need, capacity
+
+    def run_plain(capacity):
+        """One synchronous attempt on the pooled workspace: (status, per-view instance counts)."""
+        nonlocal ws
+        need = (C.c_int64 * nv)()
+        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        with torch.cuda.device(device):
+            ws = workspace(0, capacity)
             if stage_ms is not None:
-                status = L.pgr_forward_batch_profiled(C.byref(scene), C.byref(sem_struct) if sem_struct else None,
-                                                      nv, cams, outs, C.c_void_p(ws.data_ptr()), ws.numel(),
-                                                      max_inst, need, stream, ms)
+                ms = (C.c_float * _lib.PGR_NUM_STAGES)()
+                status = L.pgr_forward_batch_profiled(scene, sem, nv, cams, outs, C.c_void_p(ws.data_ptr()), ws.numel(),
+                                                      capacity, need, stream, ms)
+                stage_ms[:] = list(ms)
             else:
-                status = L.pgr_forward_batch(C.byref(scene), nv, cams, outs, C.c_void_p(ws.data_ptr()), ws.numel(),
-                                             max_inst, need, stream)
-            if status != _lib.PGR_ERR_INSTANCE_OVERFLOW:
-                break
-            max_inst = grown_capacity(max(need), 1.25)   # grow to what the largest view needs, then retry
-        _lib.check(status, "pgr_forward_batch")
-    used_max_inst = max_inst
-    peak = max(need) if nv else 0
-    if peak > 0.8 * max_inst:
-        max_inst = grown_capacity(peak, 1.6)
-    _WS.capacity_hint[key] = max_inst
-    if stage_ms is not None:
-        stage_ms[:] = list(ms)
-    _LAST_INFO.clear()
-    _LAST_INFO.update(num_instances=[int(x) for x in need], max_instances=int(max_inst),
-                      used_max_instances=int(used_max_inst), n=n, width=W, height=H, n_views=nv,
-                      workspace=ws, workspace_bytes=int(ws.numel()))
-    del keep
-    return results
+                status = L.pgr_forward_batch(scene, nv, cams, outs, C.c_void_p(ws.data_ptr()), ws.numel(), capacity,
+                                             need, stream)
+        return status, need
+
+    def render_sync():
+        if fused:
+            need, capacity = waited_on("sync-fused")
+            _remember(key, need, capacity, ws)
+        else:
+            status, need, capacity = _until_fits(run_plain, _WS.capacity_hint.get(key, default_capacity), 1.25)
+            _lib.check(status, "pgr_forward_batch")
+            _remember(key, need, capacity, ws, max_instances=_learn(key, capacity, max(need)))
+        return results
+
+    def render_layers_again():       # a layered call is asynchronous only: so is its retry, on the same slot
+        waited_on(async_slot)
+        return results
+
+    if async_slot is None:
+        return render_sync()
+    capacity = _WS.capacity_hint.get(key, default_capacity)
+    scratch, event = enqueue(async_slot, capacity, early=early_status and layers is None)
+    return PendingBatch(results, event, scratch, ws, key, capacity, render_sync if layers is None else render_layers_again,
+                        (tensors, cam_tensors, poses, semantic, posed, layers), record_info)
 
 
 def workspace_view(view_index: int = 0) -> dict:
@@ -437,16 +463,9 @@ def block_visibility(means3D, views: Sequence[ViewSpec], *, scales=None, rotatio
     n, nv = int(means3D.shape[0]), len(views)
     means3D, scales, rotations, cov3D_precomp = (dev_f32(t, device) for t in (means3D, scales, rotations, cov3D_precomp))
     ones = torch.ones((max(n, 1), 3), dtype=torch.float32, device=device)       # opacities / colours are not looked at
-    scene = _lib.PgrScene(n=n, means3d=_ptr(means3D), opacities=_ptr(ones), scales=_ptr(scales), rotations=_ptr(rotations),
-                          cov3d_precomp=_ptr(cov3D_precomp), shs=None, colors_precomp=_ptr(ones), sh_degree=0, sh_stride=0,
-                          scale_modifier=float(scale_modifier), tie_index=None)
-    cams = (_lib.PgrCamera * nv)()
-    keep = []
-    for i, v in enumerate(views):
-        bg, vm, pm, cp = (dev_f32(t, device) for t in (v.bg, v.viewmatrix, v.projmatrix, v.campos))
-        keep.append((bg, vm, pm, cp))
-        cams[i] = _lib.PgrCamera(image_width=int(v.image_width), image_height=int(v.image_height), tanfovx=float(v.tanfovx),
-                                 tanfovy=float(v.tanfovy), viewmatrix=_ptr(vm), projmatrix=_ptr(pm), campos=_ptr(cp), bg=_ptr(bg))
+    scene = scene_struct(n, means3D, ones, colors_precomp=ones, scales=scales, rotations=rotations,
+                         cov3D_precomp=cov3D_precomp, scale_modifier=scale_modifier)
+    cams, _cam_tensors = camera_structs(views, device)
     groups, words = (n + 63) // 64, (nv + 31) // 32
     out = torch.zeros((groups, words), dtype=torch.int32, device=device)
     with torch.cuda.device(device):
@@ -470,7 +489,7 @@ def scene_prepare(n: int, tie_index: Optional[torch.Tensor] = None, semantic: Op
     device = ref.device
     if device.type != "cuda":
         raise RuntimeError("scene_prepare needs tensors on a HIP device")
-    scene = _lib.PgrScene(n=int(n), tie_index=_ptr(tie_index))
+    scene = scene_struct(n, tie_index=tie_index)
     sem = None
     if semantic is not None:
         sem = _lib.PgrSemantic(object_id=_ptr(semantic["object_id"]), colors=_ptr(semantic["colors"]),

@@ -2,6 +2,8 @@
 semantic descriptor that is rejected before anything is enqueued.  (The reference extension sizes its buffers on the
 host after a device->host read of the instance total -- SURVEY.md section 2a -- and simply fails to allocate; here the
 total is computed on the device, so the device must not wrap.)"""
+import math
+
 import numpy as np
 import pytest
 
@@ -155,7 +157,7 @@ def test_early_status_reports_every_view_of_a_batch(gpu_device):
     assert min(need) < max(need)
     pb = R.forward_views(fr.means3d, fr.opacities, specs, async_slot=("early-batch", 0), early_status=True, **kw)
     got = pb.wait()
-    assert pb.num_instances == need and not getattr(pb, "_was_redone", False)
+    assert pb.num_instances == need and not pb.redone
     for g, r in zip(got, ref):
         assert torch.equal(g["color"], r["color"]) and torch.equal(g["depth"], r["depth"])
     # room for the lightest view only: the flags of the others arrive with the early status, the batch is rendered again
@@ -165,6 +167,122 @@ def test_early_status_reports_every_view_of_a_batch(gpu_device):
     pb = R.forward_views(fr.means3d, fr.opacities, specs, async_slot=("early-batch", 0), early_status=True, **kw)
     got = pb.wait()
     torch.cuda.synchronize()
-    assert getattr(pb, "_was_redone", False) and pb.num_instances == need
+    assert pb.redone and pb.num_instances == need
     for g, r in zip(got, ref):
         assert torch.equal(g["color"], r["color"]) and torch.equal(g["depth"], r["depth"])
+
+
+OVERFLOW_MODES = ("plain", "profiled", "sync-fused", "async", "early-status", "layers", "autograd", "autograd-batch")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", OVERFLOW_MODES)
+def test_every_call_mode_after_an_instance_overflow(gpu_device, mode):
+    """Each forward call mode, forced to overflow by a learned capacity far below its need: the outputs equal those of a
+    render that fitted, bit for bit, a handle reports the re-render, and the learned capacity is the mode's own -- g(p, 1.25)
+    after the synchronous plain and profiled calls (retried inside the call), g(p, 1.6) after the synchronous fused call and
+    after a handle's wait() (then re-rendered synchronously, or on its own slot when layered), and none at all after the
+    autograd path, which keeps its own workspace from max(1 << 18, 4 n) and retries at g(p, 1.25)."""
+    import torch
+    from pegasus_amd import frames as F, rasterizer as R
+    from pegasus_amd.diff_gaussian_rasterization import (GaussianRasterizationSettings, GaussianRasterizer,
+                                                         rasterize_gaussians_batch)
+    dev = torch.device(gpu_device)
+    if mode.startswith("autograd"):
+        # a few thousand splats around the C1 cube's centre that each cover the whole image: 4000 x 300 tiles, far more
+        # (Gaussian, tile) instances than the 1 << 18 the autograd path starts from
+        n, V = 4000, 1 if mode == "autograd" else 2
+        gen = torch.Generator(device="cpu").manual_seed(0)
+        means = (torch.rand((n, 3), generator=gen) - 0.5).mul_(0.2).to(dev)
+        ops = torch.full((n, 1), 0.05, device=dev)
+        scales = torch.full((n, 3), 100.0, device=dev)
+        rots = torch.zeros((n, 4), device=dev)
+        rots[:, 0] = 1.0
+        colors = torch.rand((n, 3), generator=gen).to(dev)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+        eyes = ((0.0, 0.0, -3.0), (0.6, 0.4, -3.0))[:V]         # (C1's camera, and one beside it)
+        c1 = [scenes.make_view(*scenes.G.look_at_opencv(e, (0.0, 0.0, 0.0), up=(0.0, -1.0, 0.0)), 320, 240,
+                               fovx=math.radians(50.0), fovy=math.radians(40.0)) for e in eyes]
+        sets = [GaussianRasterizationSettings(240, 320, v.tanfovx, v.tanfovy, t(np.zeros(3)), 1.0, t(v.world_view_transform),
+                                              t(v.full_proj_transform), 0, t(v.camera_center), False, False) for v in c1]
+        key = (dev, n, 320, 240)
+        R.set_capacity_hint(key, 2 * n * 20 * 15)         # room for every splat in every tile: the reference fits at once
+        want = R.forward_views(means, ops, sets, colors_precomp=colors, scales=scales, rotations=rots, want_aux=True)
+        torch.cuda.synchronize()
+        assert min(R.last_forward_info()["num_instances"]) > max(1 << 18, 4 * n)
+        R.set_capacity_hint(key, None)
+        hints = R.capacity_hints()
+        leaf = means.clone().requires_grad_(True)
+        if V == 1:
+            got = [x.unsqueeze(0) for x in GaussianRasterizer(sets[0])(leaf, None, ops, colors_precomp=colors, scales=scales,
+                                                                       rotations=rots, return_alpha=True)]
+        else:
+            got = rasterize_gaussians_batch(leaf, None, ops, sets, colors_precomp=colors, scales=scales, rotations=rots,
+                                            return_alpha=True)
+        color, radii, depth, alpha = got
+        (color.sum() + depth.sum() + alpha.sum()).backward()  # the backward walks the lists of the grown workspace
+        torch.cuda.synchronize()
+        for v in range(V):
+            assert torch.equal(color[v], want[v]["color"]) and torch.equal(depth[v], want[v]["depth"])
+            assert torch.equal(radii[v], want[v]["radii"]) and torch.equal(alpha[v, 0], 1.0 - want[v]["final_T"])
+        assert bool(torch.isfinite(leaf.grad).all()) and float(leaf.grad.abs().sum()) > 0
+        assert R.capacity_hints() == hints                  # the autograd path learns nothing
+        return
+
+    cloud, views = scenes.scene_c3(scale=0.04, n_views=2, width=320, height=240)
+    act = cloud.activated()
+    fr = F.FrameRenderer(act["means3d"], act["opacities"], act["scales"], act["rotations"], act["shs"],
+                         cloud.object_id, sh_degree=3, device=gpu_device)
+    specs = [fr.view_spec(v) for v in views]
+    kw = dict(shs=fr.shs, scales=fr.scales, rotations=fr.rotations, sh_degree=fr.sh_degree, tie_index=fr.tie_index,
+              want_radii=False)
+    n, keys = int(fr.means3d.shape[0]), ("color", "depth")
+    if mode == "layers":
+        n = int(fr.obj["means3d"].shape[0])
+        kw = dict(shs=fr.sem_shs, scales=fr.obj["scales"], rotations=fr.obj["rotations"], sh_degree=0,
+                  tie_index=fr.obj_tie_index, want_radii=False,
+                  layers=dict(layer_id=fr.semantic["object_id"][fr.n_env:].contiguous(), n_layers=fr.K,
+                              mask_colors=fr.colors, mask_threshold=0.1))
+        keys = ("sem_masks",)
+    elif mode in ("sync-fused", "async"):
+        kw["semantic"] = fr.semantic
+        keys = ("color", "depth", "sem_color", "sem_depth")
+    if mode == "profiled":
+        kw["stage_ms"] = []
+    if mode in ("async", "early-status", "layers"):
+        kw["async_slot"] = ("overflow-" + mode, 0)
+    if mode == "early-status":
+        kw["early_status"] = True
+    means, ops = (fr.obj["means3d"], fr.obj["opacities"]) if mode == "layers" else (fr.means3d, fr.opacities)
+    key = (dev, n, 320, 240) + (("layers", fr.K) if mode == "layers" else ())
+
+    def render():
+        outs = None
+        if mode == "layers":
+            outs = [dict(radii=None, sem_masks=torch.zeros((fr.K, 240, 320), dtype=torch.uint8, device=dev)) for _ in specs]
+        got = R.forward_views(means, ops, specs, outputs=outs, **kw)
+        pb = None
+        if "async_slot" in kw:
+            pb, got = got, got.wait()
+        torch.cuda.synchronize()
+        need = pb.num_instances if pb is not None else R.last_forward_info()["num_instances"]
+        return [{k: r[k].clone() for k in keys} for r in got], pb, max(int(x) for x in need)
+
+    R.set_capacity_hint(key, None)
+    R.drop_async_workspaces()
+    want, pb, peak = render()
+    assert pb is None or not pb.redone
+    assert peak > 4096
+    R.set_capacity_hint(key, peak // 3)                    # far below the need: the next call overflows
+    R.drop_async_workspaces()
+    got, pb, peak_again = render()
+    assert peak_again == peak
+    if pb is not None:
+        assert pb.redone
+    for r, w in zip(got, want):
+        for k in keys:
+            assert torch.equal(r[k], w[k]), k
+    factor = 1.25 if mode in ("plain", "profiled") else 1.6
+    assert R.capacity_hints()[key] == R.grown_capacity(peak, factor)
+    if mode == "profiled":
+        assert len(kw["stage_ms"]) == 5

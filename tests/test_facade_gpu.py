@@ -430,7 +430,7 @@ def test_render_follows_cameras_with_transposed_matrices_and_in_place_edits(gpu_
 def test_render_after_an_instance_overflow_redoes_the_queued_visibility_filter(gpu_device):
     """render() queues its visibility filter (radii > 0) behind the compositor BEFORE it reads the batch's status; if that
     status says "instance overflow" the view is rendered again and the filter must be taken from the NEW radii (the
-    `_was_redone` branch of diff_gaussian_rasterization.rasterize_gaussians): a capacity hint far below the view's need
+    `redone` branch of diff_gaussian_rasterization.rasterize_gaussians): a capacity hint far below the view's need
     forces the branch; image, radii and visibility_filter must equal the roomy first call's."""
     import sys
     from argparse import ArgumentParser

@@ -411,3 +411,57 @@ def test_capacity_and_cache_reset_hooks_are_public():
     assert RW.swap_cache(None) == {}
     with pytest.raises(RuntimeError, match="per-view limit"):      # the bounded retries end in this error, never in a recursion
         R.grown_capacity(R.MAX_INSTANCES + 1, 1.6)
+
+
+def test_overflow_retry_loop_grows_converges_and_gives_up():
+    """rasterizer._until_fits, the one instance-overflow retry of every forward call, driven by a fake attempt: it grows to
+    grown_capacity(largest count, factor), returns the capacity that held, stops after 3 attempts and lets the per-view
+    limit error through."""
+    from pegasus_amd import _lib, rasterizer as R
+    OVERFLOW = _lib.PGR_ERR_INSTANCE_OVERFLOW
+
+    def fake(counts):
+        seen = []
+
+        def run(capacity):
+            seen.append(capacity)
+            return (OVERFLOW if max(counts) > capacity else _lib.PGR_OK), counts
+        return run, seen
+
+    run, seen = fake([5000, 9000])                     # fits at once: one attempt, the capacity unchanged
+    assert R._until_fits(run, 10000, 1.25) == (_lib.PGR_OK, [5000, 9000], 10000) and seen == [10000]
+    for factor in (1.25, 1.6):                         # one overflow: the second attempt runs at the grown capacity
+        run, seen = fake([3000, 1_000_000])
+        grown = R.grown_capacity(1_000_000, factor)
+        assert grown == int(1_000_000 * factor) + 1024
+        assert R._until_fits(run, 4096, factor) == (_lib.PGR_OK, [3000, 1_000_000], grown) and seen == [4096, grown]
+    growing = []
+
+    def never_fits(capacity):                          # a count that outgrows every capacity: 3 attempts, then an error
+        growing.append(capacity)
+        return OVERFLOW, [2 * capacity]
+    with pytest.raises(RuntimeError, match="did not converge"):
+        R._until_fits(never_fits, 1000, 1.25)
+    assert growing == [1000, R.grown_capacity(2000, 1.25), R.grown_capacity(2 * R.grown_capacity(2000, 1.25), 1.25)]
+    invalid = lambda capacity: (_lib.PGR_ERR_INVALID_ARGUMENT, [0])     # any other status ends the loop: the caller checks it
+    assert R._until_fits(invalid, 10, 1.6) == (_lib.PGR_ERR_INVALID_ARGUMENT, [0], 10)
+    run, seen = fake([R.MAX_INSTANCES + 1])            # more than one view may list: the per-view limit, at once
+    with pytest.raises(RuntimeError, match="per-view limit"):
+        R._until_fits(run, 1 << 20, 1.6)
+    assert seen == [1 << 20]
+
+
+def test_learned_capacity_only_grows_and_keeps_headroom():
+    """rasterizer._learn: the learned capacity of a scene shape never drops, and a peak above 80 % of the capacity it ran
+    at asks for grown_capacity(peak, 1.6)."""
+    from pegasus_amd import rasterizer as R
+    key = ("cpu", 123, 4, 4)
+    try:
+        assert R._learn(key, 1000) == 1000 and R.capacity_hints()[key] == 1000
+        assert R._learn(key, 500) == 500 and R.capacity_hints()[key] == 1000            # max with what it held
+        assert R._learn(key, 2000, peak=1600) == 2000 and R.capacity_hints()[key] == 2000   # 80 %: room enough
+        assert R._learn(key, 2000, peak=1601) == R.grown_capacity(1601, 1.6) == R.capacity_hints()[key]
+        with pytest.raises(RuntimeError, match="per-view limit"):
+            R._learn(key, R.MAX_INSTANCES, peak=R.MAX_INSTANCES + 1)
+    finally:
+        R.set_capacity_hint(key, None)
