@@ -379,6 +379,42 @@ size_t pgr_knn_workspace_bytes(int32_t n);
 int32_t pgr_knn_mean_dist2(int32_t n, const float *xyz, float *out, void *workspace, size_t workspace_bytes,
                            void *stream);
 
+/* Object meshes from a trained model's rendered views (pegasus_amd/mesh.py; replaces the open3d alpha shape of the
+ * reference's reconstruction step).  A regular grid: point (i,j,k) sits at origin + voxel*(i,j,k); a field over it is
+ * float32 [nz,ny,nx], x fastest.  Every axis holds 2 .. 1024 points.  Results are identical from run to run. */
+typedef struct PgrGrid {
+    int32_t nx, ny, nz;
+    float origin[3];
+    float voxel;
+} PgrGrid;
+
+/* TSDF fusion with space carving.  `depth` (PGR_DEPTH_NORMALIZED) and `final_T` are device [n_views,H,W], all views of
+ * one size (cameras[v].image_width/height), n_views 1..256; each camera's viewmatrix and tanfovx/y place its view (the
+ * other PgrCamera fields are not read).  Per grid point p and view v in order, in float32:
+ *   (x,y,z) = viewmatrix_v . p; skipped when z <= 0.2 (the renderer's near cull)
+ *   pixel = floor((x/z) * W/(2 tanfovx) + (W-1)/2 + 0.5), likewise y; skipped outside the image
+ *   1 - final_T < alpha_min: carved (sdf = +1); else d = depth - z, skipped when d < -truncation,
+ *   else s += min(d, truncation) / truncation, w += 1
+ * sdf = carved ? +1 : (w == 0 ? -1 : s / w); the outermost layer of points is +1, so the surface closes.  Positive is
+ * outside.  `sdf` is device [nz,ny,nx]. */
+int32_t pgr_tsdf_integrate(const PgrGrid *grid, int32_t n_views, const PgrCamera *cameras, const float *depth,
+                           const float *final_T, float truncation, float alpha_min, float *sdf, void *stream);
+
+/* Marching tetrahedra over `sdf` (inside: sdf < 0).  Every cell splits into the 6 tetrahedra around its
+ * (0,0,0)-(1,1,1) diagonal; the mesh is closed and manifold, its triangles face positive sdf.  Each grid point owns the
+ * edges +x, +y, +z, +x+y, +x+z, +y+z, +x+y+z (in that order) and emits one vertex per crossed edge, at
+ * pa + t (pb - pa), t = fa / (fa - fb), a = the owner.  Vertices come in (point, edge) order, faces in (cell,
+ * tetrahedron, triangle) order.  Workspace: pgr_march_workspace_bytes(nx, ny, nz) device bytes (0 for a bad grid),
+ * host-only.
+ * pgr_march_count writes the vertex and face totals to device int64 counts[2]; the caller reads them, allocates
+ * vertices float32 [V,3] and faces int32 [F,3] (V < 2^31), and calls pgr_march_emit with the same grid, sdf and
+ * workspace, which it reads only. */
+size_t pgr_march_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int32_t pgr_march_count(const PgrGrid *grid, const float *sdf, void *workspace, size_t workspace_bytes, int64_t *counts,
+                        void *stream);
+int32_t pgr_march_emit(const PgrGrid *grid, const float *sdf, const void *workspace, size_t workspace_bytes,
+                       float *vertices, int32_t *faces, void *stream);
+
 /* Gradients returned by pgr_backward / pgr_backward_batch (device pointers, any may be NULL = not wanted). */
 typedef struct PgrGradOutputs {
     float *means2d;              /* [n,3] screen-space mean, NDC-scaled (what viewspace_points.grad receives) */

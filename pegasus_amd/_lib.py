@@ -112,6 +112,10 @@ class PgrAdamGroup(C.Structure):
 PGR_ADAM_MAX_GROUPS = 16
 
 
+class PgrGrid(C.Structure):
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("origin", C.c_float * 3), ("voxel", C.c_float)]
+
+
 # every symbol include/pegasus_raster.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "pgr_abi_version": (C.c_int32, []),
@@ -205,6 +209,12 @@ SYMBOLS = {
     "pgr_adam_step": (C.c_int32, [C.POINTER(PgrAdamGroup), C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p]),
     "pgr_densify_stats": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
+    "pgr_tsdf_integrate": (C.c_int32, [C.POINTER(PgrGrid), C.c_int32, C.POINTER(PgrCamera), C.c_void_p, C.c_void_p,
+                                       C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "pgr_march_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "pgr_march_count": (C.c_int32, [C.POINTER(PgrGrid), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "pgr_march_emit": (C.c_int32, [C.POINTER(PgrGrid), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
 }
 
 _lib = None

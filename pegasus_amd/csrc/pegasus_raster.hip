@@ -19,6 +19,7 @@
 #include "backward.hip.h"
 #include "blockcull.hip.h"
 #include "knn.hip.h"
+#include "mesh.hip.h"
 #include "compose.hip.h"
 #include "composite.hip.h"
 #include "pgr_common.h"
@@ -1187,6 +1188,109 @@ int32_t pgr_knn_mean_dist2(int32_t n, const float* xyz, float* out, void* worksp
     knn_scatter_kernel<<<blocks, 256, 0, stream>>>(n, xyz, grid, count, sorted);
     knn_search_kernel<<<blocks, 256, 0, stream>>>(n, grid, start, sorted, out);
     return hip_ok(hipGetLastError(), "knn launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+// ---- object meshes: TSDF fusion of rendered views, marching tetrahedra (mesh.hip.h) ------------------------------------
+namespace {
+constexpr int32_t MESH_MAX_AXIS = 1024;
+bool grid_ok(const PgrGrid* g) {
+    if (!g) return false;
+    for (int32_t a : {g->nx, g->ny, g->nz})
+        if (a < 2 || a > MESH_MAX_AXIS) return false;
+    return std::isfinite(g->origin[0]) && std::isfinite(g->origin[1]) && std::isfinite(g->origin[2]) &&
+           std::isfinite(g->voxel) && g->voxel > 0.f;
+}
+MeshGrid mesh_grid(const PgrGrid* g) { return MeshGrid{g->nx, g->ny, g->nz, g->origin[0], g->origin[1], g->origin[2], g->voxel}; }
+size_t grid_points(const PgrGrid* g) { return (size_t)g->nx * g->ny * g->nz; }
+struct MarchLayout { size_t mask, ntri, vbase, tile_tot, tile_off, total; int tiles; };
+MarchLayout march_layout(size_t n) {
+    MarchLayout M{};
+    M.tiles = (int)((n + MARCH_TILE - 1) / MARCH_TILE);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes ? bytes : 1); return o; };
+    M.mask = take(n);
+    M.ntri = take(n);
+    M.vbase = take(n * sizeof(int32_t));
+    M.tile_tot = take((size_t)M.tiles * 2 * sizeof(long long));
+    M.tile_off = take((size_t)M.tiles * 2 * sizeof(long long));
+    M.total = off;
+    return M;
+}
+}  // namespace
+
+int32_t pgr_tsdf_integrate(const PgrGrid* grid, int32_t n_views, const PgrCamera* cameras, const float* depth,
+                           const float* final_T, float truncation, float alpha_min, float* sdf, void* stream_v) {
+    if (!grid_ok(grid) || n_views < 1 || n_views > TSDF_MAX_VIEWS || !cameras || !depth || !final_T || !sdf)
+        return PGR_ERR_INVALID_ARGUMENT;
+    if (!(truncation > 0.f) || !std::isfinite(truncation) || std::isnan(alpha_min)) return PGR_ERR_INVALID_ARGUMENT;
+    const int32_t W = cameras[0].image_width, H = cameras[0].image_height;
+    if (W <= 0 || H <= 0 || (int64_t)W * H > (int64_t)1 << 28) return PGR_ERR_INVALID_ARGUMENT;
+    TsdfArgs a{};
+    for (int32_t v = 0; v < n_views; ++v) {
+        const PgrCamera& c = cameras[v];
+        if (c.image_width != W || c.image_height != H || !c.viewmatrix || !(c.tanfovx > 0.f) || !(c.tanfovy > 0.f))
+            return PGR_ERR_INVALID_ARGUMENT;
+        a.view[v] = c.viewmatrix;
+        a.fx[v] = (float)((double)W / (2.0 * (double)c.tanfovx));
+        a.fy[v] = (float)((double)H / (2.0 * (double)c.tanfovy));
+    }
+    a.g = mesh_grid(grid);
+    a.n_views = n_views;
+    a.width = W;
+    a.height = H;
+    a.cx = (float)(W - 1) * 0.5f;
+    a.cy = (float)(H - 1) * 0.5f;
+    a.truncation = truncation;
+    a.alpha_min = alpha_min;
+    a.depth = depth;
+    a.final_T = final_T;
+    a.sdf = sdf;
+    const dim3 block(TSDF_BX, TSDF_BY, TSDF_BZ);
+    const dim3 blocks((grid->nx + TSDF_BX - 1) / TSDF_BX, (grid->ny + TSDF_BY - 1) / TSDF_BY, (grid->nz + TSDF_BZ - 1) / TSDF_BZ);
+    tsdf_integrate_kernel<<<blocks, block, 0, static_cast<hipStream_t>(stream_v)>>>(a);
+    return hip_ok(hipGetLastError(), "tsdf_integrate launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+size_t pgr_march_workspace_bytes(int32_t nx, int32_t ny, int32_t nz) {
+    const PgrGrid g{nx, ny, nz, {0.f, 0.f, 0.f}, 1.f};
+    return grid_ok(&g) ? march_layout(grid_points(&g)).total : 0;
+}
+
+int32_t pgr_march_count(const PgrGrid* grid, const float* sdf, void* workspace, size_t workspace_bytes, int64_t* counts,
+                        void* stream_v) {
+    if (!grid_ok(grid) || !sdf || !workspace || !counts) return PGR_ERR_INVALID_ARGUMENT;
+    const size_t n = grid_points(grid);
+    const MarchLayout M = march_layout(n);
+    if (workspace_bytes < M.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    char* ws = static_cast<char*>(workspace);
+    auto* tile_tot = reinterpret_cast<long long*>(ws + M.tile_tot);
+    march_count_kernel<<<M.tiles, MARCH_THREADS, 0, stream>>>(mesh_grid(grid), sdf, n, reinterpret_cast<uint8_t*>(ws + M.mask),
+                                                              reinterpret_cast<uint8_t*>(ws + M.ntri), tile_tot);
+    auto* tile_off = reinterpret_cast<long long*>(ws + M.tile_off);
+    march_scan_kernel<<<1, MARCH_SCAN_THREADS, 0, stream>>>(tile_tot, M.tiles, tile_off, reinterpret_cast<long long*>(counts));
+    march_vbase_kernel<<<M.tiles, MARCH_THREADS, 0, stream>>>(n, reinterpret_cast<uint8_t*>(ws + M.mask), tile_off,
+                                                              reinterpret_cast<int32_t*>(ws + M.vbase));
+    return hip_ok(hipGetLastError(), "march_count launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+int32_t pgr_march_emit(const PgrGrid* grid, const float* sdf, const void* workspace, size_t workspace_bytes, float* vertices,
+                       int32_t* faces, void* stream_v) {
+    if (!grid_ok(grid) || !sdf || !workspace || !vertices || !faces) return PGR_ERR_INVALID_ARGUMENT;
+    const size_t n = grid_points(grid);
+    const MarchLayout M = march_layout(n);
+    if (workspace_bytes < M.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    const char* ws = static_cast<const char*>(workspace);
+    const auto* mask = reinterpret_cast<const uint8_t*>(ws + M.mask);
+    const auto* tile_off = reinterpret_cast<const long long*>(ws + M.tile_off);
+    const auto* vbase = reinterpret_cast<const int32_t*>(ws + M.vbase);
+    march_vertices_kernel<<<(unsigned)((n + MARCH_THREADS - 1) / MARCH_THREADS), MARCH_THREADS, 0, stream>>>(
+        mesh_grid(grid), sdf, n, mask, vbase, vertices);
+    march_faces_kernel<<<M.tiles, MARCH_THREADS, 0, stream>>>(mesh_grid(grid), sdf, n, mask,
+                                                              reinterpret_cast<const uint8_t*>(ws + M.ntri), tile_off, vbase,
+                                                              faces);
+    return hip_ok(hipGetLastError(), "march_emit launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
 }
 
 // ---- training step: fused L1 + D-SSIM loss, Adam over all parameter groups, densification statistics (train.hip.h) ------

@@ -1,0 +1,396 @@
+"""Watertight object meshes from trained Gaussian models: the step between training and physics / BOP records.
+
+The reference builds an object's mesh and URDF from the trained model's point cloud with an open3d alpha shape.  Here
+the model is rendered from a sphere of views (depth and alpha from one ``forward_views`` batch), the views are fused
+into a truncated signed distance field with space carving (``pgr_tsdf_integrate``), and marching tetrahedra extracts
+the closed outer surface (``pgr_march_count`` / ``pgr_march_emit``).  A density level set would not do: a trained
+3DGS object is a shell of surface Gaussians, and its level set is two nested surfaces.
+
+    python -m pegasus_amd.mesh -m <model dir> --out <dir> --obj_id N [--scale 1000] [--mass 0.1] [--resolution 256]
+
+writes ``<out>/models/obj_NNNNNN.ply`` (scaled: BOP models are in mm) with its ``models_info.json`` entry, and
+``<out>/urdf/obj_NNNNNN.{obj,urdf}`` in the model's own units for pybullet.
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import math
+import os
+import xml.etree.ElementTree as ET
+from dataclasses import dataclass
+from pathlib import Path
+from typing import Optional, Sequence
+
+import numpy as np
+
+from . import _lib
+from .ply_io import write_ply_mesh
+
+NEAR_Z = 0.2                 # pgr_common.h: the renderer culls everything closer than this
+MAX_AXIS = 1024
+MAX_VIEWS = 256
+
+
+@dataclass
+class Grid:
+    """Grid point (i,j,k) sits at origin + voxel*(i,j,k); fields over it are [nz,ny,nx], x fastest."""
+    nx: int
+    ny: int
+    nz: int
+    origin: tuple
+    voxel: float
+
+    @property
+    def shape(self):
+        return (self.nz, self.ny, self.nx)
+
+    def struct(self) -> _lib.PgrGrid:
+        return _lib.PgrGrid(nx=int(self.nx), ny=int(self.ny), nz=int(self.nz),
+                            origin=(C.c_float * 3)(*[float(x) for x in self.origin]), voxel=float(self.voxel))
+
+    @staticmethod
+    def around(lo, hi, resolution: int) -> "Grid":
+        """The grid over the box [lo, hi] with ``resolution`` points on its longest axis, centred on the box."""
+        lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+        ext = hi - lo
+        voxel = float(ext.max()) / (resolution - 1)
+        n = [int(min(MAX_AXIS, max(2, math.ceil(e / voxel - 1e-9) + 1))) for e in ext]
+        center = 0.5 * (lo + hi)
+        origin = tuple(float(c - 0.5 * voxel * (k - 1)) for c, k in zip(center, n))
+        return Grid(n[0], n[1], n[2], origin, voxel)
+
+
+@dataclass
+class Mesh:
+    vertices: np.ndarray         # float32 [V,3]
+    faces: np.ndarray            # int32 [F,3], outward winding
+
+    def _tets(self):
+        v = self.vertices.astype(np.float64)[self.faces]                  # [F,3,3]: tetrahedra (0, a, b, c)
+        return v, np.einsum("fi,fi->f", v[:, 0], np.cross(v[:, 1], v[:, 2])) / 6.0
+
+    def volume(self) -> float:
+        """Enclosed volume (divergence theorem over the closed mesh)."""
+        return float(self._tets()[1].sum())
+
+    def center_of_mass(self) -> np.ndarray:
+        v, vol = self._tets()
+        return (vol[:, None] * v.sum(axis=1) / 4.0).sum(axis=0) / vol.sum()
+
+    def inertia(self, mass: float) -> np.ndarray:
+        """3x3 inertia tensor about the centre of mass, uniform density, total ``mass``."""
+        v, vol = self._tets()
+        s = v.sum(axis=1)
+        second = (vol[:, None, None] / 20.0 * (np.einsum("fki,fkj->fij", v, v) + s[:, :, None] * s[:, None, :])).sum(axis=0)
+        c = self.center_of_mass()
+        cov = mass / vol.sum() * second - mass * np.outer(c, c)
+        return np.trace(cov) * np.eye(3) - cov
+
+    def largest_component(self) -> "Mesh":
+        """The connected piece that encloses the most volume (a cavity's inward faces count negative), vertices
+        renumbered in their old order."""
+        from scipy.sparse import coo_matrix
+        from scipy.sparse.csgraph import connected_components
+        nv = len(self.vertices)
+        if len(self.faces) == 0:
+            return self
+        f = self.faces.astype(np.int64)
+        adj = coo_matrix((np.ones(2 * len(f)), (np.r_[f[:, 0], f[:, 1]], np.r_[f[:, 1], f[:, 2]])), shape=(nv, nv))
+        n, label = connected_components(adj, directed=False)
+        if n == 1:
+            return self
+        face_label = label[f[:, 0]]
+        keep = face_label == np.bincount(face_label, weights=self._tets()[1], minlength=n).argmax()
+        used = np.zeros(nv, bool)
+        used[f[keep].ravel()] = True
+        remap = np.cumsum(used) - 1
+        return Mesh(self.vertices[used], remap[f[keep]].astype(np.int32))
+
+    def scaled(self, scale: float) -> "Mesh":
+        return Mesh((self.vertices.astype(np.float64) * scale).astype(np.float32), self.faces)
+
+
+# ---- the two GPU stages ---------------------------------------------------------------------------------------------
+def integrate(depth, final_T, views, grid: Grid, truncation: float, alpha_min: float):
+    """TSDF fusion with space carving (pgr_tsdf_integrate): float32 sdf [nz,ny,nx] on the device, positive outside.
+    ``depth`` (normalised, depth mode 1) and ``final_T`` are device [V,H,W] (or [V,1,H,W]); ``views`` the V ViewSpecs
+    (or GaussianRasterizationSettings) they were rendered with."""
+    import torch
+    from .rasterizer import camera_structs
+    if not (1 <= len(views) <= MAX_VIEWS):
+        raise ValueError(f"integrate takes 1..{MAX_VIEWS} views, got {len(views)}")
+    device = depth.device
+    if device.type != "cuda":
+        raise RuntimeError("integrate needs tensors on a HIP device; there is no CPU path")
+    V = len(views)
+    depth = depth.reshape(V, *depth.shape[-2:]).float().contiguous()
+    final_T = final_T.reshape(V, *final_T.shape[-2:]).float().contiguous()
+    if depth.shape != final_T.shape or depth.shape[1:] != (int(views[0].image_height), int(views[0].image_width)):
+        raise ValueError("depth and final_T must be [V,H,W] of the views' image size")
+    cams, keep = camera_structs(views, device)
+    sdf = torch.empty(grid.shape, dtype=torch.float32, device=device)
+    g = grid.struct()
+    with torch.cuda.device(device):
+        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        _lib.check(_lib.lib().pgr_tsdf_integrate(C.byref(g), V, cams, C.c_void_p(depth.data_ptr()),
+                                                 C.c_void_p(final_T.data_ptr()), float(truncation), float(alpha_min),
+                                                 C.c_void_p(sdf.data_ptr()), stream), "pgr_tsdf_integrate")
+    del keep
+    return sdf
+
+
+def march(sdf, grid: Grid, stage_ms: Optional[dict] = None) -> Mesh:
+    """Marching tetrahedra over a device sdf [nz,ny,nx] (inside: sdf < 0).  Reads the two counts once between the
+    count and the emit pass: the only host wait.  ``stage_ms``: a dict that receives the GPU milliseconds of the
+    "count" (count + scan) and "emit" passes."""
+    import torch
+    L = _lib.lib()
+    device = sdf.device
+    if device.type != "cuda":
+        raise RuntimeError("march needs a tensor on a HIP device; there is no CPU path")
+    if tuple(sdf.shape) != grid.shape:
+        raise ValueError(f"sdf is {tuple(sdf.shape)}, the grid {grid.shape}")
+    sdf = sdf.float().contiguous()
+    g = grid.struct()
+    nbytes = L.pgr_march_workspace_bytes(grid.nx, grid.ny, grid.nz)
+    if nbytes == 0:
+        raise ValueError(f"grid {grid.shape}: every axis must hold 2..{MAX_AXIS} points")
+    with torch.cuda.device(device):
+        stream_t = torch.cuda.current_stream(device)
+        stream = C.c_void_p(stream_t.cuda_stream)
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+        counts = torch.zeros(2, dtype=torch.int64, device=device)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if stage_ms is not None else None
+        if ev:
+            ev[0].record(stream_t)
+        _lib.check(L.pgr_march_count(C.byref(g), C.c_void_p(sdf.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
+                                     C.c_void_p(counts.data_ptr()), stream), "pgr_march_count")
+        if ev:
+            ev[1].record(stream_t)
+        nv, nf = (int(x) for x in counts.cpu())
+        if nv >= 2 ** 31 or nf >= 2 ** 31:
+            raise ValueError(f"{nv} vertices / {nf} faces: more than int32 indices hold; use a coarser grid")
+        vertices = torch.empty((max(nv, 1), 3), dtype=torch.float32, device=device)
+        faces = torch.empty((max(nf, 1), 3), dtype=torch.int32, device=device)
+        _lib.check(L.pgr_march_emit(C.byref(g), C.c_void_p(sdf.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
+                                    C.c_void_p(vertices.data_ptr()), C.c_void_p(faces.data_ptr()), stream),
+                   "pgr_march_emit")
+        if ev:
+            ev[2].record(stream_t)
+        out = Mesh(vertices[:nv].cpu().numpy(), faces[:nf].cpu().numpy())
+        if ev:
+            stage_ms["count"] = ev[0].elapsed_time(ev[1])
+            stage_ms["emit"] = ev[1].elapsed_time(ev[2])
+    return out
+
+
+# ---- from a Gaussian model ------------------------------------------------------------------------------------------
+def default_bounds(xyz: np.ndarray, opacity: np.ndarray):
+    """Per axis the 0.5-99.5 percentile of the means of Gaussians with opacity >= 0.1, padded on every side by 10 % of
+    the longest extent (a Gaussian reaches beyond its mean; a thin axis keeps the same margin as the long ones)."""
+    sel = np.asarray(opacity).reshape(-1) >= 0.1
+    pts = np.asarray(xyz, np.float64)[sel] if sel.any() else np.asarray(xyz, np.float64)
+    lo, hi = np.percentile(pts, 0.5, axis=0), np.percentile(pts, 99.5, axis=0)
+    pad = 0.1 * max(float((hi - lo).max()), 1e-6)
+    return lo - pad, hi + pad
+
+
+def sphere_views(center, half_diag: float, n_views: int, image_size: int):
+    """The full Fibonacci sphere of look-at views around ``center`` at r = max(2.5 h, NEAR_Z + 2 h), with the field of
+    view that holds the sphere of radius h (which holds the box) and a 5 % margin.  Returns (ViewSpecs, radius, fov)."""
+    import torch
+    from . import graphics as G
+    from .rasterizer import ViewSpec
+    from .scenes import make_view
+    h = float(half_diag)
+    r = max(2.5 * h, NEAR_Z + 2.0 * h)
+    fov = 2.0 * math.atan(1.05 * h / math.sqrt(r * r - h * h))
+    center = np.asarray(center, np.float64)
+    specs = []
+    for R, t in G.hemisphere_views(n_views, r, elev_range=(-0.5 * math.pi, 0.5 * math.pi)):
+        eye = -R.T @ t + center
+        v = make_view(R, -R @ eye, image_size, image_size, fovx=fov, fovy=fov)
+        dev = lambda a: torch.as_tensor(np.asarray(a, np.float32), device="cuda")
+        specs.append(ViewSpec(image_size, image_size, v.tanfovx, v.tanfovy, dev(np.zeros(3)), dev(v.world_view_transform),
+                              dev(v.full_proj_transform), dev(v.camera_center), depth_mode=_lib.PGR_DEPTH_NORMALIZED))
+    return specs, r, fov
+
+
+def render_views(gaussians, views, stage_ms: Optional[dict] = None):
+    """Normalised depth and final_T [V,H,W] of ``views``, rendered in batches sized to the free device memory."""
+    import torch
+    from .rasterizer import forward_views
+    xyz = gaussians.get_xyz.detach()
+    n = int(xyz.shape[0])
+    H, W = int(views[0].image_height), int(views[0].image_width)
+    per_view = _lib.lib().pgr_batch_workspace_bytes(n, W, H, max(1 << 20, 6 * n), 1) + 6 * 4 * H * W
+    free, _total = torch.cuda.mem_get_info(xyz.device)
+    batch = int(max(1, min(32, len(views), (free // 4) // max(per_view, 1))))
+    depth = torch.empty((len(views), H, W), dtype=torch.float32, device=xyz.device)
+    final_T = torch.empty_like(depth)
+    kw = dict(shs=gaussians.get_features.detach(), scales=gaussians.get_scaling.detach(),
+              rotations=gaussians.get_rotation.detach(), sh_degree=int(gaussians.active_sh_degree))
+    opac = gaussians.get_opacity.detach()
+    start = torch.cuda.Event(enable_timing=True) if stage_ms is not None else None
+    if start:
+        start.record()
+    for b in range(0, len(views), batch):
+        outs = forward_views(xyz, opac, views[b:b + batch], want_radii=False, want_aux=True, **kw)
+        for k, r in enumerate(outs):
+            depth[b + k] = r["depth"][0]
+            final_T[b + k] = r["final_T"]
+    if start:
+        end = torch.cuda.Event(enable_timing=True)
+        end.record()
+        end.synchronize()
+        stage_ms["render"] = start.elapsed_time(end)
+    return depth, final_T
+
+
+def extract_mesh(gaussians, *, resolution: int = 256, n_views: int = 96, image_size: int = 512, alpha_min: float = 0.5,
+                 truncation_voxels: float = 4.0, bounds=None, stage_ms: Optional[dict] = None) -> Mesh:
+    """The closed outer surface of a GaussianModel (read through its activated getters), in the model's units.
+    ``bounds``: (lo[3], hi[3]) of the grid, default default_bounds().  ``resolution``: grid points on the longest axis.
+    ``stage_ms``: a dict that receives the GPU milliseconds of the render, integrate, count and emit stages."""
+    import torch
+    if not (2 <= resolution <= MAX_AXIS):
+        raise ValueError(f"resolution must be 2..{MAX_AXIS}")
+    if bounds is None:
+        bounds = default_bounds(gaussians.get_xyz.detach().cpu().numpy(), gaussians.get_opacity.detach().cpu().numpy())
+    lo, hi = (np.asarray(b, np.float64) for b in bounds)
+    grid = Grid.around(lo, hi, resolution)
+    views, _r, _fov = sphere_views(0.5 * (lo + hi), 0.5 * float(np.linalg.norm(hi - lo)), n_views, image_size)
+    if len(views) > MAX_VIEWS:
+        raise ValueError(f"n_views: at most {MAX_VIEWS} views are fused")
+    depth, final_T = render_views(gaussians, views, stage_ms)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if stage_ms is not None else None
+    if ev:
+        ev[0].record()
+    sdf = integrate(depth, final_T, views, grid, truncation_voxels * grid.voxel, alpha_min)
+    if ev:
+        ev[1].record()
+    mesh = march(sdf, grid, stage_ms)
+    if ev:
+        stage_ms["integrate"] = ev[0].elapsed_time(ev[1])
+    # a trained shell has gaps: rays through them carve pockets inside, and an unseen speck may stay outside; the body
+    # is the largest closed piece
+    return mesh.largest_component()
+
+
+# ---- files ----------------------------------------------------------------------------------------------------------
+def write_ply(path, mesh: Mesh, scale: float = 1.0):
+    """Binary PLY with vertex and face elements; vertices multiplied by ``scale`` (1000: metres -> BOP millimetres)."""
+    write_ply_mesh(path, mesh.scaled(scale).vertices, mesh.faces)
+
+
+def write_obj(path, mesh: Mesh):
+    path = Path(path)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "w") as f:
+        f.write("# closed mesh extracted from a Gaussian model\n")
+        np.savetxt(f, mesh.vertices, fmt="v %.9g %.9g %.9g")
+        np.savetxt(f, mesh.faces.astype(np.int64) + 1, fmt="f %d %d %d")
+
+
+def write_urdf(path, mesh_filename: str, mesh: Mesh, mass: float):
+    """One link: visual and collision are the mesh file, the inertial block holds the mesh's centre of mass, ``mass``
+    and inertia about the centre of mass at uniform density."""
+    c = mesh.center_of_mass()
+    I = mesh.inertia(mass)
+    robot = ET.Element("robot", name=Path(mesh_filename).stem)
+    link = ET.SubElement(robot, "link", name="base_link")
+    inertial = ET.SubElement(link, "inertial")
+    ET.SubElement(inertial, "origin", xyz=" ".join(f"{x:.9g}" for x in c), rpy="0 0 0")
+    ET.SubElement(inertial, "mass", value=f"{mass:.9g}")
+    ET.SubElement(inertial, "inertia", ixx=f"{I[0, 0]:.9g}", ixy=f"{I[0, 1]:.9g}", ixz=f"{I[0, 2]:.9g}",
+                  iyy=f"{I[1, 1]:.9g}", iyz=f"{I[1, 2]:.9g}", izz=f"{I[2, 2]:.9g}")
+    for tag in ("visual", "collision"):
+        e = ET.SubElement(link, tag)
+        ET.SubElement(e, "origin", xyz="0 0 0", rpy="0 0 0")
+        ET.SubElement(ET.SubElement(e, "geometry"), "mesh", filename=str(mesh_filename), scale="1 1 1")
+    ET.indent(robot)
+    path = Path(path)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    path.write_text('<?xml version="1.0"?>\n' + ET.tostring(robot, encoding="unicode") + "\n")
+
+
+def _diameter(points: np.ndarray) -> float:
+    from scipy.spatial import ConvexHull
+    p = np.asarray(points, np.float64)
+    if len(p) >= 4:
+        try:
+            p = p[ConvexHull(p).vertices]
+        except Exception:          # flat or degenerate point set: every point is a candidate
+            pass
+    best = 0.0
+    for a in range(0, len(p), 1024):
+        d2 = ((p[a:a + 1024, None, :] - p[None, :, :]) ** 2).sum(axis=-1)
+        best = max(best, float(d2.max()))
+    return math.sqrt(best)
+
+
+def models_info(mesh: Mesh) -> dict:
+    """The BOP models_info.json fields of ``mesh`` (in its units): diameter (largest distance between two vertices of
+    the convex hull), min_x/y/z and size_x/y/z of the bounding box."""
+    v = mesh.vertices.astype(np.float64)
+    lo, hi = v.min(axis=0), v.max(axis=0)
+    info = {"diameter": _diameter(v)}
+    for a, name in enumerate("xyz"):
+        info[f"min_{name}"] = float(lo[a])
+    for a, name in enumerate("xyz"):
+        info[f"size_{name}"] = float(hi[a] - lo[a])
+    return info
+
+
+# ---- CLI ------------------------------------------------------------------------------------------------------------
+def load_model(model_dir, iteration: int = -1):
+    """The GaussianModel saved under <model_dir>/point_cloud/iteration_N/point_cloud.ply (N = the largest for -1)."""
+    from .gaussian_model import GaussianModel
+    from .ply_io import read_ply_vertices
+    from .scene import searchForMaxIteration
+    pc = os.path.join(model_dir, "point_cloud")
+    it = searchForMaxIteration(pc) if iteration == -1 else iteration
+    path = os.path.join(pc, f"iteration_{it}", "point_cloud.ply")
+    n_rest = sum(1 for n in read_ply_vertices(path).dtype.names if n.startswith("f_rest_"))
+    degree = int(round(math.sqrt((n_rest + 3) / 3))) - 1
+    g = GaussianModel(degree)
+    g.load_ply(path)
+    return g
+
+
+def _parser():
+    p = argparse.ArgumentParser(prog="python -m pegasus_amd.mesh", description=__doc__.split("\n\n")[0])
+    p.add_argument("-m", "--model_path", required=True)
+    p.add_argument("--iteration", type=int, default=-1)
+    p.add_argument("--out", required=True)
+    p.add_argument("--obj_id", type=int, required=True)
+    p.add_argument("--scale", type=float, default=1000.0, help="model units -> BOP units (default: m -> mm)")
+    p.add_argument("--mass", type=float, default=0.1, help="kg, for the URDF")
+    p.add_argument("--resolution", type=int, default=256)
+    p.add_argument("--n_views", type=int, default=96)
+    p.add_argument("--image_size", type=int, default=512)
+    return p
+
+
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    a = _parser().parse_args(argv)
+    mesh = extract_mesh(load_model(a.model_path, a.iteration), resolution=a.resolution, n_views=a.n_views,
+                        image_size=a.image_size)
+    name = f"obj_{a.obj_id:06d}"
+    out = Path(a.out)
+    write_ply(out / "models" / f"{name}.ply", mesh, scale=a.scale)
+    info_path = out / "models" / "models_info.json"
+    info = json.loads(info_path.read_text()) if info_path.exists() else {}
+    info[str(a.obj_id)] = models_info(mesh.scaled(a.scale))
+    info_path.write_text(json.dumps(dict(sorted(info.items(), key=lambda kv: int(kv[0]))), indent=2) + "\n")
+    write_obj(out / "urdf" / f"{name}.obj", mesh)
+    write_urdf(out / "urdf" / f"{name}.urdf", f"{name}.obj", mesh, a.mass)
+    print(f"{name}: {len(mesh.vertices)} vertices, {len(mesh.faces)} faces, volume {mesh.volume():.6g}, "
+          f"written under {out}")
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

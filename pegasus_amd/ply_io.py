@@ -65,3 +65,35 @@ def write_ply_vertices(path, columns: dict):
     with open(path, "wb") as f:
         f.write(header.encode("ascii"))
         f.write(arr.tobytes())
+
+
+def write_ply_mesh(path, vertices, faces):
+    """Binary little-endian PLY of a triangle mesh: vertex (float x, y, z) and face (list uchar int vertex_indices)."""
+    v = np.ascontiguousarray(vertices, dtype="<f4").reshape(-1, 3)
+    f = np.ascontiguousarray(faces, dtype="<i4").reshape(-1, 3)
+    rows = np.empty(len(f), dtype=np.dtype([("n", "u1"), ("idx", "<i4", (3,))]))
+    rows["n"] = 3
+    rows["idx"] = f
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\n"
+              "property float z\nelement face %d\nproperty list uchar int vertex_indices\nend_header\n" % (len(v), len(f)))
+    Path(path).parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        fh.write(v.tobytes())
+        fh.write(rows.tobytes())
+
+
+def read_ply_mesh(path):
+    """(vertices float32 [V,3], faces int32 [F,3]) of a binary PLY written by write_ply_mesh."""
+    data = Path(path).read_bytes()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    header = data[:end].decode("ascii").split("\n")
+    counts = {l.split()[1]: int(l.split()[2]) for l in header if l.startswith("element ")}
+    if "format binary_little_endian 1.0" not in header or "property list uchar int vertex_indices" not in header:
+        raise ValueError("not a binary triangle-mesh PLY of write_ply_mesh's layout")
+    nv, nf = counts["vertex"], counts.get("face", 0)
+    v = np.frombuffer(data, dtype="<f4", count=3 * nv, offset=end).reshape(nv, 3)
+    rows = np.frombuffer(data, dtype=np.dtype([("n", "u1"), ("idx", "<i4", (3,))]), count=nf, offset=end + 12 * nv)
+    if nf and not (rows["n"] == 3).all():
+        raise ValueError("faces must be triangles")
+    return v.astype(np.float32), rows["idx"].astype(np.int32)
