@@ -262,6 +262,18 @@ def lib():
     return _lib
 
 
+def ptr(t):
+    """A tensor's address as the pointer argument the ABI takes; None (NULL) for None."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream_ptr(device) -> C.c_void_p:
+    """torch's CURRENT stream on ``device`` as the stream argument the ABI takes.  Ask at every call, never keep the answer:
+    callers switch streams between calls."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
 def check(status: int, what: str = "pegasus_raster"):
     if status == PGR_OK:
         return

@@ -64,11 +64,10 @@ def compose_object(xyz, rot, f_rest, pose: _lib.PgrObjectPose, out_xyz, out_rot,
     in_stride = 3 * n_rest
     if out_rest_stride is None:
         out_rest_stride = in_stride
-    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    p = _lib.ptr
     with torch.cuda.device(xyz.device):
         _lib.check(L.pgr_compose_object(n, p(xyz), p(rot), p(f_rest), n_rest, in_stride, C.byref(pose), p(out_xyz),
-                                        p(out_rot), p(out_rest), int(out_rest_stride),
-                                        C.c_void_p(torch.cuda.current_stream(xyz.device).cuda_stream)),
+                                        p(out_rot), p(out_rest), int(out_rest_stride), _lib.stream_ptr(xyz.device)),
                    "pgr_compose_object")
 
 

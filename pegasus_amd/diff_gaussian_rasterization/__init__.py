@@ -32,7 +32,8 @@ import torch
 from torch import nn
 
 from .. import _lib, rasterizer
-from ..rasterizer import _ptr, _until_fits, camera_structs, dev_f32 as _dev_f32, scene_struct
+from .._lib import ptr, stream_ptr
+from ..rasterizer import _until_fits, camera_structs, dev_f32 as _dev_f32, scene_struct
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "rasterize_gaussians_batch",
            "last_forward_info", "alpha_from_final_T"]
@@ -151,16 +152,16 @@ class _RasterizeGaussians(torch.autograd.Function):
         final_T = torch.empty(lead + (H, W), dtype=torch.float32, device=device)
         n_contrib = torch.empty(lead + (H, W), dtype=torch.int32, device=device)
         outs = (_lib.PgrOutputs * V)(*[
-            _lib.PgrOutputs(color=_ptr(c), depth=_ptr(d), radii=_ptr(r), final_T=_ptr(ft), n_contrib=_ptr(nc))
+            _lib.PgrOutputs(color=ptr(c), depth=ptr(d), radii=ptr(r), final_T=ptr(ft), n_contrib=ptr(nc))
             for c, d, r, ft, nc in zip(*map(per_view, (color, depth, radii, final_T, n_contrib)))])
-        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        stream = stream_ptr(device)
         need = (C.c_int64 * V)()
         ws = None
 
         def run(capacity):
             nonlocal ws
             ws = torch.empty(L.pgr_batch_workspace_bytes(n, W, H, capacity, V), dtype=torch.uint8, device=device)
-            args = (cams, outs, C.c_void_p(ws.data_ptr()), ws.numel(), capacity, need, stream)
+            args = (cams, outs, ptr(ws), ws.numel(), capacity, need, stream)
             return (L.pgr_forward(C.byref(scene), *args) if single else L.pgr_forward_batch(C.byref(scene), V, *args)), need
         with torch.cuda.device(device):
             status, _, max_inst = _until_fits(run, max(1 << 18, 4 * n), 1.25)
@@ -203,55 +204,40 @@ class _RasterizeGaussians(torch.autograd.Function):
             g["cov3d"] = z(n, 6)
         else:
             g["scales"], g["rotations"] = z(n, 3), z(n, 4)
-        grads = _lib.PgrGradOutputs(**{key: _ptr(v) for key, v in g.items()})
+        grads = _lib.PgrGradOutputs(**{key: ptr(v) for key, v in g.items()})
         scene = scene_struct(n, sh_degree=ctx.sh_degree, scale_modifier=ctx.scale_modifier, **t)
         cams = (_lib.PgrCamera * V)(*[_lib.PgrCamera(image_width=W, image_height=H) for _ in range(V)])
         gc = (torch.zeros(lead + (3, H, W), dtype=torch.float32, device=device) if grad_color is None
               else grad_color.contiguous().float())
         gd = None if grad_depth is None else grad_depth.contiguous().float()
         ga = None if grad_alpha is None else grad_alpha.contiguous().float()
-        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
         # camera gradients: [V, 35] written by the camera kernels (only the wanted ones get a pointer)
         want_cam = [m is not None and ctx.needs_input_grad[11 + j] for j, m in enumerate(ctx.cam_meta)]
-        cam_g = cam_structs = cam_scratch = None
+        sl = ((0, 16), (16, 32), (32, 35))
+        cam_g, cam_args = None, ()
         if any(want_cam):
             cam_g = torch.empty((V, 35), dtype=torch.float32, device=device)
-            sl = ((0, 16), (16, 32), (32, 35))
             cam_structs = (_lib.PgrCameraGrad * V)(*[_lib.PgrCameraGrad(*[
-                _ptr(cam_g[v, a:b]) if want_cam[3 * v + c] else None for c, (a, b) in enumerate(sl)]) for v in range(V)])
+                ptr(cam_g[v, a:b]) if want_cam[3 * v + c] else None for c, (a, b) in enumerate(sl)]) for v in range(V)])
             cam_scratch = torch.empty(L.pgr_camera_grad_scratch_bytes(n, V), dtype=torch.uint8, device=device)
+            cam_args = (cam_structs, ptr(cam_scratch), cam_scratch.numel())
+        # one call per mode; the camera entries take the scene-only entries' arguments, then cam_args, then the stream
+        shared = (ptr(ws), ws.numel(), ctx.max_inst, C.byref(grads))
         with torch.cuda.device(device):
-            if single and cam_g is not None:
+            if single:
+                entry = "pgr_backward_camera" if cam_args else "pgr_backward_ex"
                 rows = torch.empty((n, 12), dtype=torch.float32, device=device)
-                _lib.check(L.pgr_backward_camera(C.byref(scene), cams, _ptr(gc), _ptr(gd), _ptr(ga), _ptr(final_T),
-                                                 _ptr(n_contrib), _ptr(radii), C.c_void_p(ws.data_ptr()), ws.numel(),
-                                                 ctx.max_inst, C.byref(grads), _ptr(rows), cam_structs,
-                                                 C.c_void_p(cam_scratch.data_ptr()), cam_scratch.numel(), stream),
-                           "pgr_backward_camera")
-            elif single:
-                rows = torch.empty((n, 12), dtype=torch.float32, device=device)
-                _lib.check(L.pgr_backward_ex(C.byref(scene), cams, _ptr(gc), _ptr(gd), _ptr(ga), _ptr(final_T),
-                                             _ptr(n_contrib), _ptr(radii), C.c_void_p(ws.data_ptr()), ws.numel(),
-                                             ctx.max_inst, C.byref(grads), _ptr(rows), stream), "pgr_backward_ex")
+                args = (cams, ptr(gc), ptr(gd), ptr(ga), ptr(final_T), ptr(n_contrib), ptr(radii), *shared, ptr(rows))
             else:
+                entry = "pgr_backward_batch_camera" if cam_args else "pgr_backward_batch_ex"
                 alpha_ptrs = None if ga is None else (C.c_void_p * V)(*[ga[v].data_ptr() for v in range(V)])
                 views = (_lib.PgrBackwardView * V)(*[
-                    _lib.PgrBackwardView(grad_color=_ptr(gc[v]), grad_depth=None if gd is None else _ptr(gd[v]),
-                                         final_T=_ptr(final_T[v]), n_contrib=_ptr(n_contrib[v]), radii=_ptr(radii[v]))
+                    _lib.PgrBackwardView(grad_color=ptr(gc[v]), grad_depth=None if gd is None else ptr(gd[v]),
+                                         final_T=ptr(final_T[v]), n_contrib=ptr(n_contrib[v]), radii=ptr(radii[v]))
                     for v in range(V)])
                 scratch = torch.empty(max(1, L.pgr_backward_batch_scratch_bytes(n, V)), dtype=torch.uint8, device=device)
-                if cam_g is not None:
-                    _lib.check(L.pgr_backward_batch_camera(C.byref(scene), V, cams, views, alpha_ptrs,
-                                                           C.c_void_p(ws.data_ptr()), ws.numel(), ctx.max_inst,
-                                                           C.byref(grads), C.c_void_p(scratch.data_ptr()), scratch.numel(),
-                                                           cam_structs, C.c_void_p(cam_scratch.data_ptr()),
-                                                           cam_scratch.numel(), stream), "pgr_backward_batch_camera")
-                else:
-                        _lib.check(L.pgr_backward_batch_ex(C.byref(scene), V, cams, views, alpha_ptrs,
-                                                       C.c_void_p(ws.data_ptr()), ws.numel(), ctx.max_inst, C.byref(grads),
-                                                       C.c_void_p(scratch.data_ptr()), scratch.numel(), stream),
-                               "pgr_backward_batch_ex")
-        sl = ((0, 16), (16, 32), (32, 35))
+                args = (V, cams, views, alpha_ptrs, *shared, ptr(scratch), scratch.numel())
+            _lib.check(getattr(L, entry)(C.byref(scene), *args, *cam_args, stream_ptr(device)), entry)
         cam_out = tuple(cam_g[j // 3, sl[j % 3][0]:sl[j % 3][1]].reshape(m[0]).to(m[1]) if want_cam[j] else None
                         for j, m in enumerate(ctx.cam_meta))
         # means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, single, return_alpha,
@@ -307,8 +293,7 @@ class GaussianRasterizer(nn.Module):
             if n:
                 view = _dev_f32(self.raster_settings.viewmatrix, device)
                 with torch.cuda.device(device):
-                    _lib.check(L.pgr_mark_visible(n, _ptr(pos), _ptr(view), _ptr(present),
-                                                  C.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
+                    _lib.check(L.pgr_mark_visible(n, ptr(pos), ptr(view), ptr(present), stream_ptr(device)),
                                "pgr_mark_visible")
             return present.bool()
 

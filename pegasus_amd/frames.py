@@ -24,6 +24,43 @@ from . import rasterizer as R
 from .sh_utils import RGB2SH
 
 
+def _cloud(means3d, opacities, scales, rotations, shs, sh_degree, tie_index=None, tie_inv=None) -> dict:
+    """The keywords that name one Gaussian cloud to rasterizer.forward_views."""
+    return dict(means3D=means3d, opacities=opacities, scales=scales, rotations=rotations, shs=shs, sh_degree=sh_degree,
+                tie_index=tie_index, tie_inv=tie_inv)
+
+
+def stream_key(kind: str, slot: int, n_streams=None):
+    """Key of the side stream a call of ``kind`` on ``slot`` is enqueued on; calls with one key queue behind each other,
+    calls with different keys overlap on the GPU."""
+    if kind == "frames":
+        # `slot` selects the workspace (and the caller's frame set); slots share `n_streams` streams round-robin when that
+        # is set: two batches queued behind each other on a stream keep it from draining when one of them completes
+        return kind, slot if not n_streams else slot % int(n_streams)
+    return kind, slot if kind == "silhouette" else 0           # "scene", "sem": one stream each, shared by all slots
+
+
+class PendingFrames:
+    """Handle of a frame batch in flight: ``wait()`` waits for its PendingBatch ``handles`` in order (each re-renders its pass
+    after an instance overflow), then synchronises ``events``, and returns ``frames``.  ``after_redo`` = (handle, step):
+    ``step()`` runs last if that handle was re-rendered.  ``keep`` holds what the enqueued work reads (view specs, pose
+    tensor) for as long as the handle lives; ``event`` (render_frames_async) is behind the whole batch, for a consumer
+    that makes its own stream wait instead of the host."""
+
+    def __init__(self, frames, handles, events=(), keep=None, after_redo=None, event=None):
+        self.frames, self.handles, self.events, self.keep = frames, handles, events, keep
+        self.after_redo, self.event = after_redo, event
+
+    def wait(self):
+        for h in self.handles:
+            h.wait()
+        for ev in self.events:
+            ev.synchronize()
+        if self.after_redo is not None and self.after_redo[0].redone:
+            self.after_redo[1]()
+        return self.frames
+
+
 class FrameRenderer:
     def __init__(self, means3d, opacities, scales, rotations, shs, object_id, sh_degree=3, device="cuda:0",
                  bg=(0.0, 0.0, 0.0), color_mode="bgr", spatial_order=True):
@@ -36,17 +73,16 @@ class FrameRenderer:
         binning and gathering does.  ``self.order[i]`` = caller's index of resident Gaussian i (None: unchanged)."""
         self.device = torch.device(device)
         self.order = None
-        _oid = (object_id.detach().cpu().numpy() if torch.is_tensor(object_id) else np.asarray(object_id)).astype(np.int64)
-        if _oid.size and (np.diff(_oid) < 0).any():
+        host = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        oid = host(object_id).astype(np.int64)
+        if oid.size and (np.diff(oid) < 0).any():
             raise ValueError("object_id must be non-decreasing: environment Gaussians first (0), then object 1, 2, ...")
         if spatial_order and len(means3d) > 1:
             from .scene_order import spatial_order as _spatial_order
-            host = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
-            perm = _spatial_order(host(means3d), host(object_id))
+            perm = _spatial_order(host(means3d), oid)
             pick = lambda a: (a[torch.as_tensor(perm, device=a.device)] if torch.is_tensor(a) else np.asarray(a)[perm])
-            means3d, opacities, scales, rotations, shs, object_id = (
-                pick(a) for a in (means3d, opacities, scales, rotations, shs, object_id))
-            self.order = perm
+            means3d, opacities, scales, rotations, shs = (pick(a) for a in (means3d, opacities, scales, rotations, shs))
+            self.order, oid = perm, oid[perm]
         # the resident copy keeps the CALLER's tie order: exact depth ties are broken by the caller's index, so the
         # frames are bit-identical to rendering the arrays as passed (PgrScene.tie_index)
         self.tie_index = None if self.order is None else torch.from_numpy(self.order.astype(np.int32)).to(self.device)
@@ -54,7 +90,6 @@ class FrameRenderer:
                                                         ).to(self.device, dt).contiguous()
         self.means3d, self.opacities, self.scales, self.rotations, self.shs = (
             t(means3d), t(opacities), t(scales), t(rotations), t(shs))
-        oid = (object_id.detach().cpu().numpy() if torch.is_tensor(object_id) else np.asarray(object_id)).astype(np.int64)
         self.sh_degree = int(sh_degree)
         self.bg = t(np.asarray(bg, np.float32))
         self.n = int(self.means3d.shape[0])
@@ -63,7 +98,32 @@ class FrameRenderer:
         if obj.size and not np.all(np.diff(obj) == 1):
             raise ValueError("object Gaussians must follow the environment Gaussians contiguously")
         self.n_env = int(obj[0]) if obj.size else self.n
-        # semantic-colour cloud of the objects alone (environment masked out, render.py:81-83)
+        self._paint_objects(oid, t, color_mode)
+        # per-scene constants of the batch calls, once (pgr_scene_prepare): the inverse tie permutation, the object ids as bytes
+        self._prep = R.scene_prepare(self.n, self.tie_index, self.semantic if self.K else None)
+        self.tie_inv = self._prep["tie_inv"]
+        self.obj_tie_inv = None
+        if self.K:
+            self.semantic["object_id_u8"] = self._prep["object_id_u8"]
+            # the objects-only cloud (separate semantic pass, silhouettes): its own inverse tie permutation; layer = object id
+            self._sil_layer_id = self.semantic["object_id"][self.n_env:].contiguous()
+            self._sil_prep = R.scene_prepare(self.n - self.n_env, self.obj_tie_index)
+            self.obj_tie_inv = self._sil_prep["tie_inv"]
+        # the two clouds every call renders: the merged scene, and the objects alone in their semantic colours
+        self._scene = _cloud(self.means3d, self.opacities, self.scales, self.rotations, self.shs, self.sh_degree,
+                             self.tie_index, self.tie_inv)
+        self._objects = _cloud(**self.obj, shs=self.sem_shs, sh_degree=0, tie_index=self.obj_tie_index,
+                               tie_inv=self.obj_tie_inv) if self.K else None
+        edges = np.searchsorted(oid, np.arange(1, self.K + 2))      # object k's Gaussians: [edges[k-1], edges[k]) of the scene
+        self._obj_slices = [(int(a), int(b)) for a, b in zip(edges[:-1], edges[1:])]
+        self.serialize_slots = False      # A/B switch for measurements: the slots of render_frames_async run one after the other
+        self.n_streams = None             # render_frames_async: that many side streams for all slots (None: one per slot)
+        self._streams = {}                # stream_key(...) -> side stream
+        self._sil_img = self._sil_d = None        # render_silhouettes_per_object: its passes' image planes
+
+    def _paint_objects(self, oid, t, color_mode):
+        """The semantic colours (``t``: array -> resident tensor) and, with objects, the fused pass's descriptor and the
+        semantic-colour cloud of the objects alone (environment masked out, render.py:81-83)."""
         self.colors_np = M.generate_colors(max(self.K, 1), color_mode)[: self.K]
         self.colors = t(self.colors_np) if self.K else None
         if self.K:
@@ -82,16 +142,6 @@ class FrameRenderer:
                             rotations=self.rotations[s])
             # tie order of the objects-only cloud: the caller's order of the object Gaussians among themselves
             self.obj_tie_index = None if self.tie_index is None else (self.tie_index[s] - self.n_env).contiguous()
-        # per-scene constants of the batch calls, once (pgr_scene_prepare): the inverse tie permutation, the object ids as bytes
-        self._prep = R.scene_prepare(self.n, self.tie_index, self.semantic if self.K else None)
-        self.tie_inv = self._prep["tie_inv"]
-        self.obj_tie_inv = None
-        if self.K:
-            self.semantic["object_id_u8"] = self._prep["object_id_u8"]
-            # the objects-only cloud (separate semantic pass, silhouettes): its own inverse tie permutation; layer = object id
-            self._sil_layer_id = self.semantic["object_id"][self.n_env:].contiguous()
-            self._sil_prep = R.scene_prepare(self.n - self.n_env, self.obj_tie_index)
-            self.obj_tie_inv = self._sil_prep["tie_inv"]
 
     def view_spec(self, view, depth_mode: int = 0) -> R.ViewSpec:
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.device)
@@ -126,15 +176,20 @@ class FrameRenderer:
         return f
 
     @staticmethod
-    def _outs(frames: dict, B: int, fused: bool):
-        """Per-view output dicts of a frame set; a records-only set (alloc_frames(images=False)) names no image."""
-        if "color" not in frames:
-            return [dict(radii=None, **({"sem_color": frames["seg"][i]} if fused and "seg" in frames else {})) for i in range(B)]
-        outs = [dict(color=frames["color"][i], depth=frames["depth"][i], radii=None) for i in range(B)]
-        if fused:
-            for i in range(B):
-                outs[i]["sem_color"], outs[i]["sem_depth"] = frames["seg"][i], frames["seg_depth"][i]
-                outs[i]["sem_masks"] = frames["masks"][i]
+    def _outs(frames: dict, B: int, fused: bool = False, records=None, image=("color", "depth")):
+        """Per-view output dicts of a frame set: planes ``image`` as color and depth, with ``fused`` the semantic image and its
+        masks; a records-only set (alloc_frames(images=False)) names no image.  View i's record goes to row i of ``records``."""
+        if image[0] in frames:
+            outs = [dict(color=frames[image[0]][i], depth=frames[image[1]][i], radii=None) for i in range(B)]
+            more = dict(sem_color=frames["seg"], sem_depth=frames["seg_depth"], sem_masks=frames["masks"]) if fused else {}
+        else:
+            outs = [dict(radii=None) for _ in range(B)]
+            more = dict(sem_color=frames["seg"]) if fused and "seg" in frames else {}
+        if records is not None:
+            more["record"] = records
+        for key, rows in more.items():
+            for i, o in enumerate(outs):
+                o[key] = rows[i]
         return outs
 
     def record_bytes(self, height: int, width: int, masks: bool = True) -> int:
@@ -152,6 +207,20 @@ class FrameRenderer:
             raise ValueError(f"poses must be [{B}, {self.K}, 20]")
         return dict(object_id=self.semantic["object_id"], poses=t)
 
+    def _forward(self, cloud: dict, specs, outs: list, **extras):
+        """Every rasterizer call of this class: ``specs`` views of ``cloud`` (self._scene, self._objects, or one object's slice) into
+        ``outs``; ``extras`` are the call's own keywords (async_slot, semantic, posed, layers, stage_ms)."""
+        return R.forward_views(views=specs, outputs=outs, want_radii=False, **cloud, **extras)
+
+    def _side_stream(self, kind: str, slot: int) -> torch.cuda.Stream:
+        """The side stream of stream_key(kind, slot), created on first use; it waits on the caller's current stream."""
+        key = stream_key(kind, slot, self.n_streams)
+        st = self._streams.get(key)
+        if st is None:
+            st = self._streams[key] = torch.cuda.Stream(self.device)
+        st.wait_stream(torch.cuda.current_stream(self.device))
+        return st
+
     def render_frames_async(self, specs: Sequence[R.ViewSpec], frames: dict, masks: bool = True, slot: int = 0,
                             poses=None, records: torch.Tensor = None):
         """The fast path: ONE batch call renders the scene (color, depth) and -- from the same per-tile lists --
@@ -163,27 +232,14 @@ class FrameRenderer:
         ``records`` (default: frames["records"] if the frame set has them): uint8 [>= B, record bytes] that receives the
         frames' records from the compositor's epilogue -- e.g. a FrameGather send buffer."""
         B = len(specs)
-        dev = self.device
-        cur = torch.cuda.current_stream(dev)
         if records is None:
             records = frames.get("records")
-        if not hasattr(self, "_slot_streams"):
-            self._slot_streams = {}
-        # `slot` selects the workspace (and the caller's frame set); slots share `n_streams` streams round-robin when that
-        # is set: two batches queued behind each other on a stream keep it from draining when one of them completes
-        n_streams = getattr(self, "n_streams", None)
-        skey = slot if not n_streams else slot % int(n_streams)
-        st = self._slot_streams.get(skey)
-        if st is None:
-            st = self._slot_streams[skey] = torch.cuda.Stream(dev)
         fused = masks and self.K > 0
-        outs = self._outs(frames, B, fused)
-        if records is not None:
-            if records.shape[1] < self.record_bytes(int(specs[0].image_height), int(specs[0].image_width), fused) or records.stride(0) % 16:
-                raise ValueError("records: rows of at least record_bytes(H, W, masks) bytes with a 16-byte-aligned stride")
-            for i in range(B):
-                outs[i]["record"] = records[i]
-        st.wait_stream(cur)
+        if records is not None and (records.stride(0) % 16 or records.shape[1] < self.record_bytes(
+                int(specs[0].image_height), int(specs[0].image_width), fused)):
+            raise ValueError("records: rows of at least record_bytes(H, W, masks) bytes with a 16-byte-aligned stride")
+        outs = self._outs(frames, B, fused, records)
+        st = self._side_stream("frames", slot)
         posed = self._posed(poses, B)
         if posed is not None:
             # allocated on the caller's stream, read on the slot stream: tell the caching allocator, so that a caller who drops
@@ -191,28 +247,17 @@ class FrameRenderer:
             # specs' matrices and every other argument are referenced by the returned handle until wait().)
             posed["poses"].record_stream(st)
         with torch.cuda.stream(st):
-            h = R.forward_views(self.means3d, self.opacities, specs, shs=self.shs, scales=self.scales, tie_index=self.tie_index,
-                                tie_inv=self.tie_inv, rotations=self.rotations, sh_degree=self.sh_degree, want_radii=False,
-                                outputs=outs, async_slot=("frames", slot), semantic=self.semantic if fused else None,
-                                posed=posed)
+            h = self._forward(self._scene, specs, outs, async_slot=("frames", slot), semantic=self.semantic if fused else None,
+                              posed=posed)
             ev = torch.cuda.Event()
             ev.record(st)
         # The caller's stream does NOT wait here: the two slots' streams then really overlap on the GPU (batch i+1's
         # HBM-bound preprocess / LDS-bound sort beside batch i's VALU-bound compositor).  Consumers are ordered by
         # wait() (host-side event synchronisation) or by making their own stream wait on ``pending.event``.
-        if getattr(self, "serialize_slots", False):      # A/B switch for measurements: round 1's behaviour
-            cur.wait_stream(st)
-        renderer = self
-
-        class _Pending:
-            event = ev
-            _args = (specs, posed)       # keeps the caller's device tensors alive while the batch runs
-
-            def wait(self_inner):
-                h.wait()           # (a batch re-rendered after an instance overflow rewrites its masks as well)
-                ev.synchronize()
-                return frames
-        return _Pending()
+        if self.serialize_slots:      # A/B switch for measurements: round 1's behaviour
+            torch.cuda.current_stream(self.device).wait_stream(st)
+        # (a batch re-rendered after an instance overflow rewrites its masks as well)
+        return PendingFrames(frames, [h], [ev], keep=(specs, posed), event=ev)
 
     def render_batch_async(self, specs: Sequence[R.ViewSpec], frames: dict, masks: bool = True, slot: int = 0):
         """Enqueues the scene pass and the semantic pass of one batch on two side streams (two workspaces) so
@@ -220,60 +265,36 @@ class FrameRenderer:
         handle without synchronising the host.  ``slot`` selects the workspace pair: keep at most one batch in
         flight per slot (two slots + two frame sets = a 2-deep pipeline)."""
         B = len(specs)
-        dev = self.device
-        cur = torch.cuda.current_stream(dev)
-        if not hasattr(self, "_streams"):
-            self._streams = (torch.cuda.Stream(dev), torch.cuda.Stream(dev))
-        s_scene, s_sem = self._streams
-        outs = [dict(color=frames["color"][i], depth=frames["depth"][i], radii=None) for i in range(B)]
-        s_scene.wait_stream(cur)
-        with torch.cuda.stream(s_scene):
-            h1 = R.forward_views(self.means3d, self.opacities, specs, shs=self.shs, scales=self.scales, tie_index=self.tie_index,
-                                 tie_inv=self.tie_inv, rotations=self.rotations, sh_degree=self.sh_degree, want_radii=False,
-                                 outputs=outs, async_slot=("scene", slot))
-        h2 = None
-        if masks and self.K:
-            souts = [dict(color=frames["seg"][i], depth=frames["seg_depth"][i], radii=None) for i in range(B)]
-            s_sem.wait_stream(cur)
-            with torch.cuda.stream(s_sem):
-                h2 = R.forward_views(self.obj["means3d"], self.obj["opacities"], specs, shs=self.sem_shs, tie_index=self.obj_tie_index,
-                                     tie_inv=self.obj_tie_inv, scales=self.obj["scales"], rotations=self.obj["rotations"], sh_degree=0,
-                                     want_radii=False, outputs=souts, async_slot=("sem", slot))
-                M.color_masks(frames["seg"][:B], self.colors, M.MASK_THRESHOLD, out=frames["masks"][:B])
-                ev_masks = torch.cuda.Event()
-                ev_masks.record(s_sem)
-        # no cur.wait_stream here either (see render_frames_async): wait() orders the consumers
-        renderer = self
+        outs = self._outs(frames, B)
+        with torch.cuda.stream(self._side_stream("scene", slot)):
+            h1 = self._forward(self._scene, specs, outs, async_slot=("scene", slot))
+        # no wait of the caller's stream here either (see render_frames_async): wait() orders the consumers
+        if not (masks and self.K):
+            return PendingFrames(frames, [h1])
+        souts = self._outs(frames, B, image=("seg", "seg_depth"))
+        s_sem = self._side_stream("sem", slot)
+        with torch.cuda.stream(s_sem):
+            h2 = self._forward(self._objects, specs, souts, async_slot=("sem", slot))
+            M.color_masks(frames["seg"][:B], self.colors, M.MASK_THRESHOLD, out=frames["masks"][:B])
+            ev_masks = torch.cuda.Event()
+            ev_masks.record(s_sem)
 
-        class _Pending:
-            def wait(self_inner):
-                h1.wait()
-                if h2 is not None:
-                    h2.wait()
-                    ev_masks.synchronize()
-                    if h2.redone:      # semantic pass was re-rendered after an overflow: redo masks
-                        M.color_masks(frames["seg"][:B], renderer.colors, M.MASK_THRESHOLD, out=frames["masks"][:B])
-                        torch.cuda.current_stream(dev).synchronize()
-                return frames
-        return _Pending()
+        def redo_masks():      # semantic pass was re-rendered after an overflow: its masks again, on the caller's stream
+            M.color_masks(frames["seg"][:B], self.colors, M.MASK_THRESHOLD, out=frames["masks"][:B])
+            torch.cuda.current_stream(self.device).synchronize()
+        return PendingFrames(frames, [h1, h2], [ev_masks], after_redo=(h2, redo_masks))
 
     def render_frames(self, specs: Sequence[R.ViewSpec], frames: dict = None, masks: bool = True,
                       stage_ms: list = None, poses=None):
         """Blocking form of render_frames_async on the current stream (fused semantic pass); ``stage_ms``
         receives the HIP-event stage times of the whole batch."""
         B = len(specs)
-        H, W = int(specs[0].image_height), int(specs[0].image_width)
         if frames is None:
-            frames = self.alloc_frames(B, H, W, masks)
+            frames = self.alloc_frames(B, int(specs[0].image_height), int(specs[0].image_width), masks)
         fused = masks and self.K > 0
-        outs = self._outs(frames, B, fused)
-        if "records" in frames:
-            for i in range(B):
-                outs[i]["record"] = frames["records"][i]
-        R.forward_views(self.means3d, self.opacities, specs, shs=self.shs, scales=self.scales, tie_index=self.tie_index,
-                        tie_inv=self.tie_inv, rotations=self.rotations, sh_degree=self.sh_degree, want_radii=False,
-                        outputs=outs, stage_ms=stage_ms, semantic=self.semantic if fused else None,
-                        posed=self._posed(poses, B))
+        outs = self._outs(frames, B, fused, frames.get("records"))
+        self._forward(self._scene, specs, outs, stage_ms=stage_ms, semantic=self.semantic if fused else None,
+                      posed=self._posed(poses, B))
         return frames
 
     def render_silhouettes(self, specs: Sequence[R.ViewSpec], out: torch.Tensor = None, poses=None, slot: int = 0,
@@ -292,28 +313,16 @@ class FrameRenderer:
             out = torch.empty((B, max(self.K, 1), H, W), dtype=torch.uint8, device=self.device)
         if self.K == 0:
             return out[:, :0] if wait else (out[:, :0], None)
-        posed = None
-        if poses is not None:
-            posed = dict(object_id=self._sil_layer_id, poses=self._posed(poses, B)["poses"])
+        posed = None if poses is None else dict(object_id=self._sil_layer_id, poses=self._posed(poses, B)["poses"])
         layers = dict(layer_id=self._sil_layer_id, n_layers=self.K, mask_colors=self.colors,
                       mask_threshold=M.MASK_THRESHOLD)
         outs = [dict(radii=None, sem_masks=out[i]) for i in range(B)]
-        dev = self.device
-        cur = torch.cuda.current_stream(dev)
-        if not hasattr(self, "_sil_streams"):
-            self._sil_streams = {}
-        st = self._sil_streams.get(slot)
-        if st is None:
-            st = self._sil_streams[slot] = torch.cuda.Stream(dev)
-        st.wait_stream(cur)
+        st = self._side_stream("silhouette", slot)
         out.record_stream(st)                  # written on the slot's stream: the allocator must not recycle it under the pass
         if posed is not None:
             posed["poses"].record_stream(st)
         with torch.cuda.stream(st):
-            h = R.forward_views(self.obj["means3d"], self.obj["opacities"], specs, shs=self.sem_shs, scales=self.obj["scales"],
-                                rotations=self.obj["rotations"], sh_degree=0, want_radii=False, posed=posed,
-                                tie_index=self.obj_tie_index, tie_inv=self.obj_tie_inv, outputs=outs,
-                                async_slot=("silhouette", slot), layers=layers)
+            h = self._forward(self._objects, specs, outs, posed=posed, async_slot=("silhouette", slot), layers=layers)
         if not wait:
             return out[:, :self.K], h
         h.wait()
@@ -328,33 +337,30 @@ class FrameRenderer:
             out = torch.empty((B, max(self.K, 1), H, W), dtype=torch.uint8, device=self.device)
         if self.K == 0:
             return out[:, :0]
-        if not hasattr(self, "_obj_slices"):
-            oid = self.semantic["object_id"].cpu().numpy()
-            self._obj_slices = [(int(np.searchsorted(oid, k, "left")), int(np.searchsorted(oid, k, "right")))
-                                for k in range(1, self.K + 1)]
         posed_all = self._posed(poses, B)
-        if getattr(self, "_sil_img", None) is None or self._sil_img[0].shape != (B, 3, H, W):
+        if self._sil_img is None or self._sil_img[0].shape != (B, 3, H, W):
             self._sil_img = [torch.empty((B, 3, H, W), device=self.device) for _ in range(2)]
+            self._sil_d = torch.empty((B, 1, H, W), device=self.device)      # depth of the object passes: not kept
         pending = [None, None]
         for k, (a, b) in enumerate(self._obj_slices):
             if b <= a:
                 out[:, k] = 0
                 continue
-            s = slice(a, b)
             posed = None
             if posed_all is not None:
                 posed = dict(object_id=torch.ones(b - a, dtype=torch.int32, device=self.device),
                              poses=posed_all["poses"][:, k:k + 1].contiguous())
+            # the object's slice of the merged scene as a cloud of its own, in its semantic colour
+            s = slice(a, b)
             tie = None if self.tie_index is None else self._dense_rank(self.tie_index[s])
+            cloud = _cloud(self.means3d[s], self.opacities[s], self.scales[s], self.rotations[s],
+                           self.sem_shs[a - self.n_env:b - self.n_env], 0, tie)
             slot = k % 2
             if pending[slot] is not None:
                 pending[slot].wait()
             img = self._sil_img[slot]
-            outs = [dict(color=img[i], depth=self._sil_depth(B, H, W)[i], radii=None) for i in range(B)]
-            pending[slot] = R.forward_views(self.means3d[s], self.opacities[s], specs,
-                                            shs=self.sem_shs[a - self.n_env:b - self.n_env], scales=self.scales[s],
-                                            rotations=self.rotations[s], sh_degree=0, want_radii=False, posed=posed,
-                                            tie_index=tie, outputs=outs, async_slot=("silhouette1", slot))
+            outs = self._outs(dict(color=img, depth=self._sil_d), B)
+            pending[slot] = self._forward(cloud, specs, outs, posed=posed, async_slot=("silhouette1", slot))
             out[:, k:k + 1] = M.color_masks(img, self.colors[k:k + 1], M.MASK_THRESHOLD)      # (kernel output is contiguous)
         redo = False
         for p in pending:
@@ -364,11 +370,6 @@ class FrameRenderer:
         if redo:            # an instance overflow re-rendered a pass after its masks were taken: start over (sized now)
             return self.render_silhouettes_per_object(specs, out, poses)
         return out[:, :self.K]
-
-    def _sil_depth(self, B, H, W):
-        if getattr(self, "_sil_d", None) is None or self._sil_d.shape != (B, 1, H, W):
-            self._sil_d = torch.empty((B, 1, H, W), device=self.device)      # depth of the object passes: not kept
-        return self._sil_d
 
     @staticmethod
     def _dense_rank(t: torch.Tensor) -> torch.Tensor:
@@ -383,17 +384,10 @@ class FrameRenderer:
         """Renders len(specs) frames into ``frames`` (allocated if None).  Returns the dict of batched
         tensors: color [B,3,H,W], depth [B,1,H,W], and with masks: seg [B,3,H,W], masks [B,K,H,W] uint8."""
         B = len(specs)
-        H, W = int(specs[0].image_height), int(specs[0].image_width)
         if frames is None:
-            frames = self.alloc_frames(B, H, W, masks)
-        outs = [dict(color=frames["color"][i], depth=frames["depth"][i], radii=None) for i in range(B)]
-        R.forward_views(self.means3d, self.opacities, specs, shs=self.shs, scales=self.scales, tie_index=self.tie_index,
-                        tie_inv=self.tie_inv, rotations=self.rotations, sh_degree=self.sh_degree, want_radii=False,
-                        outputs=outs, stage_ms=stage_ms)
+            frames = self.alloc_frames(B, int(specs[0].image_height), int(specs[0].image_width), masks)
+        self._forward(self._scene, specs, self._outs(frames, B), stage_ms=stage_ms)
         if masks and self.K:
-            souts = [dict(color=frames["seg"][i], depth=frames["seg_depth"][i], radii=None) for i in range(B)]
-            R.forward_views(self.obj["means3d"], self.obj["opacities"], specs, shs=self.sem_shs, tie_index=self.obj_tie_index,
-                            tie_inv=self.obj_tie_inv, scales=self.obj["scales"], rotations=self.obj["rotations"], sh_degree=0,
-                            want_radii=False, outputs=souts, stage_ms=sem_stage_ms)
+            self._forward(self._objects, specs, self._outs(frames, B, image=("seg", "seg_depth")), stage_ms=sem_stage_ms)
             M.color_masks(frames["seg"][:B], self.colors, M.MASK_THRESHOLD, out=frames["masks"][:B])
         return frames

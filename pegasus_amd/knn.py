@@ -2,8 +2,6 @@
 /root/reference/src/gs/gaussian_model.py:25,147) on the HIP library's grid search (`pgr_knn_mean_dist2`)."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
@@ -24,10 +22,8 @@ def dist2(points: torch.Tensor) -> torch.Tensor:
         return out
     with torch.cuda.device(pts.device):
         ws = torch.empty((L.pgr_knn_workspace_bytes(n),), dtype=torch.uint8, device=pts.device)
-        _lib.check(L.pgr_knn_mean_dist2(n, C.c_void_p(pts.data_ptr()), C.c_void_p(out.data_ptr()),
-                                        C.c_void_p(ws.data_ptr()), ws.numel(),
-                                        C.c_void_p(torch.cuda.current_stream(pts.device).cuda_stream)),
-                   "pgr_knn_mean_dist2")
+        _lib.check(L.pgr_knn_mean_dist2(n, _lib.ptr(pts), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+                                        _lib.stream_ptr(pts.device)), "pgr_knn_mean_dist2")
     return out
 
 

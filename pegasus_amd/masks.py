@@ -33,10 +33,6 @@ def generate_colors(n: int, mode: str = "bgr") -> np.ndarray:
     return np.asarray(colors, dtype=np.float32).reshape(n, 3)
 
 
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def color_masks(img_chw: torch.Tensor, colors: torch.Tensor, threshold: float = MASK_THRESHOLD,
                 out: torch.Tensor = None) -> torch.Tensor:
     """uint8 [K,H,W] (or [B,K,H,W] for a [B,3,H,W] batch, one launch): 1 where the rendered colour is within
@@ -53,9 +49,8 @@ def color_masks(img_chw: torch.Tensor, colors: torch.Tensor, threshold: float = 
     if out is None:
         out = torch.empty(((nb, K, H, W) if batched else (K, H, W)), dtype=torch.uint8, device=img.device)
     with torch.cuda.device(img.device):
-        _lib.check(L.pgr_color_masks(C.c_void_p(img.data_ptr()), nb, W, H, C.c_void_p(colors.data_ptr()), K,
-                                     float(threshold), C.c_void_p(out.data_ptr()), _stream(img.device)),
-                   "pgr_color_masks")
+        _lib.check(L.pgr_color_masks(_lib.ptr(img), nb, W, H, _lib.ptr(colors), K, float(threshold), _lib.ptr(out),
+                                     _lib.stream_ptr(img.device)), "pgr_color_masks")
     return out
 
 
@@ -70,9 +65,8 @@ def quantize_frame(img_chw: torch.Tensor, depth: torch.Tensor):
     rgb = torch.empty((H, W, 3), dtype=torch.uint8, device=img.device)
     mm = torch.empty((H, W), dtype=torch.int16, device=img.device)   # bit pattern of uint16 millimetres
     with torch.cuda.device(img.device):
-        _lib.check(L.pgr_quantize_frame(C.c_void_p(img.data_ptr()), C.c_void_p(d.data_ptr()), W, H,
-                                        C.c_void_p(rgb.data_ptr()), C.c_void_p(mm.data_ptr()), _stream(img.device)),
-                   "pgr_quantize_frame")
+        _lib.check(L.pgr_quantize_frame(_lib.ptr(img), _lib.ptr(d), W, H, _lib.ptr(rgb), _lib.ptr(mm),
+                                        _lib.stream_ptr(img.device)), "pgr_quantize_frame")
     return rgb, mm
 
 
@@ -87,7 +81,7 @@ def pack_frames(color: torch.Tensor = None, depth: torch.Tensor = None, masks: t
         raise RuntimeError("pack_frames needs HIP device tensors; there is no CPU path")
     dev = ref.device
     B, (H, W) = int(ref.shape[0]), ref.shape[-2:]
-    out, ptr = {}, lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    out, ptr = {}, _lib.ptr
     if color is not None:
         color = color.contiguous().float()
         out["rgb"] = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
@@ -103,7 +97,7 @@ def pack_frames(color: torch.Tensor = None, depth: torch.Tensor = None, masks: t
         out["mask_bits"] = torch.empty((B, H, W, (K + 7) // 8), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         _lib.check(L.pgr_pack_frames(ptr(color), ptr(depth), ptr(masks), B, K, W, H, ptr(out.get("rgb")),
-                                     ptr(out.get("depth_mm")), ptr(out.get("mask_bits")), _stream(dev)),
+                                     ptr(out.get("depth_mm")), ptr(out.get("mask_bits")), _lib.stream_ptr(dev)),
                    "pgr_pack_frames")
     return out
 
@@ -143,10 +137,10 @@ def pack_records(color: torch.Tensor = None, depth: torch.Tensor = None, masks: 
     if out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] < B or out.shape[1] < nbytes or out.stride(1) != 1 \
             or out.stride(0) % 16 or out.device != dev:
         raise ValueError(f"out must be a uint8 [>= {B}, >= {nbytes}] device tensor with a 16-byte-aligned row stride")
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    ptr = _lib.ptr
     with torch.cuda.device(dev):
         _lib.check(L.pgr_pack_records(ptr(color), ptr(depth), ptr(masks), B, K, W, H, ptr(out), int(out.stride(0)),
-                                      _stream(dev)), "pgr_pack_records")
+                                      _lib.stream_ptr(dev)), "pgr_pack_records")
     return out
 
 

@@ -133,10 +133,9 @@ def integrate(depth, final_T, views, grid: Grid, truncation: float, alpha_min: f
     sdf = torch.empty(grid.shape, dtype=torch.float32, device=device)
     g = grid.struct()
     with torch.cuda.device(device):
-        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        _lib.check(_lib.lib().pgr_tsdf_integrate(C.byref(g), V, cams, C.c_void_p(depth.data_ptr()),
-                                                 C.c_void_p(final_T.data_ptr()), float(truncation), float(alpha_min),
-                                                 C.c_void_p(sdf.data_ptr()), stream), "pgr_tsdf_integrate")
+        _lib.check(_lib.lib().pgr_tsdf_integrate(C.byref(g), V, cams, _lib.ptr(depth), _lib.ptr(final_T), float(truncation),
+                                                 float(alpha_min), _lib.ptr(sdf), _lib.stream_ptr(device)),
+                   "pgr_tsdf_integrate")
     del keep
     return sdf
 
@@ -159,14 +158,14 @@ def march(sdf, grid: Grid, stage_ms: Optional[dict] = None) -> Mesh:
         raise ValueError(f"grid {grid.shape}: every axis must hold 2..{MAX_AXIS} points")
     with torch.cuda.device(device):
         stream_t = torch.cuda.current_stream(device)
-        stream = C.c_void_p(stream_t.cuda_stream)
+        stream = _lib.stream_ptr(device)
         ws = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
         counts = torch.zeros(2, dtype=torch.int64, device=device)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if stage_ms is not None else None
         if ev:
             ev[0].record(stream_t)
-        _lib.check(L.pgr_march_count(C.byref(g), C.c_void_p(sdf.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
-                                     C.c_void_p(counts.data_ptr()), stream), "pgr_march_count")
+        _lib.check(L.pgr_march_count(C.byref(g), _lib.ptr(sdf), _lib.ptr(ws), ws.numel(), _lib.ptr(counts), stream),
+                   "pgr_march_count")
         if ev:
             ev[1].record(stream_t)
         nv, nf = (int(x) for x in counts.cpu())
@@ -174,9 +173,8 @@ def march(sdf, grid: Grid, stage_ms: Optional[dict] = None) -> Mesh:
             raise ValueError(f"{nv} vertices / {nf} faces: more than int32 indices hold; use a coarser grid")
         vertices = torch.empty((max(nv, 1), 3), dtype=torch.float32, device=device)
         faces = torch.empty((max(nf, 1), 3), dtype=torch.int32, device=device)
-        _lib.check(L.pgr_march_emit(C.byref(g), C.c_void_p(sdf.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
-                                    C.c_void_p(vertices.data_ptr()), C.c_void_p(faces.data_ptr()), stream),
-                   "pgr_march_emit")
+        _lib.check(L.pgr_march_emit(C.byref(g), _lib.ptr(sdf), _lib.ptr(ws), ws.numel(), _lib.ptr(vertices),
+                                    _lib.ptr(faces), stream), "pgr_march_emit")
         if ev:
             ev[2].record(stream_t)
         out = Mesh(vertices[:nv].cpu().numpy(), faces[:nf].cpu().numpy())

@@ -15,7 +15,6 @@ read or written in between flushes first), results replace the attribute with a 
 methods do, and autograd-tracked or host-resident models never defer."""
 from __future__ import annotations
 
-import ctypes as C
 import weakref
 
 import numpy as np
@@ -131,9 +130,8 @@ def flush_all():
             dirs, pinv = _sh_tables(dev)
             arr_t = (_lib.PgrPoseJob * len(sel))(*[jobs[i] for i in sel])
             with torch.cuda.device(dev):
-                _lib.check(L.pgr_pose_objects(len(sel), arr_t, C.c_void_p(dirs.data_ptr()), C.c_void_p(pinv.data_ptr()),
-                                              C.c_void_p(ws.data_ptr()), int(ws.numel()),
-                                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "pgr_pose_objects")
+                _lib.check(L.pgr_pose_objects(len(sel), arr_t, _lib.ptr(dirs), _lib.ptr(pinv), _lib.ptr(ws), int(ws.numel()),
+                                              _lib.stream_ptr(dev)), "pgr_pose_objects")
         for m, arr, dst in outs:
             m.__dict__[arr] = dst
         # (`keep` dies here: the caching allocator hands the sources' blocks out again in stream order, behind the launches)

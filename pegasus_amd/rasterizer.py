@@ -135,8 +135,7 @@ def dev_f32(t: Optional[torch.Tensor], device) -> Optional[torch.Tensor]:
     return t.contiguous()
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
+_ptr = _lib.ptr
 
 
 def scene_struct(n: int, means3D=None, opacities=None, *, shs=None, shs_rest=None, colors_precomp=None, scales=None,
@@ -192,7 +191,7 @@ def _learn(key, capacity: int, peak: Optional[int] = None) -> int:
 def _batch_status(scratch: torch.Tensor, nv: int):
     """(status, per-view instance counts) of the asynchronous call whose pinned host scratch is ``scratch``."""
     need = (C.c_int64 * nv)()
-    status = _lib.lib().pgr_batch_status(C.c_void_p(scratch.data_ptr()), nv, need)
+    status = _lib.lib().pgr_batch_status(_ptr(scratch), nv, need)
     return status, [int(x) for x in need]
 
 
@@ -216,11 +215,6 @@ class PendingBatch:
         self._event, self._scratch, self._workspace = event, scratch, workspace
         self._key, self._capacity, self._redo, self._keep = key, capacity, redo, keep
         self._record_info = record_info      # wait() fills last_forward_info() like a synchronous call (single-view drop-in)
-
-    @property
-    def _was_redone(self) -> bool:
-        """The earlier name of ``redone``, still read by code written against it."""
-        return self.redone
 
     def wait(self):
         if self._event is None:
@@ -369,12 +363,11 @@ def forward_views(means3D, opacities, views: Sequence[ViewSpec], *, shs=None, co
     def enqueue(slot, capacity, early=False):
         """One asynchronous attempt on ``slot``'s workspace and pinned scratch: (scratch, event behind the status words)."""
         nonlocal ws
-        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        stream = _lib.stream_ptr(device)
         with torch.cuda.device(device):
             ws = workspace(("async", slot), capacity)
             scratch = _WS.pinned(slot, L.pgr_host_scratch_bytes(nv))
-            args = (nv, cams, outs, C.c_void_p(ws.data_ptr()), ws.numel(), capacity, C.c_void_p(scratch.data_ptr()),
-                    scratch.numel(), stream)
+            args = (nv, cams, outs, _ptr(ws), ws.numel(), capacity, _ptr(scratch), scratch.numel(), stream)
             if layers is not None:
                 _lib.check(L.pgr_forward_layers_async(scene, layers_ref, posed_ref, *args), "pgr_forward_layers_async")
             elif early:
@@ -405,17 +398,16 @@ def forward_views(means3D, opacities, views: Sequence[ViewSpec], *, shs=None, co
         """One synchronous attempt on the pooled workspace: (status, per-view instance counts)."""
         nonlocal ws
         need = (C.c_int64 * nv)()
-        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        stream = _lib.stream_ptr(device)
         with torch.cuda.device(device):
             ws = workspace(0, capacity)
             if stage_ms is not None:
                 ms = (C.c_float * _lib.PGR_NUM_STAGES)()
-                status = L.pgr_forward_batch_profiled(scene, sem, nv, cams, outs, C.c_void_p(ws.data_ptr()), ws.numel(),
-                                                      capacity, need, stream, ms)
+                status = L.pgr_forward_batch_profiled(scene, sem, nv, cams, outs, _ptr(ws), ws.numel(), capacity, need,
+                                                      stream, ms)
                 stage_ms[:] = list(ms)
             else:
-                status = L.pgr_forward_batch(scene, nv, cams, outs, C.c_void_p(ws.data_ptr()), ws.numel(), capacity,
-                                             need, stream)
+                status = L.pgr_forward_batch(scene, nv, cams, outs, _ptr(ws), ws.numel(), capacity, need, stream)
         return status, need
 
     def render_sync():
@@ -446,7 +438,7 @@ def workspace_view(view_index: int = 0) -> dict:
     info = _LAST_INFO
     ws = info["workspace"]
     v = _lib.PgrWorkspaceView()
-    _lib.check(L.pgr_workspace_view(C.c_void_p(ws.data_ptr()), ws.numel(), info["n"], info["width"], info["height"],
+    _lib.check(L.pgr_workspace_view(_ptr(ws), ws.numel(), info["n"], info["width"], info["height"],
                                     info["used_max_instances"], info["n_views"], view_index, C.byref(v)),
                "pgr_workspace_view")
     return {k: getattr(v, k) for k, _ in _lib.PgrWorkspaceView._fields_}
@@ -470,9 +462,8 @@ def block_visibility(means3D, views: Sequence[ViewSpec], *, scales=None, rotatio
     out = torch.zeros((groups, words), dtype=torch.int32, device=device)
     with torch.cuda.device(device):
         ws = torch.empty(L.pgr_block_visibility_workspace_bytes(n, nv) + 256, dtype=torch.uint8, device=device)
-        _lib.check(L.pgr_block_visibility(C.byref(scene), nv, cams, C.c_void_p(ws.data_ptr()), ws.numel(),
-                                          C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
-                   "pgr_block_visibility")
+        _lib.check(L.pgr_block_visibility(C.byref(scene), nv, cams, _ptr(ws), ws.numel(), _ptr(out),
+                                          _lib.stream_ptr(device)), "pgr_block_visibility")
         torch.cuda.current_stream(device).synchronize()
     bits = (out.unsqueeze(2) >> torch.arange(32, device=device, dtype=torch.int32)) & 1
     return bits.reshape(groups, words * 32)[:, :nv].bool()
@@ -497,9 +488,9 @@ def scene_prepare(n: int, tie_index: Optional[torch.Tensor] = None, semantic: Op
     with torch.cuda.device(device):
         cache = torch.empty(int(L.pgr_scene_cache_bytes(int(n))) + 256, dtype=torch.uint8, device=device)
         p_inv, p_u8 = C.c_void_p(), C.c_void_p()
-        _lib.check(L.pgr_scene_prepare(C.byref(scene), C.byref(sem) if sem is not None else None,
-                                       C.c_void_p(cache.data_ptr()), cache.numel(), C.byref(p_inv), C.byref(p_u8),
-                                       C.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "pgr_scene_prepare")
+        _lib.check(L.pgr_scene_prepare(C.byref(scene), C.byref(sem) if sem is not None else None, _ptr(cache),
+                                       cache.numel(), C.byref(p_inv), C.byref(p_u8), _lib.stream_ptr(device)),
+                   "pgr_scene_prepare")
 
     def view(ptr, nbytes, dtype):
         if not ptr.value:

@@ -12,18 +12,12 @@
 Everything is enqueued on torch's current stream; memory comes from torch's caching allocator.  There is no CPU path."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
 
 __all__ = ["ImageLoss", "image_loss", "image_loss_terms", "MaskedImageLoss", "masked_image_loss", "masked_image_loss_terms",
            "l1_loss", "ssim", "FusedAdam", "densify_stats"]
-
-
-def _stream(device) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def _image(t: torch.Tensor, what: str) -> torch.Tensor:
@@ -45,9 +39,8 @@ def image_loss_terms(x: torch.Tensor, y: torch.Tensor, lambda_dssim: float, want
     grad = torch.empty_like(xc) if want_grad else None
     ws = torch.empty(L.pgr_image_loss_workspace_bytes(H, W), dtype=torch.uint8, device=xc.device)
     with torch.cuda.device(xc.device):
-        _lib.check(L.pgr_image_loss(C.c_void_p(xc.data_ptr()), C.c_void_p(yc.data_ptr()), H, W, float(lambda_dssim),
-                                    C.c_void_p(out.data_ptr()), None if grad is None else C.c_void_p(grad.data_ptr()),
-                                    C.c_void_p(ws.data_ptr()), ws.numel(), _stream(xc.device)), "pgr_image_loss")
+        _lib.check(L.pgr_image_loss(_lib.ptr(xc), _lib.ptr(yc), H, W, float(lambda_dssim), _lib.ptr(out), _lib.ptr(grad),
+                                    _lib.ptr(ws), ws.numel(), _lib.stream_ptr(xc.device)), "pgr_image_loss")
     return out, grad
 
 
@@ -106,10 +99,10 @@ def masked_image_loss_terms(x, alpha, y, mask, bg, lambda_dssim: float, lambda_a
     grad = torch.empty_like(xc) if want_grad else None
     grad_a = torch.empty((1, H, W), dtype=torch.float32, device=dev) if (want_grad_alpha and ac is not None) else None
     ws = torch.empty(L.pgr_image_loss_masked_workspace_bytes(H, W), dtype=torch.uint8, device=dev)
-    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    p = _lib.ptr
     with torch.cuda.device(dev):
         _lib.check(L.pgr_image_loss_masked(p(xc), p(yc), p(mc), p(bc), p(ac), H, W, float(lambda_dssim), float(lambda_alpha),
-                                           p(out), p(grad), p(grad_a), p(ws), ws.numel(), _stream(dev)),
+                                           p(out), p(grad), p(grad_a), p(ws), ws.numel(), _lib.stream_ptr(dev)),
                    "pgr_image_loss_masked")
     return out, grad, grad_a
 
@@ -213,7 +206,7 @@ class FusedAdam(torch.optim.Optimizer):
                 chunk = entries[k:k + _lib.PGR_ADAM_MAX_GROUPS]
                 table = (_lib.PgrAdamGroup * len(chunk))(*(e for e, _ in chunk))
                 with torch.cuda.device(device):
-                    _lib.check(L.pgr_adam_step(table, len(chunk), b1, b2, eps, _stream(device)), "pgr_adam_step")
+                    _lib.check(L.pgr_adam_step(table, len(chunk), b1, b2, eps, _lib.stream_ptr(device)), "pgr_adam_step")
         if written:
             torch.autograd.graph.increment_version(written)
         return loss
@@ -234,10 +227,9 @@ def densify_stats(viewspace_grad: torch.Tensor, radii: torch.Tensor, grad_accum:
                          "with N fp32 elements, all contiguous on one HIP device")
     L = _lib.lib()
     with torch.cuda.device(radii.device):
-        _lib.check(L.pgr_densify_stats(n, C.c_void_p(viewspace_grad.data_ptr()), int(viewspace_grad.shape[1]),
-                                       C.c_void_p(radii.data_ptr()), C.c_void_p(grad_accum.data_ptr()),
-                                       C.c_void_p(denom.data_ptr()), C.c_void_p(max_radii2D.data_ptr()),
-                                       _stream(radii.device)), "pgr_densify_stats")
+        _lib.check(L.pgr_densify_stats(n, _lib.ptr(viewspace_grad), int(viewspace_grad.shape[1]), _lib.ptr(radii),
+                                       _lib.ptr(grad_accum), _lib.ptr(denom), _lib.ptr(max_radii2D),
+                                       _lib.stream_ptr(radii.device)), "pgr_densify_stats")
     torch.autograd.graph.increment_version([grad_accum, denom, max_radii2D])
 
 

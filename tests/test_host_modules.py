@@ -465,3 +465,86 @@ def test_learned_capacity_only_grows_and_keeps_headroom():
             R._learn(key, R.MAX_INSTANCES, peak=R.MAX_INSTANCES + 1)
     finally:
         R.set_capacity_hint(key, None)
+
+
+def test_side_stream_key_rule():
+    """frames.stream_key decides which batches share a side stream, i.e. which queue behind each other on the GPU: frame
+    batches one stream per slot, or n_streams streams round-robin; the scene and semantic passes of render_batch_async one
+    stream each whatever the slot; silhouette passes one per slot."""
+    from pegasus_amd.frames import stream_key
+    for n_streams in (None, 1, 2, 3):
+        for slot in range(6):
+            assert stream_key("frames", slot, n_streams) == ("frames", slot if not n_streams else slot % int(n_streams))
+            assert stream_key("scene", slot, n_streams) == ("scene", 0)
+            assert stream_key("sem", slot, n_streams) == ("sem", 0)
+            assert stream_key("silhouette", slot, n_streams) == ("silhouette", slot)
+    keys = {stream_key(kind, slot, 2) for kind in ("frames", "scene", "sem", "silhouette") for slot in range(6)}
+    assert len(keys) == 2 + 1 + 1 + 6          # no two kinds share a stream
+
+
+def test_pending_frames_waits_in_order_and_redoes_only_its_own_pass():
+    """frames.PendingFrames with fake handles and events: handles in order, then events, then the after-redo step exactly
+    when the handle it belongs to was re-rendered; wait() returns the frame dict, and the keep-alive references live until
+    it has returned."""
+    import gc
+    import weakref
+    from pegasus_amd.frames import PendingFrames
+
+    class Kept:
+        pass
+
+    def run(redone_scene, redone_sem, with_step=True):
+        log, kept = [], Kept()
+        alive = weakref.ref(kept)
+
+        class Handle:
+            def __init__(self, name, redone):
+                self.name, self.redone_after_wait, self.redone = name, redone, False
+
+            def wait(self):
+                assert alive() is not None
+                log.append(self.name)
+                self.redone = self.redone_after_wait
+
+        class Event:
+            def __init__(self, name):
+                self.name = name
+
+            def synchronize(self):
+                assert alive() is not None
+                log.append(self.name)
+
+        frames = {"color": object()}
+        scene, sem = Handle("scene", redone_scene), Handle("sem", redone_sem)
+        events = [Event("ev0"), Event("ev1")]
+        pending = PendingFrames(frames, [scene, sem], events, keep=(kept,),
+                                after_redo=(sem, lambda: log.append("step")) if with_step else None, event=events[0])
+        del kept
+        gc.collect()
+        assert alive() is not None and pending.event is events[0]
+        assert pending.wait() is frames
+        del pending
+        gc.collect()
+        assert alive() is None
+        return log
+
+    order = ["scene", "sem", "ev0", "ev1"]
+    assert run(False, False) == order
+    assert run(True, False) == order                    # a redone scene pass does not redo the masks
+    assert run(False, True) == order + ["step"]
+    assert run(True, True) == order + ["step"]
+    assert run(True, True, with_step=False) == order
+    assert PendingFrames({}, []).wait() == {} and PendingFrames({}, []).event is None
+
+
+def test_abi_pointer_helper():
+    """_lib.ptr: a tensor's address as the c_void_p the ABI takes, NULL for None."""
+    import ctypes as C
+    import torch
+    from pegasus_amd import _lib
+    assert _lib.ptr(None) is None
+    t = torch.arange(12, dtype=torch.float32).reshape(3, 4)
+    p = _lib.ptr(t)
+    assert isinstance(p, C.c_void_p) and p.value == t.data_ptr()
+    assert _lib.ptr(t[1]).value == t.data_ptr() + 16                      # a view: its own first element
+    assert C.cast(_lib.ptr(t[2]), C.POINTER(C.c_float))[1] == 9.0
