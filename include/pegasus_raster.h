@@ -396,7 +396,8 @@ typedef struct PgrGrid {
  *   1 - final_T < alpha_min: carved (sdf = +1); else d = depth - z, skipped when d < -truncation,
  *   else s += min(d, truncation) / truncation, w += 1
  * sdf = carved ? +1 : (w == 0 ? -1 : s / w); the outermost layer of points is +1, so the surface closes.  Positive is
- * outside.  `sdf` is device [nz,ny,nx]. */
+ * outside.  `sdf` is device [nz,ny,nx].  A NaN depth counts like +inf, as an observation at the full truncation (NaN <
+ * -truncation is false and min is fminf); the depth of a carving pixel is never read. */
 int32_t pgr_tsdf_integrate(const PgrGrid *grid, int32_t n_views, const PgrCamera *cameras, const float *depth,
                            const float *final_T, float truncation, float alpha_min, float *sdf, void *stream);
 

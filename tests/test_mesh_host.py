@@ -9,6 +9,7 @@ import xml.etree.ElementTree as ET
 import numpy as np
 import pytest
 
+import mesh_cases as MC
 import mesh_reference as R
 from mesh_reference import assert_watertight, components
 from pegasus_amd import _lib
@@ -183,3 +184,90 @@ def test_largest_component_keeps_the_body():
     assert components(len(body.vertices), body.faces) == 1
     assert body.volume() == pytest.approx(27.0)
     np.testing.assert_array_equal(body.vertices, big.vertices)
+
+
+# ---- the references against each other ------------------------------------------------------------------------------
+MARCH_FIELDS = {
+    "sphere": lambda: sphere_sdf(48, 0.7),
+    "sphere-through-border": MC.off_centre_sphere,
+    "checkerboard-37x35x33": MC.checkerboard,
+    "random-signs-37x35x33": MC.random_signs,
+    "inside-on-border-21x19x17": MC.inside_on_border,
+    "all-inside": lambda: (-np.ones((5, 6, 7), np.float32), MC.unit_grid(7, 6, 5)),
+    "2x2x2": lambda: (np.array([-1, 1, 1, -1, 1, -1, 1, 1], np.float32).reshape(2, 2, 2), MC.unit_grid(2, 2, 2)),
+}
+
+
+@pytest.mark.parametrize("name", list(MARCH_FIELDS))
+def test_sparse_marching_reference_equals_the_dense_one_as_bytes(name):
+    sdf, g = MARCH_FIELDS[name]()
+    v_d, f_d = R.march_reference(sdf, g)
+    v_s, f_s = R.march_reference(sdf, g, sparse=True)
+    assert v_d.dtype == v_s.dtype and f_d.dtype == f_s.dtype and v_d.shape == v_s.shape and f_d.shape == f_s.shape
+    assert v_d.tobytes() == v_s.tobytes() and f_d.tobytes() == f_s.tobytes()
+    assert (len(f_d) == 0) == (name == "all-inside")
+    assert np.isfinite(v_d).all()
+
+
+def test_open_meshes_are_open_on_the_boundary_planes_only():
+    for make in (MC.off_centre_sphere, MC.inside_on_border):
+        sdf, g = make()
+        v, f = R.march_reference(sdf, g, sparse=True)
+        n_open, on_planes = MC.boundary_planes_hold_open_edges(v, f, g)
+        assert n_open > 0 and on_planes
+        assert_watertight(R.march_reference(MC.force_outer_layer(sdf), g, sparse=True)[1])
+
+
+ALL_PAIRS = {(t, c) for t in range(6) for c in range(1, 15)}
+
+
+def test_dense_fields_reach_every_entry_of_the_case_table():
+    """The random-sign field reaches all 6 x 14 (tetrahedron, pattern) pairs that have triangles, with and without the
+    forced outer layer.  The checkerboard reaches 12: in each tetrahedron the two patterns in which the sign alternates
+    along the walk.  The sdf of the first device case (synthetic_case(), through tsdf_reference) reaches 84 of 84 as
+    well: its noisy depth makes a rough surface, so no entry of the table was out of that case's reach, only unasserted."""
+    sdf, _g = MC.random_signs()
+    assert R.table_coverage(sdf) == ALL_PAIRS
+    assert R.table_coverage(MC.force_outer_layer(sdf)) == ALL_PAIRS
+    chk, _g = MC.checkerboard()
+    assert R.table_coverage(chk) == {(t, c) for t in range(6) for c in (5, 10)}
+    case = MC.TSDF_CASES["synthetic-41x33x29-7views"]()
+    assert R.table_coverage(R.tsdf_reference(*case.reference_args())) == ALL_PAIRS
+    # what the hostile field is made of
+    assert (sdf == 0).sum() > 100 and np.signbit(sdf[sdf == 0]).any() and not np.signbit(sdf[sdf == 0]).all()
+    tiny = np.abs(sdf[sdf != 0]) < np.finfo(np.float32).tiny
+    assert tiny.sum() > 100
+
+
+@pytest.mark.parametrize("name", list(MC.TSDF_CASES))
+def test_float64_oracle_agrees_with_the_float32_transcription(name):
+    case = MC.TSDF_CASES[name]()
+    MC.check_against_oracle(case)
+    assert np.isfinite(R.tsdf_reference(*case.reference_args())).all()
+
+
+def test_oracle_tells_a_wrong_convention_from_the_right_one():
+    """What the transcription could share with the kernel unnoticed, the oracle does not share: read the view matrix
+    untransposed, centre the image at W/2, or truncate instead of rounding to the nearest pixel centre, and the
+    agreement is gone."""
+    case = MC.TSDF_CASES["synthetic-41x33x29-7views"]()
+    args = list(case.reference_args())
+    sdf, masked, tol, _census = R.tsdf_oracle(*args)
+
+    def disagreement(want32):
+        return float((~masked & ~(np.abs(want32.astype(np.float64) - sdf) <= tol)).mean())
+    assert disagreement(R.tsdf_reference(*args)) == 0.0
+    transposed = [np.asarray(m).reshape(4, 4).T.reshape(16).copy() for m in args[1]]
+    assert disagreement(R.tsdf_reference(args[0], transposed, *args[2:])) > 0.1
+    shifted = [np.asarray(m, np.float32).copy() for m in args[1]]
+    for m, v in zip(shifted, case.raw):
+        m[12] += np.float32(0.5 * 2.0 * v.tanfovx / case.depth.shape[2]) * m[14]      # half a pixel at z = m[14]: W/2 for (W-1)/2
+    assert disagreement(R.tsdf_reference(args[0], shifted, *args[2:])) > 0.01
+
+
+def test_carve_order_does_not_change_the_carved_set():
+    a, b = MC.TSDF_CASES["carve-after-fusing"](), MC.TSDF_CASES["carve-before-fusing"]()
+    sa, sb = R.tsdf_reference(*a.reference_args()), R.tsdf_reference(*b.reference_args())
+    inside = R.interior(a.grid)
+    np.testing.assert_array_equal((sa == 1.0) & inside, (sb == 1.0) & inside)
+    assert ((sa == 1.0) & inside).mean() > 0.05 and not np.array_equal(sa, sb)
