@@ -342,7 +342,8 @@ int32_t pgr_compose_object(int32_t n, const float *xyz, const float *rot, const 
  *   PGR_POSE_XYZ   dst[i] = R (src[i] - c) + c + t,  c = the mean of src (about_origin = 0) or 0      src, dst [n,3]
  *   PGR_POSE_ROT   dst[i] = quat(R) (x) normalise(src[i])                              (w,x,y,z)       src, dst [n,4]
  *   PGR_POSE_SH    dst[i] = band-wise D_l(R) src[i],  D_l = pinv(B_l) B_l(R^T d_k)                     src, dst [n,n_rest,3]
- * R = NULL: identity; t = NULL: zero.  R and t may point INTO a 4x4 transform (strides below): PEGASUS builds T on the device and
+ * R = NULL: identity (PGR_POSE_XYZ then writes src + t in float32, a bit-for-bit copy without t; an identity MATRIX handed over as
+ * R is multiplied like any other: 0 * Inf is NaN there, here and in pgr_compose_object); t = NULL: zero.  R and t may point INTO a 4x4 transform (strides below): PEGASUS builds T on the device and
  * hands its corner and last column over.  src == dst is allowed.  Jobs of one call must not depend on each other.
  * sh_dirs [61,3] / sh_pinv [15,61]: device fp64 tables of the SH sample directions and the three bands' pseudo-inverses
  * (pegasus_amd/sh_rotation.py builds them for the rasterizer's basis; needed only if a job is PGR_POSE_SH).

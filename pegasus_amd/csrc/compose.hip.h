@@ -212,7 +212,12 @@ __global__ __launch_bounds__(256) void pose_apply_kernel(PoseJobTable T, const O
     const ObjectPoseDev& P = poses[ji];
     const int i = (int)(blockIdx.x - j.first_block) * 256 + (int)threadIdx.x;
     if (i >= j.n) return;
-    if (j.kind == POSE_XYZ) {
+    if (j.kind == POSE_XYZ && !j.R) {
+        // R = NULL is the identity itself, not a product with ones and zeros: x + t (a copy without t), so that a row holding
+        // Inf stays Inf (0 * Inf is NaN) and -0.0 keeps its sign
+#pragma unroll
+        for (int c = 0; c < 3; ++c) j.dst[3 * i + c] = j.t ? j.src[3 * i + c] + P.t[c] : j.src[3 * i + c];
+    } else if (j.kind == POSE_XYZ) {
         const float dx = j.src[3 * i + 0] - P.center[0], dy = j.src[3 * i + 1] - P.center[1], dz = j.src[3 * i + 2] - P.center[2];
         j.dst[3 * i + 0] = fmaf(P.R[2], dz, fmaf(P.R[1], dy, P.R[0] * dx)) + P.center[0] + P.t[0];
         j.dst[3 * i + 1] = fmaf(P.R[5], dz, fmaf(P.R[4], dy, P.R[3] * dx)) + P.center[1] + P.t[1];

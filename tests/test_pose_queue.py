@@ -7,6 +7,9 @@ import numpy as np
 import pytest
 import torch
 
+import pose_cases as PC
+import pose_reference as PR
+
 
 def _objects(dev, sizes=(700, 1, 2500), seed=5, n_rest=15):
     from pegasus_amd.gaussian_model import GaussianModel
@@ -78,6 +81,39 @@ def test_recorded_pose_calls_equal_calls_applied_at_once(gpu_device, n_rest):
     assert not any(o.__dict__.get("_pose_ops") for o in objs)
     for k, (a, b) in enumerate(zip(objs, ref)):
         _same(a, b, f"object {k}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_rest", [15, 8, 3])
+def test_far_offset_object_meets_the_reference_bound_on_both_paths(gpu_device, n_rest):
+    """Near the origin a wrong or imprecise centre hides under _same's atol.  One object at (1000, -2000, 500), one update,
+    through the recorded path (float64 device mean) and through the calls applied at once (float32 torch mean): each against
+    the float64 reference within its counted bound scaled by the magnitudes involved (tests/pose_reference.py)."""
+    from pegasus_amd import pose_queue as PQ
+    x0 = PC.cloud(1500, far=True, seed=n_rest)
+    (R, t, T), = _poses(gpu_device, 1, 11)
+    R32, t32 = R.cpu().numpy(), t.cpu().numpy()
+    want, mag = PR.positions(x0, R32, t32)
+    for deferred in (True, False):
+        (o,) = _objects(gpu_device, (1500,), seed=7, n_rest=n_rest)
+        o._xyz = torch.from_numpy(x0).to(gpu_device)
+        q0, c0 = o._rotation.cpu().numpy(), o._features_rest.cpu().numpy()
+        before = PQ.set_enabled(deferred)
+        try:
+            _reference_calls(o, R.clone(), T.clone())
+            assert bool(o.__dict__.get("_pose_ops")) == deferred
+            got = o._xyz.cpu().numpy().astype(np.float64)
+            got_q, got_c = o._rotation.cpu().numpy().astype(np.float64), o._features_rest.cpu().numpy().astype(np.float64)
+        finally:
+            PQ.set_enabled(before)
+        ratio = (np.abs(got - want) / (PR.K_XYZ * PR.U * mag)).max()
+        print(f"far object, {'recorded' if deferred else 'applied at once'}: position error / bound {ratio:.3f}")
+        assert ratio <= 1.0, (deferred, ratio)
+        want_M, _ = PR.orientations(q0, R32)
+        got_M = PR.quat_matrix(got_q / np.linalg.norm(got_q, axis=1, keepdims=True))
+        assert np.abs(got_M - want_M).max() <= PR.ORIENT_ATOL
+        want_c, mag_c = PR.rotate_rest(c0, R32)
+        assert (np.abs(got_c - want_c) <= PR.K_SH * PR.U * mag_c).all()
 
 
 @pytest.mark.gpu
