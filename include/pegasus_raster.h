@@ -417,6 +417,51 @@ int32_t pgr_march_count(const PgrGrid *grid, const float *sdf, void *workspace, 
 int32_t pgr_march_emit(const PgrGrid *grid, const float *sdf, const void *workspace, size_t workspace_bytes,
                        float *vertices, int32_t *faces, void *stream);
 
+/* Depth images of triangle meshes at given poses: the depth renderer of the BOP toolkit (its renderer.render_object(...)
+ * ['depth']), for ground-truth masks, scene_gt_info and VSD (pegasus_amd/mesh_render.py).  One call renders n_jobs jobs.  A
+ * job is one mesh at one pose into one canvas: the mesh is a range of the shared device arrays `vertices` (float32
+ * [n_vertices,3]) and `faces` (int32 [n_faces,3], indices relative to the mesh's vertex_first); R (row-major 3x3) and t take a
+ * model point to the camera in the model's units; fx, fy, cx, cy project it; `slot` names the canvas.  All canvases are
+ * width x height, each 1..8192; `depth` is device float32 [n_slots,height,width] and receives the camera z of the nearest
+ * surface, 0 where nothing is hit.  Jobs that share a slot render into the same canvas.  The exact rules (float32 operation
+ * order, the sample point (i + 0.5, j + 0.5), the 1/256-pixel snap, int64 edge functions with a top-left fill rule, no
+ * back-face culling, perspective-correct depth, integer atomic min) are pinned at the top of
+ * pegasus_amd/csrc/meshraster.hip.h; two runs give equal bytes.  near > 0: faces wholly nearer are dropped; faces that straddle
+ * it are dropped whole and counted in the device int32 *straddle_count (there is no clipping).
+ * `jobs` is a host array.  Workspace: pgr_mesh_depth_workspace_bytes(n_jobs, jobs) device bytes; host-only, 0 for bad
+ * arguments (n_jobs <= 0, NULL jobs, a negative range, more than 2^22 faces in one job). */
+typedef struct PgrMeshJob {
+    int32_t vertex_first, vertex_count;
+    int32_t face_first, face_count;
+    float R[9];
+    float t[3];
+    float fx, fy, cx, cy;
+    int32_t slot;
+} PgrMeshJob;
+size_t pgr_mesh_depth_workspace_bytes(int32_t n_jobs, const PgrMeshJob *jobs);
+int32_t pgr_mesh_depth(const float *vertices, int64_t n_vertices, const int32_t *faces, int64_t n_faces, int32_t n_jobs,
+                       const PgrMeshJob *jobs, int32_t width, int32_t height, float near_z, float *depth, int32_t n_slots,
+                       int32_t *straddle_count, void *workspace, size_t workspace_bytes, void *stream);
+
+/* BOP ground truth of n_jobs (object, image) pairs from depth canvases, the sequence of the toolkit's
+ * scripts/calc_gt_info.py:117-177.  Job k reads canvas `slot` of `canvases` [n_slots,canvas_height,canvas_width] (as
+ * pgr_mesh_depth leaves it) and image `frame` of `scene_depth` [n_frames,height,width] (same unit, 0 = missing); the image
+ * window sits at (margin_x, margin_y) inside the canvas (the toolkit renders a 3x canvas: margins = the image size, cx + margin_x,
+ * cy + margin_y).  fx, fy, cx, cy are the image's own K in float64: the distance images are computed in float64 as
+ * misc.depth_im_to_dist_im_fast does, rounded to float32, compared in float32:
+ *   visib = (dist_model - dist_test <= delta or dist_test == 0) and dist_model > 0        (visibility.py, mode bop19)
+ * Outputs: `mask` and `mask_visib` uint8 [n_jobs,height,width] (0/1), and `stats` int32 [n_jobs,11]: px_count_all (whole
+ * canvas), px_count_valid, px_count_visib, then min x, min y, max x, max y of the silhouette over the canvas and of the visible
+ * mask, in image coordinates (INT32_MAX / INT32_MIN when empty). */
+typedef struct PgrGtInfoJob {
+    int32_t slot, frame;
+    double fx, fy, cx, cy;
+} PgrGtInfoJob;
+int32_t pgr_bop_gt_info(const float *canvases, int32_t n_slots, int32_t canvas_width, int32_t canvas_height, int32_t margin_x,
+                        int32_t margin_y, const float *scene_depth, int32_t n_frames, int32_t width, int32_t height,
+                        int32_t n_jobs, const PgrGtInfoJob *jobs, float delta, uint8_t *mask, uint8_t *mask_visib,
+                        int32_t *stats, void *stream);
+
 /* Gradients returned by pgr_backward / pgr_backward_batch (device pointers, any may be NULL = not wanted). */
 typedef struct PgrGradOutputs {
     float *means2d;              /* [n,3] screen-space mean, NDC-scaled (what viewspace_points.grad receives) */

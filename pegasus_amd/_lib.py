@@ -116,6 +116,20 @@ class PgrGrid(C.Structure):
     _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("origin", C.c_float * 3), ("voxel", C.c_float)]
 
 
+class PgrMeshJob(C.Structure):
+    _fields_ = [("vertex_first", C.c_int32), ("vertex_count", C.c_int32), ("face_first", C.c_int32), ("face_count", C.c_int32),
+                ("R", C.c_float * 9), ("t", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("slot", C.c_int32)]
+
+
+class PgrGtInfoJob(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("frame", C.c_int32), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double),
+                ("cy", C.c_double)]
+
+
+PGR_GT_INFO_STATS = 11
+
+
 # every symbol include/pegasus_raster.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "pgr_abi_version": (C.c_int32, []),
@@ -215,6 +229,13 @@ SYMBOLS = {
     "pgr_march_count": (C.c_int32, [C.POINTER(PgrGrid), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "pgr_march_emit": (C.c_int32, [C.POINTER(PgrGrid), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),
+    "pgr_mesh_depth_workspace_bytes": (C.c_size_t, [C.c_int32, C.POINTER(PgrMeshJob)]),
+    "pgr_mesh_depth": (C.c_int32, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(PgrMeshJob), C.c_int32,
+                                   C.c_int32, C.c_float, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
+                                   C.c_void_p]),
+    "pgr_bop_gt_info": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                    C.c_int32, C.c_int32, C.c_int32, C.POINTER(PgrGtInfoJob), C.c_float, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -1,0 +1,358 @@
+// meshraster.hip.h -- depth images of triangle meshes at given poses (the BOP toolkit's depth renderer) and their reduction
+// to BOP ground truth (scene_gt_info, mask, mask_visib).
+//
+// pgr_mesh_depth: the rules (tests/mesh_raster_reference.py restates them in NumPy and reproduces the output bit for bit)
+//
+//   Vertex.     A model point p goes to the camera in float32, no contraction, in this order:
+//                   X = ((R[0] p.x + R[1] p.y) + R[2] p.z) + t[0]        (Y with R[3..5], t[1]; Z with R[6..8], t[2])
+//               The camera looks along +z:  u = (fx X) / Z + cx,  v = (fy Y) / Z + cy  (IEEE division),  w = 1 / Z.
+//   Snap.       Pixel (i, j) samples the image point (i + 0.5, j + 0.5).  Coordinates are snapped to 1/256 pixel in a frame
+//               whose integers*256 are the samples:  q = u * 256 - 128 (the product is exact, the difference rounds once),
+//               s = rint(min(max(q, -2^30), 2^30)) as int32, round to nearest even; a NaN snaps to -2^30 (fmaxf).
+//   Near plane. A face whose three Z are all < near is dropped.  A face with one or two Z < near straddles the plane: it
+//               is dropped whole and counted in *straddle_count.  There is no clipping.  A face with a vertex index
+//               outside its mesh's vertex range is dropped.
+//   Coverage.   Exact integers.  For the edge p -> q:  E_pq(x, y) = (q.x - p.x)(y - p.y) - (q.y - p.y)(x - p.x)  in int64
+//               (it is twice a triangle's area inside a box of side <= 2^31: |E| <= 2^62).  area2 = E_ab(c); zero: the
+//               face is dropped; negative: b and c swap (no back-face culling), so area2 > 0 and the inside has E > 0.
+//               Sample (x, y) = (256 i, 256 j) is covered when every edge has E >= 0 if it is a top or a left edge
+//               (q.y - p.y < 0, or q.y == p.y and q.x - p.x > 0; y points down) and E >= 1 otherwise.  Two faces on
+//               opposite sides of a shared edge walk it in opposite directions, so a sample on it belongs to exactly one.
+//   Depth.      Perspective-correct from the integer edge values, in float32, in this order:
+//                   den = ((float)E_bc * w_a + (float)E_ca * w_b) + (float)E_ab * w_c,    z = (float)area2 / den
+//               (int64 -> float32 rounds to nearest even, IEEE division).  The sample counts when den > 0 and 0 < z < inf.
+//   Nearest.    The canvas holds the float's bits; an integer atomic min picks the nearest surface (positive floats order
+//               like their bits), so the result does not depend on the execution order.  Empty pixels (0xFFFFFFFF during
+//               the call) end as 0.0.  No float atomics.
+//
+// Work.  One lane per face: it redoes the three vertex transforms (a vertex is shared by ~6 faces of a marching-tetrahedra
+// mesh, but 3 x ~40 VALU instructions per face stay far under the 48 bytes per face the gather costs, and a per-job vertex
+// workspace would add a launch and 24 bytes per vertex), clips the face's box to the canvas and walks it when it holds at
+// most MESHR_LARGE_BOX samples.  A larger box goes to a queue: one ballot and ONE 64-bit vector atomic per wave hands out
+// both the entries and their first 16x16 tile (count << 41 | tiles, so entries are sorted by first tile), and a second
+// launch of MESHR_LARGE_WAVES waves splits the total tile count evenly: a wave finds its first entry by bisection, then
+// walks tiles, 4 samples per lane.  A 12-face box over a 2400^2 canvas is 45 k tiles over 8192 waves.
+//
+// pgr_bop_gt_info: per canvas pixel the sequence of the toolkit's calc_gt_info.py, see the kernel.
+#pragma once
+#include "pgr_common.h"
+
+namespace pgr {
+
+constexpr int MESHR_JOBS_PER_LAUNCH = 32;
+constexpr int MESHR_THREADS = 256;
+constexpr int MESHR_LARGE_BOX = 256;                 // samples in the clipped box above which a face is queued
+constexpr int MESHR_TILE = 16;
+constexpr int MESHR_LARGE_WAVES = 8192;
+constexpr int MESHR_TILE_BITS = 41;                  // 2^22 faces x 2^18 tiles of an 8192^2 canvas < 2^41
+constexpr int64_t MESHR_MAX_GROUP_FACES = (int64_t)1 << 22;
+constexpr uint32_t MESHR_EMPTY = 0xFFFFFFFFu;
+constexpr float MESHR_SNAP_LIMIT = 1073741824.0f;    // 2^30
+
+struct MeshJobDev {
+    int32_t v0, nv, f0, nf;
+    float R[9], t[3];
+    float fx, fy, cx, cy;
+    int32_t slot;
+    uint32_t block0;                                 // first workgroup of the job in the small launch
+};
+
+struct MeshJobTable {
+    int32_t count, width, height;
+    float near;
+    MeshJobDev job[MESHR_JOBS_PER_LAUNCH];
+};
+
+struct MeshQueueEntry {
+    int32_t job, face;
+    unsigned long long tile_base;
+};
+
+struct MeshTri {
+    int32_t ax, ay, bx, by, cx, cy;                  // snapped, area2 > 0
+    float wa, wb, wc;
+    long long area2;
+    int32_t i0, i1, j0, j1;                          // clipped box in pixels, inclusive
+};
+
+__device__ __forceinline__ int32_t mesh_snap(float u) {
+    const float q = u * 256.0f - 128.0f;
+    return (int32_t)rintf(fminf(fmaxf(q, -MESHR_SNAP_LIMIT), MESHR_SNAP_LIMIT));
+}
+
+__device__ __forceinline__ long long mesh_edge(int32_t px, int32_t py, int32_t qx, int32_t qy, int32_t x, int32_t y) {
+    return ((long long)qx - px) * ((long long)y - py) - ((long long)qy - py) * ((long long)x - px);
+}
+
+// smallest E that still covers: 0 for a top or left edge, 1 otherwise
+__device__ __forceinline__ long long mesh_edge_bias(int32_t px, int32_t py, int32_t qx, int32_t qy) {
+    const long long dx = (long long)qx - px, dy = (long long)qy - py;
+    return (dy < 0 || (dy == 0 && dx > 0)) ? 0 : 1;
+}
+
+// 0: dropped, 1: to rasterise, 2: dropped because it straddles the near plane
+__device__ __forceinline__ int mesh_setup(const MeshJobDev& J, const float* __restrict__ vertices,
+                                          const int32_t* __restrict__ faces, int face, int W, int H, float near, MeshTri& T) {
+    const int32_t* f = faces + 3 * ((size_t)J.f0 + (size_t)face);
+    int32_t sx[3], sy[3];
+    float w[3];
+    int behind = 0;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const int32_t vi = f[q];
+        if (vi < 0 || vi >= J.nv) return 0;
+        const float* p = vertices + 3 * ((size_t)J.v0 + (size_t)vi);
+        const float px = p[0], py = p[1], pz = p[2];
+        const float X = ((J.R[0] * px + J.R[1] * py) + J.R[2] * pz) + J.t[0];
+        const float Y = ((J.R[3] * px + J.R[4] * py) + J.R[5] * pz) + J.t[1];
+        const float Z = ((J.R[6] * px + J.R[7] * py) + J.R[8] * pz) + J.t[2];
+        behind += Z < near ? 1 : 0;
+        sx[q] = mesh_snap((J.fx * X) / Z + J.cx);
+        sy[q] = mesh_snap((J.fy * Y) / Z + J.cy);
+        w[q] = 1.0f / Z;
+    }
+    if (behind == 3) return 0;
+    if (behind) return 2;
+    long long area2 = mesh_edge(sx[0], sy[0], sx[1], sy[1], sx[2], sy[2]);
+    if (area2 == 0) return 0;
+    int b = 1, c = 2;
+    if (area2 < 0) { b = 2; c = 1; area2 = -area2; }
+    T.ax = sx[0]; T.ay = sy[0]; T.bx = sx[b]; T.by = sy[b]; T.cx = sx[c]; T.cy = sy[c];
+    T.wa = w[0]; T.wb = w[b]; T.wc = w[c];
+    T.area2 = area2;
+    const int32_t minx = min(sx[0], min(sx[1], sx[2])), maxx = max(sx[0], max(sx[1], sx[2]));
+    const int32_t miny = min(sy[0], min(sy[1], sy[2])), maxy = max(sy[0], max(sy[1], sy[2]));
+    T.i0 = max(0, (minx + 255) >> 8);
+    T.i1 = min(W - 1, maxx >> 8);
+    T.j0 = max(0, (miny + 255) >> 8);
+    T.j1 = min(H - 1, maxy >> 8);
+    return (T.i0 <= T.i1 && T.j0 <= T.j1) ? 1 : 0;
+}
+
+__device__ __forceinline__ void mesh_sample(const MeshTri& T, long long ea, long long eb, long long ec, uint32_t* pix) {
+    const float den = ((float)ea * T.wa + (float)eb * T.wb) + (float)ec * T.wc;
+    const float z = (float)T.area2 / den;
+    if (den > 0.f && z > 0.f && z < INFINITY)
+        __hip_atomic_fetch_min((PGR_GLOBAL uint32_t*)pix, __float_as_uint(z), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the job of a workgroup of the small launch
+__device__ __forceinline__ int mesh_job_of_block(const MeshJobTable& T, uint32_t block) {
+    int k = 0;
+    for (int q = 1; q < T.count; ++q)
+        if (block >= T.job[q].block0) k = q;
+    return k;
+}
+
+__global__ __launch_bounds__(MESHR_THREADS) void mesh_small_kernel(const MeshJobTable T, const float* __restrict__ vertices,
+                                                                  const int32_t* __restrict__ faces, uint32_t* __restrict__ out,
+                                                                  size_t plane, unsigned long long* __restrict__ qctr,
+                                                                  MeshQueueEntry* __restrict__ queue, long long queue_cap,
+                                                                  int32_t* __restrict__ straddle) {
+    const int k = mesh_job_of_block(T, blockIdx.x);
+    const MeshJobDev& J = T.job[k];
+    const int lane = threadIdx.x & (WAVE - 1);
+    const long long face = (long long)(blockIdx.x - J.block0) * MESHR_THREADS + threadIdx.x;
+    MeshTri tri;
+    int status = 0;
+    if (face < J.nf) status = mesh_setup(J, vertices, faces, (int)face, T.width, T.height, T.near, tri);
+    const unsigned long long sb = __ballot(status == 2);
+    if (sb && lane == 0) atomicAdd(straddle, (int32_t)__popcll(sb));
+    unsigned long long ntiles = 0;
+    if (status == 1) {
+        const long long bw = tri.i1 - tri.i0 + 1, bh = tri.j1 - tri.j0 + 1;
+        if (bw * bh > MESHR_LARGE_BOX)
+            ntiles = (unsigned long long)(((bw + MESHR_TILE - 1) / MESHR_TILE) * ((bh + MESHR_TILE - 1) / MESHR_TILE));
+    }
+    const bool large = ntiles != 0;
+    const unsigned long long lb = __ballot(large);
+    if (lb) {                                        // wave-uniform: every lane takes part in the scan
+        unsigned long long incl = ntiles;
+#pragma unroll
+        for (int d = 1; d < WAVE; d <<= 1) {
+            const unsigned long long up = __shfl_up(incl, d, WAVE);
+            if (lane >= d) incl += up;
+        }
+        const unsigned long long total = __shfl(incl, WAVE - 1, WAVE);
+        unsigned long long base = 0;
+        if (lane == 0)
+            base = __hip_atomic_fetch_add((PGR_GLOBAL unsigned long long*)qctr,
+                                          ((unsigned long long)__popcll(lb) << MESHR_TILE_BITS) | total, __ATOMIC_RELAXED,
+                                          __HIP_MEMORY_SCOPE_AGENT);
+        base = __shfl(base, 0, WAVE);
+        if (large) {
+            const long long idx = (long long)(base >> MESHR_TILE_BITS) + __popcll(lb & ((1ull << lane) - 1ull));
+            if (idx < queue_cap)
+                queue[idx] = MeshQueueEntry{k, (int32_t)face, (base & ((1ull << MESHR_TILE_BITS) - 1ull)) + incl - ntiles};
+        }
+    }
+    if (status != 1 || large) return;
+    // walk the box: edge values at the row's first sample, then one add per sample
+    uint32_t* canvas = out + (size_t)J.slot * plane;
+    const long long ba = mesh_edge_bias(tri.bx, tri.by, tri.cx, tri.cy), bb = mesh_edge_bias(tri.cx, tri.cy, tri.ax, tri.ay),
+                    bc = mesh_edge_bias(tri.ax, tri.ay, tri.bx, tri.by);
+    const long long sa = -256ll * ((long long)tri.cy - tri.by), sbx = -256ll * ((long long)tri.ay - tri.cy),
+                    sc = -256ll * ((long long)tri.by - tri.ay);
+    for (int j = tri.j0; j <= tri.j1; ++j) {
+        long long ea = mesh_edge(tri.bx, tri.by, tri.cx, tri.cy, tri.i0 << 8, j << 8);
+        long long eb = mesh_edge(tri.cx, tri.cy, tri.ax, tri.ay, tri.i0 << 8, j << 8);
+        long long ec = mesh_edge(tri.ax, tri.ay, tri.bx, tri.by, tri.i0 << 8, j << 8);
+        for (int i = tri.i0; i <= tri.i1; ++i) {
+            if (ea >= ba && eb >= bb && ec >= bc) mesh_sample(tri, ea, eb, ec, canvas + (size_t)j * T.width + i);
+            ea += sa; eb += sbx; ec += sc;
+        }
+    }
+}
+
+__global__ __launch_bounds__(MESHR_THREADS) void mesh_large_kernel(const MeshJobTable T, const float* __restrict__ vertices,
+                                                                  const int32_t* __restrict__ faces, uint32_t* __restrict__ out,
+                                                                  size_t plane, const unsigned long long* __restrict__ qctr,
+                                                                  const MeshQueueEntry* __restrict__ queue, long long queue_cap) {
+    const unsigned long long packed = *qctr;
+    const unsigned long long total = packed & ((1ull << MESHR_TILE_BITS) - 1ull);
+    const long long count = min((long long)(packed >> MESHR_TILE_BITS), queue_cap);
+    if (total == 0 || count == 0) return;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const unsigned long long wave = ((unsigned long long)blockIdx.x * MESHR_THREADS + threadIdx.x) / WAVE;
+    const unsigned long long n_waves = (unsigned long long)gridDim.x * (MESHR_THREADS / WAVE);
+    const unsigned long long per = (total + n_waves - 1) / n_waves;
+    unsigned long long k = wave * per;
+    const unsigned long long k_end = min(total, k + per);
+    if (k >= k_end) return;
+    long long lo = 0, hi = count - 1;                // the last entry whose first tile is <= k
+    while (lo < hi) {
+        const long long mid = (lo + hi + 1) >> 1;
+        if (queue[mid].tile_base <= k) lo = mid; else hi = mid - 1;
+    }
+    for (long long e = lo; e < count && k < k_end; ++e) {
+        const MeshQueueEntry q = queue[e];
+        const unsigned long long next = e + 1 < count ? queue[e + 1].tile_base : total;
+        const unsigned long long stop = min(k_end, next);
+        const int job = __builtin_amdgcn_readfirstlane(q.job);           // the entry is the wave's: a scalar index into the table
+        if (job < 0 || job >= T.count) { k = stop; continue; }
+        const MeshJobDev& J = T.job[job];
+        MeshTri tri;
+        if (q.face < 0 || q.face >= J.nf || mesh_setup(J, vertices, faces, q.face, T.width, T.height, T.near, tri) != 1) {
+            k = stop;
+            continue;
+        }
+        uint32_t* canvas = out + (size_t)J.slot * plane;
+        const unsigned long long tiles_x = (unsigned long long)((tri.i1 - tri.i0 + MESHR_TILE) / MESHR_TILE);
+        const long long ba = mesh_edge_bias(tri.bx, tri.by, tri.cx, tri.cy), bb = mesh_edge_bias(tri.cx, tri.cy, tri.ax, tri.ay),
+                        bc = mesh_edge_bias(tri.ax, tri.ay, tri.bx, tri.by);
+        for (; k < stop; ++k) {
+            const unsigned long long t = k - q.tile_base;
+            const int i = tri.i0 + (int)(t % tiles_x) * MESHR_TILE + (lane & (MESHR_TILE - 1));
+            const int jt = tri.j0 + (int)(t / tiles_x) * MESHR_TILE + (lane >> 4);
+            if (i > tri.i1) continue;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int j = jt + 4 * r;
+                if (j > tri.j1) break;
+                const long long ea = mesh_edge(tri.bx, tri.by, tri.cx, tri.cy, i << 8, j << 8);
+                const long long eb = mesh_edge(tri.cx, tri.cy, tri.ax, tri.ay, i << 8, j << 8);
+                const long long ec = mesh_edge(tri.ax, tri.ay, tri.bx, tri.by, i << 8, j << 8);
+                if (ea >= ba && eb >= bb && ec >= bc) mesh_sample(tri, ea, eb, ec, canvas + (size_t)j * T.width + i);
+            }
+        }
+    }
+}
+
+// empty pixels end as 0.0
+__global__ __launch_bounds__(256) void mesh_finalize_kernel(uint32_t* __restrict__ out, size_t n) {
+    for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (size_t)gridDim.x * 256)
+        if (out[p] == MESHR_EMPTY) out[p] = 0u;
+}
+
+// ---- BOP ground truth from a depth canvas ---------------------------------------------------------------------------
+// The toolkit's scripts/calc_gt_info.py:117-177 for one (object, image) pair, per pixel of the canvas:
+//   silhouette over the WHOLE canvas: depth > 0 (px_count_all, bbox_obj in image coordinates = canvas - margin);
+//   inside the image window: distance images as misc.depth_im_to_dist_im_fast computes them, in float64 --
+//       dist = sqrt(((x - cx) / fx * d)^2 + ((y - cy) / fy * d)^2 + d^2)   at the integer pixel index, summed left to right
+//   -- both rounded to float32, d_diff = dist_model - dist_test in float32, and (visibility.py:34-37, mode bop19)
+//       visib = (d_diff <= delta or dist_test == 0) and dist_model > 0.
+// One int32 row per job: px_count_all, px_count_valid, px_count_visib, then min x, min y, max x, max y of the silhouette
+// and of the visible mask (image coordinates, INT32_MAX / INT32_MIN when empty).  Integer atomics only.
+constexpr int GT_JOBS_PER_LAUNCH = 64;
+constexpr int GT_STATS = 11;
+constexpr int GT_BLOCKS_X = 512;
+
+struct GtJobDev {
+    int32_t slot, frame;
+    double fx, fy, cx, cy;
+};
+
+struct GtJobTable {
+    int32_t count, first;
+    int32_t canvas_w, canvas_h, width, height, mx, my;
+    float delta;
+    GtJobDev job[GT_JOBS_PER_LAUNCH];
+};
+
+__global__ __launch_bounds__(256) void gt_info_init_kernel(int32_t* __restrict__ stats, int n_jobs) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_jobs * GT_STATS) return;
+    const int s = e % GT_STATS;
+    stats[e] = s < 3 ? 0 : (((s - 3) & 2) ? INT32_MIN : INT32_MAX);
+}
+
+__device__ __forceinline__ double gt_dist(double d, int x, int y, double fx, double fy, double cx, double cy) {
+    const double X = (((double)x - cx) / fx) * d, Y = (((double)y - cy) / fy) * d;
+    return sqrt((X * X + Y * Y) + d * d);
+}
+
+__global__ __launch_bounds__(256) void gt_info_kernel(const GtJobTable T, const float* __restrict__ canvases,
+                                                      const float* __restrict__ scene_depth, uint8_t* __restrict__ mask,
+                                                      uint8_t* __restrict__ mask_visib, int32_t* __restrict__ stats) {
+    const GtJobDev& J = T.job[blockIdx.y];
+    const size_t job = (size_t)T.first + blockIdx.y;
+    const size_t plane = (size_t)T.canvas_w * T.canvas_h, image = (size_t)T.width * T.height;
+    const float* canvas = canvases + (size_t)J.slot * plane;
+    const float* scene = scene_depth + (size_t)J.frame * image;
+    int32_t v[GT_STATS];
+#pragma unroll
+    for (int s = 0; s < GT_STATS; ++s) v[s] = s < 3 ? 0 : (((s - 3) & 2) ? INT32_MIN : INT32_MAX);
+    for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < plane; p += (size_t)gridDim.x * 256) {
+        const int yc = (int)(p / T.canvas_w), xc = (int)(p % T.canvas_w);
+        const int x = xc - T.mx, y = yc - T.my;
+        const float d = canvas[p];
+        if (d > 0.f) {
+            v[0] += 1;
+            v[3] = min(v[3], x); v[4] = min(v[4], y); v[5] = max(v[5], x); v[6] = max(v[6], y);
+        }
+        if (x < 0 || y < 0 || x >= T.width || y >= T.height) continue;
+        const float dt = scene[(size_t)y * T.width + x];
+        const float dist_model = (float)gt_dist((double)d, x, y, J.fx, J.fy, J.cx, J.cy);
+        const float dist_test = (float)gt_dist((double)dt, x, y, J.fx, J.fy, J.cx, J.cy);
+        const float diff = dist_model - dist_test;
+        const bool in_mask = dist_model > 0.f;
+        const bool visible = (diff <= T.delta || dist_test == 0.f) && in_mask;
+        mask[job * image + (size_t)y * T.width + x] = in_mask ? 1 : 0;
+        mask_visib[job * image + (size_t)y * T.width + x] = visible ? 1 : 0;
+        if (in_mask && dist_test > 0.f) v[1] += 1;
+        if (visible) {
+            v[2] += 1;
+            v[7] = min(v[7], x); v[8] = min(v[8], y); v[9] = max(v[9], x); v[10] = max(v[10], y);
+        }
+    }
+    if (!__ballot(v[0] != 0 || v[1] != 0 || v[2] != 0)) return;      // nothing of the object in this wave's pixels
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+#pragma unroll
+        for (int s = 0; s < GT_STATS; ++s) {
+            const int32_t o = __shfl_xor(v[s], d, WAVE);
+            v[s] = s < 3 ? v[s] + o : (((s - 3) & 2) ? max(v[s], o) : min(v[s], o));
+        }
+    }
+    if ((threadIdx.x & (WAVE - 1)) == 0) {
+        int32_t* row = stats + job * GT_STATS;
+#pragma unroll
+        for (int s = 0; s < GT_STATS; ++s) {
+            if (s < 3) { if (v[s]) atomicAdd(row + s, v[s]); }
+            else if ((s - 3) & 2) atomicMax(row + s, v[s]);
+            else atomicMin(row + s, v[s]);
+        }
+    }
+}
+
+}  // namespace pgr

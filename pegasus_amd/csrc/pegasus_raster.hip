@@ -20,6 +20,7 @@
 #include "blockcull.hip.h"
 #include "knn.hip.h"
 #include "mesh.hip.h"
+#include "meshraster.hip.h"
 #include "compose.hip.h"
 #include "composite.hip.h"
 #include "pgr_common.h"
@@ -1291,6 +1292,139 @@ int32_t pgr_march_emit(const PgrGrid* grid, const float* sdf, const void* worksp
                                                               reinterpret_cast<const uint8_t*>(ws + M.ntri), tile_off, vbase,
                                                               faces);
     return hip_ok(hipGetLastError(), "march_emit launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+// ---- mesh depth renderer and BOP ground truth (meshraster.hip.h) ------------------------------------------------------
+namespace {
+constexpr int32_t MESHR_MAX_CANVAS = 8192;
+bool mesh_jobs_ok(int32_t n_jobs, const PgrMeshJob* jobs) {
+    if (n_jobs < 0 || (n_jobs > 0 && !jobs)) return false;
+    for (int32_t k = 0; k < n_jobs; ++k) {
+        const PgrMeshJob& j = jobs[k];
+        if (j.vertex_first < 0 || j.vertex_count < 0 || j.face_first < 0 || j.face_count < 0 ||
+            j.face_count > MESHR_MAX_GROUP_FACES)
+            return false;
+    }
+    return true;
+}
+// jobs [k0, end) of one launch: at most MESHR_JOBS_PER_LAUNCH jobs and MESHR_MAX_GROUP_FACES faces
+int32_t mesh_group_end(int32_t n_jobs, const PgrMeshJob* jobs, int32_t k0, int64_t* faces_out) {
+    int64_t faces = 0;
+    int32_t k = k0;
+    while (k < n_jobs && k - k0 < MESHR_JOBS_PER_LAUNCH && (k == k0 || faces + jobs[k].face_count <= MESHR_MAX_GROUP_FACES))
+        faces += jobs[k++].face_count;
+    *faces_out = faces;
+    return k;
+}
+int64_t mesh_queue_capacity(int32_t n_jobs, const PgrMeshJob* jobs) {
+    int64_t cap = 0, faces = 0;
+    for (int32_t k0 = 0; k0 < n_jobs;) {
+        k0 = mesh_group_end(n_jobs, jobs, k0, &faces);
+        cap = std::max(cap, faces);
+    }
+    return cap;
+}
+}  // namespace
+
+size_t pgr_mesh_depth_workspace_bytes(int32_t n_jobs, const PgrMeshJob* jobs) {
+    if (n_jobs <= 0 || !mesh_jobs_ok(n_jobs, jobs)) return 0;
+    return align_up(sizeof(unsigned long long)) + align_up((size_t)std::max<int64_t>(mesh_queue_capacity(n_jobs, jobs), 1) * sizeof(MeshQueueEntry));
+}
+
+int32_t pgr_mesh_depth(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int32_t n_jobs,
+                       const PgrMeshJob* jobs, int32_t width, int32_t height, float near_z, float* depth, int32_t n_slots,
+                       int32_t* straddle_count, void* workspace, size_t workspace_bytes, void* stream_v) {
+    if (!mesh_jobs_ok(n_jobs, jobs) || !depth || !straddle_count || n_slots < 1 || n_vertices < 0 || n_faces < 0 ||
+        width < 1 || width > MESHR_MAX_CANVAS || height < 1 || height > MESHR_MAX_CANVAS || !(near_z > 0.f) ||
+        !std::isfinite(near_z))
+        return PGR_ERR_INVALID_ARGUMENT;
+    bool any_faces = false;
+    for (int32_t k = 0; k < n_jobs; ++k) {
+        const PgrMeshJob& j = jobs[k];
+        if ((int64_t)j.vertex_first + j.vertex_count > n_vertices || (int64_t)j.face_first + j.face_count > n_faces ||
+            j.slot < 0 || j.slot >= n_slots)
+            return PGR_ERR_INVALID_ARGUMENT;
+        any_faces = any_faces || j.face_count > 0;
+    }
+    if (any_faces && (!vertices || !faces)) return PGR_ERR_INVALID_ARGUMENT;
+    if (n_jobs > 0 && (!workspace || workspace_bytes < pgr_mesh_depth_workspace_bytes(n_jobs, jobs)))
+        return PGR_ERR_WORKSPACE_TOO_SMALL;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    const size_t plane = (size_t)width * height, total = plane * (size_t)n_slots;
+    auto* out = reinterpret_cast<uint32_t*>(depth);
+    if (!hip_ok(hipMemsetAsync(out, 0xFF, total * sizeof(uint32_t), stream), "mesh_depth clear") ||
+        !hip_ok(hipMemsetAsync(straddle_count, 0, sizeof(int32_t), stream), "mesh_depth clear"))
+        return PGR_ERR_LAUNCH_FAILURE;
+    char* ws = static_cast<char*>(workspace);
+    auto* qctr = reinterpret_cast<unsigned long long*>(ws);
+    auto* queue = reinterpret_cast<MeshQueueEntry*>(ws + align_up(sizeof(unsigned long long)));
+    int64_t group_faces = 0;
+    for (int32_t k0 = 0; k0 < n_jobs;) {
+        const int32_t k1 = mesh_group_end(n_jobs, jobs, k0, &group_faces);
+        MeshJobTable T{};
+        T.count = k1 - k0;
+        T.width = width;
+        T.height = height;
+        T.near = near_z;
+        uint32_t blocks = 0;
+        for (int32_t k = k0; k < k1; ++k) {
+            const PgrMeshJob& j = jobs[k];
+            MeshJobDev& d = T.job[k - k0];
+            d.v0 = j.vertex_first; d.nv = j.vertex_count; d.f0 = j.face_first; d.nf = j.face_count;
+            std::memcpy(d.R, j.R, sizeof(d.R));
+            std::memcpy(d.t, j.t, sizeof(d.t));
+            d.fx = j.fx; d.fy = j.fy; d.cx = j.cx; d.cy = j.cy;
+            d.slot = j.slot;
+            d.block0 = blocks;
+            blocks += (uint32_t)((j.face_count + MESHR_THREADS - 1) / MESHR_THREADS);
+        }
+        k0 = k1;
+        if (!blocks) continue;
+        if (!hip_ok(hipMemsetAsync(qctr, 0, sizeof(unsigned long long), stream), "mesh_depth queue clear"))
+            return PGR_ERR_LAUNCH_FAILURE;
+        mesh_small_kernel<<<blocks, MESHR_THREADS, 0, stream>>>(T, vertices, faces, out, plane, qctr, queue,
+                                                                (long long)group_faces, straddle_count);
+        mesh_large_kernel<<<MESHR_LARGE_WAVES / (MESHR_THREADS / WAVE), MESHR_THREADS, 0, stream>>>(
+            T, vertices, faces, out, plane, qctr, queue, (long long)group_faces);
+    }
+    mesh_finalize_kernel<<<(unsigned)std::min<size_t>((total + 255) / 256, 65536), 256, 0, stream>>>(out, total);
+    return hip_ok(hipGetLastError(), "mesh_depth launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+int32_t pgr_bop_gt_info(const float* canvases, int32_t n_slots, int32_t canvas_width, int32_t canvas_height, int32_t margin_x,
+                        int32_t margin_y, const float* scene_depth, int32_t n_frames, int32_t width, int32_t height,
+                        int32_t n_jobs, const PgrGtInfoJob* jobs, float delta, uint8_t* mask, uint8_t* mask_visib,
+                        int32_t* stats, void* stream_v) {
+    if (n_jobs < 0 || (n_jobs > 0 && !jobs) || !canvases || !scene_depth || !mask || !mask_visib || !stats || n_slots < 1 ||
+        n_frames < 1 || canvas_width < 1 || canvas_width > MESHR_MAX_CANVAS || canvas_height < 1 ||
+        canvas_height > MESHR_MAX_CANVAS || width < 1 || height < 1 || margin_x < 0 || margin_y < 0 ||
+        (int64_t)margin_x + width > canvas_width || (int64_t)margin_y + height > canvas_height || std::isnan(delta))
+        return PGR_ERR_INVALID_ARGUMENT;
+    for (int32_t k = 0; k < n_jobs; ++k) {
+        const PgrGtInfoJob& j = jobs[k];
+        if (j.slot < 0 || j.slot >= n_slots || j.frame < 0 || j.frame >= n_frames || !(j.fx != 0.0) || !(j.fy != 0.0) ||
+            !std::isfinite(j.fx) || !std::isfinite(j.fy) || !std::isfinite(j.cx) || !std::isfinite(j.cy))
+            return PGR_ERR_INVALID_ARGUMENT;
+    }
+    if (n_jobs == 0) return PGR_OK;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    gt_info_init_kernel<<<(n_jobs * GT_STATS + 255) / 256, 256, 0, stream>>>(stats, n_jobs);
+    const size_t plane = (size_t)canvas_width * canvas_height;
+    const unsigned blocks_x = (unsigned)std::min<size_t>((plane + 255) / 256, GT_BLOCKS_X);
+    for (int32_t k0 = 0; k0 < n_jobs; k0 += GT_JOBS_PER_LAUNCH) {
+        GtJobTable T{};
+        T.count = std::min(GT_JOBS_PER_LAUNCH, n_jobs - k0);
+        T.first = k0;
+        T.canvas_w = canvas_width; T.canvas_h = canvas_height; T.width = width; T.height = height;
+        T.mx = margin_x; T.my = margin_y;
+        T.delta = delta;
+        for (int32_t k = 0; k < T.count; ++k) {
+            const PgrGtInfoJob& j = jobs[k0 + k];
+            T.job[k] = GtJobDev{j.slot, j.frame, j.fx, j.fy, j.cx, j.cy};
+        }
+        gt_info_kernel<<<dim3(blocks_x, (unsigned)T.count), 256, 0, stream>>>(T, canvases, scene_depth, mask, mask_visib, stats);
+    }
+    return hip_ok(hipGetLastError(), "bop_gt_info launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
 }
 
 // ---- training step: fused L1 + D-SSIM loss, Adam over all parameter groups, densification statistics (train.hip.h) ------

@@ -102,10 +102,14 @@ class BopSceneWriter:
             batch_futures.append(self._pool.submit(self._write, path, image))
 
     def add_batch(self, frames: dict, scene_gt: dict, scene_camera: dict, n: int = None, silhouettes=None, frame_ids=None,
-                  record_shape=None):
+                  record_shape=None, meshes=None, delta: float = 15.0, translation_scale: float = 1.0):
         """``frames``: FrameRenderer output (color, depth, and with masks: seg, masks); ``silhouettes``: uint8 [B,K,H,W]
         of FrameRenderer.render_silhouettes (or frames["sil"]) -> the mask/ directory.  ``frame_ids``: the frames' numbers in
-        the dataset (default: consecutive) -- a view-sharded run gives every rank's writer the GLOBAL ids of its frames."""
+        the dataset (default: consecutive) -- a view-sharded run gives every rank's writer the GLOBAL ids of its frames.
+        ``meshes``: a mesh_render.MeshSet in scene_gt's unit (``translation_scale``: 1 = metres, 1000 = millimetres) -> mask/,
+        mask_visib/ and scene_gt_info.json come from the meshes' depth renders tested against the written depth image with
+        tolerance ``delta`` millimetres (mesh_render.gt_from_meshes: the toolkit's calc_gt_info.py and calc_gt_masks.py),
+        not from the splat masks."""
         from . import masks as M
         masks_dev = frames.get("masks")
         if "color" in frames:
@@ -138,9 +142,23 @@ class BopSceneWriter:
             # BOP's scene_gt_info from the masks the batch already holds, counted on the GPU (a few hundred numbers per batch)
             from . import bop_pose
             info = bop_pose.gt_info_from_masks(masks_dev[:n], silhouettes[:n], depth_mm_dev != 0)
+        mesh_gt = None
+        if meshes is not None:
+            import torch
+            from . import mesh_render
+            mm_dev = depth_mm_dev.to(torch.int32) & 0xFFFF                   # int16 storage of uint16 millimetres
+            mesh_gt = mesh_render.gt_from_meshes(meshes, {str(i): scene_gt[str(i)] for i in range(n)},
+                                                 {str(i): scene_camera[str(i)] for i in range(n)}, mm_dev, delta=delta,
+                                                 translation_scale=translation_scale)
+            mk = sil = info = None
         futures = []
         for i in range(n):
             fid = self.n_frames if frame_ids is None else int(frame_ids[i])
+            if mesh_gt is not None:
+                for name, stack in (("mask", mesh_gt[0][i]), ("mask_visib", mesh_gt[1][i])):
+                    for k, image in enumerate((stack * 255).cpu().numpy()):
+                        self._submit(self.scene / name / f"{fid:06d}_{k:06d}.png", image, futures)
+                self.scene_gt_info[str(fid)] = mesh_gt[2][i]
             self._submit(self.scene / "rgb" / f"{fid:06d}.png", rgb8[i], futures)
             self._submit(self.scene / "depth" / f"{fid:06d}.png", mm[i], futures)
             if mk is not None:

@@ -29,6 +29,10 @@ def main():
     ap.add_argument("--size", type=int, default=800)
     ap.add_argument("--dynamic", action="store_true", help="every frame a time step with its own object poses")
     ap.add_argument("--writers", type=int, default=None, help="PNG encoder threads (default: host cores, at most 32)")
+    ap.add_argument("--gt-from-meshes", default=None, metavar="MODELS_DIR",
+                    help="take mask/, mask_visib/ and scene_gt_info.json from the depth renders of the obj_NNNNNN.ply meshes "
+                         "(millimetres, as pegasus_amd.mesh writes them) of this directory, as the BOP toolkit does")
+    ap.add_argument("--delta", type=float, default=15.0, help="visibility tolerance in millimetres for --gt-from-meshes")
     args = ap.parse_args()
 
     import os
@@ -64,6 +68,10 @@ def main():
     if writers is None and world > 1:        # N ranks share the host's cores: their encoder pools must not add up to N x 32
         writers = max(1, min(32, (os.cpu_count() or 1) // world))
     w = BopSceneWriter(args.out, workers=writers)
+    meshes = None
+    if args.gt_from_meshes:
+        from .mesh_render import MeshSet
+        meshes = MeshSet.from_dir(args.gt_from_meshes, device=device, scale=0.001)      # scene_gt is in metres here
     t0 = time.perf_counter()
     t_gpu = 0.0
     mine = list(range(rank, args.frames, world))          # frame f -> rank f mod world
@@ -91,7 +99,8 @@ def main():
         torch.cuda.synchronize(device)
         t_gpu += time.perf_counter() - t1
         gt, cam = bop_pose.batch_pose_records(vs, m2w, boxes=boxes)
-        w.add_batch(frames, gt, cam, n=len(vs), silhouettes=sil, frame_ids=ids, record_shape=(H, W, fr.K))
+        w.add_batch(frames, gt, cam, n=len(vs), silhouettes=sil, frame_ids=ids, record_shape=(H, W, fr.K), meshes=meshes,
+                    delta=args.delta)
     scene = w.close(write_json=False)
     if world > 1:
         import torch.distributed as dist
