@@ -462,6 +462,40 @@ int32_t pgr_bop_gt_info(const float *canvases, int32_t n_slots, int32_t canvas_w
                         int32_t n_jobs, const PgrGtInfoJob *jobs, float delta, uint8_t *mask, uint8_t *mask_visib,
                         int32_t *stats, void *stream);
 
+/* The BOP pose errors of n_jobs (estimate, ground truth) pairs: the toolkit's pose_error.mssd, mspd, add, proj, re and te
+ * (bop_toolkit_lib/pose_error.py) in one call.  A job names its object's model points as a range of the shared device array
+ * `vertices` (float32 [n_vertices,3], what mesh_render.MeshSet uploads) and the object's symmetry transforms as a range of
+ * the device array `syms` (float64 [n_syms,12]: R row-major, then t; what misc.get_symmetry_transformations returns, the
+ * identity first), the two poses in float64 and the intrinsics (no skew).  `errors` is device float32 [n_jobs,6]: mssd, mspd,
+ * add, proj, re (degrees), te; `re_te` (device float64 [n_jobs,2], may be NULL) receives re and te unrounded.  Ground truth
+ * and symmetry are composed in float64 on the device and rounded to float32 once, the per-vertex arithmetic is float32; the
+ * exact rules are pinned at the top of pegasus_amd/csrc/poseerr.hip.h.  est == gt gives mssd = mspd = add = proj = 0 exactly;
+ * two runs give equal bytes (integer atomic min, fixed-order sums).  `jobs` is a host array.  PGR_ERR_INVALID_ARGUMENT before
+ * anything is enqueued: a NULL array with n_jobs > 0, a vertex or symmetry range that leaves its array, vertex_count <= 0,
+ * sym_count <= 0.  n_jobs == 0: PGR_OK, no launch.  PGR_POSE_SYM_CHUNK symmetries of a job share one workgroup. */
+#define PGR_POSE_ERRORS 6
+#define PGR_POSE_SYM_CHUNK 4
+typedef struct PgrPoseErrorJob {
+    int32_t vertex_first, vertex_count;
+    int32_t sym_first, sym_count;
+    double R_est[9], t_est[3];   /* model to camera, row-major */
+    double R_gt[9], t_gt[3];
+    double fx, fy, cx, cy;       /* rounded to float32 for the projection */
+} PgrPoseErrorJob;
+int32_t pgr_pose_errors(const float *vertices, int64_t n_vertices, const double *syms, int64_t n_syms, int32_t n_jobs,
+                        const PgrPoseErrorJob *jobs, float *errors, double *re_te, void *stream);
+
+/* ADI (ADD-S) of n_jobs pairs: the toolkit's pose_error.adi, the mean over the ground-truth-posed model points of the
+ * distance to the nearest estimate-posed model point.  Exact brute-force search in float32 in the model's frame (only the
+ * queries are transformed, by R_est^T R_gt and R_est^T (t_gt - t_est) composed in float64 on the host and rounded once; rules
+ * in pegasus_amd/csrc/poseerr.hip.h).  `adi` is device float32 [n_jobs].  est == gt gives 0 exactly; two runs give equal
+ * bytes.  The jobs' symmetry ranges and intrinsics are not read.  Workspace: pgr_pose_adi_workspace_bytes(n_jobs, jobs)
+ * device bytes (host-only; 0 for n_jobs <= 0, NULL jobs or a vertex_count <= 0).  Argument checks as pgr_pose_errors makes
+ * them for the vertices; PGR_ERR_WORKSPACE_TOO_SMALL for a workspace below the query. */
+size_t pgr_pose_adi_workspace_bytes(int32_t n_jobs, const PgrPoseErrorJob *jobs);
+int32_t pgr_pose_adi(const float *vertices, int64_t n_vertices, int32_t n_jobs, const PgrPoseErrorJob *jobs, float *adi,
+                     void *workspace, size_t workspace_bytes, void *stream);
+
 /* Gradients returned by pgr_backward / pgr_backward_batch (device pointers, any may be NULL = not wanted). */
 typedef struct PgrGradOutputs {
     float *means2d;              /* [n,3] screen-space mean, NDC-scaled (what viewspace_points.grad receives) */

@@ -130,6 +130,16 @@ class PgrGtInfoJob(C.Structure):
 PGR_GT_INFO_STATS = 11
 
 
+class PgrPoseErrorJob(C.Structure):
+    _fields_ = [("vertex_first", C.c_int32), ("vertex_count", C.c_int32), ("sym_first", C.c_int32), ("sym_count", C.c_int32),
+                ("R_est", C.c_double * 9), ("t_est", C.c_double * 3), ("R_gt", C.c_double * 9), ("t_gt", C.c_double * 3),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
+
+
+PGR_POSE_ERRORS = 6          # mssd, mspd, add, proj, re, te
+PGR_POSE_SYM_CHUNK = 4       # include/pegasus_raster.h PGR_POSE_SYM_CHUNK
+
+
 # every symbol include/pegasus_raster.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "pgr_abi_version": (C.c_int32, []),
@@ -236,6 +246,11 @@ SYMBOLS = {
     "pgr_bop_gt_info": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                     C.c_int32, C.c_int32, C.c_int32, C.POINTER(PgrGtInfoJob), C.c_float, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pgr_pose_errors": (C.c_int32, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(PgrPoseErrorJob),
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pgr_pose_adi_workspace_bytes": (C.c_size_t, [C.c_int32, C.POINTER(PgrPoseErrorJob)]),
+    "pgr_pose_adi": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(PgrPoseErrorJob), C.c_void_p, C.c_void_p,
+                                 C.c_size_t, C.c_void_p]),
 }
 
 _lib = None

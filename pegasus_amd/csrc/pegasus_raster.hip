@@ -24,6 +24,7 @@
 #include "compose.hip.h"
 #include "composite.hip.h"
 #include "pgr_common.h"
+#include "poseerr.hip.h"
 #include "preprocess.hip.h"
 #include "tilebin.hip.h"
 #include "train.hip.h"
@@ -1425,6 +1426,103 @@ int32_t pgr_bop_gt_info(const float* canvases, int32_t n_slots, int32_t canvas_w
         gt_info_kernel<<<dim3(blocks_x, (unsigned)T.count), 256, 0, stream>>>(T, canvases, scene_depth, mask, mask_visib, stats);
     }
     return hip_ok(hipGetLastError(), "bop_gt_info launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+// ---- BOP pose errors (poseerr.hip.h) -----------------------------------------------------------------------------------
+namespace {
+bool pose_vertices_ok(const float* vertices, int64_t n_vertices, int32_t n_jobs, const PgrPoseErrorJob* jobs) {
+    if (n_jobs < 0 || n_vertices < 0 || (n_jobs > 0 && (!jobs || !vertices))) return false;
+    for (int32_t k = 0; k < n_jobs; ++k) {
+        const PgrPoseErrorJob& j = jobs[k];
+        if (j.vertex_first < 0 || j.vertex_count <= 0 || (int64_t)j.vertex_first + j.vertex_count > n_vertices) return false;
+    }
+    return true;
+}
+int64_t adi_groups(const PgrPoseErrorJob& j) { return ((int64_t)j.vertex_count + ADI_TILE - 1) / ADI_TILE; }
+}  // namespace
+
+int32_t pgr_pose_errors(const float* vertices, int64_t n_vertices, const double* syms, int64_t n_syms, int32_t n_jobs,
+                        const PgrPoseErrorJob* jobs, float* errors, double* re_te, void* stream_v) {
+    if (!pose_vertices_ok(vertices, n_vertices, n_jobs, jobs) || n_syms < 0 || (n_jobs > 0 && (!syms || !errors)))
+        return PGR_ERR_INVALID_ARGUMENT;
+    for (int32_t k = 0; k < n_jobs; ++k) {
+        const PgrPoseErrorJob& j = jobs[k];
+        if (j.sym_first < 0 || j.sym_count <= 0 || (int64_t)j.sym_first + j.sym_count > n_syms) return PGR_ERR_INVALID_ARGUMENT;
+    }
+    if (n_jobs == 0) return PGR_OK;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    pose_init_kernel<<<(n_jobs * PGR_POSE_ERRORS + 255) / 256, 256, 0, stream>>>(errors, n_jobs);
+    for (int32_t k0 = 0; k0 < n_jobs; k0 += PERR_JOBS_PER_LAUNCH) {
+        PoseErrJobTable T{};
+        T.count = std::min(PERR_JOBS_PER_LAUNCH, n_jobs - k0);
+        T.first = k0;
+        uint32_t blocks = 0;
+        for (int32_t k = 0; k < T.count; ++k) {
+            const PgrPoseErrorJob& j = jobs[k0 + k];
+            PoseErrJobDev& d = T.job[k];
+            d.v0 = j.vertex_first; d.nv = j.vertex_count; d.s0 = j.sym_first; d.ns = j.sym_count;
+            std::memcpy(d.Re, j.R_est, sizeof(d.Re));
+            std::memcpy(d.te, j.t_est, sizeof(d.te));
+            std::memcpy(d.Rg, j.R_gt, sizeof(d.Rg));
+            std::memcpy(d.tg, j.t_gt, sizeof(d.tg));
+            d.fx = (float)j.fx; d.fy = (float)j.fy; d.cx = (float)j.cx; d.cy = (float)j.cy;
+            d.block0 = blocks;
+            blocks += (uint32_t)((j.sym_count + PERR_SYM_CHUNK - 1) / PERR_SYM_CHUNK);
+        }
+        pose_errors_kernel<<<blocks, PERR_THREADS, 0, stream>>>(T, vertices, syms, errors, re_te);
+    }
+    return hip_ok(hipGetLastError(), "pose_errors launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+size_t pgr_pose_adi_workspace_bytes(int32_t n_jobs, const PgrPoseErrorJob* jobs) {
+    if (n_jobs <= 0 || !jobs) return 0;
+    int64_t groups = 0;
+    for (int32_t k = 0; k < n_jobs; ++k) {
+        if (jobs[k].vertex_count <= 0) return 0;
+        groups += adi_groups(jobs[k]);
+    }
+    return groups > INT32_MAX ? 0 : align_up((size_t)groups * sizeof(double));
+}
+
+int32_t pgr_pose_adi(const float* vertices, int64_t n_vertices, int32_t n_jobs, const PgrPoseErrorJob* jobs, float* adi,
+                     void* workspace, size_t workspace_bytes, void* stream_v) {
+    if (!pose_vertices_ok(vertices, n_vertices, n_jobs, jobs) || (n_jobs > 0 && !adi)) return PGR_ERR_INVALID_ARGUMENT;
+    if (n_jobs == 0) return PGR_OK;
+    const size_t need = pgr_pose_adi_workspace_bytes(n_jobs, jobs);
+    if (need == 0) return PGR_ERR_INVALID_ARGUMENT;
+    if (!workspace || workspace_bytes < need) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    auto* partials = static_cast<double*>(workspace);
+    uint32_t part = 0;
+    for (int32_t k0 = 0; k0 < n_jobs; k0 += ADI_JOBS_PER_LAUNCH) {
+        AdiJobTable T{};
+        T.count = std::min(ADI_JOBS_PER_LAUNCH, n_jobs - k0);
+        T.first = k0;
+        uint32_t blocks = 0;
+        for (int32_t k = 0; k < T.count; ++k) {
+            const PgrPoseErrorJob& j = jobs[k0 + k];
+            AdiJobDev& d = T.job[k];
+            d.v0 = j.vertex_first; d.nv = j.vertex_count;
+            const double* Re = j.R_est;
+            const double* Rg = j.R_gt;
+            const bool same_R = std::memcmp(Re, Rg, sizeof(j.R_est)) == 0;    // R^T R of a rotation: the identity, exactly
+            const double dt[3] = {j.t_gt[0] - j.t_est[0], j.t_gt[1] - j.t_est[1], j.t_gt[2] - j.t_est[2]};
+            for (int r = 0; r < 3; ++r) {
+                for (int c = 0; c < 3; ++c)
+                    d.M[3 * r + c] = same_R ? (r == c ? 1.f : 0.f)
+                                            : (float)((Re[r] * Rg[c] + Re[3 + r] * Rg[3 + c]) + Re[6 + r] * Rg[6 + c]);
+                d.c[r] = (float)((Re[r] * dt[0] + Re[3 + r] * dt[1]) + Re[6 + r] * dt[2]);
+            }
+            d.block0 = blocks;
+            d.part0 = part;
+            const uint32_t g = (uint32_t)adi_groups(j);
+            blocks += g;
+            part += g;
+        }
+        pose_adi_kernel<<<blocks, ADI_TILE, 0, stream>>>(T, vertices, partials);
+        pose_adi_mean_kernel<<<1, 64, 0, stream>>>(T, partials, adi);
+    }
+    return hip_ok(hipGetLastError(), "pose_adi launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
 }
 
 // ---- training step: fused L1 + D-SSIM loss, Adam over all parameter groups, densification statistics (train.hip.h) ------

@@ -329,9 +329,11 @@ def _diameter(points: np.ndarray) -> float:
     return math.sqrt(best)
 
 
-def models_info(mesh: Mesh) -> dict:
+def models_info(mesh: Mesh, symmetries_discrete=None, symmetries_continuous=None) -> dict:
     """The BOP models_info.json fields of ``mesh`` (in its units): diameter (largest distance between two vertices of
-    the convex hull), min_x/y/z and size_x/y/z of the bounding box."""
+    the convex hull), min_x/y/z and size_x/y/z of the bounding box.  ``symmetries_discrete`` (a list of 4x4 transforms as 16
+    numbers, row-major, whose 3x3 part must be a rotation to 1e-6) and ``symmetries_continuous`` (a list of {'axis': [3],
+    'offset': [3]}, or of 6 numbers ax ay az ox oy oz) are passed through in the toolkit's layout when given."""
     v = mesh.vertices.astype(np.float64)
     lo, hi = v.min(axis=0), v.max(axis=0)
     info = {"diameter": _diameter(v)}
@@ -339,6 +341,32 @@ def models_info(mesh: Mesh) -> dict:
         info[f"min_{name}"] = float(lo[a])
     for a, name in enumerate("xyz"):
         info[f"size_{name}"] = float(hi[a] - lo[a])
+    if symmetries_discrete:
+        out = []
+        for sym in symmetries_discrete:
+            m = np.asarray(sym, np.float64).reshape(-1)
+            if m.size != 16:
+                raise ValueError(f"a discrete symmetry is 16 numbers (4x4, row-major), got {m.size}")
+            R = m.reshape(4, 4)[:3, :3]
+            if np.abs(R.dot(R.T) - np.eye(3)).max() > 1e-6 or abs(np.linalg.det(R) - 1.0) > 1e-6:
+                raise ValueError("the 3x3 part of a discrete symmetry must be a rotation (to 1e-6)")
+            out.append([float(x) for x in m])
+        info["symmetries_discrete"] = out
+    if symmetries_continuous:
+        out = []
+        for sym in symmetries_continuous:
+            if isinstance(sym, dict):
+                axis, offset = sym["axis"], sym["offset"]
+            else:
+                flat = np.asarray(sym, np.float64).reshape(-1)
+                if flat.size != 6:
+                    raise ValueError(f"a continuous symmetry is 6 numbers (axis, offset), got {flat.size}")
+                axis, offset = flat[:3], flat[3:]
+            axis, offset = [float(x) for x in axis], [float(x) for x in offset]
+            if len(axis) != 3 or len(offset) != 3 or not any(axis):
+                raise ValueError("a continuous symmetry needs a non-zero axis [3] and an offset [3]")
+            out.append({"axis": axis, "offset": offset})
+        info["symmetries_continuous"] = out
     return info
 
 
@@ -369,7 +397,22 @@ def _parser():
     p.add_argument("--resolution", type=int, default=256)
     p.add_argument("--n_views", type=int, default=96)
     p.add_argument("--image_size", type=int, default=512)
+    p.add_argument("--sym_continuous", type=float, nargs=6, action="append", metavar=("AX", "AY", "AZ", "OX", "OY", "OZ"),
+                   help="a continuous rotational symmetry: axis and a point on it, in model units (repeatable)")
+    p.add_argument("--sym_discrete", type=float, nargs=16, action="append", metavar="M",
+                   help="a discrete symmetry: a 4x4 transform, row-major, in model units (repeatable)")
     return p
+
+
+def scaled_symmetries(sym_discrete, sym_continuous, scale: float):
+    """The command line's symmetries (model units) in the units of the written model: translations and offsets times scale."""
+    disc = []
+    for m in sym_discrete or []:
+        m = np.asarray(m, np.float64).reshape(4, 4).copy()
+        m[:3, 3] *= scale
+        disc.append(m.reshape(16).tolist())
+    cont = [{"axis": list(c[:3]), "offset": [float(o) * scale for o in c[3:]]} for c in sym_continuous or []]
+    return disc or None, cont or None
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:
@@ -381,7 +424,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     write_ply(out / "models" / f"{name}.ply", mesh, scale=a.scale)
     info_path = out / "models" / "models_info.json"
     info = json.loads(info_path.read_text()) if info_path.exists() else {}
-    info[str(a.obj_id)] = models_info(mesh.scaled(a.scale))
+    disc, cont = scaled_symmetries(a.sym_discrete, a.sym_continuous, a.scale)
+    info[str(a.obj_id)] = models_info(mesh.scaled(a.scale), disc, cont)
     info_path.write_text(json.dumps(dict(sorted(info.items(), key=lambda kv: int(kv[0]))), indent=2) + "\n")
     write_obj(out / "urdf" / f"{name}.obj", mesh)
     write_urdf(out / "urdf" / f"{name}.urdf", f"{name}.obj", mesh, a.mass)
