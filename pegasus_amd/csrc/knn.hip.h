@@ -2,9 +2,14 @@
 // simple_knn._C.distCUDA2, used once per scene by GaussianModel.create_from_pcd to size the initial splats,
 // /root/reference/src/gs/gaussian_model.py:25,147).  Not on the render path.
 //
-// Exact 3-NN through a uniform grid built on the device (no host round trip): bounding box (ordered-int atomics) ->
+// 3-NN through a uniform grid built on the device (no host round trip): bounding box (ordered-int atomics) ->
 // cell histogram -> scan -> counting-sort of the points by cell -> per point, shells of cells of growing Chebyshev
-// radius until the third-best distance is inside the shell already covered.
+// radius until the third-best distance is inside the shell already covered.  The search stops once that distance is at
+// most 0.99999 r cells.  That is not an exact 3-NN: a point's cell index is itself rounded (a float subtract and a
+// multiply, about 1e-5 of a cell at index 127), so a point the index arithmetic puts r + 1 cells away can be nearer than
+// 0.99999 r cells, by about 2e-6 of a cell at 128 cells per axis.  What the margin guarantees: a neighbour the search
+// misses lies no nearer than the rounding lets it, so a reported squared distance exceeds the true one by less than
+// 1 - 0.99999^2 = 2e-5 of itself, and the mean of the three by less than that (7e-6 when only the third is affected).
 #pragma once
 #include "pgr_common.h"
 

@@ -299,26 +299,7 @@ def test_batch_ex_sums_single_view_ex(monkeypatch, gpu_device, V):
 
 
 # ---- 6. the masked loss -----------------------------------------------------------------------------------------------------
-def _reference_masked(x, a, y, m, bg, lam, lam_a):
-    import torch
-    import torch.nn.functional as F
-    xs = x.double().clone().requires_grad_(True)
-    as_ = a.double().clone().requires_grad_(True)
-    md = m.double().reshape(1, *m.shape[-2:])
-    yt = y.double() * md + bg.double().reshape(3, 1, 1) * (1.0 - md)
-    k = torch.exp(-(torch.arange(11, dtype=torch.float64) - 5) ** 2 / (2 * 1.5 ** 2))
-    k = k / k.sum()
-    win = (k[:, None] * k[None, :]).expand(3, 1, 11, 11).contiguous()
-    blur = lambda t: F.conv2d(t[None], win, padding=5, groups=3)[0]
-    mx, my = blur(xs), blur(yt)
-    sxx, syy, sxy = blur(xs * xs) - mx * mx, blur(yt * yt) - my * my, blur(xs * yt) - mx * my
-    C1, C2 = 0.01 ** 2, 0.03 ** 2
-    ssim = ((2 * mx * my + C1) * (2 * sxy + C2) / ((mx * mx + my * my + C1) * (sxx + syy + C2))).mean()
-    l1 = (xs - yt).abs().mean()
-    al1 = (as_ - md).abs().mean()
-    loss = (1 - lam) * l1 + lam * (1 - ssim) + lam_a * al1
-    loss.backward()
-    return float(loss.detach()), float(l1.detach()), float(ssim.detach()), float(al1.detach()), xs.grad, as_.grad
+from train_reference import masked_loss_f64 as _reference_masked      # noqa: E402  (float64 autograd, shared)
 
 
 @pytest.mark.parametrize("hw,lam,lam_a", [((37, 53), 0.2, 0.5), ((16, 16), 0.0, 1.0), ((70, 45), 1.0, 0.3),

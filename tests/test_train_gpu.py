@@ -15,24 +15,7 @@ ROOT = Path(__file__).resolve().parents[1]
 
 
 # ---- loss -------------------------------------------------------------------------------------------------------------------
-def _reference_loss(x, y, lam):
-    """The 3DGS loss in float64 on the CPU: F.conv2d with an 11x11 Gaussian window, padding 5, groups 3."""
-    import torch
-    import torch.nn.functional as F
-    x = x.detach().cpu().double().requires_grad_(True)
-    y = y.detach().cpu().double()
-    g = torch.tensor([math.exp(-((k - 5) ** 2) / (2 * 1.5 ** 2)) for k in range(11)], dtype=torch.float64)
-    g = g / g.sum()
-    w = (g[:, None] @ g[None, :]).expand(3, 1, 11, 11).contiguous()
-    blur = lambda t: F.conv2d(t[None], w, padding=5, groups=3)[0]
-    mx, my = blur(x), blur(y)
-    sxx, syy, sxy = blur(x * x) - mx * mx, blur(y * y) - my * my, blur(x * y) - mx * my
-    C1, C2 = 0.01 ** 2, 0.03 ** 2
-    s = ((2 * mx * my + C1) * (2 * sxy + C2)) / ((mx * mx + my * my + C1) * (sxx + syy + C2))
-    l1 = (x - y).abs().mean()
-    loss = (1 - lam) * l1 + lam * (1 - s.mean())
-    loss.backward()
-    return float(loss.detach()), x.grad, float(l1.detach()), float(s.mean().detach())
+from train_reference import loss_f64 as _reference_loss      # noqa: E402  (float64 autograd, shared with the kernel tests)
 
 
 @pytest.mark.parametrize("hw,lams", [((1, 1), (0.0, 0.2, 1.0)), ((17, 13), (0.0, 0.2, 1.0)), ((255, 257), (0.0, 0.2, 1.0)),
