@@ -152,7 +152,8 @@ typedef struct PgrSemantic {
                                     n_env >= 0, k_objects > 0, outs[v].sem_color non-NULL for every view, mask_colors
                                     non-NULL if any view passes sem_masks */
 
-/* Device pointers into one view's slice of a workspace, for stage-level parity tests and for backward. */
+/* Device pointers to one view's share of a workspace -- its slice and, for num_instances, its two status words in the
+ * batch header -- for stage-level parity tests and for backward. */
 typedef struct PgrWorkspaceView {
     const float *splats;         /* [n,12] per-Gaussian record: x, y, conic A, B, C, opacity, B/C, B/A, r, g, b, depth
                                     (defined only for Gaussians with a non-empty rectangle) */
@@ -160,7 +161,7 @@ typedef struct PgrWorkspaceView {
                                     Written only for views rendered WITH a radii output. */
     const uint32_t *gauss_sorted;/* [num_instances] Gaussian index, tile-major, (depth, index) ascending per tile */
     const uint32_t *ranges;      /* [tiles,2] start,end into gauss_sorted */
-    const uint32_t *num_instances; /* [0] listed instances, [1] overflow flag */
+    const uint32_t *num_instances; /* [0] listed instances, [1] overflow flag: the words the forward of this view wrote */
 } PgrWorkspaceView;
 
 int32_t pgr_abi_version(void);

@@ -310,6 +310,20 @@ def stream_ptr(device) -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def enqueue(name: str, device, *args, after_stream=()) -> int:
+    """THE way the package calls an entry point that takes a stream: with ``device`` current, on torch's current stream of
+    ``device`` at the time of the call, which goes behind ``args`` (``after_stream``: what the entry takes behind its
+    stream).  Returns the raw status: callers that handle one themselves (instance overflow) use this, all others ``call``."""
+    import torch
+    with torch.cuda.device(device):
+        return getattr(lib(), name)(*args, stream_ptr(device), *after_stream)
+
+
+def call(name: str, device, *args, after_stream=()):
+    """``enqueue`` whose status other than PGR_OK raises, naming the entry."""
+    check(enqueue(name, device, *args, after_stream=after_stream), name)
+
+
 def check(status: int, what: str = "pegasus_raster"):
     if status == PGR_OK:
         return

@@ -56,7 +56,6 @@ def pose_table(poses) -> np.ndarray:
 
 def compose_object(xyz, rot, f_rest, pose: _lib.PgrObjectPose, out_xyz, out_rot, out_rest, out_rest_stride=None):
     """Thin wrapper over pgr_compose_object for torch device tensors (f_rest [n,R,3] contiguous)."""
-    L = _lib.lib()
     if xyz.device.type != "cuda":
         raise RuntimeError("compose_object needs HIP device tensors; there is no CPU path")
     n = int(xyz.shape[0])
@@ -65,10 +64,8 @@ def compose_object(xyz, rot, f_rest, pose: _lib.PgrObjectPose, out_xyz, out_rot,
     if out_rest_stride is None:
         out_rest_stride = in_stride
     p = _lib.ptr
-    with torch.cuda.device(xyz.device):
-        _lib.check(L.pgr_compose_object(n, p(xyz), p(rot), p(f_rest), n_rest, in_stride, C.byref(pose), p(out_xyz),
-                                        p(out_rot), p(out_rest), int(out_rest_stride), _lib.stream_ptr(xyz.device)),
-                   "pgr_compose_object")
+    _lib.call("pgr_compose_object", xyz.device, n, p(xyz), p(rot), p(f_rest), n_rest, in_stride, C.byref(pose), p(out_xyz),
+              p(out_rot), p(out_rest), int(out_rest_stride))
 
 
 class SceneComposer:

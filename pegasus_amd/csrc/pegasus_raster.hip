@@ -39,7 +39,13 @@ static bool hip_ok(hipError_t e, const char* what) {
     return false;
 }
 
-static size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
+static constexpr size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
+
+// Hands out consecutive slices of a buffer, each aligned to 256 B; a slice of zero bytes still takes one unit.
+struct Carver {
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t o = off; off += align_up(bytes ? bytes : 1); return o; }
+};
 
 // Calls of one or two views (the drop-in GaussianRasterizer: one camera per call) cannot fill the chip; their launches are
 // latency-bound and get a few arrangements of their own (fewer, fuller launches).  Results never depend on it.
@@ -72,20 +78,17 @@ static Layout make_layout(int32_t n, int32_t width, int32_t height, int64_t max_
     L.grid_y = gy;
     L.n_blocks = (int)((N + PRE_BLOCK - 1) / PRE_BLOCK);
     L.n_chunks = (int)((N + BIN_CHUNK - 1) / BIN_CHUNK);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes ? bytes : 1); return o; };
-    L.cam = take(sizeof(CameraDev));
-    L.counters = take(64);
-    L.splats = take(N * 48);
-    L.radii = take(N * 4);
-    L.rects = take(N * 8);
-    L.crects = take(N * 8);
-    L.rel = take((size_t)L.n_chunks * L.tiles * 4);
-    L.ranges = take((size_t)L.tiles * 8);
-    L.bucket = take(I * 8);
-    L.alt = take(I * 8);
-    L.gauss_sorted = take(I * 4);
-    L.total = off;
+    Carver c;
+    L.splats = c.take(N * 48);
+    L.radii = c.take(N * 4);
+    L.rects = c.take(N * 8);
+    L.crects = c.take(N * 8);
+    L.rel = c.take((size_t)L.n_chunks * L.tiles * 4);
+    L.ranges = c.take((size_t)L.tiles * 8);
+    L.bucket = c.take(I * 8);
+    L.alt = c.take(I * 8);
+    L.gauss_sorted = c.take(I * 4);
+    L.total = c.off;
     L.max_instances = (int64_t)I;
     return L;
 }
@@ -103,14 +106,65 @@ static int check_scene(const PgrScene* s) {
     return PGR_OK;
 }
 
-// Per-view slice of a workspace.
+// Batch header placed in front of the per-view slices.
+// The host scratch: the image of the three pointer tables (laid out exactly as in the workspace's `tables`: one H2D copy),
+// then the status words read back -- per view [0] listed instances, [1] overflow flag.
+struct HostTables { size_t view_table, bin_table, pre_table, tables_bytes, status, total; };
+
+static HostTables host_tables(int n_views) {
+    HostTables T{};
+    T.bin_table = T.view_table + align_up((size_t)n_views * sizeof(ViewEntry), 16);
+    T.pre_table = T.bin_table + align_up((size_t)n_views * sizeof(BinView), 16);
+    T.tables_bytes = T.status = T.pre_table + align_up((size_t)n_views * sizeof(PreOut), 16);
+    T.total = T.status + (size_t)n_views * 8;
+    return T;
+}
+
+// Batch header placed in front of the per-view slices.
+struct BatchLayout {
+    size_t tables, cams, status, tile_counts, order_state, work_order, long_list, tie_inv, vis, obj_u8, views, total;
+    int n_groups, vis_words;
+    HostTables host;             // offsets inside `tables`
+    size_t order_slots;
+    size_t seg_cap;              // entries of the segment queue (behind the SORT_TIERS tier queues)
+    size_t per_view;
+};
+
+static BatchLayout make_batch_layout(const Layout& L, int n_views, size_t n_scene) {
+    BatchLayout B{};
+    Carver c;
+    B.host = host_tables(n_views);
+    B.tables = c.take(B.host.tables_bytes);
+    B.cams = c.take((size_t)n_views * sizeof(CameraDev));
+    B.status = c.take((size_t)n_views * 8);        // per view: [0] listed instances, [1] overflow flag
+    B.tile_counts = c.take((size_t)n_views * L.tiles * 8);   // [tile_count u32 | obj_last u32] x views: one memset
+    B.order_state = c.take(ORDER_STATE_WORDS * 4);
+    // NUM_XCD interleaved streams; each holds the items of its band of tile rows for every view
+    B.order_slots = (size_t)NUM_XCD * max_band_rows(L.grid_y) * L.grid_x * ITEMS_PER_TILE * n_views;
+    B.work_order = c.take(B.order_slots * 4);
+    // the sort queues: one per tier, and the segment queue of the split pre-pass -- a list of n > SORT_WINDOW_MAX keys yields
+    // at most n / SEG_HALF + 2 <= n (1 / 4096 + 2 / 15872) = n / 2702 segments, and a view's lists hold max_instances keys
+    B.seg_cap = (size_t)n_views * ((size_t)(L.max_instances > 0 ? L.max_instances : 0) / 2702 + 2);
+    B.long_list = c.take(((size_t)n_views * L.tiles * SORT_TIERS + B.seg_cap) * sizeof(uint4));
+    B.tie_inv = c.take((size_t)n_scene * 4);    // inverse of PgrScene::tie_index (filled only when one is given)
+    B.n_groups = (int)((n_scene + WAVE - 1) / WAVE);
+    B.vis_words = (n_views + 31) / 32;
+    B.vis = c.take((size_t)B.n_groups * B.vis_words * 4);
+    B.obj_u8 = c.take(n_scene);                // object ids as bytes (fused semantic pass)
+    B.views = c.off;
+    B.per_view = align_up(L.total);
+    B.total = B.views + (size_t)n_views * B.per_view;
+    return B;
+}
+
+// One view's share of a workspace: its slice behind the batch header, and its entries of the header's per-view arrays
+// (the cameras of a batch are contiguous: the preprocess walks them; so are the status words: one D2H copy per batch).
 struct ViewWs {
-    CameraDev* cam;
-    uint32_t* counters;
+    CameraDev* cam;       // batch header
+    uint32_t* counters;   // batch header: [0] listed instances, [1] overflow flag
     float4* splats;   // [n,3] per-Gaussian records
-    int32_t* radii;   // per-view home of radii when the caller passes no radii output
     uint2 *rects, *crects;
-    uint32_t *tile_count, *rel;
+    uint32_t *tile_count, *rel;   // tile_count: batch header
     uint2* ranges;
     uint2* bucket;
     uint64_t* alt;
@@ -118,74 +172,52 @@ struct ViewWs {
     uint32_t* obj_last;   // batch header
 };
 
-static ViewWs carve(char* ws, const Layout& L) {
-    ViewWs v;
-    v.cam = reinterpret_cast<CameraDev*>(ws + L.cam);
-    v.counters = reinterpret_cast<uint32_t*>(ws + L.counters);
-    v.splats = reinterpret_cast<float4*>(ws + L.splats);
-    v.radii = reinterpret_cast<int32_t*>(ws + L.radii);
-    v.rects = reinterpret_cast<uint2*>(ws + L.rects);
-    v.crects = reinterpret_cast<uint2*>(ws + L.crects);
-    v.tile_count = nullptr;   // lives in the batch header (BatchLayout::tile_counts)
-    v.rel = reinterpret_cast<uint32_t*>(ws + L.rel);
-    v.ranges = reinterpret_cast<uint2*>(ws + L.ranges);
-    v.bucket = reinterpret_cast<uint2*>(ws + L.bucket);
-    v.alt = reinterpret_cast<uint64_t*>(ws + L.alt);
-    v.gauss_sorted = reinterpret_cast<uint32_t*>(ws + L.gauss_sorted);
-    v.obj_last = nullptr;
-    return v;
+static ViewWs view_slice(char* ws, const Layout& L, const BatchLayout& B, int n_views, int v) {
+    char* const slice = ws + B.views + (size_t)v * B.per_view;
+    auto* const tile_counts = reinterpret_cast<uint32_t*>(ws + B.tile_counts);
+    ViewWs w;
+    w.cam = reinterpret_cast<CameraDev*>(ws + B.cams) + v;
+    w.counters = reinterpret_cast<uint32_t*>(ws + B.status) + 2 * v;
+    w.splats = reinterpret_cast<float4*>(slice + L.splats);
+    w.rects = reinterpret_cast<uint2*>(slice + L.rects);
+    w.crects = reinterpret_cast<uint2*>(slice + L.crects);
+    w.tile_count = tile_counts + (size_t)v * L.tiles;
+    w.rel = reinterpret_cast<uint32_t*>(slice + L.rel);
+    w.ranges = reinterpret_cast<uint2*>(slice + L.ranges);
+    w.bucket = reinterpret_cast<uint2*>(slice + L.bucket);
+    w.alt = reinterpret_cast<uint64_t*>(slice + L.alt);
+    w.gauss_sorted = reinterpret_cast<uint32_t*>(slice + L.gauss_sorted);
+    w.obj_last = tile_counts + (size_t)(n_views + v) * L.tiles;
+    return w;
 }
 
-// Batch header placed in front of the per-view slices.
-struct BatchLayout {
-    size_t tables, cams, status, tile_counts, order_state, work_order, long_list, tie_inv, vis, obj_u8, views, total;
-    int n_groups, vis_words;
-    size_t view_table_off, bin_table_off, pre_table_off, tables_bytes;   // inside `tables` (one H2D copy)
-    size_t order_slots;
-    size_t seg_cap;              // entries of the segment queue (behind the SORT_TIERS tier queues)
-    size_t per_view;
-};
-
-// Host-side image of the tables + the status words read back, laid out exactly as on the device.
-static size_t host_scratch_bytes(int n_views) {
-    return align_up((size_t)n_views * sizeof(ViewEntry), 16) + align_up((size_t)n_views * sizeof(BinView), 16) +
-           align_up((size_t)n_views * sizeof(PreOut), 16) + (size_t)n_views * 8;
+static bool camera_ok(const PgrCamera& c) {      // what every entry that packs cameras asks of one
+    return c.image_width > 0 && c.image_height > 0 && c.tanfovx > 0.f && c.tanfovy > 0.f && c.viewmatrix && c.projmatrix &&
+           c.campos && c.bg;
 }
 
-static BatchLayout make_batch_layout(const Layout& L, int n_views, size_t n_scene) {
-    BatchLayout B{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes ? bytes : 1); return o; };
-    B.view_table_off = 0;
-    B.bin_table_off = B.view_table_off + align_up((size_t)n_views * sizeof(ViewEntry), 16);
-    B.pre_table_off = B.bin_table_off + align_up((size_t)n_views * sizeof(BinView), 16);
-    B.tables_bytes = B.pre_table_off + align_up((size_t)n_views * sizeof(PreOut), 16);
-    B.tables = take(B.tables_bytes);
-    B.cams = take((size_t)n_views * sizeof(CameraDev));
-    B.status = take((size_t)n_views * 8);          // per view: [0] listed instances, [1] overflow flag
-    B.tile_counts = take((size_t)n_views * L.tiles * 8);   // [tile_count u32 | obj_last u32] x views: one memset
-    B.order_state = take(ORDER_STATE_WORDS * 4);
-    // NUM_XCD interleaved streams; each holds the items of its band of tile rows for every view
-    B.order_slots = (size_t)NUM_XCD * max_band_rows(L.grid_y) * L.grid_x * ITEMS_PER_TILE * n_views;
-    B.work_order = take(B.order_slots * 4);
-    // the sort queues: one per tier, and the segment queue of the split pre-pass -- a list of n > SORT_WINDOW_MAX keys yields
-    // at most n / SEG_HALF + 2 <= n (1 / 4096 + 2 / 15872) = n / 2702 segments, and a view's lists hold max_instances keys
-    B.seg_cap = (size_t)n_views * ((size_t)(L.max_instances > 0 ? L.max_instances : 0) / 2702 + 2);
-    B.long_list = take(((size_t)n_views * L.tiles * SORT_TIERS + B.seg_cap) * sizeof(uint4));
-    B.tie_inv = take((size_t)n_scene * 4);     // inverse of PgrScene::tie_index (filled only when one is given)
-    B.n_groups = (int)((n_scene + WAVE - 1) / WAVE);
-    B.vis_words = (n_views + 31) / 32;
-    B.vis = take((size_t)B.n_groups * B.vis_words * 4);
-    B.obj_u8 = take(n_scene);                  // object ids as bytes (fused semantic pass)
-    B.views = off;
-    B.per_view = align_up(L.total);
-    B.total = off + (size_t)n_views * B.per_view;
-    return B;
+// The launch argument that packs up to CAM_PACK_MAX cameras (pack_camera: preprocess.hip.h).
+static CamPack pack_cameras(const PgrCamera* cams, int cnt, bool with_depth_mode) {
+    CamPack cp;
+    for (int k = 0; k < cnt; ++k) {
+        const PgrCamera& c = cams[k];
+        cp.view[k] = c.viewmatrix; cp.proj[k] = c.projmatrix; cp.campos[k] = c.campos; cp.bg[k] = c.bg;
+        cp.tanfovx[k] = c.tanfovx; cp.tanfovy[k] = c.tanfovy; cp.depth_mode[k] = with_depth_mode ? c.depth_mode : 0;
+    }
+    return cp;
+}
+
+static PgrRecordLayout record_layout(size_t P, int k) {       // one view's frame record (pgr_frame_record_layout)
+    PgrRecordLayout R;
+    R.off_rgb = 0;
+    R.off_depth = (int64_t)align_up(3 * P, 16);
+    R.off_masks = R.off_depth + (int64_t)align_up(2 * P, 16);
+    R.bytes = R.off_masks + (int64_t)align_up((size_t)((k + 7) / 8) * P, 16);
+    return R;
 }
 
 static int check_camera(const PgrCamera* cam, const PgrOutputs* out, bool layered = false) {
-    if (!cam || !out || cam->image_width <= 0 || cam->image_height <= 0 || !(cam->tanfovx > 0.f) ||
-        !(cam->tanfovy > 0.f) || !cam->viewmatrix || !cam->projmatrix || !cam->campos || !cam->bg ||
+    if (!cam || !out || !camera_ok(*cam) ||
         // color + depth, or (records-only view) the frame record alone; a layered call writes mask planes only
         (layered ? !out->sem_masks : !((out->color && out->depth) || (out->record && !out->color && !out->depth))) ||
         (cam->depth_mode != PGR_DEPTH_EXPECTED && cam->depth_mode != PGR_DEPTH_NORMALIZED))
@@ -197,24 +229,14 @@ static int check_camera(const PgrCamera* cam, const PgrOutputs* out, bool layere
 }
 
 static int zero_outputs(const PgrOutputs* out, size_t P, hipStream_t stream, int n_masks) {
-    if (out->color && !hip_ok(hipMemsetAsync(out->color, 0, 3 * P * sizeof(float), stream), "memset color"))
-        return PGR_ERR_LAUNCH_FAILURE;
-    if (out->depth && !hip_ok(hipMemsetAsync(out->depth, 0, P * sizeof(float), stream), "memset depth"))
-        return PGR_ERR_LAUNCH_FAILURE;
-    if (out->sem_masks && n_masks > 0 && !hip_ok(hipMemsetAsync(out->sem_masks, 0, (size_t)n_masks * P, stream), "memset masks"))
-        return PGR_ERR_LAUNCH_FAILURE;
-    if (out->record) {
-        const size_t bytes = align_up(3 * P, 16) + align_up(2 * P, 16) + align_up((size_t)((n_masks + 7) / 8) * P, 16);
-        if (!hip_ok(hipMemsetAsync(out->record, 0, bytes, stream), "memset record")) return PGR_ERR_LAUNCH_FAILURE;
-    }
-    if (out->final_T && !hip_ok(hipMemsetAsync(out->final_T, 0, P * sizeof(float), stream), "memset T"))
-        return PGR_ERR_LAUNCH_FAILURE;
-    if (out->n_contrib && !hip_ok(hipMemsetAsync(out->n_contrib, 0, P * sizeof(uint32_t), stream), "memset n"))
-        return PGR_ERR_LAUNCH_FAILURE;
-    if (out->sem_color && !hip_ok(hipMemsetAsync(out->sem_color, 0, 3 * P * sizeof(float), stream), "memset sem"))
-        return PGR_ERR_LAUNCH_FAILURE;
-    if (out->sem_depth && !hip_ok(hipMemsetAsync(out->sem_depth, 0, P * sizeof(float), stream), "memset semd"))
-        return PGR_ERR_LAUNCH_FAILURE;
+    const struct { void* p; size_t bytes; const char* what; } fills[] = {
+        {out->color, 3 * P * sizeof(float), "memset color"}, {out->depth, P * sizeof(float), "memset depth"},
+        {n_masks > 0 ? out->sem_masks : nullptr, (size_t)n_masks * P, "memset masks"},
+        {out->record, (size_t)record_layout(P, n_masks).bytes, "memset record"},
+        {out->final_T, P * sizeof(float), "memset T"}, {out->n_contrib, P * sizeof(uint32_t), "memset n"},
+        {out->sem_color, 3 * P * sizeof(float), "memset sem"}, {out->sem_depth, P * sizeof(float), "memset semd"}};
+    for (const auto& f : fills)
+        if (f.p && !hip_ok(hipMemsetAsync(f.p, 0, f.bytes, stream), f.what)) return PGR_ERR_LAUNCH_FAILURE;
     return PGR_OK;
 }
 
@@ -311,9 +333,9 @@ static int32_t forward_batch_impl(const PgrScene* scene, int n_views, const PgrC
     const BatchLayout B = make_batch_layout(L, n_views, (size_t)N);
     if (workspace_bytes < B.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
     char* ws = static_cast<char*>(workspace);
-    auto* view_table = reinterpret_cast<ViewEntry*>(ws + B.tables + B.view_table_off);
-    auto* bin_table = reinterpret_cast<BinView*>(ws + B.tables + B.bin_table_off);
-    auto* pre_table = reinterpret_cast<PreOut*>(ws + B.tables + B.pre_table_off);
+    auto* view_table = reinterpret_cast<ViewEntry*>(ws + B.tables + B.host.view_table);
+    auto* bin_table = reinterpret_cast<BinView*>(ws + B.tables + B.host.bin_table);
+    auto* pre_table = reinterpret_cast<PreOut*>(ws + B.tables + B.host.pre_table);
     auto* cams_dev = reinterpret_cast<CameraDev*>(ws + B.cams);
     auto* status_dev = reinterpret_cast<uint32_t*>(ws + B.status);
     auto* order_state = reinterpret_cast<uint32_t*>(ws + B.order_state);
@@ -323,24 +345,20 @@ static int32_t forward_batch_impl(const PgrScene* scene, int n_views, const PgrC
     std::vector<char> pageable;
     char* hs = static_cast<char*>(host_scratch);
     if (!hs) {
-        pageable.resize(host_scratch_bytes(n_views));
+        pageable.resize(B.host.total);
         hs = pageable.data();
     }
-    auto* table = reinterpret_cast<ViewEntry*>(hs + B.view_table_off);
-    auto* bins = reinterpret_cast<BinView*>(hs + B.bin_table_off);
-    auto* pres = reinterpret_cast<PreOut*>(hs + B.pre_table_off);
-    auto* h_status = reinterpret_cast<uint32_t*>(hs + B.tables_bytes);
+    auto* table = reinterpret_cast<ViewEntry*>(hs + B.host.view_table);
+    auto* bins = reinterpret_cast<BinView*>(hs + B.host.bin_table);
+    auto* pres = reinterpret_cast<PreOut*>(hs + B.host.pre_table);
+    auto* h_status = reinterpret_cast<uint32_t*>(hs + B.host.status);
     bool want_aux = false, want_sem = false;
     // the count walk's verdicts live where the sort's outputs will (alt, gauss_sorted: contiguous, dead until the sort)
     const size_t verdict_room = (L.total - L.alt) / (VERDICT_REGION_WORDS * 4);
     const int verdict_groups = layer_tiles <= BIN_LDS_TILES && records_enabled()
                                    ? (int)std::min<size_t>(verdict_room, (size_t)(N + WAVE - 1) / WAVE) : 0;
     for (int v = 0; v < n_views; ++v) {
-        vw[v] = carve(ws + B.views + (size_t)v * B.per_view, L);
-        vw[v].cam = cams_dev + v;          // cameras of a batch are contiguous: preprocess walks them
-        vw[v].counters = status_dev + 2 * v;   // and so are the status words: one D2H copy per batch
-        vw[v].tile_count = reinterpret_cast<uint32_t*>(ws + B.tile_counts) + (size_t)v * L.tiles;
-        vw[v].obj_last = reinterpret_cast<uint32_t*>(ws + B.tile_counts + (size_t)n_views * L.tiles * 4) + (size_t)v * L.tiles;
+        vw[v] = view_slice(ws, L, B, n_views, v);
         ViewEntry& e = table[v];
         memset(&e, 0, sizeof(e));
         e.cam = vw[v].cam; e.ranges = vw[v].ranges; e.gauss_sorted = vw[v].gauss_sorted; e.splats = vw[v].splats;
@@ -366,29 +384,20 @@ static int32_t forward_batch_impl(const PgrScene* scene, int n_views, const PgrC
     // the pointer tables: in the header launch's arguments when they are small (one / two views), else one H2D copy
     HeaderTables header_tables;
     int table_words = 0;
-    if (n_views <= SMALL_BATCH_VIEWS && B.tables_bytes <= sizeof(header_tables)) {
-        memcpy(header_tables.w, hs, B.tables_bytes);
-        table_words = (int)(B.tables_bytes / 4);
-    } else if (!hip_ok(hipMemcpyAsync(ws + B.tables, hs, B.tables_bytes, hipMemcpyHostToDevice, stream), "memcpy tables"))
+    if (n_views <= SMALL_BATCH_VIEWS && B.host.tables_bytes <= sizeof(header_tables)) {
+        memcpy(header_tables.w, hs, B.host.tables_bytes);
+        table_words = (int)(B.host.tables_bytes / 4);
+    } else if (!hip_ok(hipMemcpyAsync(ws + B.tables, hs, B.host.tables_bytes, hipMemcpyHostToDevice, stream), "memcpy tables"))
         return fail(PGR_ERR_LAUNCH_FAILURE);
 
     // ---- stage 0: batch header (+ cameras) + per-Gaussian preprocess
     mark(0);
     static_assert(ORDER_STATE_WORDS * 4 <= 256, "order state fits its slot");
-    auto camera_pack = [&](int v0, int cnt) {
-        CamPack cp;
-        for (int k = 0; k < cnt; ++k) {
-            const PgrCamera& c = cams[v0 + k];
-            cp.view[k] = c.viewmatrix; cp.proj[k] = c.projmatrix; cp.campos[k] = c.campos; cp.bg[k] = c.bg;
-            cp.tanfovx[k] = c.tanfovx; cp.tanfovy[k] = c.tanfovy; cp.depth_mode[k] = c.depth_mode;
-        }
-        return cp;
-    };
     {
         const int cnt = std::min(CAM_PACK_MAX, n_views);
         batch_header_kernel<<<256, 256, 0, stream>>>(
             reinterpret_cast<uint32_t*>(ws + B.tile_counts), (B.work_order - B.tile_counts) / 4,
-            reinterpret_cast<uint32_t*>(ws + B.work_order), B.order_slots, camera_pack(0, cnt), cnt, W, H, cams_dev, header_tables,
+            reinterpret_cast<uint32_t*>(ws + B.work_order), B.order_slots, pack_cameras(cams, cnt, true), cnt, W, H, cams_dev, header_tables,
             reinterpret_cast<uint32_t*>(ws + B.tables), table_words);
     }
     if (scene->tie_index && !scene->tie_inv)     // (a per-scene constant: pgr_scene_prepare computes it once)
@@ -396,7 +405,7 @@ static int32_t forward_batch_impl(const PgrScene* scene, int n_views, const PgrC
                                                                       reinterpret_cast<uint32_t*>(ws + B.tie_inv));
     for (int v0 = CAM_PACK_MAX; v0 < n_views; v0 += CAM_PACK_MAX) {
         const int cnt = std::min(CAM_PACK_MAX, n_views - v0);
-        pack_camera_kernel<<<cnt, 64, 0, stream>>>(camera_pack(v0, cnt), W, H, cams_dev + v0);
+        pack_camera_kernel<<<cnt, 64, 0, stream>>>(pack_cameras(cams + v0, cnt, true), W, H, cams_dev + v0);
     }
     // which 64-Gaussian blocks can show up in which view: decided by the preprocess waves themselves (conservative;
     // PGR_BLOCK_CULL=0 switches the test off), left in `vis` for the binning walks
@@ -534,6 +543,17 @@ static int32_t forward_batch_impl(const PgrScene* scene, int n_views, const PgrC
     return overflow ? PGR_ERR_INSTANCE_OVERFLOW : PGR_OK;
 }
 
+// The batched backward's scratch: the gradient rows [n_views, n, GRAD_ROW], then the BwdViewDev table.
+struct BackwardScratch { size_t rows_bytes, table, total; };
+
+static BackwardScratch backward_scratch(int32_t n, int32_t n_views) {
+    const size_t rows_bytes = (size_t)n_views * (size_t)n * GRAD_ROW * sizeof(float), table = align_up(rows_bytes);
+    return {rows_bytes, table, table + align_up((size_t)n_views * sizeof(BwdViewDev))};
+}
+
+// What a backward entry's checks leave behind for its launches (all zero for an empty scene, which launches nothing).
+struct BackwardPlan { char* ws; Layout L; BatchLayout B; float* rows; BwdViewDev* table; };
+
 // Both backward entries after their checks: the per-view table into `table` from the launch arguments (no host staging that
 // would have to outlive the call), `rows` [n_views, n, GRAD_ROW] cleared, the walk of every (view, tile, quarter) item of the
 // forward's work order, then one thread per Gaussian over the views.  One view runs the kernels' ONE instances.
@@ -542,22 +562,21 @@ static int32_t backward_impl(const PgrScene* scene, int n_views, const PgrBackwa
                              const PgrGradOutputs* grads, float* rows, BwdViewDev* table, hipStream_t stream) {
     const int N = scene->n;
     const CameraDev* cams_dev = reinterpret_cast<const CameraDev*>(ws + B.cams);
-    const uint32_t* status_dev = reinterpret_cast<const uint32_t*>(ws + B.status);
     for (int v0 = 0; v0 < n_views; v0 += BWD_TABLE_CHUNK) {
         const int cnt = std::min(BWD_TABLE_CHUNK, n_views - v0);
         BwdTableChunk chunk;
         memset(&chunk, 0, sizeof(chunk));
         for (int k = 0; k < cnt; ++k) {
             const int v = v0 + k;
-            const ViewWs vw = carve(ws + B.views + (size_t)v * B.per_view, L);
+            const ViewWs vw = view_slice(ws, L, B, n_views, v);
             const PgrBackwardView& bv = views[v];
-            chunk.v[k] = BwdViewDev{vw.ranges, vw.gauss_sorted, vw.splats, status_dev + 2 * v, bv.grad_color, bv.grad_depth,
+            chunk.v[k] = BwdViewDev{vw.ranges, vw.gauss_sorted, vw.splats, vw.counters, bv.grad_color, bv.grad_depth,
                                     bv.final_T, bv.n_contrib, bv.radii, rows + (size_t)v * N * GRAD_ROW,
                                     grad_alpha ? grad_alpha[v] : nullptr};
         }
         backward_table_kernel<<<1, 64, 0, stream>>>(chunk, cnt, table + v0);
     }
-    if (!hip_ok(hipMemsetAsync(rows, 0, (size_t)n_views * N * GRAD_ROW * sizeof(float), stream), "memset grad rows"))
+    if (!hip_ok(hipMemsetAsync(rows, 0, backward_scratch(N, n_views).rows_bytes, stream), "memset grad rows"))
         return PGR_ERR_LAUNCH_FAILURE;
     bool any_alpha = false;
     for (int v = 0; grad_alpha && v < n_views; ++v) any_alpha = any_alpha || grad_alpha[v];
@@ -624,6 +643,10 @@ static int32_t camera_backward_impl(const PgrScene* scene, int n_views, const Pg
 static_assert(sizeof(BwdViewDev) <= sizeof(ViewEntry) + sizeof(BinView) + sizeof(PreOut),
               "pgr_backward_ex writes its BwdViewDev into the one-view tables region");
 
+// pgr_pose_objects' workspace, per launch of POSE_JOBS_PER_LAUNCH jobs: the centroid partials, then the jobs' poses.
+constexpr size_t POSE_PART_BYTES = align_up((size_t)POSE_JOBS_PER_LAUNCH * POSE_REDUCE_BLOCKS * 3 * sizeof(double));
+constexpr size_t POSE_LAUNCH_BYTES = POSE_PART_BYTES + align_up((size_t)POSE_JOBS_PER_LAUNCH * sizeof(ObjectPoseDev));
+
 }  // namespace pgr
 
 using namespace pgr;
@@ -668,7 +691,7 @@ int32_t pgr_workspace_view(void* workspace, size_t workspace_bytes, int32_t n, i
     const Layout L = make_layout(n, width, height, max_instances);
     const BatchLayout B = make_batch_layout(L, n_views, (size_t)n);
     if (workspace_bytes < B.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
-    const ViewWs w = carve(static_cast<char*>(workspace) + B.views + (size_t)view_index * B.per_view, L);
+    const ViewWs w = view_slice(static_cast<char*>(workspace), L, B, n_views, view_index);
     v->splats = reinterpret_cast<const float*>(w.splats);
     v->rects = reinterpret_cast<const uint16_t*>(w.rects);
     v->gauss_sorted = w.gauss_sorted;
@@ -691,15 +714,15 @@ int32_t pgr_forward_batch(const PgrScene* scene, int32_t n_views, const PgrCamer
                               num_instances, static_cast<hipStream_t>(stream_v));
 }
 
-size_t pgr_host_scratch_bytes(int32_t n_views) { return n_views > 0 ? host_scratch_bytes(n_views) : 0; }
+size_t pgr_host_scratch_bytes(int32_t n_views) { return n_views > 0 ? host_tables(n_views).total : 0; }
 
 // The asynchronous entries after their own checks: the pinned host scratch must hold host_scratch_bytes(n_views), and an
 // empty scene, which launches nothing, gets its status words (all zero) written here.
 static int32_t forward_async(const PgrScene* scene, int32_t n_views, const PgrCamera* cameras, const PgrOutputs* outs,
                              void* workspace, size_t workspace_bytes, int64_t max_instances_per_view,
                              size_t host_scratch_size, void* stream_v, const ForwardOptions& opt) {
-    if (!opt.host_scratch || n_views <= 0 || host_scratch_size < host_scratch_bytes(n_views)) return PGR_ERR_INVALID_ARGUMENT;
-    if (scene && scene->n == 0) memset(opt.host_scratch, 0, host_scratch_bytes(n_views));
+    if (!opt.host_scratch || n_views <= 0 || host_scratch_size < host_tables(n_views).total) return PGR_ERR_INVALID_ARGUMENT;
+    if (scene && scene->n == 0) memset(opt.host_scratch, 0, host_tables(n_views).total);
     return forward_batch_impl(scene, n_views, cameras, outs, workspace, workspace_bytes, max_instances_per_view, nullptr,
                               static_cast<hipStream_t>(stream_v), opt);
 }
@@ -801,8 +824,7 @@ int32_t pgr_scene_prepare(const PgrScene* scene, const PgrSemantic* semantic, vo
 
 int32_t pgr_batch_status(const void* host_scratch, int32_t n_views, int64_t* num_instances) {
     if (!host_scratch || n_views <= 0) return PGR_ERR_INVALID_ARGUMENT;
-    const size_t tables = host_scratch_bytes(n_views) - (size_t)n_views * 8;   // status words follow the tables
-    const uint32_t* st = reinterpret_cast<const uint32_t*>(static_cast<const char*>(host_scratch) + tables);
+    const uint32_t* st = reinterpret_cast<const uint32_t*>(static_cast<const char*>(host_scratch) + host_tables(n_views).status);
     bool overflow = false;
     for (int v = 0; v < n_views; ++v) {
         if (num_instances) num_instances[v] = (int64_t)st[2 * v];
@@ -843,29 +865,78 @@ int32_t pgr_backward(const PgrScene* scene, const PgrCamera* cam, const float* g
                            workspace_bytes, max_instances, grads, grad_rows, stream_v);
 }
 
+// The single-view backward's checks and layouts (`view` = the entry's image arguments).
+static int32_t backward_plan(const PgrScene* scene, const PgrCamera* cam, const PgrBackwardView& view, void* workspace,
+                             size_t workspace_bytes, int64_t max_instances, const PgrGradOutputs* grads, float* grad_rows,
+                             BackwardPlan* p) {
+    if (int rc = check_scene(scene)) return rc;
+    if (scene->shs_rest) return PGR_ERR_INVALID_ARGUMENT;      // the SH gradient is one [n,sh_stride,3] array
+    if (!cam || !grads || !view.grad_color || !view.final_T || !view.n_contrib || cam->image_width <= 0 || cam->image_height <= 0)
+        return PGR_ERR_INVALID_ARGUMENT;
+    const int N = scene->n;
+    if (N == 0) return PGR_OK;
+    if (!workspace || !grad_rows || !view.radii) return PGR_ERR_INVALID_ARGUMENT;
+    p->L = make_layout(N, cam->image_width, cam->image_height, max_instances);
+    p->B = make_batch_layout(p->L, 1, (size_t)N);
+    if (workspace_bytes < p->B.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    p->ws = static_cast<char*>(workspace);
+    p->rows = grad_rows;
+    p->table = reinterpret_cast<BwdViewDev*>(p->ws + p->B.tables);
+    return PGR_OK;
+}
+
+// The batched backward's: every check before the first enqueue.
+static int32_t backward_batch_plan(const PgrScene* scene, int32_t n_views, const PgrCamera* cameras,
+                                   const PgrBackwardView* views, void* workspace, size_t workspace_bytes,
+                                   int64_t max_instances_per_view, const PgrGradOutputs* grads, void* scratch,
+                                   size_t scratch_bytes, BackwardPlan* p) {
+    if (int rc = check_scene(scene)) return rc;
+    if (scene->shs_rest) return PGR_ERR_INVALID_ARGUMENT;      // the SH gradient is one [n,sh_stride,3] array
+    if (n_views <= 0 || !cameras || !views || !grads) return PGR_ERR_INVALID_ARGUMENT;
+    if (max_instances_per_view < 0 || max_instances_per_view > 0x7fffffffLL) return PGR_ERR_INVALID_ARGUMENT;
+    const int N = scene->n, W = cameras[0].image_width, H = cameras[0].image_height;
+    if (W <= 0 || H <= 0) return PGR_ERR_INVALID_ARGUMENT;
+    for (int v = 0; v < n_views; ++v) {
+        if (cameras[v].image_width != W || cameras[v].image_height != H) return PGR_ERR_INVALID_ARGUMENT;
+        if (!views[v].grad_color || !views[v].final_T || !views[v].n_contrib) return PGR_ERR_INVALID_ARGUMENT;
+        if (N > 0 && !views[v].radii) return PGR_ERR_INVALID_ARGUMENT;
+    }
+    if (N == 0) return PGR_OK;
+    const BackwardScratch S = backward_scratch(N, n_views);
+    if (!workspace || !scratch || scratch_bytes < S.total) return PGR_ERR_INVALID_ARGUMENT;
+    p->L = make_layout(N, W, H, max_instances_per_view);
+    p->B = make_batch_layout(p->L, n_views, (size_t)N);
+    if (workspace_bytes < p->B.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    p->ws = static_cast<char*>(workspace);
+    p->rows = static_cast<float*>(scratch);
+    p->table = reinterpret_cast<BwdViewDev*>(static_cast<char*>(scratch) + S.table);
+    return PGR_OK;
+}
+
+// The launches behind a plan: the scene backward, then (camera entries: `camera_grads`) the camera kernels.
+static int32_t backward_launch(const PgrScene* scene, int n_views, const PgrBackwardView* views,
+                               const float* const* grad_alpha, const BackwardPlan& p, const PgrGradOutputs* grads,
+                               const PgrCameraGrad* camera_grads, void* cam_scratch, void* stream_v) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    if (scene->n > 0)
+        if (int32_t rc = backward_impl(scene, n_views, views, grad_alpha, p.ws, p.L, p.B, grads, p.rows, p.table, stream)) return rc;
+    if (!camera_grads) return PGR_OK;
+    return camera_backward_impl(scene, n_views, camera_grads, p.table, reinterpret_cast<const CameraDev*>(p.ws + p.B.cams),
+                                static_cast<float*>(cam_scratch), stream);
+}
+
 int32_t pgr_backward_ex(const PgrScene* scene, const PgrCamera* cam, const float* grad_color, const float* grad_depth,
                         const float* grad_alpha, const float* final_T, const uint32_t* n_contrib, const int32_t* radii,
                         void* workspace, size_t workspace_bytes, int64_t max_instances, const PgrGradOutputs* grads,
                         float* grad_rows, void* stream_v) {
-    if (int rc = check_scene(scene)) return rc;
-    if (scene->shs_rest) return PGR_ERR_INVALID_ARGUMENT;      // the SH gradient is one [n,sh_stride,3] array
-    if (!cam || !grads || !grad_color || !final_T || !n_contrib || cam->image_width <= 0 || cam->image_height <= 0)
-        return PGR_ERR_INVALID_ARGUMENT;
-    const int N = scene->n;
-    if (N == 0) return PGR_OK;
-    if (!workspace || !grad_rows || !radii) return PGR_ERR_INVALID_ARGUMENT;
-    const Layout L = make_layout(N, cam->image_width, cam->image_height, max_instances);
-    const BatchLayout B = make_batch_layout(L, 1, (size_t)N);
-    if (workspace_bytes < B.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
-    char* ws = static_cast<char*>(workspace);
     const PgrBackwardView view{grad_color, grad_depth, final_T, n_contrib, radii};
-    return backward_impl(scene, 1, &view, &grad_alpha, ws, L, B, grads, grad_rows,
-                         reinterpret_cast<BwdViewDev*>(ws + B.tables), static_cast<hipStream_t>(stream_v));
+    BackwardPlan p{};
+    if (int rc = backward_plan(scene, cam, view, workspace, workspace_bytes, max_instances, grads, grad_rows, &p)) return rc;
+    return backward_launch(scene, 1, &view, &grad_alpha, p, grads, nullptr, nullptr, stream_v);
 }
 
 size_t pgr_backward_batch_scratch_bytes(int32_t n, int32_t n_views) {
-    if (n < 0 || n_views <= 0) return 0;
-    return align_up((size_t)n_views * (size_t)n * GRAD_ROW * sizeof(float)) + align_up((size_t)n_views * sizeof(BwdViewDev));
+    return (n < 0 || n_views <= 0) ? 0 : backward_scratch(n, n_views).total;
 }
 
 int32_t pgr_backward_batch(const PgrScene* scene, int32_t n_views, const PgrCamera* cameras, const PgrBackwardView* views,
@@ -879,32 +950,15 @@ int32_t pgr_backward_batch_ex(const PgrScene* scene, int32_t n_views, const PgrC
                               const PgrBackwardView* views, const float* const* grad_alpha, void* workspace,
                               size_t workspace_bytes, int64_t max_instances_per_view, const PgrGradOutputs* grads,
                               void* scratch, size_t scratch_bytes, void* stream_v) {
-    // every check before the first enqueue
-    if (int rc = check_scene(scene)) return rc;
-    if (scene->shs_rest) return PGR_ERR_INVALID_ARGUMENT;      // the SH gradient is one [n,sh_stride,3] array
-    if (n_views <= 0 || !cameras || !views || !grads) return PGR_ERR_INVALID_ARGUMENT;
-    if (max_instances_per_view < 0 || max_instances_per_view > 0x7fffffffLL) return PGR_ERR_INVALID_ARGUMENT;
-    const int N = scene->n, W = cameras[0].image_width, H = cameras[0].image_height;
-    if (W <= 0 || H <= 0) return PGR_ERR_INVALID_ARGUMENT;
-    for (int v = 0; v < n_views; ++v) {
-        if (cameras[v].image_width != W || cameras[v].image_height != H) return PGR_ERR_INVALID_ARGUMENT;
-        if (!views[v].grad_color || !views[v].final_T || !views[v].n_contrib) return PGR_ERR_INVALID_ARGUMENT;
-        if (N > 0 && !views[v].radii) return PGR_ERR_INVALID_ARGUMENT;
-    }
-    if (N == 0) return PGR_OK;
-    if (!workspace || !scratch || scratch_bytes < pgr_backward_batch_scratch_bytes(N, n_views)) return PGR_ERR_INVALID_ARGUMENT;
-    const Layout L = make_layout(N, W, H, max_instances_per_view);
-    const BatchLayout B = make_batch_layout(L, n_views, (size_t)N);
-    if (workspace_bytes < B.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
-    const size_t rows_bytes = (size_t)n_views * (size_t)N * GRAD_ROW * sizeof(float);
-    auto* table = reinterpret_cast<BwdViewDev*>(static_cast<char*>(scratch) + align_up(rows_bytes));
-    return backward_impl(scene, n_views, views, grad_alpha, static_cast<char*>(workspace), L, B, grads,
-                         static_cast<float*>(scratch), table, static_cast<hipStream_t>(stream_v));
+    BackwardPlan p{};
+    if (int rc = backward_batch_plan(scene, n_views, cameras, views, workspace, workspace_bytes, max_instances_per_view, grads,
+                                     scratch, scratch_bytes, &p))
+        return rc;
+    return backward_launch(scene, n_views, views, grad_alpha, p, grads, nullptr, nullptr, stream_v);
 }
 
 size_t pgr_camera_grad_scratch_bytes(int32_t n, int32_t n_views) {
-    if (n < 0 || n_views <= 0) return 0;
-    return camera_scratch_bytes(n, n_views);
+    return (n < 0 || n_views <= 0) ? 0 : camera_scratch_bytes(n, n_views);
 }
 
 int32_t pgr_backward_camera(const PgrScene* scene, const PgrCamera* cam, const float* grad_color, const float* grad_depth,
@@ -914,16 +968,10 @@ int32_t pgr_backward_camera(const PgrScene* scene, const PgrCamera* cam, const f
                             void* stream_v) {
     if (!camera_grad || !scene || scene->n < 0 || !cam_scratch || cam_scratch_bytes < camera_scratch_bytes(scene->n, 1))
         return PGR_ERR_INVALID_ARGUMENT;
-    const int32_t rc = pgr_backward_ex(scene, cam, grad_color, grad_depth, grad_alpha, final_T, n_contrib, radii, workspace,
-                                       workspace_bytes, max_instances, grads, grad_rows, stream_v);
-    if (rc != PGR_OK) return rc;
-    const int N = scene->n;
-    const Layout L = make_layout(N, cam->image_width, cam->image_height, max_instances);
-    const BatchLayout B = make_batch_layout(L, 1, (size_t)N);
-    char* ws = static_cast<char*>(workspace);
-    return camera_backward_impl(scene, 1, camera_grad, reinterpret_cast<const BwdViewDev*>(ws + B.tables),
-                                reinterpret_cast<const CameraDev*>(ws + B.cams), static_cast<float*>(cam_scratch),
-                                static_cast<hipStream_t>(stream_v));
+    const PgrBackwardView view{grad_color, grad_depth, final_T, n_contrib, radii};
+    BackwardPlan p{};
+    if (int rc = backward_plan(scene, cam, view, workspace, workspace_bytes, max_instances, grads, grad_rows, &p)) return rc;
+    return backward_launch(scene, 1, &view, &grad_alpha, p, grads, camera_grad, cam_scratch, stream_v);
 }
 
 int32_t pgr_backward_batch_camera(const PgrScene* scene, int32_t n_views, const PgrCamera* cameras,
@@ -934,17 +982,11 @@ int32_t pgr_backward_batch_camera(const PgrScene* scene, int32_t n_views, const 
     if (!camera_grads || !scene || scene->n < 0 || n_views <= 0 || !cam_scratch ||
         cam_scratch_bytes < camera_scratch_bytes(scene->n, n_views))
         return PGR_ERR_INVALID_ARGUMENT;
-    const int32_t rc = pgr_backward_batch_ex(scene, n_views, cameras, views, grad_alpha, workspace, workspace_bytes,
-                                             max_instances_per_view, grads, scratch, scratch_bytes, stream_v);
-    if (rc != PGR_OK) return rc;
-    const int N = scene->n;
-    const Layout L = make_layout(N, cameras[0].image_width, cameras[0].image_height, max_instances_per_view);
-    const BatchLayout B = make_batch_layout(L, n_views, (size_t)N);
-    const size_t rows_bytes = (size_t)n_views * (size_t)N * GRAD_ROW * sizeof(float);
-    return camera_backward_impl(scene, n_views, camera_grads,
-                                reinterpret_cast<const BwdViewDev*>(static_cast<char*>(scratch) + align_up(rows_bytes)),
-                                reinterpret_cast<const CameraDev*>(static_cast<char*>(workspace) + B.cams),
-                                static_cast<float*>(cam_scratch), static_cast<hipStream_t>(stream_v));
+    BackwardPlan p{};
+    if (int rc = backward_batch_plan(scene, n_views, cameras, views, workspace, workspace_bytes, max_instances_per_view, grads,
+                                     scratch, scratch_bytes, &p))
+        return rc;
+    return backward_launch(scene, n_views, views, grad_alpha, p, grads, camera_grads, cam_scratch, stream_v);
 }
 
 int32_t pgr_compose_object(int32_t n, const float* xyz, const float* rot, const float* f_rest, int32_t n_rest,
@@ -986,9 +1028,7 @@ int32_t pgr_clock_probe(uint64_t* ticks, uint32_t spin_us, void* stream_v) {
 
 size_t pgr_pose_objects_workspace_bytes(int32_t n_jobs) {
     if (n_jobs <= 0) return 0;
-    const size_t launches = ((size_t)n_jobs + POSE_JOBS_PER_LAUNCH - 1) / POSE_JOBS_PER_LAUNCH;
-    return launches * (align_up((size_t)POSE_JOBS_PER_LAUNCH * POSE_REDUCE_BLOCKS * 3 * sizeof(double)) +
-                       align_up((size_t)POSE_JOBS_PER_LAUNCH * sizeof(ObjectPoseDev)));
+    return ((size_t)n_jobs + POSE_JOBS_PER_LAUNCH - 1) / POSE_JOBS_PER_LAUNCH * POSE_LAUNCH_BYTES;
 }
 
 int32_t pgr_pose_objects(int32_t n_jobs, const PgrPoseJob* jobs, const double* sh_dirs, const double* sh_pinv,
@@ -1004,8 +1044,6 @@ int32_t pgr_pose_objects(int32_t n_jobs, const PgrPoseJob* jobs, const double* s
     }
     if (!workspace || workspace_bytes < pgr_pose_objects_workspace_bytes(n_jobs)) return PGR_ERR_WORKSPACE_TOO_SMALL;
     char* ws = static_cast<char*>(workspace);
-    const size_t part_bytes = align_up((size_t)POSE_JOBS_PER_LAUNCH * POSE_REDUCE_BLOCKS * 3 * sizeof(double));
-    const size_t per_launch = part_bytes + align_up((size_t)POSE_JOBS_PER_LAUNCH * sizeof(ObjectPoseDev));
     for (int k0 = 0, launch = 0; k0 < n_jobs; k0 += POSE_JOBS_PER_LAUNCH, ++launch) {
         PoseJobTable T{};
         T.count = std::min(POSE_JOBS_PER_LAUNCH, n_jobs - k0);
@@ -1018,8 +1056,8 @@ int32_t pgr_pose_objects(int32_t n_jobs, const PgrPoseJob* jobs, const double* s
             blocks += (uint32_t)((j.n + 255) / 256);
             reduce = reduce || (j.kind == PGR_POSE_XYZ && !j.about_origin && j.R && j.n > 0);
         }
-        auto* partial = reinterpret_cast<double*>(ws + (size_t)launch * per_launch);
-        auto* poses = reinterpret_cast<ObjectPoseDev*>(ws + (size_t)launch * per_launch + part_bytes);
+        auto* partial = reinterpret_cast<double*>(ws + (size_t)launch * POSE_LAUNCH_BYTES);
+        auto* poses = reinterpret_cast<ObjectPoseDev*>(ws + (size_t)launch * POSE_LAUNCH_BYTES + POSE_PART_BYTES);
         if (reduce) pose_reduce_kernel<<<dim3(POSE_REDUCE_BLOCKS, T.count), 256, 0, stream>>>(T, partial);
         pose_prepare_kernel<<<T.count, 128, 0, stream>>>(T, partial, sh_dirs, sh_pinv, poses);
         if (blocks) pose_apply_kernel<<<blocks, 256, 0, stream>>>(T, poses);
@@ -1042,21 +1080,13 @@ int32_t pgr_block_visibility(const PgrScene* scene, int32_t n_views, const PgrCa
     if (workspace_bytes < pgr_block_visibility_workspace_bytes(scene->n, n_views)) return PGR_ERR_WORKSPACE_TOO_SMALL;
     const int W = cams[0].image_width, H = cams[0].image_height;
     for (int v = 0; v < n_views; ++v)
-        if (cams[v].image_width != W || cams[v].image_height != H || W <= 0 || H <= 0 || !cams[v].viewmatrix ||
-            !cams[v].projmatrix || !cams[v].campos || !cams[v].bg || !(cams[v].tanfovx > 0.f) || !(cams[v].tanfovy > 0.f))
-            return PGR_ERR_INVALID_ARGUMENT;
+        if (cams[v].image_width != W || cams[v].image_height != H || !camera_ok(cams[v])) return PGR_ERR_INVALID_ARGUMENT;
     char* ws = static_cast<char*>(workspace);
     auto* cams_dev = reinterpret_cast<CameraDev*>(ws);
     auto* bounds = reinterpret_cast<BlockBounds*>(ws + align_up((size_t)n_views * sizeof(CameraDev)));
     for (int v0 = 0; v0 < n_views; v0 += CAM_PACK_MAX) {
-        CamPack cp;
         const int cnt = std::min(CAM_PACK_MAX, n_views - v0);
-        for (int k = 0; k < cnt; ++k) {
-            const PgrCamera& c = cams[v0 + k];
-            cp.view[k] = c.viewmatrix; cp.proj[k] = c.projmatrix; cp.campos[k] = c.campos; cp.bg[k] = c.bg;
-            cp.tanfovx[k] = c.tanfovx; cp.tanfovy[k] = c.tanfovy; cp.depth_mode[k] = 0;
-        }
-        pack_camera_kernel<<<cnt, 64, 0, stream>>>(cp, W, H, cams_dev + v0);
+        pack_camera_kernel<<<cnt, 64, 0, stream>>>(pack_cameras(cams + v0, cnt, false), W, H, cams_dev + v0);
     }
     const int groups = (scene->n + WAVE - 1) / WAVE, words = (n_views + 31) / 32;
     block_bounds_kernel<<<(groups + 3) / 4, 256, 0, stream>>>(*scene, nullptr, bounds, groups);
@@ -1111,11 +1141,7 @@ int32_t pgr_pack_frames(const float* color_b3hw, const float* depth_bhw, const u
 
 int32_t pgr_frame_record_layout(int32_t width, int32_t height, int32_t k, PgrRecordLayout* layout) {
     if (!layout || width <= 0 || height <= 0 || k < 0) return PGR_ERR_INVALID_ARGUMENT;
-    const size_t P = (size_t)width * height;
-    layout->off_rgb = 0;
-    layout->off_depth = (int64_t)align_up(3 * P, 16);
-    layout->off_masks = layout->off_depth + (int64_t)align_up(2 * P, 16);
-    layout->bytes = layout->off_masks + (int64_t)align_up((size_t)((k + 7) / 8) * P, 16);
+    *layout = record_layout((size_t)width * height, k);
     return PGR_OK;
 }
 
@@ -1135,10 +1161,6 @@ int32_t pgr_pack_records(const float* color_b3hw, const float* depth_bhw, const 
 
 }  // extern "C"
 
-
-
-
-
 // ---- 3-nearest-neighbour mean squared distance (simple_knn.distCUDA2) ---------------------------------------------
 namespace {
 struct KnnLayout { size_t grid, count, start, sorted, total; int target; size_t cells; };
@@ -1148,13 +1170,12 @@ KnnLayout knn_layout(int32_t n) {
     while (target < KNN_MAX_GRID && (double)target * target * target < 0.5 * (double)n) ++target;   // ~2 points per cell
     K.target = target;
     K.cells = (size_t)target * target * target;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes ? bytes : 1); return o; };
-    K.grid = take(sizeof(KnnGrid));
-    K.count = take(K.cells * 4);
-    K.start = take((K.cells + 1) * 4);
-    K.sorted = take((size_t)(n > 0 ? n : 1) * 16);
-    K.total = off;
+    Carver c;
+    K.grid = c.take(sizeof(KnnGrid));
+    K.count = c.take(K.cells * 4);
+    K.start = c.take((K.cells + 1) * 4);
+    K.sorted = c.take((size_t)(n > 0 ? n : 1) * 16);
+    K.total = c.off;
     return K;
 }
 }  // namespace
@@ -1208,14 +1229,13 @@ struct MarchLayout { size_t mask, ntri, vbase, tile_tot, tile_off, total; int ti
 MarchLayout march_layout(size_t n) {
     MarchLayout M{};
     M.tiles = (int)((n + MARCH_TILE - 1) / MARCH_TILE);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes ? bytes : 1); return o; };
-    M.mask = take(n);
-    M.ntri = take(n);
-    M.vbase = take(n * sizeof(int32_t));
-    M.tile_tot = take((size_t)M.tiles * 2 * sizeof(long long));
-    M.tile_off = take((size_t)M.tiles * 2 * sizeof(long long));
-    M.total = off;
+    Carver c;
+    M.mask = c.take(n);
+    M.ntri = c.take(n);
+    M.vbase = c.take(n * sizeof(int32_t));
+    M.tile_tot = c.take((size_t)M.tiles * 2 * sizeof(long long));
+    M.tile_off = c.take((size_t)M.tiles * 2 * sizeof(long long));
+    M.total = c.off;
     return M;
 }
 }  // namespace
@@ -1533,15 +1553,14 @@ LossLayout loss_layout(int32_t height, int32_t width) {
     L.tiles_x = (width + LOSS_TILE - 1) / LOSS_TILE;
     L.tiles_y = (height + LOSS_TILE - 1) / LOSS_TILE;
     const size_t map = (size_t)3 * height * width * sizeof(float);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes ? bytes : 1); return o; };
-    L.a = take(map);
-    L.b = take(map);
-    L.c = take(map);
-    L.partial = take((size_t)3 * L.tiles_x * L.tiles_y * 2 * sizeof(double));
-    L.total = off;
-    L.partial_a = take((size_t)L.tiles_x * L.tiles_y * sizeof(double));      // the masked loss's alpha partials
-    L.total_masked = off;
+    Carver c;
+    L.a = c.take(map);
+    L.b = c.take(map);
+    L.c = c.take(map);
+    L.partial = c.take((size_t)3 * L.tiles_x * L.tiles_y * 2 * sizeof(double));
+    L.total = c.off;
+    L.partial_a = c.take((size_t)L.tiles_x * L.tiles_y * sizeof(double));      // the masked loss's alpha partials
+    L.total_masked = c.off;
     return L;
 }
 LossWindow ssim_window() {

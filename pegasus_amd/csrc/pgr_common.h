@@ -69,10 +69,10 @@ struct alignas(16) CameraDev {
 };
 static_assert(sizeof(CameraDev) == 256, "CameraDev must be 256 B");
 
-// Workspace carve-up (all offsets multiples of 256 B).
+// One view's slice of a workspace (all offsets multiples of 256 B); the view's camera, status words, tile_count and
+// obj_last live in the batch header (pegasus_raster.hip, view_slice).
 struct Layout {
-    size_t cam, counters, splats, radii, rects, crects, rel, ranges, bucket, alt,
-        gauss_sorted, total;
+    size_t splats, radii, rects, crects, rel, ranges, bucket, alt, gauss_sorted, total;
     int32_t tiles, grid_x, grid_y;
     int32_t n_blocks;
     int32_t n_chunks;

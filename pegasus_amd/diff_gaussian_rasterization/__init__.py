@@ -32,7 +32,7 @@ import torch
 from torch import nn
 
 from .. import _lib, rasterizer
-from .._lib import ptr, stream_ptr
+from .._lib import ptr
 from ..rasterizer import _until_fits, camera_structs, dev_f32 as _dev_f32, scene_struct
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "rasterize_gaussians_batch",
@@ -154,18 +154,16 @@ class _RasterizeGaussians(torch.autograd.Function):
         outs = (_lib.PgrOutputs * V)(*[
             _lib.PgrOutputs(color=ptr(c), depth=ptr(d), radii=ptr(r), final_T=ptr(ft), n_contrib=ptr(nc))
             for c, d, r, ft, nc in zip(*map(per_view, (color, depth, radii, final_T, n_contrib)))])
-        stream = stream_ptr(device)
         need = (C.c_int64 * V)()
         ws = None
+        entry, lead_args = ("pgr_forward", (C.byref(scene),)) if single else ("pgr_forward_batch", (C.byref(scene), V))
 
         def run(capacity):
             nonlocal ws
             ws = torch.empty(L.pgr_batch_workspace_bytes(n, W, H, capacity, V), dtype=torch.uint8, device=device)
-            args = (cams, outs, ptr(ws), ws.numel(), capacity, need, stream)
-            return (L.pgr_forward(C.byref(scene), *args) if single else L.pgr_forward_batch(C.byref(scene), V, *args)), need
-        with torch.cuda.device(device):
-            status, _, max_inst = _until_fits(run, max(1 << 18, 4 * n), 1.25)
-            _lib.check(status, "pgr_forward" if single else "pgr_forward_batch")
+            return _lib.enqueue(entry, device, *lead_args, cams, outs, ptr(ws), ws.numel(), capacity, need), need
+        status, _, max_inst = _until_fits(run, max(1 << 18, 4 * n), 1.25)
+        _lib.check(status, entry)
         ctx.hw, ctx.V, ctx.n, ctx.max_inst, ctx.single = (H, W), V, n, max_inst, single
         ctx.sh_degree, ctx.scale_modifier = int(rs0.sh_degree), float(rs0.scale_modifier)
         ctx.cam_meta = tuple(None if x is None else (tuple(x.shape), x.dtype) for x in cam_inputs)
@@ -223,21 +221,20 @@ class _RasterizeGaussians(torch.autograd.Function):
             cam_args = (cam_structs, ptr(cam_scratch), cam_scratch.numel())
         # one call per mode; the camera entries take the scene-only entries' arguments, then cam_args, then the stream
         shared = (ptr(ws), ws.numel(), ctx.max_inst, C.byref(grads))
-        with torch.cuda.device(device):
-            if single:
-                entry = "pgr_backward_camera" if cam_args else "pgr_backward_ex"
-                rows = torch.empty((n, 12), dtype=torch.float32, device=device)
-                args = (cams, ptr(gc), ptr(gd), ptr(ga), ptr(final_T), ptr(n_contrib), ptr(radii), *shared, ptr(rows))
-            else:
-                entry = "pgr_backward_batch_camera" if cam_args else "pgr_backward_batch_ex"
-                alpha_ptrs = None if ga is None else (C.c_void_p * V)(*[ga[v].data_ptr() for v in range(V)])
-                views = (_lib.PgrBackwardView * V)(*[
-                    _lib.PgrBackwardView(grad_color=ptr(gc[v]), grad_depth=None if gd is None else ptr(gd[v]),
-                                         final_T=ptr(final_T[v]), n_contrib=ptr(n_contrib[v]), radii=ptr(radii[v]))
-                    for v in range(V)])
-                scratch = torch.empty(max(1, L.pgr_backward_batch_scratch_bytes(n, V)), dtype=torch.uint8, device=device)
-                args = (V, cams, views, alpha_ptrs, *shared, ptr(scratch), scratch.numel())
-            _lib.check(getattr(L, entry)(C.byref(scene), *args, *cam_args, stream_ptr(device)), entry)
+        if single:
+            entry = "pgr_backward_camera" if cam_args else "pgr_backward_ex"
+            rows = torch.empty((n, 12), dtype=torch.float32, device=device)
+            args = (cams, ptr(gc), ptr(gd), ptr(ga), ptr(final_T), ptr(n_contrib), ptr(radii), *shared, ptr(rows))
+        else:
+            entry = "pgr_backward_batch_camera" if cam_args else "pgr_backward_batch_ex"
+            alpha_ptrs = None if ga is None else (C.c_void_p * V)(*[ga[v].data_ptr() for v in range(V)])
+            views = (_lib.PgrBackwardView * V)(*[
+                _lib.PgrBackwardView(grad_color=ptr(gc[v]), grad_depth=None if gd is None else ptr(gd[v]),
+                                     final_T=ptr(final_T[v]), n_contrib=ptr(n_contrib[v]), radii=ptr(radii[v]))
+                for v in range(V)])
+            scratch = torch.empty(max(1, L.pgr_backward_batch_scratch_bytes(n, V)), dtype=torch.uint8, device=device)
+            args = (V, cams, views, alpha_ptrs, *shared, ptr(scratch), scratch.numel())
+        _lib.call(entry, device, C.byref(scene), *args, *cam_args)
         cam_out = tuple(cam_g[j // 3, sl[j % 3][0]:sl[j % 3][1]].reshape(m[0]).to(m[1]) if want_cam[j] else None
                         for j, m in enumerate(ctx.cam_meta))
         # means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, single, return_alpha,
@@ -282,7 +279,6 @@ class GaussianRasterizer(nn.Module):
 
     def markVisible(self, positions: torch.Tensor) -> torch.Tensor:
         """bool[N]: Gaussian centre is in front of the near plane of this view."""
-        L = _lib.lib()
         with torch.no_grad():
             device = positions.device
             if device.type != "cuda":
@@ -292,9 +288,7 @@ class GaussianRasterizer(nn.Module):
             present = torch.zeros((n,), dtype=torch.uint8, device=device)
             if n:
                 view = _dev_f32(self.raster_settings.viewmatrix, device)
-                with torch.cuda.device(device):
-                    _lib.check(L.pgr_mark_visible(n, ptr(pos), ptr(view), ptr(present), stream_ptr(device)),
-                               "pgr_mark_visible")
+                _lib.call("pgr_mark_visible", device, n, ptr(pos), ptr(view), ptr(present))
             return present.bool()
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,

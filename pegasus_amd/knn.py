@@ -20,10 +20,8 @@ def dist2(points: torch.Tensor) -> torch.Tensor:
     out = torch.empty((n,), dtype=torch.float32, device=pts.device)
     if n == 0:
         return out
-    with torch.cuda.device(pts.device):
-        ws = torch.empty((L.pgr_knn_workspace_bytes(n),), dtype=torch.uint8, device=pts.device)
-        _lib.check(L.pgr_knn_mean_dist2(n, _lib.ptr(pts), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
-                                        _lib.stream_ptr(pts.device)), "pgr_knn_mean_dist2")
+    ws = torch.empty((L.pgr_knn_workspace_bytes(n),), dtype=torch.uint8, device=pts.device)
+    _lib.call("pgr_knn_mean_dist2", pts.device, n, _lib.ptr(pts), _lib.ptr(out), _lib.ptr(ws), ws.numel())
     return out
 
 

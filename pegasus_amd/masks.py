@@ -37,7 +37,6 @@ def color_masks(img_chw: torch.Tensor, colors: torch.Tensor, threshold: float = 
                 out: torch.Tensor = None) -> torch.Tensor:
     """uint8 [K,H,W] (or [B,K,H,W] for a [B,3,H,W] batch, one launch): 1 where the rendered colour is within
     ``threshold`` (L2) of semantic colour k."""
-    L = _lib.lib()
     if img_chw.device.type != "cuda":
         raise RuntimeError("color_masks needs a HIP device tensor; there is no CPU path")
     img = img_chw.contiguous().float()
@@ -48,15 +47,12 @@ def color_masks(img_chw: torch.Tensor, colors: torch.Tensor, threshold: float = 
     K = colors.shape[0]
     if out is None:
         out = torch.empty(((nb, K, H, W) if batched else (K, H, W)), dtype=torch.uint8, device=img.device)
-    with torch.cuda.device(img.device):
-        _lib.check(L.pgr_color_masks(_lib.ptr(img), nb, W, H, _lib.ptr(colors), K, float(threshold), _lib.ptr(out),
-                                     _lib.stream_ptr(img.device)), "pgr_color_masks")
+    _lib.call("pgr_color_masks", img.device, _lib.ptr(img), nb, W, H, _lib.ptr(colors), K, float(threshold), _lib.ptr(out))
     return out
 
 
 def quantize_frame(img_chw: torch.Tensor, depth: torch.Tensor):
     """(uint8 [H,W,3], uint16-as-int16-storage [H,W]) exactly as the reference's numpy casts."""
-    L = _lib.lib()
     if img_chw.device.type != "cuda":
         raise RuntimeError("quantize_frame needs HIP device tensors; there is no CPU path")
     img = img_chw.contiguous().float()
@@ -64,9 +60,7 @@ def quantize_frame(img_chw: torch.Tensor, depth: torch.Tensor):
     _, H, W = img.shape
     rgb = torch.empty((H, W, 3), dtype=torch.uint8, device=img.device)
     mm = torch.empty((H, W), dtype=torch.int16, device=img.device)   # bit pattern of uint16 millimetres
-    with torch.cuda.device(img.device):
-        _lib.check(L.pgr_quantize_frame(_lib.ptr(img), _lib.ptr(d), W, H, _lib.ptr(rgb), _lib.ptr(mm),
-                                        _lib.stream_ptr(img.device)), "pgr_quantize_frame")
+    _lib.call("pgr_quantize_frame", img.device, _lib.ptr(img), _lib.ptr(d), W, H, _lib.ptr(rgb), _lib.ptr(mm))
     return rgb, mm
 
 
@@ -75,7 +69,6 @@ def pack_frames(color: torch.Tensor = None, depth: torch.Tensor = None, masks: t
     ``depth`` [B,1,H,W] -> "depth_mm" int16 storage of uint16 millimetres [B,H,W] (both exactly the reference's numpy
     casts, /root/reference/pegasus.py:347,355), ``masks`` uint8 [B,K,H,W] -> "mask_bits" uint8 [B,H,W,ceil(K/8)] with
     mask m in bit m % 8 of byte m // 8.  The outputs are NEW tensors: a frame set may be re-rendered while they travel."""
-    L = _lib.lib()
     ref = next(t for t in (color, depth, masks) if t is not None)
     if ref.device.type != "cuda":
         raise RuntimeError("pack_frames needs HIP device tensors; there is no CPU path")
@@ -95,10 +88,8 @@ def pack_frames(color: torch.Tensor = None, depth: torch.Tensor = None, masks: t
             raise ValueError("masks must be uint8 [B,K,H,W] (pgr_color_masks output)")
         K = int(masks.shape[1])
         out["mask_bits"] = torch.empty((B, H, W, (K + 7) // 8), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.pgr_pack_frames(ptr(color), ptr(depth), ptr(masks), B, K, W, H, ptr(out.get("rgb")),
-                                     ptr(out.get("depth_mm")), ptr(out.get("mask_bits")), _lib.stream_ptr(dev)),
-                   "pgr_pack_frames")
+    _lib.call("pgr_pack_frames", dev, ptr(color), ptr(depth), ptr(masks), B, K, W, H, ptr(out.get("rgb")),
+              ptr(out.get("depth_mm")), ptr(out.get("mask_bits")))
     return out
 
 
@@ -115,7 +106,6 @@ def pack_records(color: torch.Tensor = None, depth: torch.Tensor = None, masks: 
     uint8 RGB (HWC), uint16 depth millimetres and the K masks as bit planes back to back -- the unit the gather to the root
     rank and the disk writers move.  ``out``: a preallocated [>= B, bytes] uint8 tensor (e.g. a FrameGather send buffer)
     is filled in place; record_views() slices a record tensor back into the three images without copying."""
-    L = _lib.lib()
     ref = next(t for t in (color, depth, masks) if t is not None)
     if ref.device.type != "cuda":
         raise RuntimeError("pack_records needs HIP device tensors; there is no CPU path")
@@ -138,9 +128,7 @@ def pack_records(color: torch.Tensor = None, depth: torch.Tensor = None, masks: 
             or out.stride(0) % 16 or out.device != dev:
         raise ValueError(f"out must be a uint8 [>= {B}, >= {nbytes}] device tensor with a 16-byte-aligned row stride")
     ptr = _lib.ptr
-    with torch.cuda.device(dev):
-        _lib.check(L.pgr_pack_records(ptr(color), ptr(depth), ptr(masks), B, K, W, H, ptr(out), int(out.stride(0)),
-                                      _lib.stream_ptr(dev)), "pgr_pack_records")
+    _lib.call("pgr_pack_records", dev, ptr(color), ptr(depth), ptr(masks), B, K, W, H, ptr(out), int(out.stride(0)))
     return out
 
 

@@ -132,10 +132,8 @@ def integrate(depth, final_T, views, grid: Grid, truncation: float, alpha_min: f
     cams, keep = camera_structs(views, device)
     sdf = torch.empty(grid.shape, dtype=torch.float32, device=device)
     g = grid.struct()
-    with torch.cuda.device(device):
-        _lib.check(_lib.lib().pgr_tsdf_integrate(C.byref(g), V, cams, _lib.ptr(depth), _lib.ptr(final_T), float(truncation),
-                                                 float(alpha_min), _lib.ptr(sdf), _lib.stream_ptr(device)),
-                   "pgr_tsdf_integrate")
+    _lib.call("pgr_tsdf_integrate", device, C.byref(g), V, cams, _lib.ptr(depth), _lib.ptr(final_T), float(truncation),
+              float(alpha_min), _lib.ptr(sdf))
     del keep
     return sdf
 
@@ -156,31 +154,28 @@ def march(sdf, grid: Grid, stage_ms: Optional[dict] = None) -> Mesh:
     nbytes = L.pgr_march_workspace_bytes(grid.nx, grid.ny, grid.nz)
     if nbytes == 0:
         raise ValueError(f"grid {grid.shape}: every axis must hold 2..{MAX_AXIS} points")
-    with torch.cuda.device(device):
-        stream_t = torch.cuda.current_stream(device)
-        stream = _lib.stream_ptr(device)
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
-        counts = torch.zeros(2, dtype=torch.int64, device=device)
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if stage_ms is not None else None
-        if ev:
-            ev[0].record(stream_t)
-        _lib.check(L.pgr_march_count(C.byref(g), _lib.ptr(sdf), _lib.ptr(ws), ws.numel(), _lib.ptr(counts), stream),
-                   "pgr_march_count")
-        if ev:
-            ev[1].record(stream_t)
-        nv, nf = (int(x) for x in counts.cpu())
-        if nv >= 2 ** 31 or nf >= 2 ** 31:
-            raise ValueError(f"{nv} vertices / {nf} faces: more than int32 indices hold; use a coarser grid")
-        vertices = torch.empty((max(nv, 1), 3), dtype=torch.float32, device=device)
-        faces = torch.empty((max(nf, 1), 3), dtype=torch.int32, device=device)
-        _lib.check(L.pgr_march_emit(C.byref(g), _lib.ptr(sdf), _lib.ptr(ws), ws.numel(), _lib.ptr(vertices),
-                                    _lib.ptr(faces), stream), "pgr_march_emit")
-        if ev:
-            ev[2].record(stream_t)
-        out = Mesh(vertices[:nv].cpu().numpy(), faces[:nf].cpu().numpy())
-        if ev:
-            stage_ms["count"] = ev[0].elapsed_time(ev[1])
-            stage_ms["emit"] = ev[1].elapsed_time(ev[2])
+    stream_t = torch.cuda.current_stream(device)
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+    counts = torch.zeros(2, dtype=torch.int64, device=device)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if stage_ms is not None else None
+    if ev:
+        ev[0].record(stream_t)
+    _lib.call("pgr_march_count", device, C.byref(g), _lib.ptr(sdf), _lib.ptr(ws), ws.numel(), _lib.ptr(counts))
+    if ev:
+        ev[1].record(stream_t)
+    nv, nf = (int(x) for x in counts.cpu())
+    if nv >= 2 ** 31 or nf >= 2 ** 31:
+        raise ValueError(f"{nv} vertices / {nf} faces: more than int32 indices hold; use a coarser grid")
+    vertices = torch.empty((max(nv, 1), 3), dtype=torch.float32, device=device)
+    faces = torch.empty((max(nf, 1), 3), dtype=torch.int32, device=device)
+    _lib.call("pgr_march_emit", device, C.byref(g), _lib.ptr(sdf), _lib.ptr(ws), ws.numel(), _lib.ptr(vertices),
+              _lib.ptr(faces))
+    if ev:
+        ev[2].record(stream_t)
+    out = Mesh(vertices[:nv].cpu().numpy(), faces[:nf].cpu().numpy())
+    if ev:
+        stage_ms["count"] = ev[0].elapsed_time(ev[1])
+        stage_ms["emit"] = ev[1].elapsed_time(ev[2])
     return out
 
 

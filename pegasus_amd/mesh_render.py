@@ -126,21 +126,18 @@ def render_depth(meshes: MeshSet, jobs: Sequence, K, size, margin=(0, 0), near: 
     out = torch.empty((J, Hc, Wc), dtype=torch.float32, device=device)
     straddle = torch.zeros(1, dtype=torch.int32, device=device)
     per_call = max(1, int(budget_bytes) // (4 * Hc * Wc))
-    with torch.cuda.device(device):
-        stream = _lib.stream_ptr(device)
-        for j0 in range(0, J, per_call):
-            chunk = jobs[j0:j0 + per_call]
-            arr = mesh_jobs(meshes, chunk, np.stack(Ks[j0:j0 + per_call]), (mx, my))
-            nbytes = int(L.pgr_mesh_depth_workspace_bytes(len(chunk), arr))
-            if nbytes == 0:
-                raise ValueError("pgr_mesh_depth_workspace_bytes rejected the jobs")
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-            count = torch.zeros(1, dtype=torch.int32, device=device)
-            _lib.check(L.pgr_mesh_depth(_lib.ptr(meshes.vertices), meshes.vertices.shape[0], _lib.ptr(meshes.faces),
-                                        meshes.faces.shape[0], len(chunk), arr, Wc, Hc, float(near),
-                                        _lib.ptr(out[j0:j0 + len(chunk)]), len(chunk), _lib.ptr(count), _lib.ptr(ws),
-                                        ws.numel(), stream), "pgr_mesh_depth")
-            straddle += count
+    for j0 in range(0, J, per_call):
+        chunk = jobs[j0:j0 + per_call]
+        arr = mesh_jobs(meshes, chunk, np.stack(Ks[j0:j0 + per_call]), (mx, my))
+        nbytes = int(L.pgr_mesh_depth_workspace_bytes(len(chunk), arr))
+        if nbytes == 0:
+            raise ValueError("pgr_mesh_depth_workspace_bytes rejected the jobs")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        count = torch.zeros(1, dtype=torch.int32, device=device)
+        _lib.call("pgr_mesh_depth", device, _lib.ptr(meshes.vertices), meshes.vertices.shape[0], _lib.ptr(meshes.faces),
+                  meshes.faces.shape[0], len(chunk), arr, Wc, Hc, float(near), _lib.ptr(out[j0:j0 + len(chunk)]), len(chunk),
+                  _lib.ptr(count), _lib.ptr(ws), ws.numel())
+        straddle += count
     return (out, straddle) if return_straddle else out
 
 
@@ -220,10 +217,8 @@ def reduce_gt_info(canvases, margin, scene_depth, frames, Ks, delta: float):
     mask = torch.empty((J, H, W), dtype=torch.uint8, device=dev)
     visib = torch.empty_like(mask)
     stats = torch.empty((J, _lib.PGR_GT_INFO_STATS), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().pgr_bop_gt_info(_lib.ptr(canvases), J, Wc, Hc, int(margin[0]), int(margin[1]),
-                                              _lib.ptr(scene_depth), F, W, H, J, arr, float(delta), _lib.ptr(mask),
-                                              _lib.ptr(visib), _lib.ptr(stats), _lib.stream_ptr(dev)), "pgr_bop_gt_info")
+    _lib.call("pgr_bop_gt_info", dev, _lib.ptr(canvases), J, Wc, Hc, int(margin[0]), int(margin[1]), _lib.ptr(scene_depth),
+              F, W, H, J, arr, float(delta), _lib.ptr(mask), _lib.ptr(visib), _lib.ptr(stats))
     return mask, visib, stats
 
 

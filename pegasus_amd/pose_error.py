@@ -208,22 +208,19 @@ def pose_errors(models: PoseErrorModels, obj_ids, R_est, t_est, R_gt, t_gt, K=No
     re_te = torch.empty((P, 2), dtype=torch.float64, device=dev)
     adi = torch.empty(P, dtype=torch.float32, device=dev) if "adi" in errors else None
     main = any(n != "adi" for n in errors)
-    with torch.cuda.device(dev):
-        stream = _lib.stream_ptr(dev)
-        for j0 in range(0, P, MAX_JOBS_PER_CALL):
-            part = jobs[j0:j0 + MAX_JOBS_PER_CALL]
-            n = len(part)
-            if main:
-                _lib.check(L.pgr_pose_errors(_lib.ptr(models.vertices), models.vertices.shape[0], _lib.ptr(models.syms),
-                                             models.syms.shape[0], n, _job_ptr(part), _lib.ptr(out[j0:j0 + n]),
-                                             _lib.ptr(re_te[j0:j0 + n]), stream), "pgr_pose_errors")
-            if adi is not None:
-                nbytes = int(L.pgr_pose_adi_workspace_bytes(n, _job_ptr(part)))
-                if nbytes == 0:
-                    raise ValueError("pgr_pose_adi_workspace_bytes rejected the jobs")
-                ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                _lib.check(L.pgr_pose_adi(_lib.ptr(models.vertices), models.vertices.shape[0], n, _job_ptr(part),
-                                          _lib.ptr(adi[j0:j0 + n]), _lib.ptr(ws), ws.numel(), stream), "pgr_pose_adi")
+    for j0 in range(0, P, MAX_JOBS_PER_CALL):
+        part = jobs[j0:j0 + MAX_JOBS_PER_CALL]
+        n = len(part)
+        if main:
+            _lib.call("pgr_pose_errors", dev, _lib.ptr(models.vertices), models.vertices.shape[0], _lib.ptr(models.syms),
+                      models.syms.shape[0], n, _job_ptr(part), _lib.ptr(out[j0:j0 + n]), _lib.ptr(re_te[j0:j0 + n]))
+        if adi is not None:
+            nbytes = int(L.pgr_pose_adi_workspace_bytes(n, _job_ptr(part)))
+            if nbytes == 0:
+                raise ValueError("pgr_pose_adi_workspace_bytes rejected the jobs")
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            _lib.call("pgr_pose_adi", dev, _lib.ptr(models.vertices), models.vertices.shape[0], n, _job_ptr(part),
+                      _lib.ptr(adi[j0:j0 + n]), _lib.ptr(ws), ws.numel())
     res = {}
     host = out.cpu().numpy().astype(np.float64) if main else None
     host64 = re_te.cpu().numpy() if ("re" in errors or "te" in errors) else None

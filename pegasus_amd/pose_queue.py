@@ -129,9 +129,7 @@ def flush_all():
                 ws = _workspace[dev] = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=dev)
             dirs, pinv = _sh_tables(dev)
             arr_t = (_lib.PgrPoseJob * len(sel))(*[jobs[i] for i in sel])
-            with torch.cuda.device(dev):
-                _lib.check(L.pgr_pose_objects(len(sel), arr_t, _lib.ptr(dirs), _lib.ptr(pinv), _lib.ptr(ws), int(ws.numel()),
-                                              _lib.stream_ptr(dev)), "pgr_pose_objects")
+            _lib.call("pgr_pose_objects", dev, len(sel), arr_t, _lib.ptr(dirs), _lib.ptr(pinv), _lib.ptr(ws), int(ws.numel()))
         for m, arr, dst in outs:
             m.__dict__[arr] = dst
         # (`keep` dies here: the caching allocator hands the sources' blocks out again in stream order, behind the launches)

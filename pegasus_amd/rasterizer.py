@@ -363,22 +363,20 @@ def forward_views(means3D, opacities, views: Sequence[ViewSpec], *, shs=None, co
     def enqueue(slot, capacity, early=False):
         """One asynchronous attempt on ``slot``'s workspace and pinned scratch: (scratch, event behind the status words)."""
         nonlocal ws
-        stream = _lib.stream_ptr(device)
-        with torch.cuda.device(device):
-            ws = workspace(("async", slot), capacity)
-            scratch = _WS.pinned(slot, L.pgr_host_scratch_bytes(nv))
-            args = (nv, cams, outs, _ptr(ws), ws.numel(), capacity, _ptr(scratch), scratch.numel(), stream)
-            if layers is not None:
-                _lib.check(L.pgr_forward_layers_async(scene, layers_ref, posed_ref, *args), "pgr_forward_layers_async")
-            elif early:
-                event = _WS.status_event(device, slot)
-                _lib.check(L.pgr_forward_posed_early_status(scene, sem, posed_ref, *args, C.c_void_p(event.cuda_event)),
-                           "pgr_forward_posed_early_status")
-                return scratch, event
-            else:
-                _lib.check(L.pgr_forward_posed_async(scene, sem, posed_ref, *args), "pgr_forward_posed_async")
-            event = torch.cuda.Event()
-            event.record(torch.cuda.current_stream(device))
+        ws = workspace(("async", slot), capacity)
+        scratch = _WS.pinned(slot, L.pgr_host_scratch_bytes(nv))
+        args = (nv, cams, outs, _ptr(ws), ws.numel(), capacity, _ptr(scratch), scratch.numel())
+        if layers is not None:
+            _lib.call("pgr_forward_layers_async", device, scene, layers_ref, posed_ref, *args)
+        elif early:
+            event = _WS.status_event(device, slot)
+            _lib.call("pgr_forward_posed_early_status", device, scene, sem, posed_ref, *args,
+                      after_stream=(C.c_void_p(event.cuda_event),))
+            return scratch, event
+        else:
+            _lib.call("pgr_forward_posed_async", device, scene, sem, posed_ref, *args)
+        event = torch.cuda.Event()
+        event.record(torch.cuda.current_stream(device))
         return scratch, event
 
     def waited_on(slot):
@@ -398,16 +396,14 @@ def forward_views(means3D, opacities, views: Sequence[ViewSpec], *, shs=None, co
         """One synchronous attempt on the pooled workspace: (status, per-view instance counts)."""
         nonlocal ws
         need = (C.c_int64 * nv)()
-        stream = _lib.stream_ptr(device)
-        with torch.cuda.device(device):
-            ws = workspace(0, capacity)
-            if stage_ms is not None:
-                ms = (C.c_float * _lib.PGR_NUM_STAGES)()
-                status = L.pgr_forward_batch_profiled(scene, sem, nv, cams, outs, _ptr(ws), ws.numel(), capacity, need,
-                                                      stream, ms)
-                stage_ms[:] = list(ms)
-            else:
-                status = L.pgr_forward_batch(scene, nv, cams, outs, _ptr(ws), ws.numel(), capacity, need, stream)
+        ws = workspace(0, capacity)
+        if stage_ms is not None:
+            ms = (C.c_float * _lib.PGR_NUM_STAGES)()
+            status = _lib.enqueue("pgr_forward_batch_profiled", device, scene, sem, nv, cams, outs, _ptr(ws), ws.numel(),
+                                  capacity, need, after_stream=(ms,))
+            stage_ms[:] = list(ms)
+        else:
+            status = _lib.enqueue("pgr_forward_batch", device, scene, nv, cams, outs, _ptr(ws), ws.numel(), capacity, need)
         return status, need
 
     def render_sync():
@@ -460,11 +456,9 @@ def block_visibility(means3D, views: Sequence[ViewSpec], *, scales=None, rotatio
     cams, _cam_tensors = camera_structs(views, device)
     groups, words = (n + 63) // 64, (nv + 31) // 32
     out = torch.zeros((groups, words), dtype=torch.int32, device=device)
-    with torch.cuda.device(device):
-        ws = torch.empty(L.pgr_block_visibility_workspace_bytes(n, nv) + 256, dtype=torch.uint8, device=device)
-        _lib.check(L.pgr_block_visibility(C.byref(scene), nv, cams, _ptr(ws), ws.numel(), _ptr(out),
-                                          _lib.stream_ptr(device)), "pgr_block_visibility")
-        torch.cuda.current_stream(device).synchronize()
+    ws = torch.empty(L.pgr_block_visibility_workspace_bytes(n, nv) + 256, dtype=torch.uint8, device=device)
+    _lib.call("pgr_block_visibility", device, C.byref(scene), nv, cams, _ptr(ws), ws.numel(), _ptr(out))
+    torch.cuda.current_stream(device).synchronize()
     bits = (out.unsqueeze(2) >> torch.arange(32, device=device, dtype=torch.int32)) & 1
     return bits.reshape(groups, words * 32)[:, :nv].bool()
 
@@ -485,12 +479,10 @@ def scene_prepare(n: int, tie_index: Optional[torch.Tensor] = None, semantic: Op
     if semantic is not None:
         sem = _lib.PgrSemantic(object_id=_ptr(semantic["object_id"]), colors=_ptr(semantic["colors"]),
                                n_env=int(semantic["n_env"]), k_objects=int(semantic["k"]))
-    with torch.cuda.device(device):
-        cache = torch.empty(int(L.pgr_scene_cache_bytes(int(n))) + 256, dtype=torch.uint8, device=device)
-        p_inv, p_u8 = C.c_void_p(), C.c_void_p()
-        _lib.check(L.pgr_scene_prepare(C.byref(scene), C.byref(sem) if sem is not None else None, _ptr(cache),
-                                       cache.numel(), C.byref(p_inv), C.byref(p_u8), _lib.stream_ptr(device)),
-                   "pgr_scene_prepare")
+    cache = torch.empty(int(L.pgr_scene_cache_bytes(int(n))) + 256, dtype=torch.uint8, device=device)
+    p_inv, p_u8 = C.c_void_p(), C.c_void_p()
+    _lib.call("pgr_scene_prepare", device, C.byref(scene), C.byref(sem) if sem is not None else None, _ptr(cache),
+              cache.numel(), C.byref(p_inv), C.byref(p_u8))
 
     def view(ptr, nbytes, dtype):
         if not ptr.value:

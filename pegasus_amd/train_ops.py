@@ -38,9 +38,8 @@ def image_loss_terms(x: torch.Tensor, y: torch.Tensor, lambda_dssim: float, want
     out = torch.empty(3, dtype=torch.float32, device=xc.device)
     grad = torch.empty_like(xc) if want_grad else None
     ws = torch.empty(L.pgr_image_loss_workspace_bytes(H, W), dtype=torch.uint8, device=xc.device)
-    with torch.cuda.device(xc.device):
-        _lib.check(L.pgr_image_loss(_lib.ptr(xc), _lib.ptr(yc), H, W, float(lambda_dssim), _lib.ptr(out), _lib.ptr(grad),
-                                    _lib.ptr(ws), ws.numel(), _lib.stream_ptr(xc.device)), "pgr_image_loss")
+    _lib.call("pgr_image_loss", xc.device, _lib.ptr(xc), _lib.ptr(yc), H, W, float(lambda_dssim), _lib.ptr(out), _lib.ptr(grad),
+              _lib.ptr(ws), ws.numel())
     return out, grad
 
 
@@ -100,10 +99,8 @@ def masked_image_loss_terms(x, alpha, y, mask, bg, lambda_dssim: float, lambda_a
     grad_a = torch.empty((1, H, W), dtype=torch.float32, device=dev) if (want_grad_alpha and ac is not None) else None
     ws = torch.empty(L.pgr_image_loss_masked_workspace_bytes(H, W), dtype=torch.uint8, device=dev)
     p = _lib.ptr
-    with torch.cuda.device(dev):
-        _lib.check(L.pgr_image_loss_masked(p(xc), p(yc), p(mc), p(bc), p(ac), H, W, float(lambda_dssim), float(lambda_alpha),
-                                           p(out), p(grad), p(grad_a), p(ws), ws.numel(), _lib.stream_ptr(dev)),
-                   "pgr_image_loss_masked")
+    _lib.call("pgr_image_loss_masked", dev, p(xc), p(yc), p(mc), p(bc), p(ac), H, W, float(lambda_dssim), float(lambda_alpha),
+              p(out), p(grad), p(grad_a), p(ws), ws.numel())
     return out, grad, grad_a
 
 
@@ -170,7 +167,6 @@ class FusedAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        L = _lib.lib()
         # one launch per (device, betas, eps) and per PGR_ADAM_MAX_GROUPS table entries -- one launch for a 3DGS model
         batches = {}
         written = []
@@ -205,8 +201,7 @@ class FusedAdam(torch.optim.Optimizer):
             for k in range(0, len(entries), _lib.PGR_ADAM_MAX_GROUPS):
                 chunk = entries[k:k + _lib.PGR_ADAM_MAX_GROUPS]
                 table = (_lib.PgrAdamGroup * len(chunk))(*(e for e, _ in chunk))
-                with torch.cuda.device(device):
-                    _lib.check(L.pgr_adam_step(table, len(chunk), b1, b2, eps, _lib.stream_ptr(device)), "pgr_adam_step")
+                _lib.call("pgr_adam_step", device, table, len(chunk), b1, b2, eps)
         if written:
             torch.autograd.graph.increment_version(written)
         return loss
@@ -225,11 +220,8 @@ def densify_stats(viewspace_grad: torch.Tensor, radii: torch.Tensor, grad_accum:
     if not ok or viewspace_grad.device != radii.device or radii.device.type != "cuda":
         raise ValueError("densify_stats: viewspace_grad [N,>=2] fp32, radii [N] int32, grad_accum / denom / max_radii2D "
                          "with N fp32 elements, all contiguous on one HIP device")
-    L = _lib.lib()
-    with torch.cuda.device(radii.device):
-        _lib.check(L.pgr_densify_stats(n, _lib.ptr(viewspace_grad), int(viewspace_grad.shape[1]), _lib.ptr(radii),
-                                       _lib.ptr(grad_accum), _lib.ptr(denom), _lib.ptr(max_radii2D),
-                                       _lib.stream_ptr(radii.device)), "pgr_densify_stats")
+    _lib.call("pgr_densify_stats", radii.device, n, _lib.ptr(viewspace_grad), int(viewspace_grad.shape[1]), _lib.ptr(radii),
+              _lib.ptr(grad_accum), _lib.ptr(denom), _lib.ptr(max_radii2D))
     torch.autograd.graph.increment_version([grad_accum, denom, max_radii2D])
 
 

@@ -286,3 +286,78 @@ def test_every_call_mode_after_an_instance_overflow(gpu_device, mode):
     assert R.capacity_hints()[key] == R.grown_capacity(peak, factor)
     if mode == "profiled":
         assert len(kw["stage_ms"]) == 5
+
+
+@pytest.mark.gpu
+def test_workspace_view_points_at_the_views_status_words(gpu_device):
+    """PgrWorkspaceView::num_instances is the view's two status words in the batch header -- [0] listed instances, [1]
+    overflow flag -- for every view of a batch.  Two views: the least at which a view's slice and its status words sit at
+    different strides."""
+    import torch
+    from pegasus_amd import graphics as G, rasterizer as R
+    dev = gpu_device
+    cloud, _ = scenes.scene_c1(n=300)
+    act = {k: torch.from_numpy(np.ascontiguousarray(a)).to(dev) for k, a in cloud.activated().items()}
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+    specs = []
+    for eye in ((0.0, 0.0, -3.0), (2.0, 0.5, -2.0)):
+        Rm, tv = G.look_at_opencv(eye, (0.0, 0.0, 0.0), up=(0.0, -1.0, 0.0))
+        v = scenes.make_view(Rm, tv, 48, 40, fovx=math.radians(50.0), fovy=math.radians(43.0))
+        specs.append(R.ViewSpec(v.height, v.width, v.tanfovx, v.tanfovy, t(np.zeros(3)), t(v.world_view_transform),
+                                t(v.full_proj_transform), t(v.camera_center)))
+    R.forward_views(act["means3d"], act["opacities"], specs, shs=act["shs"], scales=act["scales"], rotations=act["rotations"],
+                    sh_degree=3, want_radii=True)
+    torch.cuda.synchronize()
+    info = R.last_forward_info()
+    ws = info["workspace"]
+    assert info["n_views"] == 2
+    for v in range(2):
+        off = R.workspace_view(v)["num_instances"] - ws.data_ptr()
+        assert 0 <= off and off + 8 <= ws.numel()
+        words = ws[off:off + 8].cpu().numpy().view(np.uint32)
+        assert int(words[0]) == info["num_instances"][v] and int(words[0]) > 0, (v, words, info["num_instances"])
+        assert int(words[1]) == 0
+
+
+@pytest.mark.gpu
+def test_gateway_names_the_entry_in_its_errors(gpu_device):
+    """_lib.call raises with the entry's name; _lib.enqueue hands the raw status back.  (pgr_knn_mean_dist2 rejects a negative
+    count before any launch.)"""
+    from pegasus_amd import _lib
+    args = ("pgr_knn_mean_dist2", gpu_device, -1, None, None, None, 0)
+    with pytest.raises(ValueError, match="pgr_knn_mean_dist2"):
+        _lib.call(*args)
+    assert _lib.enqueue(*args) == _lib.PGR_ERR_INVALID_ARGUMENT
+
+
+@pytest.mark.gpu
+def test_gateway_uses_the_stream_current_at_the_call(gpu_device):
+    """A call made under torch.cuda.stream(s) runs on s, and nothing on its way synchronises the device: with the default
+    stream kept busy (some tens of milliseconds of matrix products), the call returns while that work is still running,
+    and after s.synchronize() ALONE its result is complete and equals the default stream's bit for bit."""
+    import torch
+    from pegasus_amd import masks as M
+    dev = gpu_device
+    g = torch.Generator().manual_seed(7)
+    colors = torch.rand((5, 3), generator=g)
+    img = colors[torch.randint(0, 5, (16, 16), generator=g)].permute(2, 0, 1).contiguous()
+    img = (img + 0.02 * torch.rand((3, 16, 16), generator=g)).to(dev)
+    colors = colors.to(dev)
+    want = M.color_masks(img, colors, 0.1)
+    out = torch.full_like(want, 7)
+    a = torch.ones((8192, 8192), device=dev)
+    b = torch.mm(a, a)                                     # (the first product also loads its kernel)
+    s = torch.cuda.Stream(device=dev)
+    torch.cuda.synchronize()
+    assert int(want.sum()) > 0
+    for _ in range(8):
+        torch.mm(a, a, out=b)
+    with torch.cuda.stream(s):
+        got = M.color_masks(img, colors, 0.1, out=out)
+    still_busy = not torch.cuda.current_stream(dev).query()
+    s.synchronize()
+    with torch.cuda.stream(s):
+        host = got.cpu()                                   # a copy on s: the default stream is not waited for
+    torch.cuda.synchronize()
+    assert still_busy, "the call waited for the default stream"
+    assert torch.equal(host, want.cpu())
