@@ -636,6 +636,53 @@ int32_t pgr_frame_record_layout(int32_t width, int32_t height, int32_t k, PgrRec
 int32_t pgr_pack_records(const float *color_b3hw, const float *depth_bhw, const uint8_t *masks_bkhw, int32_t n_images,
                          int32_t k, int32_t width, int32_t height, uint8_t *records, int64_t record_stride, void *stream);
 
+/* ---- COCO annotations of binary masks (pegasus_amd/coco.py; csrc/cocorle.hip.h) -------------------------------------------
+ * The BOP toolkit's bop_toolkit_lib/pycoco_utils.py on the device: binary_mask_to_rle, bbox_from_binary_mask,
+ * rle_to_binary_mask and the integer parts of compute_ious.  A mask is uint8 [height,width], row-major, masks of a stack
+ * follow each other without padding (mask k starts at byte k * height * width: no alignment is asked of it); a pixel is SET
+ * when its byte is non-zero.  width and height are 1..8192 each.  Everything is an integer and no result depends on the
+ * order of execution.
+ *
+ * Run-length encoding: pixels in column-major order, p = x * height + y; runs alternate and start with a run of zeros
+ * (counts[0] = 0 when pixel 0 is set); an all-zero mask is [H*W], an all-set one [0, H*W]; a run that leaves a column at its
+ * bottom and enters the next at its top is ONE run.  n_counts = transitions + 1 + (pixel 0 set).
+ *
+ * Two calls, as pgr_march_count / pgr_march_emit: the count pass leaves the masks as bit planes and per-column records in
+ * `workspace` (pgr_mask_rle_workspace_bytes: about H*W/8 + 16 W bytes per mask; 0 for n_masks <= 0 or a side outside
+ * 1..8192; device memory, 16-byte aligned) and writes
+ *   stats int32 [n_masks,6] = n_counts, area (set pixels), x_min, y_min, x_max, y_max of the set pixels
+ * (INT32_MAX / INT32_MIN extents for an empty mask, as pgr_bop_gt_info writes them; the COCO box is
+ * [x_min, y_min, x_max - x_min + 1, y_max - y_min + 1]).  The caller forms offsets int64 [n_masks+1], the exclusive sum of
+ * n_counts (device memory), allocates counts int32 [capacity] and calls the emit pass with the SAME workspace, untouched in
+ * between (`masks` is not read again): mask k's counts go to counts[offsets[k] .. offsets[k+1]).  `total` is offsets[n_masks]
+ * as the caller computed it: capacity < total, total < n_masks or total > n_masks * (H*W + 1) is refused on the host, and no
+ * store leaves counts[offsets[k] .. min(offsets[k+1], total)) whatever the device-side offsets hold.  No atomics: two runs
+ * give equal bytes.  The tile sizes below are the shapes at which the kernels change path (for tests). */
+#define PGR_RLE_WORD_ROWS 32         /* rows per bit-plane word */
+#define PGR_RLE_TILE_COLS 256        /* columns per wave of the plane kernel, and per workgroup of the column kernels */
+#define PGR_RLE_BLOCK_ROWS 128       /* rows per workgroup of the plane kernel */
+#define PGR_RLE_DECODE_CHUNK 256     /* runs a decode workgroup scans at a time */
+#define PGR_RLE_DECODE_MIN_SLICE 16384   /* pixels per decode workgroup, at least */
+#define PGR_RLE_DECODE_MAX_SLICES 64  /* decode workgroups per mask, at most: beyond, the slices grow */
+#define PGR_MASK_OVERLAP_CHUNK 16384 /* pixels per overlap workgroup */
+size_t pgr_mask_rle_workspace_bytes(int32_t n_masks, int32_t width, int32_t height);
+int32_t pgr_mask_rle_count(const uint8_t *masks, int32_t n_masks, int32_t width, int32_t height, int32_t *stats,
+                           void *workspace, size_t workspace_bytes, void *stream);
+int32_t pgr_mask_rle_emit(const uint8_t *masks, int32_t n_masks, int32_t width, int32_t height, const int64_t *offsets,
+                          int64_t total, int32_t *counts, int64_t capacity, const void *workspace, size_t workspace_bytes,
+                          void *stream);
+/* rle_to_binary_mask for the list form: masks uint8 [n_masks,height,width] of 0 / 1 from counts int32 (device) and offsets
+ * int64 [n_masks+1] (device; mask k's counts are counts[offsets[k] .. offsets[k+1])).  Every pixel is written once.
+ * Zero-length runs are legal anywhere.  Negative counts read as 0; pixels behind the last run are 0 and runs beyond H*W are
+ * cut -- the toolkit does the same silently, pegasus_amd.coco.rle_decode refuses such lists before it calls. */
+int32_t pgr_mask_rle_decode(const int32_t *counts, const int64_t *offsets, int32_t n_masks, int32_t width, int32_t height,
+                            uint8_t *masks, void *stream);
+/* inter int32 [n_a,n_b] = pixels set in both a[i] and b[j]; area_a int32 [n_a], area_b int32 [n_b] = set pixels; a and b
+ * uint8 [n,height,width].  The union is area_a[i] + area_b[j] - inter[i,j].  Integer atomic adds into outputs the call
+ * clears first: exact, whatever the order.  n_a, n_b >= 1. */
+int32_t pgr_mask_overlap(const uint8_t *a, int32_t n_a, const uint8_t *b, int32_t n_b, int32_t width, int32_t height,
+                         int32_t *inter, int32_t *area_a, int32_t *area_b, void *stream);
+
 /* ---- training step (pegasus_amd/train_ops.py) ----------------------------------------------------------------------------
  * Fused 3DGS image loss over x, y [3,H,W] fp32 (x: the render, y: the ground truth):
  *   loss = (1 - lambda) mean|x - y| + lambda (1 - mean SSIM(x, y))

@@ -138,6 +138,10 @@ class PgrPoseErrorJob(C.Structure):
 
 PGR_POSE_ERRORS = 6          # mssd, mspd, add, proj, re, te
 PGR_POSE_SYM_CHUNK = 4       # include/pegasus_raster.h PGR_POSE_SYM_CHUNK
+# include/pegasus_raster.h: the shapes at which the mask kernels change path (tests/test_coco_host.py holds them against it)
+PGR_RLE_WORD_ROWS, PGR_RLE_TILE_COLS, PGR_RLE_BLOCK_ROWS = 32, 256, 128
+PGR_RLE_DECODE_CHUNK, PGR_RLE_DECODE_MIN_SLICE, PGR_RLE_DECODE_MAX_SLICES, PGR_MASK_OVERLAP_CHUNK = 256, 16384, 64, 16384
+PGR_MASK_STATS = 6           # n_counts, area, x_min, y_min, x_max, y_max
 
 
 # every symbol include/pegasus_raster.h declares: name -> (restype, argtypes)
@@ -251,6 +255,14 @@ SYMBOLS = {
     "pgr_pose_adi_workspace_bytes": (C.c_size_t, [C.c_int32, C.POINTER(PgrPoseErrorJob)]),
     "pgr_pose_adi": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(PgrPoseErrorJob), C.c_void_p, C.c_void_p,
                                  C.c_size_t, C.c_void_p]),
+    "pgr_mask_rle_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "pgr_mask_rle_count": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
+                                       C.c_void_p]),
+    "pgr_mask_rle_emit": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                      C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pgr_mask_rle_decode": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "pgr_mask_overlap": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -1,0 +1,391 @@
+"""COCO annotations of a BOP dataset on the GPU: ``scene_gt_coco.json`` (the BOP toolkit's scripts/calc_gt_coco.py over
+bop_toolkit_lib/pycoco_utils.py), the reverse direction and the mask overlap the 2D detection / segmentation tasks are
+evaluated with.
+
+    python -m pegasus_amd.coco --dataset <dir> [--bbox_type modal]
+
+reads ``mask/``, ``mask_visib/``, ``scene_gt.json`` and ``scene_gt_info.json`` of every scene under ``<dataset>/train`` and
+writes ``scene_gt_coco.json`` (``scene_gt_coco_modal.json`` with modal boxes).
+
+The kernels and their rule are pinned in pegasus_amd/csrc/cocorle.hip.h: run lengths in column-major pixel order, starting
+with a run of zeros (``pycoco_utils.binary_mask_to_rle``), boxes ``[x, y, x_max - x + 1, y_max - y + 1]``
+(``pycoco_utils.bbox_from_binary_mask`` -- NOT the ``w = x_max - x_min`` of ``misc.calc_2d_bbox`` that scene_gt_info uses).
+
+Out of scope: polygon segmentations, compressed RLE strings (both need packages that are not requirements of this
+project: skimage, pycocotools), COCO mAP and merge_coco_annotations.
+"""
+from __future__ import annotations
+
+import argparse
+import datetime
+import json
+import sys
+from pathlib import Path
+from typing import Optional, Sequence
+
+import numpy as np
+
+from . import _lib
+
+MAX_SIDE = 8192
+IGNORE_BELOW = 0.1                   # calc_gt_coco.py: ignore = visib_fract < 0.1
+COCO_URL = "https://github.com/thodan/bop_toolkit"
+COMPRESSED_MESSAGE = ("a compressed RLE (a `counts` string) needs pycocotools to be read; only the list form "
+                      "(uncompressed counts) is supported")
+
+
+# ---- the device calls -------------------------------------------------------------------------------------------------
+def _device_masks(masks, what="masks"):
+    """uint8 [n,H,W], contiguous, on a HIP device (bool tensors are taken as their bytes)."""
+    import torch
+    if not torch.is_tensor(masks):
+        raise TypeError(f"{what}: a torch tensor on a HIP device is expected (there is no CPU path)")
+    if masks.device.type != "cuda":
+        raise RuntimeError(f"{what} must be on a HIP device; there is no CPU path")
+    if masks.dtype == torch.bool:
+        masks = masks.contiguous().view(torch.uint8)
+    if masks.dtype != torch.uint8 or masks.dim() != 3:
+        raise ValueError(f"{what} must be uint8 (or bool) [n,H,W]")
+    n, H, W = masks.shape
+    if n < 1 or not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
+        raise ValueError(f"{what}: at least one mask with sides 1..{MAX_SIDE}, got {tuple(masks.shape)}")
+    return masks.contiguous()
+
+
+def _count_pass(masks):
+    import torch
+    n, H, W = masks.shape
+    nbytes = int(_lib.lib().pgr_mask_rle_workspace_bytes(n, W, H))
+    if nbytes == 0:
+        raise ValueError(f"pgr_mask_rle_workspace_bytes rejected {n} masks of {W} x {H}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=masks.device)
+    stats = torch.empty((n, _lib.PGR_MASK_STATS), dtype=torch.int32, device=masks.device)
+    _lib.call("pgr_mask_rle_count", masks.device, _lib.ptr(masks), n, W, H, _lib.ptr(stats), _lib.ptr(ws), nbytes)
+    return stats, ws
+
+
+def mask_stats(masks):
+    """The count pass alone: int32 [n,6] on the masks' device -- n_counts, area, x_min, y_min, x_max, y_max (INT32_MAX /
+    INT32_MIN extents for an empty mask)."""
+    return _count_pass(_device_masks(masks))[0]
+
+
+def rle_encode(masks):
+    """``pycoco_utils.binary_mask_to_rle`` of a stack of masks uint8 [n,H,W] on the device.  Returns (counts, offsets,
+    stats): ``counts`` a device int32 tensor holding every mask's run lengths back to back, ``offsets`` a host int64 array
+    [n+1] (mask k: ``counts[offsets[k]:offsets[k+1]]``), ``stats`` the device int32 [n,6] of ``mask_stats``.  Between the
+    two passes the n values of n_counts come to the host (the one synchronisation of the call)."""
+    import torch
+    masks = _device_masks(masks)
+    n, H, W = masks.shape
+    stats, ws = _count_pass(masks)
+    n_counts = stats[:, 0].cpu().numpy().astype(np.int64)
+    offsets = np.zeros(n + 1, np.int64)
+    np.cumsum(n_counts, out=offsets[1:])
+    total = int(offsets[-1])
+    offsets_dev = torch.from_numpy(offsets).to(masks.device, non_blocking=True)
+    counts = torch.empty(total, dtype=torch.int32, device=masks.device)
+    _lib.call("pgr_mask_rle_emit", masks.device, _lib.ptr(masks), n, W, H, _lib.ptr(offsets_dev), total, _lib.ptr(counts),
+              total, _lib.ptr(ws), ws.numel())
+    return counts, offsets, stats
+
+
+def _rle_lists(rles, size):
+    """Host lists of counts and the common (H, W) of ``rles``: dicts {"counts": [...], "size": [H, W]} or bare lists."""
+    lists, sizes = [], set()
+    for r in rles:
+        c = r["counts"] if isinstance(r, dict) else r
+        if isinstance(c, (str, bytes)):
+            raise ValueError(COMPRESSED_MESSAGE)
+        if isinstance(r, dict) and r.get("size") is not None:
+            sizes.add((int(r["size"][0]), int(r["size"][1])))
+        lists.append(np.asarray(c, np.int64).reshape(-1))
+    if size is not None:
+        sizes.add((int(size[0]), int(size[1])))
+    if len(sizes) != 1:
+        raise ValueError(f"the masks of one call share one size [H, W]; got {sorted(sizes) or 'none'}")
+    return lists, next(iter(sizes))
+
+
+def check_counts(sums, minimum, n_pixels):
+    """Refuses what ``rle_to_binary_mask`` would clip or leave as a tail: every mask's counts are >= 0 and sum to H*W."""
+    sums = np.asarray(sums, np.int64)
+    if int(minimum) < 0:
+        raise ValueError("RLE counts must not be negative")
+    bad = np.flatnonzero(sums != n_pixels)
+    if len(bad):
+        raise ValueError(f"RLE counts of mask {int(bad[0])} sum to {int(sums[bad[0]])}, not to H*W = {n_pixels}")
+
+
+def rle_decode(rles, size=None, device="cuda"):
+    """``pycoco_utils.rle_to_binary_mask`` for the list form, on the device: uint8 [n,H,W] of 0 / 1.  ``rles``: a sequence of
+    annotation ``segmentation`` dicts ({"counts": [...], "size": [H, W]}) or of bare count lists with ``size`` = (H, W), or a
+    pair (counts, offsets) as ``rle_encode`` returns it with ``size``.  Zero-length runs are legal anywhere.  A mask whose
+    counts do not sum to H*W is refused (the toolkit clips it or leaves a tail silently), and so is a compressed ``counts``
+    string, which needs pycocotools."""
+    import torch
+    if isinstance(rles, dict):
+        rles = [rles]
+    pair = isinstance(rles, tuple) and len(rles) == 2 and (torch.is_tensor(rles[0]) or isinstance(rles[0], np.ndarray))
+    if pair:
+        if size is None:
+            raise ValueError("(counts, offsets) needs size=(H, W)")
+        H, W = int(size[0]), int(size[1])
+        offsets = np.ascontiguousarray(np.asarray(rles[1].cpu() if torch.is_tensor(rles[1]) else rles[1], np.int64))
+        counts = rles[0] if torch.is_tensor(rles[0]) else torch.from_numpy(np.ascontiguousarray(rles[0], np.int32))
+        if counts.dtype != torch.int32 or counts.dim() != 1:
+            raise ValueError("counts must be int32 [total]")
+        counts = counts.to(device if counts.device.type != "cuda" else counts.device).contiguous()
+        if offsets.ndim != 1 or len(offsets) < 2 or offsets[0] < 0 or (np.diff(offsets) < 0).any() or offsets[-1] > counts.numel():
+            raise ValueError("offsets must be a non-decreasing int64 [n+1] inside counts")
+        off_dev = torch.from_numpy(offsets).to(counts.device)
+        run = torch.cat([torch.zeros(1, dtype=torch.int64, device=counts.device), torch.cumsum(counts.to(torch.int64), 0)])
+        sums = (run[off_dev[1:]] - run[off_dev[:-1]]).cpu().numpy()
+        minimum = int(counts.min()) if counts.numel() else 0
+    else:
+        lists, (H, W) = _rle_lists(rles, size)
+        if not lists:
+            raise ValueError("no RLE to decode")
+        offsets = np.zeros(len(lists) + 1, np.int64)
+        np.cumsum([len(c) for c in lists], out=offsets[1:])
+        flat = np.concatenate(lists) if offsets[-1] else np.zeros(0, np.int64)
+        sums = np.asarray([int(c.sum()) for c in lists], np.int64)
+        minimum = int(flat.min()) if len(flat) else 0
+        if len(flat) and int(flat.max()) > 2 ** 31 - 1:
+            raise ValueError("RLE counts are 32-bit")
+    if not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
+        raise ValueError(f"size [H, W] = [{H}, {W}]: each side must be 1..{MAX_SIDE}")
+    check_counts(sums, minimum, H * W)
+    if not pair:
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("rle_decode needs a HIP device; there is no CPU path")
+        counts = torch.from_numpy(flat.astype(np.int32)).to(dev)
+        off_dev = torch.from_numpy(offsets).to(dev)
+    n = len(offsets) - 1
+    out = torch.empty((n, H, W), dtype=torch.uint8, device=counts.device)
+    _lib.call("pgr_mask_rle_decode", counts.device, _lib.ptr(counts), _lib.ptr(off_dev), n, W, H, _lib.ptr(out))
+    return out
+
+
+def mask_overlap(dt, gt):
+    """The integer parts of a mask IoU matrix, on the device: (inter int32 [n_dt,n_gt] = pixels set in both, area_dt int32
+    [n_dt], area_gt int32 [n_gt]) of two stacks uint8 [n,H,W] of one size; union = area_dt[:,None] + area_gt[None] - inter."""
+    import torch
+    dt, gt = _device_masks(dt, "dt"), _device_masks(gt, "gt")
+    if dt.shape[1:] != gt.shape[1:] or dt.device != gt.device:
+        raise ValueError("dt and gt must share their image size and device")
+    n_dt, H, W = dt.shape
+    n_gt = gt.shape[0]
+    inter = torch.empty((n_dt, n_gt), dtype=torch.int32, device=dt.device)
+    area_dt = torch.empty(n_dt, dtype=torch.int32, device=dt.device)
+    area_gt = torch.empty(n_gt, dtype=torch.int32, device=dt.device)
+    _lib.call("pgr_mask_overlap", dt.device, _lib.ptr(dt), n_dt, _lib.ptr(gt), n_gt, W, H, _lib.ptr(inter), _lib.ptr(area_dt),
+              _lib.ptr(area_gt))
+    return inter, area_dt, area_gt
+
+
+def mask_ious(dt, gt):
+    """Intersection over union between every mask of ``dt`` and of ``gt`` (uint8 [n,H,W] on the device): float64 [n_dt,n_gt]
+    on that device, 0 where the union is empty.
+
+    This is the IoU the docstring of ``pycoco_utils.compute_ious`` promises, not what that function returns: it forms the
+    intersections with an einsum over the BOOLEAN masks, so the "intersection" is any-overlap (dtype bool with numpy 2.2)
+    and the quotient is 1 / union or 0.  Only its ``unions`` and ``intersection > 0`` agree with the
+    counts of ``mask_overlap``, and only those are compared with the toolkit in the tests."""
+    import torch
+    inter, a, b = mask_overlap(dt, gt)
+    union = a[:, None].to(torch.int64) + b[None, :].to(torch.int64) - inter.to(torch.int64)
+    return torch.where(union > 0, inter.to(torch.float64) / union.clamp(min=1).to(torch.float64),
+                       torch.zeros((), dtype=torch.float64, device=inter.device))
+
+
+# ---- host side: annotations and the scene file ------------------------------------------------------------------------
+def _host(a):
+    return np.asarray(a.cpu() if hasattr(a, "cpu") else a)
+
+
+def bbox_from_stats(stats):
+    """``pycoco_utils.bbox_from_binary_mask`` from stats rows [..., 6]: int64 [..., 4] = x, y, w, h with w = x_max - x_min +
+    1 and h = y_max - y_min + 1 (the smallest box that holds every set pixel).  Rows of empty masks are meaningless: the
+    toolkit cannot box an empty mask either."""
+    s = _host(stats).astype(np.int64)
+    return np.stack([s[..., 2], s[..., 3], s[..., 4] - s[..., 2] + 1, s[..., 5] - s[..., 3] + 1], -1)
+
+
+def annotations_from_encoded(counts, offsets, stats_visib, stats_full, size, obj_ids, visib_fract, image_id,
+                             bbox_type="amodal", first=0):
+    """The annotations of one image from encoded masks on the host (see ``annotations``): instance k of the image is mask
+    ``first + k`` of the stack that was encoded.  ``stats_full`` may be None with modal boxes."""
+    if bbox_type not in ("amodal", "modal"):
+        raise ValueError(f"{bbox_type} is not a valid bounding box type")
+    if bbox_type == "amodal" and stats_full is None:
+        raise ValueError("amodal boxes need the full masks")
+    H, W = int(size[0]), int(size[1])
+    counts, offsets = _host(counts), _host(offsets).astype(np.int64)
+    sv = _host(stats_visib).astype(np.int64)
+    sf = _host(stats_full).astype(np.int64) if stats_full is not None else None
+    box_v = bbox_from_stats(sv)
+    box_f = bbox_from_stats(sf) if sf is not None else None
+    out = []
+    for k, obj_id in enumerate(obj_ids):
+        m = first + k
+        if sv[m, 1] < 1:
+            continue
+        if bbox_type == "amodal":
+            if sf[m, 1] < 1:
+                continue
+            box = box_f[m]
+        else:
+            box = box_v[m]
+        fract = None if visib_fract is None else visib_fract[k]
+        out.append({"image_id": int(image_id), "category_id": int(obj_id), "iscrowd": 0, "area": int(sv[m, 1]),
+                    "bbox": [int(e) for e in box],
+                    "segmentation": {"counts": [int(c) for c in counts[offsets[m]:offsets[m + 1]]], "size": [H, W]},
+                    "width": W, "height": H, "ignore": bool(fract < IGNORE_BELOW) if fract is not None else False})
+    return out
+
+
+def annotations(masks_visib, masks_full, obj_ids, visib_fract, image_id, bbox_type="amodal", backend=None):
+    """The inner loop of calc_gt_coco.py (lines 94-121) for one image: one ``create_annotation_info`` dict per instance,
+    WITHOUT its ``id`` (``scene_coco`` numbers them).  ``masks_visib`` / ``masks_full``: uint8 [K,H,W] on the device, in the
+    order of ``obj_ids`` (= the image's scene_gt entries); ``visib_fract`` [K] from scene_gt_info (None: unknown, nothing
+    is ignored).  An instance whose visible mask is empty is skipped; with amodal boxes one whose full mask is empty too.
+    ``bbox``: of the full mask (amodal) or of the visible one (modal); ``area`` and ``segmentation``: of the visible mask;
+    ``ignore = visib_fract < 0.1`` as a Python bool.  ``backend``: an object with ``rle_encode`` and ``mask_stats`` of this
+    module's signatures (default: this module, on the device)."""
+    if bbox_type == "amodal" and masks_full is None:
+        raise ValueError("amodal boxes need the full masks (silhouettes or meshes); without them only bbox_type='modal' "
+                         "is supported")
+    if len(obj_ids) == 0:
+        return []
+    enc = encode_stack(masks_visib, masks_full if bbox_type == "amodal" else None, backend)
+    return annotations_from_encoded(*enc, masks_visib.shape[-2:], obj_ids, visib_fract, image_id, bbox_type)
+
+
+def image_info(image_id, file_name, image_size) -> dict:
+    """``pycoco_utils.create_image_info``; ``image_size`` = [W, H]."""
+    return {"id": int(image_id), "file_name": str(file_name), "width": int(image_size[0]), "height": int(image_size[1]),
+            "date_captured": datetime.datetime.now(datetime.timezone.utc).replace(tzinfo=None).isoformat(" "), "license": 1,
+            "coco_url": "", "flickr_url": ""}
+
+
+def scene_coco(images, annotations_per_image: dict, obj_ids, dataset_name: str, split: str = "train") -> dict:
+    """The dict calc_gt_coco.py dumps for one scene.  ``images``: (image_id, file_name relative to the scene folder, [W,
+    H]) triples; ``annotations_per_image``: {image_id: the list ``annotations`` returned}.  Images and annotations go in
+    ascending image id, annotations of an image in instance order, and ``id`` counts from 1 over the annotations that
+    exist: the toolkit's ``continue`` for a skipped instance comes before its increment.  ``categories``: one per object id
+    of ``obj_ids`` (the toolkit lists the dataset's models)."""
+    now = datetime.datetime.now(datetime.timezone.utc).replace(tzinfo=None)
+    per = {int(k): v for k, v in annotations_per_image.items()}
+    out = {"info": {"description": f"{dataset_name}_{split}", "url": COCO_URL, "version": "0.1.0", "year": now.year,
+                    "contributor": "", "date_created": now.isoformat(" ")},
+           "licenses": [],
+           "categories": [{"id": int(o), "name": str(int(o)), "supercategory": str(dataset_name)} for o in obj_ids],
+           "images": [], "annotations": []}
+    next_id = 1
+    for image_id, file_name, size in sorted(images, key=lambda t: int(t[0])):
+        out["images"].append(image_info(image_id, file_name, size))
+        for a in per.get(int(image_id), []):
+            out["annotations"].append({"id": next_id, **a})
+            next_id += 1
+    return out
+
+
+def coco_file_name(bbox_type: str) -> str:
+    return "scene_gt_coco.json" if bbox_type == "amodal" else "scene_gt_coco_modal.json"
+
+
+def scene_obj_ids(scene_gt: dict) -> list:
+    """The categories of a scene written without a models directory: the object ids its scene_gt names, ascending."""
+    return sorted({int(e["obj_id"]) for entries in scene_gt.values() for e in entries})
+
+
+def recompute_dataset(dataset_dir, bbox_type: str = "amodal", backend=None, batch: int = 8, device="cuda"):
+    """``scene_gt_coco.json`` (``scene_gt_coco_modal.json`` with ``bbox_type='modal'``) of every scene under
+    <dataset>/train from its mask_visib/ and mask/ PNGs, scene_gt.json and scene_gt_info.json: scripts/calc_gt_coco.py.
+    ``backend``: see ``annotations`` (masks then stay host arrays); ``batch``: images encoded per call, at least 1."""
+    from .dataset_writer import decode_png
+    if bbox_type not in ("amodal", "modal"):
+        raise ValueError(f"{bbox_type} is not a valid bounding box type")
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError(f"batch = {batch}: at least one image per call")
+    dataset_dir = Path(dataset_dir)
+    scenes = sorted(p for p in (dataset_dir / "train").iterdir() if (p / "scene_gt.json").exists())
+    for scene in scenes:
+        gt = json.loads((scene / "scene_gt.json").read_text())
+        info_path = scene / "scene_gt_info.json"
+        if info_path.exists():
+            info = json.loads(info_path.read_text())
+        elif bbox_type == "modal":
+            info = None                                   # no visible fraction on record: nothing is ignored
+        else:
+            raise FileNotFoundError(f"{info_path} is missing (amodal annotations need scene_gt_info.json and mask/)")
+        ids = sorted(gt, key=int)
+        per_image, images = {}, []
+
+        def load(i, kind, k):
+            return decode_png((scene / kind / f"{int(i):06d}_{k:06d}.png").read_bytes())
+        for b0 in range(0, len(ids), batch):
+            chunk = ids[b0:b0 + batch]
+            visib = [load(i, "mask_visib", k) for i in chunk for k in range(len(gt[i]))]
+            full = [load(i, "mask", k) for i in chunk for k in range(len(gt[i]))] if bbox_type == "amodal" else None
+            if not visib:
+                for i in chunk:
+                    per_image[int(i)] = []
+                continue
+            size = visib[0].shape
+            enc = encode_stack(np.stack(visib), np.stack(full) if full is not None else None, backend, device)
+            at = 0
+            for i in chunk:
+                K = len(gt[i])
+                fract = [float(e["visib_fract"]) for e in info[i]] if info is not None else None
+                per_image[int(i)] = annotations_from_encoded(*enc, size, [int(e["obj_id"]) for e in gt[i]], fract, int(i),
+                                                             bbox_type, at)
+                at += K
+        for i in ids:
+            rgb = scene / "rgb" / f"{int(i):06d}.png"
+            size = _png_size(rgb) if rgb.exists() else None
+            if size is None:
+                first = next(iter(sorted((scene / "mask_visib").glob(f"{int(i):06d}_*.png"))), None)
+                size = _png_size(first) if first is not None else (0, 0)
+            images.append((int(i), f"rgb/{int(i):06d}.png", [size[0], size[1]]))
+        doc = scene_coco(images, per_image, scene_obj_ids(gt), dataset_dir.resolve().name)
+        (scene / coco_file_name(bbox_type)).write_text(json.dumps(doc))
+    return scenes
+
+
+def _png_size(path):
+    """(W, H) from a PNG's IHDR."""
+    import struct
+    head = Path(path).read_bytes()[:24]
+    return struct.unpack(">II", head[16:24])
+
+
+def encode_stack(visib, full=None, backend=None, device="cuda"):
+    """(counts, offsets, stats_visib, stats_full or None) of a stack of visible masks [n,H,W] and, for amodal boxes, of the
+    full masks: the run lengths of the first, only the count pass of the second.  Without a ``backend`` host arrays go to
+    ``device`` first."""
+    be = sys.modules[__name__] if backend is None else backend
+    if backend is None:
+        import torch
+        to_dev = lambda a: a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a)).to(device)
+        visib, full = to_dev(visib), (to_dev(full) if full is not None else None)
+    counts, offsets, stats = be.rle_encode(visib)
+    return counts, offsets, stats, (be.mask_stats(full) if full is not None else None)
+
+
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    p = argparse.ArgumentParser(prog="python -m pegasus_amd.coco", description=__doc__.split("\n\n")[0])
+    p.add_argument("--dataset", required=True)
+    p.add_argument("--bbox_type", default="amodal", choices=["amodal", "modal"])
+    p.add_argument("--batch", type=int, default=8)
+    a = p.parse_args(argv)
+    scenes = recompute_dataset(a.dataset, a.bbox_type, batch=a.batch)
+    print(f"wrote {coco_file_name(a.bbox_type)} of {len(scenes)} scene(s)")
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

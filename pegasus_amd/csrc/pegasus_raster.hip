@@ -18,6 +18,7 @@
 
 #include "backward.hip.h"
 #include "blockcull.hip.h"
+#include "cocorle.hip.h"
 #include "knn.hip.h"
 #include "mesh.hip.h"
 #include "meshraster.hip.h"
@@ -1543,6 +1544,107 @@ int32_t pgr_pose_adi(const float* vertices, int64_t n_vertices, int32_t n_jobs, 
         pose_adi_mean_kernel<<<1, 64, 0, stream>>>(T, partials, adi);
     }
     return hip_ok(hipGetLastError(), "pose_adi launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+// ---- COCO annotations: mask run-length encoding, decoding, overlap counts (cocorle.hip.h) -------------------------------
+namespace {
+constexpr int32_t RLE_MAX_SIDE = 8192;
+constexpr int64_t RLE_MAX_BLOCKS = 0x7fffffff;
+struct RleLayout { size_t planes, columns, total; int S, Wp, col_tiles, row_groups, col_blocks; int64_t plane_blocks, column_blocks; };
+bool rle_shape_ok(int64_t n_masks, int32_t width, int32_t height) {
+    return n_masks >= 1 && n_masks <= INT32_MAX && width >= 1 && width <= RLE_MAX_SIDE && height >= 1 && height <= RLE_MAX_SIDE;
+}
+// the encoder's workspace: the bit planes, then 16 bytes per column; launches that would not fit a grid make it invalid
+bool rle_layout(int32_t n_masks, int32_t width, int32_t height, RleLayout* out) {
+    if (!rle_shape_ok(n_masks, width, height)) return false;
+    RleLayout L{};
+    L.S = (height + RLE_WORD_ROWS - 1) / RLE_WORD_ROWS;
+    L.Wp = (width + 3) / 4 * 4;
+    L.col_tiles = (width + RLE_TILE_COLS - 1) / RLE_TILE_COLS;
+    L.row_groups = (height + RLE_BLOCK_ROWS - 1) / RLE_BLOCK_ROWS;
+    L.col_blocks = (width + RLE_THREADS - 1) / RLE_THREADS;
+    L.plane_blocks = (int64_t)n_masks * L.col_tiles * L.row_groups;
+    L.column_blocks = (int64_t)n_masks * L.col_blocks;
+    if (L.plane_blocks > RLE_MAX_BLOCKS || L.column_blocks > RLE_MAX_BLOCKS) return false;
+    Carver c;
+    L.planes = c.take((size_t)n_masks * L.S * L.Wp * sizeof(uint32_t));
+    L.columns = c.take((size_t)n_masks * width * sizeof(RleColumn));
+    L.total = c.off;
+    *out = L;
+    return true;
+}
+bool rle_workspace_aligned(const void* workspace) { return reinterpret_cast<uintptr_t>(workspace) % 16 == 0; }
+}  // namespace
+
+size_t pgr_mask_rle_workspace_bytes(int32_t n_masks, int32_t width, int32_t height) {
+    RleLayout L;
+    return rle_layout(n_masks, width, height, &L) ? L.total : 0;
+}
+
+int32_t pgr_mask_rle_count(const uint8_t* masks, int32_t n_masks, int32_t width, int32_t height, int32_t* stats, void* workspace,
+                           size_t workspace_bytes, void* stream_v) {
+    RleLayout L;
+    if (!masks || !stats || !workspace || !rle_workspace_aligned(workspace) || !rle_layout(n_masks, width, height, &L))
+        return PGR_ERR_INVALID_ARGUMENT;
+    if (workspace_bytes < L.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    char* ws = static_cast<char*>(workspace);
+    auto* planes = reinterpret_cast<uint32_t*>(ws + L.planes);
+    auto* columns = reinterpret_cast<RleColumn*>(ws + L.columns);
+    rle_planes_kernel<<<(unsigned)L.plane_blocks, RLE_THREADS, 0, stream>>>(masks, width, height, L.S, L.Wp, L.col_tiles,
+                                                                            L.row_groups, planes);
+    rle_columns_kernel<<<(unsigned)L.column_blocks, RLE_THREADS, 0, stream>>>(planes, width, height, L.S, L.Wp, L.col_blocks,
+                                                                              columns);
+    rle_scan_kernel<<<(unsigned)n_masks, RLE_THREADS, 0, stream>>>(columns, width, height, stats);
+    return hip_ok(hipGetLastError(), "mask_rle_count launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+int32_t pgr_mask_rle_emit(const uint8_t* masks, int32_t n_masks, int32_t width, int32_t height, const int64_t* offsets,
+                          int64_t total, int32_t* counts, int64_t capacity, const void* workspace, size_t workspace_bytes,
+                          void* stream_v) {
+    RleLayout L;
+    if (!masks || !offsets || !counts || !workspace || !rle_workspace_aligned(workspace) ||
+        !rle_layout(n_masks, width, height, &L))
+        return PGR_ERR_INVALID_ARGUMENT;
+    // every mask has at least one count and at most one per pixel plus one
+    if (total < n_masks || total > (int64_t)n_masks * ((int64_t)width * height + 1) || capacity < total)
+        return PGR_ERR_INVALID_ARGUMENT;
+    if (workspace_bytes < L.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    const char* ws = static_cast<const char*>(workspace);
+    rle_emit_kernel<<<(unsigned)L.column_blocks, RLE_THREADS, 0, static_cast<hipStream_t>(stream_v)>>>(
+        reinterpret_cast<const uint32_t*>(ws + L.planes), reinterpret_cast<const RleColumn*>(ws + L.columns), width, height, L.S,
+        L.Wp, L.col_blocks, reinterpret_cast<const long long*>(offsets), counts, (long long)total);
+    return hip_ok(hipGetLastError(), "mask_rle_emit launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+int32_t pgr_mask_rle_decode(const int32_t* counts, const int64_t* offsets, int32_t n_masks, int32_t width, int32_t height,
+                            uint8_t* masks, void* stream_v) {
+    if (!counts || !offsets || !masks || !rle_shape_ok(n_masks, width, height)) return PGR_ERR_INVALID_ARGUMENT;
+    const int64_t HW = (int64_t)width * height;
+    const int64_t slice = std::max<int64_t>(RLE_DECODE_MIN_SLICE, (HW + RLE_DECODE_MAX_SLICES - 1) / RLE_DECODE_MAX_SLICES);
+    const int64_t slices = (HW + slice - 1) / slice;
+    if ((int64_t)n_masks * slices > RLE_MAX_BLOCKS) return PGR_ERR_INVALID_ARGUMENT;
+    rle_decode_kernel<<<(unsigned)(n_masks * slices), RLE_THREADS, 0, static_cast<hipStream_t>(stream_v)>>>(
+        counts, reinterpret_cast<const long long*>(offsets), width, height, (int)slices, (int)slice, masks);
+    return hip_ok(hipGetLastError(), "mask_rle_decode launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+int32_t pgr_mask_overlap(const uint8_t* a, int32_t n_a, const uint8_t* b, int32_t n_b, int32_t width, int32_t height,
+                         int32_t* inter, int32_t* area_a, int32_t* area_b, void* stream_v) {
+    if (!a || !b || !inter || !area_a || !area_b || !rle_shape_ok(n_a, width, height) || !rle_shape_ok(n_b, width, height))
+        return PGR_ERR_INVALID_ARGUMENT;
+    const size_t HW = (size_t)width * height;
+    const int64_t chunks = (int64_t)((HW + OVERLAP_CHUNK - 1) / OVERLAP_CHUNK);
+    const int64_t pairs = (int64_t)n_a * n_b;
+    if (pairs > RLE_MAX_BLOCKS || pairs * chunks > RLE_MAX_BLOCKS) return PGR_ERR_INVALID_ARGUMENT;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    if (!hip_ok(hipMemsetAsync(inter, 0, (size_t)pairs * sizeof(int32_t), stream), "mask_overlap clear") ||
+        !hip_ok(hipMemsetAsync(area_a, 0, (size_t)n_a * sizeof(int32_t), stream), "mask_overlap clear") ||
+        !hip_ok(hipMemsetAsync(area_b, 0, (size_t)n_b * sizeof(int32_t), stream), "mask_overlap clear"))
+        return PGR_ERR_LAUNCH_FAILURE;
+    mask_overlap_kernel<<<(unsigned)(pairs * chunks), RLE_THREADS, 0, stream>>>(a, n_a, b, n_b, HW, (int)chunks, inter, area_a,
+                                                                               area_b);
+    return hip_ok(hipGetLastError(), "mask_overlap launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
 }
 
 // ---- training step: fused L1 + D-SSIM loss, Adam over all parameter groups, densification statistics (train.hip.h) ------

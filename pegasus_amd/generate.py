@@ -33,6 +33,9 @@ def main():
                     help="take mask/, mask_visib/ and scene_gt_info.json from the depth renders of the obj_NNNNNN.ply meshes "
                          "(millimetres, as pegasus_amd.mesh writes them) of this directory, as the BOP toolkit does")
     ap.add_argument("--delta", type=float, default=15.0, help="visibility tolerance in millimetres for --gt-from-meshes")
+    ap.add_argument("--gt-coco", nargs="?", const="amodal", default=None, choices=["amodal", "modal"],
+                    help="also write scene_gt_coco.json (modal: scene_gt_coco_modal.json): the COCO annotations of the BOP "
+                         "toolkit's calc_gt_coco.py, encoded on the GPU from the masks that are written")
     args = ap.parse_args()
 
     import os
@@ -100,12 +103,12 @@ def main():
         t_gpu += time.perf_counter() - t1
         gt, cam = bop_pose.batch_pose_records(vs, m2w, boxes=boxes)
         w.add_batch(frames, gt, cam, n=len(vs), silhouettes=sil, frame_ids=ids, record_shape=(H, W, fr.K), meshes=meshes,
-                    delta=args.delta)
+                    delta=args.delta, coco=args.gt_coco or False)
     scene = w.close(write_json=False)
     if world > 1:
         import torch.distributed as dist
         records = [None] * world if rank == 0 else None
-        dist.gather_object((w.scene_gt, w.scene_camera, w.scene_gt_info), records, dst=0)
+        dist.gather_object((w.scene_gt, w.scene_camera, w.scene_gt_info, w.coco_records()), records, dst=0)
         if rank == 0:
             w.merge_records(records[1:])
     if rank == 0:
