@@ -453,7 +453,12 @@ int32_t pgr_mesh_depth(const float *vertices, int64_t n_vertices, const int32_t 
  *   visib = (dist_model - dist_test <= delta or dist_test == 0) and dist_model > 0        (visibility.py, mode bop19)
  * Outputs: `mask` and `mask_visib` uint8 [n_jobs,height,width] (0/1), and `stats` int32 [n_jobs,11]: px_count_all (whole
  * canvas), px_count_valid, px_count_visib, then min x, min y, max x, max y of the silhouette over the canvas and of the visible
- * mask, in image coordinates (INT32_MAX / INT32_MIN when empty). */
+ * mask, in image coordinates (INT32_MAX / INT32_MIN when empty).
+ * The two shapes at which the launch changes path (tests/gt_info_cases.py is built around them): jobs go to the device
+ * PGR_GT_INFO_JOBS_PER_LAUNCH at a time, and a canvas of more than PGR_GT_INFO_BLOCKS_X * 256 pixels is walked by a
+ * grid-stride loop. */
+#define PGR_GT_INFO_JOBS_PER_LAUNCH 64  /* jobs per kernel launch (one job table per launch) */
+#define PGR_GT_INFO_BLOCKS_X 512        /* workgroups of 256 pixels per job, at most */
 typedef struct PgrGtInfoJob {
     int32_t slot, frame;
     double fx, fy, cx, cy;

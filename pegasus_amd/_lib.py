@@ -128,6 +128,9 @@ class PgrGtInfoJob(C.Structure):
 
 
 PGR_GT_INFO_STATS = 11
+# include/pegasus_raster.h: jobs per launch and workgroups per job of pgr_bop_gt_info (tests/test_gt_info_host.py holds them
+# against it)
+PGR_GT_INFO_JOBS_PER_LAUNCH, PGR_GT_INFO_BLOCKS_X = 64, 512
 
 
 class PgrPoseErrorJob(C.Structure):

@@ -273,9 +273,9 @@ __global__ __launch_bounds__(256) void mesh_finalize_kernel(uint32_t* __restrict
 //       visib = (d_diff <= delta or dist_test == 0) and dist_model > 0.
 // One int32 row per job: px_count_all, px_count_valid, px_count_visib, then min x, min y, max x, max y of the silhouette
 // and of the visible mask (image coordinates, INT32_MAX / INT32_MIN when empty).  Integer atomics only.
-constexpr int GT_JOBS_PER_LAUNCH = 64;
+constexpr int GT_JOBS_PER_LAUNCH = PGR_GT_INFO_JOBS_PER_LAUNCH;
 constexpr int GT_STATS = 11;
-constexpr int GT_BLOCKS_X = 512;
+constexpr int GT_BLOCKS_X = PGR_GT_INFO_BLOCKS_X;
 
 struct GtJobDev {
     int32_t slot, frame;

@@ -1,4 +1,4 @@
-"""Generates tests/golden/mesh_gt_info.npz and tests/golden/mesh_vsd.npz from the BOP toolkit of the reference checkout.
+"""Generates tests/golden/mesh_gt_info.npz, mesh_vsd.npz and mesh_vsd_edges.npz from the BOP toolkit of the reference checkout.
 
 Run on the build machine only (``python tests/golden/make_golden_mesh_render.py``); nothing at test time reads the
 reference.  Only inputs and the toolkit's OUTPUTS are stored, no reference source text.  The depth images come from the
@@ -9,6 +9,9 @@ them:
                  nearer scene, missing-depth holes, and depth differences exactly at delta and one float32 step either side
   mesh_vsd       pose_error.vsd with a stub renderer that returns those NumPy depth images: 12 (estimate, GT) pairs, both
                  cost types, several taus, with and without normalisation by the diameter
+  mesh_vsd_edges pose_error.vsd through the same stub on hand-written depth images: an empty union (errors all 1), an estimate
+                 wholly outside the image, an all-zero test image, a distance exactly equal to tau under 'step', 'tlinear'
+                 clipping at 1, 1x1 images; both cost types, normalised and not
 """
 import sys
 import types
@@ -172,8 +175,79 @@ def vsd_golden():
                         depth_test=test, depth_est=d_est, depth_gt=d_gt, **errs)
 
 
+def vsd_edge_groups():
+    """The inputs of mesh_vsd_edges.npz: groups of estimates against one ground-truth render and one test image, written by
+    hand.  Per group: name, K, delta, taus, diameter, depth_gt [H,W], depth_test [H,W], depth_est [B,H,W] and the names of
+    the estimates.  At the principal point (an integer pixel here) the distance IS the depth, so differences there are exact."""
+    diameter = 143.0
+    K = np.array([[90.0, 0, 4.0], [0, 92.0, 3.0], [0, 0, 1.0]])
+    H, W = 6, 8
+    blob = np.zeros((H, W), np.float32)
+    blob[1:5, 2:7] = 600.0 + np.arange(20, dtype=np.float32).reshape(4, 5)
+    centre = blob[3, 4]
+    taus = [0.05, 20.0 / diameter, float(np.nextafter(20.0 / diameter, 1.0)), 0.5, 20.0, float(np.nextafter(20.0, 100.0)), 60.0]
+    test = np.where(blob > 0, blob + 2.0, 1000.0).astype(np.float32)
+    test[:, :3] = 380.0                                                       # an occluder over the left columns
+    test[2, 5] = test[4, 6] = 0.0                                             # missing depth
+    shifted = np.where(blob > 0, blob + 7.0, 0).astype(np.float32)
+    shifted[3, 4] = centre + 20.0                                             # |dist_gt - dist_est| == 20 == tau exactly (step: >=)
+    shifted[1, 2:7] = 0.0                                                     # the estimate misses a row
+    far = np.where(blob > 0, blob + 10.0, 0).astype(np.float32)              # visible, and 10 away: tlinear 10 / 0.05 clips at 1,
+    far[0, 1:4] = 590.0                                                       # 10 / 20 does not; and pixels the GT does not cover
+    zeros = np.zeros((H, W), np.float32)
+    groups = [dict(name="blob", K=K, delta=15.0, taus=taus, diameter=diameter, depth_gt=blob, depth_test=test,
+                   depth_est=np.stack([zeros, shifted, far, blob]), est_names=["outside_the_image", "at_tau", "clipped", "perfect"]),
+              dict(name="no_gt", K=K, delta=15.0, taus=taus, diameter=diameter, depth_gt=zeros, depth_test=test,
+                   depth_est=np.stack([zeros, far, shifted]), est_names=["empty_union", "estimate_only", "estimate_only_2"]),
+              dict(name="zero_test", K=K, delta=15.0, taus=taus, diameter=diameter, depth_gt=blob, depth_test=zeros,
+                   depth_est=np.stack([shifted, zeros, far]), est_names=["at_tau", "outside_the_image", "clipped"])]
+    one = lambda v: np.full((1, 1), v, np.float32)
+    for name, K1 in (("pixel_on_axis", np.array([[50.0, 0, 0.0], [0, 50.0, 0.0], [0, 0, 1.0]])),
+                     ("pixel_off_axis", np.array([[50.0, 0, 0.3], [0, 55.0, -0.4], [0, 0, 1.0]]))):
+        groups.append(dict(name=name, K=K1, delta=15.0, taus=taus, diameter=diameter, depth_gt=one(600.0), depth_test=one(605.0),
+                           depth_est=np.stack([one(620.0), one(0.0), one(600.0)]), est_names=["at_tau", "outside_the_image", "perfect"]))
+    return groups
+
+
+def vsd_edges_golden():
+    """mesh_vsd_edges.npz: pose_error.vsd at its edges, through the same stub renderer.  errors [B, cost (step, tlinear),
+    normalised (0, 1), tau] per group."""
+    misc, _, pose_error = toolkit()
+
+    class Stub:
+        def __init__(self, est, gt):
+            self.queue = [est, gt]
+
+        def render_object(self, obj_id, R, t, fx, fy, cx, cy):
+            return {"depth": self.queue.pop(0)}
+    out = dict(groups=np.asarray([g["name"] for g in vsd_edge_groups()]))
+    for g in vsd_edge_groups():
+        rows = []
+        for est in g["depth_est"]:
+            per_cost = []
+            for cost in ("step", "tlinear"):
+                per_norm = []
+                for norm in (False, True):
+                    fresh(misc)
+                    per_norm.append(pose_error.vsd(np.eye(3), np.zeros((3, 1)), np.eye(3), np.zeros((3, 1)), g["depth_test"].copy(), g["K"],
+                                                   g["delta"], g["taus"], norm, g["diameter"], Stub(est.copy(), g["depth_gt"].copy()), 1, cost))
+                per_cost.append(per_norm)
+            rows.append(per_cost)
+        errors = np.asarray(rows, np.float64)
+        print(g["name"], errors.shape, np.round(errors[:, 1, 0], 4).tolist())
+        for key in ("K", "depth_gt", "depth_test", "depth_est"):
+            out[f"{g['name']}_{key}"] = g[key]
+        out[f"{g['name']}_delta"] = np.float64(g["delta"])
+        out[f"{g['name']}_taus"] = np.asarray(g["taus"], np.float64)
+        out[f"{g['name']}_diameter"] = np.float64(g["diameter"])
+        out[f"{g['name']}_est_names"] = np.asarray(g["est_names"])
+        out[f"{g['name']}_errors"] = errors
+    np.savez_compressed(OUT / "mesh_vsd_edges.npz", **out)
+
+
 if __name__ == "__main__":
     gt_info_golden()
     vsd_golden()
-    for p in ("mesh_gt_info.npz", "mesh_vsd.npz"):
+    vsd_edges_golden()
+    for p in ("mesh_gt_info.npz", "mesh_vsd.npz", "mesh_vsd_edges.npz"):
         print(p, (OUT / p).stat().st_size, "bytes")
