@@ -17,8 +17,9 @@
  *   pgr_pack_records       <- the same casts for a whole batch + the K masks as bit planes, ONE record per frame: what the
  *                             writer threads of /root/reference/pegasus.py:346-358 consume / what the gather to the root
  *                             rank carries
- *   pgr_forward_layers_async <- render_silhouette_mask, /root/reference/src/gs/render.py:36-65 (every object rendered
+ *   pgr_forward + PgrLayers <- render_silhouette_mask, /root/reference/src/gs/render.py:36-65 (every object rendered
  *                             ALONE and thresholded), for all objects and a batch of cameras in one pipeline pass
+ *   pgr_backward           <- _C.rasterize_gaussians_backward(...), training only: /root/reference/src/gs/gs_training.py:7,46
  *
  * Conventions
  *   - Every pointer in PgrScene / PgrCamera / PgrOutputs is a DEVICE address of a contiguous
@@ -42,7 +43,7 @@
 extern "C" {
 #endif
 
-#define PGR_ABI_VERSION 3
+#define PGR_ABI_VERSION 4
 #define PGR_TILE_SIZE 16
 
 typedef enum PgrStatus {
@@ -79,8 +80,8 @@ typedef struct PgrScene {
                                     _features_rest (coefficients 1 .. sh_stride-1).  Saves the caller the torch.cat of
                                     get_features (/root/reference/src/gs/gaussian_model.py:118-121: 768 MB moved per
                                     render() of a freshly merged 2 M-Gaussian scene).  Same coefficients, same arithmetic:
-                                    results are bit-identical.  Forward entry points without PgrPosedObjects only
-                                    (with poses, and in pgr_backward -- whose SH gradient is one [n,sh_stride,3] array --
+                                    results are bit-identical.  pgr_forward without PgrPosedObjects only (with poses, and
+                                    in pgr_backward -- whose SH gradient is one [n,sh_stride,3] array --
                                     PGR_ERR_INVALID_ARGUMENT). */
 } PgrScene;
 
@@ -112,7 +113,7 @@ typedef struct PgrOutputs {
                                     25.6 MB of fp32 / mask planes beside it) */
     float *depth;                /* [1,H,W]  required (same exceptions; NULL exactly when color is): sum_i T_i alpha_i z_i, no
                                     bg term; PgrCamera::depth_mode selects the normalised form */
-    int32_t *radii;              /* [n]      required */
+    int32_t *radii;              /* [n]      optional (NULL); a view pgr_backward is to differentiate needs it */
     float *final_T;              /* [H,W]    optional (NULL) */
     uint32_t *n_contrib;         /* [H,W]    optional (NULL) */
     float *sem_color;            /* [3,H,W]  the objects-only semantic render: REQUIRED on every view of a call that
@@ -123,7 +124,7 @@ typedef struct PgrOutputs {
     uint8_t *sem_masks;          /* [K,H,W]  optional: the K colour-distance masks of the semantic image
                                     (pgr_color_masks of sem_color against PgrSemantic::mask_colors, bit for bit), written by
                                     the compositor's epilogue from the pixel it holds in registers -- needs
-                                    PgrSemantic::mask_colors.  In a LAYERED call (pgr_forward_layers_async) the one output:
+                                    PgrSemantic::mask_colors.  In a LAYERED call (PgrForwardCall::layers) the one output:
                                     [n_layers,H,W], plane k = layer k's image against mask_colors[k]. */
     uint8_t *record;             /* optional: this view's FRAME RECORD (PgrRecordLayout below: uint8 rgb | uint16 depth mm |
                                     mask bit planes, pgr_frame_record_layout(width, height, K) bytes), written by the
@@ -173,44 +174,12 @@ const char *pgr_last_hip_error(void);
 /* Bytes of workspace needed to render one view of `n` Gaussians at width x height with room for
  * `max_instances` (Gaussian,tile) pairs. */
 size_t pgr_workspace_bytes(int32_t n, int32_t width, int32_t height, int64_t max_instances);
-/* Same for a batch of `n_views` views in flight at once (pgr_forward_batch). */
+/* Same for a batch of `n_views` views in flight at once. */
 size_t pgr_batch_workspace_bytes(int32_t n, int32_t width, int32_t height, int64_t max_instances_per_view,
                                  int32_t n_views);
 
-/* Render one view.  `num_instances` (host, optional) receives the number of listed (Gaussian, tile)
- * instances.  Everything is enqueued on `stream`; the call synchronises the stream once, at the end, to
- * read the instance count and the overflow flag (the reference synchronises mid-pipeline to read
- * num_rendered), so that an overflow is reported instead of returned as an image. */
-int32_t pgr_forward(const PgrScene *scene, const PgrCamera *camera, const PgrOutputs *out,
-                    void *workspace, size_t workspace_bytes, int64_t max_instances,
-                    int64_t *num_instances, void *stream);
-
-/* Render `n_views` views of ONE scene (the per-frame loop of /root/reference/pegasus.py:254-325 calls
- * render() once per camera over the same merged cloud; this is that loop as one call).  `cameras` and
- * `outs` are HOST arrays of n_views entries; all views share the image size; outs[v].radii may be NULL.
- * The batch is what fills an MI355X: the compositing of every (view, tile) list is one launch, ordered
- * longest list first, so no view waits on its own slowest tile.  One stream synchronisation per batch, at
- * its end (instance counts + overflow flags); `num_instances` (host, optional) receives n_views counts. */
-int32_t pgr_forward_batch(const PgrScene *scene, int32_t n_views, const PgrCamera *cameras,
-                          const PgrOutputs *outs, void *workspace, size_t workspace_bytes,
-                          int64_t max_instances_per_view, int64_t *num_instances, void *stream);
-
-/* Asynchronous form: enqueues the whole batch on `stream` and returns without synchronising.  `host_scratch`
- * is PINNED host memory of pgr_host_scratch_bytes(n_views) that the library uses to stage its pointer tables and
- * to receive the status words; it must stay untouched until `stream` has passed the call.  After synchronising,
- * pgr_batch_status(host_scratch, n_views, num_instances) returns PGR_OK or PGR_ERR_INSTANCE_OVERFLOW (frames of
- * an overflowed batch are not valid; re-run with a larger capacity).  Lets two batches -- e.g. the scene pass
- * and the semantic pass of a frame set -- run concurrently on two streams with two workspaces. */
+/* Pinned host memory an asynchronous pgr_forward call stages its tables in and receives its status words in. */
 size_t pgr_host_scratch_bytes(int32_t n_views);
-int32_t pgr_forward_batch_async(const PgrScene *scene, int32_t n_views, const PgrCamera *cameras,
-                                const PgrOutputs *outs, void *workspace, size_t workspace_bytes,
-                                int64_t max_instances_per_view, void *host_scratch, size_t host_scratch_size,
-                                void *stream);
-/* Same, with the fused semantic pass (`semantic` may be NULL = plain batch). */
-int32_t pgr_forward_frames_async(const PgrScene *scene, const PgrSemantic *semantic, int32_t n_views,
-                                 const PgrCamera *cameras, const PgrOutputs *outs, void *workspace,
-                                 size_t workspace_bytes, int64_t max_instances_per_view, void *host_scratch,
-                                 size_t host_scratch_size, void *stream);
 
 /* Dynamic scenes: per-view rigid poses of the scene's objects, applied INSIDE the preprocess instead of composing a
  * posed copy of the scene per time step (reference: update_object_pose + deepcopy + merge per frame,
@@ -226,25 +195,6 @@ typedef struct PgrPosedObjects {
                                    R[9] row-major, t[3], center[3], q[4] = R as unit quaternion (w,x,y,z), pad */
     int32_t k_objects;
 } PgrPosedObjects;
-/* pgr_forward_frames_async with per-view object poses (`posed` may be NULL = same as pgr_forward_frames_async). */
-int32_t pgr_forward_posed_async(const PgrScene *scene, const PgrSemantic *semantic, const PgrPosedObjects *posed,
-                                int32_t n_views, const PgrCamera *cameras, const PgrOutputs *outs, void *workspace,
-                                size_t workspace_bytes, int64_t max_instances_per_view, void *host_scratch,
-                                size_t host_scratch_size, void *stream);
-int32_t pgr_batch_status(const void *host_scratch, int32_t n_views, int64_t *num_instances);
-/* pgr_forward_posed_async whose status words reach the host EARLY.  The instance counts and overflow flags are final once the
- * tile scan has run -- a third into a single-view call -- and nothing later changes them: the scan stores them into
- * `host_scratch` itself (which must therefore be device-accessible at its host address: hipHostMalloc memory, what torch's
- * pin_memory() hands out) and `status_event` (a hipEvent_t) is recorded on `stream` right behind it.  After
- * hipEventSynchronize(status_event), pgr_batch_status(host_scratch, ...) is valid while scatter, sort and compositor still
- * run: the caller of a single view (PEGASUS's render(), /root/reference/src/gs/render.py:17-24 -- the upstream rasterizer
- * blocks on its own instance count in the middle of every call the same way) returns to its host code without leaving the
- * GPU idle; the outputs are complete in STREAM order, as for every asynchronous call.  On PGR_ERR_INSTANCE_OVERFLOW the rest
- * of the call does nothing; re-run with a larger capacity. */
-int32_t pgr_forward_posed_early_status(const PgrScene *scene, const PgrSemantic *semantic, const PgrPosedObjects *posed,
-                                       int32_t n_views, const PgrCamera *cameras, const PgrOutputs *outs, void *workspace,
-                                       size_t workspace_bytes, int64_t max_instances_per_view, void *host_scratch,
-                                       size_t host_scratch_size, void *stream, void *status_event);
 
 /* Per-SCENE constants the batch calls would otherwise rebuild on every call (round 3: invert_tie_index_kernel and
  * pack_object_ids_kernel, 24 us + 76 MB of traffic per batch of the 2 M-Gaussian scene): the inverse of
@@ -263,7 +213,7 @@ int32_t pgr_scene_prepare(const PgrScene *scene, const PgrSemantic *semantic, vo
  * rows; projection, lists and blending of a layer are those of rendering its Gaussians alone), and the compositor's
  * epilogue writes outs[v].sem_masks[k-1] = || pixel - mask_colors[k-1] ||_2 <= mask_threshold.  No colour image is
  * written (outs[v].color / depth may be NULL).  layer_id must be non-decreasing along the scene (PEGASUS merges object
- * after object); Gaussians with layer_id 0 are dropped.  `posed` as in pgr_forward_posed_async (may be NULL).
+ * after object); Gaussians with layer_id 0 are dropped.  Goes with PgrForwardCall::posed or without.
  * EMPTY LAYERS: the plane of a layer no Gaussian carries is all 0, whatever the background -- the reference never renders
  * an object that is not in gs_object_list and leaves its mask column 0 (/root/reference/src/gs/render.py:44-63); an
  * empty scene (n == 0) is the same rule for every layer.  A layer WITH Gaussians of which none reaches a pixel holds the
@@ -276,14 +226,10 @@ typedef struct PgrLayers {
 } PgrLayers;
 size_t pgr_layers_workspace_bytes(int32_t n, int32_t width, int32_t height, int64_t max_instances_per_view,
                                   int32_t n_views, int32_t n_layers);
-int32_t pgr_forward_layers_async(const PgrScene *scene, const PgrLayers *layers, const PgrPosedObjects *posed,
-                                 int32_t n_views, const PgrCamera *cameras, const PgrOutputs *outs, void *workspace,
-                                 size_t workspace_bytes, int64_t max_instances_per_view, void *host_scratch,
-                                 size_t host_scratch_size, void *stream);
 
-/* Profiling twin of pgr_forward_batch (bench / rocprof only): records HIP events on `stream` at the
- * stage boundaries (each stage runs for all views before the next starts), synchronises, and writes the
- * elapsed milliseconds of each stage for the whole batch to stage_ms[PGR_NUM_STAGES] in PgrStage order. */
+/* The stages PgrForwardCall::stage_ms times (bench / rocprof only): HIP events on `stream` at the stage boundaries (each
+ * stage runs for all views before the next starts), elapsed milliseconds of each stage for the whole batch, in PgrStage
+ * order. */
 #define PGR_NUM_STAGES 5
 typedef enum PgrStage {
     PGR_STAGE_PREPROCESS = 0,  /* camera pack + per-Gaussian projection / EWA / SH */
@@ -293,10 +239,54 @@ typedef enum PgrStage {
     PGR_STAGE_COMPOSITE = 4    /* front-to-back alpha compositing of all views; with a PgrSemantic the same
                                   walk also accumulates the objects-only semantic image */
 } PgrStage;
-int32_t pgr_forward_batch_profiled(const PgrScene *scene, const PgrSemantic *semantic, int32_t n_views,
-                                   const PgrCamera *cameras, const PgrOutputs *outs, void *workspace,
-                                   size_t workspace_bytes, int64_t max_instances_per_view,
-                                   int64_t *num_instances, void *stream, float *stage_ms);
+
+/* THE forward: render `n_views` views of ONE scene (the per-frame loop of /root/reference/pegasus.py:254-325 calls render()
+ * once per camera over the same merged cloud; this is that loop as one call, and one view is a batch of one).  `cameras`
+ * and `outs` are HOST arrays of n_views entries; all views share the image size.  The batch is what fills an MI355X: the
+ * compositing of every (view, tile) list is one launch, ordered longest list first, so no view waits on its own slowest
+ * tile.  `workspace`: device, pgr_batch_workspace_bytes (a layered call: pgr_layers_workspace_bytes) for
+ * `max_instances_per_view` (Gaussian, tile) pairs per view.
+ *
+ * SYNCHRONOUS (host_scratch NULL): everything is enqueued on `stream` and the call synchronises it once, at its end, to
+ * read the instance counts and overflow flags (the reference synchronises mid-pipeline to read num_rendered, SURVEY.md
+ * section 2a), so that an overflow is returned as PGR_ERR_INSTANCE_OVERFLOW instead of as an image.  `num_instances` (host,
+ * n_views entries) receives the counts.  With `stage_ms` the call also times its stages (PgrStage above).
+ *
+ * ASYNCHRONOUS (host_scratch non-NULL): enqueues and returns without synchronising.  `host_scratch` is PINNED host memory
+ * of pgr_host_scratch_bytes(n_views) in which the library stages its pointer tables and receives the status words; it must
+ * stay untouched until `stream` has passed the call.  After synchronising, pgr_batch_status(host_scratch, n_views,
+ * num_instances) returns PGR_OK or PGR_ERR_INSTANCE_OVERFLOW (frames of an overflowed batch are not valid: the rest of the
+ * call did nothing; re-run with a larger capacity).  Two batches can run concurrently on two streams with two workspaces.
+ * With `status_event` (a hipEvent_t) the status words reach the host EARLY: they are final once the tile scan has run -- a
+ * third into a single-view call -- so the scan stores them into `host_scratch` itself (which must therefore be
+ * device-accessible at its host address: hipHostMalloc memory, what torch's pin_memory() hands out) and the event is
+ * recorded on `stream` right behind it.  After hipEventSynchronize(status_event), pgr_batch_status is valid while scatter,
+ * sort and compositor still run: the caller of a single view (PEGASUS's render(), /root/reference/src/gs/render.py:17-24 --
+ * the upstream rasterizer blocks on its own instance count in the middle of every call the same way) returns to its host
+ * code without leaving the GPU idle; the outputs are complete in STREAM order, as for every asynchronous call.
+ *
+ * PGR_ERR_INVALID_ARGUMENT before anything is enqueued: call NULL; a synchronous call with posed, layers or status_event;
+ * an asynchronous one with num_instances or stage_ms, or with host_scratch_bytes below pgr_host_scratch_bytes(n_views);
+ * status_event with layers; layers with semantic; and what the descriptors above say of themselves. */
+typedef struct PgrForwardCall {
+    const PgrScene *scene;
+    int32_t n_views;
+    const PgrCamera *cameras;
+    const PgrOutputs *outs;
+    void *workspace;
+    size_t workspace_bytes;
+    int64_t max_instances_per_view;
+    const PgrSemantic *semantic;         /* optional: the fused objects-only semantic image */
+    const PgrPosedObjects *posed;        /* optional, asynchronous only: per-view object poses */
+    const PgrLayers *layers;             /* optional, asynchronous only: a layered call */
+    void *host_scratch;                  /* NULL = synchronous */
+    size_t host_scratch_bytes;
+    int64_t *num_instances;              /* optional, synchronous only */
+    float *stage_ms;                     /* optional, synchronous only: [PGR_NUM_STAGES] */
+    void *status_event;                  /* optional, asynchronous only, not with layers */
+} PgrForwardCall;
+int32_t pgr_forward(const PgrForwardCall *call, void *stream);
+int32_t pgr_batch_status(const void *host_scratch, int32_t n_views, int64_t *num_instances);
 
 /* Conservative block visibility (pegasus_amd/csrc/blockcull.hip.h): bit (v % 32) of
  * vis_words[g * ceil(n_views / 32) + v / 32] is CLEAR only if none of the Gaussians [64 g, 64 g + 64) can get a
@@ -502,7 +492,7 @@ size_t pgr_pose_adi_workspace_bytes(int32_t n_jobs, const PgrPoseErrorJob *jobs)
 int32_t pgr_pose_adi(const float *vertices, int64_t n_vertices, int32_t n_jobs, const PgrPoseErrorJob *jobs, float *adi,
                      void *workspace, size_t workspace_bytes, void *stream);
 
-/* Gradients returned by pgr_backward / pgr_backward_batch (device pointers, any may be NULL = not wanted). */
+/* Gradients returned by pgr_backward (device pointers, any may be NULL = not wanted). */
 typedef struct PgrGradOutputs {
     float *means2d;              /* [n,3] screen-space mean, NDC-scaled (what viewspace_points.grad receives) */
     float *means3d;              /* [n,3] */
@@ -514,39 +504,25 @@ typedef struct PgrGradOutputs {
     float *rotations;            /* [n,4] */
 } PgrGradOutputs;
 
-/* Backward of ONE view rendered by pgr_forward into `workspace` (which must be untouched since, with the same
- * n / image size / max_instances), given dL/dcolor [3,H,W] and optionally dL/ddepth [1,H,W], and the forward's
- * final_T / n_contrib outputs.  Replaces _C.rasterize_gaussians_backward of the reference's extension (used by
- * training only: /root/reference/src/gs/gs_training.py:7,46).  `grad_rows` is scratch of n*12 floats.  It is the
- * one-view case of pgr_backward_batch (same kernels, same results), with `grad_rows` as its rows; its one per-view table
- * entry is written into the workspace's `tables` region, which only the forward reads (and the next forward rewrites). */
-int32_t pgr_backward(const PgrScene *scene, const PgrCamera *camera, const float *grad_color,
-                     const float *grad_depth, const float *final_T, const uint32_t *n_contrib,
-                     const int32_t *radii, void *workspace, size_t workspace_bytes, int64_t max_instances,
-                     const PgrGradOutputs *grads, float *grad_rows, void *stream);
-
-/* pgr_backward with the gradient of the accumulated opacity: grad_alpha = dL/dalpha [1,H,W] or NULL, alpha = 1 - final_T
- * (what the forward's final_T output leaves behind).  For every blended entry i of a pixel, dalpha/dalpha_i =
+/* THE backward (PgrBackwardCall below), of a pgr_forward call without semantic, posed or layers: the gradients of a loss
+ * over all n_views images at once; one view is a batch of one (same kernels, same results).  Replaces _C.rasterize_gaussians_backward of the
+ * reference's extension (used by training only: /root/reference/src/gs/gs_training.py:7,46).  `workspace` must be exactly
+ * as that call left it (same n, image size, max_instances_per_view and n_views) and is only read; `cameras` are the forward's
+ * (only the image size is read: the packed cameras live in the workspace).  `views` is a HOST array of n_views entries, one
+ * per view: dL/dcolor, optionally dL/ddepth, and the forward's final_T / n_contrib / radii outputs.
+ * `grad_alpha`: the gradient of the accumulated opacity alpha = 1 - final_T, a HOST array of n_views device pointers ([1,H,W]
+ * each), any of which may be NULL; the whole array may be NULL.  For every blended entry i of a pixel, dalpha/dalpha_i =
  * final_T / (1 - alpha_i), under the colour term's conventions (the 0.99 clamp passes the gradient straight through, the
- * T < 1e-4 stop and n_contrib bound the walk).  grad_alpha = NULL reads nothing and gives exactly pgr_backward's results
- * (pgr_backward is this call with NULL). */
-int32_t pgr_backward_ex(const PgrScene *scene, const PgrCamera *camera, const float *grad_color,
-                        const float *grad_depth, const float *grad_alpha, const float *final_T,
-                        const uint32_t *n_contrib, const int32_t *radii, void *workspace, size_t workspace_bytes,
-                        int64_t max_instances, const PgrGradOutputs *grads, float *grad_rows, void *stream);
-
-/* Backward of a pgr_forward_batch call: the gradients of a loss over all n_views images at once.  `workspace` must be exactly
- * as that call left it (same n, image size, max_instances_per_view and n_views); `cameras` are the forward's (only the image
- * size is read: the packed cameras live in the workspace).  `views` is a HOST array of n_views entries, one per view.
+ * T < 1e-4 stop and n_contrib bound the walk).  NULL reads nothing and adds nothing.
  * Every gradient in `grads` is the SUM over the views, except means2d, which is [n_views, n, 3] view-major: each view's own
  * screen-space gradient (densification gathers its statistics per view).  Two launches do the work: the compositor backward
  * of every (view, tile) list in the forward's interleaved work order, and one thread per Gaussian looping over the views in
  * order (cov3D -> scale / rotation once, on the summed cov3D gradient; no atomics across views).
  * `scratch`: device memory of pgr_backward_batch_scratch_bytes(n, n_views) bytes -- per-view accumulator rows of 48 bytes
  * per Gaussian (48 n n_views: 768 MB for 8 views of 2 M Gaussians) and a small table.
- * PGR_ERR_INVALID_ARGUMENT (before anything is enqueued): shs_rest, NULL cameras / views / grads, n_views <= 0, mixed image
- * sizes, a view without grad_color / final_T / n_contrib (or radii, n > 0), scratch NULL or smaller than required.  Posed,
- * semantic and layered batches have no backward. */
+ * PGR_ERR_INVALID_ARGUMENT (before anything is enqueued): call NULL, shs_rest, NULL cameras / views / grads, n_views <= 0, mixed
+ * image sizes, a view without grad_color / final_T / n_contrib (or radii, n > 0), scratch NULL or smaller than required; with
+ * camera_grads (below): camera_scratch NULL or smaller than pgr_camera_grad_scratch_bytes(n, n_views). */
 typedef struct PgrBackwardView {
     const float *grad_color;     /* [3,H,W] required */
     const float *grad_depth;     /* [1,H,W] or NULL */
@@ -555,17 +531,6 @@ typedef struct PgrBackwardView {
     const int32_t *radii;        /* [n]     the forward's (required) */
 } PgrBackwardView;
 size_t pgr_backward_batch_scratch_bytes(int32_t n, int32_t n_views);
-int32_t pgr_backward_batch(const PgrScene *scene, int32_t n_views, const PgrCamera *cameras, const PgrBackwardView *views,
-                           void *workspace, size_t workspace_bytes, int64_t max_instances_per_view,
-                           const PgrGradOutputs *grads, void *scratch, size_t scratch_bytes, void *stream);
-/* pgr_backward_batch with the per-view gradient of the accumulated opacity (see pgr_backward_ex): grad_alpha is a HOST
- * array of n_views device pointers ([1,H,W] each), any of which may be NULL; the whole array may be NULL (pgr_backward_batch
- * is this call with NULL). */
-int32_t pgr_backward_batch_ex(const PgrScene *scene, int32_t n_views, const PgrCamera *cameras,
-                              const PgrBackwardView *views, const float *const *grad_alpha, void *workspace,
-                              size_t workspace_bytes, int64_t max_instances_per_view, const PgrGradOutputs *grads,
-                              void *scratch, size_t scratch_bytes, void *stream);
-
 /* Camera gradients: the exact partials of the loss with respect to the 35 camera numbers the forward reads per view --
  * viewmatrix [16] and projmatrix [16] (PgrCamera's transposed storage) and campos [3] -- each treated as an independent
  * input (a caller that ties them together, e.g. through a pose, composes them).  With p = (x, y, z, 1) per Gaussian the
@@ -583,23 +548,25 @@ typedef struct PgrCameraGrad {   /* device pointers, any NULL = not wanted; WRIT
 } PgrCameraGrad;
 /* Device scratch of the camera kernels: 140 bytes per view and 256 Gaussians (0 for n < 0 or n_views <= 0). */
 size_t pgr_camera_grad_scratch_bytes(int32_t n, int32_t n_views);
-/* pgr_backward_ex plus the camera gradient of its view.  The scene gradients are exactly pgr_backward_ex's.
- * PGR_ERR_INVALID_ARGUMENT before anything is enqueued: camera_grad NULL, cam_scratch NULL or smaller than
- * pgr_camera_grad_scratch_bytes(n, 1), and every case pgr_backward_ex refuses. */
-int32_t pgr_backward_camera(const PgrScene *scene, const PgrCamera *camera, const float *grad_color,
-                            const float *grad_depth, const float *grad_alpha, const float *final_T,
-                            const uint32_t *n_contrib, const int32_t *radii, void *workspace, size_t workspace_bytes,
-                            int64_t max_instances, const PgrGradOutputs *grads, float *grad_rows,
-                            const PgrCameraGrad *camera_grad, void *cam_scratch, size_t cam_scratch_bytes, void *stream);
-/* pgr_backward_batch_ex plus every view's camera gradient: camera_grads is a HOST array of n_views entries (the outputs
- * reach the device 16 views per launch, as the batch backward's table does).  The scene gradients are exactly
- * pgr_backward_batch_ex's.  PGR_ERR_INVALID_ARGUMENT before anything is enqueued: camera_grads NULL, cam_scratch NULL or
- * smaller than pgr_camera_grad_scratch_bytes(n, n_views), and every case pgr_backward_batch_ex refuses. */
-int32_t pgr_backward_batch_camera(const PgrScene *scene, int32_t n_views, const PgrCamera *cameras,
-                                  const PgrBackwardView *views, const float *const *grad_alpha, void *workspace,
-                                  size_t workspace_bytes, int64_t max_instances_per_view, const PgrGradOutputs *grads,
-                                  void *scratch, size_t scratch_bytes, const PgrCameraGrad *camera_grads,
-                                  void *cam_scratch, size_t cam_scratch_bytes, void *stream);
+
+typedef struct PgrBackwardCall {
+    const PgrScene *scene;
+    int32_t n_views;
+    const PgrCamera *cameras;
+    const PgrBackwardView *views;
+    const float *const *grad_alpha;      /* NULL, or n_views entries, any NULL */
+    void *workspace;
+    size_t workspace_bytes;
+    int64_t max_instances_per_view;
+    const PgrGradOutputs *grads;
+    void *scratch;                       /* device, pgr_backward_batch_scratch_bytes(n, n_views) */
+    size_t scratch_bytes;
+    const PgrCameraGrad *camera_grads;   /* NULL = scene gradients only (and no camera launch); else a HOST array of n_views
+                                            entries; the scene gradients are the same with it and without */
+    void *camera_scratch;                /* device, pgr_camera_grad_scratch_bytes(n, n_views); only with camera_grads */
+    size_t camera_scratch_bytes;
+} PgrBackwardCall;
+int32_t pgr_backward(const PgrBackwardCall *call, void *stream);
 
 /* present[i] = 1 iff Gaussian i passes the near-plane test of `viewmatrix` (device [16]). */
 int32_t pgr_mark_visible(int32_t n, const float *means3d, const float *viewmatrix, uint8_t *present,

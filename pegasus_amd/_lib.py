@@ -14,7 +14,7 @@ import os
 # from build_variants/ instead of overwriting the product .so)
 LIB_PATH = Path(os.environ.get("PGR_LIB") or Path(__file__).resolve().parent / "csrc" / "libpegasus_raster.so")
 
-PGR_ABI_VERSION = 3          # include/pegasus_raster.h PGR_ABI_VERSION
+PGR_ABI_VERSION = 4          # include/pegasus_raster.h PGR_ABI_VERSION
 PGR_OK = 0
 PGR_ERR_INVALID_ARGUMENT = -1
 PGR_ERR_WORKSPACE_TOO_SMALL = -2
@@ -100,6 +100,25 @@ class PgrCameraGrad(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("viewmatrix", "projmatrix", "campos")]
 
 
+class PgrForwardCall(C.Structure):
+    """One pgr_forward call.  The pointer fields keep what is assigned to them alive as long as the struct."""
+    _fields_ = [("scene", C.POINTER(PgrScene)), ("n_views", C.c_int32), ("cameras", C.POINTER(PgrCamera)),
+                ("outs", C.POINTER(PgrOutputs)), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("max_instances_per_view", C.c_int64), ("semantic", C.POINTER(PgrSemantic)),
+                ("posed", C.POINTER(PgrPosedObjects)), ("layers", C.POINTER(PgrLayers)), ("host_scratch", C.c_void_p),
+                ("host_scratch_bytes", C.c_size_t), ("num_instances", C.POINTER(C.c_int64)),
+                ("stage_ms", C.POINTER(C.c_float)), ("status_event", C.c_void_p)]
+
+
+class PgrBackwardCall(C.Structure):
+    """One pgr_backward call."""
+    _fields_ = [("scene", C.POINTER(PgrScene)), ("n_views", C.c_int32), ("cameras", C.POINTER(PgrCamera)),
+                ("views", C.POINTER(PgrBackwardView)), ("grad_alpha", C.POINTER(C.c_void_p)), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t), ("max_instances_per_view", C.c_int64), ("grads", C.POINTER(PgrGradOutputs)),
+                ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t), ("camera_grads", C.POINTER(PgrCameraGrad)),
+                ("camera_scratch", C.c_void_p), ("camera_scratch_bytes", C.c_size_t)]
+
+
 class PgrWorkspaceView(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("splats", "rects", "gauss_sorted", "ranges", "num_instances")]
 
@@ -154,63 +173,22 @@ SYMBOLS = {
     "pgr_status_string": (C.c_char_p, [C.c_int32]),
     "pgr_last_hip_error": (C.c_char_p, []),
     "pgr_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
-    "pgr_forward": (C.c_int32, [C.POINTER(PgrScene), C.POINTER(PgrCamera), C.POINTER(PgrOutputs), C.c_void_p,
-                                C.c_size_t, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
+    "pgr_forward": (C.c_int32, [C.POINTER(PgrForwardCall), C.c_void_p]),
     "pgr_batch_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
-    "pgr_forward_batch": (C.c_int32, [C.POINTER(PgrScene), C.c_int32, C.POINTER(PgrCamera), C.POINTER(PgrOutputs),
-                                      C.c_void_p, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]),
     "pgr_host_scratch_bytes": (C.c_size_t, [C.c_int32]),
-    "pgr_forward_batch_async": (C.c_int32, [C.POINTER(PgrScene), C.c_int32, C.POINTER(PgrCamera),
-                                            C.POINTER(PgrOutputs), C.c_void_p, C.c_size_t, C.c_int64, C.c_void_p,
-                                            C.c_size_t, C.c_void_p]),
-    "pgr_forward_frames_async": (C.c_int32, [C.POINTER(PgrScene), C.POINTER(PgrSemantic), C.c_int32,
-                                             C.POINTER(PgrCamera), C.POINTER(PgrOutputs), C.c_void_p, C.c_size_t,
-                                             C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "pgr_forward_posed_async": (C.c_int32, [C.POINTER(PgrScene), C.POINTER(PgrSemantic), C.POINTER(PgrPosedObjects),
-                                            C.c_int32, C.POINTER(PgrCamera), C.POINTER(PgrOutputs), C.c_void_p,
-                                            C.c_size_t, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "pgr_forward_posed_early_status": (C.c_int32, [C.POINTER(PgrScene), C.POINTER(PgrSemantic), C.POINTER(PgrPosedObjects),
-                                                   C.c_int32, C.POINTER(PgrCamera), C.POINTER(PgrOutputs), C.c_void_p,
-                                                   C.c_size_t, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "pgr_batch_status": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]),
     "pgr_scene_cache_bytes": (C.c_size_t, [C.c_int32]),
     "pgr_scene_prepare": (C.c_int32, [C.POINTER(PgrScene), C.POINTER(PgrSemantic), C.c_void_p, C.c_size_t,
                                       C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]),
     "pgr_layers_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
-    "pgr_forward_layers_async": (C.c_int32, [C.POINTER(PgrScene), C.POINTER(PgrLayers), C.POINTER(PgrPosedObjects),
-                                             C.c_int32, C.POINTER(PgrCamera), C.POINTER(PgrOutputs), C.c_void_p,
-                                             C.c_size_t, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pgr_frame_record_layout": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(PgrRecordLayout)]),
     "pgr_pack_records": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_void_p, C.c_int64, C.c_void_p]),
-    "pgr_forward_batch_profiled": (C.c_int32, [C.POINTER(PgrScene), C.POINTER(PgrSemantic), C.c_int32,
-                                               C.POINTER(PgrCamera),
-                                               C.POINTER(PgrOutputs), C.c_void_p, C.c_size_t, C.c_int64,
-                                               C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_float)]),
     "pgr_workspace_view": (C.c_int32, [C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
                                        C.c_int32, C.c_int32, C.POINTER(PgrWorkspaceView)]),
-    "pgr_backward": (C.c_int32, [C.POINTER(PgrScene), C.POINTER(PgrCamera), C.c_void_p, C.c_void_p, C.c_void_p,
-                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.POINTER(PgrGradOutputs),
-                                 C.c_void_p, C.c_void_p]),
-    "pgr_backward_ex": (C.c_int32, [C.POINTER(PgrScene), C.POINTER(PgrCamera), C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64,
-                                    C.POINTER(PgrGradOutputs), C.c_void_p, C.c_void_p]),
+    "pgr_backward": (C.c_int32, [C.POINTER(PgrBackwardCall), C.c_void_p]),
     "pgr_backward_batch_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
-    "pgr_backward_batch": (C.c_int32, [C.POINTER(PgrScene), C.c_int32, C.POINTER(PgrCamera), C.POINTER(PgrBackwardView),
-                                       C.c_void_p, C.c_size_t, C.c_int64, C.POINTER(PgrGradOutputs), C.c_void_p,
-                                       C.c_size_t, C.c_void_p]),
-    "pgr_backward_batch_ex": (C.c_int32, [C.POINTER(PgrScene), C.c_int32, C.POINTER(PgrCamera),
-                                          C.POINTER(PgrBackwardView), C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t,
-                                          C.c_int64, C.POINTER(PgrGradOutputs), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pgr_camera_grad_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
-    "pgr_backward_camera": (C.c_int32, [C.POINTER(PgrScene), C.POINTER(PgrCamera), C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64,
-                                        C.POINTER(PgrGradOutputs), C.c_void_p, C.POINTER(PgrCameraGrad), C.c_void_p,
-                                        C.c_size_t, C.c_void_p]),
-    "pgr_backward_batch_camera": (C.c_int32, [C.POINTER(PgrScene), C.c_int32, C.POINTER(PgrCamera),
-                                              C.POINTER(PgrBackwardView), C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t,
-                                              C.c_int64, C.POINTER(PgrGradOutputs), C.c_void_p, C.c_size_t,
-                                              C.POINTER(PgrCameraGrad), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pgr_compose_object": (C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                        C.POINTER(PgrObjectPose), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                        C.c_void_p]),
@@ -325,18 +303,18 @@ def stream_ptr(device) -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
-def enqueue(name: str, device, *args, after_stream=()) -> int:
+def enqueue(name: str, device, *args) -> int:
     """THE way the package calls an entry point that takes a stream: with ``device`` current, on torch's current stream of
-    ``device`` at the time of the call, which goes behind ``args`` (``after_stream``: what the entry takes behind its
-    stream).  Returns the raw status: callers that handle one themselves (instance overflow) use this, all others ``call``."""
+    ``device`` at the time of the call, which goes behind ``args``.  Returns the raw status: callers that handle one
+    themselves (instance overflow) use this, all others ``call``."""
     import torch
     with torch.cuda.device(device):
-        return getattr(lib(), name)(*args, stream_ptr(device), *after_stream)
+        return getattr(lib(), name)(*args, stream_ptr(device))
 
 
-def call(name: str, device, *args, after_stream=()):
+def call(name: str, device, *args):
     """``enqueue`` whose status other than PGR_OK raises, naming the entry."""
-    check(enqueue(name, device, *args, after_stream=after_stream), name)
+    check(enqueue(name, device, *args), name)
 
 
 def check(status: int, what: str = "pegasus_raster"):

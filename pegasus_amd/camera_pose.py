@@ -3,7 +3,7 @@
 A pose correction is a 6-vector ``delta = (omega, tau)`` (rotation vector, translation) in the CAMERA frame, applied on the
 left of the camera's world-to-camera transform:  W2C' = se3_exp(delta) @ W2C.  ``PosedCamera`` exposes what
 ``gaussian_renderer.render`` / ``render_batch`` read from a camera, built from W2C' with torch operations, so the camera
-gradient the rasterizer returns (pgr_backward_camera: viewmatrix, projmatrix, campos) reaches ``delta`` through autograd.
+gradient the rasterizer returns (PgrBackwardCall.camera_grads: viewmatrix, projmatrix, campos) reaches ``delta`` through autograd.
 
 ``refine_pose`` is render-and-compare pose refinement of a frozen model: rendering an object model alone from a camera whose
 world frame is the model frame makes W2C' the BOP pose (cam_R_m2c, cam_t_m2c; ``pegasus_amd.bop_pose``)."""

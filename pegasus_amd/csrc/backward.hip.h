@@ -3,8 +3,8 @@
 // of alpha is not differentiated, the screen-space mean gradient is NDC-scaled (pixel gradient * W/2, H/2),
 // colours clamped at 0 and clamped view-space coordinates pass no gradient.
 //
-// Both entries (pgr_backward_ex: one view, pgr_backward_batch_ex: a pgr_forward_batch call) run the same two kernels on a
-// table of per-view entries; a one-view call runs their ONE instances (n_views pinned to 1, view 0).
+// pgr_backward, for one view as for a batch, runs the same two kernels on a table of per-view entries; a one-view call
+// runs their ONE instances (n_views pinned to 1, view 0).
 //   composite_backward_batch_kernel  one wave per 4x4-pixel block, four list entries per step (below), for every
 //       (view, tile) item of the forward's interleaved work order in one launch, into per-view rows [n_views, n, GRAD_ROW]:
 //       the ten per-Gaussian partial gradients of an entry are summed over the block's pixels and land as one 10-lane
@@ -223,7 +223,7 @@ __device__ __forceinline__ void composite_backward_block(
     }
 }
 
-// ---- batch backward (pgr_backward_batch): the backward of a pgr_forward_batch call -------------------------------------
+// ---- batch backward (pgr_backward): the backward of a pgr_forward call of any number of views -------------------------
 // One entry per view, in device memory (written by backward_table_kernel from the launch arguments), read through the
 // scalar cache: the forward's lists in the workspace, the view's image gradients and forward outputs, and the view's own
 // rows of the [n_views, n, GRAD_ROW] accumulator (screen-space partials: they cannot be summed over views).  The packed
@@ -531,7 +531,7 @@ __device__ __forceinline__ void scale_rot_backward(const PgrScene& sc, int i, co
 // per view) is written per view; the cov3D -> scale / rotation chain is linear in the cov3D gradient and runs ONCE, on the
 // sum.  Every output is written exactly once, no atomics.
 // Registers: cov3D and the active SH coefficients are loaded where they are first used, and colour / opacity summed after
-// the SH step, so that none of them is live across the geometry chain.  ONE: the one-view instance (pgr_backward_ex); at
+// the SH step, so that none of them is live across the geometry chain.  ONE: the one-view instance (n_views == 1); at
 // DEG 0-1 it is bounded to 8 waves per SIMD (64 VGPRs, no spills) -- left alone the scheduler stops at 65-66.
 template <int DEG, bool ONE>
 __global__ __launch_bounds__(256, ONE && DEG < 2 ? 8 : 1) void preprocess_backward_batch_kernel(
@@ -647,7 +647,7 @@ __global__ __launch_bounds__(256, ONE && DEG < 2 ? 8 : 1) void preprocess_backwa
     }
 }
 
-// ---- camera backward (pgr_backward_camera / pgr_backward_batch_camera) -------------------------------------------------
+// ---- camera backward (PgrBackwardCall::camera_grads) -------------------------------------------------------------------
 // The exact partials of the loss with respect to the 35 camera numbers the forward reads per view (viewmatrix [16],
 // projmatrix [16], campos [3]; treated as independent inputs), after the two launches above and from their rows:
 //   camera_backward_kernel      one thread per Gaussian over the views in order, as preprocess_backward_batch_kernel: the

@@ -141,7 +141,7 @@ constexpr int PAIR_UNROLL = PGR_PAIR_UNROLL;   // entry pairs per trip of the co
 // continues over object entries only (environment entries are dropped before their record is even gathered) up to
 // the tile's last object entry (ViewEntry::obj_last, a by-product of the tile sort).  Pixel arithmetic is the
 // sequence a separate objects-only pass executes: bit-identical (tests/test_gpu_parity.py).
-// LAYERED (pgr_forward_layers_async): the work item's tile index runs over n_layers stacked copies of the tile grid;
+// LAYERED (PgrForwardCall::layers): the work item's tile index runs over n_layers stacked copies of the tile grid;
 // pixels and lists are those of the layer rendered alone, and the only output is the layer's colour-distance mask.
 template <bool AUX, bool FUSED, bool LAYERED = false>
 __device__ __forceinline__ void composite_quarter(const ViewEntry& ve, uint32_t item, const SemanticDev& sem, int n_sem,

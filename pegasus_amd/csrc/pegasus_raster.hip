@@ -69,7 +69,7 @@ static bool records_enabled() {      // PGR_BIN_RECORDS=0: the scatter walk re-e
     return !(e && e[0] == '0');
 }
 
-// layers > 1 (pgr_forward_layers_async): the view is `layers` stacked copies of the tile grid -- per-(tile, layer) lists
+// layers > 1 (PgrForwardCall::layers): the view is `layers` stacked copies of the tile grid -- per-(tile, layer) lists
 static Layout make_layout(int32_t n, int32_t width, int32_t height, int64_t max_instances, int32_t layers = 1) {
     Layout L{};
     const size_t N = (size_t)(n > 0 ? n : 0), I = (size_t)(max_instances > 0 ? max_instances : 0);
@@ -259,9 +259,9 @@ __global__ __launch_bounds__(256) void batch_header_kernel(uint32_t* __restrict_
         for (int i = threadIdx.x; i < table_words; i += blockDim.x) gstore(tables_out + i, tables.w[i]);
 }
 
-// What an entry adds to the plain batch call; every field is optional.
+// What a call adds to the plain batch; every field is optional.
 struct ForwardOptions {
-    hipEvent_t* ev = nullptr;             // PGR_NUM_STAGES+1 events recorded at the stage boundaries (profiling entry)
+    hipEvent_t* ev = nullptr;             // PGR_NUM_STAGES+1 events recorded at the stage boundaries (a call with stage_ms)
     // NULL = synchronous call (tables staged from pageable memory, stream synchronised at the end, num_instances
     // filled).  Non-NULL = pinned host memory of host_scratch_bytes(n_views): nothing blocks, the status words land in
     // its tail when the stream reaches them (pgr_batch_status reads them).
@@ -552,10 +552,10 @@ static BackwardScratch backward_scratch(int32_t n, int32_t n_views) {
     return {rows_bytes, table, table + align_up((size_t)n_views * sizeof(BwdViewDev))};
 }
 
-// What a backward entry's checks leave behind for its launches (all zero for an empty scene, which launches nothing).
+// What the backward's checks leave behind for its launches (all zero for an empty scene, which launches nothing).
 struct BackwardPlan { char* ws; Layout L; BatchLayout B; float* rows; BwdViewDev* table; };
 
-// Both backward entries after their checks: the per-view table into `table` from the launch arguments (no host staging that
+// The backward after its checks: the per-view table into `table` from the launch arguments (no host staging that
 // would have to outlive the call), `rows` [n_views, n, GRAD_ROW] cleared, the walk of every (view, tile, quarter) item of the
 // forward's work order, then one thread per Gaussian over the views.  One view runs the kernels' ONE instances.
 static int32_t backward_impl(const PgrScene* scene, int n_views, const PgrBackwardView* views,
@@ -639,11 +639,6 @@ static int32_t camera_backward_impl(const PgrScene* scene, int n_views, const Pg
     return hip_ok(hipGetLastError(), "camera backward launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
 }
 
-// The one-view table entry lives in the forward's `tables` region, which the backward never reads and the next forward
-// rewrites; at one view that region holds a ViewEntry, a BinView and a PreOut.
-static_assert(sizeof(BwdViewDev) <= sizeof(ViewEntry) + sizeof(BinView) + sizeof(PreOut),
-              "pgr_backward_ex writes its BwdViewDev into the one-view tables region");
-
 // pgr_pose_objects' workspace, per launch of POSE_JOBS_PER_LAUNCH jobs: the centroid partials, then the jobs' poses.
 constexpr size_t POSE_PART_BYTES = align_up((size_t)POSE_JOBS_PER_LAUNCH * POSE_REDUCE_BLOCKS * 3 * sizeof(double));
 constexpr size_t POSE_LAUNCH_BYTES = POSE_PART_BYTES + align_up((size_t)POSE_JOBS_PER_LAUNCH * sizeof(ObjectPoseDev));
@@ -701,77 +696,47 @@ int32_t pgr_workspace_view(void* workspace, size_t workspace_bytes, int32_t n, i
     return PGR_OK;
 }
 
-int32_t pgr_forward(const PgrScene* scene, const PgrCamera* cam, const PgrOutputs* out, void* workspace,
-                    size_t workspace_bytes, int64_t max_instances, int64_t* num_instances, void* stream_v) {
-    if (scene && scene->n > 0 && out && !out->radii) return PGR_ERR_INVALID_ARGUMENT;
-    return forward_batch_impl(scene, 1, cam, out, workspace, workspace_bytes, max_instances, num_instances,
-                              static_cast<hipStream_t>(stream_v));
-}
-
-int32_t pgr_forward_batch(const PgrScene* scene, int32_t n_views, const PgrCamera* cameras, const PgrOutputs* outs,
-                          void* workspace, size_t workspace_bytes, int64_t max_instances_per_view,
-                          int64_t* num_instances, void* stream_v) {
-    return forward_batch_impl(scene, n_views, cameras, outs, workspace, workspace_bytes, max_instances_per_view,
-                              num_instances, static_cast<hipStream_t>(stream_v));
-}
-
 size_t pgr_host_scratch_bytes(int32_t n_views) { return n_views > 0 ? host_tables(n_views).total : 0; }
 
-// The asynchronous entries after their own checks: the pinned host scratch must hold host_scratch_bytes(n_views), and an
-// empty scene, which launches nothing, gets its status words (all zero) written here.
-static int32_t forward_async(const PgrScene* scene, int32_t n_views, const PgrCamera* cameras, const PgrOutputs* outs,
-                             void* workspace, size_t workspace_bytes, int64_t max_instances_per_view,
-                             size_t host_scratch_size, void* stream_v, const ForwardOptions& opt) {
-    if (!opt.host_scratch || n_views <= 0 || host_scratch_size < host_tables(n_views).total) return PGR_ERR_INVALID_ARGUMENT;
-    if (scene && scene->n == 0) memset(opt.host_scratch, 0, host_tables(n_views).total);
-    return forward_batch_impl(scene, n_views, cameras, outs, workspace, workspace_bytes, max_instances_per_view, nullptr,
-                              static_cast<hipStream_t>(stream_v), opt);
+// The synchronous call with stage_ms: PGR_NUM_STAGES + 1 events around forward_batch_impl, their elapsed times read afterwards.
+static int32_t forward_profiled(const PgrForwardCall* c, ForwardOptions opt, hipStream_t stream) {
+    hipEvent_t ev[PGR_NUM_STAGES + 1];
+    for (auto& e : ev)
+        if (!hip_ok(hipEventCreate(&e), "hipEventCreate")) return PGR_ERR_LAUNCH_FAILURE;
+    for (int k = 0; k < PGR_NUM_STAGES; ++k) c->stage_ms[k] = 0.f;
+    opt.ev = ev;
+    int32_t rc = forward_batch_impl(c->scene, c->n_views, c->cameras, c->outs, c->workspace, c->workspace_bytes,
+                                    c->max_instances_per_view, c->num_instances, stream, opt);
+    if (rc == PGR_OK && c->scene->n > 0) {
+        for (int k = 0; rc == PGR_OK && k < PGR_NUM_STAGES; ++k)
+            if (!hip_ok(hipEventElapsedTime(&c->stage_ms[k], ev[k], ev[k + 1]), "hipEventElapsedTime"))
+                rc = PGR_ERR_LAUNCH_FAILURE;
+    }
+    for (auto& e : ev) (void)hipEventDestroy(e);
+    return rc;
 }
 
-int32_t pgr_forward_batch_async(const PgrScene* scene, int32_t n_views, const PgrCamera* cameras, const PgrOutputs* outs,
-                                void* workspace, size_t workspace_bytes, int64_t max_instances_per_view,
-                                void* host_scratch, size_t host_scratch_size, void* stream_v) {
+// forward_batch_impl behind the checks of what goes with a synchronous and with an asynchronous call.  An empty scene
+// launches nothing: the asynchronous call's status words (all zero) are written here.
+int32_t pgr_forward(const PgrForwardCall* c, void* stream_v) {
+    if (!c) return PGR_ERR_INVALID_ARGUMENT;
+    if (c->host_scratch ? (c->num_instances || c->stage_ms) : (c->posed || c->layers || c->status_event))
+        return PGR_ERR_INVALID_ARGUMENT;
+    if (c->status_event && c->layers) return PGR_ERR_INVALID_ARGUMENT;
+    if (c->host_scratch) {
+        if (c->n_views <= 0 || c->host_scratch_bytes < host_tables(c->n_views).total) return PGR_ERR_INVALID_ARGUMENT;
+        if (c->scene && c->scene->n == 0) memset(c->host_scratch, 0, host_tables(c->n_views).total);
+    }
     ForwardOptions opt;
-    opt.host_scratch = host_scratch;
-    return forward_async(scene, n_views, cameras, outs, workspace, workspace_bytes, max_instances_per_view,
-                         host_scratch_size, stream_v, opt);
-}
-
-int32_t pgr_forward_frames_async(const PgrScene* scene, const PgrSemantic* semantic, int32_t n_views,
-                                 const PgrCamera* cameras, const PgrOutputs* outs, void* workspace,
-                                 size_t workspace_bytes, int64_t max_instances_per_view, void* host_scratch,
-                                 size_t host_scratch_size, void* stream_v) {
-    ForwardOptions opt;
-    opt.host_scratch = host_scratch;
-    opt.semantic = semantic;
-    return forward_async(scene, n_views, cameras, outs, workspace, workspace_bytes, max_instances_per_view,
-                         host_scratch_size, stream_v, opt);
-}
-
-int32_t pgr_forward_posed_async(const PgrScene* scene, const PgrSemantic* semantic, const PgrPosedObjects* posed,
-                                int32_t n_views, const PgrCamera* cameras, const PgrOutputs* outs, void* workspace,
-                                size_t workspace_bytes, int64_t max_instances_per_view, void* host_scratch,
-                                size_t host_scratch_size, void* stream_v) {
-    ForwardOptions opt;
-    opt.host_scratch = host_scratch;
-    opt.semantic = semantic;
-    opt.posed = posed;
-    return forward_async(scene, n_views, cameras, outs, workspace, workspace_bytes, max_instances_per_view,
-                         host_scratch_size, stream_v, opt);
-}
-
-int32_t pgr_forward_posed_early_status(const PgrScene* scene, const PgrSemantic* semantic, const PgrPosedObjects* posed,
-                                       int32_t n_views, const PgrCamera* cameras, const PgrOutputs* outs, void* workspace,
-                                       size_t workspace_bytes, int64_t max_instances_per_view, void* host_scratch,
-                                       size_t host_scratch_size, void* stream_v, void* status_event) {
-    if (!status_event) return PGR_ERR_INVALID_ARGUMENT;
-    ForwardOptions opt;
-    opt.host_scratch = host_scratch;
-    opt.semantic = semantic;
-    opt.posed = posed;
-    opt.status_event = static_cast<hipEvent_t>(status_event);
-    return forward_async(scene, n_views, cameras, outs, workspace, workspace_bytes, max_instances_per_view,
-                         host_scratch_size, stream_v, opt);
+    opt.host_scratch = c->host_scratch;
+    opt.semantic = c->semantic;
+    opt.posed = c->posed;
+    opt.layers = c->layers;
+    opt.status_event = static_cast<hipEvent_t>(c->status_event);
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    if (c->stage_ms) return forward_profiled(c, opt, stream);
+    return forward_batch_impl(c->scene, c->n_views, c->cameras, c->outs, c->workspace, c->workspace_bytes,
+                              c->max_instances_per_view, c->num_instances, stream, opt);
 }
 
 size_t pgr_layers_workspace_bytes(int32_t n, int32_t width, int32_t height, int64_t max_instances, int32_t n_views,
@@ -780,19 +745,6 @@ size_t pgr_layers_workspace_bytes(int32_t n, int32_t width, int32_t height, int6
         n_layers <= 0 || n_layers > 4096)
         return 0;
     return make_batch_layout(make_layout(n, width, height, max_instances, n_layers), n_views, (size_t)n).total;
-}
-
-int32_t pgr_forward_layers_async(const PgrScene* scene, const PgrLayers* layers, const PgrPosedObjects* posed,
-                                 int32_t n_views, const PgrCamera* cameras, const PgrOutputs* outs, void* workspace,
-                                 size_t workspace_bytes, int64_t max_instances_per_view, void* host_scratch,
-                                 size_t host_scratch_size, void* stream_v) {
-    if (!layers) return PGR_ERR_INVALID_ARGUMENT;
-    ForwardOptions opt;
-    opt.host_scratch = host_scratch;
-    opt.posed = posed;
-    opt.layers = layers;
-    return forward_async(scene, n_views, cameras, outs, workspace, workspace_bytes, max_instances_per_view,
-                         host_scratch_size, stream_v, opt);
 }
 
 size_t pgr_scene_cache_bytes(int32_t n) { return n < 0 ? 0 : align_up((size_t)n * 4) + align_up((size_t)n); }
@@ -834,160 +786,57 @@ int32_t pgr_batch_status(const void* host_scratch, int32_t n_views, int64_t* num
     return overflow ? PGR_ERR_INSTANCE_OVERFLOW : PGR_OK;
 }
 
-int32_t pgr_forward_batch_profiled(const PgrScene* scene, const PgrSemantic* semantic, int32_t n_views,
-                                   const PgrCamera* cameras, const PgrOutputs* outs, void* workspace,
-                                   size_t workspace_bytes, int64_t max_instances_per_view, int64_t* num_instances,
-                                   void* stream_v, float* stage_ms) {
-    if (!stage_ms) return PGR_ERR_INVALID_ARGUMENT;
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    hipEvent_t ev[PGR_NUM_STAGES + 1];
-    for (auto& e : ev)
-        if (!hip_ok(hipEventCreate(&e), "hipEventCreate")) return PGR_ERR_LAUNCH_FAILURE;
-    for (int k = 0; k < PGR_NUM_STAGES; ++k) stage_ms[k] = 0.f;
-    ForwardOptions opt;
-    opt.ev = ev;
-    opt.semantic = semantic;
-    int32_t rc = forward_batch_impl(scene, n_views, cameras, outs, workspace, workspace_bytes, max_instances_per_view,
-                                    num_instances, stream, opt);
-    if (rc == PGR_OK && scene->n > 0) {
-        for (int k = 0; rc == PGR_OK && k < PGR_NUM_STAGES; ++k)
-            if (!hip_ok(hipEventElapsedTime(&stage_ms[k], ev[k], ev[k + 1]), "hipEventElapsedTime"))
-                rc = PGR_ERR_LAUNCH_FAILURE;
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    return rc;
-}
-
-int32_t pgr_backward(const PgrScene* scene, const PgrCamera* cam, const float* grad_color, const float* grad_depth,
-                     const float* final_T, const uint32_t* n_contrib, const int32_t* radii, void* workspace,
-                     size_t workspace_bytes, int64_t max_instances, const PgrGradOutputs* grads, float* grad_rows,
-                     void* stream_v) {
-    return pgr_backward_ex(scene, cam, grad_color, grad_depth, nullptr, final_T, n_contrib, radii, workspace,
-                           workspace_bytes, max_instances, grads, grad_rows, stream_v);
-}
-
-// The single-view backward's checks and layouts (`view` = the entry's image arguments).
-static int32_t backward_plan(const PgrScene* scene, const PgrCamera* cam, const PgrBackwardView& view, void* workspace,
-                             size_t workspace_bytes, int64_t max_instances, const PgrGradOutputs* grads, float* grad_rows,
-                             BackwardPlan* p) {
-    if (int rc = check_scene(scene)) return rc;
-    if (scene->shs_rest) return PGR_ERR_INVALID_ARGUMENT;      // the SH gradient is one [n,sh_stride,3] array
-    if (!cam || !grads || !view.grad_color || !view.final_T || !view.n_contrib || cam->image_width <= 0 || cam->image_height <= 0)
-        return PGR_ERR_INVALID_ARGUMENT;
-    const int N = scene->n;
-    if (N == 0) return PGR_OK;
-    if (!workspace || !grad_rows || !view.radii) return PGR_ERR_INVALID_ARGUMENT;
-    p->L = make_layout(N, cam->image_width, cam->image_height, max_instances);
-    p->B = make_batch_layout(p->L, 1, (size_t)N);
-    if (workspace_bytes < p->B.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
-    p->ws = static_cast<char*>(workspace);
-    p->rows = grad_rows;
-    p->table = reinterpret_cast<BwdViewDev*>(p->ws + p->B.tables);
-    return PGR_OK;
-}
-
-// The batched backward's: every check before the first enqueue.
-static int32_t backward_batch_plan(const PgrScene* scene, int32_t n_views, const PgrCamera* cameras,
-                                   const PgrBackwardView* views, void* workspace, size_t workspace_bytes,
-                                   int64_t max_instances_per_view, const PgrGradOutputs* grads, void* scratch,
-                                   size_t scratch_bytes, BackwardPlan* p) {
-    if (int rc = check_scene(scene)) return rc;
-    if (scene->shs_rest) return PGR_ERR_INVALID_ARGUMENT;      // the SH gradient is one [n,sh_stride,3] array
-    if (n_views <= 0 || !cameras || !views || !grads) return PGR_ERR_INVALID_ARGUMENT;
-    if (max_instances_per_view < 0 || max_instances_per_view > 0x7fffffffLL) return PGR_ERR_INVALID_ARGUMENT;
-    const int N = scene->n, W = cameras[0].image_width, H = cameras[0].image_height;
-    if (W <= 0 || H <= 0) return PGR_ERR_INVALID_ARGUMENT;
-    for (int v = 0; v < n_views; ++v) {
-        if (cameras[v].image_width != W || cameras[v].image_height != H) return PGR_ERR_INVALID_ARGUMENT;
-        if (!views[v].grad_color || !views[v].final_T || !views[v].n_contrib) return PGR_ERR_INVALID_ARGUMENT;
-        if (N > 0 && !views[v].radii) return PGR_ERR_INVALID_ARGUMENT;
-    }
-    if (N == 0) return PGR_OK;
-    const BackwardScratch S = backward_scratch(N, n_views);
-    if (!workspace || !scratch || scratch_bytes < S.total) return PGR_ERR_INVALID_ARGUMENT;
-    p->L = make_layout(N, W, H, max_instances_per_view);
-    p->B = make_batch_layout(p->L, n_views, (size_t)N);
-    if (workspace_bytes < p->B.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
-    p->ws = static_cast<char*>(workspace);
-    p->rows = static_cast<float*>(scratch);
-    p->table = reinterpret_cast<BwdViewDev*>(static_cast<char*>(scratch) + S.table);
-    return PGR_OK;
-}
-
-// The launches behind a plan: the scene backward, then (camera entries: `camera_grads`) the camera kernels.
-static int32_t backward_launch(const PgrScene* scene, int n_views, const PgrBackwardView* views,
-                               const float* const* grad_alpha, const BackwardPlan& p, const PgrGradOutputs* grads,
-                               const PgrCameraGrad* camera_grads, void* cam_scratch, void* stream_v) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    if (scene->n > 0)
-        if (int32_t rc = backward_impl(scene, n_views, views, grad_alpha, p.ws, p.L, p.B, grads, p.rows, p.table, stream)) return rc;
-    if (!camera_grads) return PGR_OK;
-    return camera_backward_impl(scene, n_views, camera_grads, p.table, reinterpret_cast<const CameraDev*>(p.ws + p.B.cams),
-                                static_cast<float*>(cam_scratch), stream);
-}
-
-int32_t pgr_backward_ex(const PgrScene* scene, const PgrCamera* cam, const float* grad_color, const float* grad_depth,
-                        const float* grad_alpha, const float* final_T, const uint32_t* n_contrib, const int32_t* radii,
-                        void* workspace, size_t workspace_bytes, int64_t max_instances, const PgrGradOutputs* grads,
-                        float* grad_rows, void* stream_v) {
-    const PgrBackwardView view{grad_color, grad_depth, final_T, n_contrib, radii};
-    BackwardPlan p{};
-    if (int rc = backward_plan(scene, cam, view, workspace, workspace_bytes, max_instances, grads, grad_rows, &p)) return rc;
-    return backward_launch(scene, 1, &view, &grad_alpha, p, grads, nullptr, nullptr, stream_v);
-}
-
 size_t pgr_backward_batch_scratch_bytes(int32_t n, int32_t n_views) {
     return (n < 0 || n_views <= 0) ? 0 : backward_scratch(n, n_views).total;
-}
-
-int32_t pgr_backward_batch(const PgrScene* scene, int32_t n_views, const PgrCamera* cameras, const PgrBackwardView* views,
-                           void* workspace, size_t workspace_bytes, int64_t max_instances_per_view,
-                           const PgrGradOutputs* grads, void* scratch, size_t scratch_bytes, void* stream_v) {
-    return pgr_backward_batch_ex(scene, n_views, cameras, views, nullptr, workspace, workspace_bytes,
-                                 max_instances_per_view, grads, scratch, scratch_bytes, stream_v);
-}
-
-int32_t pgr_backward_batch_ex(const PgrScene* scene, int32_t n_views, const PgrCamera* cameras,
-                              const PgrBackwardView* views, const float* const* grad_alpha, void* workspace,
-                              size_t workspace_bytes, int64_t max_instances_per_view, const PgrGradOutputs* grads,
-                              void* scratch, size_t scratch_bytes, void* stream_v) {
-    BackwardPlan p{};
-    if (int rc = backward_batch_plan(scene, n_views, cameras, views, workspace, workspace_bytes, max_instances_per_view, grads,
-                                     scratch, scratch_bytes, &p))
-        return rc;
-    return backward_launch(scene, n_views, views, grad_alpha, p, grads, nullptr, nullptr, stream_v);
 }
 
 size_t pgr_camera_grad_scratch_bytes(int32_t n, int32_t n_views) {
     return (n < 0 || n_views <= 0) ? 0 : camera_scratch_bytes(n, n_views);
 }
 
-int32_t pgr_backward_camera(const PgrScene* scene, const PgrCamera* cam, const float* grad_color, const float* grad_depth,
-                            const float* grad_alpha, const float* final_T, const uint32_t* n_contrib, const int32_t* radii,
-                            void* workspace, size_t workspace_bytes, int64_t max_instances, const PgrGradOutputs* grads,
-                            float* grad_rows, const PgrCameraGrad* camera_grad, void* cam_scratch, size_t cam_scratch_bytes,
-                            void* stream_v) {
-    if (!camera_grad || !scene || scene->n < 0 || !cam_scratch || cam_scratch_bytes < camera_scratch_bytes(scene->n, 1))
+// The backward's checks and layouts: every check before the first enqueue.
+static int32_t backward_plan(const PgrBackwardCall& c, BackwardPlan* p) {
+    const PgrScene* scene = c.scene;
+    if (c.camera_grads && (!scene || scene->n < 0 || c.n_views <= 0 || !c.camera_scratch ||
+                           c.camera_scratch_bytes < camera_scratch_bytes(scene->n, c.n_views)))
         return PGR_ERR_INVALID_ARGUMENT;
-    const PgrBackwardView view{grad_color, grad_depth, final_T, n_contrib, radii};
-    BackwardPlan p{};
-    if (int rc = backward_plan(scene, cam, view, workspace, workspace_bytes, max_instances, grads, grad_rows, &p)) return rc;
-    return backward_launch(scene, 1, &view, &grad_alpha, p, grads, camera_grad, cam_scratch, stream_v);
+    if (int rc = check_scene(scene)) return rc;
+    if (scene->shs_rest) return PGR_ERR_INVALID_ARGUMENT;      // the SH gradient is one [n,sh_stride,3] array
+    if (c.n_views <= 0 || !c.cameras || !c.views || !c.grads) return PGR_ERR_INVALID_ARGUMENT;
+    if (c.max_instances_per_view < 0 || c.max_instances_per_view > 0x7fffffffLL) return PGR_ERR_INVALID_ARGUMENT;
+    const int N = scene->n, W = c.cameras[0].image_width, H = c.cameras[0].image_height;
+    if (W <= 0 || H <= 0) return PGR_ERR_INVALID_ARGUMENT;
+    for (int v = 0; v < c.n_views; ++v) {
+        if (c.cameras[v].image_width != W || c.cameras[v].image_height != H) return PGR_ERR_INVALID_ARGUMENT;
+        if (!c.views[v].grad_color || !c.views[v].final_T || !c.views[v].n_contrib) return PGR_ERR_INVALID_ARGUMENT;
+        if (N > 0 && !c.views[v].radii) return PGR_ERR_INVALID_ARGUMENT;
+    }
+    if (N == 0) return PGR_OK;
+    const BackwardScratch S = backward_scratch(N, c.n_views);
+    if (!c.workspace || !c.scratch || c.scratch_bytes < S.total) return PGR_ERR_INVALID_ARGUMENT;
+    p->L = make_layout(N, W, H, c.max_instances_per_view);
+    p->B = make_batch_layout(p->L, c.n_views, (size_t)N);
+    if (c.workspace_bytes < p->B.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    p->ws = static_cast<char*>(c.workspace);
+    p->rows = static_cast<float*>(c.scratch);
+    p->table = reinterpret_cast<BwdViewDev*>(static_cast<char*>(c.scratch) + S.table);
+    return PGR_OK;
 }
 
-int32_t pgr_backward_batch_camera(const PgrScene* scene, int32_t n_views, const PgrCamera* cameras,
-                                  const PgrBackwardView* views, const float* const* grad_alpha, void* workspace,
-                                  size_t workspace_bytes, int64_t max_instances_per_view, const PgrGradOutputs* grads,
-                                  void* scratch, size_t scratch_bytes, const PgrCameraGrad* camera_grads, void* cam_scratch,
-                                  size_t cam_scratch_bytes, void* stream_v) {
-    if (!camera_grads || !scene || scene->n < 0 || n_views <= 0 || !cam_scratch ||
-        cam_scratch_bytes < camera_scratch_bytes(scene->n, n_views))
-        return PGR_ERR_INVALID_ARGUMENT;
+// The plan, the scene backward, then (with camera_grads) the camera kernels.
+int32_t pgr_backward(const PgrBackwardCall* c, void* stream_v) {
+    if (!c) return PGR_ERR_INVALID_ARGUMENT;
     BackwardPlan p{};
-    if (int rc = backward_batch_plan(scene, n_views, cameras, views, workspace, workspace_bytes, max_instances_per_view, grads,
-                                     scratch, scratch_bytes, &p))
-        return rc;
-    return backward_launch(scene, n_views, views, grad_alpha, p, grads, camera_grads, cam_scratch, stream_v);
+    if (int rc = backward_plan(*c, &p)) return rc;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    if (c->scene->n > 0)
+        if (int32_t rc = backward_impl(c->scene, c->n_views, c->views, c->grad_alpha, p.ws, p.L, p.B, c->grads, p.rows, p.table,
+                                       stream))
+            return rc;
+    if (!c->camera_grads) return PGR_OK;
+    return camera_backward_impl(c->scene, c->n_views, c->camera_grads, p.table,
+                                reinterpret_cast<const CameraDev*>(p.ws + p.B.cams), static_cast<float*>(c->camera_scratch),
+                                stream);
 }
 
 int32_t pgr_compose_object(int32_t n, const float* xyz, const float* rot, const float* f_rest, int32_t n_rest,

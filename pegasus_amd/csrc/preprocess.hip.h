@@ -239,7 +239,7 @@ struct PosedDev {
     int32_t k;
 };
 
-// LAYERED (pgr_forward_layers_async: silhouettes): Gaussian i belongs to image layer_id[i] of the view (0: to none, it is
+// LAYERED (PgrForwardCall::layers: silhouettes): Gaussian i belongs to image layer_id[i] of the view (0: to none, it is
 // dropped).  Everything per Gaussian is computed as if its layer were rendered alone; only the tile ROWS of its rectangles
 // are moved down by (layer - 1) x grid_y, so that the binning sees one tall image of n_layers x grid_y tile rows and
 // builds per-(tile, layer) lists.

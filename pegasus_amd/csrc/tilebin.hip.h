@@ -138,7 +138,7 @@ __host__ __device__ inline size_t bin_lds_bytes(int tiles, int threads) {
     return ((size_t)(tiles < BIN_LDS_TILES ? tiles : BIN_LDS_TILES) + 3) / 4 * 16 + (size_t)(threads / WAVE) * BIN_STAGE_WORDS * 4 + 16;
 }
 
-// LAYERED binning (pgr_forward_layers_async): the view is one tall image of n_layers x layer_rows tile rows, `tiles` =
+// LAYERED binning (PgrForwardCall::layers): the view is one tall image of n_layers x layer_rows tile rows, `tiles` =
 // n_layers x layer_tiles.  Gaussians are ordered by layer, so a chunk of 4096 holds one layer (two at a boundary): the
 // chunk histograms ONE layer per LDS pass -- lo = (layer - 1) x layer_tiles, span = layer_tiles -- over the layers its
 // first and last Gaussian name; a 64-Gaussian group takes part in the passes of the layers it holds, and a group that
@@ -399,7 +399,7 @@ __global__ __launch_bounds__(1024) void tile_scan_kernel(const BinView* __restri
         const uint32_t over = carry_s > (unsigned long long)max_instances ? 1u : 0u;
         bv.counters[0] = total;
         bv.counters[1] = over;
-        // early status (pgr_forward_posed_early_status): the two words are FINAL here -- nothing after the scan changes them --
+        // early status (PgrForwardCall::status_event): the two words are FINAL here -- nothing after the scan changes them --
         // so they go straight to the caller's pinned host memory, and the event recorded behind this kernel lets the host
         // decide about an overflow while scatter, sort and compositor still run
         if (host_status) {

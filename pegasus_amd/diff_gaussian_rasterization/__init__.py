@@ -14,7 +14,7 @@ Same surface as the module the reference installs from its (absent) submodule
 Camera gradients: the viewmatrix, projmatrix and campos tensors of the settings are differentiable inputs too.  When
 autograd is on and any of them requires grad, the render takes the differentiable path even if no scene tensor does (a
 frozen model rendered from a camera being refined), and their .grad receives the exact partial of the loss with respect
-to each of their entries, each treated as an independent input (pgr_backward_camera / pgr_backward_batch_camera;
+to each of their entries, each treated as an independent input (PgrBackwardCall.camera_grads;
 entries the forward never reads -- viewmatrix[4k+3], projmatrix[4k+2] -- get 0, campos gets 0 with colors_precomp).
 A camera built from a pose (pegasus_amd.camera_pose.PosedCamera) passes them on to the pose through torch.  Without a
 camera tensor that requires grad the call and its launches are those of a scene-only backward.
@@ -69,7 +69,7 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     """Forward rasterization of one view.  Returns (color, radii, depth) -- plus (final_T, n_contrib)
     when ``want_aux``.
 
-    The call is ENQUEUED without a host round trip (pgr_forward_posed_early_status: tables through pinned memory), then
+    The call is ENQUEUED without a host round trip (PgrForwardCall.status_event: tables through pinned memory), then
     ``after_enqueue(result_dict)`` runs -- work that only needs the outputs in stream order, e.g. render()'s visibility
     filter, is queued behind the compositor -- and then the host waits for the call's STATUS WORDS only, which are final
     behind the tile scan (a third into the call: the one thing the host has to decide is whether the instance capacity
@@ -104,8 +104,7 @@ class _RasterizeGaussians(torch.autograd.Function):
     GaussianRasterizationSettings with one image size.  Outputs color [V,3,H,W], radii [V,n] (not differentiable), depth
     [V,1,H,W]; gradients of the scene inputs are summed over the views, and ``means2D`` [V,n,3] receives every view's own
     screen-space gradient.  ``single`` (the drop-in GaussianRasterizer: V = 1) drops the view axis of every output and of
-    ``means2D`` and goes through pgr_forward / pgr_backward_ex; otherwise one pgr_forward_batch call and its
-    pgr_backward_batch_ex.
+    ``means2D``; either way the forward is one pgr_forward call and the backward one pgr_backward call.
 
     The call keeps its own workspace (the backward walks the same per-tile lists), so it does not share the pooled scratch
     of the no-grad path, and retries an instance overflow with a grown capacity.  Every tensor the backward re-reads goes
@@ -118,7 +117,7 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     ``cam_inputs``: empty, or the 3 V tensors (viewmatrix, projmatrix, campos of every view, None allowed) passed when one of
     them requires grad (``_camera_inputs``).  They are the tensors ``settings`` holds, handed to ``apply`` so that autograd
-    tracks them; the backward then goes through the camera entries and returns their gradients shaped like them."""
+    tracks them; the backward then asks for the camera gradients and returns them shaped like the tensors."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, single,
@@ -156,14 +155,15 @@ class _RasterizeGaussians(torch.autograd.Function):
             for c, d, r, ft, nc in zip(*map(per_view, (color, depth, radii, final_T, n_contrib)))])
         need = (C.c_int64 * V)()
         ws = None
-        entry, lead_args = ("pgr_forward", (C.byref(scene),)) if single else ("pgr_forward_batch", (C.byref(scene), V))
+        call = _lib.PgrForwardCall(scene=C.pointer(scene), n_views=V, cameras=cams, outs=outs, num_instances=need)
 
         def run(capacity):
             nonlocal ws
             ws = torch.empty(L.pgr_batch_workspace_bytes(n, W, H, capacity, V), dtype=torch.uint8, device=device)
-            return _lib.enqueue(entry, device, *lead_args, cams, outs, ptr(ws), ws.numel(), capacity, need), need
+            call.workspace, call.workspace_bytes, call.max_instances_per_view = ws.data_ptr(), ws.numel(), capacity
+            return _lib.enqueue("pgr_forward", device, call), need
         status, _, max_inst = _until_fits(run, max(1 << 18, 4 * n), 1.25)
-        _lib.check(status, entry)
+        _lib.check(status, "pgr_forward")
         ctx.hw, ctx.V, ctx.n, ctx.max_inst, ctx.single = (H, W), V, n, max_inst, single
         ctx.sh_degree, ctx.scale_modifier = int(rs0.sh_degree), float(rs0.scale_modifier)
         ctx.cam_meta = tuple(None if x is None else (tuple(x.shape), x.dtype) for x in cam_inputs)
@@ -209,32 +209,28 @@ class _RasterizeGaussians(torch.autograd.Function):
               else grad_color.contiguous().float())
         gd = None if grad_depth is None else grad_depth.contiguous().float()
         ga = None if grad_alpha is None else grad_alpha.contiguous().float()
-        # camera gradients: [V, 35] written by the camera kernels (only the wanted ones get a pointer)
+        per_view = lambda x: (None,) * V if x is None else (x,) if single else x.unbind(0)
+        views = (_lib.PgrBackwardView * V)(*[
+            _lib.PgrBackwardView(grad_color=ptr(c), grad_depth=ptr(d), final_T=ptr(ft), n_contrib=ptr(nc), radii=ptr(r))
+            for c, d, ft, nc, r in zip(*map(per_view, (gc, gd, final_T, n_contrib, radii)))])
+        scratch = torch.empty(max(1, L.pgr_backward_batch_scratch_bytes(n, V)), dtype=torch.uint8, device=device)
+        call = _lib.PgrBackwardCall(scene=C.pointer(scene), n_views=V, cameras=cams, views=views, workspace=ws.data_ptr(),
+                                    workspace_bytes=ws.numel(), max_instances_per_view=ctx.max_inst, grads=C.pointer(grads),
+                                    scratch=scratch.data_ptr(), scratch_bytes=scratch.numel())
+        if ga is not None:
+            call.grad_alpha = (C.c_void_p * V)(*[a.data_ptr() for a in per_view(ga)])
+        # camera gradients: [V, 35] written by the camera kernels (only the wanted ones get a pointer); without them the
+        # call and its launches are the scene-only ones
         want_cam = [m is not None and ctx.needs_input_grad[11 + j] for j, m in enumerate(ctx.cam_meta)]
         sl = ((0, 16), (16, 32), (32, 35))
-        cam_g, cam_args = None, ()
+        cam_g = None
         if any(want_cam):
             cam_g = torch.empty((V, 35), dtype=torch.float32, device=device)
-            cam_structs = (_lib.PgrCameraGrad * V)(*[_lib.PgrCameraGrad(*[
+            call.camera_grads = (_lib.PgrCameraGrad * V)(*[_lib.PgrCameraGrad(*[
                 ptr(cam_g[v, a:b]) if want_cam[3 * v + c] else None for c, (a, b) in enumerate(sl)]) for v in range(V)])
             cam_scratch = torch.empty(L.pgr_camera_grad_scratch_bytes(n, V), dtype=torch.uint8, device=device)
-            cam_args = (cam_structs, ptr(cam_scratch), cam_scratch.numel())
-        # one call per mode; the camera entries take the scene-only entries' arguments, then cam_args, then the stream
-        shared = (ptr(ws), ws.numel(), ctx.max_inst, C.byref(grads))
-        if single:
-            entry = "pgr_backward_camera" if cam_args else "pgr_backward_ex"
-            rows = torch.empty((n, 12), dtype=torch.float32, device=device)
-            args = (cams, ptr(gc), ptr(gd), ptr(ga), ptr(final_T), ptr(n_contrib), ptr(radii), *shared, ptr(rows))
-        else:
-            entry = "pgr_backward_batch_camera" if cam_args else "pgr_backward_batch_ex"
-            alpha_ptrs = None if ga is None else (C.c_void_p * V)(*[ga[v].data_ptr() for v in range(V)])
-            views = (_lib.PgrBackwardView * V)(*[
-                _lib.PgrBackwardView(grad_color=ptr(gc[v]), grad_depth=None if gd is None else ptr(gd[v]),
-                                     final_T=ptr(final_T[v]), n_contrib=ptr(n_contrib[v]), radii=ptr(radii[v]))
-                for v in range(V)])
-            scratch = torch.empty(max(1, L.pgr_backward_batch_scratch_bytes(n, V)), dtype=torch.uint8, device=device)
-            args = (V, cams, views, alpha_ptrs, *shared, ptr(scratch), scratch.numel())
-        _lib.call(entry, device, C.byref(scene), *args, *cam_args)
+            call.camera_scratch, call.camera_scratch_bytes = cam_scratch.data_ptr(), cam_scratch.numel()
+        _lib.call("pgr_backward", device, call)
         cam_out = tuple(cam_g[j // 3, sl[j % 3][0]:sl[j % 3][1]].reshape(m[0]).to(m[1]) if want_cam[j] else None
                         for j, m in enumerate(ctx.cam_meta))
         # means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, settings, single, return_alpha,

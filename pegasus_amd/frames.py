@@ -302,7 +302,7 @@ class FrameRenderer:
         """Silhouette masks [B, K, H, W] uint8: object k rendered ALONE in its semantic colour and thresholded, i.e. its
         full outline whatever occludes it in the scene (/root/reference/src/gs/render.py:36-65 does this with one
         deepcopy + merge + render per object and camera).  ONE layered batch call for all K objects (round 4;
-        pgr_forward_layers_async): the objects-only cloud is binned into per-(tile, object) lists -- the view is K stacked
+        PgrForwardCall.layers): the objects-only cloud is binned into per-(tile, object) lists -- the view is K stacked
         copies of the tile grid -- and the compositor's epilogue thresholds layer k against colour k, so no image is
         written or read back.  Bit-identical to K single-object passes (render_silhouettes_per_object, kept as the
         checker).  ``poses`` as in render_frames; ``wait=False`` returns (out, pending) with the batch still in flight

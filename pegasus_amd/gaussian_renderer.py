@@ -188,8 +188,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
 
 def render_batch(cameras, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
                  return_alpha=False):
-    """Render ``pc`` from V cameras of one image size in one differentiable call (pgr_forward_batch; backward
-    pgr_backward_batch): the training path's several views per optimiser step.  ``bg_color`` is [3] (every view) or [V,3]
+    """Render ``pc`` from V cameras of one image size in one differentiable call (pgr_forward; backward
+    pgr_backward): the training path's several views per optimiser step.  ``bg_color`` is [3] (every view) or [V,3]
     (one background per view).  Returns "render" [V,3,H,W], "depth" [V,1,H,W], "viewspace_points" [V,N,3] (a leaf whose
     .grad receives each view's own screen-space gradient when autograd is on), "visibility_filter" [V,N] (radii > 0) and
     "radii" [V,N].  Colours come from the kernel-evaluated SH (or ``override_color``, shared by every view);

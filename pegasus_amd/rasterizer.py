@@ -1,7 +1,7 @@
 """Host side of the rasterizer: turns torch tensors into the C-ABI structs of
 include/pegasus_raster.h, manages the torch-owned workspace, and handles instance-capacity growth.
 
-``forward_views`` renders a batch of views of one scene through ``pgr_forward_batch``; the
+``forward_views`` renders a batch of views of one scene through ``pgr_forward``; the
 drop-in ``GaussianRasterizer`` (pegasus_amd.diff_gaussian_rasterization) is the n_views == 1 case.
 There is no CPU fallback anywhere in this module.
 """
@@ -56,7 +56,7 @@ class _Workspace:
         return t
 
     def status_event(self, device, slot) -> torch.cuda.Event:
-        """One event per asynchronous slot for pgr_forward_posed_early_status.  torch creates the HIP event at the first
+        """One event per asynchronous slot for PgrForwardCall.status_event.  torch creates the HIP event at the first
         record(); after that ``cuda_event`` is the handle the library records again on every call."""
         key = ("status-event", device, slot)
         ev = self.buf.get(key)
@@ -245,22 +245,22 @@ def forward_views(means3D, opacities, views: Sequence[ViewSpec], *, shs=None, co
     """Renders ``len(views)`` views of one scene.  Returns a list of dicts with keys
     color[3,H,W], depth[1,H,W], radii[N] (or None), and final_T / n_contrib when ``want_aux``.
 
-    ``stage_ms``: pass an empty list to use the profiling entry point; it receives the per-stage
+    ``stage_ms``: pass an empty list to have the call timed (PgrForwardCall.stage_ms); it receives the per-stage
     milliseconds (whole batch) measured with HIP events on the launch stream.
     ``outputs``: optional pre-allocated list of dicts (same keys) to render into.
     ``async_slot``: not None -> enqueue on torch's CURRENT stream without synchronising and return a
     PendingBatch; the slot names the workspace / pinned scratch to use (one batch in flight per slot).  After an instance
     overflow its wait() renders the batch again: a layered call on the same slot, any other as the synchronous call does.
     A synchronous call with ``semantic`` or ``posed`` (and no ``stage_ms``) is an asynchronous one on the "sync-fused" slot,
-    waited for; any other goes through pgr_forward_batch (or pgr_forward_batch_profiled) on the pooled workspace.
+    waited for; any other is a synchronous pgr_forward call on the pooled workspace.
     ``record_info`` (with ``async_slot``): PendingBatch.wait() fills last_forward_info() like a synchronous call.
     ``shs_rest``: the SH coefficients as the model stores them -- ``shs`` = _features_dc [N,1,3], ``shs_rest`` = _features_rest
     [N,K-1,3] (PgrScene::shs_rest) -- instead of their concatenation; results are bit-identical.
     ``early_status`` (with ``async_slot``, not layered): PendingBatch.wait() returns as soon as the call's status words are
-    final -- behind the tile scan, pgr_forward_posed_early_status -- instead of at the end of the call; the outputs are
+    final -- behind the tile scan, PgrForwardCall.status_event -- instead of at the end of the call; the outputs are
     complete in stream order (whatever the caller queues on the current stream, or fetches with .cpu(), comes after them).
     ``semantic``: dict(object_id int32[N], colors float32[K,3], n_env, k) -> the fused objects-only semantic
-    render is written to r["sem_color"] (and r["sem_depth"]) of every view (pgr_forward_posed_async).
+    render is written to r["sem_color"] (and r["sem_depth"]) of every view (PgrForwardCall.semantic).
     ``semantic`` may also carry ``mask_colors`` float32[K,3] (+ ``mask_threshold``): every output dict with a ``sem_masks``
     uint8[K,H,W] tensor then receives the K colour-distance masks of the semantic image from the compositor's epilogue
     (bit for bit what color_masks() computes from ``sem_color``), and ``object_id_u8`` (scene_prepare()).
@@ -270,10 +270,10 @@ def forward_views(means3D, opacities, views: Sequence[ViewSpec], *, shs=None, co
     ``tie_index``: int32[N] permutation -- exact depth ties are broken by it instead of the position (PgrScene.tie_index);
     ``tie_inv``: its inverse from scene_prepare() (otherwise rebuilt per call).
     ``layers``: dict(layer_id int32[N], n_layers, mask_colors float32[n_layers,3], mask_threshold) -> LAYERED call
-    (pgr_forward_layers_async, asynchronous only): Gaussian i is composited into image layer_id[i] alone and every
+    (PgrForwardCall.layers, asynchronous only): Gaussian i is composited into image layer_id[i] alone and every
     output dict's ``sem_masks`` uint8[n_layers,H,W] receives the layers' masks (silhouettes); no colour image.
     ``posed``: dict(object_id int32[N], poses float32[len(views), K, 20]) -> dynamic scene: view i places object k by
-    poses[i, k-1] inside the preprocess (pgr_forward_posed_async; pegasus_amd.compose.pose_table builds the rows).
+    poses[i, k-1] inside the preprocess (PgrForwardCall.posed; pegasus_amd.compose.pose_table builds the rows).
     """
     L = _lib.lib()
     device = means3D.device
@@ -286,11 +286,11 @@ def forward_views(means3D, opacities, views: Sequence[ViewSpec], *, shs=None, co
     if any(int(v.image_height) != H or int(v.image_width) != W for v in views):
         raise ValueError("all views of a batch must share the image size")
     if posed is not None and stage_ms is not None:
-        raise ValueError("the profiling entry point does not take posed objects")
+        raise ValueError("a profiled call does not take posed objects")
     if layers is not None and (async_slot is None or semantic is not None or stage_ms is not None):
         raise ValueError("a layered call is asynchronous (async_slot) and takes no semantic descriptor")
     if async_slot is not None:
-        stage_ms = None          # the asynchronous entries are not profiled, nor is the synchronous retry of an overflow
+        stage_ms = None          # an asynchronous call is not profiled, nor is the synchronous retry of an overflow
     fused = (semantic is not None or posed is not None) and stage_ms is None
     n = int(means3D.shape[0])
     shs, shs_rest = dev_f32(shs, device), dev_f32(shs_rest, device)
@@ -303,7 +303,6 @@ def forward_views(means3D, opacities, views: Sequence[ViewSpec], *, shs=None, co
                    cov3D_precomp=cov3D_precomp)
     tensors = {k: dev_f32(t, device) for k, t in tensors.items()}
     tensors.update(shs=shs, shs_rest=shs_rest, tie_index=tie_index, tie_inv=tie_inv)
-    scene = C.byref(scene_struct(n, sh_degree=sh_degree, scale_modifier=scale_modifier, **tensors))
     cams, cam_tensors = camera_structs(views, device)
 
     if outputs is not None:
@@ -330,53 +329,52 @@ def forward_views(means3D, opacities, views: Sequence[ViewSpec], *, shs=None, co
                         record=_ptr(r.get("record")) if layers is None else None)
         for r in results])
 
-    sem = posed_ref = poses = layers_ref = None
+    # ONE call descriptor; an attempt sets its workspace, its capacity and what makes it synchronous or asynchronous
+    call = _lib.PgrForwardCall(scene=C.pointer(scene_struct(n, sh_degree=sh_degree, scale_modifier=scale_modifier, **tensors)),
+                               n_views=nv, cameras=cams, outs=outs)
+    poses = None
     if posed is not None:
         poses = dev_f32(posed["poses"], device)
         if poses.dim() != 3 or poses.shape[0] != nv or poses.shape[2] != _lib.PGR_POSE_STRIDE:
             raise ValueError("posed['poses'] must be [n_views, K, 20]")
-        posed_ref = C.byref(_lib.PgrPosedObjects(object_id=_ptr(posed["object_id"]), poses=_ptr(poses),
-                                                 k_objects=int(poses.shape[1])))
+        call.posed = C.pointer(_lib.PgrPosedObjects(object_id=_ptr(posed["object_id"]), poses=_ptr(poses),
+                                                    k_objects=int(poses.shape[1])))
     if semantic is not None:
-        sem = C.byref(_lib.PgrSemantic(object_id=_ptr(semantic["object_id"]), colors=_ptr(semantic["colors"]),
-                                       n_env=int(semantic["n_env"]), k_objects=int(semantic["k"]),
-                                       object_id_u8=_ptr(semantic.get("object_id_u8")),
-                                       mask_colors=_ptr(semantic.get("mask_colors")),
-                                       mask_threshold=float(semantic.get("mask_threshold", 0.1))))
+        call.semantic = C.pointer(_lib.PgrSemantic(object_id=_ptr(semantic["object_id"]), colors=_ptr(semantic["colors"]),
+                                                   n_env=int(semantic["n_env"]), k_objects=int(semantic["k"]),
+                                                   object_id_u8=_ptr(semantic.get("object_id_u8")),
+                                                   mask_colors=_ptr(semantic.get("mask_colors")),
+                                                   mask_threshold=float(semantic.get("mask_threshold", 0.1))))
     key = (device, n, W, H)
     if layers is not None:
         n_layers = int(layers["n_layers"])
-        layers_ref = C.byref(_lib.PgrLayers(layer_id=_ptr(layers["layer_id"]), n_layers=n_layers,
-                                            mask_colors=_ptr(layers["mask_colors"]),
-                                            mask_threshold=float(layers.get("mask_threshold", 0.1))))
+        call.layers = C.pointer(_lib.PgrLayers(layer_id=_ptr(layers["layer_id"]), n_layers=n_layers,
+                                               mask_colors=_ptr(layers["mask_colors"]),
+                                               mask_threshold=float(layers.get("mask_threshold", 0.1))))
         key += ("layers", n_layers)
     default_capacity = max(1 << 20, 6 * n)
     ws = None          # the workspace of the latest attempt
 
     def workspace(slot, capacity):
+        nonlocal ws
         nbytes = (L.pgr_batch_workspace_bytes(n, W, H, capacity, nv) if layers is None else
                   L.pgr_layers_workspace_bytes(n, W, H, capacity, nv, n_layers))
         if nbytes == 0:
             raise ValueError("pgr_batch_workspace_bytes: invalid sizes")
-        return _WS.get(device, nbytes, slot=slot)
+        ws = _WS.get(device, nbytes, slot=slot)
+        call.workspace, call.workspace_bytes, call.max_instances_per_view = ws.data_ptr(), ws.numel(), capacity
 
     def enqueue(slot, capacity, early=False):
         """One asynchronous attempt on ``slot``'s workspace and pinned scratch: (scratch, event behind the status words)."""
-        nonlocal ws
-        ws = workspace(("async", slot), capacity)
+        workspace(("async", slot), capacity)
         scratch = _WS.pinned(slot, L.pgr_host_scratch_bytes(nv))
-        args = (nv, cams, outs, _ptr(ws), ws.numel(), capacity, _ptr(scratch), scratch.numel())
-        if layers is not None:
-            _lib.call("pgr_forward_layers_async", device, scene, layers_ref, posed_ref, *args)
-        elif early:
-            event = _WS.status_event(device, slot)
-            _lib.call("pgr_forward_posed_early_status", device, scene, sem, posed_ref, *args,
-                      after_stream=(C.c_void_p(event.cuda_event),))
-            return scratch, event
-        else:
-            _lib.call("pgr_forward_posed_async", device, scene, sem, posed_ref, *args)
-        event = torch.cuda.Event()
-        event.record(torch.cuda.current_stream(device))
+        event = _WS.status_event(device, slot) if early else torch.cuda.Event()
+        call.host_scratch, call.host_scratch_bytes = scratch.data_ptr(), scratch.numel()
+        call.status_event = event.cuda_event if early else None
+        call.num_instances = call.stage_ms = None
+        _lib.call("pgr_forward", device, call)
+        if not early:
+            event.record(torch.cuda.current_stream(device))
         return scratch, event
 
     def waited_on(slot):
@@ -394,16 +392,14 @@ def forward_views(means3D, opacities, views: Sequence[ViewSpec], *, shs=None, co
 
     def run_plain(capacity):
         """One synchronous attempt on the pooled workspace: (status, per-view instance counts)."""
-        nonlocal ws
+        workspace(0, capacity)
         need = (C.c_int64 * nv)()
-        ws = workspace(0, capacity)
-        if stage_ms is not None:
-            ms = (C.c_float * _lib.PGR_NUM_STAGES)()
-            status = _lib.enqueue("pgr_forward_batch_profiled", device, scene, sem, nv, cams, outs, _ptr(ws), ws.numel(),
-                                  capacity, need, after_stream=(ms,))
+        ms = None if stage_ms is None else (C.c_float * _lib.PGR_NUM_STAGES)()
+        call.host_scratch = call.status_event = None
+        call.num_instances, call.stage_ms = need, ms
+        status = _lib.enqueue("pgr_forward", device, call)
+        if ms is not None:
             stage_ms[:] = list(ms)
-        else:
-            status = _lib.enqueue("pgr_forward_batch", device, scene, nv, cams, outs, _ptr(ws), ws.numel(), capacity, need)
         return status, need
 
     def render_sync():
@@ -412,7 +408,7 @@ def forward_views(means3D, opacities, views: Sequence[ViewSpec], *, shs=None, co
             _remember(key, need, capacity, ws)
         else:
             status, need, capacity = _until_fits(run_plain, _WS.capacity_hint.get(key, default_capacity), 1.25)
-            _lib.check(status, "pgr_forward_batch")
+            _lib.check(status, "pgr_forward")
             _remember(key, need, capacity, ws, max_instances=_learn(key, capacity, max(need)))
         return results
 

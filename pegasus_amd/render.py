@@ -45,7 +45,7 @@ def _without_environment(scene, n_env):
 
 def render_silhouette_mask(cam, gs_object_list, gs_env, width, height, color_set, pipe_settings, bg):
     """Every object rendered ALONE in its semantic colour over an empty environment and thresholded (render.py:36-65: one
-    deepcopy + merge + render per object).  Here: ONE layered rasterizer call for all objects (pgr_forward_layers_async:
+    deepcopy + merge + render per object).  Here: ONE layered rasterizer call for all objects (PgrForwardCall.layers:
     per-(tile, object) lists, the compositor's epilogue thresholds layer k against colour k) over the objects-only scene
     the other two semantic wrappers share -- bit-equal to the per-object form below, which stays as the path for the
     settings the layered call does not take (python-side covariances / SH, autograd, object ids that do not ascend)."""

@@ -15,12 +15,12 @@ With --masks (an object trained from per-image masks, as PEGASUS's reconstructio
 accumulated opacity too and takes MaskedImageLoss (pgr_image_loss_masked): the target is the image inside the mask over
 the step's own background, plus lambda_alpha mean|alpha - mask|, whose gradient reaches the backward as dL/dalpha.
 
-With --batch_size B > 1 a step renders B views in one render_batch (pgr_forward_batch / pgr_backward_batch) and the Adam
+With --batch_size B > 1 a step renders B views in one render_batch (pgr_forward / pgr_backward) and the Adam
 step, which touches every parameter whatever the number of views, is paid once per B views.
 
 With --pose_lr > 0 the training cameras' poses are refined with the Gaussians (scans whose registration is slightly off):
 every training camera gets a pose correction (pegasus_amd.camera_pose.PosedCamera), a 6-vector that the camera gradient
-of the rasterizer (pgr_backward_camera) reaches through torch, updated by its own Adam (rotation lr pose_lr, translation lr
+of the rasterizer (PgrBackwardCall.camera_grads) reaches through torch, updated by its own Adam (rotation lr pose_lr, translation lr
 pose_lr x cameras_extent) with the Gaussian optimiser's step.  The train report renders the refined cameras, test cameras
 keep their poses, every save writes cameras_refined.json and every checkpoint the corrections to chkpntN_poses.pth.
 """

@@ -1,4 +1,4 @@
-"""Stage times of ONE call against the number of views in it (HIP events at the stage boundaries, pgr_forward_batch_profiled):
+"""Stage times of ONE call against the number of views in it (HIP events at the stage boundaries, PgrForwardCall.stage_ms):
 where a call stops being bound by the critical path of its longest lists / chunks and becomes throughput.
     python scripts/batch_size_curve.py [c3|c5]"""
 import sys

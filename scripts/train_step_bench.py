@@ -3,12 +3,12 @@ forward / loss / backward / stats / optimizer with HIP events, plus two same-box
     loss:      pgr_image_loss (value + gradient, one call)  vs  the torch conv2d form of the same loss + its backward
     optimizer: FusedAdam (one pgr_adam_step launch)         vs  torch.optim.Adam(foreach=True)
 Inputs are random (targets, gradients); every stage is warmed up first; each number is the median of 5 repeats.
---batch B ... adds multi-view steps (render_batch: B views per optimiser step, one pgr_forward_batch and one
-pgr_backward_batch) with the same stage split, per step and per view; "backward" is the HIP-event time of loss.backward(),
+--batch B ... adds multi-view steps (render_batch: B views per optimiser step, one pgr_forward and one
+pgr_backward) with the same stage split, per step and per view; "backward" is the HIP-event time of loss.backward(),
 i.e. of the backward kernels.  B = 1 is the single-view loop above (the default, whose output is unchanged).
 --masks adds, beside every plain step, the same step trained from object masks (a seeded synthetic soft mask per camera):
 render with return_alpha, MaskedImageLoss (pgr_image_loss_masked) against the step's background, backward with dL/dalpha
-(pgr_backward_ex / pgr_backward_batch_ex); reported as "masked" next to the plain numbers.
+(PgrBackwardCall.grad_alpha); reported as "masked" next to the plain numbers.
 
     python scripts/train_step_bench.py [--iters 20] [--warmup 5] [--repeats 5] [--scenes c2 c3] [--batch 1 2 4 8]
                                        [--masks] [--json out.json]

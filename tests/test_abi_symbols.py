@@ -31,7 +31,7 @@ def test_library_exports_every_declared_symbol():
 def test_version_and_status_strings():
     from pegasus_amd import _lib
     lib = _lib.lib()
-    assert lib.pgr_abi_version() == 3 == _lib.PGR_ABI_VERSION
+    assert lib.pgr_abi_version() == 4 == _lib.PGR_ABI_VERSION
     assert b"gfx950" in lib.pgr_version()
     assert lib.pgr_status_string(0) == b"ok"
     assert lib.pgr_status_string(-3) == b"instance buffer overflow"
@@ -67,12 +67,20 @@ def test_invalid_arguments_are_rejected_before_any_launch():
     cam = _lib.PgrCamera(image_width=64, image_height=64, tanfovx=0.5, tanfovy=0.5)
     out = _lib.PgrOutputs()
     need = C.c_int64(0)
-    rc = lib.pgr_forward(C.byref(scene), C.byref(cam), C.byref(out), None, 0, 100, C.byref(need), None)
+    rc = lib.pgr_forward(_forward_call(_lib, scene, cam, out, num_instances=C.pointer(need)), None)
     assert rc == _lib.PGR_ERR_INVALID_ARGUMENT
     with pytest.raises(ValueError):
         _lib.check(rc, "pgr_forward")
     assert lib.pgr_mark_visible(-1, None, None, None, None) == _lib.PGR_ERR_INVALID_ARGUMENT
     assert lib.pgr_color_masks(None, 1, 8, 8, None, 1, 0.1, None, None) == _lib.PGR_ERR_INVALID_ARGUMENT
+
+
+def _forward_call(_lib, scene, cam, out, workspace=None, workspace_bytes=0, **fields):
+    """A one-view PgrForwardCall at capacity 100; ``fields`` sets or overrides anything."""
+    kw = dict(scene=C.pointer(scene), n_views=1, cameras=C.pointer(cam), outs=C.pointer(out), workspace=workspace,
+              workspace_bytes=workspace_bytes, max_instances_per_view=100)
+    kw.update(fields)
+    return _lib.PgrForwardCall(**kw)
 
 
 def test_rasterizer_refuses_cpu_tensors():
@@ -91,7 +99,7 @@ def test_rasterizer_refuses_cpu_tensors():
 
 
 def test_new_entry_points_validate_before_any_launch():
-    """pgr_forward_layers_async / sem_masks / depth_mode / pgr_pack_records / pgr_scene_prepare: argument misuse is an
+    """PgrForwardCall.layers / sem_masks / depth_mode / pgr_pack_records / pgr_scene_prepare: argument misuse is an
     integer status from host-side checks (fake non-NULL device pointers are never dereferenced; no device is touched)."""
     from pegasus_amd import _lib
     lib = _lib.lib()
@@ -103,9 +111,11 @@ def test_new_entry_points_validate_before_any_launch():
     scratch = (C.c_char * int(lib.pgr_host_scratch_bytes(1)))()
     good_layers = _lib.PgrLayers(layer_id=fake, n_layers=3, mask_colors=fake, mask_threshold=0.1)
 
+    host = dict(host_scratch=C.addressof(scratch), host_scratch_bytes=len(scratch))
+
     def layers_rc(layers, out, camera=cam):
-        return lib.pgr_forward_layers_async(C.byref(scene), C.byref(layers) if layers is not None else None, None, 1,
-                                            C.byref(camera), C.byref(out), None, 0, 100, scratch, len(scratch), None)
+        return lib.pgr_forward(_forward_call(_lib, scene, camera, out, layers=None if layers is None else C.pointer(layers),
+                                             **host), None)
     no_masks = _lib.PgrOutputs(color=fake, depth=fake)
     with_masks = _lib.PgrOutputs(sem_masks=fake)
     assert layers_rc(None, with_masks) == _lib.PGR_ERR_INVALID_ARGUMENT                       # no descriptor
@@ -120,27 +130,29 @@ def test_new_entry_points_validate_before_any_launch():
                              campos=fake, bg=fake, depth_mode=7)
     need = C.c_int64(0)
     out = _lib.PgrOutputs(color=fake, depth=fake, radii=fake)
-    assert lib.pgr_forward(C.byref(scene), C.byref(bad_cam), C.byref(out), None, 0, 100, C.byref(need), None) == _lib.PGR_ERR_INVALID_ARGUMENT
+    assert lib.pgr_forward(_forward_call(_lib, scene, bad_cam, out, num_instances=C.pointer(need)), None) == _lib.PGR_ERR_INVALID_ARGUMENT
     # masks from the compositor's epilogue need the colours to threshold against
     sem = _lib.PgrSemantic(object_id=fake, colors=fake, n_env=5, k_objects=2)                 # no mask_colors
     out_m = _lib.PgrOutputs(color=fake, depth=fake, sem_color=fake, sem_masks=fake)
-    assert lib.pgr_forward_frames_async(C.byref(scene), C.byref(sem), 1, C.byref(cam), C.byref(out_m), None, 0, 100, scratch,
-                                        len(scratch), None) == _lib.PGR_ERR_INVALID_ARGUMENT
+    assert lib.pgr_forward(_forward_call(_lib, scene, cam, out_m, semantic=C.pointer(sem), **host), None) == _lib.PGR_ERR_INVALID_ARGUMENT
     # the split SH layout (PgrScene::shs_rest): needs the first coefficient in `shs` and room for more than one; the
     # backward takes the concatenated layout only (its SH gradient is one array)
     for bad_scene in (_lib.PgrScene(n=10, means3d=fake, opacities=fake, scales=fake, rotations=fake, colors_precomp=fake,
                                     shs_rest=fake, scale_modifier=1.0),
                       _lib.PgrScene(n=10, means3d=fake, opacities=fake, scales=fake, rotations=fake, shs=fake, shs_rest=fake,
                                     sh_degree=0, sh_stride=1, scale_modifier=1.0)):
-        assert lib.pgr_forward(C.byref(bad_scene), C.byref(cam), C.byref(out), None, 0, 100, C.byref(need), None) == _lib.PGR_ERR_INVALID_ARGUMENT
+        assert lib.pgr_forward(_forward_call(_lib, bad_scene, cam, out, num_instances=C.pointer(need)), None) == _lib.PGR_ERR_INVALID_ARGUMENT
     split = _lib.PgrScene(n=10, means3d=fake, opacities=fake, scales=fake, rotations=fake, shs=fake, shs_rest=fake, sh_degree=3,
                           sh_stride=16, scale_modifier=1.0)
     posed = _lib.PgrPosedObjects(object_id=fake, poses=fake, k_objects=2)
-    assert lib.pgr_forward_posed_async(C.byref(split), None, C.byref(posed), 1, C.byref(cam), C.byref(out), fake, 1 << 30, 100,
-                                       scratch, len(scratch), None) == _lib.PGR_ERR_INVALID_ARGUMENT
+    assert lib.pgr_forward(_forward_call(_lib, split, cam, out, fake, 1 << 30, posed=C.pointer(posed), **host),
+                           None) == _lib.PGR_ERR_INVALID_ARGUMENT
     grads = _lib.PgrGradOutputs()
-    assert lib.pgr_backward(C.byref(split), C.byref(cam), fake, None, fake, fake, fake, fake, 1 << 30, 100, C.byref(grads), fake,
-                            None) == _lib.PGR_ERR_INVALID_ARGUMENT
+    view = _lib.PgrBackwardView(grad_color=fake, final_T=fake, n_contrib=fake, radii=fake)
+    back = _lib.PgrBackwardCall(scene=C.pointer(split), n_views=1, cameras=C.pointer(cam), views=C.pointer(view), workspace=fake,
+                                workspace_bytes=1 << 30, max_instances_per_view=100, grads=C.pointer(grads), scratch=fake,
+                                scratch_bytes=lib.pgr_backward_batch_scratch_bytes(10, 1))
+    assert lib.pgr_backward(back, None) == _lib.PGR_ERR_INVALID_ARGUMENT
     # records: stride below the layout's size, unaligned stride, NULL destination
     lay = _lib.PgrRecordLayout()
     assert lib.pgr_frame_record_layout(16, 16, 8, C.byref(lay)) == 0
@@ -155,6 +167,66 @@ def test_new_entry_points_validate_before_any_launch():
     assert lib.pgr_scene_prepare(C.byref(sc), None, fake, 1 << 20, None, C.byref(p2), None) == _lib.PGR_ERR_INVALID_ARGUMENT
     empty = _lib.PgrScene(n=0)
     assert lib.pgr_scene_prepare(C.byref(empty), None, None, 0, C.byref(p1), C.byref(p2), None) == 0 and not p1.value and not p2.value
+
+
+def test_forward_call_rejects_mixed_modes_before_any_launch():
+    """What goes with a synchronous call only, with an asynchronous one only, or with neither: PGR_ERR_INVALID_ARGUMENT from
+    the host-side checks, with fake pointers and no device.  Every call here has a workspace that is merely too small -- the
+    last check before the first enqueue -- so a case let through would answer PGR_ERR_WORKSPACE_TOO_SMALL, as the unmixed
+    control calls at the end do: the rejection is the combination's."""
+    from pegasus_amd import _lib
+    lib = _lib.lib()
+    bad, fake = _lib.PGR_ERR_INVALID_ARGUMENT, C.c_void_p(0x1000)
+    assert lib.pgr_forward(None, None) == bad                                                  # no call
+    scene = _lib.PgrScene(n=10, means3d=fake, opacities=fake, scales=fake, rotations=fake, shs=fake, sh_degree=0, sh_stride=1,
+                          scale_modifier=1.0)
+    cam = _lib.PgrCamera(image_width=64, image_height=64, tanfovx=0.5, tanfovy=0.5, viewmatrix=fake, projmatrix=fake,
+                         campos=fake, bg=fake, depth_mode=0)
+    out, out_masks = _lib.PgrOutputs(color=fake, depth=fake, radii=fake), _lib.PgrOutputs(sem_masks=fake)
+    scratch = (C.c_char * int(lib.pgr_host_scratch_bytes(1)))()
+    host = dict(host_scratch=C.addressof(scratch), host_scratch_bytes=len(scratch))
+    posed = C.pointer(_lib.PgrPosedObjects(object_id=fake, poses=fake, k_objects=2))
+    layers = C.pointer(_lib.PgrLayers(layer_id=fake, n_layers=3, mask_colors=fake, mask_threshold=0.1))
+    need, ms = C.pointer(C.c_int64(0)), (C.c_float * _lib.PGR_NUM_STAGES)()
+
+    def rc(o=out, **fields):
+        return lib.pgr_forward(_forward_call(_lib, scene, cam, o, fake, 16, **fields), None)
+    # synchronous (no host scratch): no posed objects, no layers, no status event
+    assert rc(posed=posed) == bad
+    assert rc(o=out_masks, layers=layers) == bad
+    assert rc(status_event=fake) == bad
+    # asynchronous: no instance counts, no stage times, a host scratch of the full size
+    assert rc(num_instances=need, **host) == bad
+    assert rc(stage_ms=ms, **host) == bad
+    assert rc(host_scratch=C.addressof(scratch), host_scratch_bytes=len(scratch) - 1) == bad
+    # the early status words and a layered call do not go together
+    assert rc(o=out_masks, layers=layers, status_event=fake, **host) == bad
+    # controls: the same fields, unmixed, pass every argument check
+    small = _lib.PGR_ERR_WORKSPACE_TOO_SMALL
+    assert rc(num_instances=need) == small                      # (stage_ms creates its HIP events first: needs a device)
+    assert rc(posed=posed, status_event=fake, **host) == small
+    assert rc(o=out_masks, layers=layers, posed=posed, **host) == small
+
+
+def test_backward_call_rejects_null_and_short_camera_scratch():
+    from pegasus_amd import _lib
+    lib = _lib.lib()
+    bad, fake, n = _lib.PGR_ERR_INVALID_ARGUMENT, C.c_void_p(0x1000), 10
+    assert lib.pgr_backward(None, None) == bad
+    scene = _lib.PgrScene(n=n, means3d=fake, opacities=fake, scales=fake, rotations=fake, shs=fake, sh_degree=0, sh_stride=1,
+                          scale_modifier=1.0)
+    cam = _lib.PgrCamera(image_width=64, image_height=48, tanfovx=0.5, tanfovy=0.5)
+    view = _lib.PgrBackwardView(grad_color=fake, final_T=fake, n_contrib=fake, radii=fake)
+    call = _lib.PgrBackwardCall(scene=C.pointer(scene), n_views=1, cameras=C.pointer(cam), views=C.pointer(view), workspace=fake,
+                                workspace_bytes=16, max_instances_per_view=100, grads=C.pointer(_lib.PgrGradOutputs(means3d=fake)),
+                                scratch=fake, scratch_bytes=lib.pgr_backward_batch_scratch_bytes(n, 1))
+    assert lib.pgr_backward(call, None) == _lib.PGR_ERR_WORKSPACE_TOO_SMALL       # control: every argument check passed
+    call.camera_grads = C.pointer(_lib.PgrCameraGrad(viewmatrix=fake))
+    assert lib.pgr_backward(call, None) == bad                                     # camera gradients without their scratch
+    call.camera_scratch, call.camera_scratch_bytes = fake, lib.pgr_camera_grad_scratch_bytes(n, 1) - 1
+    assert lib.pgr_backward(call, None) == bad                                     # one byte short
+    call.camera_scratch_bytes += 1
+    assert lib.pgr_backward(call, None) == _lib.PGR_ERR_WORKSPACE_TOO_SMALL
 
 
 def test_stale_or_foreign_library_is_named_not_crashed_on(tmp_path):
@@ -197,6 +269,7 @@ int main(void) {
     PgrScene scene = {0};
     PgrCamera cam = {0};
     PgrOutputs out = {0};
+    PgrForwardCall call = {0};
     int64_t need = -1;
     scene.n = 10;                               /* no pointers: must be rejected on the host */
     cam.image_width = 64; cam.image_height = 64; cam.tanfovx = 0.5f; cam.tanfovy = 0.5f;
@@ -206,9 +279,11 @@ int main(void) {
     printf("ws %zu\n", pgr_batch_workspace_bytes(100000, 800, 800, 1 << 20, 8));
     printf("layout_rc %d\n", (int)pgr_frame_record_layout(800, 800, 8, &lay));
     printf("record %lld %lld %lld\n", (long long)lay.off_depth, (long long)lay.off_masks, (long long)lay.bytes);
-    printf("forward_rc %d\n", (int)pgr_forward(&scene, &cam, &out, NULL, 0, 100, &need, NULL));
-    printf("sizes %zu %zu %zu %zu %zu %zu\n", sizeof(PgrScene), sizeof(PgrCamera), sizeof(PgrOutputs), sizeof(PgrSemantic),
-           sizeof(PgrLayers), sizeof(PgrPosedObjects));
+    call.scene = &scene; call.n_views = 1; call.cameras = &cam; call.outs = &out;
+    call.max_instances_per_view = 100; call.num_instances = &need;
+    printf("forward_rc %d\n", (int)pgr_forward(&call, NULL));
+    printf("sizes %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(PgrScene), sizeof(PgrCamera), sizeof(PgrOutputs), sizeof(PgrSemantic),
+           sizeof(PgrLayers), sizeof(PgrPosedObjects), sizeof(PgrForwardCall), sizeof(PgrBackwardCall));
     return 0;
 }
 ''')
@@ -226,7 +301,7 @@ int main(void) {
     assert int(got["forward_rc"]) == _lib.PGR_ERR_INVALID_ARGUMENT
     sizes = [int(x) for x in got["sizes"].split()]
     assert sizes == [C.sizeof(t) for t in (_lib.PgrScene, _lib.PgrCamera, _lib.PgrOutputs, _lib.PgrSemantic, _lib.PgrLayers,
-                                           _lib.PgrPosedObjects)]
+                                           _lib.PgrPosedObjects, _lib.PgrForwardCall, _lib.PgrBackwardCall)]
 
 
 def test_loading_the_library_leaves_one_hip_runtime_in_the_process():

@@ -1,5 +1,5 @@
 """Differentiable alpha (1 - final_T) and training from object masks, on the GPU: the alpha output, its gradient through
-pgr_backward_ex / pgr_backward_batch_ex against the oracle, the bit-equality of the NULL paths, the masked image loss
+pgr_backward's grad_alpha (one view and batches) against the oracle, the bit-equality of the NULL paths, the masked image loss
 against float64 torch autograd, and a masked end-to-end training run.
 
 The alpha-gradient reference is the unchanged oracle: image = C + T bg and alpha = 1 - T, so the gradient of
@@ -167,28 +167,16 @@ def test_background_equals_alpha_weight(gpu_device, scene):
 
 
 # ---- 4. bit-equality of the NULL paths ------------------------------------------------------------------------------------
-def _grads_via(monkeypatch, X, v, deg, gC, gD, mode, dev):
-    """mode: 'old' (pgr_backward itself), 'null' (pgr_backward_ex, grad_alpha NULL), 'zero' (an all-zero grad_alpha)."""
+def _grads_via(X, v, deg, gC, gD, mode, dev):
+    """mode: 'null' (pgr_backward with grad_alpha NULL), 'zero' (an all-zero grad_alpha)."""
     import torch
-    from pegasus_amd import _lib
-    L = _lib.lib()
-    with monkeypatch.context() as mp:
-        if mode == "old":
-            real = L.pgr_backward
-
-            def old(scene, cam, gc, gd, ga, *rest):
-                assert ga is None
-                return real(scene, cam, gc, gd, *rest)
-            mp.setattr(L, "pgr_backward_ex", old, raising=False)
-        if mode == "zero":
-            got, _, _ = hip_alpha_backward(X, v, deg, 1.0, gC, gD, np.zeros((v.height, v.width), np.float32), dev)
-        else:
-            got, _, _ = hip_alpha_backward(X, v, deg, 1.0, gC, gD, None, dev)
+    ga = np.zeros((v.height, v.width), np.float32) if mode == "zero" else None
+    got, _, _ = hip_alpha_backward(X, v, deg, 1.0, gC, gD, ga, dev)
     return {k: torch.from_numpy(g) for k, g in got.items()}
 
 
 @pytest.mark.parametrize("scene", ["tiny", "cube", "opaque"])
-def test_null_and_zero_alpha_are_bit_identical_to_pgr_backward(monkeypatch, gpu_device, scene):
+def test_null_and_zero_alpha_are_bit_identical_to_pgr_backward(gpu_device, scene):
     import torch
     P, v = single_scene(scene)
     X, deg = mode_inputs(P, "sh3_16")
@@ -196,18 +184,15 @@ def test_null_and_zero_alpha_are_bit_identical_to_pgr_backward(monkeypatch, gpu_
     gC = rng.normal(size=(3, v.height, v.width)).astype(np.float32)
     gD = rng.normal(size=(v.height, v.width)).astype(np.float32)
     # one Gaussian per pixel block at most on 'tiny' / a sorted walk: the atomics' order is fixed only where one entry
-    # reaches a row per block; compare two runs of the SAME entry first to know what is deterministic
-    old = _grads_via(monkeypatch, X, v, deg, gC, gD, "old", gpu_device)
-    old2 = _grads_via(monkeypatch, X, v, deg, gC, gD, "old", gpu_device)
-    null = _grads_via(monkeypatch, X, v, deg, gC, gD, "null", gpu_device)
-    zero = _grads_via(monkeypatch, X, v, deg, gC, gD, "zero", gpu_device)
-    for k in old:
-        if not torch.equal(old[k], old2[k]):          # float atomics in a different order: not comparable bit for bit
-            torch.testing.assert_close(null[k], old[k], rtol=1e-5, atol=1e-6 * float(old[k].abs().max()))
-            torch.testing.assert_close(zero[k], old[k], rtol=1e-5, atol=1e-6 * float(old[k].abs().max()))
+    # reaches a row per block; compare two runs of the SAME call first to know what is deterministic
+    null = _grads_via(X, v, deg, gC, gD, "null", gpu_device)
+    null2 = _grads_via(X, v, deg, gC, gD, "null", gpu_device)
+    zero = _grads_via(X, v, deg, gC, gD, "zero", gpu_device)
+    for k in null:
+        if not torch.equal(null[k], null2[k]):        # float atomics in a different order: not comparable bit for bit
+            torch.testing.assert_close(zero[k], null[k], rtol=1e-5, atol=1e-6 * float(null[k].abs().max()))
             continue
-        assert torch.equal(null[k], old[k]), (scene, k)
-        assert torch.equal(zero[k], old[k]), (scene, k)
+        assert torch.equal(zero[k], null[k]), (scene, k)
 
 
 def test_masked_loss_with_unit_mask_is_pgr_image_loss(gpu_device):
@@ -238,7 +223,7 @@ def _batch_setup(V):
 
 @pytest.mark.parametrize("V", [1, 2, 4, 8, 17])
 def test_batch_ex_sums_single_view_ex(monkeypatch, gpu_device, V):
-    """pgr_backward_batch_ex against the sum of single-view pgr_backward_ex calls; every third view hands the batch a NULL
+    """A batch pgr_backward against the sum of single-view pgr_backward calls; every third view hands the batch a NULL
     grad_alpha (its alpha takes no part in the loss), the others an alpha weight."""
     import torch
     from pegasus_amd import _lib
@@ -267,14 +252,15 @@ def test_batch_ex_sums_single_view_ex(monkeypatch, gpu_device, V):
         sums = g if sums is None else {k: sums[k] + g[k] for k in g}
         m2ds.append(m2d.grad.clone())
     L = _lib.lib()
-    real = L.pgr_backward_batch_ex
+    real = L.pgr_backward
     seen = {}
 
-    def with_nulls(scene, n_views, cams, views_arr, ga, *rest):
-        arr = (C.c_void_p * n_views)(*[None if wa[v] is None else ga[v] for v in range(n_views)])
-        seen["nulls"] = sum(1 for v in range(n_views) if arr[v] is None)
-        return real(scene, n_views, cams, views_arr, arr, *rest)
-    monkeypatch.setattr(L, "pgr_backward_batch_ex", with_nulls, raising=False)
+    def with_nulls(call, stream):
+        arr = (C.c_void_p * call.n_views)(*[None if wa[v] is None else call.grad_alpha[v] for v in range(call.n_views)])
+        seen["nulls"] = sum(1 for v in range(call.n_views) if arr[v] is None)
+        call.grad_alpha = arr
+        return real(call, stream)
+    monkeypatch.setattr(L, "pgr_backward", with_nulls, raising=False)
     for t in x.values():
         t.grad = None
     m2d = torch.zeros((V,) + tuple(x["means3D"].shape), device=gpu_device, requires_grad=True)

@@ -110,10 +110,11 @@ def _load():
 def test_new_entries_are_declared_exported_and_prototyped():
     from test_abi_symbols import declared_symbols
     _lib, lib = _load()
-    for name in ("pgr_backward_ex", "pgr_backward_batch_ex", "pgr_image_loss_masked",
+    for name in ("pgr_backward", "pgr_image_loss_masked",
                  "pgr_image_loss_masked_workspace_bytes"):
         assert name in declared_symbols() and name in _lib.SYMBOLS and hasattr(lib, name)
-    assert lib.pgr_abi_version() == 3
+    assert lib.pgr_abi_version() == 4
+    assert "grad_alpha" in [f[0] for f in _lib.PgrBackwardCall._fields_]
     assert lib.pgr_image_loss_masked_workspace_bytes(37, 53) > lib.pgr_image_loss_workspace_bytes(37, 53) > 0
     assert lib.pgr_image_loss_masked_workspace_bytes(0, 5) == 0
 
@@ -149,25 +150,28 @@ def test_backward_ex_entries_reject_bad_arguments_before_any_launch():
                           sh_stride=1, scale_modifier=1.0)
     cam = _lib.PgrCamera(image_width=64, image_height=48, tanfovx=0.5, tanfovy=0.5)
     g = _lib.PgrGradOutputs(means3d=FAKE)
-    f = C.c_void_p(FAKE)
     bad = _lib.PGR_ERR_INVALID_ARGUMENT
-    assert lib.pgr_backward_ex(C.byref(scene), C.byref(cam), None, None, f, f, f, f, f, 1 << 40, 1000, C.byref(g), f,
-                               None) == bad                                   # no grad_color
-    assert lib.pgr_backward_ex(C.byref(scene), C.byref(cam), f, None, f, f, f, None, f, 1 << 40, 1000, C.byref(g), f,
-                               None) == bad                                   # no radii
-    assert lib.pgr_backward_ex(C.byref(scene), None, f, None, f, f, f, f, f, 1 << 40, 1000, C.byref(g), f, None) == bad
+
+    def rc(n_views, cams, views, ga, scratch_bytes):
+        call = _lib.PgrBackwardCall(scene=C.pointer(scene), n_views=n_views, cameras=cams, views=views, grad_alpha=ga,
+                                    workspace=FAKE, workspace_bytes=1 << 40, max_instances_per_view=1000, grads=C.pointer(g),
+                                    scratch=FAKE, scratch_bytes=scratch_bytes)
+        return lib.pgr_backward(call, None)
+    # one view with a grad_alpha
+    one = lambda **kw: C.pointer(_lib.PgrBackwardView(**{**dict(grad_color=FAKE, final_T=FAKE, n_contrib=FAKE, radii=FAKE), **kw}))
+    ga1, sb1 = (C.c_void_p * 1)(FAKE), lib.pgr_backward_batch_scratch_bytes(n, 1)
+    assert rc(1, C.pointer(cam), one(grad_color=None), ga1, sb1) == bad      # no grad_color
+    assert rc(1, C.pointer(cam), one(radii=None), ga1, sb1) == bad           # no radii
+    assert rc(1, None, one(), ga1, sb1) == bad                               # no camera
     cams = (_lib.PgrCamera * 2)(cam, _lib.PgrCamera(image_width=32, image_height=48))
     views = (_lib.PgrBackwardView * 2)(*[_lib.PgrBackwardView(grad_color=FAKE, final_T=FAKE, n_contrib=FAKE, radii=FAKE)
                                          for _ in range(2)])
     ga = (C.c_void_p * 2)(FAKE, None)
     sb = lib.pgr_backward_batch_scratch_bytes(n, 2)
-    assert lib.pgr_backward_batch_ex(C.byref(scene), 2, cams, views, ga, f, 1 << 40, 1000, C.byref(g), f, sb,
-                                     None) == bad                             # mixed image sizes
+    assert rc(2, cams, views, ga, sb) == bad                                 # mixed image sizes
     cams[1] = cam
-    assert lib.pgr_backward_batch_ex(C.byref(scene), 2, cams, views, ga, f, 1 << 40, 1000, C.byref(g), f, sb - 1,
-                                     None) == bad                             # scratch too small
-    assert lib.pgr_backward_batch_ex(C.byref(scene), 0, cams, views, None, f, 1 << 40, 1000, C.byref(g), f, sb,
-                                     None) == bad                             # no views
+    assert rc(2, cams, views, ga, sb - 1) == bad                             # scratch too small
+    assert rc(0, cams, views, None, sb) == bad                               # no views
 
 
 # ---- the alpha-gradient reference against finite differences --------------------------------------------------------------

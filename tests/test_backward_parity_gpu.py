@@ -1,4 +1,4 @@
-"""The HIP backward (pgr_backward through the drop-in GaussianRasterizer, pgr_backward_batch through
+"""The HIP backward (pgr_backward through the drop-in GaussianRasterizer, a batch pgr_backward through
 rasterize_gaussians_batch) against the oracle's backward, PER ELEMENT, for every gradient the ABI returns, in every
 input mode training and the drop-in surface use, at the edges of the model (opaque stacks that reach the 0.99 alpha clamp
 and the T < 1e-4 stop, Gaussians past the frustum clamp and at the near plane, one-pixel and ragged images), on the
@@ -231,7 +231,7 @@ def _batch_views(V, W, H):
 
 @pytest.mark.parametrize("V", [16, 17, 33])
 def test_batch_matches_sum_of_oracle_views(oracle, gpu_device, V):
-    """pgr_backward_batch beyond one per-view table chunk (16 views) and on the split-views preprocess (N <= 400 k,
+    """A batch pgr_backward beyond one per-view table chunk (16 views) and on the split-views preprocess (N <= 400 k,
     V >= 16): summed gradients against the sum of per-view oracle backwards, and every view's means2D."""
     import torch
     from pegasus_amd import diff_gaussian_rasterization as dgr, scenes

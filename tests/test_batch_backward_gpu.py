@@ -1,5 +1,5 @@
-"""Multi-view training on the GPU: pgr_backward_batch against single-view pgr_backward (one view, and sums over 2 / 4 / 8
-views), against the oracle, through render_batch's autograd, the per-view densification statistics of a batch step, and
+"""Multi-view training on the GPU: a batch pgr_backward against single-view pgr_backward calls (one view, and sums over
+2 / 4 / 8 views), against the oracle, through render_batch's autograd, the per-view densification statistics of a batch step, and
 an end-to-end training run with four views per step."""
 import math
 import random
@@ -142,6 +142,31 @@ def test_one_view_batch_matches_pgr_backward(gpu_device, case, mode, depth):
         _close(got[k], ref[k], 3e-6, k)
     _close(m2d[0], ref_m2d, 3e-6, "means2d")
     assert float(ref["means3D"].abs().max()) > 0
+
+
+@pytest.mark.parametrize("V", [1, 3])
+def test_backward_leaves_the_saved_workspace_alone(gpu_device, V):
+    """The forward's workspace is a tensor autograd saved for the backward: the backward only reads it (its per-view table
+    and gradient rows live in its own scratch).  V = 1 through the drop-in GaussianRasterizer, V = 3 through
+    rasterize_gaussians_batch; the workspace after loss.backward() equals its clone from before, byte for byte."""
+    import torch
+    from pegasus_amd import diff_gaussian_rasterization as dgr
+    P, (W, H) = _scene("tiny")
+    views = _views(V, W, H)
+    x, deg = _leaves(P, gpu_device, "sh3")
+    kw = {k: t for k, t in x.items() if k not in ("means3D", "opacities")}
+    sets = [_settings(v, gpu_device, (0.2, 0.4, 0.1), deg) for v in views]
+    if V == 1:
+        color, _, depth = dgr.GaussianRasterizer(sets[0])(x["means3D"], None, x["opacities"], **kw)
+    else:
+        color, _, depth = dgr.rasterize_gaussians_batch(x["means3D"], None, x["opacities"], sets, **kw)
+    (ws,) = [t for t in color.grad_fn.saved_tensors if t.dtype == torch.uint8]
+    assert ws.numel() > 0
+    before = ws.clone()
+    (color.square().sum() + depth.sum()).backward()
+    torch.cuda.synchronize()
+    assert float(x["means3D"].grad.abs().max()) > 0
+    assert torch.equal(ws, before)
 
 
 @pytest.mark.parametrize("V", [2, 4, 8])

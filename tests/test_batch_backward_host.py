@@ -17,7 +17,7 @@ def _load():
 def test_batch_backward_symbols_are_declared_exported_and_prototyped():
     from test_abi_symbols import declared_symbols
     _lib, lib = _load()
-    for name in ("pgr_backward_batch", "pgr_backward_batch_scratch_bytes"):
+    for name in ("pgr_backward", "pgr_backward_batch_scratch_bytes"):
         assert name in declared_symbols()
         assert name in _lib.SYMBOLS
         assert hasattr(lib, name)
@@ -51,9 +51,10 @@ def _call(lib, _lib, *, scene=None, n_views=2, cams=True, views=None, grads=True
     g = _lib.PgrGradOutputs(means3d=FAKE) if grads else None
     if scratch_bytes is None:
         scratch_bytes = lib.pgr_backward_batch_scratch_bytes(n, max(n_views, 1))
-    return lib.pgr_backward_batch(C.byref(scene), n_views, cam_arr, view_arr, C.c_void_p(FAKE), 1 << 40, 1000,
-                                  C.byref(g) if g is not None else None, C.c_void_p(scratch) if scratch else None,
-                                  scratch_bytes, None)
+    call = _lib.PgrBackwardCall(scene=C.pointer(scene), n_views=n_views, cameras=cam_arr, views=view_arr, workspace=FAKE,
+                                workspace_bytes=1 << 40, max_instances_per_view=1000,
+                                grads=C.pointer(g) if g is not None else None, scratch=scratch, scratch_bytes=scratch_bytes)
+    return lib.pgr_backward(call, None)
 
 
 def test_backward_batch_rejects_bad_arguments_before_any_launch():
@@ -75,8 +76,12 @@ def test_backward_batch_rejects_bad_arguments_before_any_launch():
     assert _call(lib, _lib, sizes=[(64, 48), (64, 32)]) == bad                   # mixed image sizes
     assert _call(lib, _lib, scratch=None) == bad
     assert _call(lib, _lib, scratch_bytes=lib.pgr_backward_batch_scratch_bytes(10, 2) - 1) == bad    # scratch too small
+    # one view is a batch of one: the same rules
+    assert _call(lib, _lib, n_views=1, scratch=None) == bad
+    assert _call(lib, _lib, n_views=1, scratch_bytes=lib.pgr_backward_batch_scratch_bytes(10, 1) - 1) == bad
+    assert _call(lib, _lib, n_views=1, view_kw=dict(radii=None)) == bad
     with pytest.raises(ValueError):
-        _lib.check(_call(lib, _lib, n_views=0), "pgr_backward_batch")
+        _lib.check(_call(lib, _lib, n_views=0), "pgr_backward")
 
 
 def test_cli_accepts_batch_size():

@@ -1,4 +1,4 @@
-"""Camera gradients of the HIP rasterizer (pgr_backward_camera / pgr_backward_batch_camera through the autograd surface)
+"""Camera gradients of the HIP rasterizer (pgr_backward with PgrBackwardCall.camera_grads, through the autograd surface)
 and pose refinement on them (pegasus_amd/camera_pose.py).
 
   - per element: dL/d(viewmatrix, projmatrix, campos) against central differences of the dense float64 forward
@@ -189,7 +189,7 @@ def test_batch_camera_gradient_matches_single_view(gpu_device, V):
 
 
 class _Spy:
-    """The library with its entry points counted."""
+    """The library with its backward calls recorded: (entry name, whether camera_grads was NULL)."""
 
     def __init__(self, lib):
         self._lib, self.calls = lib, []
@@ -199,9 +199,9 @@ class _Spy:
         if not name.startswith("pgr_backward") or name.endswith("_bytes"):
             return f
 
-        def wrapped(*a):
-            self.calls.append(name)
-            return f(*a)
+        def wrapped(call, stream):
+            self.calls.append((name, not call.camera_grads))
+            return f(call, stream)
         return wrapped
 
 
@@ -233,11 +233,10 @@ def test_camera_gradients_move_nothing_else(gpu_device, monkeypatch, batch):
         return {k: x.grad.cpu().numpy() for k, x in X.items()}
 
     plain = run(False)
-    expect = "pgr_backward_batch_ex" if batch else "pgr_backward_ex"
-    assert spy.calls == [expect], spy.calls
+    assert spy.calls == [("pgr_backward", True)], spy.calls
     spy.calls.clear()
     with_cam = run(True)
-    assert spy.calls == ["pgr_backward_batch_camera" if batch else "pgr_backward_camera"], spy.calls
+    assert spy.calls == [("pgr_backward", False)], spy.calls
     assert_grads_match(with_cam, plain, "camera grads requested", bounds=dict(rotations=4.0))
 
 

@@ -157,7 +157,7 @@ def test_posed_objects_equal_composed_scene(oracle):
 
 @pytest.mark.gpu
 def test_posed_batch_matches_oracle(oracle, gpu_device):
-    """A batch of TIME STEPS (one camera each, its own object poses) through pgr_forward_posed_async == the oracle's
+    """A batch of TIME STEPS (one camera each, its own object poses) through PgrForwardCall.posed == the oracle's
     posed preprocess per step: radii and n_contrib bit-exact, images within 1e-4."""
     import torch
     from pegasus_amd import rasterizer as R

@@ -138,7 +138,7 @@ def test_batch_in_which_only_some_views_overflow(gpu_device):
 
 @pytest.mark.gpu
 def test_early_status_reports_every_view_of_a_batch(gpu_device):
-    """pgr_forward_posed_early_status with FOUR views: the tile scan of every view stores that view's instance count and
+    """PgrForwardCall.status_event with FOUR views: the tile scan of every view stores that view's instance count and
     overflow flag into the pinned host scratch, the event behind the scan releases the host, and the status it reads is the
     batch's -- the counts of every view, and PGR_ERR_INSTANCE_OVERFLOW (re-render at the grown capacity) when only some views
     do not fit.  Images equal the synchronous call's."""

@@ -469,7 +469,7 @@ def test_render_after_an_instance_overflow_redoes_the_queued_visibility_filter(g
 
 @pytest.mark.gpu
 def test_render_returns_behind_the_tile_scan_with_stream_ordered_outputs(gpu_device):
-    """render() waits for the call's STATUS WORDS only (pgr_forward_posed_early_status: final behind the tile scan) and returns
+    """render() waits for the call's STATUS WORDS only (PgrForwardCall.status_event: final behind the tile scan) and returns
     while scatter, sort and compositor still run.  What the caller does next is ordered behind them by the stream: a clone
     queued straight after the return, a second render() into the SAME workspace, and an in-place edit of the model between two
     calls must all see complete images -- equal to the synchronous batch call's."""

@@ -337,7 +337,7 @@ def test_c5_posed_sequence_step_matches_oracle(oracle, gpu_device):
 
 def test_full_size_backward_matches_oracle_per_element(c3_full, oracle, gpu_device):
     """The backward at full size (2 M Gaussians, 800x800, SH degree 3: long lists from every sort tier, the forward's
-    48-byte records and tie order re-read) on one spread and one grazing view: pgr_backward per view, and pgr_backward_batch
+    48-byte records and tie order re-read) on one spread and one grazing view: pgr_backward per view, and a batch pgr_backward
     on the two views together, against the oracle per element (tests/test_backward_parity_gpu.py's rules)."""
     import torch
     from helpers import assert_grads_match

@@ -176,7 +176,7 @@ def test_masks_and_quantisation(oracle, gpu_device):
 
 
 def test_batch_matches_single_view_and_oracle(oracle, gpu_device):
-    """pgr_forward_batch: every view of a batch equals the single-view result bit for bit, and the oracle."""
+    """pgr_forward with several views: every view of a batch equals the single-view result bit for bit, and the oracle."""
     import torch
     from helpers import assert_images_match, fetch_workspace, gpu_forward
     from pegasus_amd import rasterizer
@@ -878,7 +878,7 @@ def test_scene_prepare_constants_match_the_per_call_path(gpu_device):
 
 @pytest.mark.parametrize("n_views,env_switch", [(1, None), (2, None), (5, None), (5, "PGR_BIN_RECORDS"), (5, "PGR_BLOCK_CULL")])
 def test_layered_call_many_small_layers_and_unlayered_gaussians(gpu_device, monkeypatch, n_views, env_switch):
-    """pgr_forward_layers_async through the C ABI on a scene the FrameRenderer never builds: Gaussians that belong to NO
+    """PgrForwardCall.layers through the C ABI on a scene the FrameRenderer never builds: Gaussians that belong to NO
     layer in front (layer id 0: dropped), then 37 small layers, so that binning chunks and 64-Gaussian groups straddle
     several layers; one- and two-view calls (their own launch shapes) and the A/B switches.  Reference: every layer rendered
     alone through the plain batch call + pgr_color_masks."""
