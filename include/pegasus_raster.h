@@ -655,6 +655,76 @@ int32_t pgr_mask_rle_decode(const int32_t *counts, const int64_t *offsets, int32
 int32_t pgr_mask_overlap(const uint8_t *a, int32_t n_a, const uint8_t *b, int32_t n_b, int32_t width, int32_t height,
                          int32_t *inter, int32_t *area_a, int32_t *area_b, void *stream);
 
+/* ---- COCO detection / segmentation scores (pegasus_amd/coco_eval.py; csrc/cocoeval.hip.h) --------------------------------
+ * pycocotools.COCOeval as the BOP toolkit's scripts/eval_bop22_coco.py runs it, in four device stages that work from run
+ * lists and boxes, never from pixels.  pycocotools is not a requirement of this project: parity with it is pinned by the
+ * written rule at the top of csrc/cocoeval.hip.h and by hand-worked known answers, not by recorded
+ * outputs.  Every result is an integer or a float64 produced by a fixed sequence of IEEE operations; no atomics: two runs
+ * give equal bytes.
+ *
+ * A GROUP is one (image, category): dt_count detections from dt_begin (sorted by -score, stable, cut to maxDets[-1] by the
+ * caller) and gt_count ground-truth annotations from gt_begin (file order); its IoU matrix is
+ * iou[iou_offset + d * gt_count + g], float64.  The table is HOST memory, read during the call (it is copied into the
+ * workspace in stream order, and the call returns when the copy has been made: the one wait of these entries).  Refused on the host with PGR_ERR_INVALID_ARGUMENT: a negative count, a slice outside [0, n_dt) / [0, n_gt) /
+ * [0, iou_total), and groups that are not ascending and disjoint in all three (dt_begin, gt_begin and iou_offset of a group
+ * are at or behind the previous group's ends): no two groups write one element.  Either count may be 0.
+ * Every entry checks its arguments on the host before anything is enqueued; every *_workspace_bytes is host-only and
+ * returns 0 for invalid arguments; workspaces are device memory, 16-byte aligned. */
+typedef struct PgrCocoGroup {
+    int32_t dt_begin, dt_count, gt_begin, gt_count;
+    int64_t iou_offset;
+} PgrCocoGroup;
+#define PGR_COCO_CHUNK 256           /* elements a workgroup scans at a time (runs of a mask, detections of a category) */
+#define PGR_COCO_LDS_RUNS 4096       /* GT runs of one group staged in LDS, at most: beyond, they are read from the workspace */
+#define PGR_COCO_MAX_LANES 64        /* n_area * n_thr of one call, at most (one lane each) */
+#define PGR_COCO_MAX_MAXDETS 8       /* n_max_dets, at most */
+/* Mask IoU inside groups from run lists in the layout pgr_mask_rle_emit produces: counts int32 [*_total] and offsets int64
+ * [n+1], both device (mask k: counts[offsets[k] .. offsets[k+1])); *_total is the length of the counts array, and no read
+ * leaves it whatever the offsets hold.  Negative counts read as 0 and sums beyond H*W are cut, as pgr_mask_rle_decode does;
+ * zero-length runs are legal anywhere.  gt_crowd uint8 [n_gt].  Writes dt_area int64 [n_dt], gt_area int64 [n_gt] (set
+ * pixels, of every mask, grouped or not), and per group inter int64 = pixels set in both and
+ *   iou = inter == 0 ? 0 : inter / (crowd ? area_d : area_d + area_g - inter)      (one float64 division). */
+size_t pgr_rle_iou_workspace_bytes(int32_t n_groups, int64_t dt_total, int64_t gt_total);
+int32_t pgr_rle_iou(const int32_t *dt_counts, const int64_t *dt_offsets, int32_t n_dt, int64_t dt_total,
+                    const int32_t *gt_counts, const int64_t *gt_offsets, int32_t n_gt, int64_t gt_total,
+                    const uint8_t *gt_crowd, int32_t width, int32_t height, const PgrCocoGroup *groups, int32_t n_groups,
+                    int64_t iou_total, int64_t *inter, double *iou, int64_t *dt_area, int64_t *gt_area, void *workspace,
+                    size_t workspace_bytes, void *stream);
+/* Box IoU inside groups: boxes float64 [n,4] = x, y, w, h (device).  iw = min(dx+dw, gx+gw) - max(dx, gx), ih likewise,
+ * inter = iw*ih if both > 0 else 0, union = dw*dh + gw*gh - inter (dw*dh for a crowd), iou = inter == 0 ? 0 : inter / union:
+ * each an IEEE operation of its own, in this order (nothing is contracted into an FMA).  0 where pycocotools divides 0/0. */
+size_t pgr_box_iou_workspace_bytes(int32_t n_groups);
+int32_t pgr_box_iou(const double *dt_boxes, int32_t n_dt, const double *gt_boxes, int32_t n_gt, const uint8_t *gt_crowd,
+                    const PgrCocoGroup *groups, int32_t n_groups, int64_t iou_total, double *iou, void *workspace,
+                    size_t workspace_bytes, void *stream);
+/* COCOeval.evaluateImg for every group, area range and threshold at once.  iou_thrs [n_thr] and area_rng [n_area,2] = lo, hi
+ * are HOST arrays; n_thr * n_area <= PGR_COCO_MAX_LANES.  dt_area, gt_area float64, gt_flag uint8 (the ignore flag: iscrowd,
+ * or iscrowd | ignore), gt_crowd uint8: device.  A GT is ignored for range a when gt_flag or area < lo or area > hi.  Writes,
+ * for the slices of the groups only (rows of detections and GT in no group keep their bytes):
+ *   dt_match int32 [n_area,n_thr,n_dt]   index (into the GT arrays) of the GT the detection is matched to, -1 for none
+ *   dt_ignore uint8 [n_area,n_thr,n_dt]  the matched GT's ignore flag; unmatched: area outside [lo, hi]
+ *   gt_match int32 [n_area,n_thr,n_gt]   index of the detection matched to the GT (the last one for a crowd), -1 for none
+ *   gt_ignore uint8 [n_area,n_gt]
+ * Detections are visited in the order of the table, so the first m of a group are matched as if the rest were absent. */
+size_t pgr_coco_match_workspace_bytes(int32_t n_groups, int32_t n_gt, int32_t n_area);
+int32_t pgr_coco_match(const PgrCocoGroup *groups, int32_t n_groups, int64_t iou_total, const double *iou,
+                       const double *dt_area, int32_t n_dt, const double *gt_area, const uint8_t *gt_flag,
+                       const uint8_t *gt_crowd, int32_t n_gt, const double *iou_thrs, int32_t n_thr, const double *area_rng,
+                       int32_t n_area, int32_t *dt_match, uint8_t *dt_ignore, int32_t *gt_match, uint8_t *gt_ignore,
+                       void *workspace, size_t workspace_bytes, void *stream);
+/* COCOeval.accumulate.  perm int64 [n_dt]: the detections stably sorted by (category, -score) over images in ascending id;
+ * seg_start int64 [n_cat+1]: category k is perm[seg_start[k] .. seg_start[k+1]); rank int32 [n_dt]: the detection's place in
+ * its group; npig int32 [n_cat,n_area]: GT of the category not ignored for the range; rec_thrs float64 [n_rec]; dt_scores
+ * float64 [n_dt]: all device (entries of perm outside [0, n_dt) are skipped and seg_start is cut to [0, n_dt]).  max_dets
+ * int32 [n_max_dets] is a HOST array.  Writes every cell once: precision and scores float64 [n_thr,n_rec,n_cat,n_area,
+ * n_max_dets], recall float64 [n_thr,n_cat,n_area,n_max_dets]; -1 where npig == 0. */
+size_t pgr_coco_accumulate_workspace_bytes(int32_t n_dt, int32_t n_area, int32_t n_max_dets);
+int32_t pgr_coco_accumulate(const int64_t *perm, const int64_t *seg_start, int32_t n_cat, const int32_t *rank,
+                            const int32_t *dt_match, const uint8_t *dt_ignore, const double *dt_scores, int32_t n_dt,
+                            const int32_t *npig, const int32_t *max_dets, int32_t n_max_dets, const double *rec_thrs,
+                            int32_t n_rec, int32_t n_thr, int32_t n_area, double *precision, double *scores, double *recall,
+                            void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- training step (pegasus_amd/train_ops.py) ----------------------------------------------------------------------------
  * Fused 3DGS image loss over x, y [3,H,W] fp32 (x: the render, y: the ground truth):
  *   loss = (1 - lambda) mean|x - y| + lambda (1 - mean SSIM(x, y))

@@ -164,6 +164,13 @@ PGR_POSE_SYM_CHUNK = 4       # include/pegasus_raster.h PGR_POSE_SYM_CHUNK
 PGR_RLE_WORD_ROWS, PGR_RLE_TILE_COLS, PGR_RLE_BLOCK_ROWS = 32, 256, 128
 PGR_RLE_DECODE_CHUNK, PGR_RLE_DECODE_MIN_SLICE, PGR_RLE_DECODE_MAX_SLICES, PGR_MASK_OVERLAP_CHUNK = 256, 16384, 64, 16384
 PGR_MASK_STATS = 6           # n_counts, area, x_min, y_min, x_max, y_max
+# include/pegasus_raster.h: the shapes at which the COCO score kernels change path, and their limits
+PGR_COCO_CHUNK, PGR_COCO_LDS_RUNS, PGR_COCO_MAX_LANES, PGR_COCO_MAX_MAXDETS = 256, 4096, 64, 8
+
+
+class PgrCocoGroup(C.Structure):
+    _fields_ = [("dt_begin", C.c_int32), ("dt_count", C.c_int32), ("gt_begin", C.c_int32), ("gt_count", C.c_int32),
+                ("iou_offset", C.c_int64)]
 
 
 # every symbol include/pegasus_raster.h declares: name -> (restype, argtypes)
@@ -244,6 +251,23 @@ SYMBOLS = {
     "pgr_mask_rle_decode": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "pgr_mask_overlap": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pgr_rle_iou_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64]),
+    "pgr_rle_iou": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64,
+                                C.c_void_p, C.c_int32, C.c_int32, C.POINTER(PgrCocoGroup), C.c_int32, C.c_int64, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pgr_box_iou_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "pgr_box_iou": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(PgrCocoGroup), C.c_int32,
+                                C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pgr_coco_match_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "pgr_coco_match": (C.c_int32, [C.POINTER(PgrCocoGroup), C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.c_int32,
+                                   C.POINTER(C.c_double), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pgr_coco_accumulate_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "pgr_coco_accumulate": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_int32,
+                                        C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                        C.c_void_p]),
 }
 
 _lib = None

@@ -11,8 +11,8 @@ The kernels and their rule are pinned in pegasus_amd/csrc/cocorle.hip.h: run len
 with a run of zeros (``pycoco_utils.binary_mask_to_rle``), boxes ``[x, y, x_max - x + 1, y_max - y + 1]``
 (``pycoco_utils.bbox_from_binary_mask`` -- NOT the ``w = x_max - x_min`` of ``misc.calc_2d_bbox`` that scene_gt_info uses).
 
-Out of scope: polygon segmentations, compressed RLE strings (both need packages that are not requirements of this
-project: skimage, pycocotools), COCO mAP and merge_coco_annotations.
+Out of scope here: polygon segmentations (skimage) and compressed RLE strings (``rle_decode`` refuses them).  Scoring
+results against these files -- COCO AP / AR, merge_coco_annotations, compressed strings -- is pegasus_amd.coco_eval.
 """
 from __future__ import annotations
 

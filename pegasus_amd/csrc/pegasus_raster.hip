@@ -18,6 +18,7 @@
 
 #include "backward.hip.h"
 #include "blockcull.hip.h"
+#include "cocoeval.hip.h"
 #include "cocorle.hip.h"
 #include "knn.hip.h"
 #include "mesh.hip.h"
@@ -1494,6 +1495,177 @@ int32_t pgr_mask_overlap(const uint8_t* a, int32_t n_a, const uint8_t* b, int32_
     mask_overlap_kernel<<<(unsigned)(pairs * chunks), RLE_THREADS, 0, stream>>>(a, n_a, b, n_b, HW, (int)chunks, inter, area_a,
                                                                                area_b);
     return hip_ok(hipGetLastError(), "mask_overlap launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+// ---- COCO scores: IoU inside groups, matching, accumulation (cocoeval.hip.h) ----------------------------------------------
+namespace {
+// a group table a kernel may index with: slices inside the arrays, ascending and disjoint (no two groups write one element)
+bool coco_groups_ok(const PgrCocoGroup* groups, int32_t n_groups, int32_t n_dt, int32_t n_gt, int64_t iou_total) {
+    if (n_groups < 0 || n_dt < 0 || n_gt < 0 || iou_total < 0 || (n_groups > 0 && !groups)) return false;
+    int64_t dt_end = 0, gt_end = 0, iou_end = 0;
+    for (int32_t k = 0; k < n_groups; ++k) {
+        const PgrCocoGroup& G = groups[k];
+        if (G.dt_count < 0 || G.gt_count < 0 || G.dt_begin < dt_end || G.gt_begin < gt_end || G.iou_offset < iou_end) return false;
+        dt_end = (int64_t)G.dt_begin + G.dt_count;
+        gt_end = (int64_t)G.gt_begin + G.gt_count;
+        iou_end = G.iou_offset + (int64_t)G.dt_count * G.gt_count;
+        if (dt_end > n_dt || gt_end > n_gt || iou_end > iou_total) return false;
+    }
+    return true;
+}
+struct CocoIouLayout { size_t groups, dt_ends, dt_cover, gt_ends, gt_cover, total; };
+bool coco_iou_layout(int32_t n_groups, int64_t dt_total, int64_t gt_total, CocoIouLayout* out) {
+    if (n_groups < 0 || dt_total < 0 || gt_total < 0 || dt_total > ((int64_t)1 << 40) || gt_total > ((int64_t)1 << 40)) return false;
+    Carver c;
+    out->groups = c.take((size_t)n_groups * sizeof(PgrCocoGroup));
+    out->dt_ends = c.take((size_t)dt_total * sizeof(int32_t));
+    out->dt_cover = c.take((size_t)dt_total * sizeof(int32_t));      // (read for the detections' areas only)
+    out->gt_ends = c.take((size_t)gt_total * sizeof(int32_t));
+    out->gt_cover = c.take((size_t)gt_total * sizeof(int32_t));
+    out->total = c.off;
+    return true;
+}
+// the table goes to the device in stream order and has been read when this returns: the caller may free it after the call
+bool coco_groups_upload(void* dst, const PgrCocoGroup* groups, int32_t n_groups, hipStream_t stream) {
+    return n_groups == 0 || hip_ok(hipMemcpyWithStream(dst, groups, (size_t)n_groups * sizeof(PgrCocoGroup), hipMemcpyHostToDevice, stream),
+                                   "memcpy coco groups");
+}
+}  // namespace
+
+size_t pgr_rle_iou_workspace_bytes(int32_t n_groups, int64_t dt_total, int64_t gt_total) {
+    CocoIouLayout L;
+    return coco_iou_layout(n_groups, dt_total, gt_total, &L) ? L.total : 0;
+}
+
+int32_t pgr_rle_iou(const int32_t* dt_counts, const int64_t* dt_offsets, int32_t n_dt, int64_t dt_total,
+                    const int32_t* gt_counts, const int64_t* gt_offsets, int32_t n_gt, int64_t gt_total, const uint8_t* gt_crowd,
+                    int32_t width, int32_t height, const PgrCocoGroup* groups, int32_t n_groups, int64_t iou_total,
+                    int64_t* inter, double* iou, int64_t* dt_area, int64_t* gt_area, void* workspace, size_t workspace_bytes,
+                    void* stream_v) {
+    CocoIouLayout L;
+    if (width < 1 || width > RLE_MAX_SIDE || height < 1 || height > RLE_MAX_SIDE || !coco_groups_ok(groups, n_groups, n_dt, n_gt, iou_total) ||
+        !coco_iou_layout(n_groups, dt_total, gt_total, &L) || !workspace || !rle_workspace_aligned(workspace))
+        return PGR_ERR_INVALID_ARGUMENT;
+    if ((n_dt > 0 && (!dt_offsets || !dt_area || (dt_total > 0 && !dt_counts))) ||
+        (n_gt > 0 && (!gt_offsets || !gt_area || !gt_crowd || (gt_total > 0 && !gt_counts))) || (iou_total > 0 && (!inter || !iou)))
+        return PGR_ERR_INVALID_ARGUMENT;
+    if (workspace_bytes < L.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    char* ws = static_cast<char*>(workspace);
+    auto* groups_dev = reinterpret_cast<PgrCocoGroup*>(ws + L.groups);
+    auto* dt_ends = reinterpret_cast<int32_t*>(ws + L.dt_ends);
+    auto* gt_ends = reinterpret_cast<int32_t*>(ws + L.gt_ends);
+    auto* gt_cover = reinterpret_cast<int32_t*>(ws + L.gt_cover);
+    auto* dt_cover = reinterpret_cast<int32_t*>(ws + L.dt_cover);
+    if (!coco_groups_upload(groups_dev, groups, n_groups, stream)) return PGR_ERR_LAUNCH_FAILURE;
+    const int HW = width * height;
+    if (n_dt > 0)
+        coco_rle_prefix_kernel<<<(unsigned)n_dt, COCO_THREADS, 0, stream>>>(dt_counts, reinterpret_cast<const long long*>(dt_offsets),
+                                                                           (long long)dt_total, HW, dt_ends, dt_cover,
+                                                                           reinterpret_cast<long long*>(dt_area));
+    if (n_gt > 0)
+        coco_rle_prefix_kernel<<<(unsigned)n_gt, COCO_THREADS, 0, stream>>>(gt_counts, reinterpret_cast<const long long*>(gt_offsets),
+                                                                           (long long)gt_total, HW, gt_ends, gt_cover,
+                                                                           reinterpret_cast<long long*>(gt_area));
+    if (n_groups > 0 && iou_total > 0)
+        coco_rle_iou_kernel<<<(unsigned)n_groups, COCO_THREADS, 0, stream>>>(
+            groups_dev, reinterpret_cast<const long long*>(dt_offsets), (long long)dt_total,
+            reinterpret_cast<const long long*>(gt_offsets), (long long)gt_total, gt_crowd, dt_ends, gt_ends, gt_cover,
+            reinterpret_cast<const long long*>(dt_area), reinterpret_cast<const long long*>(gt_area),
+            reinterpret_cast<long long*>(inter), iou);
+    return hip_ok(hipGetLastError(), "rle_iou launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+size_t pgr_box_iou_workspace_bytes(int32_t n_groups) {
+    return n_groups < 0 ? 0 : align_up((size_t)std::max(n_groups, 1) * sizeof(PgrCocoGroup));
+}
+
+int32_t pgr_box_iou(const double* dt_boxes, int32_t n_dt, const double* gt_boxes, int32_t n_gt, const uint8_t* gt_crowd,
+                    const PgrCocoGroup* groups, int32_t n_groups, int64_t iou_total, double* iou, void* workspace,
+                    size_t workspace_bytes, void* stream_v) {
+    if (!coco_groups_ok(groups, n_groups, n_dt, n_gt, iou_total) || !workspace || !rle_workspace_aligned(workspace) ||
+        (n_dt > 0 && !dt_boxes) || (n_gt > 0 && (!gt_boxes || !gt_crowd)) || (iou_total > 0 && !iou))
+        return PGR_ERR_INVALID_ARGUMENT;
+    if (workspace_bytes < pgr_box_iou_workspace_bytes(n_groups)) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    if (n_groups == 0 || iou_total == 0) return PGR_OK;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    auto* groups_dev = static_cast<PgrCocoGroup*>(workspace);
+    if (!coco_groups_upload(groups_dev, groups, n_groups, stream)) return PGR_ERR_LAUNCH_FAILURE;
+    coco_box_iou_kernel<<<(unsigned)n_groups, COCO_THREADS, 0, stream>>>(groups_dev, dt_boxes, gt_boxes, gt_crowd, iou);
+    return hip_ok(hipGetLastError(), "box_iou launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+size_t pgr_coco_match_workspace_bytes(int32_t n_groups, int32_t n_gt, int32_t n_area) {
+    if (n_groups < 0 || n_gt < 0 || n_area < 1 || n_area > COCO_MAX_LANES) return 0;
+    return align_up((size_t)std::max(n_groups, 1) * sizeof(PgrCocoGroup)) + align_up(std::max<size_t>((size_t)n_area * n_gt, 1) * sizeof(int32_t));
+}
+
+int32_t pgr_coco_match(const PgrCocoGroup* groups, int32_t n_groups, int64_t iou_total, const double* iou, const double* dt_area,
+                       int32_t n_dt, const double* gt_area, const uint8_t* gt_flag, const uint8_t* gt_crowd, int32_t n_gt,
+                       const double* iou_thrs, int32_t n_thr, const double* area_rng, int32_t n_area, int32_t* dt_match,
+                       uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore, void* workspace, size_t workspace_bytes,
+                       void* stream_v) {
+    if (n_thr < 1 || n_area < 1 || (int64_t)n_thr * n_area > COCO_MAX_LANES || !iou_thrs || !area_rng ||
+        !coco_groups_ok(groups, n_groups, n_dt, n_gt, iou_total) || !workspace || !rle_workspace_aligned(workspace) ||
+        (n_dt > 0 && (!dt_area || !dt_match || !dt_ignore)) ||
+        (n_gt > 0 && (!gt_area || !gt_flag || !gt_crowd || !gt_match || !gt_ignore)) || (iou_total > 0 && !iou))
+        return PGR_ERR_INVALID_ARGUMENT;
+    CocoMatchParams P{};
+    P.n_thr = n_thr;
+    P.n_area = n_area;
+    for (int32_t a = 0; a < n_area; ++a)
+        for (int32_t t = 0; t < n_thr; ++t) {
+            if (!(iou_thrs[t] == iou_thrs[t]) || !(area_rng[2 * a] <= area_rng[2 * a + 1])) return PGR_ERR_INVALID_ARGUMENT;
+            P.thr[a * n_thr + t] = std::min(iou_thrs[t], 1.0 - 1e-10);
+            P.lo[a * n_thr + t] = area_rng[2 * a];
+            P.hi[a * n_thr + t] = area_rng[2 * a + 1];
+        }
+    if (workspace_bytes < pgr_coco_match_workspace_bytes(n_groups, n_gt, n_area)) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    if (n_groups == 0) return PGR_OK;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    char* ws = static_cast<char*>(workspace);
+    auto* groups_dev = reinterpret_cast<PgrCocoGroup*>(ws);
+    auto* order = reinterpret_cast<int32_t*>(ws + align_up((size_t)n_groups * sizeof(PgrCocoGroup)));
+    if (!coco_groups_upload(groups_dev, groups, n_groups, stream)) return PGR_ERR_LAUNCH_FAILURE;
+    coco_match_kernel<<<(unsigned)n_groups, WAVE, 0, stream>>>(groups_dev, P, iou, dt_area, gt_area, gt_flag, gt_crowd, (long long)n_dt,
+                                                              (long long)n_gt, order, dt_match, dt_ignore, gt_match, gt_ignore);
+    return hip_ok(hipGetLastError(), "coco_match launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+size_t pgr_coco_accumulate_workspace_bytes(int32_t n_dt, int32_t n_area, int32_t n_max_dets) {
+    if (n_dt < 0 || n_area < 1 || n_area > COCO_MAX_LANES || n_max_dets < 1 || n_max_dets > PGR_COCO_MAX_MAXDETS) return 0;
+    const size_t cells = std::max<size_t>((size_t)n_area * n_max_dets * n_dt, 1);
+    return 2 * align_up(cells * sizeof(int32_t)) + align_up(cells * sizeof(double));
+}
+
+int32_t pgr_coco_accumulate(const int64_t* perm, const int64_t* seg_start, int32_t n_cat, const int32_t* rank,
+                            const int32_t* dt_match, const uint8_t* dt_ignore, const double* dt_scores, int32_t n_dt,
+                            const int32_t* npig, const int32_t* max_dets, int32_t n_max_dets, const double* rec_thrs,
+                            int32_t n_rec, int32_t n_thr, int32_t n_area, double* precision, double* scores, double* recall,
+                            void* workspace, size_t workspace_bytes, void* stream_v) {
+    const size_t need = pgr_coco_accumulate_workspace_bytes(n_dt, n_area, n_max_dets);
+    if (need == 0 || n_cat < 0 || n_rec < 1 || n_thr < 1 || (int64_t)n_thr * n_area > COCO_MAX_LANES || !max_dets || !rec_thrs ||
+        !workspace || !rle_workspace_aligned(workspace) || (n_dt > 0 && (!perm || !rank || !dt_match || !dt_ignore || !dt_scores)))
+        return PGR_ERR_INVALID_ARGUMENT;
+    if (n_cat > 0 && (!seg_start || !npig || !precision || !scores || !recall)) return PGR_ERR_INVALID_ARGUMENT;
+    if ((int64_t)n_cat * n_area * n_max_dets > RLE_MAX_BLOCKS) return PGR_ERR_INVALID_ARGUMENT;
+    CocoAccumulateParams P{};
+    for (int32_t m = 0; m < n_max_dets; ++m) {
+        if (max_dets[m] < 0) return PGR_ERR_INVALID_ARGUMENT;
+        P.max_dets[m] = max_dets[m];
+    }
+    P.K = n_cat; P.A = n_area; P.M = n_max_dets; P.T = n_thr; P.R = n_rec;
+    if (workspace_bytes < need) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    if (n_cat == 0) return PGR_OK;
+    char* ws = static_cast<char*>(workspace);
+    const size_t cells = std::max<size_t>((size_t)n_area * n_max_dets * n_dt, 1);
+    auto* ws_tp = reinterpret_cast<int32_t*>(ws);
+    auto* ws_idx = reinterpret_cast<int32_t*>(ws + align_up(cells * sizeof(int32_t)));
+    auto* ws_pr = reinterpret_cast<double*>(ws + 2 * align_up(cells * sizeof(int32_t)));
+    coco_accumulate_kernel<<<(unsigned)(n_cat * n_area * n_max_dets), COCO_THREADS, 0, static_cast<hipStream_t>(stream_v)>>>(
+        P, reinterpret_cast<const long long*>(perm), reinterpret_cast<const long long*>(seg_start), (long long)n_dt, rank, dt_match,
+        dt_ignore, npig, rec_thrs, dt_scores, ws_tp, ws_idx, ws_pr, precision, scores, recall);
+    return hip_ok(hipGetLastError(), "coco_accumulate launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
 }
 
 // ---- training step: fused L1 + D-SSIM loss, Adam over all parameter groups, densification statistics (train.hip.h) ------
