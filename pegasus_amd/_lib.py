@@ -341,6 +341,17 @@ def call(name: str, device, *args):
     check(enqueue(name, device, *args), name)
 
 
+def workspace(entry: str, device, *size_args):
+    """THE way the package sizes and allocates the workspace of ``entry``: a fresh uint8 tensor on ``device`` of exactly
+    ``<entry>_workspace_bytes(*size_args)`` bytes.  A size of 0 is that function refusing its arguments and raises.  (Callers
+    with a policy of their own -- a cached buffer, slack bytes, a memory estimate -- ask the size function themselves.)"""
+    import torch
+    nbytes = int(getattr(lib(), f"{entry}_workspace_bytes")(*size_args))
+    if nbytes == 0:
+        raise ValueError(f"{entry}_workspace_bytes rejected its arguments: {size_args!r}")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
 def check(status: int, what: str = "pegasus_raster"):
     if status == PGR_OK:
         return

@@ -55,12 +55,9 @@ def _device_masks(masks, what="masks"):
 def _count_pass(masks):
     import torch
     n, H, W = masks.shape
-    nbytes = int(_lib.lib().pgr_mask_rle_workspace_bytes(n, W, H))
-    if nbytes == 0:
-        raise ValueError(f"pgr_mask_rle_workspace_bytes rejected {n} masks of {W} x {H}")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=masks.device)
+    ws = _lib.workspace("pgr_mask_rle", masks.device, n, W, H)
     stats = torch.empty((n, _lib.PGR_MASK_STATS), dtype=torch.int32, device=masks.device)
-    _lib.call("pgr_mask_rle_count", masks.device, _lib.ptr(masks), n, W, H, _lib.ptr(stats), _lib.ptr(ws), nbytes)
+    _lib.call("pgr_mask_rle_count", masks.device, _lib.ptr(masks), n, W, H, _lib.ptr(stats), _lib.ptr(ws), ws.numel())
     return stats, ws
 
 
@@ -90,31 +87,53 @@ def rle_encode(masks):
     return counts, offsets, stats
 
 
-def _rle_lists(rles, size):
-    """Host lists of counts and the common (H, W) of ``rles``: dicts {"counts": [...], "size": [H, W]} or bare lists."""
-    lists, sizes = [], set()
-    for r in rles:
-        c = r["counts"] if isinstance(r, dict) else r
-        if isinstance(c, (str, bytes)):
+# ---- run lists on the host: the one path from what a caller hands in to what the kernels read ------------------------------
+def check_counts(what, size, total, lowest=0, highest=0):
+    """THE rule for one mask of ``size`` = (H, W), from the sum and the extremes of its counts (0 for no counts): sides within
+    1..MAX_SIDE, counts >= 0 that fit 32 bits and sum to H*W (``rle_to_binary_mask`` clips an excess and leaves a tail)."""
+    H, W = size
+    if not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
+        raise ValueError(f"size [H, W] = [{H}, {W}]: each side must be 1..{MAX_SIDE}")
+    if lowest < 0:
+        raise ValueError(f"{what} must not be negative")
+    if highest > 2 ** 31 - 1:
+        raise ValueError(f"{what} are 32-bit")
+    if total != H * W:
+        raise ValueError(f"{what} sum to {total}, not to H*W = {H * W} (a mask's counts are >= 0 and sum to H*W)")
+
+
+def rle_counts(counts, size, what="RLE counts", decode_string=None):
+    """One mask's counts as an int64 array that passed ``check_counts``.  A compressed ``counts`` string goes through
+    ``decode_string`` (coco_eval.rle_string_decode) or, without one, is refused."""
+    if isinstance(counts, (str, bytes)):
+        if decode_string is None:
             raise ValueError(COMPRESSED_MESSAGE)
-        if isinstance(r, dict) and r.get("size") is not None:
-            sizes.add((int(r["size"][0]), int(r["size"][1])))
-        lists.append(np.asarray(c, np.int64).reshape(-1))
-    if size is not None:
-        sizes.add((int(size[0]), int(size[1])))
+        counts = decode_string(counts)
+    counts = np.asarray(counts, np.int64).reshape(-1)
+    check_counts(what, size, int(counts.sum()), int(counts.min(initial=0)), int(counts.max(initial=0)))
+    return counts
+
+
+def rle_lists(rles, size=None, decode_string=None):
+    """(per-mask count arrays as ``rle_counts`` returns them, (H, W)) of ``rles``: dicts {"counts": ..., "size": [H, W]} or bare
+    counts, with ``size`` where no dict names one.  The masks of one call share one size."""
+    rles = list(rles)
+    sizes = set() if size is None else {(int(size[0]), int(size[1]))}
+    sizes.update((int(r["size"][0]), int(r["size"][1])) for r in rles if isinstance(r, dict) and r.get("size") is not None)
     if len(sizes) != 1:
         raise ValueError(f"the masks of one call share one size [H, W]; got {sorted(sizes) or 'none'}")
-    return lists, next(iter(sizes))
+    size = next(iter(sizes))
+    return [rle_counts(r["counts"] if isinstance(r, dict) else r, size, f"RLE counts of mask {k}", decode_string)
+            for k, r in enumerate(rles)], size
 
 
-def check_counts(sums, minimum, n_pixels):
-    """Refuses what ``rle_to_binary_mask`` would clip or leave as a tail: every mask's counts are >= 0 and sum to H*W."""
-    sums = np.asarray(sums, np.int64)
-    if int(minimum) < 0:
-        raise ValueError("RLE counts must not be negative")
-    bad = np.flatnonzero(sums != n_pixels)
-    if len(bad):
-        raise ValueError(f"RLE counts of mask {int(bad[0])} sum to {int(sums[bad[0]])}, not to H*W = {n_pixels}")
+def rle_flatten(lists, device):
+    """Checked count arrays as the kernels read them: (counts int32 [total] and offsets int64 [n+1] on ``device``, total)."""
+    import torch
+    offsets = np.zeros(len(lists) + 1, np.int64)
+    np.cumsum([len(c) for c in lists], out=offsets[1:])
+    flat = np.concatenate(lists) if offsets[-1] else np.zeros(0, np.int64)
+    return torch.from_numpy(flat.astype(np.int32)).to(device), torch.from_numpy(offsets).to(device), int(offsets[-1])
 
 
 def rle_decode(rles, size=None, device="cuda"):
@@ -126,8 +145,7 @@ def rle_decode(rles, size=None, device="cuda"):
     import torch
     if isinstance(rles, dict):
         rles = [rles]
-    pair = isinstance(rles, tuple) and len(rles) == 2 and (torch.is_tensor(rles[0]) or isinstance(rles[0], np.ndarray))
-    if pair:
+    if isinstance(rles, tuple) and len(rles) == 2 and (torch.is_tensor(rles[0]) or isinstance(rles[0], np.ndarray)):
         if size is None:
             raise ValueError("(counts, offsets) needs size=(H, W)")
         H, W = int(size[0]), int(size[1])
@@ -140,29 +158,18 @@ def rle_decode(rles, size=None, device="cuda"):
             raise ValueError("offsets must be a non-decreasing int64 [n+1] inside counts")
         off_dev = torch.from_numpy(offsets).to(counts.device)
         run = torch.cat([torch.zeros(1, dtype=torch.int64, device=counts.device), torch.cumsum(counts.to(torch.int64), 0)])
-        sums = (run[off_dev[1:]] - run[off_dev[:-1]]).cpu().numpy()
-        minimum = int(counts.min()) if counts.numel() else 0
+        lowest = int(counts.min()) if counts.numel() else 0
+        for k, total in enumerate((run[off_dev[1:]] - run[off_dev[:-1]]).tolist()):
+            check_counts(f"RLE counts of mask {k}", (H, W), total, lowest)
     else:
-        lists, (H, W) = _rle_lists(rles, size)
+        lists, (H, W) = rle_lists(rles, size)
         if not lists:
             raise ValueError("no RLE to decode")
-        offsets = np.zeros(len(lists) + 1, np.int64)
-        np.cumsum([len(c) for c in lists], out=offsets[1:])
-        flat = np.concatenate(lists) if offsets[-1] else np.zeros(0, np.int64)
-        sums = np.asarray([int(c.sum()) for c in lists], np.int64)
-        minimum = int(flat.min()) if len(flat) else 0
-        if len(flat) and int(flat.max()) > 2 ** 31 - 1:
-            raise ValueError("RLE counts are 32-bit")
-    if not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
-        raise ValueError(f"size [H, W] = [{H}, {W}]: each side must be 1..{MAX_SIDE}")
-    check_counts(sums, minimum, H * W)
-    if not pair:
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError("rle_decode needs a HIP device; there is no CPU path")
-        counts = torch.from_numpy(flat.astype(np.int32)).to(dev)
-        off_dev = torch.from_numpy(offsets).to(dev)
-    n = len(offsets) - 1
+        counts, off_dev, _ = rle_flatten(lists, dev)
+    n = off_dev.numel() - 1
     out = torch.empty((n, H, W), dtype=torch.uint8, device=counts.device)
     _lib.call("pgr_mask_rle_decode", counts.device, _lib.ptr(counts), _lib.ptr(off_dev), n, W, H, _lib.ptr(out))
     return out

@@ -29,7 +29,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .coco import MAX_SIDE, coco_file_name
+from .coco import coco_file_name, rle_counts, rle_flatten, rle_lists
 
 STAT_NAMES = ("AP", "AP50", "AP75", "AP_small", "AP_medium", "AP_large", "AR1", "AR10", "AR100", "AR_small", "AR_medium",
               "AR_large")
@@ -134,13 +134,6 @@ def summarize(precision, recall, params: Params) -> np.ndarray:
 
 
 # ---- host side: the problem as arrays -------------------------------------------------------------------------------------
-def _counts_of(seg, what):
-    """(counts as an int64 array, (H, W)) of a segmentation dict; the counts a list or a compressed string."""
-    c = seg["counts"]
-    c = np.asarray(rle_string_decode(c) if isinstance(c, (str, bytes)) else c, np.int64).reshape(-1)
-    return c, (int(seg["size"][0]), int(seg["size"][1]))
-
-
 @dataclass
 class Problem:
     """One evaluation as flat host arrays.  GT sorted by (image, category), stable: file order inside a group.  Detections
@@ -195,14 +188,10 @@ def prepare(gt: dict, dt: Sequence[dict], iou_type: str = "segm", params: Option
         seg = entry.get(key)
         if not isinstance(seg, dict) or "counts" not in seg or "size" not in seg:
             raise ValueError(f"{what}: segmentation must be an RLE dict with counts and size")
-        counts, size = _counts_of(seg, what)
+        size = (int(seg["size"][0]), int(seg["size"][1]))
         if size != sizes[image]:
             raise ValueError(f"{what}: RLE size {list(size)} differs from its image's {list(sizes[image])}")
-        if len(counts) and int(counts.min()) < 0:
-            raise ValueError(f"{what}: RLE counts must not be negative")
-        if int(counts.sum()) != size[0] * size[1]:
-            raise ValueError(f"{what}: RLE counts sum to {int(counts.sum())}, not to H*W = {size[0] * size[1]}")
-        return counts
+        return rle_counts(seg["counts"], size, f"{what}: RLE counts", rle_string_decode)
 
     gi, gc, garea, gcrowd, gflag, gshape = [], [], [], [], [], []
     for n, a in enumerate(gt["annotations"]):
@@ -272,6 +261,11 @@ def _device(device):
     return dev
 
 
+def _to_dev(a, dev):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
 def _groups(groups) -> np.ndarray:
     """A group table as GROUP_DTYPE: that already, or rows (dt_begin, dt_count, gt_begin, gt_count[, iou_offset]); without the
     last column the matrices follow each other."""
@@ -298,58 +292,21 @@ def _iou_total(groups: np.ndarray) -> int:
     return int((groups["iou_offset"] + groups["dt_count"].astype(np.int64) * groups["gt_count"]).max())
 
 
-def _workspace(nbytes, what, dev):
-    import torch
-    if nbytes == 0:
-        raise ValueError(f"{what} rejected its arguments")
-    return torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-
-
-def _flat_counts(lists, dev):
-    import torch
-    offsets = np.zeros(len(lists) + 1, np.int64)
-    np.cumsum([len(c) for c in lists], out=offsets[1:])
-    flat = np.concatenate([np.asarray(c, np.int64).reshape(-1) for c in lists]) if offsets[-1] else np.zeros(0, np.int64)
-    if len(flat) and (int(flat.max()) > 2 ** 31 - 1 or int(flat.min()) < 0):
-        raise ValueError("RLE counts are non-negative 32-bit integers")
-    return torch.from_numpy(flat.astype(np.int32)).to(dev), torch.from_numpy(offsets).to(dev), int(offsets[-1])
-
-
 def _rle_iou_call(dt_lists, gt_lists, crowd, size, groups, iou_total, inter, iou, dev):
-    """pgr_rle_iou over host count lists of ONE image size; fills the groups' cells of ``inter`` / ``iou`` and returns
-    (dt_area, gt_area) int64 on the device."""
+    """pgr_rle_iou over host count lists of ONE image size, as ``coco.rle_counts`` checked them against it; fills the groups'
+    cells of ``inter`` / ``iou`` and returns (dt_area, gt_area) int64 on the device."""
     import torch
-    H, W = int(size[0]), int(size[1])
-    if not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
-        raise ValueError(f"size [H, W] = [{H}, {W}]: each side must be 1..{MAX_SIDE}")
-    dc, do, dtot = _flat_counts(dt_lists, dev)
-    gc, go, gtot = _flat_counts(gt_lists, dev)
-    crowd_dev = torch.from_numpy(np.ascontiguousarray(crowd, np.uint8)).to(dev)
+    H, W = size
+    dc, do, dtot = rle_flatten(dt_lists, dev)
+    gc, go, gtot = rle_flatten(gt_lists, dev)
+    crowd_dev = _to_dev(np.asarray(crowd, np.uint8), dev)
     dt_area = torch.empty(len(dt_lists), dtype=torch.int64, device=dev)
     gt_area = torch.empty(len(gt_lists), dtype=torch.int64, device=dev)
-    ws = _workspace(_lib.lib().pgr_rle_iou_workspace_bytes(len(groups), dtot, gtot), "pgr_rle_iou_workspace_bytes", dev)
+    ws = _lib.workspace("pgr_rle_iou", dev, len(groups), dtot, gtot)
     _lib.call("pgr_rle_iou", dev, _lib.ptr(dc), _lib.ptr(do), len(dt_lists), dtot, _lib.ptr(gc), _lib.ptr(go), len(gt_lists),
               gtot, _lib.ptr(crowd_dev), W, H, _group_ptr(groups), len(groups), iou_total, _lib.ptr(inter), _lib.ptr(iou),
               _lib.ptr(dt_area), _lib.ptr(gt_area), _lib.ptr(ws), ws.numel())
     return dt_area, gt_area
-
-
-def _lists(rles, size):
-    lists, sizes = [], set() if size is None else {(int(size[0]), int(size[1]))}
-    for n, r in enumerate(rles):
-        if isinstance(r, dict):
-            c, s = _counts_of(r, f"RLE {n}")
-            sizes.add(s)
-        else:
-            c = np.asarray(rle_string_decode(r) if isinstance(r, (str, bytes)) else r, np.int64).reshape(-1)
-        lists.append(c)
-    if len(sizes) != 1:
-        raise ValueError(f"the masks of one call share one size [H, W]; got {sorted(sizes) or 'none'}")
-    H, W = next(iter(sizes))
-    for n, c in enumerate(lists):
-        if (len(c) and int(c.min()) < 0) or int(c.sum()) != H * W:
-            raise ValueError(f"RLE {n}: counts must be >= 0 and sum to H*W = {H * W}")
-    return lists, (H, W)
 
 
 def rle_ious(dt_rles, gt_rles, groups, crowd=None, size=None, device="cuda"):
@@ -359,7 +316,7 @@ def rle_ious(dt_rles, gt_rles, groups, crowd=None, size=None, device="cuda"):
     matrix is ``iou[iou_offset:][:dt_count * gt_count].reshape(dt_count, gt_count)``."""
     import torch
     dev = _device(device)
-    both, size = _lists(list(dt_rles) + list(gt_rles), size)
+    both, size = rle_lists(list(dt_rles) + list(gt_rles), size, rle_string_decode)
     dt_lists, gt_lists = both[:len(dt_rles)], both[len(dt_rles):]
     groups = _groups(groups)
     crowd = np.zeros(len(gt_lists), np.uint8) if crowd is None else np.asarray(crowd, np.uint8)
@@ -376,16 +333,15 @@ def box_ious(dt_boxes, gt_boxes, groups, crowd=None, device="cuda"):
     """Box IoU inside groups: boxes [n,4] = x, y, w, h (float64).  Returns the device tensor iou float64 [total]."""
     import torch
     dev = _device(device)
-    to_dev = lambda b: torch.from_numpy(np.ascontiguousarray(np.asarray(b, np.float64).reshape(-1, 4))).to(dev)
-    d, g = to_dev(dt_boxes), to_dev(gt_boxes)
+    d, g = (_to_dev(np.asarray(b, np.float64).reshape(-1, 4), dev) for b in (dt_boxes, gt_boxes))
     groups = _groups(groups)
     crowd = np.zeros(len(g), np.uint8) if crowd is None else np.asarray(crowd, np.uint8)
     if len(crowd) != len(g):
         raise ValueError("one crowd flag per ground-truth box")
-    crowd_dev = torch.from_numpy(np.ascontiguousarray(crowd)).to(dev)
+    crowd_dev = _to_dev(crowd, dev)
     total = _iou_total(groups)
     iou = torch.zeros(total, dtype=torch.float64, device=dev)
-    ws = _workspace(_lib.lib().pgr_box_iou_workspace_bytes(len(groups)), "pgr_box_iou_workspace_bytes", dev)
+    ws = _lib.workspace("pgr_box_iou", dev, len(groups))
     _lib.call("pgr_box_iou", dev, _lib.ptr(d), len(d), _lib.ptr(g), len(g), _lib.ptr(crowd_dev), _group_ptr(groups), len(groups),
               total, _lib.ptr(iou), _lib.ptr(ws), ws.numel())
     return iou
@@ -426,13 +382,12 @@ def problem_match(prob: Problem, iou, dt_area, device="cuda"):
     thr = np.ascontiguousarray(P.iou_thrs, np.float64)
     rng = np.ascontiguousarray(np.asarray(P.area_rng, np.float64).reshape(-1, 2))
     A, T, n_dt, n_gt = len(rng), len(thr), len(prob.dt_score), len(prob.gt_area)
-    to_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    gt_area, gt_flag, gt_crowd = to_dev(prob.gt_area), to_dev(prob.gt_flag), to_dev(prob.gt_crowd)
+    gt_area, gt_flag, gt_crowd = (_to_dev(a, dev) for a in (prob.gt_area, prob.gt_flag, prob.gt_crowd))
     dt_match = torch.full((A, T, n_dt), -1, dtype=torch.int32, device=dev)
     dt_ignore = torch.zeros((A, T, n_dt), dtype=torch.uint8, device=dev)
     gt_match = torch.full((A, T, n_gt), -1, dtype=torch.int32, device=dev)
     gt_ignore = torch.zeros((A, n_gt), dtype=torch.uint8, device=dev)
-    ws = _workspace(_lib.lib().pgr_coco_match_workspace_bytes(len(prob.groups), n_gt, A), "pgr_coco_match_workspace_bytes", dev)
+    ws = _lib.workspace("pgr_coco_match", dev, len(prob.groups), n_gt, A)
     _lib.call("pgr_coco_match", dev, _group_ptr(prob.groups), len(prob.groups), prob.iou_total, _lib.ptr(iou), _lib.ptr(dt_area),
               n_dt, _lib.ptr(gt_area), _lib.ptr(gt_flag), _lib.ptr(gt_crowd), n_gt, thr.ctypes.data_as(C.POINTER(C.c_double)), T,
               rng.ctypes.data_as(C.POINTER(C.c_double)), A, _lib.ptr(dt_match), _lib.ptr(dt_ignore), _lib.ptr(gt_match),
@@ -448,18 +403,17 @@ def problem_accumulate(prob: Problem, dt_match, dt_ignore, device="cuda"):
     P = prob.params
     A, T, R, M, K = len(P.area_rng), len(P.iou_thrs), len(P.rec_thrs), len(P.max_dets), len(prob.cat_ids)
     n_dt = len(prob.dt_score)
-    to_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    score, cat, rank = to_dev(prob.dt_score), to_dev(prob.dt_cat.astype(np.int64)), to_dev(prob.dt_rank)
+    score, cat, rank = (_to_dev(a, dev) for a in (prob.dt_score, prob.dt_cat.astype(np.int64), prob.dt_rank))
     by_score = torch.sort(-score, stable=True).indices
     perm = by_score[torch.sort(cat[by_score], stable=True).indices].contiguous()
     seg = np.zeros(K + 1, np.int64)
     np.cumsum(np.bincount(prob.dt_cat, minlength=K)[:K], out=seg[1:])
-    seg_dev, npig_dev, rec = to_dev(seg), to_dev(npig(prob)), to_dev(np.asarray(P.rec_thrs, np.float64))
+    seg_dev, npig_dev, rec = (_to_dev(a, dev) for a in (seg, npig(prob), np.asarray(P.rec_thrs, np.float64)))
     max_dets = (C.c_int32 * M)(*[int(m) for m in P.max_dets])
     precision = torch.empty((T, R, K, A, M), dtype=torch.float64, device=dev)
     scores = torch.empty((T, R, K, A, M), dtype=torch.float64, device=dev)
     recall = torch.empty((T, K, A, M), dtype=torch.float64, device=dev)
-    ws = _workspace(_lib.lib().pgr_coco_accumulate_workspace_bytes(n_dt, A, M), "pgr_coco_accumulate_workspace_bytes", dev)
+    ws = _lib.workspace("pgr_coco_accumulate", dev, n_dt, A, M)
     _lib.call("pgr_coco_accumulate", dev, _lib.ptr(perm), _lib.ptr(seg_dev), K, _lib.ptr(rank), _lib.ptr(dt_match),
               _lib.ptr(dt_ignore), _lib.ptr(score), n_dt, _lib.ptr(npig_dev), max_dets, M, _lib.ptr(rec), R, T, A,
               _lib.ptr(precision), _lib.ptr(scores), _lib.ptr(recall), _lib.ptr(ws), ws.numel())

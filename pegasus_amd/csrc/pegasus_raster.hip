@@ -43,11 +43,17 @@ static bool hip_ok(hipError_t e, const char* what) {
 
 static constexpr size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
-// Hands out consecutive slices of a buffer, each aligned to 256 B; a slice of zero bytes still takes one unit.
+// Hands out consecutive slices of a buffer, each aligned to 256 B; a slice of zero bytes still takes one unit.  So no layout
+// is empty, and the layout functions that check their sizing arguments themselves return one whose total is 0 for "refused".
 struct Carver {
     size_t off = 0;
     size_t take(size_t bytes) { const size_t o = off; off += align_up(bytes ? bytes : 1); return o; }
 };
+
+// What the evaluation entries (masks, COCO scores) ask of a workspace pointer: their kernels read and write it in 16-byte and
+// 8-byte elements at the carved offsets.  And the most workgroups one launch of theirs may have: grid.x is 31 bits.
+static bool workspace_aligned_16(const void* workspace) { return reinterpret_cast<uintptr_t>(workspace) % 16 == 0; }
+constexpr int64_t MAX_GRID_BLOCKS = 0x7fffffff;
 
 // Calls of one or two views (the drop-in GaussianRasterizer: one camera per call) cannot fill the chip; their launches are
 // latency-bound and get a few arrangements of their own (fewer, fuller launches).  Results never depend on it.
@@ -1196,12 +1202,20 @@ int64_t mesh_queue_capacity(int32_t n_jobs, const PgrMeshJob* jobs) {
     }
     return cap;
 }
+// pgr_mesh_depth's workspace: the queue's counter, then a queue that holds the faces of the largest launch
+struct MeshDepthLayout { size_t qctr, queue, total; };
+MeshDepthLayout mesh_depth_layout(int32_t n_jobs, const PgrMeshJob* jobs) {
+    MeshDepthLayout L{};
+    if (n_jobs <= 0 || !mesh_jobs_ok(n_jobs, jobs)) return L;
+    Carver c;
+    L.qctr = c.take(sizeof(unsigned long long));
+    L.queue = c.take((size_t)mesh_queue_capacity(n_jobs, jobs) * sizeof(MeshQueueEntry));
+    L.total = c.off;
+    return L;
+}
 }  // namespace
 
-size_t pgr_mesh_depth_workspace_bytes(int32_t n_jobs, const PgrMeshJob* jobs) {
-    if (n_jobs <= 0 || !mesh_jobs_ok(n_jobs, jobs)) return 0;
-    return align_up(sizeof(unsigned long long)) + align_up((size_t)std::max<int64_t>(mesh_queue_capacity(n_jobs, jobs), 1) * sizeof(MeshQueueEntry));
-}
+size_t pgr_mesh_depth_workspace_bytes(int32_t n_jobs, const PgrMeshJob* jobs) { return mesh_depth_layout(n_jobs, jobs).total; }
 
 int32_t pgr_mesh_depth(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int32_t n_jobs,
                        const PgrMeshJob* jobs, int32_t width, int32_t height, float near_z, float* depth, int32_t n_slots,
@@ -1219,8 +1233,8 @@ int32_t pgr_mesh_depth(const float* vertices, int64_t n_vertices, const int32_t*
         any_faces = any_faces || j.face_count > 0;
     }
     if (any_faces && (!vertices || !faces)) return PGR_ERR_INVALID_ARGUMENT;
-    if (n_jobs > 0 && (!workspace || workspace_bytes < pgr_mesh_depth_workspace_bytes(n_jobs, jobs)))
-        return PGR_ERR_WORKSPACE_TOO_SMALL;
+    const MeshDepthLayout L = mesh_depth_layout(n_jobs, jobs);
+    if (n_jobs > 0 && (!L.total || !workspace || workspace_bytes < L.total)) return PGR_ERR_WORKSPACE_TOO_SMALL;
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     const size_t plane = (size_t)width * height, total = plane * (size_t)n_slots;
     auto* out = reinterpret_cast<uint32_t*>(depth);
@@ -1228,8 +1242,8 @@ int32_t pgr_mesh_depth(const float* vertices, int64_t n_vertices, const int32_t*
         !hip_ok(hipMemsetAsync(straddle_count, 0, sizeof(int32_t), stream), "mesh_depth clear"))
         return PGR_ERR_LAUNCH_FAILURE;
     char* ws = static_cast<char*>(workspace);
-    auto* qctr = reinterpret_cast<unsigned long long*>(ws);
-    auto* queue = reinterpret_cast<MeshQueueEntry*>(ws + align_up(sizeof(unsigned long long)));
+    auto* qctr = reinterpret_cast<unsigned long long*>(ws + L.qctr);
+    auto* queue = reinterpret_cast<MeshQueueEntry*>(ws + L.queue);
     int64_t group_faces = 0;
     for (int32_t k0 = 0; k0 < n_jobs;) {
         const int32_t k1 = mesh_group_end(n_jobs, jobs, k0, &group_faces);
@@ -1310,6 +1324,22 @@ bool pose_vertices_ok(const float* vertices, int64_t n_vertices, int32_t n_jobs,
     return true;
 }
 int64_t adi_groups(const PgrPoseErrorJob& j) { return ((int64_t)j.vertex_count + ADI_TILE - 1) / ADI_TILE; }
+// pgr_pose_adi's workspace: one float64 partial sum per tile of queries, the jobs' tiles back to back
+struct AdiLayout { size_t partials, total; };
+AdiLayout adi_layout(int32_t n_jobs, const PgrPoseErrorJob* jobs) {
+    AdiLayout L{};
+    if (n_jobs <= 0 || !jobs) return L;
+    int64_t groups = 0;
+    for (int32_t k = 0; k < n_jobs; ++k) {
+        if (jobs[k].vertex_count <= 0) return L;
+        groups += adi_groups(jobs[k]);
+    }
+    if (groups > INT32_MAX) return L;
+    Carver c;
+    L.partials = c.take((size_t)groups * sizeof(double));
+    L.total = c.off;
+    return L;
+}
 }  // namespace
 
 int32_t pgr_pose_errors(const float* vertices, int64_t n_vertices, const double* syms, int64_t n_syms, int32_t n_jobs,
@@ -1345,25 +1375,17 @@ int32_t pgr_pose_errors(const float* vertices, int64_t n_vertices, const double*
     return hip_ok(hipGetLastError(), "pose_errors launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
 }
 
-size_t pgr_pose_adi_workspace_bytes(int32_t n_jobs, const PgrPoseErrorJob* jobs) {
-    if (n_jobs <= 0 || !jobs) return 0;
-    int64_t groups = 0;
-    for (int32_t k = 0; k < n_jobs; ++k) {
-        if (jobs[k].vertex_count <= 0) return 0;
-        groups += adi_groups(jobs[k]);
-    }
-    return groups > INT32_MAX ? 0 : align_up((size_t)groups * sizeof(double));
-}
+size_t pgr_pose_adi_workspace_bytes(int32_t n_jobs, const PgrPoseErrorJob* jobs) { return adi_layout(n_jobs, jobs).total; }
 
 int32_t pgr_pose_adi(const float* vertices, int64_t n_vertices, int32_t n_jobs, const PgrPoseErrorJob* jobs, float* adi,
                      void* workspace, size_t workspace_bytes, void* stream_v) {
     if (!pose_vertices_ok(vertices, n_vertices, n_jobs, jobs) || (n_jobs > 0 && !adi)) return PGR_ERR_INVALID_ARGUMENT;
     if (n_jobs == 0) return PGR_OK;
-    const size_t need = pgr_pose_adi_workspace_bytes(n_jobs, jobs);
-    if (need == 0) return PGR_ERR_INVALID_ARGUMENT;
-    if (!workspace || workspace_bytes < need) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    const AdiLayout L = adi_layout(n_jobs, jobs);
+    if (!L.total) return PGR_ERR_INVALID_ARGUMENT;
+    if (!workspace || workspace_bytes < L.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    auto* partials = static_cast<double*>(workspace);
+    auto* partials = reinterpret_cast<double*>(static_cast<char*>(workspace) + L.partials);
     uint32_t part = 0;
     for (int32_t k0 = 0; k0 < n_jobs; k0 += ADI_JOBS_PER_LAUNCH) {
         AdiJobTable T{};
@@ -1399,15 +1421,14 @@ int32_t pgr_pose_adi(const float* vertices, int64_t n_vertices, int32_t n_jobs, 
 // ---- COCO annotations: mask run-length encoding, decoding, overlap counts (cocorle.hip.h) -------------------------------
 namespace {
 constexpr int32_t RLE_MAX_SIDE = 8192;
-constexpr int64_t RLE_MAX_BLOCKS = 0x7fffffff;
 struct RleLayout { size_t planes, columns, total; int S, Wp, col_tiles, row_groups, col_blocks; int64_t plane_blocks, column_blocks; };
 bool rle_shape_ok(int64_t n_masks, int32_t width, int32_t height) {
     return n_masks >= 1 && n_masks <= INT32_MAX && width >= 1 && width <= RLE_MAX_SIDE && height >= 1 && height <= RLE_MAX_SIDE;
 }
 // the encoder's workspace: the bit planes, then 16 bytes per column; launches that would not fit a grid make it invalid
-bool rle_layout(int32_t n_masks, int32_t width, int32_t height, RleLayout* out) {
-    if (!rle_shape_ok(n_masks, width, height)) return false;
+RleLayout rle_layout(int32_t n_masks, int32_t width, int32_t height) {
     RleLayout L{};
+    if (!rle_shape_ok(n_masks, width, height)) return L;
     L.S = (height + RLE_WORD_ROWS - 1) / RLE_WORD_ROWS;
     L.Wp = (width + 3) / 4 * 4;
     L.col_tiles = (width + RLE_TILE_COLS - 1) / RLE_TILE_COLS;
@@ -1415,27 +1436,21 @@ bool rle_layout(int32_t n_masks, int32_t width, int32_t height, RleLayout* out) 
     L.col_blocks = (width + RLE_THREADS - 1) / RLE_THREADS;
     L.plane_blocks = (int64_t)n_masks * L.col_tiles * L.row_groups;
     L.column_blocks = (int64_t)n_masks * L.col_blocks;
-    if (L.plane_blocks > RLE_MAX_BLOCKS || L.column_blocks > RLE_MAX_BLOCKS) return false;
+    if (L.plane_blocks > MAX_GRID_BLOCKS || L.column_blocks > MAX_GRID_BLOCKS) return L;
     Carver c;
     L.planes = c.take((size_t)n_masks * L.S * L.Wp * sizeof(uint32_t));
     L.columns = c.take((size_t)n_masks * width * sizeof(RleColumn));
     L.total = c.off;
-    *out = L;
-    return true;
+    return L;
 }
-bool rle_workspace_aligned(const void* workspace) { return reinterpret_cast<uintptr_t>(workspace) % 16 == 0; }
 }  // namespace
 
-size_t pgr_mask_rle_workspace_bytes(int32_t n_masks, int32_t width, int32_t height) {
-    RleLayout L;
-    return rle_layout(n_masks, width, height, &L) ? L.total : 0;
-}
+size_t pgr_mask_rle_workspace_bytes(int32_t n_masks, int32_t width, int32_t height) { return rle_layout(n_masks, width, height).total; }
 
 int32_t pgr_mask_rle_count(const uint8_t* masks, int32_t n_masks, int32_t width, int32_t height, int32_t* stats, void* workspace,
                            size_t workspace_bytes, void* stream_v) {
-    RleLayout L;
-    if (!masks || !stats || !workspace || !rle_workspace_aligned(workspace) || !rle_layout(n_masks, width, height, &L))
-        return PGR_ERR_INVALID_ARGUMENT;
+    const RleLayout L = rle_layout(n_masks, width, height);
+    if (!masks || !stats || !workspace || !workspace_aligned_16(workspace) || !L.total) return PGR_ERR_INVALID_ARGUMENT;
     if (workspace_bytes < L.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     char* ws = static_cast<char*>(workspace);
@@ -1452,10 +1467,8 @@ int32_t pgr_mask_rle_count(const uint8_t* masks, int32_t n_masks, int32_t width,
 int32_t pgr_mask_rle_emit(const uint8_t* masks, int32_t n_masks, int32_t width, int32_t height, const int64_t* offsets,
                           int64_t total, int32_t* counts, int64_t capacity, const void* workspace, size_t workspace_bytes,
                           void* stream_v) {
-    RleLayout L;
-    if (!masks || !offsets || !counts || !workspace || !rle_workspace_aligned(workspace) ||
-        !rle_layout(n_masks, width, height, &L))
-        return PGR_ERR_INVALID_ARGUMENT;
+    const RleLayout L = rle_layout(n_masks, width, height);
+    if (!masks || !offsets || !counts || !workspace || !workspace_aligned_16(workspace) || !L.total) return PGR_ERR_INVALID_ARGUMENT;
     // every mask has at least one count and at most one per pixel plus one
     if (total < n_masks || total > (int64_t)n_masks * ((int64_t)width * height + 1) || capacity < total)
         return PGR_ERR_INVALID_ARGUMENT;
@@ -1473,7 +1486,7 @@ int32_t pgr_mask_rle_decode(const int32_t* counts, const int64_t* offsets, int32
     const int64_t HW = (int64_t)width * height;
     const int64_t slice = std::max<int64_t>(RLE_DECODE_MIN_SLICE, (HW + RLE_DECODE_MAX_SLICES - 1) / RLE_DECODE_MAX_SLICES);
     const int64_t slices = (HW + slice - 1) / slice;
-    if ((int64_t)n_masks * slices > RLE_MAX_BLOCKS) return PGR_ERR_INVALID_ARGUMENT;
+    if ((int64_t)n_masks * slices > MAX_GRID_BLOCKS) return PGR_ERR_INVALID_ARGUMENT;
     rle_decode_kernel<<<(unsigned)(n_masks * slices), RLE_THREADS, 0, static_cast<hipStream_t>(stream_v)>>>(
         counts, reinterpret_cast<const long long*>(offsets), width, height, (int)slices, (int)slice, masks);
     return hip_ok(hipGetLastError(), "mask_rle_decode launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
@@ -1486,7 +1499,7 @@ int32_t pgr_mask_overlap(const uint8_t* a, int32_t n_a, const uint8_t* b, int32_
     const size_t HW = (size_t)width * height;
     const int64_t chunks = (int64_t)((HW + OVERLAP_CHUNK - 1) / OVERLAP_CHUNK);
     const int64_t pairs = (int64_t)n_a * n_b;
-    if (pairs > RLE_MAX_BLOCKS || pairs * chunks > RLE_MAX_BLOCKS) return PGR_ERR_INVALID_ARGUMENT;
+    if (pairs > MAX_GRID_BLOCKS || pairs * chunks > MAX_GRID_BLOCKS) return PGR_ERR_INVALID_ARGUMENT;
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     if (!hip_ok(hipMemsetAsync(inter, 0, (size_t)pairs * sizeof(int32_t), stream), "mask_overlap clear") ||
         !hip_ok(hipMemsetAsync(area_a, 0, (size_t)n_a * sizeof(int32_t), stream), "mask_overlap clear") ||
@@ -1514,16 +1527,50 @@ bool coco_groups_ok(const PgrCocoGroup* groups, int32_t n_groups, int32_t n_dt, 
     return true;
 }
 struct CocoIouLayout { size_t groups, dt_ends, dt_cover, gt_ends, gt_cover, total; };
-bool coco_iou_layout(int32_t n_groups, int64_t dt_total, int64_t gt_total, CocoIouLayout* out) {
-    if (n_groups < 0 || dt_total < 0 || gt_total < 0 || dt_total > ((int64_t)1 << 40) || gt_total > ((int64_t)1 << 40)) return false;
+CocoIouLayout coco_iou_layout(int32_t n_groups, int64_t dt_total, int64_t gt_total) {
+    CocoIouLayout L{};
+    if (n_groups < 0 || dt_total < 0 || gt_total < 0 || dt_total > ((int64_t)1 << 40) || gt_total > ((int64_t)1 << 40)) return L;
     Carver c;
-    out->groups = c.take((size_t)n_groups * sizeof(PgrCocoGroup));
-    out->dt_ends = c.take((size_t)dt_total * sizeof(int32_t));
-    out->dt_cover = c.take((size_t)dt_total * sizeof(int32_t));      // (read for the detections' areas only)
-    out->gt_ends = c.take((size_t)gt_total * sizeof(int32_t));
-    out->gt_cover = c.take((size_t)gt_total * sizeof(int32_t));
-    out->total = c.off;
-    return true;
+    L.groups = c.take((size_t)n_groups * sizeof(PgrCocoGroup));
+    L.dt_ends = c.take((size_t)dt_total * sizeof(int32_t));
+    L.dt_cover = c.take((size_t)dt_total * sizeof(int32_t));      // (read for the detections' areas only)
+    L.gt_ends = c.take((size_t)gt_total * sizeof(int32_t));
+    L.gt_cover = c.take((size_t)gt_total * sizeof(int32_t));
+    L.total = c.off;
+    return L;
+}
+struct CocoBoxLayout { size_t groups, total; };
+CocoBoxLayout coco_box_layout(int32_t n_groups) {
+    CocoBoxLayout L{};
+    if (n_groups < 0) return L;
+    Carver c;
+    L.groups = c.take((size_t)n_groups * sizeof(PgrCocoGroup));
+    L.total = c.off;
+    return L;
+}
+// pgr_coco_match's workspace: the group table, then per area range the order in which each GT is tried
+struct CocoMatchLayout { size_t groups, order, total; };
+CocoMatchLayout coco_match_layout(int32_t n_groups, int32_t n_gt, int32_t n_area) {
+    CocoMatchLayout L{};
+    if (n_groups < 0 || n_gt < 0 || n_area < 1 || n_area > COCO_MAX_LANES) return L;
+    Carver c;
+    L.groups = c.take((size_t)n_groups * sizeof(PgrCocoGroup));
+    L.order = c.take((size_t)n_area * n_gt * sizeof(int32_t));
+    L.total = c.off;
+    return L;
+}
+// pgr_coco_accumulate's workspace: three arrays of one cell per (area range, maxDets entry, detection)
+struct CocoAccumulateLayout { size_t tp, idx, pr, total; };
+CocoAccumulateLayout coco_accumulate_layout(int32_t n_dt, int32_t n_area, int32_t n_max_dets) {
+    CocoAccumulateLayout L{};
+    if (n_dt < 0 || n_area < 1 || n_area > COCO_MAX_LANES || n_max_dets < 1 || n_max_dets > PGR_COCO_MAX_MAXDETS) return L;
+    const size_t cells = (size_t)n_area * n_max_dets * n_dt;
+    Carver c;
+    L.tp = c.take(cells * sizeof(int32_t));
+    L.idx = c.take(cells * sizeof(int32_t));
+    L.pr = c.take(cells * sizeof(double));
+    L.total = c.off;
+    return L;
 }
 // the table goes to the device in stream order and has been read when this returns: the caller may free it after the call
 bool coco_groups_upload(void* dst, const PgrCocoGroup* groups, int32_t n_groups, hipStream_t stream) {
@@ -1533,8 +1580,7 @@ bool coco_groups_upload(void* dst, const PgrCocoGroup* groups, int32_t n_groups,
 }  // namespace
 
 size_t pgr_rle_iou_workspace_bytes(int32_t n_groups, int64_t dt_total, int64_t gt_total) {
-    CocoIouLayout L;
-    return coco_iou_layout(n_groups, dt_total, gt_total, &L) ? L.total : 0;
+    return coco_iou_layout(n_groups, dt_total, gt_total).total;
 }
 
 int32_t pgr_rle_iou(const int32_t* dt_counts, const int64_t* dt_offsets, int32_t n_dt, int64_t dt_total,
@@ -1542,9 +1588,9 @@ int32_t pgr_rle_iou(const int32_t* dt_counts, const int64_t* dt_offsets, int32_t
                     int32_t width, int32_t height, const PgrCocoGroup* groups, int32_t n_groups, int64_t iou_total,
                     int64_t* inter, double* iou, int64_t* dt_area, int64_t* gt_area, void* workspace, size_t workspace_bytes,
                     void* stream_v) {
-    CocoIouLayout L;
+    const CocoIouLayout L = coco_iou_layout(n_groups, dt_total, gt_total);
     if (width < 1 || width > RLE_MAX_SIDE || height < 1 || height > RLE_MAX_SIDE || !coco_groups_ok(groups, n_groups, n_dt, n_gt, iou_total) ||
-        !coco_iou_layout(n_groups, dt_total, gt_total, &L) || !workspace || !rle_workspace_aligned(workspace))
+        !L.total || !workspace || !workspace_aligned_16(workspace))
         return PGR_ERR_INVALID_ARGUMENT;
     if ((n_dt > 0 && (!dt_offsets || !dt_area || (dt_total > 0 && !dt_counts))) ||
         (n_gt > 0 && (!gt_offsets || !gt_area || !gt_crowd || (gt_total > 0 && !gt_counts))) || (iou_total > 0 && (!inter || !iou)))
@@ -1576,28 +1622,26 @@ int32_t pgr_rle_iou(const int32_t* dt_counts, const int64_t* dt_offsets, int32_t
     return hip_ok(hipGetLastError(), "rle_iou launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
 }
 
-size_t pgr_box_iou_workspace_bytes(int32_t n_groups) {
-    return n_groups < 0 ? 0 : align_up((size_t)std::max(n_groups, 1) * sizeof(PgrCocoGroup));
-}
+size_t pgr_box_iou_workspace_bytes(int32_t n_groups) { return coco_box_layout(n_groups).total; }
 
 int32_t pgr_box_iou(const double* dt_boxes, int32_t n_dt, const double* gt_boxes, int32_t n_gt, const uint8_t* gt_crowd,
                     const PgrCocoGroup* groups, int32_t n_groups, int64_t iou_total, double* iou, void* workspace,
                     size_t workspace_bytes, void* stream_v) {
-    if (!coco_groups_ok(groups, n_groups, n_dt, n_gt, iou_total) || !workspace || !rle_workspace_aligned(workspace) ||
+    const CocoBoxLayout L = coco_box_layout(n_groups);
+    if (!coco_groups_ok(groups, n_groups, n_dt, n_gt, iou_total) || !L.total || !workspace || !workspace_aligned_16(workspace) ||
         (n_dt > 0 && !dt_boxes) || (n_gt > 0 && (!gt_boxes || !gt_crowd)) || (iou_total > 0 && !iou))
         return PGR_ERR_INVALID_ARGUMENT;
-    if (workspace_bytes < pgr_box_iou_workspace_bytes(n_groups)) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    if (workspace_bytes < L.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
     if (n_groups == 0 || iou_total == 0) return PGR_OK;
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    auto* groups_dev = static_cast<PgrCocoGroup*>(workspace);
+    auto* groups_dev = reinterpret_cast<PgrCocoGroup*>(static_cast<char*>(workspace) + L.groups);
     if (!coco_groups_upload(groups_dev, groups, n_groups, stream)) return PGR_ERR_LAUNCH_FAILURE;
     coco_box_iou_kernel<<<(unsigned)n_groups, COCO_THREADS, 0, stream>>>(groups_dev, dt_boxes, gt_boxes, gt_crowd, iou);
     return hip_ok(hipGetLastError(), "box_iou launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
 }
 
 size_t pgr_coco_match_workspace_bytes(int32_t n_groups, int32_t n_gt, int32_t n_area) {
-    if (n_groups < 0 || n_gt < 0 || n_area < 1 || n_area > COCO_MAX_LANES) return 0;
-    return align_up((size_t)std::max(n_groups, 1) * sizeof(PgrCocoGroup)) + align_up(std::max<size_t>((size_t)n_area * n_gt, 1) * sizeof(int32_t));
+    return coco_match_layout(n_groups, n_gt, n_area).total;
 }
 
 int32_t pgr_coco_match(const PgrCocoGroup* groups, int32_t n_groups, int64_t iou_total, const double* iou, const double* dt_area,
@@ -1605,8 +1649,9 @@ int32_t pgr_coco_match(const PgrCocoGroup* groups, int32_t n_groups, int64_t iou
                        const double* iou_thrs, int32_t n_thr, const double* area_rng, int32_t n_area, int32_t* dt_match,
                        uint8_t* dt_ignore, int32_t* gt_match, uint8_t* gt_ignore, void* workspace, size_t workspace_bytes,
                        void* stream_v) {
-    if (n_thr < 1 || n_area < 1 || (int64_t)n_thr * n_area > COCO_MAX_LANES || !iou_thrs || !area_rng ||
-        !coco_groups_ok(groups, n_groups, n_dt, n_gt, iou_total) || !workspace || !rle_workspace_aligned(workspace) ||
+    const CocoMatchLayout L = coco_match_layout(n_groups, n_gt, n_area);
+    if (n_thr < 1 || !L.total || (int64_t)n_thr * n_area > COCO_MAX_LANES || !iou_thrs || !area_rng ||
+        !coco_groups_ok(groups, n_groups, n_dt, n_gt, iou_total) || !workspace || !workspace_aligned_16(workspace) ||
         (n_dt > 0 && (!dt_area || !dt_match || !dt_ignore)) ||
         (n_gt > 0 && (!gt_area || !gt_flag || !gt_crowd || !gt_match || !gt_ignore)) || (iou_total > 0 && !iou))
         return PGR_ERR_INVALID_ARGUMENT;
@@ -1620,12 +1665,12 @@ int32_t pgr_coco_match(const PgrCocoGroup* groups, int32_t n_groups, int64_t iou
             P.lo[a * n_thr + t] = area_rng[2 * a];
             P.hi[a * n_thr + t] = area_rng[2 * a + 1];
         }
-    if (workspace_bytes < pgr_coco_match_workspace_bytes(n_groups, n_gt, n_area)) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    if (workspace_bytes < L.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
     if (n_groups == 0) return PGR_OK;
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     char* ws = static_cast<char*>(workspace);
-    auto* groups_dev = reinterpret_cast<PgrCocoGroup*>(ws);
-    auto* order = reinterpret_cast<int32_t*>(ws + align_up((size_t)n_groups * sizeof(PgrCocoGroup)));
+    auto* groups_dev = reinterpret_cast<PgrCocoGroup*>(ws + L.groups);
+    auto* order = reinterpret_cast<int32_t*>(ws + L.order);
     if (!coco_groups_upload(groups_dev, groups, n_groups, stream)) return PGR_ERR_LAUNCH_FAILURE;
     coco_match_kernel<<<(unsigned)n_groups, WAVE, 0, stream>>>(groups_dev, P, iou, dt_area, gt_area, gt_flag, gt_crowd, (long long)n_dt,
                                                               (long long)n_gt, order, dt_match, dt_ignore, gt_match, gt_ignore);
@@ -1633,9 +1678,7 @@ int32_t pgr_coco_match(const PgrCocoGroup* groups, int32_t n_groups, int64_t iou
 }
 
 size_t pgr_coco_accumulate_workspace_bytes(int32_t n_dt, int32_t n_area, int32_t n_max_dets) {
-    if (n_dt < 0 || n_area < 1 || n_area > COCO_MAX_LANES || n_max_dets < 1 || n_max_dets > PGR_COCO_MAX_MAXDETS) return 0;
-    const size_t cells = std::max<size_t>((size_t)n_area * n_max_dets * n_dt, 1);
-    return 2 * align_up(cells * sizeof(int32_t)) + align_up(cells * sizeof(double));
+    return coco_accumulate_layout(n_dt, n_area, n_max_dets).total;
 }
 
 int32_t pgr_coco_accumulate(const int64_t* perm, const int64_t* seg_start, int32_t n_cat, const int32_t* rank,
@@ -1643,25 +1686,24 @@ int32_t pgr_coco_accumulate(const int64_t* perm, const int64_t* seg_start, int32
                             const int32_t* npig, const int32_t* max_dets, int32_t n_max_dets, const double* rec_thrs,
                             int32_t n_rec, int32_t n_thr, int32_t n_area, double* precision, double* scores, double* recall,
                             void* workspace, size_t workspace_bytes, void* stream_v) {
-    const size_t need = pgr_coco_accumulate_workspace_bytes(n_dt, n_area, n_max_dets);
-    if (need == 0 || n_cat < 0 || n_rec < 1 || n_thr < 1 || (int64_t)n_thr * n_area > COCO_MAX_LANES || !max_dets || !rec_thrs ||
-        !workspace || !rle_workspace_aligned(workspace) || (n_dt > 0 && (!perm || !rank || !dt_match || !dt_ignore || !dt_scores)))
+    const CocoAccumulateLayout L = coco_accumulate_layout(n_dt, n_area, n_max_dets);
+    if (!L.total || n_cat < 0 || n_rec < 1 || n_thr < 1 || (int64_t)n_thr * n_area > COCO_MAX_LANES || !max_dets || !rec_thrs ||
+        !workspace || !workspace_aligned_16(workspace) || (n_dt > 0 && (!perm || !rank || !dt_match || !dt_ignore || !dt_scores)))
         return PGR_ERR_INVALID_ARGUMENT;
     if (n_cat > 0 && (!seg_start || !npig || !precision || !scores || !recall)) return PGR_ERR_INVALID_ARGUMENT;
-    if ((int64_t)n_cat * n_area * n_max_dets > RLE_MAX_BLOCKS) return PGR_ERR_INVALID_ARGUMENT;
+    if ((int64_t)n_cat * n_area * n_max_dets > MAX_GRID_BLOCKS) return PGR_ERR_INVALID_ARGUMENT;
     CocoAccumulateParams P{};
     for (int32_t m = 0; m < n_max_dets; ++m) {
         if (max_dets[m] < 0) return PGR_ERR_INVALID_ARGUMENT;
         P.max_dets[m] = max_dets[m];
     }
     P.K = n_cat; P.A = n_area; P.M = n_max_dets; P.T = n_thr; P.R = n_rec;
-    if (workspace_bytes < need) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    if (workspace_bytes < L.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
     if (n_cat == 0) return PGR_OK;
     char* ws = static_cast<char*>(workspace);
-    const size_t cells = std::max<size_t>((size_t)n_area * n_max_dets * n_dt, 1);
-    auto* ws_tp = reinterpret_cast<int32_t*>(ws);
-    auto* ws_idx = reinterpret_cast<int32_t*>(ws + align_up(cells * sizeof(int32_t)));
-    auto* ws_pr = reinterpret_cast<double*>(ws + 2 * align_up(cells * sizeof(int32_t)));
+    auto* ws_tp = reinterpret_cast<int32_t*>(ws + L.tp);
+    auto* ws_idx = reinterpret_cast<int32_t*>(ws + L.idx);
+    auto* ws_pr = reinterpret_cast<double*>(ws + L.pr);
     coco_accumulate_kernel<<<(unsigned)(n_cat * n_area * n_max_dets), COCO_THREADS, 0, static_cast<hipStream_t>(stream_v)>>>(
         P, reinterpret_cast<const long long*>(perm), reinterpret_cast<const long long*>(seg_start), (long long)n_dt, rank, dt_match,
         dt_ignore, npig, rec_thrs, dt_scores, ws_tp, ws_idx, ws_pr, precision, scores, recall);

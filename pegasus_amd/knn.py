@@ -12,7 +12,6 @@ def dist2(points: torch.Tensor) -> torch.Tensor:
     points.  There is no CPU path."""
     if points.device.type != "cuda":
         raise RuntimeError("distCUDA2 needs a tensor on a HIP device (torch device 'cuda'); there is no CPU path")
-    L = _lib.lib()
     pts = points.detach().to(torch.float32).contiguous()
     if pts.dim() != 2 or pts.shape[1] != 3:
         raise ValueError("points must be [N,3]")
@@ -20,7 +19,7 @@ def dist2(points: torch.Tensor) -> torch.Tensor:
     out = torch.empty((n,), dtype=torch.float32, device=pts.device)
     if n == 0:
         return out
-    ws = torch.empty((L.pgr_knn_workspace_bytes(n),), dtype=torch.uint8, device=pts.device)
+    ws = _lib.workspace("pgr_knn", pts.device, n)
     _lib.call("pgr_knn_mean_dist2", pts.device, n, _lib.ptr(pts), _lib.ptr(out), _lib.ptr(ws), ws.numel())
     return out
 

@@ -143,7 +143,6 @@ def march(sdf, grid: Grid, stage_ms: Optional[dict] = None) -> Mesh:
     count and the emit pass: the only host wait.  ``stage_ms``: a dict that receives the GPU milliseconds of the
     "count" (count + scan) and "emit" passes."""
     import torch
-    L = _lib.lib()
     device = sdf.device
     if device.type != "cuda":
         raise RuntimeError("march needs a tensor on a HIP device; there is no CPU path")
@@ -151,11 +150,8 @@ def march(sdf, grid: Grid, stage_ms: Optional[dict] = None) -> Mesh:
         raise ValueError(f"sdf is {tuple(sdf.shape)}, the grid {grid.shape}")
     sdf = sdf.float().contiguous()
     g = grid.struct()
-    nbytes = L.pgr_march_workspace_bytes(grid.nx, grid.ny, grid.nz)
-    if nbytes == 0:
-        raise ValueError(f"grid {grid.shape}: every axis must hold 2..{MAX_AXIS} points")
+    ws = _lib.workspace("pgr_march", device, grid.nx, grid.ny, grid.nz)
     stream_t = torch.cuda.current_stream(device)
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
     counts = torch.zeros(2, dtype=torch.int64, device=device)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if stage_ms is not None else None
     if ev:

@@ -120,7 +120,6 @@ def render_depth(meshes: MeshSet, jobs: Sequence, K, size, margin=(0, 0), near: 
     device = meshes.device
     if device.type != "cuda":
         raise RuntimeError("render_depth needs a mesh set on a HIP device; there is no CPU path")
-    L = _lib.lib()
     J = len(jobs)
     Ks = _K_list(K, J)
     out = torch.empty((J, Hc, Wc), dtype=torch.float32, device=device)
@@ -129,10 +128,7 @@ def render_depth(meshes: MeshSet, jobs: Sequence, K, size, margin=(0, 0), near: 
     for j0 in range(0, J, per_call):
         chunk = jobs[j0:j0 + per_call]
         arr = mesh_jobs(meshes, chunk, np.stack(Ks[j0:j0 + per_call]), (mx, my))
-        nbytes = int(L.pgr_mesh_depth_workspace_bytes(len(chunk), arr))
-        if nbytes == 0:
-            raise ValueError("pgr_mesh_depth_workspace_bytes rejected the jobs")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        ws = _lib.workspace("pgr_mesh_depth", device, len(chunk), arr)
         count = torch.zeros(1, dtype=torch.int32, device=device)
         _lib.call("pgr_mesh_depth", device, _lib.ptr(meshes.vertices), meshes.vertices.shape[0], _lib.ptr(meshes.faces),
                   meshes.faces.shape[0], len(chunk), arr, Wc, Hc, float(near), _lib.ptr(out[j0:j0 + len(chunk)]), len(chunk),

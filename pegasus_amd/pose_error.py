@@ -203,7 +203,6 @@ def pose_errors(models: PoseErrorModels, obj_ids, R_est, t_est, R_gt, t_gt, K=No
     dev = models.device
     if dev.type != "cuda":
         raise RuntimeError("pose_errors needs models on a HIP device; there is no CPU path")
-    L = _lib.lib()
     out = torch.empty((P, _lib.PGR_POSE_ERRORS), dtype=torch.float32, device=dev)
     re_te = torch.empty((P, 2), dtype=torch.float64, device=dev)
     adi = torch.empty(P, dtype=torch.float32, device=dev) if "adi" in errors else None
@@ -215,10 +214,7 @@ def pose_errors(models: PoseErrorModels, obj_ids, R_est, t_est, R_gt, t_gt, K=No
             _lib.call("pgr_pose_errors", dev, _lib.ptr(models.vertices), models.vertices.shape[0], _lib.ptr(models.syms),
                       models.syms.shape[0], n, _job_ptr(part), _lib.ptr(out[j0:j0 + n]), _lib.ptr(re_te[j0:j0 + n]))
         if adi is not None:
-            nbytes = int(L.pgr_pose_adi_workspace_bytes(n, _job_ptr(part)))
-            if nbytes == 0:
-                raise ValueError("pgr_pose_adi_workspace_bytes rejected the jobs")
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            ws = _lib.workspace("pgr_pose_adi", dev, n, _job_ptr(part))
             _lib.call("pgr_pose_adi", dev, _lib.ptr(models.vertices), models.vertices.shape[0], n, _job_ptr(part),
                       _lib.ptr(adi[j0:j0 + n]), _lib.ptr(ws), ws.numel())
     res = {}

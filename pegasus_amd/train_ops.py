@@ -33,11 +33,10 @@ def image_loss_terms(x: torch.Tensor, y: torch.Tensor, lambda_dssim: float, want
     xc, yc = _image(x, "x"), _image(y, "y")
     if xc.shape != yc.shape or xc.device != yc.device:
         raise ValueError(f"image loss: x {tuple(xc.shape)} on {xc.device} vs y {tuple(yc.shape)} on {yc.device}")
-    L = _lib.lib()
     _, H, W = xc.shape
     out = torch.empty(3, dtype=torch.float32, device=xc.device)
     grad = torch.empty_like(xc) if want_grad else None
-    ws = torch.empty(L.pgr_image_loss_workspace_bytes(H, W), dtype=torch.uint8, device=xc.device)
+    ws = _lib.workspace("pgr_image_loss", xc.device, H, W)
     _lib.call("pgr_image_loss", xc.device, _lib.ptr(xc), _lib.ptr(yc), H, W, float(lambda_dssim), _lib.ptr(out), _lib.ptr(grad),
               _lib.ptr(ws), ws.numel())
     return out, grad
@@ -93,11 +92,10 @@ def masked_image_loss_terms(x, alpha, y, mask, bg, lambda_dssim: float, lambda_a
         if not isinstance(bg, torch.Tensor) or bg.numel() != 3 or bg.device != dev:
             raise ValueError(f"bg: expected 3 values on {dev}, got {getattr(bg, 'shape', type(bg))}")
         bc = bg.detach().to(torch.float32).reshape(3).contiguous()
-    L = _lib.lib()
     out = torch.empty(4, dtype=torch.float32, device=dev)
     grad = torch.empty_like(xc) if want_grad else None
     grad_a = torch.empty((1, H, W), dtype=torch.float32, device=dev) if (want_grad_alpha and ac is not None) else None
-    ws = torch.empty(L.pgr_image_loss_masked_workspace_bytes(H, W), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace("pgr_image_loss_masked", dev, H, W)
     p = _lib.ptr
     _lib.call("pgr_image_loss_masked", dev, p(xc), p(yc), p(mc), p(bc), p(ac), H, W, float(lambda_dssim), float(lambda_alpha),
               p(out), p(grad), p(grad_a), p(ws), ws.numel())

@@ -144,6 +144,34 @@ def test_pose_errors_never_read_outside_a_job_and_repeat_bit_for_bit(calls, refe
 
 
 @pytest.mark.gpu
+def test_adi_stays_inside_a_workspace_of_the_size_it_asks_for(calls, references):
+    """pgr_pose_adi called directly, its workspace exactly pgr_pose_adi_workspace_bytes long between guard bytes and its output
+    between guard values: eight jobs of the interleaved call, seven of one tile of queries and one of four (1000 vertices), so
+    that a job's partial sums start where the previous job's end."""
+    import torch
+    from pegasus_amd import _lib
+    from pegasus_amd.pose_error import _job_ptr, pose_jobs
+    guard = 4096
+    call = PC.subset(calls["interleaved"], 8)
+    assert sorted(len(call["objects"][int(o)][0]) for o in set(call["obj_ids"])) == [65, 256, 1000]
+    models = build_models(call)
+    jobs = pose_jobs(models, 2 * np.asarray(call["obj_ids"]), call["R_est"], call["t_est"], call["R_gt"], call["t_gt"], call["K"])
+    n, dev = len(jobs), models.device
+    nbytes = int(_lib.lib().pgr_pose_adi_workspace_bytes(n, _job_ptr(jobs)))
+    assert nbytes == 256                                                     # 11 float64 partial sums, one 256-byte unit
+    ws = torch.full((nbytes + 2 * guard,), 0xA5, dtype=torch.uint8, device=dev)
+    out = torch.full((n + 2 * guard,), -7.0, dtype=torch.float32, device=dev)
+    _lib.call("pgr_pose_adi", dev, _lib.ptr(models.vertices), models.vertices.shape[0], n, _job_ptr(jobs), _lib.ptr(out[guard:]),
+              _lib.ptr(ws[guard:]), nbytes)
+    torch.cuda.synchronize()
+    assert (ws[:guard] == 0xA5).all() and (ws[guard + nbytes:] == 0xA5).all(), "workspace guard overwritten"
+    assert (out[:guard] == -7.0).all() and (out[guard + n:] == -7.0).all(), "output guard overwritten"
+    got = out[guard:guard + n].cpu().numpy().astype(np.float64)
+    assert np.array_equal(got, run(models, call, ("adi",))["adi"])             # the wrapper's call, bit for bit
+    assert (np.abs(got - references["interleaved"]["adi"][:n]) <= TOL["adi"]).all()
+
+
+@pytest.mark.gpu
 def test_scalar_functions_agree_with_the_batched_call(calls):
     from pegasus_amd import pose_error as PE
     call = calls["s_sweep"]
