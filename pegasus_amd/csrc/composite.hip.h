@@ -596,28 +596,15 @@ constexpr int ORDER_BINS = NUM_XCD * ORDER_CLASSES_USED;
 // order_state layout (uint32): [ORDER_BINS] counters -> cursors, then [SORT_TIERS] lengths of the sort queues, then the
 // ticket of tile_scan_kernel's workgroups (the last one turns the counters into cursors)
 // Sort queues: every non-empty list of a view that did not overflow is one uint4 (item, first instance, keys, 0) in the
-// queue of its tier -- 1..2048 keys, 2049..4096, 4097..8192, 8193..SORT_WINDOW_MAX (round 6: the windowed sort), longer
-// (round 6: the split pre-pass, whose depth segments join the SEGMENT queue of the 4097..8192 tier's kernel), and the open-ended
+// queue of its tier (SortTier, pgr_common.h) -- 1..2048 keys, 2049..4096, 4097..8192, 8193..SORT_WINDOW_MAX (round 6: the
+// windowed sort), longer (round 6: the split pre-pass, whose depth segments join the SEGMENT queue of the 4097..8192 tier's kernel), and the open-ended
 // kernel's queue, which order_scatter fills only in one- and two-view calls and which otherwise receives what the windowed
 // sort and the split pre-pass reject: one queue and one sort launch each.  A sort
 // workgroup learns its list from that one word (the view's table entry arrives beside it through the scalar cache)
 // instead of chasing item -> view table -> ranges -> keys; and a launch has no workgroups for empty tiles.
-constexpr int SORT_TIERS = 6;
-constexpr int SORT_WINDOW_MAX = 2 * (8192 - 256);   // tilebin.hip.h: two windows of the windowed sort's 8192-key image
 constexpr int ORDER_DONE_WORD = ORDER_BINS + SORT_TIERS;
 constexpr int ORDER_SEG_WORD = ORDER_DONE_WORD + 1; // entries of the segment queue
 constexpr int ORDER_STATE_WORDS = ORDER_BINS + SORT_TIERS + 2;
-
-#ifndef PGR_WINDOW_TIER
-#define PGR_WINDOW_TIER 1        // 0: no windowed sort (A/B builds): lists of 8193..15872 keys take the next tier's path
-#endif
-#ifndef PGR_SPLIT_TIER
-#define PGR_SPLIT_TIER 1         // 0: no split pre-pass (A/B builds): lists beyond the windowed sort go to the open-ended kernel
-#endif
-__device__ __forceinline__ int sort_tier(uint32_t len) {
-    const int beyond = PGR_SPLIT_TIER ? 4 : 5;
-    return len > (uint32_t)SORT_WINDOW_MAX ? beyond : (len > 8192u ? (PGR_WINDOW_TIER ? 3 : beyond) : (len > 4096u ? 2 : (len > 2048u ? 1 : 0)));
-}
 
 __device__ __forceinline__ int xcd_of_tile(int tile, int grid_x) { return (tile / grid_x / ORDER_BAND_ROWS) % NUM_XCD; }
 
@@ -660,7 +647,7 @@ __global__ __launch_bounds__(256) void order_scatter_kernel(const ViewEntry* __r
             tier = sort_tier(len);
             // a launch of one or two views has a handful of lists per long tier: three launches that each wait for their
             // longest list.  They all go to the open-ended tier's kernel, which sorts any length.
-            if (merge_long_tiers && tier > 0) tier = SORT_TIERS - 1;
+            if (merge_long_tiers && tier != TIER_SHORT) tier = TIER_OPEN;
             queue_rank = atomicAdd(&n_queue_s[tier], 1u);
         }
     }

@@ -4,7 +4,7 @@
 // Pipeline of one batch of views of one scene (all stages enqueued on the caller's stream, no host
 // round trip until the end-of-batch status read):
 //   per view : pack_camera, preprocess                           (preprocess.hip.h)
-//   batch    : bin_count -> tile_scan -> bin_scatter -> work order -> tile_sort(_large)   (tilebin.hip.h)
+//   batch    : bin_count -> tile_scan -> bin_scatter -> work order -> tile_sort, one launch per tier   (tilebin.hip.h, tilesort.hip.h)
 //   batch    : composite_wave over every (view, tile, half) work item, longest lists first (composite.hip.h)
 #include <hip/hip_runtime.h>
 
@@ -29,6 +29,7 @@
 #include "poseerr.hip.h"
 #include "preprocess.hip.h"
 #include "tilebin.hip.h"
+#include "tilesort.hip.h"
 #include "train.hip.h"
 
 namespace pgr {
@@ -477,32 +478,34 @@ static int32_t forward_batch_impl(const PgrScene* scene, int n_views, const PgrC
     const bool merge_long = n_views <= SMALL_BATCH_VIEWS;
     order_scatter_kernel<<<og, 256, 0, stream>>>(view_table, L.tiles, L.grid_x, order_state, work_order, sort_queue,
                                                  (uint32_t)items, merge_long ? 1 : 0, layers ? 1 : 0);
-    const uint32_t* n_queue = order_state + ORDER_BINS;
-    uint32_t* const n_open = order_state + ORDER_BINS + 5;
+    // a tier's queue and its length word (SortTier, pgr_common.h); the segment queue lies behind the tiers' queues
+    const auto queue_of = [&](SortTier tier) { return sort_queue + (size_t)tier * qs; };
+    const auto n_queue_of = [&](SortTier tier) { return order_state + ORDER_BINS + tier; };
+    uint4* const seg_queue = sort_queue + (size_t)SORT_TIERS * qs;
+    uint32_t* const n_seg = order_state + ORDER_SEG_WORD;
     if (!merge_long) {
         // 8193..15872 keys: the windowed sort (two workgroups per CU); longer: the split pre-pass, whose depth segments the
         // 512 x 16 tier's kernel sorts from the segment queue; what either rejects joins the open-ended kernel's queue
         // (one launch: its first workgroups run the split pre-pass, the windowed sort fills the chip beside them)
         const int part_blocks = std::min(items, 1024);          // every third workgroup: 3 x part_blocks in all, two thirds sort
         tile_sort_window_kernel<<<3 * part_blocks, SORT_WINDOW_THREADS, 0, stream>>>(
-            bin_table, L.tiles, sort_queue + 3 * qs, n_queue + 3, sort_queue + 5 * qs, n_open, (uint32_t)part_blocks,
-            sort_queue + 4 * qs, n_queue + 4, sort_queue + SORT_TIERS * qs, order_state + ORDER_SEG_WORD, (uint32_t)B.seg_cap);
+            bin_table, L.tiles, queue_of(TIER_WINDOW), n_queue_of(TIER_WINDOW), queue_of(TIER_OPEN), n_queue_of(TIER_OPEN),
+            (uint32_t)part_blocks, queue_of(TIER_SPLIT), n_queue_of(TIER_SPLIT), seg_queue, n_seg, (uint32_t)B.seg_cap);
     }
     // the open-ended kernel: every long list of a one- / two-view call; in a batch only what the two kernels above rejected
     // (piled-up depths: rare) -- a handful of workgroups then, 512 of them cost 20 us to find an empty queue
     tile_sort_long_kernel<1024, 16, true><<<merge_long ? std::min(items, 512) : 32, 1024, 0, stream>>>(
-        bin_table, L.tiles, sort_queue + 5 * qs, n_queue + 5);
+        bin_table, L.tiles, queue_of(TIER_OPEN), n_queue_of(TIER_OPEN));
     if (!merge_long) {
         // 4097..8192 keys: 512 threads x 16 keys over 3584 buckets = 80 KiB, TWO workgroups per CU (round 5: the position-owned
         // ranking needs no index image, so the bucket count is free; 1024 x 8 over 8192 buckets = 96 KiB held a CU alone);
         // the same launch sorts the split pre-pass's segments behind its own lists
         tile_sort_long_kernel<512, 16, false, SORT_T2_BUCKETS, 4, true><<<std::min(items, 2048), 512, 0, stream>>>(
-            bin_table, L.tiles, sort_queue + 2 * qs, n_queue + 2, sort_queue + SORT_TIERS * qs, order_state + ORDER_SEG_WORD,
-            (uint32_t)B.seg_cap);
+            bin_table, L.tiles, queue_of(TIER_8K), n_queue_of(TIER_8K), seg_queue, n_seg, (uint32_t)B.seg_cap);
         tile_sort_long_kernel<512, 8, false><<<std::min(items, 2048), 512, 0, stream>>>(
-            bin_table, L.tiles, sort_queue + qs, n_queue + 1);
+            bin_table, L.tiles, queue_of(TIER_4K), n_queue_of(TIER_4K));
     }
-    tile_sort_kernel<<<items, SORT_THREADS, 0, stream>>>(bin_table, L.tiles, sort_queue, n_queue);
+    tile_sort_kernel<<<items, SORT_THREADS, 0, stream>>>(bin_table, L.tiles, queue_of(TIER_SHORT), n_queue_of(TIER_SHORT));
     mark(4);
     // ---- stage 4: compositing of every (view, tile, quarter) work item in ONE launch; with `semantic` the same
     // walk also produces the objects-only semantic image

@@ -89,6 +89,36 @@ __device__ __forceinline__ int length_class(uint32_t len) {
     return msb * 8 + (int)frac + 1;   // 1..256 -> clamp below
 }
 
+// Sort tiers: the per-tile sort (tilesort.hip.h) has one queue and one launch per list-length tier.  order_scatter_kernel
+// (composite.hip.h) files every non-empty list under sort_tier(length); the queues lie one behind the other in the
+// workspace, their lengths one behind the other in order_state.
+enum SortTier : int {
+    TIER_SHORT = 0,              // 1 .. SORT_SHORT_MAX keys
+    TIER_4K,                     // .. SORT_4K_MAX
+    TIER_8K,                     // .. SORT_8K_MAX; its kernel also sorts the depth segments the split pre-pass cuts
+    TIER_WINDOW,                 // .. SORT_WINDOW_MAX: the windowed sort
+    TIER_SPLIT,                  // longer: the split pre-pass
+    TIER_OPEN,                   // the open-ended kernel: any length (one- and two-view calls; what the two above reject)
+};
+constexpr int SORT_TIERS = TIER_OPEN + 1;
+constexpr int SORT_SHORT_MAX = 2048;
+constexpr int SORT_4K_MAX = 4096;
+constexpr int SORT_8K_MAX = 8192;
+constexpr int SORT_WINDOW_MAX = 2 * (8192 - 256);   // two windows of the windowed sort's 8192-key image
+
+#ifndef PGR_WINDOW_TIER
+#define PGR_WINDOW_TIER 1        // 0: no windowed sort (A/B builds): lists of 8193..15872 keys take the next tier's path
+#endif
+#ifndef PGR_SPLIT_TIER
+#define PGR_SPLIT_TIER 1         // 0: no split pre-pass (A/B builds): lists beyond the windowed sort go to the open-ended kernel
+#endif
+__device__ __forceinline__ int sort_tier(uint32_t len) {
+    constexpr int beyond = PGR_SPLIT_TIER ? TIER_SPLIT : TIER_OPEN;
+    if (len > (uint32_t)SORT_WINDOW_MAX) return beyond;
+    if (len > (uint32_t)SORT_8K_MAX) return PGR_WINDOW_TIER ? TIER_WINDOW : beyond;
+    return len > (uint32_t)SORT_4K_MAX ? TIER_8K : (len > (uint32_t)SORT_SHORT_MAX ? TIER_4K : TIER_SHORT);
+}
+
 constexpr int PRE_BLOCK = 256;               // Gaussians per preprocess workgroup
 
 }  // namespace pgr

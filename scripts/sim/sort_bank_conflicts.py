@@ -1,4 +1,4 @@
-"""Offline simulation of the LDS bank behaviour of the per-tile bucket sort (pegasus_amd/csrc/tilebin.hip.h
+"""Offline simulation of the LDS bank behaviour of the per-tile bucket sort (pegasus_amd/csrc/tilesort.hip.h
 bucket_sort_tile) on the real lists of a full-size view, for the layouts round 5 considered (round-4 verdict item 3).
 
 Per wave-instruction a wave64 LDS access is served in lane groups (MI355X_MICROARCH.md, LDS table): 4-byte accesses in two

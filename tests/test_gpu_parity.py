@@ -418,7 +418,7 @@ def test_spatial_order_does_not_change_frames(gpu_device):
 @pytest.mark.parametrize("n,spread", [(120000, 0.05), (300000, 0.08)])
 def test_very_long_lists_depth_partitioned(oracle, gpu_device, n, spread):
     """Lists of 20-100 k entries with smoothly spread depths: the sort partitions them by depth through the alt
-    buffer and sorts every < 16384-key segment in LDS (tilebin.hip.h partition_sort_long)."""
+    buffer and sorts every < 16384-key segment in LDS (tilesort.hip.h partition_sort_long)."""
     rng = np.random.default_rng(n)
     cloud, views = scenes.scene_c1(seed=4, n=n)
     cloud.xyz[:] = rng.normal(0, spread, size=(n, 3)).astype(np.float32)
@@ -466,7 +466,7 @@ def test_tie_index_order_on_long_lists(oracle, gpu_device, n, spread, equal):
 
 @pytest.mark.parametrize("n,pairs", [(9000, 300), (12000, 40), (15800, 1500)])
 def test_windowed_sort_with_scattered_depth_ties(oracle, gpu_device, n, pairs):
-    """The windowed sort (8193..15 872 keys, tilebin.hip.h window_sort_tile) in a three-view batch with `pairs` groups of two
+    """The windowed sort (8193..15 872 keys, tilesort.hip.h window_sort_tile) in a three-view batch with `pairs` groups of two
     or three Gaussians at exactly equal depth spread over the list (a few keys per bucket share their depth: the in-bucket
     tie-break by the caller's tie_index runs, the list is NOT rejected) -- positions and tie indices both shuffled."""
     import torch
