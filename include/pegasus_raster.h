@@ -371,6 +371,20 @@ size_t pgr_knn_workspace_bytes(int32_t n);
 int32_t pgr_knn_mean_dist2(int32_t n, const float *xyz, float *out, void *workspace, size_t workspace_bytes,
                            void *stream);
 
+/* How many points lie within `radius` of every point, the point itself included (open3d's remove_radius_outlier, which
+ * keeps point i iff counts[i] > nb_points: the reference's load_ply(clean_pcd=True) and denoise_point_cloud,
+ * /root/reference/src/gs/gaussian_model.py:238-247,633-651).  Point j counts for point i iff
+ * ((dx*dx) + dy*dy) + dz*dz < radius*radius, evaluated in float64 with every operation rounded on its own (the float32
+ * coordinates widened exactly, radius*radius rounded once) and compared STRICTLY.  Counting stops at `cap` hits:
+ * counts[i] = min(count_i, cap); cap = n gives exact counts, cap = nb_points + 1 is all the filter needs.  A sparse grid with
+ * cells of about `radius` is built on the device, in storage proportional to n wherever the points lie.  Results are exact
+ * integers, identical from run to run.  The caller's contract, which the entry cannot check: every coordinate is finite and
+ * |x| / radius < 2^30.  `xyz` [n,3] and `counts` [n] are device pointers; workspace (16-byte aligned) of
+ * pgr_radius_count_workspace_bytes(n) bytes (0 for n < 0).  n == 0 returns PGR_OK without a launch. */
+size_t pgr_radius_count_workspace_bytes(int32_t n);
+int32_t pgr_radius_count(int32_t n, const float *xyz, double radius, int32_t cap, int32_t *counts, void *workspace,
+                         size_t workspace_bytes, void *stream);
+
 /* Object meshes from a trained model's rendered views (pegasus_amd/mesh.py; replaces the open3d alpha shape of the
  * reference's reconstruction step).  A regular grid: point (i,j,k) sits at origin + voxel*(i,j,k); a field over it is
  * float32 [nz,ny,nx], x fastest.  Every axis holds 2 .. 1024 points.  Results are identical from run to run. */

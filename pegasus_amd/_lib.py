@@ -211,6 +211,9 @@ SYMBOLS = {
                                     C.c_void_p, C.c_void_p]),
     "pgr_knn_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "pgr_knn_mean_dist2": (C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pgr_radius_count_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "pgr_radius_count": (C.c_int32, [C.c_int32, C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
+                                     C.c_void_p]),
     "pgr_quantize_frame": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),
     "pgr_pack_frames": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

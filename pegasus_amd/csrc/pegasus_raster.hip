@@ -28,6 +28,7 @@
 #include "pgr_common.h"
 #include "poseerr.hip.h"
 #include "preprocess.hip.h"
+#include "radius.hip.h"
 #include "tilebin.hip.h"
 #include "tilesort.hip.h"
 #include "train.hip.h"
@@ -1071,6 +1072,52 @@ int32_t pgr_knn_mean_dist2(int32_t n, const float* xyz, float* out, void* worksp
     knn_scatter_kernel<<<blocks, 256, 0, stream>>>(n, xyz, grid, count, sorted);
     knn_search_kernel<<<blocks, 256, 0, stream>>>(n, grid, start, sorted, out);
     return hip_ok(hipGetLastError(), "knn launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+// ---- radius neighbour counts (open3d's remove_radius_outlier; radius.hip.h) ---------------------------------------------
+namespace {
+struct RadiusLayout { size_t total_word, slots, begin, point_slot, sorted, total; size_t n_slots; };
+RadiusLayout radius_layout(int32_t n) {
+    RadiusLayout R{};
+    R.n_slots = RADIUS_BLOCK;                                  // a power of two, a multiple of the block, at least 2 n
+    while (R.n_slots < 2 * (size_t)(n > 0 ? n : 0)) R.n_slots *= 2;
+    Carver c;
+    R.total_word = c.take(sizeof(uint32_t));
+    R.slots = c.take(R.n_slots * sizeof(RadiusSlot));
+    R.begin = c.take(R.n_slots * sizeof(uint32_t));
+    R.point_slot = c.take((size_t)(n > 0 ? n : 1) * sizeof(uint32_t));
+    R.sorted = c.take((size_t)(n > 0 ? n : 1) * sizeof(float4));
+    R.total = c.off;
+    return R;
+}
+}  // namespace
+
+size_t pgr_radius_count_workspace_bytes(int32_t n) { return n < 0 ? 0 : radius_layout(n).total; }
+
+int32_t pgr_radius_count(int32_t n, const float* xyz, double radius, int32_t cap, int32_t* counts, void* workspace,
+                         size_t workspace_bytes, void* stream_v) {
+    if (n < 0 || cap < 1 || !std::isfinite(radius) || !(radius > 0.0)) return PGR_ERR_INVALID_ARGUMENT;
+    if (n == 0) return PGR_OK;
+    if (!xyz || !counts || !workspace || !workspace_aligned_16(workspace)) return PGR_ERR_INVALID_ARGUMENT;
+    const RadiusLayout R = radius_layout(n);
+    if (workspace_bytes < R.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    char* ws = static_cast<char*>(workspace);
+    auto* total = reinterpret_cast<uint32_t*>(ws + R.total_word);
+    auto* slots = reinterpret_cast<RadiusSlot*>(ws + R.slots);
+    auto* begin = reinterpret_cast<uint32_t*>(ws + R.begin);
+    auto* point_slot = reinterpret_cast<uint32_t*>(ws + R.point_slot);
+    auto* sorted = reinterpret_cast<float4*>(ws + R.sorted);
+    // the running total and the table lie one behind the other: one memset
+    if (!hip_ok(hipMemsetAsync(total, 0, R.begin - R.total_word, stream), "memset radius table")) return PGR_ERR_LAUNCH_FAILURE;
+    const double inv_h = 1.0 / (radius * RADIUS_CELL_MARGIN), r2 = radius * radius;
+    const uint32_t mask = (uint32_t)(R.n_slots - 1);
+    const int blocks = (n + RADIUS_BLOCK - 1) / RADIUS_BLOCK;
+    radius_insert_kernel<<<blocks, RADIUS_BLOCK, 0, stream>>>(n, xyz, inv_h, slots, mask, point_slot);
+    radius_ranges_kernel<<<(unsigned)(R.n_slots / RADIUS_BLOCK), RADIUS_BLOCK, 0, stream>>>(slots, begin, total);
+    radius_scatter_kernel<<<blocks, RADIUS_BLOCK, 0, stream>>>(n, xyz, point_slot, begin, sorted);
+    radius_count_kernel<<<blocks, RADIUS_BLOCK, 0, stream>>>(n, sorted, slots, begin, mask, inv_h, r2, cap, counts);
+    return hip_ok(hipGetLastError(), "radius count launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
 }
 
 // ---- object meshes: TSDF fusion of rendered views, marching tetrahedra (mesh.hip.h) ------------------------------------

@@ -121,9 +121,12 @@ class GaussianModel:
         return m
 
     def load_ply(self, path, clean_pcd: bool = False):
-        if clean_pcd:
-            raise NotImplementedError("clean_pcd needs open3d's radius-outlier filter (offline asset step)")
         v = read_ply_vertices(path)
+        if clean_pcd:
+            # the reference's radius-outlier filter on the file's positions, before anything else is kept (reference :238-247)
+            from .outliers import radius_outlier_mask
+            pos = np.stack([v["x"], v["y"], v["z"]], axis=1).astype(np.float32)
+            v = v[radius_outlier_mask(torch.from_numpy(pos).to(self.device), 16, 0.03).cpu().numpy()]
         names = v.dtype.names
         xyz = np.stack([v["x"], v["y"], v["z"]], axis=1)
         f_dc = np.stack([v["f_dc_0"], v["f_dc_1"], v["f_dc_2"]], axis=1)[:, None, :]           # [N,1,3]
@@ -355,13 +358,22 @@ class GaussianModel:
         return self.__dict__
 
     def mask_points(self, mask):
+        """Keeps the rows where ``mask`` is True; with an optimizer set, in its parameters and their Adam moments too
+        (reference :598-623)."""
         if self.optimizer:
-            raise NotImplementedError("optimizer state pruning belongs to training (out of scope)")
-        for k in ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation"):
-            setattr(self, k, getattr(self, k)[mask])
+            self._set_params(self._prune_optimizer(mask))
+        else:
+            for k in ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation"):
+                setattr(self, k, getattr(self, k)[mask])
         for k in ("xyz_gradient_accum", "denom", "max_radii2D"):
             if len(getattr(self, k)) != 0:
                 setattr(self, k, getattr(self, k)[mask])
+
+    def denoise_point_cloud(self, nb_points=16, radius=0.05, debug=False):
+        """Drops the Gaussians with at most ``nb_points`` positions within ``radius`` of their own, itself included
+        (reference :633-651).  ``debug`` opened a viewer there; there is none here and it is ignored."""
+        from .outliers import radius_outlier_mask
+        self.mask_points(radius_outlier_mask(self.get_xyz.detach(), nb_points, radius))
 
     def translate_selected_points(self, mask, t):
         translation = torch.zeros(self._xyz.shape, device=t.device)

@@ -362,8 +362,9 @@ def models_info(mesh: Mesh, symmetries_discrete=None, symmetries_continuous=None
 
 
 # ---- CLI ------------------------------------------------------------------------------------------------------------
-def load_model(model_dir, iteration: int = -1):
-    """The GaussianModel saved under <model_dir>/point_cloud/iteration_N/point_cloud.ply (N = the largest for -1)."""
+def load_model(model_dir, iteration: int = -1, clean_pcd: bool = False):
+    """The GaussianModel saved under <model_dir>/point_cloud/iteration_N/point_cloud.ply (N = the largest for -1);
+    ``clean_pcd``: without its floaters (GaussianModel.load_ply)."""
     from .gaussian_model import GaussianModel
     from .ply_io import read_ply_vertices
     from .scene import searchForMaxIteration
@@ -373,7 +374,7 @@ def load_model(model_dir, iteration: int = -1):
     n_rest = sum(1 for n in read_ply_vertices(path).dtype.names if n.startswith("f_rest_"))
     degree = int(round(math.sqrt((n_rest + 3) / 3))) - 1
     g = GaussianModel(degree)
-    g.load_ply(path)
+    g.load_ply(path, clean_pcd=clean_pcd)
     return g
 
 
@@ -388,6 +389,8 @@ def _parser():
     p.add_argument("--resolution", type=int, default=256)
     p.add_argument("--n_views", type=int, default=96)
     p.add_argument("--image_size", type=int, default=512)
+    p.add_argument("--clean_pcd", action="store_true",
+                   help="drop the model's floaters first: the radius-outlier filter (16 points, 0.03) of load_ply")
     p.add_argument("--sym_continuous", type=float, nargs=6, action="append", metavar=("AX", "AY", "AZ", "OX", "OY", "OZ"),
                    help="a continuous rotational symmetry: axis and a point on it, in model units (repeatable)")
     p.add_argument("--sym_discrete", type=float, nargs=16, action="append", metavar="M",
@@ -408,7 +411,7 @@ def scaled_symmetries(sym_discrete, sym_continuous, scale: float):
 
 def main(argv: Optional[Sequence[str]] = None) -> int:
     a = _parser().parse_args(argv)
-    mesh = extract_mesh(load_model(a.model_path, a.iteration), resolution=a.resolution, n_views=a.n_views,
+    mesh = extract_mesh(load_model(a.model_path, a.iteration, a.clean_pcd), resolution=a.resolution, n_views=a.n_views,
                         image_size=a.image_size)
     name = f"obj_{a.obj_id:06d}"
     out = Path(a.out)
