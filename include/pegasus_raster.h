@@ -506,6 +506,46 @@ size_t pgr_pose_adi_workspace_bytes(int32_t n_jobs, const PgrPoseErrorJob *jobs)
 int32_t pgr_pose_adi(const float *vertices, int64_t n_vertices, int32_t n_jobs, const PgrPoseErrorJob *jobs, float *adi,
                      void *workspace, size_t workspace_bytes, void *stream);
 
+/* Minimal oriented bounding boxes by open3d's rule (OrientedBoundingBox::CreateFromPointsMinimal: one candidate box per
+ * triangle, normally the convex hull's) for n_jobs jobs in one call (pegasus_amd/obb.py; rules in
+ * pegasus_amd/csrc/obb.hip.h and DESIGN.md section 16).  A job is a range of the device array `points` (float32
+ * [n_points,3]) and a range of the device array `triangles` (int32 [n_triangles,3], indices relative to the job's
+ * point_first).  Triangle (i0,i1,i2) spans the frame a = p[i0], u = p[i1]-a, w = u x (p[i2]-a), v = w x u, normalised, all in
+ * float64; its candidate is the box of all the job's points in that frame.  Outputs (device): `volumes` float64
+ * [n_triangles] (written for every triangle of every job, not finite for a degenerate triangle or a job that holds an Inf or
+ * NaN point), and per job `best` int32 (the finite volume that is smallest, the lowest index within the job among equal
+ * ones, -1 if there is none) and `lohi` float64 [n_jobs,6] (min then max of the chosen candidate's projections; NaN for -1).
+ * No float atomics: equal bytes from run to run, for a job alone or in a batch, and however its points are cut.
+ * PGR_ERR_INVALID_ARGUMENT before anything is enqueued: NULL arrays that are needed, a negative count, a range that leaves
+ * its array, triangles over no points.  The kernels do NOT clamp an index: when `triangles_host` (a host copy of
+ * `triangles`, may be NULL) is given, every index of every job is checked against [0, point_count) here; a caller that passes
+ * NULL has checked them itself.  n_jobs == 0: PGR_OK, no launch; a job without triangles: best = -1.  `jobs` is a host array.
+ * Workspace (16-byte aligned): pgr_obb_candidates_workspace_bytes(n_jobs, jobs) device bytes; host-only, 0 for n_jobs <= 0,
+ * NULL jobs, a negative count or triangles over no points.  A job's points go through LDS PGR_OBB_POINT_TILE at a time,
+ * its triangles PGR_OBB_TRI_TILE per workgroup (tests/obb_cases.py is built around both). */
+#define PGR_OBB_TRI_TILE 256
+#define PGR_OBB_POINT_TILE 512
+typedef struct PgrObbJob {
+    int32_t point_first, point_count;
+    int32_t tri_first, tri_count;
+} PgrObbJob;
+size_t pgr_obb_candidates_workspace_bytes(int32_t n_jobs, const PgrObbJob *jobs);
+int32_t pgr_obb_candidates(const float *points, int64_t n_points, const int32_t *triangles, int64_t n_triangles,
+                           const int32_t *triangles_host, int32_t n_jobs, const PgrObbJob *jobs, double *volumes,
+                           int32_t *best, double *lohi, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The two points of every job's point range that lie farthest apart (the toolkit's misc.calc_pts_diameter, exact brute
+ * force): d2(i,j) = fma(dz, dz, fma(dy, dy, dx dx)) of p[j] - p[i] in float64 over i < j.  `pair` device int32 [n_jobs,2]
+ * receives the pair of largest d2 (indices within the job, the lexicographically lowest pair among equal ones), `d2` device
+ * float64 [n_jobs] its value.  One point: pair (0,0), d2 0; no point: pair (-1,-1), d2 0.  A NaN distance is never chosen.
+ * The jobs' triangle ranges are not read.  Equal bytes from run to run and for a job alone or in a batch.  Argument checks
+ * as pgr_obb_candidates makes them for the points; workspace (16-byte aligned) of pgr_point_diameter_workspace_bytes device
+ * bytes (host-only; 0 for n_jobs <= 0, NULL jobs or a negative count).  Points are walked PGR_DIAMETER_TILE at a time. */
+#define PGR_DIAMETER_TILE 256
+size_t pgr_point_diameter_workspace_bytes(int32_t n_jobs, const PgrObbJob *jobs);
+int32_t pgr_point_diameter(const float *points, int64_t n_points, int32_t n_jobs, const PgrObbJob *jobs, int32_t *pair,
+                           double *d2, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Gradients returned by pgr_backward (device pointers, any may be NULL = not wanted). */
 typedef struct PgrGradOutputs {
     float *means2d;              /* [n,3] screen-space mean, NDC-scaled (what viewspace_points.grad receives) */

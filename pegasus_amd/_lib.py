@@ -160,6 +160,14 @@ class PgrPoseErrorJob(C.Structure):
 
 PGR_POSE_ERRORS = 6          # mssd, mspd, add, proj, re, te
 PGR_POSE_SYM_CHUNK = 4       # include/pegasus_raster.h PGR_POSE_SYM_CHUNK
+
+
+class PgrObbJob(C.Structure):
+    _fields_ = [("point_first", C.c_int32), ("point_count", C.c_int32), ("tri_first", C.c_int32), ("tri_count", C.c_int32)]
+
+
+# include/pegasus_raster.h: the tiles of the box and diameter kernels (tests/obb_cases.py is built around them)
+PGR_OBB_TRI_TILE, PGR_OBB_POINT_TILE, PGR_DIAMETER_TILE = 256, 512, 256
 # include/pegasus_raster.h: the shapes at which the mask kernels change path (tests/test_coco_host.py holds them against it)
 PGR_RLE_WORD_ROWS, PGR_RLE_TILE_COLS, PGR_RLE_BLOCK_ROWS = 32, 256, 128
 PGR_RLE_DECODE_CHUNK, PGR_RLE_DECODE_MIN_SLICE, PGR_RLE_DECODE_MAX_SLICES, PGR_MASK_OVERLAP_CHUNK = 256, 16384, 64, 16384
@@ -246,6 +254,13 @@ SYMBOLS = {
     "pgr_pose_adi_workspace_bytes": (C.c_size_t, [C.c_int32, C.POINTER(PgrPoseErrorJob)]),
     "pgr_pose_adi": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(PgrPoseErrorJob), C.c_void_p, C.c_void_p,
                                  C.c_size_t, C.c_void_p]),
+    "pgr_obb_candidates_workspace_bytes": (C.c_size_t, [C.c_int32, C.POINTER(PgrObbJob)]),
+    "pgr_obb_candidates": (C.c_int32, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
+                                       C.POINTER(PgrObbJob), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                       C.c_void_p]),
+    "pgr_point_diameter_workspace_bytes": (C.c_size_t, [C.c_int32, C.POINTER(PgrObbJob)]),
+    "pgr_point_diameter": (C.c_int32, [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(PgrObbJob), C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_size_t, C.c_void_p]),
     "pgr_mask_rle_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "pgr_mask_rle_count": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
                                        C.c_void_p]),

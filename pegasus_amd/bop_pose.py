@@ -4,8 +4,9 @@ Reference (the surviving copy of the writer): /root/reference/src/tools/pegasus_
 For every frame and object:  T_m2c = T_w2c @ T_m2w  with  T_w2c[:3,:3] = cam.R.T, T_w2c[:3,3] = cam.T
 (pegasus_working.py:464-466);  scene_gt entry (pegasus_working.py:565-576) = {"cam_R_m2c": 9 floats row-major,
 "cam_t_m2c": 3 floats, "T_w2c": 16, "T_m2w": 16, "obj_id", "bullet_obj_id"} and -- when the caller supplies the object's
-model-space bounding box (the reference takes the 8 corners of the mesh's minimal oriented box from open3d, which is out of
-scope here, in the NDDS corner order of pegasus_working.py:470-495) -- "3d_bounding_box_model_coord" [8,3],
+model-space bounding box (the reference takes the 8 corners of the mesh's minimal oriented box from open3d, in the NDDS
+corner order of pegasus_working.py:470-495; pegasus_amd.obb.boxes_for computes the same box on the GPU) --
+"3d_bounding_box_model_coord" [8,3],
 "3d_bounding_center" [3], "projected_points" [8,2] and "projected_center" [1,2] with P = K @ T_m2c[:3] applied to the
 homogeneous points (pegasus_working.py:547-563);  scene_camera entry = {"cam_K": 9 floats, "depth_scale"} with K from the FoV
 (fov2focal, pegasus_working.py:349-356).  Format: submodules/bop_toolkit/docs/bop_datasets_format.md:75-109.
@@ -47,7 +48,8 @@ def scene_gt_entry(R_c2w, t_w2c, object_poses_m2w: dict, translation_scale: floa
     """object_poses_m2w: {bullet_obj_id: 4x4 model-to-world}.  Returns the scene_gt list for one image with the fields of
     the reference's writer (pegasus_working.py:565-576).  ``dataset_ids``: {bullet_obj_id: the object's dataset ID (the
     reference's meta_info.ID)}, default: the same number.  ``boxes``: {bullet_obj_id: (corners [8,3], center [3])} in
-    model coordinates + ``K`` [3,3] add the box and its projection."""
+    model coordinates + ``K`` [3,3] add the box and its projection.  A third tuple element is the point projected as
+    ``projected_center`` instead of ``center`` (the reference stores the vertex mean but projects the box's centre)."""
     T_w2c = world_to_camera(R_c2w, t_w2c)
     out = []
     for obj_id, T_m2w in object_poses_m2w.items():
@@ -60,12 +62,13 @@ def scene_gt_entry(R_c2w, t_w2c, object_poses_m2w: dict, translation_scale: floa
         if boxes is not None and obj_id in boxes:
             if K is None:
                 raise ValueError("boxes need the camera matrix K for their projection")
-            corners, center = boxes[obj_id]
+            corners, center, *projected = boxes[obj_id]
             corners = np.asarray(corners, dtype=np.float64).reshape(8, 3)
             center = np.asarray(center, dtype=np.float64).reshape(3)
+            projected = np.asarray(projected[0], dtype=np.float64).reshape(3) if projected else center
             e["3d_bounding_box_model_coord"] = corners.tolist()
             e["3d_bounding_center"] = center.tolist()
-            e["projected_center"] = project_points(K, T, center[None]).tolist()
+            e["projected_center"] = project_points(K, T, projected[None]).tolist()
             e["projected_points"] = project_points(K, T, corners).tolist()
         out.append(e)
     return out

@@ -23,6 +23,7 @@
 #include "knn.hip.h"
 #include "mesh.hip.h"
 #include "meshraster.hip.h"
+#include "obb.hip.h"
 #include "compose.hip.h"
 #include "composite.hip.h"
 #include "pgr_common.h"
@@ -1466,6 +1467,142 @@ int32_t pgr_pose_adi(const float* vertices, int64_t n_vertices, int32_t n_jobs, 
         pose_adi_mean_kernel<<<1, 64, 0, stream>>>(T, partials, adi);
     }
     return hip_ok(hipGetLastError(), "pose_adi launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+// ---- minimal oriented boxes and diameters (obb.hip.h) --------------------------------------------------------------------
+namespace {
+// how a job's points are cut: `splits` chunks of `chunk` points (whole tiles), none of them empty
+struct ObbCut { uint32_t splits, chunk; };
+ObbCut obb_cut(const PgrObbJob& j) {
+    const int64_t tri_blocks = ((int64_t)j.tri_count + OBB_TF - 1) / OBB_TF;
+    const int64_t tiles = ((int64_t)j.point_count + OBB_TP - 1) / OBB_TP;
+    const int64_t want = std::min(tiles, std::max<int64_t>(1, (OBB_TARGET_BLOCKS + tri_blocks - 1) / tri_blocks));
+    const int64_t chunk = (tiles + want - 1) / want * OBB_TP;
+    return ObbCut{(uint32_t)(((int64_t)j.point_count + chunk - 1) / chunk), (uint32_t)chunk};
+}
+// the j range of a block of points is cut into at most this many chunks (diameter_partial_kernel sizes them per block)
+uint32_t diameter_splits(const PgrObbJob& j) {
+    const int64_t blocks = ((int64_t)j.point_count + DIAM_TILE - 1) / DIAM_TILE;
+    return (uint32_t)std::min(blocks, std::max<int64_t>(1, (OBB_TARGET_BLOCKS + blocks - 1) / blocks));
+}
+bool obb_points_ok(int64_t n_points, int32_t n_jobs, const PgrObbJob* jobs) {
+    if (n_jobs < 0 || n_points < 0 || (n_jobs > 0 && !jobs)) return false;
+    for (int32_t k = 0; k < n_jobs; ++k)
+        if (jobs[k].point_first < 0 || jobs[k].point_count < 0 || (int64_t)jobs[k].point_first + jobs[k].point_count > n_points)
+            return false;
+    return true;
+}
+}  // namespace
+
+// float64 partial extremes [chunk][6][triangle], the jobs one behind the other
+size_t pgr_obb_candidates_workspace_bytes(int32_t n_jobs, const PgrObbJob* jobs) {
+    if (n_jobs <= 0 || !jobs) return 0;
+    size_t doubles = 0;
+    for (int32_t k = 0; k < n_jobs; ++k) {
+        if (jobs[k].tri_count < 0 || jobs[k].point_count < 0 || (jobs[k].tri_count > 0 && jobs[k].point_count == 0)) return 0;
+        if (jobs[k].tri_count > 0) doubles += (size_t)jobs[k].tri_count * 6 * obb_cut(jobs[k]).splits;
+    }
+    Carver c;
+    c.take(doubles * sizeof(double));
+    return c.off;
+}
+
+int32_t pgr_obb_candidates(const float* points, int64_t n_points, const int32_t* triangles, int64_t n_triangles,
+                           const int32_t* triangles_host, int32_t n_jobs, const PgrObbJob* jobs, double* volumes,
+                           int32_t* best, double* lohi, void* workspace, size_t workspace_bytes, void* stream_v) {
+    if (!obb_points_ok(n_points, n_jobs, jobs) || n_triangles < 0) return PGR_ERR_INVALID_ARGUMENT;
+    if (n_jobs == 0) return PGR_OK;
+    if (!best || !lohi) return PGR_ERR_INVALID_ARGUMENT;
+    int64_t total_tris = 0;
+    for (int32_t k = 0; k < n_jobs; ++k) {
+        const PgrObbJob& j = jobs[k];
+        if (j.tri_first < 0 || j.tri_count < 0 || (int64_t)j.tri_first + j.tri_count > n_triangles) return PGR_ERR_INVALID_ARGUMENT;
+        if (j.tri_count > 0 && j.point_count == 0) return PGR_ERR_INVALID_ARGUMENT;       // no index can be valid
+        total_tris += j.tri_count;
+        if (triangles_host)
+            for (int64_t e = 3 * (int64_t)j.tri_first; e < 3 * ((int64_t)j.tri_first + j.tri_count); ++e)
+                if (triangles_host[e] < 0 || triangles_host[e] >= j.point_count) return PGR_ERR_INVALID_ARGUMENT;
+    }
+    if (total_tris > 0 && (!points || !triangles || !volumes)) return PGR_ERR_INVALID_ARGUMENT;
+    const size_t need = pgr_obb_candidates_workspace_bytes(n_jobs, jobs);
+    if (total_tris > 0 && (!workspace || !workspace_aligned_16(workspace))) return PGR_ERR_INVALID_ARGUMENT;
+    if (total_tris > 0 && workspace_bytes < need) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    auto* partials = static_cast<double*>(workspace);
+    uint64_t part = 0;
+    for (int32_t k0 = 0; k0 < n_jobs; k0 += OBB_JOBS_PER_LAUNCH) {
+        ObbJobTable T{};
+        T.count = std::min(OBB_JOBS_PER_LAUNCH, n_jobs - k0);
+        T.first = k0;
+        uint32_t blocks = 0, mblocks = 0;
+        for (int32_t k = 0; k < T.count; ++k) {
+            const PgrObbJob& j = jobs[k0 + k];
+            ObbJobDev& d = T.job[k];
+            d.p0 = j.point_first; d.np = j.point_count; d.t0 = j.tri_first; d.nt = j.tri_count;
+            d.block0 = blocks; d.mblock0 = mblocks; d.part0 = part;
+            d.splits = 1; d.chunk = OBB_TP;
+            if (j.tri_count == 0) continue;
+            const ObbCut cut = obb_cut(j);
+            d.splits = cut.splits; d.chunk = cut.chunk;
+            const uint32_t tri_blocks = (uint32_t)(((int64_t)j.tri_count + OBB_TF - 1) / OBB_TF);
+            blocks += tri_blocks * cut.splits;
+            mblocks += tri_blocks;
+            part += (uint64_t)j.tri_count * 6 * cut.splits;
+        }
+        if (blocks) {
+            obb_partial_kernel<<<blocks, OBB_TF, 0, stream>>>(T, points, triangles, partials);
+            obb_merge_kernel<<<mblocks, OBB_TF, 0, stream>>>(T, partials, volumes);
+        }
+        obb_argmin_kernel<<<(unsigned)T.count, 256, 0, stream>>>(T, partials, volumes, best, lohi);
+    }
+    return hip_ok(hipGetLastError(), "obb_candidates launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+// one DiamPartial per (block of points, chunk), the jobs one behind the other
+size_t pgr_point_diameter_workspace_bytes(int32_t n_jobs, const PgrObbJob* jobs) {
+    if (n_jobs <= 0 || !jobs) return 0;
+    size_t records = 0;
+    for (int32_t k = 0; k < n_jobs; ++k) {
+        if (jobs[k].point_count < 0) return 0;
+        if (jobs[k].point_count > 0)
+            records += (size_t)(((int64_t)jobs[k].point_count + DIAM_TILE - 1) / DIAM_TILE) * diameter_splits(jobs[k]);
+    }
+    Carver c;
+    c.take(records * sizeof(DiamPartial));
+    return c.off;
+}
+
+int32_t pgr_point_diameter(const float* points, int64_t n_points, int32_t n_jobs, const PgrObbJob* jobs, int32_t* pair,
+                           double* d2, void* workspace, size_t workspace_bytes, void* stream_v) {
+    if (!obb_points_ok(n_points, n_jobs, jobs)) return PGR_ERR_INVALID_ARGUMENT;
+    if (n_jobs == 0) return PGR_OK;
+    if (!pair || !d2) return PGR_ERR_INVALID_ARGUMENT;
+    int64_t total_points = 0;
+    for (int32_t k = 0; k < n_jobs; ++k) total_points += jobs[k].point_count;
+    if (total_points > 0 && (!points || !workspace || !workspace_aligned_16(workspace))) return PGR_ERR_INVALID_ARGUMENT;
+    if (total_points > 0 && workspace_bytes < pgr_point_diameter_workspace_bytes(n_jobs, jobs)) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    auto* partials = static_cast<DiamPartial*>(workspace);
+    uint64_t part = 0;
+    for (int32_t k0 = 0; k0 < n_jobs; k0 += OBB_JOBS_PER_LAUNCH) {
+        ObbJobTable T{};
+        T.count = std::min(OBB_JOBS_PER_LAUNCH, n_jobs - k0);
+        T.first = k0;
+        uint32_t blocks = 0;
+        for (int32_t k = 0; k < T.count; ++k) {
+            const PgrObbJob& j = jobs[k0 + k];
+            ObbJobDev& d = T.job[k];
+            d.p0 = j.point_first; d.np = j.point_count;
+            d.block0 = blocks; d.part0 = part;
+            d.splits = j.point_count > 0 ? diameter_splits(j) : 1;
+            const uint32_t n = (uint32_t)(((int64_t)j.point_count + DIAM_TILE - 1) / DIAM_TILE) * d.splits;
+            blocks += n;
+            part += n;
+        }
+        if (blocks) diameter_partial_kernel<<<blocks, DIAM_TILE, 0, stream>>>(T, points, partials);
+        diameter_reduce_kernel<<<(unsigned)T.count, 256, 0, stream>>>(T, partials, pair, d2);
+    }
+    return hip_ok(hipGetLastError(), "point_diameter launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
 }
 
 // ---- COCO annotations: mask run-length encoding, decoding, overlap counts (cocorle.hip.h) -------------------------------

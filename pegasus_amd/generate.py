@@ -19,7 +19,7 @@ import time
 import numpy as np
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
     ap.add_argument("--frames", type=int, default=32)
@@ -36,7 +36,12 @@ def main():
     ap.add_argument("--gt-coco", nargs="?", const="amodal", default=None, choices=["amodal", "modal"],
                     help="also write scene_gt_coco.json (modal: scene_gt_coco_modal.json): the COCO annotations of the BOP "
                          "toolkit's calc_gt_coco.py, encoded on the GPU from the masks that are written")
-    args = ap.parse_args()
+    ap.add_argument("--boxes", default="aabb", choices=["aabb", "oriented"],
+                    help="the box fields of scene_gt: the axis-aligned box of the object's Gaussians, or the minimal oriented "
+                         "box of its mesh in NDDS corner order as the reference writes it (needs --gt-from-meshes)")
+    args = ap.parse_args(argv)
+    if args.boxes == "oriented" and not args.gt_from_meshes:
+        ap.error("--boxes oriented takes the boxes from the meshes: it requires --gt-from-meshes MODELS_DIR")
 
     import os
     import torch
@@ -75,6 +80,12 @@ def main():
     if args.gt_from_meshes:
         from .mesh_render import MeshSet
         meshes = MeshSet.from_dir(args.gt_from_meshes, device=device, scale=0.001)      # scene_gt is in metres here
+    if args.boxes == "oriented":
+        from . import obb
+        boxes = obb.boxes_for(meshes)
+        missing = [k for k in range(1, fr.K + 1) if k not in boxes]
+        if missing:
+            raise SystemExit(f"--boxes oriented: no mesh for object(s) {missing} under {args.gt_from_meshes}")
     t0 = time.perf_counter()
     t_gpu = 0.0
     mine = list(range(rank, args.frames, world))          # frame f -> rank f mod world
