@@ -33,6 +33,16 @@ def camera_K(fovx, fovy, width, height) -> np.ndarray:
     return np.array([[fx, 0, width / 2.0], [0, fy, height / 2.0], [0, 0, 1.0]])
 
 
+def broadcast_K(K, n: int) -> np.ndarray:
+    """``K`` [3,3] or [n,3,3] as float64 [n,3,3] (one matrix for all: a read-only view)."""
+    K = np.asarray(K, np.float64)
+    if K.shape == (3, 3):
+        K = np.broadcast_to(K, (n, 3, 3))
+    if K.shape != (n, 3, 3):
+        raise ValueError(f"K must be [3,3] or [{n},3,3]")
+    return K
+
+
 def project_points(K, T_m2c, points) -> np.ndarray:
     """[n,2] pixel coordinates of model-space points: P = K @ T_m2c[:3] on homogeneous points, then the division
     cv2.convertPointsFromHomogeneous does (a zero last coordinate divides by 1)   (pegasus_working.py:547-563)."""

@@ -18,14 +18,13 @@ from __future__ import annotations
 
 import argparse
 import datetime
-import json
 import sys
 from pathlib import Path
 from typing import Optional, Sequence
 
 import numpy as np
 
-from . import _lib
+from . import _lib, bop_dataset as BD
 
 MAX_SIDE = 8192
 IGNORE_BELOW = 0.1                   # calc_gt_coco.py: ignore = visib_fract < 0.1
@@ -312,32 +311,22 @@ def recompute_dataset(dataset_dir, bbox_type: str = "amodal", backend=None, batc
     """``scene_gt_coco.json`` (``scene_gt_coco_modal.json`` with ``bbox_type='modal'``) of every scene under
     <dataset>/train from its mask_visib/ and mask/ PNGs, scene_gt.json and scene_gt_info.json: scripts/calc_gt_coco.py.
     ``backend``: see ``annotations`` (masks then stay host arrays); ``batch``: images encoded per call, at least 1."""
-    from .dataset_writer import decode_png
     if bbox_type not in ("amodal", "modal"):
         raise ValueError(f"{bbox_type} is not a valid bounding box type")
     batch = int(batch)
     if batch < 1:
         raise ValueError(f"batch = {batch}: at least one image per call")
     dataset_dir = Path(dataset_dir)
-    scenes = sorted(p for p in (dataset_dir / "train").iterdir() if (p / "scene_gt.json").exists())
-    for scene in scenes:
-        gt = json.loads((scene / "scene_gt.json").read_text())
-        info_path = scene / "scene_gt_info.json"
-        if info_path.exists():
-            info = json.loads(info_path.read_text())
-        elif bbox_type == "modal":
-            info = None                                   # no visible fraction on record: nothing is ignored
-        else:
-            raise FileNotFoundError(f"{info_path} is missing (amodal annotations need scene_gt_info.json and mask/)")
-        ids = sorted(gt, key=int)
-        per_image, images = {}, []
-
-        def load(i, kind, k):
-            return decode_png((scene / kind / f"{int(i):06d}_{k:06d}.png").read_bytes())
+    scenes = BD.scene_dirs(dataset_dir, "train")
+    for scene in map(BD.BopScene, scenes):
+        gt, info, ids = scene.gt, scene.gt_info, scene.image_ids     # modal without info: no visible fraction, nothing ignored
+        if info is None and bbox_type != "modal":
+            raise FileNotFoundError(f"{scene.path / BD.SCENE_GT_INFO} is missing (amodal annotations need scene_gt_info.json and mask/)")
+        per_image = {}
         for b0 in range(0, len(ids), batch):
             chunk = ids[b0:b0 + batch]
-            visib = [load(i, "mask_visib", k) for i in chunk for k in range(len(gt[i]))]
-            full = [load(i, "mask", k) for i in chunk for k in range(len(gt[i]))] if bbox_type == "amodal" else None
+            visib = [scene.read_png("mask_visib", i, k) for i in chunk for k in range(len(gt[i]))]
+            full = [scene.read_png("mask", i, k) for i in chunk for k in range(len(gt[i]))] if bbox_type == "amodal" else None
             if not visib:
                 for i in chunk:
                     per_image[int(i)] = []
@@ -351,23 +340,9 @@ def recompute_dataset(dataset_dir, bbox_type: str = "amodal", backend=None, batc
                 per_image[int(i)] = annotations_from_encoded(*enc, size, [int(e["obj_id"]) for e in gt[i]], fract, int(i),
                                                              bbox_type, at)
                 at += K
-        for i in ids:
-            rgb = scene / "rgb" / f"{int(i):06d}.png"
-            size = _png_size(rgb) if rgb.exists() else None
-            if size is None:
-                first = next(iter(sorted((scene / "mask_visib").glob(f"{int(i):06d}_*.png"))), None)
-                size = _png_size(first) if first is not None else (0, 0)
-            images.append((int(i), f"rgb/{int(i):06d}.png", [size[0], size[1]]))
-        doc = scene_coco(images, per_image, scene_obj_ids(gt), dataset_dir.resolve().name)
-        (scene / coco_file_name(bbox_type)).write_text(json.dumps(doc))
+        images = [(int(i), f"rgb/{BD.image_name(i)}", list(scene.image_size(i))) for i in ids]
+        scene.write_json(coco_file_name(bbox_type), scene_coco(images, per_image, scene_obj_ids(gt), dataset_dir.resolve().name))
     return scenes
-
-
-def _png_size(path):
-    """(W, H) from a PNG's IHDR."""
-    import struct
-    head = Path(path).read_bytes()[:24]
-    return struct.unpack(">II", head[16:24])
 
 
 def encode_stack(visib, full=None, backend=None, device="cuda"):

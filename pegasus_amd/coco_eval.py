@@ -28,7 +28,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from . import _lib
+from . import _lib, bop_dataset as BD
 from .coco import coco_file_name, rle_counts, rle_flatten, rle_lists
 
 STAT_NAMES = ("AP", "AP50", "AP75", "AP_small", "AP_medium", "AP_large", "AR1", "AR10", "AR100", "AR_small", "AR_medium",
@@ -445,8 +445,8 @@ def write_results(path, results) -> None:
 def results_from_gt(dataset_dir, split: str = "train", bbox_type: str = "amodal", score: float = 1.0) -> list:
     """The dataset's own scene_gt_coco annotations as ``write_results`` input: every annotation a detection of ``score``."""
     out = []
-    for scene in sorted(p for p in (Path(dataset_dir) / split).iterdir() if (p / coco_file_name(bbox_type)).exists()):
-        doc = json.loads((scene / coco_file_name(bbox_type)).read_text())
+    for scene in BD.scene_dirs(dataset_dir, split, coco_file_name(bbox_type)):
+        doc = BD.BopScene(scene).read_json(coco_file_name(bbox_type))
         out += [{"scene_id": int(scene.name), "im_id": a["image_id"], "obj_id": a["category_id"], "score": score,
                  "bbox": a["bbox"], "segmentation": a["segmentation"], "run_time": 0.0} for a in doc["annotations"]]
     return out
@@ -515,14 +515,14 @@ def load_dataset(results, dataset_dir, ann_type="segm", bbox_type="amodal", targ
             per_scene.setdefault(int(r["scene_id"]), []).append(r)
     name = coco_file_name(bbox_type if ann_type == "bbox" else "amodal")
     if targets is None:
-        wanted = {int(p.name): None for p in sorted(root.iterdir()) if p.name.isdigit() and (p / name).exists()}
+        wanted = {int(p.name): None for p in BD.scene_dirs(dataset_dir, split, name) if p.name.isdigit()}
     else:
         wanted = {}
         for t in targets:
             wanted.setdefault(int(t["scene_id"]), set()).add(int(t["im_id"]))
     scenes = []
     for sid, ims in wanted.items():
-        path = root / f"{sid:06d}" / name
+        path = BD.scene_dir(dataset_dir, split, sid) / name
         if not path.exists():
             raise FileNotFoundError(f"{path} is missing (python -m pegasus_amd.coco writes it)")
         doc = json.loads(path.read_text())

@@ -1,76 +1,19 @@
 """BOP-layout writer for the batch path ("mask/depth writers").
 
-Layout and naming follow the reference's writer (/root/reference/src/visualization/object_visualization.py:373-391,
-458-480; /root/reference/pegasus.py:347-358):
-
-    <out>/train/<scene:06d>/rgb/<frame:06d>.png              8-bit RGB,  (img * 255).astype(uint8)
-    <out>/train/<scene:06d>/depth/<frame:06d>.png            16-bit grey, (depth * 1000).astype(uint16)  (millimetres)
-    <out>/train/<scene:06d>/mask_visib/<frame:06d>_<obj:06d>.png   8-bit 0/255      visible masks ('seg_vis')
-    <out>/train/<scene:06d>/mask/<frame:06d>_<obj:06d>.png         8-bit 0/255      silhouettes   ('seg_sil')
-    <out>/train/<scene:06d>/sem_mask/<frame:06d>.png               8-bit RGB, uint8 of the semantic image ('sem_seg')
-    <out>/train/<scene:06d>/scene_gt.json, scene_camera.json      pegasus_amd.bop_pose records
-    <out>/train/<scene:06d>/scene_gt_info.json                    per object and frame: pixel counts, visible fraction, 2D
-                                                                  boxes (BOP format, bop_datasets_format.md:116-129) -- written
-                                                                  when a batch brings both visible masks and silhouettes
-    <out>/train/<scene:06d>/scene_gt_coco.json                    COCO annotations (run-length masks, boxes, ignore flags:
-                                                                  pegasus_amd.coco) -- written for batches added with coco=
-
-(the five image kinds of the reference's write_training_data, /root/reference/src/tools/pegasus_working.py:412-439, for the
-data points ['rgb','depth','seg_vis','seg_sil','sem_seg'] of /root/reference/pegasus.py:491)
-
-The reference encodes PNGs with imageio (absent here); PNG is deflate + CRC, so zlib is all it takes.  Quantisation
-runs on the GPU (pgr_quantize_frame); only the 8/16-bit images cross PCIe.
+The directory layout, the file names, the record files and the PNG codec are ``pegasus_amd.bop_dataset``'s; this module
+fills them from the renderer's frames: the five image kinds of the reference's write_training_data
+(src/tools/pegasus_working.py:412-439) for the data points ['rgb','depth','seg_vis','seg_sil','sem_seg'], scene_gt_info.json
+when a batch brings both visible masks and silhouettes (or meshes), scene_gt_coco.json for batches added with ``coco=``.
+Quantisation runs on the GPU (pgr_quantize_frame); only the 8/16-bit images cross PCIe.
 """
 from __future__ import annotations
 
-import json
-import struct
-import zlib
 from pathlib import Path
 
 import numpy as np
 
-
-def encode_png(a: np.ndarray, level: int = 1) -> bytes:
-    """uint8 [H,W] / [H,W,3] or uint16 [H,W] -> PNG bytes (colour type 0 or 2, no interlace, filter 0)."""
-    a = np.ascontiguousarray(a)
-    if a.dtype == np.uint8 and a.ndim == 2:
-        depth, ctype, rows = 8, 0, a
-    elif a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] == 3:
-        depth, ctype, rows = 8, 2, a.reshape(a.shape[0], -1)
-    elif a.dtype == np.uint16 and a.ndim == 2:
-        depth, ctype, rows = 16, 0, a.astype(">u2").view(np.uint8).reshape(a.shape[0], -1)     # big-endian samples
-    else:
-        raise ValueError("encode_png takes uint8 [H,W], uint8 [H,W,3] or uint16 [H,W]")
-    h, w = a.shape[:2]
-    raw = np.concatenate([np.zeros((h, 1), np.uint8), rows], axis=1).tobytes()                  # filter type 0 per row
-
-    def chunk(tag: bytes, data: bytes) -> bytes:
-        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
-    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, depth, ctype, 0, 0, 0)) +
-            chunk(b"IDAT", zlib.compress(raw, level)) + chunk(b"IEND", b""))
-
-
-def decode_png(data: bytes) -> np.ndarray:
-    """Inverse of encode_png for the files this module writes (filter 0 only): used by the tests."""
-    assert data[:8] == b"\x89PNG\r\n\x1a\n"
-    pos, idat, hdr = 8, b"", None
-    while pos < len(data):
-        n, tag = struct.unpack(">I", data[pos:pos + 4])[0], data[pos + 4:pos + 8]
-        body = data[pos + 8:pos + 8 + n]
-        if tag == b"IHDR":
-            hdr = struct.unpack(">IIBBBBB", body)
-        elif tag == b"IDAT":
-            idat += body
-        pos += 12 + n
-    w, h, depth, ctype = hdr[:4]
-    ch = 3 if ctype == 2 else 1
-    raw = np.frombuffer(zlib.decompress(idat), np.uint8).reshape(h, 1 + w * ch * depth // 8)
-    assert not raw[:, 0].any()
-    body = raw[:, 1:]
-    if depth == 16:
-        return body.reshape(h, w, 2).copy().view(">u2").reshape(h, w).astype(np.uint16)
-    return body.reshape(h, w, 3).copy() if ch == 3 else body.copy()
+from . import bop_dataset as BD
+from .bop_dataset import decode_png, encode_png  # noqa: F401  (importable from here too)
 
 
 class BopSceneWriter:
@@ -85,9 +28,9 @@ class BopSceneWriter:
     def __init__(self, out_dir, scene_id: int = 0, png_level: int = 1, workers: int = None, max_pending: int = 4):
         import os
         from concurrent.futures import ThreadPoolExecutor
-        self.scene = Path(out_dir) / "train" / f"{scene_id:06d}"
-        for d in ("rgb", "depth", "mask_visib", "mask", "sem_mask"):
-            (self.scene / d).mkdir(parents=True, exist_ok=True)
+        self.scene = BD.scene_dir(out_dir, "train", scene_id)
+        self.files = BD.BopScene(self.scene)
+        self.files.make_dirs()
         self.scene_gt, self.scene_camera, self.scene_gt_info = {}, {}, {}
         self.scene_gt_coco, self.coco_bbox_type, self.coco_size = {}, None, None      # per frame: annotations without ids
         self.dataset_name = Path(out_dir).resolve().name
@@ -99,7 +42,8 @@ class BopSceneWriter:
     def _write(self, path, image):
         path.write_bytes(encode_png(image, self.level))
 
-    def _submit(self, path, image, batch_futures):
+    def _submit(self, batch_futures, image, kind, i, k=None):
+        path = self.files.image_path(kind, i, k)
         if self._pool is None:
             self._write(path, image)
         else:
@@ -202,18 +146,18 @@ class BopSceneWriter:
             if mesh_gt is not None:
                 for name, stack in (("mask", mesh_gt[0][i]), ("mask_visib", mesh_gt[1][i])):
                     for k, image in enumerate((stack * 255).cpu().numpy()):
-                        self._submit(self.scene / name / f"{fid:06d}_{k:06d}.png", image, futures)
+                        self._submit(futures, image, name, fid, k)
                 self.scene_gt_info[str(fid)] = mesh_gt[2][i]
-            self._submit(self.scene / "rgb" / f"{fid:06d}.png", rgb8[i], futures)
-            self._submit(self.scene / "depth" / f"{fid:06d}.png", mm[i], futures)
+            self._submit(futures, rgb8[i], "rgb", fid)
+            self._submit(futures, mm[i], "depth", fid)
             if mk is not None:
                 for k in range(mk.shape[1]):
-                    self._submit(self.scene / "mask_visib" / f"{fid:06d}_{k:06d}.png", mk[i, k], futures)
+                    self._submit(futures, mk[i, k], "mask_visib", fid, k)
             if sem8 is not None:
-                self._submit(self.scene / "sem_mask" / f"{fid:06d}.png", sem8[i], futures)
+                self._submit(futures, sem8[i], "sem_mask", fid)
             if sil is not None:
                 for k in range(sil.shape[1]):
-                    self._submit(self.scene / "mask" / f"{fid:06d}_{k:06d}.png", sil[i, k], futures)
+                    self._submit(futures, sil[i, k], "mask", fid, k)
             self.scene_gt[str(fid)] = scene_gt[str(i)]
             self.scene_camera[str(fid)] = scene_camera[str(i)]
             if info is not None:
@@ -265,13 +209,12 @@ class BopSceneWriter:
         return {"bbox_type": self.coco_bbox_type, "size": list(self.coco_size), "frames": self.scene_gt_coco}
 
     def write_records(self):
-        order = lambda d: {k: d[k] for k in sorted(d, key=int)}
-        (self.scene / "scene_gt.json").write_text(json.dumps(order(self.scene_gt)))
-        (self.scene / "scene_camera.json").write_text(json.dumps(order(self.scene_camera)))
+        self.files.write_json(BD.SCENE_GT, BD.by_frame(self.scene_gt))
+        self.files.write_json(BD.SCENE_CAMERA, BD.by_frame(self.scene_camera))
         if self.scene_gt_info:
-            (self.scene / "scene_gt_info.json").write_text(json.dumps(order(self.scene_gt_info)))
+            self.files.write_json(BD.SCENE_GT_INFO, BD.by_frame(self.scene_gt_info))
         if self.coco_bbox_type is not None:
             from . import coco as CO
-            images = [(int(k), f"rgb/{int(k):06d}.png", list(self.coco_size)) for k in self.scene_gt_coco]
+            images = [(int(k), f"rgb/{BD.image_name(k)}", list(self.coco_size)) for k in self.scene_gt_coco]
             doc = CO.scene_coco(images, self.scene_gt_coco, CO.scene_obj_ids(self.scene_gt), self.dataset_name)
-            (self.scene / CO.coco_file_name(self.coco_bbox_type)).write_text(json.dumps(doc))
+            self.files.write_json(CO.coco_file_name(self.coco_bbox_type), doc)

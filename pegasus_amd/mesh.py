@@ -25,7 +25,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from . import _lib
+from . import _lib, bop_dataset as BD
 from .ply_io import write_ply_mesh
 
 NEAR_Z = 0.2                 # pgr_common.h: the renderer culls everything closer than this
@@ -413,14 +413,13 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     a = _parser().parse_args(argv)
     mesh = extract_mesh(load_model(a.model_path, a.iteration, a.clean_pcd), resolution=a.resolution, n_views=a.n_views,
                         image_size=a.image_size)
-    name = f"obj_{a.obj_id:06d}"
+    name = BD.model_stem(a.obj_id)
     out = Path(a.out)
     write_ply(out / "models" / f"{name}.ply", mesh, scale=a.scale)
-    info_path = out / "models" / "models_info.json"
-    info = json.loads(info_path.read_text()) if info_path.exists() else {}
+    info = BD.read_models_info(out / "models")
     disc, cont = scaled_symmetries(a.sym_discrete, a.sym_continuous, a.scale)
     info[str(a.obj_id)] = models_info(mesh.scaled(a.scale), disc, cont)
-    info_path.write_text(json.dumps(dict(sorted(info.items(), key=lambda kv: int(kv[0]))), indent=2) + "\n")
+    (out / "models" / BD.MODELS_INFO).write_text(json.dumps(dict(sorted(info.items(), key=lambda kv: int(kv[0]))), indent=2) + "\n")
     write_obj(out / "urdf" / f"{name}.obj", mesh)
     write_urdf(out / "urdf" / f"{name}.urdf", f"{name}.obj", mesh, a.mass)
     print(f"{name}: {len(mesh.vertices)} vertices, {len(mesh.faces)} faces, volume {mesh.volume():.6g}, "

@@ -14,14 +14,13 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
-import json
-import re
 from pathlib import Path
 from typing import Optional, Sequence
 
 import numpy as np
 
-from . import _lib
+from . import _lib, bop_dataset as BD
+from .bop_pose import broadcast_K, scene_gt_info_entry
 
 MAX_CANVAS = 8192
 DEFAULT_NEAR = 1e-3                  # model units; any positive value keeps the projection defined
@@ -60,12 +59,8 @@ class MeshSet:
     @classmethod
     def from_dir(cls, models_dir, device="cuda", scale: float = 1.0) -> "MeshSet":
         """Every ``obj_NNNNNN.ply`` of a BOP models directory, diameters from its ``models_info.json`` (scaled alike)."""
-        models_dir = Path(models_dir)
-        files = {int(m.group(1)): p for p in sorted(models_dir.glob("obj_*.ply")) if (m := re.fullmatch(r"obj_(\d+)", p.stem))}
-        if not files:
-            raise FileNotFoundError(f"no obj_NNNNNN.ply under {models_dir}")
-        info = models_dir / "models_info.json"
-        diam = {int(k): v["diameter"] * scale for k, v in json.loads(info.read_text()).items()} if info.exists() else None
+        files = BD.model_files(models_dir)
+        diam = {int(k): v["diameter"] * scale for k, v in BD.read_models_info(models_dir).items()}
         return cls(files, device=device, scale=scale, diameters=diam)
 
     def mesh(self, obj_id: int):
@@ -74,19 +69,10 @@ class MeshSet:
         return self.vertices[v0:v0 + nv].cpu().numpy(), self.faces[f0:f0 + nf].cpu().numpy()
 
 
-def _K_list(K, n):
-    K = np.asarray(K, np.float64)
-    if K.shape == (3, 3):
-        return [K] * n
-    if K.shape != (n, 3, 3):
-        raise ValueError(f"K must be [3,3] or [{n},3,3]")
-    return list(K)
-
-
 def mesh_jobs(meshes: MeshSet, jobs: Sequence, K, margin=(0, 0), slots: Optional[Sequence[int]] = None):
     """The PgrMeshJob array of ``jobs`` = [(obj_id, R [3,3], t [3]), ...]: pose and intrinsics rounded to float32, the
     principal point moved by the margin."""
-    Ks = _K_list(K, len(jobs))
+    Ks = broadcast_K(K, len(jobs))
     arr = (_lib.PgrMeshJob * max(len(jobs), 1))()
     for k, (obj_id, R, t) in enumerate(jobs):
         if int(obj_id) not in meshes.ranges:
@@ -121,13 +107,13 @@ def render_depth(meshes: MeshSet, jobs: Sequence, K, size, margin=(0, 0), near: 
     if device.type != "cuda":
         raise RuntimeError("render_depth needs a mesh set on a HIP device; there is no CPU path")
     J = len(jobs)
-    Ks = _K_list(K, J)
+    Ks = broadcast_K(K, J)
     out = torch.empty((J, Hc, Wc), dtype=torch.float32, device=device)
     straddle = torch.zeros(1, dtype=torch.int32, device=device)
     per_call = max(1, int(budget_bytes) // (4 * Hc * Wc))
     for j0 in range(0, J, per_call):
         chunk = jobs[j0:j0 + per_call]
-        arr = mesh_jobs(meshes, chunk, np.stack(Ks[j0:j0 + per_call]), (mx, my))
+        arr = mesh_jobs(meshes, chunk, Ks[j0:j0 + per_call], (mx, my))
         ws = _lib.workspace("pgr_mesh_depth", device, len(chunk), arr)
         count = torch.zeros(1, dtype=torch.int32, device=device)
         _lib.call("pgr_mesh_depth", device, _lib.ptr(meshes.vertices), meshes.vertices.shape[0], _lib.ptr(meshes.faces),
@@ -244,15 +230,14 @@ def gt_from_meshes(meshes: MeshSet, scene_gt: dict, scene_camera: dict, depth, d
     dev = meshes.device
     depth = torch.as_tensor(depth).to(dev)
     B, H, W = depth.shape
-    unit = float(translation_scale) / 1000.0
-    scale = torch.tensor([float(scene_camera[str(i)].get("depth_scale", 1.0)) * unit for i in range(B)], device=dev)
+    unit = BD.unit_of(translation_scale)
+    scale = torch.tensor([BD.depth_unit(scene_camera[str(i)], unit) for i in range(B)], device=dev)
     scene = (depth.to(torch.float32) * scale.to(torch.float32)[:, None, None]).contiguous()
     jobs, frames, Ks = [], [], []
     for i in range(B):
-        K = np.asarray(scene_camera[str(i)]["cam_K"], np.float64).reshape(3, 3)
+        K = BD.cam_K(scene_camera[str(i)])
         for e in scene_gt[str(i)]:
-            jobs.append((int(e["obj_id"]), np.asarray(e["cam_R_m2c"], np.float64).reshape(3, 3),
-                         np.asarray(e["cam_t_m2c"], np.float64).reshape(3)))
+            jobs.append((int(e["obj_id"]), *BD.pose_of(e)))
             frames.append(i); Ks.append(K)
     masks = [[] for _ in range(B)]
     visibs = [[] for _ in range(B)]
@@ -266,7 +251,6 @@ def gt_from_meshes(meshes: MeshSet, scene_gt: dict, scene_camera: dict, depth, d
         for k, i in enumerate(frames[sl]):
             masks[i].append(m[k]); visibs[i].append(v[k])
     stats = torch.cat(rows).cpu().numpy() if rows else np.zeros((0, _lib.PGR_GT_INFO_STATS), np.int32)
-    from .bop_pose import scene_gt_info_entry
     info, at = [], 0
     empty = torch.zeros((0, H, W), dtype=torch.uint8, device=dev)
     for i in range(B):
@@ -334,19 +318,15 @@ def recompute_dataset(dataset_dir, models_dir, delta: float = 15.0, translation_
                       device="cuda"):
     """mask/, mask_visib/ and scene_gt_info.json of every scene under <dataset>/train, from the meshes of ``models_dir``
     (millimetres), scene_gt.json, scene_camera.json and the depth images: calc_gt_info.py plus calc_gt_masks.py."""
-    from .dataset_writer import decode_png, encode_png
-    meshes = MeshSet.from_dir(models_dir, device=device, scale=float(translation_scale) / 1000.0)
-    scenes = sorted(p for p in (Path(dataset_dir) / "train").iterdir() if (p / "scene_gt.json").exists())
-    for scene in scenes:
-        gt = json.loads((scene / "scene_gt.json").read_text())
-        cam = json.loads((scene / "scene_camera.json").read_text())
-        ids = sorted(gt, key=int)
+    meshes = MeshSet.from_dir(models_dir, device=device, scale=BD.unit_of(translation_scale))
+    scenes = BD.scene_dirs(dataset_dir, "train")
+    for scene in map(BD.BopScene, scenes):
+        gt, cam, ids = scene.gt, scene.camera, scene.image_ids
         info = {}
-        for d in ("mask", "mask_visib"):
-            (scene / d).mkdir(exist_ok=True)
+        scene.make_dirs(("mask", "mask_visib"))
         for b0 in range(0, len(ids), batch):
             chunk = ids[b0:b0 + batch]
-            depth = np.stack([decode_png((scene / "depth" / f"{int(i):06d}.png").read_bytes()).astype(np.float32) for i in chunk])
+            depth = np.stack([scene.read_png("depth", i).astype(np.float32) for i in chunk])
             masks, visibs, infos = gt_from_meshes(meshes, {str(k): gt[i] for k, i in enumerate(chunk)},
                                                   {str(k): cam[i] for k, i in enumerate(chunk)}, depth, delta=delta,
                                                   translation_scale=translation_scale)
@@ -354,8 +334,8 @@ def recompute_dataset(dataset_dir, models_dir, delta: float = 15.0, translation_
                 info[i] = infos[k]
                 for name, stack in (("mask", masks[k]), ("mask_visib", visibs[k])):
                     for o, image in enumerate((stack * 255).cpu().numpy()):
-                        (scene / name / f"{int(i):06d}_{o:06d}.png").write_bytes(encode_png(image))
-        (scene / "scene_gt_info.json").write_text(json.dumps({k: info[k] for k in ids}))
+                        scene.image_path(name, i, o).write_bytes(BD.encode_png(image))
+        scene.write_json(BD.SCENE_GT_INFO, {k: info[k] for k in ids})
     return scenes
 
 

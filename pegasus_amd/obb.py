@@ -14,14 +14,13 @@ from __future__ import annotations
 
 import argparse
 import json
-import re
 from dataclasses import dataclass
 from pathlib import Path
 from typing import Optional, Sequence
 
 import numpy as np
 
-from . import _lib
+from . import _lib, bop_dataset as BD
 
 NDDS_ORDER = (0, 2, 5, 3, 1, 7, 4, 6)           # pegasus_working.py:488-495, rows of open3d's GetBoxPoints
 
@@ -216,9 +215,7 @@ def models_boxes(models_dir, robust: bool = True, device="cuda") -> dict:
     """{obj_id: {"center", "R", "extent", "ndds_corners", "diameter"}} of every obj_NNNNNN.ply under ``models_dir``, in the
     files' own units."""
     from .ply_io import read_ply_mesh
-    files = {int(m.group(1)): p for p in sorted(Path(models_dir).glob("obj_*.ply")) if (m := re.fullmatch(r"obj_(\d+)", p.stem))}
-    if not files:
-        raise FileNotFoundError(f"no obj_NNNNNN.ply under {models_dir}")
+    files = BD.model_files(models_dir)
     ids = sorted(files)
     verts = [read_ply_mesh(files[i])[0] for i in ids]
     boxes = minimal_oriented_boxes(verts, robust, device)
@@ -233,25 +230,22 @@ def rewrite_dataset(dataset_dir, models_dir, translation_scale: float = 1.0, rob
     ``cam_t_m2c`` and scene_camera.json's ``cam_K``.  ``translation_scale`` is what the translations were written with."""
     from . import bop_pose
     from .mesh_render import MeshSet
-    boxes = boxes_for(MeshSet.from_dir(models_dir, device=device, scale=float(translation_scale) / 1000.0), robust)
-    scenes = sorted(p for p in (Path(dataset_dir) / "train").iterdir() if (p / "scene_gt.json").exists())
-    for scene in scenes:
-        gt = json.loads((scene / "scene_gt.json").read_text())
-        cam = json.loads((scene / "scene_camera.json").read_text())
-        for image, entries in gt.items():
-            K = np.asarray(cam[image]["cam_K"], np.float64).reshape(3, 3)
+    boxes = boxes_for(MeshSet.from_dir(models_dir, device=device, scale=BD.unit_of(translation_scale)), robust)
+    scenes = BD.scene_dirs(dataset_dir, "train")
+    for scene in map(BD.BopScene, scenes):
+        for image, entries in scene.gt.items():
+            K = BD.cam_K(scene.camera[image])
             for e in entries:
                 if int(e["obj_id"]) not in boxes:
-                    raise KeyError(f"{scene}: object {e['obj_id']} has no mesh under {models_dir}")
+                    raise KeyError(f"{scene.path}: object {e['obj_id']} has no mesh under {models_dir}")
                 corners, mean, center = boxes[int(e["obj_id"])]
                 T = np.eye(4)
-                T[:3, :3] = np.asarray(e["cam_R_m2c"], np.float64).reshape(3, 3)
-                T[:3, 3] = np.asarray(e["cam_t_m2c"], np.float64)
+                T[:3, :3], T[:3, 3] = BD.pose_of(e)
                 e["3d_bounding_box_model_coord"] = corners.tolist()
                 e["3d_bounding_center"] = mean.tolist()
                 e["projected_points"] = bop_pose.project_points(K, T, corners).tolist()
                 e["projected_center"] = bop_pose.project_points(K, T, center[None]).tolist()
-        (scene / "scene_gt.json").write_text(json.dumps(gt))
+        scene.write_json(BD.SCENE_GT, scene.gt)
     return scenes
 
 

@@ -14,15 +14,15 @@ points are the vertices a ``mesh_render.MeshSet`` holds on the device, the symme
 from __future__ import annotations
 
 import ctypes as C
-import json
 import math
-from pathlib import Path
 from typing import Optional, Sequence
 
 import numpy as np
 
 from . import _lib
-from .mesh_render import MeshSet, _K_list  # noqa: F401  (MeshSet is part of this module's interface)
+from .bop_dataset import read_models_info
+from .bop_pose import broadcast_K
+from .mesh_render import MeshSet
 
 ERROR_NAMES = ("mssd", "mspd", "add", "adi", "proj", "re", "te")
 SYM_CHUNK = _lib.PGR_POSE_SYM_CHUNK          # symmetries of a job that share one workgroup
@@ -122,8 +122,7 @@ class PoseErrorModels:
         """The ``obj_NNNNNN.ply`` files and ``models_info.json`` of a BOP models directory; ``scale`` multiplies the vertices,
         the diameters and the symmetries' translations and offsets alike (0.001: millimetres to metres)."""
         meshes = MeshSet.from_dir(models_dir, device=device, scale=scale)
-        path = Path(models_dir) / "models_info.json"
-        info = json.loads(path.read_text()) if path.exists() else {}
+        info = read_models_info(models_dir)
         return cls(meshes, {int(k): scaled_model_info(v, scale) for k, v in info.items()}, max_sym_disc_step)
 
     @classmethod
@@ -152,11 +151,7 @@ class PoseErrorModels:
 # ---- the batched call -----------------------------------------------------------------------------------------------
 def intrinsics(K, n: int) -> np.ndarray:
     """(fx, fy, cx, cy) float64 [n,4] of ``K`` [3,3] or [n,3,3]; a K with skew is refused."""
-    K = np.asarray(K, np.float64)
-    if K.shape == (3, 3):
-        K = np.broadcast_to(K, (n, 3, 3))
-    if K.shape != (n, 3, 3):
-        raise ValueError(f"K must be [3,3] or [{n},3,3]")
+    K = broadcast_K(K, n)
     if np.any(K[:, 0, 1] != 0.0) or np.any(K[:, 1, 0] != 0.0) or np.any(K[:, 2, :2] != 0.0):
         raise ValueError("K with skew (or a third row other than 0 0 1) is not supported")
     return np.stack([K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]], axis=1)

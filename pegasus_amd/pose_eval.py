@@ -14,13 +14,12 @@ from __future__ import annotations
 
 import argparse
 import json
-import struct
 from pathlib import Path
 from typing import Optional, Sequence
 
 import numpy as np
 
-from . import pose_error as PE
+from . import bop_dataset as BD, pose_error as PE
 
 VISIB_GT_MIN = 0.1
 VSD_DELTA = 15.0
@@ -74,16 +73,6 @@ def load_errors(path) -> list:
     return rows
 
 
-def image_width(scene_dir: Path) -> Optional[int]:
-    """The width of the scene's images, from the header of its first rgb (or depth) PNG."""
-    for sub in ("rgb", "depth"):
-        for p in sorted((scene_dir / sub).glob("*.png")) if (scene_dir / sub).is_dir() else []:
-            head = p.read_bytes()[:24]
-            if head[12:16] == b"IHDR":
-                return struct.unpack(">I", head[16:20])[0]
-    return None
-
-
 def scene_pairs(ests: Sequence[dict], scene_gt: dict, unit: float):
     """Every (estimate, ground-truth instance of its object in its image) pair of one scene.  Returns (errs, index, arrays):
     ``errs`` the error records with est_id counted per (image, object) in file order, ``index`` [(record, gt_id)] per pair,
@@ -100,8 +89,7 @@ def scene_pairs(ests: Sequence[dict], scene_gt: dict, unit: float):
             if int(gt["obj_id"]) != e["obj_id"]:
                 continue
             index.append((len(errs) - 1, gt_id))
-            for c, v in zip(cols, (e["obj_id"], e["R"], e["t"] * unit, np.asarray(gt["cam_R_m2c"], np.float64).reshape(3, 3),
-                                   np.asarray(gt["cam_t_m2c"], np.float64).reshape(3), e["im_id"])):
+            for c, v in zip(cols, (e["obj_id"], e["R"], e["t"] * unit, *BD.pose_of(gt), e["im_id"])):
                 c.append(v)
     return errs, index, cols
 
@@ -110,7 +98,7 @@ def evaluate(results, dataset, models_dir, split: str = "train", errors: Sequenc
              translation_scale: float = 1.0, vsd: bool = False, out: Optional[str] = None, device="cuda",
              width: Optional[int] = None) -> dict:
     """The average recalls {'AR_MSSD', 'AR_MSPD', ('AR_VSD',) 'AR'} of a results file; see the module's text."""
-    unit = float(translation_scale) / 1000.0
+    unit = BD.unit_of(translation_scale)
     models = PE.PoseErrorModels.from_dir(models_dir, device=device, scale=unit)
     ests = read_results(results)
     types = list(errors) + (["vsd"] if vsd else [])
@@ -119,11 +107,9 @@ def evaluate(results, dataset, models_dir, split: str = "train", errors: Sequenc
     per_type = {t: {} for t in types}                 # type -> scene -> error records (normalised for the thresholds)
     gts, valid, n_tops = {}, {}, {}
     for sid in scene_ids:
-        scene = Path(dataset) / split / f"{sid:06d}"
-        scene_gt = json.loads((scene / "scene_gt.json").read_text())
-        cam = json.loads((scene / "scene_camera.json").read_text())
-        info = json.loads((scene / "scene_gt_info.json").read_text())
-        w = width or image_width(scene) or 640
+        scene = BD.BopScene(BD.scene_dir(dataset, split, sid))
+        scene_gt, cam, info = scene.gt, scene.camera, scene.read_json(BD.SCENE_GT_INFO)
+        w = width or (scene.first_image_size() or (0, 0))[0] or 640          # MSPD is normalised to 640 px wide images
         gts[sid] = {int(i): [{"obj_id": int(g["obj_id"])} for g in v] for i, v in scene_gt.items()}
         valid[sid] = {int(i): [float(g["visib_fract"]) >= VISIB_GT_MIN for g in v] for i, v in info.items()}
         n_tops[sid] = {}
@@ -136,10 +122,10 @@ def evaluate(results, dataset, models_dir, split: str = "train", errors: Sequenc
         values = {}
         plain = [t for t in types if t != "vsd"]
         if index and plain:
-            K = np.stack([np.asarray(cam[str(i)]["cam_K"], np.float64).reshape(3, 3) for i in ims])
+            K = np.stack([BD.cam_K(cam[str(i)]) for i in ims])
             values = PE.pose_errors(models, objs, np.stack(R_est), np.stack(t_est), np.stack(R_gt), np.stack(t_gt), K, plain)
         if index and vsd:
-            values["vsd"] = _vsd_errors(models, scene, cam, objs, R_est, t_est, R_gt, t_gt, ims, unit)
+            values["vsd"] = _vsd_errors(models, scene, objs, R_est, t_est, R_gt, t_gt, ims, unit)
         for t in types:
             recs = [dict(e, errors={}) for e in errs]
             normed = [dict(e, errors={}) for e in errs]
@@ -155,7 +141,7 @@ def evaluate(results, dataset, models_dir, split: str = "train", errors: Sequenc
                 recs[r]["errors"][gt_id] = written.tolist()
                 normed[r]["errors"][gt_id] = norm.tolist()
             if out:
-                d = Path(out) / f"{sid:06d}"
+                d = Path(out) / BD.scene_name(sid)
                 d.mkdir(parents=True, exist_ok=True)
                 save_errors(d / f"errors_{t}.json", recs)
             per_type[t][sid] = normed
@@ -185,10 +171,9 @@ def _recall(scene_ids, obj_ids, gts, valid, n_tops, errs_by_scene, th, element: 
     return PE.localization_recall(scene_ids, obj_ids, matches, n_top=-1)["recall"]
 
 
-def _vsd_errors(models, scene: Path, cam, objs, R_est, t_est, R_gt, t_gt, ims, unit):
+def _vsd_errors(models, scene: BD.BopScene, objs, R_est, t_est, R_gt, t_gt, ims, unit):
     """VSD of every pair through mesh_render.vsd (normalised by the diameter, one value per tau), pairs of one ground truth
     in one call."""
-    from .dataset_writer import decode_png
     from .mesh_render import vsd
     if models.meshes is None:
         raise ValueError("VSD needs models with faces (PoseErrorModels.from_dir)")
@@ -198,12 +183,11 @@ def _vsd_errors(models, scene: Path, cam, objs, R_est, t_est, R_gt, t_gt, ims, u
         groups.setdefault((ims[p], objs[p], R_gt[p].tobytes(), t_gt[p].tobytes()), []).append(p)
     depth_of = {}
     for (im, obj, _, _), ps in groups.items():
+        cam = scene.camera[str(im)]
         if im not in depth_of:
-            raw = decode_png((scene / "depth" / f"{im:06d}.png").read_bytes()).astype(np.float32)
-            depth_of[im] = raw * np.float32(float(cam[str(im)].get("depth_scale", 1.0)) * unit)
-        K = np.asarray(cam[str(im)]["cam_K"], np.float64).reshape(3, 3)
-        e = vsd(np.stack([R_est[p] for p in ps]), np.stack([t_est[p] for p in ps]), R_gt[ps[0]], t_gt[ps[0]], depth_of[im], K,
-                VSD_DELTA * unit, list(VSD_TAUS), True, models.diameters[obj], models.meshes, obj)
+            depth_of[im] = scene.read_png("depth", im).astype(np.float32) * np.float32(BD.depth_unit(cam, unit))
+        e = vsd(np.stack([R_est[p] for p in ps]), np.stack([t_est[p] for p in ps]), R_gt[ps[0]], t_gt[ps[0]], depth_of[im],
+                BD.cam_K(cam), VSD_DELTA * unit, list(VSD_TAUS), True, models.diameters[obj], models.meshes, obj)
         out[ps] = e.cpu().numpy()
     return out
 

@@ -144,6 +144,28 @@ def test_recompute_dataset_reads_a_written_directory(tmp_path, golden_json, bbox
     assert undated(got) == undated(golden_json["scene"][bbox_type])
 
 
+def test_recompute_dataset_takes_the_image_size_from_rgb_then_the_first_mask_then_zero(tmp_path):
+    """Image 0 has an rgb PNG 7 wide and 2 high beside a 5 x 3 mask, image 1 only masks (the first one's header counts),
+    image 2 neither."""
+    from pegasus_amd import coco as CO, dataset_writer as DW
+    scene = tmp_path / "ds" / "train" / "000004"
+    for d in ("rgb", "mask_visib"):
+        (scene / d).mkdir(parents=True)
+    mask = np.zeros((3, 5), np.uint8)
+    mask[1, 1:4] = 255
+    (scene / "rgb" / "000000.png").write_bytes(DW.encode_png(np.zeros((2, 7, 3), np.uint8)))
+    for name in ("000000_000000.png", "000001_000000.png", "000001_000001.png"):
+        (scene / "mask_visib" / name).write_bytes(DW.encode_png(mask))
+    gt = {"0": [{"obj_id": 3}], "1": [{"obj_id": 3}, {"obj_id": 5}], "2": []}
+    (scene / "scene_gt.json").write_text(json.dumps(gt))
+    assert CO.recompute_dataset(tmp_path / "ds", "modal", backend=CR, batch=1) == [scene]
+    doc = json.loads((scene / "scene_gt_coco_modal.json").read_text())
+    assert [(i["id"], i["file_name"], i["width"], i["height"]) for i in doc["images"]] == [
+        (0, "rgb/000000.png", 7, 2), (1, "rgb/000001.png", 5, 3), (2, "rgb/000002.png", 0, 0)]
+    assert [(a["image_id"], a["category_id"], a["bbox"]) for a in doc["annotations"]] == [(0, 3, [1, 1, 3, 1]), (1, 3, [1, 1, 3, 1]),
+                                                                                           (1, 5, [1, 1, 3, 1])]
+
+
 def test_writer_merges_annotations_and_numbers_after_the_merge(tmp_path, golden_json):
     """Two writers of one scene (a view-sharded run): each keeps its frames' annotations WITHOUT ids; the merged writer
     numbers them in frame order -- also one that added no frame of its own and has box type and size from the others."""
