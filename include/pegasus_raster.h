@@ -385,6 +385,60 @@ size_t pgr_radius_count_workspace_bytes(int32_t n);
 int32_t pgr_radius_count(int32_t n, const float *xyz, double radius, int32_t cap, int32_t *counts, void *workspace,
                          size_t workspace_bytes, void *stream);
 
+/* Rigid registration of a source cloud to a target cloud (open3d's evaluate_registration / registration_icp, which the
+ * reference's marker alignment refines with: /root/reference/submodules/aruco-estimator/aruco_estimator/utils.py:82-98;
+ * pegasus_amd/registration.py drives these entries; DESIGN.md section 17 holds the rules).  Points are float32 [n,3] device
+ * arrays.  A `transformation` is a HOST pointer to a row-major float64 4x4 whose upper 3x4 is read and handed to the kernel
+ * by value; a value that is not finite is PGR_ERR_INVALID_ARGUMENT.  The posed source point is s' = R s + t in float64, each
+ * coordinate ((r0*x + r1*y) + r2*z) + t with every operation rounded on its own.  The caller's contract, which the entries
+ * cannot check: every target coordinate and every s' is finite with |x| / max_distance < 2^30.  Every argument check comes
+ * before any launch; a count of 0 returns PGR_OK without a launch; workspaces are 16-byte aligned.
+ *
+ * pgr_nn_grid_build files the target into pgr_radius_count's sparse grid with cells of max_distance * 1.0001, in a
+ * caller-owned workspace of pgr_nn_grid_build_workspace_bytes(n_target) bytes (0 for a negative count) that later calls read
+ * with the same n_target and max_distance, for as long as the target stays where it is.
+ *
+ * pgr_nn_correspond: for every source point the target of smallest d2 = ((dx*dx) + dy*dy) + dz*dz (dx = q.x - s'.x, float64,
+ * every operation rounded on its own), among equal d2 the lowest target index, accepted iff d2 < max_distance * max_distance
+ * (rounded once, compared STRICTLY): `index` int32 [n_source] (-1: none) and `d2` float64 [n_source] (0 where none), exact and
+ * identical from run to run.  `order` (device int32 [n_source], may be NULL = row order) is a permutation of the source rows:
+ * lane i works on point order[i]; it changes no result.  n_target == 0: every index is -1 and `grid` is not read.
+ *
+ * pgr_nn_source_order writes such a permutation: the source rows in the order of the grid cells their s' fall into (a grid of
+ * the source's own, in the workspace); pgr_nn_source_order_workspace_bytes(n_source) bytes.
+ *
+ * pgr_icp_sums: one pass over the source given `index` and `d2` as pgr_nn_correspond wrote them (an index outside
+ * [0, n_target) counts as none), reduced in a fixed order without floating-point atomics, so equal inputs give equal bytes.
+ * `sums` is device float64 [PGR_ICP_SUMS].  With q the correspondent, n its row of `target_normals` (device float64
+ * [n_target,3]; NULL: the first 27 sums are 0), r = (s' - q) . n and J = [s' x n, n]:
+ *   [0,21) the upper triangle of sum J^T J, row by row    [21,27) sum J^T r    [27] the count    [28] sum d2
+ *   [29,32) sum s'    [32,35) sum q    [35,44) sum s' q^T, row by row    [44] sum |s'|^2    [45,48) 0
+ * (point-to-plane reads [0,32), point-to-point [16,48)).  Workspace: pgr_icp_sums_workspace_bytes(n_source) bytes.
+ *
+ * pgr_radius_normals (open3d's estimate_normals(KDTreeSearchParamRadius(radius)): /root/reference/src/gs/ao_test.py:21): for
+ * every point the float64 covariance of the points within `radius` of it -- pgr_radius_count's strict test, the point itself
+ * included -- and of it the unit eigenvector of the smallest eigenvalue, signed so that its component of largest magnitude is
+ * positive; (0,0,1) with fewer than 3 neighbours.  `normals` float64 [n,3], `counts` int32 [n] (exact).  The neighbour sums
+ * run in grid order, so the normals may differ in their last bits from run to run; the counts may not.  Workspace:
+ * pgr_radius_normals_workspace_bytes(n) bytes; the contract on the coordinates is pgr_radius_count's. */
+#define PGR_ICP_SUMS 48
+size_t pgr_nn_grid_build_workspace_bytes(int32_t n_target);
+int32_t pgr_nn_grid_build(int32_t n_target, const float *target, double max_distance, void *workspace, size_t workspace_bytes,
+                          void *stream);
+size_t pgr_nn_source_order_workspace_bytes(int32_t n_source);
+int32_t pgr_nn_source_order(int32_t n_source, const float *source, const double *transformation, double max_distance,
+                            int32_t *order, void *workspace, size_t workspace_bytes, void *stream);
+int32_t pgr_nn_correspond(int32_t n_source, const float *source, const int32_t *order, const double *transformation,
+                          int32_t n_target, double max_distance, const void *grid, size_t grid_bytes, int32_t *index,
+                          double *d2, void *stream);
+size_t pgr_icp_sums_workspace_bytes(int32_t n_source);
+int32_t pgr_icp_sums(int32_t n_source, const float *source, const double *transformation, const int32_t *index,
+                     const double *d2, int32_t n_target, const float *target, const double *target_normals, double *sums,
+                     void *workspace, size_t workspace_bytes, void *stream);
+size_t pgr_radius_normals_workspace_bytes(int32_t n);
+int32_t pgr_radius_normals(int32_t n, const float *xyz, double radius, double *normals, int32_t *counts, void *workspace,
+                           size_t workspace_bytes, void *stream);
+
 /* Object meshes from a trained model's rendered views (pegasus_amd/mesh.py; replaces the open3d alpha shape of the
  * reference's reconstruction step).  A regular grid: point (i,j,k) sits at origin + voxel*(i,j,k); a field over it is
  * float32 [nz,ny,nx], x fastest.  Every axis holds 2 .. 1024 points.  Results are identical from run to run. */

@@ -222,6 +222,19 @@ SYMBOLS = {
     "pgr_radius_count_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "pgr_radius_count": (C.c_int32, [C.c_int32, C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
                                      C.c_void_p]),
+    "pgr_nn_grid_build_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "pgr_nn_grid_build": (C.c_int32, [C.c_int32, C.c_void_p, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pgr_nn_source_order_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "pgr_nn_source_order": (C.c_int32, [C.c_int32, C.c_void_p, C.POINTER(C.c_double), C.c_double, C.c_void_p, C.c_void_p,
+                                        C.c_size_t, C.c_void_p]),
+    "pgr_nn_correspond": (C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int32, C.c_double,
+                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pgr_icp_sums_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "pgr_icp_sums": (C.c_int32, [C.c_int32, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pgr_radius_normals_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "pgr_radius_normals": (C.c_int32, [C.c_int32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                       C.c_void_p]),
     "pgr_quantize_frame": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),
     "pgr_pack_frames": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

@@ -30,6 +30,7 @@
 #include "poseerr.hip.h"
 #include "preprocess.hip.h"
 #include "radius.hip.h"
+#include "registration.hip.h"
 #include "tilebin.hip.h"
 #include "tilesort.hip.h"
 #include "train.hip.h"
@@ -1119,6 +1120,145 @@ int32_t pgr_radius_count(int32_t n, const float* xyz, double radius, int32_t cap
     radius_scatter_kernel<<<blocks, RADIUS_BLOCK, 0, stream>>>(n, xyz, point_slot, begin, sorted);
     radius_count_kernel<<<blocks, RADIUS_BLOCK, 0, stream>>>(n, sorted, slots, begin, mask, inv_h, r2, cap, counts);
     return hip_ok(hipGetLastError(), "radius count launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+// ---- registration: correspondences, ICP sums, normals by radius (registration.hip.h) --------------------------------------
+namespace {
+struct RadiusGrid { uint32_t* total; RadiusSlot* slots; uint32_t* begin; uint32_t* point_slot; float4* sorted; uint32_t mask; };
+RadiusGrid radius_grid(const RadiusLayout& R, void* workspace) {
+    char* ws = static_cast<char*>(workspace);
+    return RadiusGrid{reinterpret_cast<uint32_t*>(ws + R.total_word), reinterpret_cast<RadiusSlot*>(ws + R.slots),
+                      reinterpret_cast<uint32_t*>(ws + R.begin), reinterpret_cast<uint32_t*>(ws + R.point_slot),
+                      reinterpret_cast<float4*>(ws + R.sorted), (uint32_t)(R.n_slots - 1)};
+}
+// files the n points of `xyz` into the grid (the first three kernels of pgr_radius_count); afterwards begin[] holds the ends
+bool radius_grid_build(int32_t n, const float* xyz, double inv_h, const RadiusLayout& R, const RadiusGrid& G, hipStream_t stream) {
+    if (!hip_ok(hipMemsetAsync(G.total, 0, R.begin - R.total_word, stream), "memset radius table")) return false;
+    const int blocks = (n + RADIUS_BLOCK - 1) / RADIUS_BLOCK;
+    radius_insert_kernel<<<blocks, RADIUS_BLOCK, 0, stream>>>(n, xyz, inv_h, G.slots, G.mask, G.point_slot);
+    radius_ranges_kernel<<<(unsigned)(R.n_slots / RADIUS_BLOCK), RADIUS_BLOCK, 0, stream>>>(G.slots, G.begin, G.total);
+    radius_scatter_kernel<<<blocks, RADIUS_BLOCK, 0, stream>>>(n, xyz, G.point_slot, G.begin, G.sorted);
+    return true;
+}
+bool distance_ok(double d) { return std::isfinite(d) && d > 0.0; }
+// the 3x4 of a row-major 4x4 (the last row is not read); false for NULL or a value that is not finite
+bool reg_pose(const double* T, RegPose& P) {
+    if (!T) return false;
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) P.r[3 * r + c] = T[4 * r + c];
+        P.t[r] = T[4 * r + 3];
+    }
+    for (double v : P.r) if (!std::isfinite(v)) return false;
+    for (double v : P.t) if (!std::isfinite(v)) return false;
+    return true;
+}
+int32_t reg_blocks(int32_t n) { return (n + REG_BLOCK - 1) / REG_BLOCK; }
+// the posed source as float32 in front of a grid's layout
+struct OrderLayout { size_t posed, grid, total; };
+OrderLayout order_layout(int32_t n) {
+    Carver c;
+    OrderLayout L{};
+    L.posed = c.take((size_t)(n > 0 ? n : 1) * 3 * sizeof(float));
+    L.grid = c.off;
+    L.total = L.grid + radius_layout(n).total;
+    return L;
+}
+}  // namespace
+
+size_t pgr_nn_grid_build_workspace_bytes(int32_t n_target) { return n_target < 0 ? 0 : radius_layout(n_target).total; }
+
+int32_t pgr_nn_grid_build(int32_t n_target, const float* target, double max_distance, void* workspace, size_t workspace_bytes,
+                          void* stream_v) {
+    if (n_target < 0 || !distance_ok(max_distance)) return PGR_ERR_INVALID_ARGUMENT;
+    if (n_target == 0) return PGR_OK;
+    if (!target || !workspace || !workspace_aligned_16(workspace)) return PGR_ERR_INVALID_ARGUMENT;
+    const RadiusLayout R = radius_layout(n_target);
+    if (workspace_bytes < R.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    if (!radius_grid_build(n_target, target, 1.0 / (max_distance * RADIUS_CELL_MARGIN), R, radius_grid(R, workspace), stream))
+        return PGR_ERR_LAUNCH_FAILURE;
+    return hip_ok(hipGetLastError(), "nn grid launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+size_t pgr_nn_source_order_workspace_bytes(int32_t n_source) { return n_source < 0 ? 0 : order_layout(n_source).total; }
+
+int32_t pgr_nn_source_order(int32_t n_source, const float* source, const double* transformation, double max_distance,
+                            int32_t* order, void* workspace, size_t workspace_bytes, void* stream_v) {
+    RegPose P;
+    if (n_source < 0 || !distance_ok(max_distance) || !reg_pose(transformation, P)) return PGR_ERR_INVALID_ARGUMENT;
+    if (n_source == 0) return PGR_OK;
+    if (!source || !order || !workspace || !workspace_aligned_16(workspace)) return PGR_ERR_INVALID_ARGUMENT;
+    const OrderLayout L = order_layout(n_source);
+    if (workspace_bytes < L.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    char* ws = static_cast<char*>(workspace);
+    auto* posed = reinterpret_cast<float*>(ws + L.posed);
+    const RadiusLayout R = radius_layout(n_source);
+    const RadiusGrid G = radius_grid(R, ws + L.grid);
+    registration_pose_kernel<<<reg_blocks(n_source), REG_BLOCK, 0, stream>>>(n_source, source, P, posed);
+    if (!radius_grid_build(n_source, posed, 1.0 / (max_distance * RADIUS_CELL_MARGIN), R, G, stream)) return PGR_ERR_LAUNCH_FAILURE;
+    registration_order_kernel<<<reg_blocks(n_source), REG_BLOCK, 0, stream>>>(n_source, G.sorted, order);
+    return hip_ok(hipGetLastError(), "nn source order launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+int32_t pgr_nn_correspond(int32_t n_source, const float* source, const int32_t* order, const double* transformation,
+                          int32_t n_target, double max_distance, const void* grid, size_t grid_bytes, int32_t* index,
+                          double* d2, void* stream_v) {
+    RegPose P;
+    if (n_source < 0 || n_target < 0 || !distance_ok(max_distance) || !reg_pose(transformation, P)) return PGR_ERR_INVALID_ARGUMENT;
+    if (n_source == 0) return PGR_OK;
+    if (!source || !index || !d2) return PGR_ERR_INVALID_ARGUMENT;
+    const RadiusLayout R = radius_layout(n_target);
+    RadiusGrid G{};
+    if (n_target > 0) {
+        if (!grid || !workspace_aligned_16(grid)) return PGR_ERR_INVALID_ARGUMENT;
+        if (grid_bytes < R.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
+        G = radius_grid(R, const_cast<void*>(grid));
+    }
+    registration_correspond_kernel<<<reg_blocks(n_source), REG_BLOCK, 0, static_cast<hipStream_t>(stream_v)>>>(
+        n_source, source, order, P, n_target, G.sorted, G.slots, G.begin, G.mask, 1.0 / (max_distance * RADIUS_CELL_MARGIN),
+        max_distance * max_distance, index, d2);
+    return hip_ok(hipGetLastError(), "nn correspond launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+size_t pgr_icp_sums_workspace_bytes(int32_t n_source) {
+    return n_source < 0 ? 0 : align_up((size_t)std::max(reg_blocks(n_source), 1) * REG_SUMS * sizeof(double));
+}
+
+int32_t pgr_icp_sums(int32_t n_source, const float* source, const double* transformation, const int32_t* index,
+                     const double* d2, int32_t n_target, const float* target, const double* target_normals, double* sums,
+                     void* workspace, size_t workspace_bytes, void* stream_v) {
+    RegPose P;
+    if (n_source < 0 || n_target < 0 || !reg_pose(transformation, P) || !sums) return PGR_ERR_INVALID_ARGUMENT;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    if (n_source == 0 || n_target == 0)                          // nothing corresponds: every sum is 0
+        return hip_ok(hipMemsetAsync(sums, 0, REG_SUMS * sizeof(double), stream), "memset icp sums") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+    if (!source || !index || !d2 || !target || !workspace || !workspace_aligned_16(workspace)) return PGR_ERR_INVALID_ARGUMENT;
+    if (workspace_bytes < pgr_icp_sums_workspace_bytes(n_source)) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    auto* partials = static_cast<double*>(workspace);
+    const int32_t blocks = reg_blocks(n_source);
+    registration_sums_kernel<<<blocks, REG_BLOCK, 0, stream>>>(n_source, source, P, index, d2, n_target, target, target_normals,
+                                                               partials);
+    registration_sums_final_kernel<<<1, REG_FINAL_BLOCK, 0, stream>>>(blocks, partials, sums);
+    return hip_ok(hipGetLastError(), "icp sums launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+size_t pgr_radius_normals_workspace_bytes(int32_t n) { return n < 0 ? 0 : radius_layout(n).total; }
+
+int32_t pgr_radius_normals(int32_t n, const float* xyz, double radius, double* normals, int32_t* counts, void* workspace,
+                           size_t workspace_bytes, void* stream_v) {
+    if (n < 0 || !distance_ok(radius)) return PGR_ERR_INVALID_ARGUMENT;
+    if (n == 0) return PGR_OK;
+    if (!xyz || !normals || !counts || !workspace || !workspace_aligned_16(workspace)) return PGR_ERR_INVALID_ARGUMENT;
+    const RadiusLayout R = radius_layout(n);
+    if (workspace_bytes < R.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    const RadiusGrid G = radius_grid(R, workspace);
+    const double inv_h = 1.0 / (radius * RADIUS_CELL_MARGIN);
+    if (!radius_grid_build(n, xyz, inv_h, R, G, stream)) return PGR_ERR_LAUNCH_FAILURE;
+    registration_normals_kernel<<<reg_blocks(n), REG_BLOCK, 0, stream>>>(n, G.sorted, G.slots, G.begin, G.mask, inv_h,
+                                                                        radius * radius, normals, counts);
+    return hip_ok(hipGetLastError(), "radius normals launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
 }
 
 // ---- object meshes: TSDF fusion of rendered views, marching tetrahedra (mesh.hip.h) ------------------------------------
