@@ -884,6 +884,44 @@ int32_t pgr_adam_step(const PgrAdamGroup *groups, int32_t n_groups, double beta1
 int32_t pgr_densify_stats(int32_t n, const float *viewspace_grad, int32_t grad_stride, const int32_t *radii,
                           float *grad_accum, float *denom, float *max_radii2d, void *stream);
 
+/* ---- ground plane by RANSAC (pegasus_amd/alignment.py) --------------------------------------------------------------------
+ * The dominant plane of a point cloud (open3d's segment_plane, on which the reference's ReconstructionAlignment.align2plane
+ * rests: /root/reference/src/reconstruction/environment_reconstruction.py:53-66; DESIGN.md section 18 holds the rules).
+ * `xyz` is a device float32 [n,3]; a plane is four float64 (nx, ny, nz, d).  Every argument check comes before any launch:
+ * PGR_ERR_INVALID_ARGUMENT for a needed NULL, a negative count, a workspace that is not 16-byte aligned, a threshold that is
+ * not finite and positive or (pgr_plane_inliers) a plane or pivot value that is not finite; PGR_ERR_WORKSPACE_TOO_SMALL
+ * otherwise.  A count of 0 returns PGR_OK without a launch (outputs that have rows are set to 0).  The size functions return 0
+ * for a negative count.  Results are identical from call to call.  The caller's contract, which the entries cannot check:
+ * every coordinate is finite.
+ *
+ * pgr_plane_hypotheses: the plane through rows (i0, i1, i2) of `triples` (device int32 [n_hyp,3]).  With the points widened
+ * exactly to float64 and every operation rounded on its own: e1 = p1 - p0, e2 = p2 - p0, c = e1 x e2 (each component
+ * (a*b) - (c*d)), norm = sqrt(((cx*cx) + cy*cy) + cz*cz), nrm = c / norm, d = -(((nx*x0) + ny*y0) + nz*z0).  `planes` float64
+ * [n_hyp,4], `valid` uint8 [n_hyp].  A row outside [0, n) is never dereferenced: such a triple, one with two equal rows, a norm
+ * of 0 and a norm that is not finite give four zeros and valid = 0.
+ *
+ * pgr_plane_score: every plane against every point.  dist = |((nx*x + ny*y) + nz*z) + d| in float64, every operation rounded
+ * on its own; the point is an inlier iff dist < threshold (STRICTLY).  counts int32 [n_hyp] (exact), sumsq float64 [n_hyp]:
+ * the sum of dist*dist over the inliers, in a fixed order without floating-point atomics.  A plane of four zeros scores 0, 0.
+ * The points are read once per call; workspace: pgr_plane_score_workspace_bytes(n, n_hyp) bytes, 12 bytes per hypothesis and
+ * PGR_PLANE_TILE points.
+ *
+ * pgr_plane_inliers: one pass under one plane.  `plane` (HOST float64 [4]) and `pivot` (HOST float64 [3]) are read during the
+ * call and handed to the kernel by value.  mask (device uint8 [n], may be NULL): 1 for the inliers.  sums (device float64
+ * [PGR_PLANE_SUMS]) over the inliers, with q = p - pivot in float64: [0] the count (a sum of ones)  [1,4) sum q  [4,10) the
+ * upper triangle of sum q q^T, row by row  [10] sum dist*dist  [11] 0.  A plane of four zeros has no inliers.  Workspace:
+ * pgr_plane_inliers_workspace_bytes(n) bytes. */
+#define PGR_PLANE_SUMS 12
+#define PGR_PLANE_TILE 2048
+int32_t pgr_plane_hypotheses(int32_t n, const float *xyz, int32_t n_hyp, const int32_t *triples, double *planes, uint8_t *valid,
+                             void *stream);
+size_t pgr_plane_score_workspace_bytes(int32_t n, int32_t n_hyp);
+int32_t pgr_plane_score(int32_t n, const float *xyz, int32_t n_hyp, const double *planes, double threshold, int32_t *counts,
+                        double *sumsq, void *workspace, size_t workspace_bytes, void *stream);
+size_t pgr_plane_inliers_workspace_bytes(int32_t n);
+int32_t pgr_plane_inliers(int32_t n, const float *xyz, const double *plane, const double *pivot, double threshold,
+                          uint8_t *mask, double *sums, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -174,6 +174,8 @@ PGR_RLE_DECODE_CHUNK, PGR_RLE_DECODE_MIN_SLICE, PGR_RLE_DECODE_MAX_SLICES, PGR_M
 PGR_MASK_STATS = 6           # n_counts, area, x_min, y_min, x_max, y_max
 # include/pegasus_raster.h: the shapes at which the COCO score kernels change path, and their limits
 PGR_COCO_CHUNK, PGR_COCO_LDS_RUNS, PGR_COCO_MAX_LANES, PGR_COCO_MAX_MAXDETS = 256, 4096, 64, 8
+# include/pegasus_raster.h: the sums of pgr_plane_inliers and the points of one workgroup of pgr_plane_score
+PGR_PLANE_SUMS, PGR_PLANE_TILE = 12, 2048
 
 
 class PgrCocoGroup(C.Structure):
@@ -235,6 +237,13 @@ SYMBOLS = {
     "pgr_radius_normals_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "pgr_radius_normals": (C.c_int32, [C.c_int32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                        C.c_void_p]),
+    "pgr_plane_hypotheses": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pgr_plane_score_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "pgr_plane_score": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pgr_plane_inliers_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "pgr_plane_inliers": (C.c_int32, [C.c_int32, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pgr_quantize_frame": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),
     "pgr_pack_frames": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

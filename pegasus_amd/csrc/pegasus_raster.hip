@@ -27,6 +27,7 @@
 #include "compose.hip.h"
 #include "composite.hip.h"
 #include "pgr_common.h"
+#include "plane.hip.h"
 #include "poseerr.hip.h"
 #include "preprocess.hip.h"
 #include "radius.hip.h"
@@ -1259,6 +1260,98 @@ int32_t pgr_radius_normals(int32_t n, const float* xyz, double radius, double* n
     registration_normals_kernel<<<reg_blocks(n), REG_BLOCK, 0, stream>>>(n, G.sorted, G.slots, G.begin, G.mask, inv_h,
                                                                         radius * radius, normals, counts);
     return hip_ok(hipGetLastError(), "radius normals launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+// ---- ground plane by RANSAC: hypotheses, scores, the inlier pass (plane.hip.h) --------------------------------------------
+namespace {
+static_assert(PLANE_TILE == PGR_PLANE_TILE, "include/pegasus_raster.h names the tile of plane_score_kernel");
+int32_t plane_blocks(int32_t n, int32_t per_block) { return std::max((int32_t)(((int64_t)n + per_block - 1) / per_block), 1); }
+// the workgroups' partials of pgr_plane_score: the sums [blocks, n_hyp] in front of the counts [blocks, n_hyp]
+struct PlaneScoreLayout { size_t sumsq, count, total; int32_t blocks; };
+PlaneScoreLayout plane_score_layout(int32_t n, int32_t n_hyp) {
+    PlaneScoreLayout L{};
+    L.blocks = plane_blocks(n, PLANE_TILE);
+    const size_t cells = (size_t)L.blocks * (size_t)std::max(n_hyp, 1);
+    Carver c;
+    L.sumsq = c.take(cells * sizeof(double));
+    L.count = c.take(cells * sizeof(int32_t));
+    L.total = c.off;
+    return L;
+}
+}  // namespace
+
+int32_t pgr_plane_hypotheses(int32_t n, const float* xyz, int32_t n_hyp, const int32_t* triples, double* planes, uint8_t* valid,
+                             void* stream_v) {
+    if (n < 0 || n_hyp < 0) return PGR_ERR_INVALID_ARGUMENT;
+    if (n_hyp == 0) return PGR_OK;
+    if (!triples || !planes || !valid || (n > 0 && !xyz)) return PGR_ERR_INVALID_ARGUMENT;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    if (n == 0) {                                                // no row is inside [0, 0): every hypothesis is invalid
+        if (!hip_ok(hipMemsetAsync(planes, 0, (size_t)n_hyp * 4 * sizeof(double), stream), "memset planes") ||
+            !hip_ok(hipMemsetAsync(valid, 0, (size_t)n_hyp, stream), "memset plane validity"))
+            return PGR_ERR_LAUNCH_FAILURE;
+        return PGR_OK;
+    }
+    plane_hypotheses_kernel<<<plane_blocks(n_hyp, PLANE_BLOCK), PLANE_BLOCK, 0, stream>>>(n, xyz, n_hyp, triples, planes, valid);
+    return hip_ok(hipGetLastError(), "plane hypotheses launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+size_t pgr_plane_score_workspace_bytes(int32_t n, int32_t n_hyp) {
+    return n < 0 || n_hyp < 0 ? 0 : plane_score_layout(n, n_hyp).total;
+}
+
+int32_t pgr_plane_score(int32_t n, const float* xyz, int32_t n_hyp, const double* planes, double threshold, int32_t* counts,
+                        double* sumsq, void* workspace, size_t workspace_bytes, void* stream_v) {
+    if (n < 0 || n_hyp < 0 || !distance_ok(threshold)) return PGR_ERR_INVALID_ARGUMENT;
+    if (n_hyp == 0) return PGR_OK;
+    if (!counts || !sumsq) return PGR_ERR_INVALID_ARGUMENT;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    if (n == 0) {                                                // no point: every score is 0
+        if (!hip_ok(hipMemsetAsync(counts, 0, (size_t)n_hyp * sizeof(int32_t), stream), "memset plane counts") ||
+            !hip_ok(hipMemsetAsync(sumsq, 0, (size_t)n_hyp * sizeof(double), stream), "memset plane sums"))
+            return PGR_ERR_LAUNCH_FAILURE;
+        return PGR_OK;
+    }
+    if (!xyz || !planes || !workspace || !workspace_aligned_16(workspace)) return PGR_ERR_INVALID_ARGUMENT;
+    const PlaneScoreLayout L = plane_score_layout(n, n_hyp);
+    if (workspace_bytes < L.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    char* ws = static_cast<char*>(workspace);
+    auto* part_sumsq = reinterpret_cast<double*>(ws + L.sumsq);
+    auto* part_count = reinterpret_cast<int32_t*>(ws + L.count);
+    // few tiles: the batches of hypotheses are spread over gridDim.y (at most PLANE_SCORE_MIN_BLOCKS groups)
+    const int32_t batches = plane_blocks(n_hyp, PLANE_HYP_BATCH);
+    const int32_t wanted = std::min(batches, (PLANE_SCORE_MIN_BLOCKS + L.blocks - 1) / L.blocks);
+    const int32_t per_group = (batches + wanted - 1) / wanted;
+    const dim3 grid((unsigned)L.blocks, (unsigned)((batches + per_group - 1) / per_group));
+    plane_score_kernel<<<grid, PLANE_BLOCK, 0, stream>>>(n, xyz, n_hyp, planes, threshold, per_group, part_sumsq, part_count);
+    if (!hip_ok(hipGetLastError(), "plane score launch")) return PGR_ERR_LAUNCH_FAILURE;     // (no second pass over nothing)
+    plane_score_final_kernel<<<plane_blocks(n_hyp, PLANE_BLOCK), PLANE_BLOCK, 0, stream>>>(L.blocks, n_hyp, part_sumsq, part_count,
+                                                                                        counts, sumsq);
+    return hip_ok(hipGetLastError(), "plane score final launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+size_t pgr_plane_inliers_workspace_bytes(int32_t n) {
+    return n < 0 ? 0 : align_up((size_t)plane_blocks(n, PLANE_BLOCK) * PLANE_SUM_TERMS * sizeof(double));
+}
+
+int32_t pgr_plane_inliers(int32_t n, const float* xyz, const double* plane, const double* pivot, double threshold, uint8_t* mask,
+                          double* sums, void* workspace, size_t workspace_bytes, void* stream_v) {
+    if (n < 0 || !distance_ok(threshold) || !plane || !pivot || !sums) return PGR_ERR_INVALID_ARGUMENT;
+    PlaneModel P{{plane[0], plane[1], plane[2]}, plane[3], {pivot[0], pivot[1], pivot[2]}};
+    for (double v : {P.n[0], P.n[1], P.n[2], P.d, P.pivot[0], P.pivot[1], P.pivot[2]})
+        if (!std::isfinite(v)) return PGR_ERR_INVALID_ARGUMENT;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    if (n == 0)                                                  // no point: every sum is 0
+        return hip_ok(hipMemsetAsync(sums, 0, PLANE_SUM_TERMS * sizeof(double), stream), "memset plane sums") ? PGR_OK
+                                                                                                                 : PGR_ERR_LAUNCH_FAILURE;
+    if (!xyz || !workspace || !workspace_aligned_16(workspace)) return PGR_ERR_INVALID_ARGUMENT;
+    if (workspace_bytes < pgr_plane_inliers_workspace_bytes(n)) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    auto* partials = static_cast<double*>(workspace);
+    const int32_t blocks = plane_blocks(n, PLANE_BLOCK);
+    plane_inliers_kernel<<<blocks, PLANE_BLOCK, 0, stream>>>(n, xyz, P, threshold, mask, partials);
+    if (!hip_ok(hipGetLastError(), "plane inliers launch")) return PGR_ERR_LAUNCH_FAILURE;
+    plane_inliers_final_kernel<<<1, PLANE_FINAL_BLOCK, 0, stream>>>(blocks, partials, sums);
+    return hip_ok(hipGetLastError(), "plane inliers final launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
 }
 
 // ---- object meshes: TSDF fusion of rendered views, marching tetrahedra (mesh.hip.h) ------------------------------------

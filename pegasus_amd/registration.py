@@ -84,7 +84,8 @@ def _rigid(T, what="transformation"):
     R = T[:3, :3]
     if np.abs(R.T @ R - np.eye(3)).max() > ROTATION_TOL or abs(np.linalg.det(R) - 1.0) > ROTATION_TOL:
         scale = float(np.cbrt(abs(np.linalg.det(R))))
-        raise ValueError(f"the 3x3 block of {what} is not a rotation (scale {scale:.6g}); scaling a model is not supported")
+        raise ValueError(f"the 3x3 block of {what} is not a rotation (scale {scale:.6g}); scaling a model is not supported here "
+                         "(pegasus_amd.alignment.transform_model applies a similarity)")
     if not np.array_equal(T[3], [0.0, 0.0, 0.0, 1.0]):
         raise ValueError(f"the last row of {what} must be 0 0 0 1")
     return T
@@ -409,7 +410,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         R, c, t = kabsch_umeyama(np.loadtxt(a.points_target, ndmin=2), np.loadtxt(a.points_source, ndmin=2))
         if abs(c - 1.0) > 0.01:
             raise SystemExit(f"the picked points give a scale of {c:.6g} between the two scans: more than 1 % from 1, and "
-                             "scaling a model is not supported")
+                             "scaling a model is not supported here (pegasus_amd.alignment.transform_model applies a "
+                             "similarity)")
         init = np.eye(4)
         init[:3, :3], init[:3, 3] = R, t
     target, source = GaussianModel(3), GaussianModel(3)
