@@ -303,6 +303,14 @@ int32_t pgr_block_visibility(const PgrScene *scene, int32_t n_views, const PgrCa
 int32_t pgr_workspace_view(void *workspace, size_t workspace_bytes, int32_t n, int32_t width, int32_t height,
                            int64_t max_instances, int32_t n_views, int32_t view_index, PgrWorkspaceView *view);
 
+/* Where a batch call of that shape (not a layered one) leaves its block-visibility words in its workspace: *vis_words is
+ * the device pointer of [ceil(n / 64) * *words_per_block] words in pgr_block_visibility's layout, or NULL when such a call
+ * runs no block test (environment PGR_BLOCK_CULL=0, one- and two-view calls, a small scene whose views are spread over the
+ * grid) -- decided by the function the forward call itself asks.  Host only: launches nothing, reads no device memory. */
+int32_t pgr_workspace_block_visibility(void *workspace, size_t workspace_bytes, int32_t n, int32_t width,
+                                       int32_t height, int64_t max_instances, int32_t n_views,
+                                       const uint32_t **vis_words, int32_t *words_per_block);
+
 /* Rigid pose of one object, host struct (copied into the launch).  R row-major, q = R as a unit quaternion
  * (w,x,y,z), D1/D2/D3 = real-SH band rotation matrices (row-major, c' = D c) for the rasterizer's basis. */
 typedef struct PgrObjectPose {

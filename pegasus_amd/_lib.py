@@ -203,6 +203,8 @@ SYMBOLS = {
                                      C.c_void_p, C.c_int64, C.c_void_p]),
     "pgr_workspace_view": (C.c_int32, [C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
                                        C.c_int32, C.c_int32, C.POINTER(PgrWorkspaceView)]),
+    "pgr_workspace_block_visibility": (C.c_int32, [C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                                   C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]),
     "pgr_backward": (C.c_int32, [C.POINTER(PgrBackwardCall), C.c_void_p]),
     "pgr_backward_batch_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "pgr_camera_grad_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),

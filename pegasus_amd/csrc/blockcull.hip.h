@@ -13,7 +13,9 @@
 // Result-preserving by construction: the test only ever claims "every Gaussian of this block is culled by the exact
 // per-Gaussian code", with margins far above fp32 rounding, and answers "visible" whenever it cannot tell (box across
 // the near plane, non-finite numbers, posed objects).  Any storage order is correct; a spatially incoherent one just
-// has boxes too big to cull.  tests/test_block_cull.py: bit-identical radii, lists and images with the test on and off.
+// has boxes too big to cull.  tests/test_block_cull.py: bit-identical radii, lists and images with the test on and off;
+// tests/test_block_cull_edges_gpu.py: blocks built onto the edges of the bound below (its tightest fixture leaves it 1.6 px),
+// against three independent radii, for these bits and for the ones a batch call computes in its preprocess waves.
 #pragma once
 #include "pgr_common.h"
 

@@ -76,6 +76,15 @@ static bool block_cull_enabled() {
 }
 
 
+// Does a batch call of this shape run the block test (blockcull.hip.h) inside its preprocess?  Not when it is switched off,
+// not for one- and two-view calls (bounding the blocks costs their latency-bound preprocess more than it returns), and not
+// when a small scene's views are spread over gridDim.y (split_views_shape: the visibility words hold 32 views).  The one
+// place this is decided: forward_batch_impl and pgr_workspace_block_visibility both ask here.
+static bool split_views_shape(int n, int n_views) { return n <= PRE_SMALL_SCENE && n_views >= 2 * PRE_VIEW_GROUP; }
+static bool call_runs_block_cull(int n, int n_views) {
+    return block_cull_enabled() && n_views > SMALL_BATCH_VIEWS && !split_views_shape(n, n_views);
+}
+
 static bool records_enabled() {      // PGR_BIN_RECORDS=0: the scatter walk re-evaluates every candidate (A/B, tests)
     const char* e = getenv("PGR_BIN_RECORDS");
     return !(e && e[0] == '0');
@@ -427,10 +436,10 @@ static int32_t forward_batch_impl(const PgrScene* scene, int n_views, const PgrC
     // small scene, many views (an objects-only pass, a single object): the batch's views are spread over gridDim.y in groups of
     // PRE_VIEW_GROUP instead of walked by one wave -- 200 k Gaussians are 3 000 waves, a quarter of what the chip holds, and 32
     // views in a row per wave cost 0.31 ms where the arithmetic is 0.1.  Block culling is off there (its words hold 32 views).
-    const bool split_views = N <= PRE_SMALL_SCENE && n_views >= 2 * PRE_VIEW_GROUP;
+    const bool split_views = split_views_shape(N, n_views);
     const int view_groups = split_views ? (n_views + PRE_VIEW_GROUP - 1) / PRE_VIEW_GROUP : 1;
     const int views_per_block = split_views ? PRE_VIEW_GROUP : n_views;
-    uint32_t* vis = block_cull_enabled() && n_views > SMALL_BATCH_VIEWS && !split_views ? reinterpret_cast<uint32_t*>(ws + B.vis) : nullptr;
+    uint32_t* vis = call_runs_block_cull(N, n_views) ? reinterpret_cast<uint32_t*>(ws + B.vis) : nullptr;
     // one pass over the Gaussians for the whole batch (scene data read once, per-view outputs written)
     const PosedDev pd{posed ? posed->object_id : nullptr, posed ? posed->poses : nullptr, posed ? posed->k_objects : 0};
     const int deg = scene->shs ? scene->sh_degree : 0;
@@ -707,6 +716,22 @@ int32_t pgr_workspace_view(void* workspace, size_t workspace_bytes, int32_t n, i
     v->gauss_sorted = w.gauss_sorted;
     v->ranges = reinterpret_cast<const uint32_t*>(w.ranges);
     v->num_instances = w.counters;
+    return PGR_OK;
+}
+
+// Host only, launches nothing: where a batch call of this shape leaves its visibility words (NULL = it runs no block test).
+int32_t pgr_workspace_block_visibility(void* workspace, size_t workspace_bytes, int32_t n, int32_t width, int32_t height,
+                                       int64_t max_instances, int32_t n_views, const uint32_t** vis_words,
+                                       int32_t* words_per_block) {
+    if (!workspace || !vis_words || !words_per_block || n < 0 || width <= 0 || height <= 0 || max_instances < 0 ||
+        n_views <= 0)
+        return PGR_ERR_INVALID_ARGUMENT;
+    const Layout L = make_layout(n, width, height, max_instances);
+    const BatchLayout B = make_batch_layout(L, n_views, (size_t)n);
+    if (workspace_bytes < B.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    *words_per_block = B.vis_words;
+    *vis_words = n > 0 && call_runs_block_cull(n, n_views)
+                     ? reinterpret_cast<const uint32_t*>(static_cast<char*>(workspace) + B.vis) : nullptr;
     return PGR_OK;
 }
 

@@ -69,6 +69,7 @@ class _Workspace:
 
 _WS = _Workspace()
 _LAST_INFO: dict = {}
+_LAST_BLOCK_VIS = [None]     # _block_vis_words() of the call _LAST_INFO describes
 
 MAX_INSTANCES = 0x7FFFFFFF      # per view: list positions are 32-bit (include/pegasus_raster.h)
 
@@ -195,9 +196,20 @@ def _batch_status(scratch: torch.Tensor, nv: int):
     return status, [int(x) for x in need]
 
 
-def _remember(key, need, used: int, ws: torch.Tensor, max_instances: Optional[int] = None) -> None:
-    """Fills last_forward_info() for a call of scene shape ``key`` that ran at capacity ``used`` in ``ws``."""
+def _block_vis_words(ws: torch.Tensor, n: int, width: int, height: int, capacity: int, nv: int):
+    """(device pointer or None, words per block) of the visibility words a batch call of this shape, made NOW, leaves in
+    ``ws`` (pgr_workspace_block_visibility: host only; None = such a call runs no block test)."""
+    ptr, words = C.c_void_p(), C.c_int32()
+    _lib.check(_lib.lib().pgr_workspace_block_visibility(_ptr(ws), ws.numel(), n, width, height, capacity, nv,
+                                                         C.byref(ptr), C.byref(words)), "pgr_workspace_block_visibility")
+    return ptr.value, int(words.value)
+
+
+def _remember(key, need, used: int, ws: torch.Tensor, max_instances: Optional[int] = None, block_vis=None) -> None:
+    """Fills last_forward_info() for a call of scene shape ``key`` that ran at capacity ``used`` in ``ws``; ``block_vis``:
+    _block_vis_words() as asked when the call was made (None: a layered call, whose workspace is laid out differently)."""
     _LAST_INFO.clear()
+    _LAST_BLOCK_VIS[0] = block_vis
     _LAST_INFO.update(num_instances=[int(x) for x in need], max_instances=int(used if max_instances is None else max_instances),
                       used_max_instances=int(used), n=int(key[1]), width=int(key[2]), height=int(key[3]),
                       n_views=len(need), workspace=ws, workspace_bytes=int(ws.numel()))
@@ -208,13 +220,14 @@ class PendingBatch:
     the overflow flags -- after an overflow ``redo()`` renders the batch again at a grown capacity and ``redone`` is True
     -- and returns the list of result dicts.  ``keep`` holds every tensor the enqueued call reads until then."""
 
-    def __init__(self, results, event, scratch, workspace, key, capacity, redo, keep, record_info=False):
+    def __init__(self, results, event, scratch, workspace, key, capacity, redo, keep, record_info=False, block_vis=None):
         self.results = results
         self.num_instances = None
         self.redone = False
         self._event, self._scratch, self._workspace = event, scratch, workspace
         self._key, self._capacity, self._redo, self._keep = key, capacity, redo, keep
         self._record_info = record_info      # wait() fills last_forward_info() like a synchronous call (single-view drop-in)
+        self._block_vis = block_vis
 
     def wait(self):
         if self._event is None:
@@ -232,7 +245,7 @@ class PendingBatch:
         else:
             _lib.check(status, "pgr_batch_status")
             if self._record_info:
-                _remember(self._key, self.num_instances, self._capacity, self._workspace)
+                _remember(self._key, self.num_instances, self._capacity, self._workspace, block_vis=self._block_vis)
         return self.results
 
 
@@ -354,15 +367,17 @@ def forward_views(means3D, opacities, views: Sequence[ViewSpec], *, shs=None, co
         key += ("layers", n_layers)
     default_capacity = max(1 << 20, 6 * n)
     ws = None          # the workspace of the latest attempt
+    block_vis = None   # ... and where that attempt leaves its block-visibility words (asked as the call is made)
 
     def workspace(slot, capacity):
-        nonlocal ws
+        nonlocal ws, block_vis
         nbytes = (L.pgr_batch_workspace_bytes(n, W, H, capacity, nv) if layers is None else
                   L.pgr_layers_workspace_bytes(n, W, H, capacity, nv, n_layers))
         if nbytes == 0:
             raise ValueError("pgr_batch_workspace_bytes: invalid sizes")
         ws = _WS.get(device, nbytes, slot=slot)
         call.workspace, call.workspace_bytes, call.max_instances_per_view = ws.data_ptr(), ws.numel(), capacity
+        block_vis = _block_vis_words(ws, n, W, H, capacity, nv) if layers is None else None
 
     def enqueue(slot, capacity, early=False):
         """One asynchronous attempt on ``slot``'s workspace and pinned scratch: (scratch, event behind the status words)."""
@@ -405,11 +420,11 @@ def forward_views(means3D, opacities, views: Sequence[ViewSpec], *, shs=None, co
     def render_sync():
         if fused:
             need, capacity = waited_on("sync-fused")
-            _remember(key, need, capacity, ws)
+            _remember(key, need, capacity, ws, block_vis=block_vis)
         else:
             status, need, capacity = _until_fits(run_plain, _WS.capacity_hint.get(key, default_capacity), 1.25)
             _lib.check(status, "pgr_forward")
-            _remember(key, need, capacity, ws, max_instances=_learn(key, capacity, max(need)))
+            _remember(key, need, capacity, ws, max_instances=_learn(key, capacity, max(need)), block_vis=block_vis)
         return results
 
     def render_layers_again():       # a layered call is asynchronous only: so is its retry, on the same slot
@@ -421,7 +436,7 @@ def forward_views(means3D, opacities, views: Sequence[ViewSpec], *, shs=None, co
     capacity = _WS.capacity_hint.get(key, default_capacity)
     scratch, event = enqueue(async_slot, capacity, early=early_status and layers is None)
     return PendingBatch(results, event, scratch, ws, key, capacity, render_sync if layers is None else render_layers_again,
-                        (tensors, cam_tensors, poses, semantic, posed, layers), record_info)
+                        (tensors, cam_tensors, poses, semantic, posed, layers), record_info, block_vis)
 
 
 def workspace_view(view_index: int = 0) -> dict:
@@ -434,6 +449,33 @@ def workspace_view(view_index: int = 0) -> dict:
                                     info["used_max_instances"], info["n_views"], view_index, C.byref(v)),
                "pgr_workspace_view")
     return {k: getattr(v, k) for k, _ in _lib.PgrWorkspaceView._fields_}
+
+
+def _unpack_visibility(words: torch.Tensor, nv: int) -> torch.Tensor:
+    """int32 [groups, ceil(nv / 32)] visibility words -> bool [groups, nv]."""
+    bits = (words.unsqueeze(2) >> torch.arange(32, device=words.device, dtype=torch.int32)) & 1
+    return bits.reshape(words.shape[0], words.shape[1] * 32)[:, :nv].bool()
+
+
+def last_block_visibility() -> Optional[torch.Tensor]:
+    """bool[ceil(n / 64), n_views]: the block-visibility bits the forward call that last_forward_info() describes computed
+    inside its preprocess and left in its workspace (block_visibility()'s layout and meaning), or None when that call ran
+    no block test (PGR_BLOCK_CULL=0, one or two views, a small scene with its views spread over the grid).  Call it before
+    the next forward on that workspace."""
+    info = _LAST_INFO
+    if not info:
+        raise RuntimeError("last_block_visibility: no forward call on record")
+    if _LAST_BLOCK_VIS[0] is None:
+        raise RuntimeError("last_block_visibility: not available for a layered call")
+    ptr, words = _LAST_BLOCK_VIS[0]
+    if ptr is None or info["n"] == 0:
+        return None
+    ws = info["workspace"]
+    groups = (info["n"] + 63) // 64
+    off = ptr - ws.data_ptr()
+    torch.cuda.current_stream(ws.device).synchronize()
+    raw = ws[off:off + groups * words * 4].clone().view(torch.int32).reshape(groups, words)
+    return _unpack_visibility(raw, info["n_views"])
 
 
 def block_visibility(means3D, views: Sequence[ViewSpec], *, scales=None, rotations=None, cov3D_precomp=None,
@@ -455,8 +497,7 @@ def block_visibility(means3D, views: Sequence[ViewSpec], *, scales=None, rotatio
     ws = torch.empty(L.pgr_block_visibility_workspace_bytes(n, nv) + 256, dtype=torch.uint8, device=device)
     _lib.call("pgr_block_visibility", device, C.byref(scene), nv, cams, _ptr(ws), ws.numel(), _ptr(out))
     torch.cuda.current_stream(device).synchronize()
-    bits = (out.unsqueeze(2) >> torch.arange(32, device=device, dtype=torch.int32)) & 1
-    return bits.reshape(groups, words * 32)[:, :nv].bool()
+    return _unpack_visibility(out, nv)
 
 
 def scene_prepare(n: int, tie_index: Optional[torch.Tensor] = None, semantic: Optional[dict] = None) -> dict:
