@@ -930,6 +930,39 @@ size_t pgr_plane_inliers_workspace_bytes(int32_t n);
 int32_t pgr_plane_inliers(int32_t n, const float *xyz, const double *plane, const double *pivot, double threshold,
                           uint8_t *mask, double *sums, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Mesh decimation by vertex clustering (after open3d's TriangleMesh.simplify_vertex_clustering; the rule stands at the top
+ * of pegasus_amd/csrc/decimate.hip.h and in DESIGN.md section 19; parity with open3d is not pinned).  `vertices` is a device
+ * float32 [n_vertices,3], `faces` a device int32 [n_faces,3]; n_vertices <= 2^30 and 3 n_faces < 2^31.  `voxel` is the cell
+ * edge and (lo_x, lo_y, lo_z) the grid's origin: the caller's minimum over the vertices minus voxel / 2.
+ *
+ * Two calls, as pgr_march_count / pgr_march_emit.  pgr_mesh_cluster_count numbers the occupied cells and the distinct
+ * canonical faces and writes device int64 counts[2] = {K, F'}; the caller reads them (its only wait), allocates vertices
+ * float64 [K,3], faces int32 [F',3], cluster_of_vertex int32 [n_vertices] and used_quadric uint8 [K], and calls
+ * pgr_mesh_cluster_emit once with the same mesh, grid and workspace and with n_clusters = K, n_out_faces = F'.  No row at or
+ * past either number is written, whatever the workspace holds.  `contraction` picks the vertex of a cluster: the mean of its
+ * vertices, or the minimiser of its faces' plane quadrics where that is well conditioned and lies in the cell (used_quadric =
+ * 1), the mean elsewhere.
+ *
+ * The library allocates nothing: pgr_mesh_cluster_workspace_bytes(n_vertices, n_faces) device bytes (a host-only function; 0
+ * for a count out of range), 16-byte aligned.  Every argument check comes before any launch: PGR_ERR_INVALID_ARGUMENT for a
+ * needed NULL, a count out of range, a voxel that is not finite and positive, an origin that is not finite, an unknown
+ * contraction, n_clusters > n_vertices or n_out_faces > n_faces; PGR_ERR_WORKSPACE_TOO_SMALL otherwise.  n_vertices == 0
+ * gives counts {0, 0} and emits nothing.  Both calls run on `stream`, use no floating-point atomic and return the same bytes
+ * from call to call.  A face index outside [0, n_vertices) is never dereferenced: the face is dropped and adds nothing to any
+ * quadric.  The caller's contract, which the entries cannot check: every coordinate finite and (max - min) / voxel + 1 < 2^20
+ * per axis; outside it cell indices clamp to [0, 2^20 - 1], so every access stays in bounds and only the result is wrong. */
+#define PGR_CONTRACTION_AVERAGE 0
+#define PGR_CONTRACTION_QUADRIC 1
+size_t pgr_mesh_cluster_workspace_bytes(int32_t n_vertices, int32_t n_faces);
+int32_t pgr_mesh_cluster_count(int32_t n_vertices, const float *vertices, int32_t n_faces, const int32_t *faces, double voxel,
+                               double lo_x, double lo_y, double lo_z, void *workspace, size_t workspace_bytes, int64_t *counts,
+                               void *stream);
+int32_t pgr_mesh_cluster_emit(int32_t n_vertices, const float *vertices, int32_t n_faces, const int32_t *faces, double voxel,
+                              double lo_x, double lo_y, double lo_z, int32_t contraction, void *workspace,
+                              size_t workspace_bytes, int64_t n_clusters, int64_t n_out_faces, double *out_vertices,
+                              int32_t *out_faces, int32_t *cluster_of_vertex, uint8_t *used_quadric, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

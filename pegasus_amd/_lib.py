@@ -310,6 +310,12 @@ SYMBOLS = {
                                         C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_int32,
                                         C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                         C.c_void_p]),
+    "pgr_mesh_cluster_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "pgr_mesh_cluster_count": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_double,
+                                           C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "pgr_mesh_cluster_emit": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_double,
+                                          C.c_double, C.c_int32, C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

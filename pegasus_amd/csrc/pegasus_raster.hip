@@ -26,6 +26,7 @@
 #include "obb.hip.h"
 #include "compose.hip.h"
 #include "composite.hip.h"
+#include "decimate.hip.h"
 #include "pgr_common.h"
 #include "plane.hip.h"
 #include "poseerr.hip.h"
@@ -2286,4 +2287,193 @@ int32_t pgr_densify_stats(int32_t n, const float* viewspace_grad, int32_t grad_s
     densify_stats_kernel<<<(n + 255) / 256, 256, 0, static_cast<hipStream_t>(stream_v)>>>(
         n, viewspace_grad, grad_stride, radii, grad_accum, denom, max_radii2d);
     return hip_ok(hipGetLastError(), "densify stats launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+// ---- mesh decimation by vertex clustering (decimate.hip.h) ---------------------------------------------------------------
+namespace {
+constexpr int32_t DEC_MAX_VERTICES = 1 << 30, DEC_MAX_FACES = 0x7fffffff / 3;
+struct DecLayout {
+    size_t key_a, key_b, val_a, val_b, hist, flag, number, block_tot;       // scratch of either pass
+    size_t cluster_of_vertex, order, start, cluster_key, tri, perm, rank;   // what the count pass leaves for the emit pass
+    size_t corner_begin, corner_end, total;
+    uint32_t items, blocks;                                                 // the longest array sorted, and its tiles
+};
+DecLayout dec_layout(int32_t n_vertices, int32_t n_faces) {
+    DecLayout D{};
+    const size_t V = (size_t)n_vertices, F = (size_t)n_faces;
+    D.items = (uint32_t)std::max(std::max(V, 3 * F), (size_t)1);
+    D.blocks = (D.items + DEC_TILE - 1) / DEC_TILE;
+    Carver c;
+    D.key_a = c.take(D.items * sizeof(uint64_t));
+    D.key_b = c.take(D.items * sizeof(uint64_t));
+    D.val_a = c.take(D.items * sizeof(uint32_t));
+    D.val_b = c.take(D.items * sizeof(uint32_t));
+    D.hist = c.take((size_t)256 * D.blocks * sizeof(uint32_t));
+    D.flag = c.take(D.items * sizeof(uint32_t));
+    D.number = c.take(D.items * sizeof(uint32_t));
+    D.block_tot = c.take((size_t)D.blocks * sizeof(uint32_t));
+    D.cluster_of_vertex = c.take(V * sizeof(int32_t));
+    D.order = c.take(V * sizeof(uint32_t));
+    D.start = c.take((V + 1) * sizeof(uint32_t));
+    D.cluster_key = c.take(V * sizeof(uint64_t));
+    D.tri = c.take(3 * F * sizeof(int32_t));
+    D.perm = c.take(F * sizeof(uint32_t));
+    D.rank = c.take(F * sizeof(uint32_t));
+    D.corner_begin = c.take(V * sizeof(uint32_t));
+    D.corner_end = c.take(V * sizeof(uint32_t));
+    D.total = c.off;
+    return D;
+}
+int dec_bits(uint32_t v) {                                                  // the smallest b with v < 2^b
+    int b = 1;
+    while (b < 32 && (v >> b) != 0u) ++b;
+    return b;
+}
+unsigned dec_blocks(uint32_t n) { return (n + DEC_BLOCK - 1) / DEC_BLOCK; }
+struct DecSortBuffers { uint64_t* key[2]; uint32_t* val[2]; uint32_t* hist; };
+// sorts the n pairs in (key[0], val[0]) by bits [0, bits) of the key, stably; returns which buffer holds the result
+int dec_sort(uint32_t n, int bits, const DecSortBuffers& S, hipStream_t stream) {
+    const uint32_t tiles = (n + DEC_TILE - 1) / DEC_TILE;
+    int at = 0;
+    for (int shift = 0; shift < bits; shift += 8, at ^= 1) {
+        dec_sort_hist_kernel<<<tiles, DEC_BLOCK, 0, stream>>>(n, S.key[at], shift, S.hist, tiles);
+        dec_scan_kernel<<<1, DEC_SCAN_BLOCK, 0, stream>>>(S.hist, 256u * tiles);
+        dec_sort_scatter_kernel<<<tiles, DEC_BLOCK, 0, stream>>>(n, S.key[at], S.val[at], S.key[at ^ 1], S.val[at ^ 1], shift,
+                                                                 S.hist, tiles);
+    }
+    return at;
+}
+// out[i] = flag[0] + .. + flag[i]
+void dec_flag_scan(uint32_t n, const uint32_t* flag, uint32_t* block_tot, uint32_t* out, hipStream_t stream) {
+    const uint32_t tiles = (n + DEC_TILE - 1) / DEC_TILE;
+    dec_flag_reduce_kernel<<<tiles, DEC_BLOCK, 0, stream>>>(n, flag, block_tot);
+    dec_scan_kernel<<<1, DEC_SCAN_BLOCK, 0, stream>>>(block_tot, tiles);
+    dec_flag_apply_kernel<<<tiles, DEC_BLOCK, 0, stream>>>(n, flag, block_tot, out);
+}
+bool dec_sizes_ok(int32_t n_vertices, int32_t n_faces) {
+    return n_vertices >= 0 && n_vertices <= DEC_MAX_VERTICES && n_faces >= 0 && n_faces <= DEC_MAX_FACES;
+}
+bool dec_grid_ok(double voxel, double lo_x, double lo_y, double lo_z) {
+    return std::isfinite(voxel) && voxel > 0.0 && std::isfinite(lo_x) && std::isfinite(lo_y) && std::isfinite(lo_z);
+}
+}  // namespace
+
+size_t pgr_mesh_cluster_workspace_bytes(int32_t n_vertices, int32_t n_faces) {
+    return dec_sizes_ok(n_vertices, n_faces) ? dec_layout(n_vertices, n_faces).total : 0;
+}
+
+int32_t pgr_mesh_cluster_count(int32_t n_vertices, const float* vertices, int32_t n_faces, const int32_t* faces, double voxel,
+                               double lo_x, double lo_y, double lo_z, void* workspace, size_t workspace_bytes, int64_t* counts,
+                               void* stream_v) {
+    if (!dec_sizes_ok(n_vertices, n_faces) || !dec_grid_ok(voxel, lo_x, lo_y, lo_z)) return PGR_ERR_INVALID_ARGUMENT;
+    if (!counts || !workspace || !workspace_aligned_16(workspace) || (n_vertices > 0 && !vertices) || (n_faces > 0 && !faces))
+        return PGR_ERR_INVALID_ARGUMENT;
+    const DecLayout D = dec_layout(n_vertices, n_faces);
+    if (workspace_bytes < D.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    if (!hip_ok(hipMemsetAsync(counts, 0, 2 * sizeof(int64_t), stream), "memset cluster counts")) return PGR_ERR_LAUNCH_FAILURE;
+    if (n_vertices == 0) return PGR_OK;                                     // (no vertex: no cluster, and no face can be kept)
+    char* ws = static_cast<char*>(workspace);
+    const DecSortBuffers S{{reinterpret_cast<uint64_t*>(ws + D.key_a), reinterpret_cast<uint64_t*>(ws + D.key_b)},
+                           {reinterpret_cast<uint32_t*>(ws + D.val_a), reinterpret_cast<uint32_t*>(ws + D.val_b)},
+                           reinterpret_cast<uint32_t*>(ws + D.hist)};
+    auto* flag = reinterpret_cast<uint32_t*>(ws + D.flag);
+    auto* number = reinterpret_cast<uint32_t*>(ws + D.number);
+    auto* block_tot = reinterpret_cast<uint32_t*>(ws + D.block_tot);
+    auto* cluster_of_vertex = reinterpret_cast<int32_t*>(ws + D.cluster_of_vertex);
+    auto* tri = reinterpret_cast<int32_t*>(ws + D.tri);
+    auto* rank = reinterpret_cast<uint32_t*>(ws + D.rank);
+    const uint32_t V = (uint32_t)n_vertices, F = (uint32_t)n_faces;
+    const DecGrid g{{lo_x, lo_y, lo_z}, voxel};
+
+    dec_vertex_key_kernel<<<dec_blocks(V), DEC_BLOCK, 0, stream>>>(V, vertices, g, S.key[0], S.val[0]);
+    int at = dec_sort(V, 60, S, stream);
+    dec_key_heads_kernel<<<dec_blocks(V), DEC_BLOCK, 0, stream>>>(V, S.key[at], flag);
+    dec_flag_scan(V, flag, block_tot, number, stream);
+    dec_cluster_write_kernel<<<dec_blocks(V), DEC_BLOCK, 0, stream>>>(
+        V, S.key[at], S.val[at], number, cluster_of_vertex, reinterpret_cast<uint32_t*>(ws + D.order),
+        reinterpret_cast<uint32_t*>(ws + D.start), reinterpret_cast<uint64_t*>(ws + D.cluster_key),
+        reinterpret_cast<long long*>(counts));
+    if (F > 0) {
+        const int bits = dec_bits(V);
+        const bool packed = bits <= DEC_PACKED_MAX_BITS;
+        dec_face_key_kernel<<<dec_blocks(F), DEC_BLOCK, 0, stream>>>(F, faces, V, cluster_of_vertex, packed ? bits : 0, tri,
+                                                                     S.key[0], S.val[0]);
+        at = dec_sort(F, packed ? 3 * bits : bits, S, stream);
+        if (!packed) {
+            // the second stage sorts from buffer 0: the first stage's values go there unless they already are
+            if (at == 1 && !hip_ok(hipMemcpyAsync(S.val[0], S.val[1], (size_t)F * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream),
+                                   "memcpy face order"))
+                return PGR_ERR_LAUNCH_FAILURE;
+            dec_face_key2_kernel<<<dec_blocks(F), DEC_BLOCK, 0, stream>>>(F, tri, S.val[0], V, S.key[0]);
+            at = dec_sort(F, 32 + bits, S, stream);
+        }
+        dec_face_heads_kernel<<<dec_blocks(F), DEC_BLOCK, 0, stream>>>(F, tri, S.val[at], reinterpret_cast<uint32_t*>(ws + D.perm),
+                                                                       flag);
+        dec_flag_scan(F, flag, block_tot, rank, stream);
+        dec_face_total_kernel<<<1, 1, 0, stream>>>(F, rank, reinterpret_cast<long long*>(counts));
+    }
+    return hip_ok(hipGetLastError(), "mesh_cluster_count launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+int32_t pgr_mesh_cluster_emit(int32_t n_vertices, const float* vertices, int32_t n_faces, const int32_t* faces, double voxel,
+                              double lo_x, double lo_y, double lo_z, int32_t contraction, void* workspace,
+                              size_t workspace_bytes, int64_t n_clusters, int64_t n_out_faces, double* out_vertices,
+                              int32_t* out_faces, int32_t* cluster_of_vertex, uint8_t* used_quadric, void* stream_v) {
+    if (!dec_sizes_ok(n_vertices, n_faces) || !dec_grid_ok(voxel, lo_x, lo_y, lo_z)) return PGR_ERR_INVALID_ARGUMENT;
+    if (contraction != PGR_CONTRACTION_AVERAGE && contraction != PGR_CONTRACTION_QUADRIC) return PGR_ERR_INVALID_ARGUMENT;
+    if (n_clusters < 0 || n_clusters > n_vertices || n_out_faces < 0 || n_out_faces > n_faces) return PGR_ERR_INVALID_ARGUMENT;
+    if (!workspace || !workspace_aligned_16(workspace) || (n_vertices > 0 && (!vertices || !cluster_of_vertex)) ||
+        (n_faces > 0 && !faces) || (n_clusters > 0 && (!out_vertices || !used_quadric)) || (n_out_faces > 0 && !out_faces))
+        return PGR_ERR_INVALID_ARGUMENT;
+    const DecLayout D = dec_layout(n_vertices, n_faces);
+    if (workspace_bytes < D.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    if (n_vertices == 0) return PGR_OK;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    char* ws = static_cast<char*>(workspace);
+    const DecSortBuffers S{{reinterpret_cast<uint64_t*>(ws + D.key_a), reinterpret_cast<uint64_t*>(ws + D.key_b)},
+                           {reinterpret_cast<uint32_t*>(ws + D.val_a), reinterpret_cast<uint32_t*>(ws + D.val_b)},
+                           reinterpret_cast<uint32_t*>(ws + D.hist)};
+    const auto* cov = reinterpret_cast<const int32_t*>(ws + D.cluster_of_vertex);
+    auto* corner_begin = reinterpret_cast<uint32_t*>(ws + D.corner_begin);
+    auto* corner_end = reinterpret_cast<uint32_t*>(ws + D.corner_end);
+    const uint32_t V = (uint32_t)n_vertices, F = (uint32_t)n_faces;
+    if (!hip_ok(hipMemcpyAsync(cluster_of_vertex, cov, (size_t)V * sizeof(int32_t), hipMemcpyDeviceToDevice, stream),
+                "memcpy cluster_of_vertex"))
+        return PGR_ERR_LAUNCH_FAILURE;
+    if (n_out_faces > 0)
+        dec_face_emit_kernel<<<dec_blocks(F), DEC_BLOCK, 0, stream>>>(F, reinterpret_cast<const int32_t*>(ws + D.tri),
+                                                                      reinterpret_cast<const uint32_t*>(ws + D.perm),
+                                                                      reinterpret_cast<const uint32_t*>(ws + D.rank), n_out_faces,
+                                                                      out_faces);
+    if (n_clusters > 0) {
+        const bool quadric = contraction == PGR_CONTRACTION_QUADRIC && F > 0;
+        int at = 0;
+        if (quadric) {
+            // the two range tables lie one behind the other: one memset
+            if (!hip_ok(hipMemsetAsync(corner_begin, 0, D.total - D.corner_begin, stream), "memset corner ranges"))
+                return PGR_ERR_LAUNCH_FAILURE;
+            dec_corner_key_kernel<<<dec_blocks(3 * F), DEC_BLOCK, 0, stream>>>(3 * F, faces, V, cov, S.key[0], S.val[0]);
+            at = dec_sort(3 * F, dec_bits(V), S, stream);
+            dec_corner_ranges_kernel<<<dec_blocks(3 * F), DEC_BLOCK, 0, stream>>>(3 * F, S.key[at], V, corner_begin, corner_end);
+        }
+        DecPositionArgs a{};
+        a.g = DecGrid{{lo_x, lo_y, lo_z}, voxel};
+        a.n_vertices = V;
+        a.n_faces = F;
+        a.xyz = vertices;
+        a.faces = faces;
+        a.order = reinterpret_cast<const uint32_t*>(ws + D.order);
+        a.start = reinterpret_cast<const uint32_t*>(ws + D.start);
+        a.cluster_key = reinterpret_cast<const uint64_t*>(ws + D.cluster_key);
+        a.corner = S.val[at];
+        a.corner_begin = corner_begin;
+        a.corner_end = corner_end;
+        a.n_clusters = n_clusters;
+        a.quadric = quadric ? 1 : 0;
+        a.out = out_vertices;
+        a.used_quadric = used_quadric;
+        dec_position_kernel<<<(unsigned)((n_clusters + DEC_WAVES - 1) / DEC_WAVES), DEC_BLOCK, 0, stream>>>(a);
+    }
+    return hip_ok(hipGetLastError(), "mesh_cluster_emit launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
 }

@@ -7,9 +7,12 @@ the closed outer surface (``pgr_march_count`` / ``pgr_march_emit``).  A density 
 3DGS object is a shell of surface Gaussians, and its level set is two nested surfaces.
 
     python -m pegasus_amd.mesh -m <model dir> --out <dir> --obj_id N [--scale 1000] [--mass 0.1] [--resolution 256]
+                               [--collision_faces N]
 
 writes ``<out>/models/obj_NNNNNN.ply`` (scaled: BOP models are in mm) with its ``models_info.json`` entry, and
-``<out>/urdf/obj_NNNNNN.{obj,urdf}`` in the model's own units for pybullet.
+``<out>/urdf/obj_NNNNNN.{obj,urdf}`` in the model's own units for pybullet; with ``--collision_faces`` also
+``<out>/urdf/obj_NNNNNN_collision.obj``, the mesh decimated by vertex clustering (``pegasus_amd.decimate``), as the URDF's
+collision geometry.
 """
 from __future__ import annotations
 
@@ -283,9 +286,10 @@ def write_obj(path, mesh: Mesh):
         np.savetxt(f, mesh.faces.astype(np.int64) + 1, fmt="f %d %d %d")
 
 
-def write_urdf(path, mesh_filename: str, mesh: Mesh, mass: float):
+def write_urdf(path, mesh_filename: str, mesh: Mesh, mass: float, collision_filename: Optional[str] = None):
     """One link: visual and collision are the mesh file, the inertial block holds the mesh's centre of mass, ``mass``
-    and inertia about the centre of mass at uniform density."""
+    and inertia about the centre of mass at uniform density.  ``collision_filename``: another (coarser) mesh file for the
+    ``<collision>`` element only; the inertial block still comes from ``mesh``."""
     c = mesh.center_of_mass()
     I = mesh.inertia(mass)
     robot = ET.Element("robot", name=Path(mesh_filename).stem)
@@ -298,7 +302,8 @@ def write_urdf(path, mesh_filename: str, mesh: Mesh, mass: float):
     for tag in ("visual", "collision"):
         e = ET.SubElement(link, tag)
         ET.SubElement(e, "origin", xyz="0 0 0", rpy="0 0 0")
-        ET.SubElement(ET.SubElement(e, "geometry"), "mesh", filename=str(mesh_filename), scale="1 1 1")
+        filename = collision_filename if tag == "collision" and collision_filename is not None else mesh_filename
+        ET.SubElement(ET.SubElement(e, "geometry"), "mesh", filename=str(filename), scale="1 1 1")
     ET.indent(robot)
     path = Path(path)
     path.parent.mkdir(parents=True, exist_ok=True)
@@ -391,6 +396,9 @@ def _parser():
     p.add_argument("--image_size", type=int, default=512)
     p.add_argument("--clean_pcd", action="store_true",
                    help="drop the model's floaters first: the radius-outlier filter (16 points, 0.03) of load_ply")
+    p.add_argument("--collision_faces", type=int, default=None, metavar="N",
+                   help="also write urdf/<name>_collision.obj, the mesh decimated to at most N faces by vertex clustering "
+                        "(pegasus_amd.decimate.simplify_to), and name it in the URDF's <collision> element")
     p.add_argument("--sym_continuous", type=float, nargs=6, action="append", metavar=("AX", "AY", "AZ", "OX", "OY", "OZ"),
                    help="a continuous rotational symmetry: axis and a point on it, in model units (repeatable)")
     p.add_argument("--sym_discrete", type=float, nargs=16, action="append", metavar="M",
@@ -421,7 +429,13 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     info[str(a.obj_id)] = models_info(mesh.scaled(a.scale), disc, cont)
     (out / "models" / BD.MODELS_INFO).write_text(json.dumps(dict(sorted(info.items(), key=lambda kv: int(kv[0]))), indent=2) + "\n")
     write_obj(out / "urdf" / f"{name}.obj", mesh)
-    write_urdf(out / "urdf" / f"{name}.urdf", f"{name}.obj", mesh, a.mass)
+    collision = None
+    if a.collision_faces is not None:
+        from .decimate import simplify_to
+        coarse, _voxel = simplify_to(mesh, a.collision_faces)
+        collision = f"{name}_collision.obj"
+        write_obj(out / "urdf" / collision, coarse)
+    write_urdf(out / "urdf" / f"{name}.urdf", f"{name}.obj", mesh, a.mass, collision_filename=collision)
     print(f"{name}: {len(mesh.vertices)} vertices, {len(mesh.faces)} faces, volume {mesh.volume():.6g}, "
           f"written under {out}")
     return 0
