@@ -510,6 +510,56 @@ int32_t pgr_mesh_depth(const float *vertices, int64_t n_vertices, const int32_t 
                        const PgrMeshJob *jobs, int32_t width, int32_t height, float near_z, float *depth, int32_t n_slots,
                        int32_t *straddle_count, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Shaded object meshes: the toolkit's renderer.render_object(...)['rgb'] and the dense maps only a mesh gives (model
+ * coordinates, face ids, normals), in two passes (pegasus_amd/mesh_render.py render / Renderer / vis_object_poses).
+ *
+ * pgr_mesh_visibility is pgr_mesh_depth with a 64-bit canvas element: same jobs, same rules, same workspace layout, but
+ * `keys` (device uint64 [n_slots,height,width], 8-byte aligned) receives per pixel
+ *     key = (uint64)float_bits(z) << 32 | (uint32)(job_index_in_call << 22 | face_index_in_job)
+ * of the nearest surface, combined by one 64-bit integer atomic min: on equal depth bits the lower job index wins, then the
+ * lower face index; 0 where nothing is hit.  The high word equals what pgr_mesh_depth writes for the same call, bit for bit;
+ * two runs give equal bytes.  At most 2^22 faces per job and PGR_MESH_VISIBILITY_MAX_JOBS jobs per call: beyond these the
+ * workspace functions return 0 and the entries PGR_ERR_INVALID_ARGUMENT (callers chunk).
+ *
+ * pgr_mesh_shade resolves `keys` of a pgr_mesh_visibility call with the same vertices, faces, jobs, size and near_z: one
+ * lane per pixel redoes the winning face's setup and writes every output of PgrMeshShade whose pointer is non-NULL.  The
+ * rule, all float32 without contraction, correctly rounded division and square root (pinned above mesh_shade_kernel in
+ * pegasus_amd/csrc/meshraster.hip.h and restated in tests/mesh_shade_reference.py, which the outputs equal bit for bit):
+ *   weights   la = (float)E_bc w_a, lb = (float)E_ca w_b, lc = (float)E_ab w_c, den = (la + lb) + lc; an attribute A is
+ *             ((la A_a + lb A_b) + lc A_c) / den, its values swapped with b and c when the face was flipped
+ *   depth     the key's high word, 0 where empty;   face_id, job_id: -1 where empty
+ *   xyz       the attribute rule on the model vertices, 0 where empty;   P = R xyz + t,   L = (light - P) / |light - P|
+ *   normal    camera frame, unit, 0 where empty.  normals == NULL (flat): cross(P_b - P_a, P_c - P_a) normalised, negated when
+ *             dot(n, P) > 0.  Else (smooth): the attribute rule on `normals` [n_vertices,3], rotated by R, normalised.  A zero
+ *             or non-finite length gives normal 0 and diffuse 0
+ *   rgb       min(ambient + max(dot(L, n), 0), 1) * colour; colour is the attribute rule on `colors` [n_vertices,3] in [0,1],
+ *             or, when colors == NULL, row k of the HOST array surf_colors [n_jobs,3] (NULL: 0.5 grey); empty pixels get bg
+ * A key that names no face of the call is treated as empty.  Workspace (the device-side job table):
+ * pgr_mesh_shade_workspace_bytes(n_jobs, jobs), host-only, 0 for bad arguments.  Neither entry allocates or synchronises. */
+#define PGR_MESH_VISIBILITY_MAX_JOBS 1024
+typedef struct PgrMeshShade {
+    const float *normals;      /* device float32 [n_vertices,3] or NULL: flat shading */
+    const float *colors;       /* device float32 [n_vertices,3] or NULL: surf_colors */
+    const float *surf_colors;  /* HOST float32 [n_jobs,3] or NULL: 0.5 */
+    float light[3];            /* camera frame; the toolkit's default is the camera centre (0,0,0) */
+    float ambient;             /* the toolkit's default is 0.5 */
+    float bg[3];
+    float *depth;              /* outputs, device, each may be NULL: float32 [n_slots,height,width] */
+    int32_t *face_id;          /* int32 [n_slots,height,width] */
+    int32_t *job_id;           /* int32 [n_slots,height,width] */
+    float *xyz;                /* float32 [n_slots,height,width,3] */
+    float *normal;             /* float32 [n_slots,height,width,3] */
+    float *rgb;                /* float32 [n_slots,height,width,3] */
+} PgrMeshShade;
+size_t pgr_mesh_visibility_workspace_bytes(int32_t n_jobs, const PgrMeshJob *jobs);
+int32_t pgr_mesh_visibility(const float *vertices, int64_t n_vertices, const int32_t *faces, int64_t n_faces, int32_t n_jobs,
+                            const PgrMeshJob *jobs, int32_t width, int32_t height, float near_z, uint64_t *keys,
+                            int32_t n_slots, int32_t *straddle_count, void *workspace, size_t workspace_bytes, void *stream);
+size_t pgr_mesh_shade_workspace_bytes(int32_t n_jobs, const PgrMeshJob *jobs);
+int32_t pgr_mesh_shade(const float *vertices, int64_t n_vertices, const int32_t *faces, int64_t n_faces, int32_t n_jobs,
+                       const PgrMeshJob *jobs, int32_t width, int32_t height, float near_z, const uint64_t *keys,
+                       int32_t n_slots, const PgrMeshShade *shade, void *workspace, size_t workspace_bytes, void *stream);
+
 /* BOP ground truth of n_jobs (object, image) pairs from depth canvases, the sequence of the toolkit's
  * scripts/calc_gt_info.py:117-177.  Job k reads canvas `slot` of `canvases` [n_slots,canvas_height,canvas_width] (as
  * pgr_mesh_depth leaves it) and image `frame` of `scene_depth` [n_frames,height,width] (same unit, 0 = missing); the image

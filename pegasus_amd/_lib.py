@@ -141,6 +141,16 @@ class PgrMeshJob(C.Structure):
                 ("cy", C.c_float), ("slot", C.c_int32)]
 
 
+class PgrMeshShade(C.Structure):
+    _fields_ = [("normals", C.c_void_p), ("colors", C.c_void_p), ("surf_colors", C.POINTER(C.c_float)),
+                ("light", C.c_float * 3), ("ambient", C.c_float), ("bg", C.c_float * 3), ("depth", C.c_void_p),
+                ("face_id", C.c_void_p), ("job_id", C.c_void_p), ("xyz", C.c_void_p), ("normal", C.c_void_p),
+                ("rgb", C.c_void_p)]
+
+
+PGR_MESH_VISIBILITY_MAX_JOBS = 1024      # include/pegasus_raster.h
+
+
 class PgrGtInfoJob(C.Structure):
     _fields_ = [("slot", C.c_int32), ("frame", C.c_int32), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double),
                 ("cy", C.c_double)]
@@ -270,6 +280,14 @@ SYMBOLS = {
     "pgr_mesh_depth": (C.c_int32, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(PgrMeshJob), C.c_int32,
                                    C.c_int32, C.c_float, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
                                    C.c_void_p]),
+    "pgr_mesh_visibility_workspace_bytes": (C.c_size_t, [C.c_int32, C.POINTER(PgrMeshJob)]),
+    "pgr_mesh_visibility": (C.c_int32, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(PgrMeshJob),
+                                        C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                        C.c_size_t, C.c_void_p]),
+    "pgr_mesh_shade_workspace_bytes": (C.c_size_t, [C.c_int32, C.POINTER(PgrMeshJob)]),
+    "pgr_mesh_shade": (C.c_int32, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(PgrMeshJob), C.c_int32,
+                                   C.c_int32, C.c_float, C.c_void_p, C.c_int32, C.POINTER(PgrMeshShade), C.c_void_p,
+                                   C.c_size_t, C.c_void_p]),
     "pgr_bop_gt_info": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                     C.c_int32, C.c_int32, C.c_int32, C.POINTER(PgrGtInfoJob), C.c_float, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -33,6 +33,16 @@
 // launch of MESHR_LARGE_WAVES waves splits the total tile count evenly: a wave finds its first entry by bisection, then
 // walks tiles, 4 samples per lane.  A 12-face box over a 2400^2 canvas is 45 k tiles over 8192 waves.
 //
+// pgr_mesh_visibility: the same jobs, vertex, snap, near-plane, coverage and depth rules, the same two launches and the
+// same queue (one template parameter on the canvas element), but the canvas element is a 64-bit key
+//       key = (uint64)float_bits(z) << 32 | (uint32)(job_index_in_call << 22 | face_index_in_job)
+// combined with ONE 64-bit integer atomic min at agent scope: the nearest surface wins; on equal depth bits the lower job
+// index, then the lower face index.  Empty pixels are all-ones during the call and 0 after it (z > 0: no valid key is 0).
+// A job has at most 2^22 faces, a call at most MESHV_MAX_JOBS = 1024 jobs.  The high word of a finished key equals, bit for
+// bit, what pgr_mesh_depth writes for the same call.
+//
+// pgr_mesh_shade: one lane per canvas pixel turns a key into per-pixel quantities, see the rule above mesh_shade_kernel.
+//
 // pgr_bop_gt_info: per canvas pixel the sequence of the toolkit's calc_gt_info.py, see the kernel.
 #pragma once
 #include "pgr_common.h"
@@ -46,7 +56,11 @@ constexpr int MESHR_TILE = 16;
 constexpr int MESHR_LARGE_WAVES = 8192;
 constexpr int MESHR_TILE_BITS = 41;                  // 2^22 faces x 2^18 tiles of an 8192^2 canvas < 2^41
 constexpr int64_t MESHR_MAX_GROUP_FACES = (int64_t)1 << 22;
-constexpr uint32_t MESHR_EMPTY = 0xFFFFFFFFu;
+constexpr int MESHV_MAX_JOBS = PGR_MESH_VISIBILITY_MAX_JOBS;     // jobs of one pgr_mesh_visibility call: 10 bits of the key
+constexpr int MESHV_FACE_BITS = 22;                  // 2^22 = MESHR_MAX_GROUP_FACES faces of a job: the key's other 22
+static_assert(MESHV_MAX_JOBS <= (1 << (32 - MESHV_FACE_BITS)) && MESHR_MAX_GROUP_FACES <= ((int64_t)1 << MESHV_FACE_BITS), "the key's low word");
+constexpr int MESHS_TILE_W = 16, MESHS_TILE_H = 4;   // pgr_mesh_shade: the pixels of one wave
+constexpr int MESHS_THREADS = 256;                   // four waves: a 16 x 16 block of pixels
 constexpr float MESHR_SNAP_LIMIT = 1073741824.0f;    // 2^30
 
 struct MeshJobDev {
@@ -60,6 +74,7 @@ struct MeshJobDev {
 struct MeshJobTable {
     int32_t count, width, height;
     float near;
+    int32_t first;                                   // index in the call of job[0] (the keys of pgr_mesh_visibility)
     MeshJobDev job[MESHR_JOBS_PER_LAUNCH];
 };
 
@@ -73,6 +88,12 @@ struct MeshTri {
     float wa, wb, wc;
     long long area2;
     int32_t i0, i1, j0, j1;                          // clipped box in pixels, inclusive
+};
+
+// what the resolve pass needs besides: a, b, c (after the swap) as vertex indices in the mesh and as camera-frame points
+struct MeshCorners {
+    int32_t vi[3];
+    float P[3][3];
 };
 
 __device__ __forceinline__ int32_t mesh_snap(float u) {
@@ -91,11 +112,15 @@ __device__ __forceinline__ long long mesh_edge_bias(int32_t px, int32_t py, int3
 }
 
 // 0: dropped, 1: to rasterise, 2: dropped because it straddles the near plane
+template <bool CORNERS = false>
 __device__ __forceinline__ int mesh_setup(const MeshJobDev& J, const float* __restrict__ vertices,
-                                          const int32_t* __restrict__ faces, int face, int W, int H, float near, MeshTri& T) {
+                                          const int32_t* __restrict__ faces, int face, int W, int H, float near, MeshTri& T,
+                                          MeshCorners* corners = nullptr) {
     const int32_t* f = faces + 3 * ((size_t)J.f0 + (size_t)face);
     int32_t sx[3], sy[3];
     float w[3];
+    int32_t vid[3];
+    float cam[3][3];
     int behind = 0;
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
@@ -107,6 +132,7 @@ __device__ __forceinline__ int mesh_setup(const MeshJobDev& J, const float* __re
         const float Y = ((J.R[3] * px + J.R[4] * py) + J.R[5] * pz) + J.t[1];
         const float Z = ((J.R[6] * px + J.R[7] * py) + J.R[8] * pz) + J.t[2];
         behind += Z < near ? 1 : 0;
+        if constexpr (CORNERS) { vid[q] = vi; cam[q][0] = X; cam[q][1] = Y; cam[q][2] = Z; }
         sx[q] = mesh_snap((J.fx * X) / Z + J.cx);
         sy[q] = mesh_snap((J.fy * Y) / Z + J.cy);
         w[q] = 1.0f / Z;
@@ -120,6 +146,15 @@ __device__ __forceinline__ int mesh_setup(const MeshJobDev& J, const float* __re
     T.ax = sx[0]; T.ay = sy[0]; T.bx = sx[b]; T.by = sy[b]; T.cx = sx[c]; T.cy = sy[c];
     T.wa = w[0]; T.wb = w[b]; T.wc = w[c];
     T.area2 = area2;
+    if constexpr (CORNERS) {
+        const int order[3] = {0, b, c};
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            corners->vi[q] = vid[order[q]];
+#pragma unroll
+            for (int d = 0; d < 3; ++d) corners->P[q][d] = cam[order[q]][d];
+        }
+    }
     const int32_t minx = min(sx[0], min(sx[1], sx[2])), maxx = max(sx[0], max(sx[1], sx[2]));
     const int32_t miny = min(sy[0], min(sy[1], sy[2])), maxy = max(sy[0], max(sy[1], sy[2]));
     T.i0 = max(0, (minx + 255) >> 8);
@@ -129,11 +164,19 @@ __device__ __forceinline__ int mesh_setup(const MeshJobDev& J, const float* __re
     return (T.i0 <= T.i1 && T.j0 <= T.j1) ? 1 : 0;
 }
 
-__device__ __forceinline__ void mesh_sample(const MeshTri& T, long long ea, long long eb, long long ec, uint32_t* pix) {
+// the canvas element: the depth's bits (pgr_mesh_depth), or the key depth << 32 | id (pgr_mesh_visibility)
+__device__ __forceinline__ void mesh_min(uint32_t* pix, uint32_t zbits, uint32_t) {
+    __hip_atomic_fetch_min((PGR_GLOBAL uint32_t*)pix, zbits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void mesh_min(uint64_t* pix, uint32_t zbits, uint32_t id) {
+    __hip_atomic_fetch_min((PGR_GLOBAL uint64_t*)pix, ((uint64_t)zbits << 32) | id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <typename Pix>
+__device__ __forceinline__ void mesh_sample(const MeshTri& T, long long ea, long long eb, long long ec, Pix* pix, uint32_t id) {
     const float den = ((float)ea * T.wa + (float)eb * T.wb) + (float)ec * T.wc;
     const float z = (float)T.area2 / den;
-    if (den > 0.f && z > 0.f && z < INFINITY)
-        __hip_atomic_fetch_min((PGR_GLOBAL uint32_t*)pix, __float_as_uint(z), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (den > 0.f && z > 0.f && z < INFINITY) mesh_min(pix, __float_as_uint(z), id);
 }
 
 // the job of a workgroup of the small launch
@@ -144,8 +187,9 @@ __device__ __forceinline__ int mesh_job_of_block(const MeshJobTable& T, uint32_t
     return k;
 }
 
+template <typename Pix>
 __global__ __launch_bounds__(MESHR_THREADS) void mesh_small_kernel(const MeshJobTable T, const float* __restrict__ vertices,
-                                                                  const int32_t* __restrict__ faces, uint32_t* __restrict__ out,
+                                                                  const int32_t* __restrict__ faces, Pix* __restrict__ out,
                                                                   size_t plane, unsigned long long* __restrict__ qctr,
                                                                   MeshQueueEntry* __restrict__ queue, long long queue_cap,
                                                                   int32_t* __restrict__ straddle) {
@@ -188,7 +232,8 @@ __global__ __launch_bounds__(MESHR_THREADS) void mesh_small_kernel(const MeshJob
     }
     if (status != 1 || large) return;
     // walk the box: edge values at the row's first sample, then one add per sample
-    uint32_t* canvas = out + (size_t)J.slot * plane;
+    Pix* canvas = out + (size_t)J.slot * plane;
+    const uint32_t id = ((uint32_t)(T.first + k) << MESHV_FACE_BITS) | (uint32_t)face;
     const long long ba = mesh_edge_bias(tri.bx, tri.by, tri.cx, tri.cy), bb = mesh_edge_bias(tri.cx, tri.cy, tri.ax, tri.ay),
                     bc = mesh_edge_bias(tri.ax, tri.ay, tri.bx, tri.by);
     const long long sa = -256ll * ((long long)tri.cy - tri.by), sbx = -256ll * ((long long)tri.ay - tri.cy),
@@ -198,14 +243,15 @@ __global__ __launch_bounds__(MESHR_THREADS) void mesh_small_kernel(const MeshJob
         long long eb = mesh_edge(tri.cx, tri.cy, tri.ax, tri.ay, tri.i0 << 8, j << 8);
         long long ec = mesh_edge(tri.ax, tri.ay, tri.bx, tri.by, tri.i0 << 8, j << 8);
         for (int i = tri.i0; i <= tri.i1; ++i) {
-            if (ea >= ba && eb >= bb && ec >= bc) mesh_sample(tri, ea, eb, ec, canvas + (size_t)j * T.width + i);
+            if (ea >= ba && eb >= bb && ec >= bc) mesh_sample(tri, ea, eb, ec, canvas + (size_t)j * T.width + i, id);
             ea += sa; eb += sbx; ec += sc;
         }
     }
 }
 
+template <typename Pix>
 __global__ __launch_bounds__(MESHR_THREADS) void mesh_large_kernel(const MeshJobTable T, const float* __restrict__ vertices,
-                                                                  const int32_t* __restrict__ faces, uint32_t* __restrict__ out,
+                                                                  const int32_t* __restrict__ faces, Pix* __restrict__ out,
                                                                   size_t plane, const unsigned long long* __restrict__ qctr,
                                                                   const MeshQueueEntry* __restrict__ queue, long long queue_cap) {
     const unsigned long long packed = *qctr;
@@ -236,7 +282,8 @@ __global__ __launch_bounds__(MESHR_THREADS) void mesh_large_kernel(const MeshJob
             k = stop;
             continue;
         }
-        uint32_t* canvas = out + (size_t)J.slot * plane;
+        Pix* canvas = out + (size_t)J.slot * plane;
+        const uint32_t id = ((uint32_t)(T.first + job) << MESHV_FACE_BITS) | (uint32_t)q.face;
         const unsigned long long tiles_x = (unsigned long long)((tri.i1 - tri.i0 + MESHR_TILE) / MESHR_TILE);
         const long long ba = mesh_edge_bias(tri.bx, tri.by, tri.cx, tri.cy), bb = mesh_edge_bias(tri.cx, tri.cy, tri.ax, tri.ay),
                         bc = mesh_edge_bias(tri.ax, tri.ay, tri.bx, tri.by);
@@ -252,16 +299,176 @@ __global__ __launch_bounds__(MESHR_THREADS) void mesh_large_kernel(const MeshJob
                 const long long ea = mesh_edge(tri.bx, tri.by, tri.cx, tri.cy, i << 8, j << 8);
                 const long long eb = mesh_edge(tri.cx, tri.cy, tri.ax, tri.ay, i << 8, j << 8);
                 const long long ec = mesh_edge(tri.ax, tri.ay, tri.bx, tri.by, i << 8, j << 8);
-                if (ea >= ba && eb >= bb && ec >= bc) mesh_sample(tri, ea, eb, ec, canvas + (size_t)j * T.width + i);
+                if (ea >= ba && eb >= bb && ec >= bc) mesh_sample(tri, ea, eb, ec, canvas + (size_t)j * T.width + i, id);
             }
         }
     }
 }
 
-// empty pixels end as 0.0
-__global__ __launch_bounds__(256) void mesh_finalize_kernel(uint32_t* __restrict__ out, size_t n) {
+// empty pixels end as 0.0 (as key 0)
+template <typename Pix>
+__global__ __launch_bounds__(256) void mesh_finalize_kernel(Pix* __restrict__ out, size_t n) {
     for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (size_t)gridDim.x * 256)
-        if (out[p] == MESHR_EMPTY) out[p] = 0u;
+        if (out[p] == (Pix)~(Pix)0) out[p] = 0u;
+}
+
+// ---- pgr_mesh_shade: a visibility buffer resolved to per-pixel quantities ----------------------------------------------
+// One lane per canvas pixel (i, j) of a slot.  key == 0: the pixel is empty.  Otherwise job = low word >> 22, face = low
+// word & (2^22 - 1); the lane redoes mesh_setup for that face of that job (the same snapped coordinates, the same swap of b
+// and c when area2 < 0) and takes the three int64 edge values at the sample (256 i, 256 j).  All arithmetic is float32
+// without contraction, in the order written here (tests/mesh_shade_reference.py restates it in NumPy):
+//
+//   Weights.    la = (float)E_bc * w_a,  lb = (float)E_ca * w_b,  lc = (float)E_ab * w_c,  den = (la + lb) + lc  (the depth
+//               rule's den).  An attribute A with vertex values A_a, A_b, A_c is  ((la A_a + lb A_b) + lc A_c) / den;  the
+//               values are swapped together with b and c when the face was flipped.
+//   depth       the key's high word; 0 where empty.          face_id, job_id   int32; -1 where empty.
+//   xyz         the attribute rule on the face's model vertices (the model coordinates of the surface point); 0 where empty.
+//   Eye point.  P = R xyz + t in the vertex rule's order.  d = light - P,  L = d / sqrt((d.x d.x + d.y d.y) + d.z d.z)
+//               (every component divided by the root).
+//   normal      camera frame, unit length; 0 where empty.
+//               flat (normals == NULL):  m = cross(P_b - P_a, P_c - P_a) of the three camera-frame vertices of the vertex
+//                   rule, m.x = u.y v.z - u.z v.y and cyclic;  n = m / sqrt((m.x m.x + m.y m.y) + m.z m.z);  n is negated
+//                   when (n.x P.x + n.y P.y) + n.z P.z > 0: it faces the viewer whatever the winding.
+//               smooth:  the attribute rule on the model normals, m = R a in the vertex rule's order without t, normalised
+//                   alike; no flip.
+//               A root that is zero or not finite gives normal 0 and diffuse 0.
+//   rgb         diffuse = fmax((L.x n.x + L.y n.y) + L.z n.z, 0)  (a NaN counts as 0),  light_w = fmin(ambient + diffuse, 1),
+//               rgb = light_w * colour;  colour is the attribute rule on `colors`, or the job's surf_color when colors == NULL.
+//               Empty pixels get bg.
+// Division and sqrtf are the correctly rounded ones (hipcc's default; the build sets no fast-math flag).
+//
+// A wave owns a 16 x 4 pixel tile, a workgroup 16 x 16: the lanes of a wave gather few distinct faces.  No LDS.  The job
+// table does not fit a kernel argument (1024 jobs): the entry writes it to the workspace, 32 jobs per tiny launch.
+struct MeshShadeJobDev {
+    MeshJobDev job;
+    float surf[3];
+};
+
+struct MeshShadeTable {
+    int32_t count, first;
+    MeshShadeJobDev job[MESHR_JOBS_PER_LAUNCH];
+};
+
+struct MeshShadeArgs {
+    int32_t n_jobs, width, height, n_slots;
+    float near, ambient;
+    float light[3], bg[3];
+    const float* vertices;
+    const int32_t* faces;
+    const float* normals;
+    const float* colors;
+    const uint64_t* keys;
+    const MeshShadeJobDev* jobs;
+    float* depth;
+    int32_t* face_id;
+    int32_t* job_id;
+    float* xyz;
+    float* normal;
+    float* rgb;
+};
+
+__global__ __launch_bounds__(64) void mesh_shade_table_kernel(const MeshShadeTable T, MeshShadeJobDev* __restrict__ table) {
+    if ((int)threadIdx.x < T.count) table[T.first + threadIdx.x] = T.job[threadIdx.x];
+}
+
+__device__ __forceinline__ float mesh_attr(float la, float lb, float lc, float den, float a, float b, float c) {
+    return ((la * a + lb * b) + lc * c) / den;
+}
+
+__device__ __forceinline__ void mesh_store3(float* out, size_t p, float x, float y, float z) {
+    if (!out) return;
+    out[3 * p + 0] = x; out[3 * p + 1] = y; out[3 * p + 2] = z;
+}
+
+__global__ __launch_bounds__(MESHS_THREADS) void mesh_shade_kernel(const MeshShadeArgs A) {
+    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+    const int i = blockIdx.x * MESHS_TILE_W + (lane & (MESHS_TILE_W - 1));
+    const int j = (blockIdx.y * (MESHS_THREADS / WAVE) + wave) * MESHS_TILE_H + lane / MESHS_TILE_W;
+    if (i >= A.width || j >= A.height) return;
+    const size_t plane = (size_t)A.width * A.height;
+    for (int slot = blockIdx.z; slot < A.n_slots; slot += gridDim.z) {
+        const size_t p = (size_t)slot * plane + (size_t)j * A.width + i;
+        const uint64_t key = A.keys[p];
+        float depth = 0.f, x[3] = {0.f, 0.f, 0.f}, n[3] = {0.f, 0.f, 0.f}, rgb[3] = {A.bg[0], A.bg[1], A.bg[2]};
+        int32_t fid = -1, jid = -1;
+        const int job = (int)((uint32_t)key >> MESHV_FACE_BITS), face = (int)((uint32_t)key & ((1u << MESHV_FACE_BITS) - 1u));
+        MeshTri tri;
+        MeshCorners cor;
+        // a key the visibility pass wrote names a face that sets up; anything else is treated as empty, never followed
+        if (key != 0 && job < A.n_jobs && face < A.jobs[job].job.nf &&
+            mesh_setup<true>(A.jobs[job].job, A.vertices, A.faces, face, A.width, A.height, A.near, tri, &cor) == 1) {
+            const MeshShadeJobDev& S = A.jobs[job];
+            const MeshJobDev& J = S.job;
+            depth = __uint_as_float((uint32_t)(key >> 32));
+            fid = face; jid = job;
+            const float la = (float)mesh_edge(tri.bx, tri.by, tri.cx, tri.cy, i << 8, j << 8) * tri.wa;
+            const float lb = (float)mesh_edge(tri.cx, tri.cy, tri.ax, tri.ay, i << 8, j << 8) * tri.wb;
+            const float lc = (float)mesh_edge(tri.ax, tri.ay, tri.bx, tri.by, i << 8, j << 8) * tri.wc;
+            const float den = (la + lb) + lc;
+            const float* va = A.vertices + 3 * ((size_t)J.v0 + (size_t)cor.vi[0]);
+            const float* vb = A.vertices + 3 * ((size_t)J.v0 + (size_t)cor.vi[1]);
+            const float* vc = A.vertices + 3 * ((size_t)J.v0 + (size_t)cor.vi[2]);
+#pragma unroll
+            for (int d = 0; d < 3; ++d) x[d] = mesh_attr(la, lb, lc, den, va[d], vb[d], vc[d]);
+            float P[3];
+#pragma unroll
+            for (int d = 0; d < 3; ++d) P[d] = ((J.R[3 * d] * x[0] + J.R[3 * d + 1] * x[1]) + J.R[3 * d + 2] * x[2]) + J.t[d];
+            float m[3];
+            if (A.normals) {
+                const float* na = A.normals + 3 * ((size_t)J.v0 + (size_t)cor.vi[0]);
+                const float* nb = A.normals + 3 * ((size_t)J.v0 + (size_t)cor.vi[1]);
+                const float* nc = A.normals + 3 * ((size_t)J.v0 + (size_t)cor.vi[2]);
+                float a[3];
+#pragma unroll
+                for (int d = 0; d < 3; ++d) a[d] = mesh_attr(la, lb, lc, den, na[d], nb[d], nc[d]);
+#pragma unroll
+                for (int d = 0; d < 3; ++d) m[d] = (J.R[3 * d] * a[0] + J.R[3 * d + 1] * a[1]) + J.R[3 * d + 2] * a[2];
+            } else {
+                float u[3], v[3];
+#pragma unroll
+                for (int d = 0; d < 3; ++d) { u[d] = cor.P[1][d] - cor.P[0][d]; v[d] = cor.P[2][d] - cor.P[0][d]; }
+                m[0] = u[1] * v[2] - u[2] * v[1];
+                m[1] = u[2] * v[0] - u[0] * v[2];
+                m[2] = u[0] * v[1] - u[1] * v[0];
+            }
+            const float mlen = sqrtf((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]);
+            float diffuse = 0.f;
+            if (mlen > 0.f && mlen < INFINITY) {
+#pragma unroll
+                for (int d = 0; d < 3; ++d) n[d] = m[d] / mlen;
+                if (!A.normals && (n[0] * P[0] + n[1] * P[1]) + n[2] * P[2] > 0.f) {
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) n[d] = -n[d];
+                }
+                float L[3];
+#pragma unroll
+                for (int d = 0; d < 3; ++d) L[d] = A.light[d] - P[d];
+                const float llen = sqrtf((L[0] * L[0] + L[1] * L[1]) + L[2] * L[2]);
+#pragma unroll
+                for (int d = 0; d < 3; ++d) L[d] = L[d] / llen;
+                diffuse = fmaxf((L[0] * n[0] + L[1] * n[1]) + L[2] * n[2], 0.f);
+            }
+            const float light_w = fminf(A.ambient + diffuse, 1.f);
+            if (A.rgb) {
+                float col[3] = {S.surf[0], S.surf[1], S.surf[2]};
+                if (A.colors) {
+                    const float* ca = A.colors + 3 * ((size_t)J.v0 + (size_t)cor.vi[0]);
+                    const float* cb = A.colors + 3 * ((size_t)J.v0 + (size_t)cor.vi[1]);
+                    const float* cc = A.colors + 3 * ((size_t)J.v0 + (size_t)cor.vi[2]);
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) col[d] = mesh_attr(la, lb, lc, den, ca[d], cb[d], cc[d]);
+                }
+#pragma unroll
+                for (int d = 0; d < 3; ++d) rgb[d] = light_w * col[d];
+            }
+        }
+        if (A.depth) A.depth[p] = depth;
+        if (A.face_id) A.face_id[p] = fid;
+        if (A.job_id) A.job_id[p] = jid;
+        mesh_store3(A.xyz, p, x[0], x[1], x[2]);
+        mesh_store3(A.normal, p, n[0], n[1], n[2]);
+        mesh_store3(A.rgb, p, rgb[0], rgb[1], rgb[2]);
+    }
 }
 
 // ---- BOP ground truth from a depth canvas ---------------------------------------------------------------------------

@@ -1495,6 +1495,31 @@ bool mesh_jobs_ok(int32_t n_jobs, const PgrMeshJob* jobs) {
     }
     return true;
 }
+// what pgr_mesh_depth, pgr_mesh_visibility and pgr_mesh_shade ask alike of the meshes, the jobs and the canvases
+bool mesh_call_ok(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int32_t n_jobs,
+                  const PgrMeshJob* jobs, int32_t width, int32_t height, float near_z, int32_t n_slots) {
+    if (!mesh_jobs_ok(n_jobs, jobs) || n_slots < 1 || n_vertices < 0 || n_faces < 0 || width < 1 || width > MESHR_MAX_CANVAS ||
+        height < 1 || height > MESHR_MAX_CANVAS || !(near_z > 0.f) || !std::isfinite(near_z))
+        return false;
+    bool any_faces = false;
+    for (int32_t k = 0; k < n_jobs; ++k) {
+        const PgrMeshJob& j = jobs[k];
+        if ((int64_t)j.vertex_first + j.vertex_count > n_vertices || (int64_t)j.face_first + j.face_count > n_faces ||
+            j.slot < 0 || j.slot >= n_slots)
+            return false;
+        any_faces = any_faces || j.face_count > 0;
+    }
+    return !any_faces || (vertices && faces);
+}
+MeshJobDev mesh_job_dev(const PgrMeshJob& j) {
+    MeshJobDev d{};
+    d.v0 = j.vertex_first; d.nv = j.vertex_count; d.f0 = j.face_first; d.nf = j.face_count;
+    std::memcpy(d.R, j.R, sizeof(d.R));
+    std::memcpy(d.t, j.t, sizeof(d.t));
+    d.fx = j.fx; d.fy = j.fy; d.cx = j.cx; d.cy = j.cy;
+    d.slot = j.slot;
+    return d;
+}
 // jobs [k0, end) of one launch: at most MESHR_JOBS_PER_LAUNCH jobs and MESHR_MAX_GROUP_FACES faces
 int32_t mesh_group_end(int32_t n_jobs, const PgrMeshJob* jobs, int32_t k0, int64_t* faces_out) {
     int64_t faces = 0;
@@ -1525,31 +1550,20 @@ MeshDepthLayout mesh_depth_layout(int32_t n_jobs, const PgrMeshJob* jobs) {
 }
 }  // namespace
 
-size_t pgr_mesh_depth_workspace_bytes(int32_t n_jobs, const PgrMeshJob* jobs) { return mesh_depth_layout(n_jobs, jobs).total; }
-
-int32_t pgr_mesh_depth(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int32_t n_jobs,
-                       const PgrMeshJob* jobs, int32_t width, int32_t height, float near_z, float* depth, int32_t n_slots,
-                       int32_t* straddle_count, void* workspace, size_t workspace_bytes, void* stream_v) {
-    if (!mesh_jobs_ok(n_jobs, jobs) || !depth || !straddle_count || n_slots < 1 || n_vertices < 0 || n_faces < 0 ||
-        width < 1 || width > MESHR_MAX_CANVAS || height < 1 || height > MESHR_MAX_CANVAS || !(near_z > 0.f) ||
-        !std::isfinite(near_z))
+namespace {
+// pgr_mesh_depth (Pix = uint32_t: the depth's bits) and pgr_mesh_visibility (Pix = uint64_t: depth << 32 | job << 22 | face)
+template <typename Pix>
+int32_t mesh_raster_run(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int32_t n_jobs,
+                        const PgrMeshJob* jobs, int32_t width, int32_t height, float near_z, Pix* out, int32_t n_slots,
+                        int32_t* straddle_count, void* workspace, size_t workspace_bytes, void* stream_v, const char* what) {
+    if (!out || !straddle_count || !mesh_call_ok(vertices, n_vertices, faces, n_faces, n_jobs, jobs, width, height, near_z, n_slots))
         return PGR_ERR_INVALID_ARGUMENT;
-    bool any_faces = false;
-    for (int32_t k = 0; k < n_jobs; ++k) {
-        const PgrMeshJob& j = jobs[k];
-        if ((int64_t)j.vertex_first + j.vertex_count > n_vertices || (int64_t)j.face_first + j.face_count > n_faces ||
-            j.slot < 0 || j.slot >= n_slots)
-            return PGR_ERR_INVALID_ARGUMENT;
-        any_faces = any_faces || j.face_count > 0;
-    }
-    if (any_faces && (!vertices || !faces)) return PGR_ERR_INVALID_ARGUMENT;
     const MeshDepthLayout L = mesh_depth_layout(n_jobs, jobs);
     if (n_jobs > 0 && (!L.total || !workspace || workspace_bytes < L.total)) return PGR_ERR_WORKSPACE_TOO_SMALL;
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     const size_t plane = (size_t)width * height, total = plane * (size_t)n_slots;
-    auto* out = reinterpret_cast<uint32_t*>(depth);
-    if (!hip_ok(hipMemsetAsync(out, 0xFF, total * sizeof(uint32_t), stream), "mesh_depth clear") ||
-        !hip_ok(hipMemsetAsync(straddle_count, 0, sizeof(int32_t), stream), "mesh_depth clear"))
+    if (!hip_ok(hipMemsetAsync(out, 0xFF, total * sizeof(Pix), stream), what) ||
+        !hip_ok(hipMemsetAsync(straddle_count, 0, sizeof(int32_t), stream), what))
         return PGR_ERR_LAUNCH_FAILURE;
     char* ws = static_cast<char*>(workspace);
     auto* qctr = reinterpret_cast<unsigned long long*>(ws + L.qctr);
@@ -1562,29 +1576,90 @@ int32_t pgr_mesh_depth(const float* vertices, int64_t n_vertices, const int32_t*
         T.width = width;
         T.height = height;
         T.near = near_z;
+        T.first = k0;
         uint32_t blocks = 0;
         for (int32_t k = k0; k < k1; ++k) {
-            const PgrMeshJob& j = jobs[k];
-            MeshJobDev& d = T.job[k - k0];
-            d.v0 = j.vertex_first; d.nv = j.vertex_count; d.f0 = j.face_first; d.nf = j.face_count;
-            std::memcpy(d.R, j.R, sizeof(d.R));
-            std::memcpy(d.t, j.t, sizeof(d.t));
-            d.fx = j.fx; d.fy = j.fy; d.cx = j.cx; d.cy = j.cy;
-            d.slot = j.slot;
-            d.block0 = blocks;
-            blocks += (uint32_t)((j.face_count + MESHR_THREADS - 1) / MESHR_THREADS);
+            T.job[k - k0] = mesh_job_dev(jobs[k]);
+            T.job[k - k0].block0 = blocks;
+            blocks += (uint32_t)((jobs[k].face_count + MESHR_THREADS - 1) / MESHR_THREADS);
         }
         k0 = k1;
         if (!blocks) continue;
-        if (!hip_ok(hipMemsetAsync(qctr, 0, sizeof(unsigned long long), stream), "mesh_depth queue clear"))
-            return PGR_ERR_LAUNCH_FAILURE;
-        mesh_small_kernel<<<blocks, MESHR_THREADS, 0, stream>>>(T, vertices, faces, out, plane, qctr, queue,
-                                                                (long long)group_faces, straddle_count);
-        mesh_large_kernel<<<MESHR_LARGE_WAVES / (MESHR_THREADS / WAVE), MESHR_THREADS, 0, stream>>>(
+        if (!hip_ok(hipMemsetAsync(qctr, 0, sizeof(unsigned long long), stream), what)) return PGR_ERR_LAUNCH_FAILURE;
+        mesh_small_kernel<Pix><<<blocks, MESHR_THREADS, 0, stream>>>(T, vertices, faces, out, plane, qctr, queue,
+                                                                     (long long)group_faces, straddle_count);
+        mesh_large_kernel<Pix><<<MESHR_LARGE_WAVES / (MESHR_THREADS / WAVE), MESHR_THREADS, 0, stream>>>(
             T, vertices, faces, out, plane, qctr, queue, (long long)group_faces);
     }
-    mesh_finalize_kernel<<<(unsigned)std::min<size_t>((total + 255) / 256, 65536), 256, 0, stream>>>(out, total);
-    return hip_ok(hipGetLastError(), "mesh_depth launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+    mesh_finalize_kernel<Pix><<<(unsigned)std::min<size_t>((total + 255) / 256, 65536), 256, 0, stream>>>(out, total);
+    return hip_ok(hipGetLastError(), what) ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+}  // namespace
+
+size_t pgr_mesh_depth_workspace_bytes(int32_t n_jobs, const PgrMeshJob* jobs) { return mesh_depth_layout(n_jobs, jobs).total; }
+
+int32_t pgr_mesh_depth(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int32_t n_jobs,
+                       const PgrMeshJob* jobs, int32_t width, int32_t height, float near_z, float* depth, int32_t n_slots,
+                       int32_t* straddle_count, void* workspace, size_t workspace_bytes, void* stream_v) {
+    return mesh_raster_run(vertices, n_vertices, faces, n_faces, n_jobs, jobs, width, height, near_z,
+                           reinterpret_cast<uint32_t*>(depth), n_slots, straddle_count, workspace, workspace_bytes, stream_v,
+                           "mesh_depth launch");
+}
+
+// the key leaves 10 bits for the job: a call takes at most MESHV_MAX_JOBS jobs, the caller chunks
+size_t pgr_mesh_visibility_workspace_bytes(int32_t n_jobs, const PgrMeshJob* jobs) {
+    return n_jobs > MESHV_MAX_JOBS ? 0 : mesh_depth_layout(n_jobs, jobs).total;
+}
+
+int32_t pgr_mesh_visibility(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int32_t n_jobs,
+                            const PgrMeshJob* jobs, int32_t width, int32_t height, float near_z, uint64_t* keys,
+                            int32_t n_slots, int32_t* straddle_count, void* workspace, size_t workspace_bytes, void* stream_v) {
+    if (n_jobs > MESHV_MAX_JOBS || reinterpret_cast<uintptr_t>(keys) % sizeof(uint64_t)) return PGR_ERR_INVALID_ARGUMENT;
+    return mesh_raster_run(vertices, n_vertices, faces, n_faces, n_jobs, jobs, width, height, near_z, keys, n_slots,
+                           straddle_count, workspace, workspace_bytes, stream_v, "mesh_visibility launch");
+}
+
+// pgr_mesh_shade's workspace: the device-side job table
+size_t pgr_mesh_shade_workspace_bytes(int32_t n_jobs, const PgrMeshJob* jobs) {
+    if (n_jobs <= 0 || n_jobs > MESHV_MAX_JOBS || !mesh_jobs_ok(n_jobs, jobs)) return 0;
+    return align_up((size_t)n_jobs * sizeof(MeshShadeJobDev), 256);
+}
+
+int32_t pgr_mesh_shade(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int32_t n_jobs,
+                       const PgrMeshJob* jobs, int32_t width, int32_t height, float near_z, const uint64_t* keys,
+                       int32_t n_slots, const PgrMeshShade* shade, void* workspace, size_t workspace_bytes, void* stream_v) {
+    if (n_jobs > MESHV_MAX_JOBS || !keys || !shade || std::isnan(shade->ambient) || reinterpret_cast<uintptr_t>(keys) % sizeof(uint64_t) ||
+        reinterpret_cast<uintptr_t>(workspace) % alignof(MeshShadeJobDev) ||
+        !mesh_call_ok(vertices, n_vertices, faces, n_faces, n_jobs, jobs, width, height, near_z, n_slots))
+        return PGR_ERR_INVALID_ARGUMENT;
+    const size_t need = pgr_mesh_shade_workspace_bytes(n_jobs, jobs);
+    if (n_jobs > 0 && (!need || !workspace || workspace_bytes < need)) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    auto* table = static_cast<MeshShadeJobDev*>(workspace);
+    for (int32_t k0 = 0; k0 < n_jobs; k0 += MESHR_JOBS_PER_LAUNCH) {
+        MeshShadeTable T{};
+        T.count = std::min(MESHR_JOBS_PER_LAUNCH, n_jobs - k0);
+        T.first = k0;
+        for (int32_t k = 0; k < T.count; ++k) {
+            T.job[k].job = mesh_job_dev(jobs[k0 + k]);
+            for (int d = 0; d < 3; ++d) T.job[k].surf[d] = shade->surf_colors ? shade->surf_colors[3 * (size_t)(k0 + k) + d] : 0.5f;
+        }
+        mesh_shade_table_kernel<<<1, 64, 0, stream>>>(T, table);
+    }
+    MeshShadeArgs A{};
+    A.n_jobs = n_jobs; A.width = width; A.height = height; A.n_slots = n_slots;
+    A.near = near_z; A.ambient = shade->ambient;
+    std::memcpy(A.light, shade->light, sizeof(A.light));
+    std::memcpy(A.bg, shade->bg, sizeof(A.bg));
+    A.vertices = vertices; A.faces = faces; A.normals = shade->normals; A.colors = shade->colors;
+    A.keys = keys; A.jobs = table;
+    A.depth = shade->depth; A.face_id = shade->face_id; A.job_id = shade->job_id;
+    A.xyz = shade->xyz; A.normal = shade->normal; A.rgb = shade->rgb;
+    const dim3 grid((unsigned)((width + MESHS_TILE_W - 1) / MESHS_TILE_W),
+                    (unsigned)((height + MESHS_TILE_H * (MESHS_THREADS / WAVE) - 1) / (MESHS_TILE_H * (MESHS_THREADS / WAVE))),
+                    (unsigned)std::min(n_slots, 65535));
+    mesh_shade_kernel<<<grid, MESHS_THREADS, 0, stream>>>(A);
+    return hip_ok(hipGetLastError(), "mesh_shade launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
 }
 
 int32_t pgr_bop_gt_info(const float* canvases, int32_t n_slots, int32_t canvas_width, int32_t canvas_height, int32_t margin_x,

@@ -9,6 +9,15 @@ calc_gt_info.py; both are pinned in pegasus_amd/csrc/meshraster.hip.h.
 
 recomputes ``mask/``, ``mask_visib/`` and ``scene_gt_info.json`` of every scene under ``<dataset>/train`` from the meshes,
 the poses in ``scene_gt.json`` and the depth images.
+
+Shaded renders (``render``, ``Renderer``, ``vis_object_poses``) come from a visibility buffer: ``pgr_mesh_visibility`` keeps
+(depth, job, face) per pixel, ``pgr_mesh_shade`` resolves it to rgb, depth, model coordinates, normals and ids.
+
+    python -m pegasus_amd.mesh_render --dataset <dir> --models <dir> --vis <out dir> [--results <bop csv>] [--resolve_visib]
+                                      [--shading flat|phong]
+
+writes ``<out>/<scene>/<image>.png`` instead: the models over the photographs at the ground-truth poses (the toolkit's
+vis_gt_poses.py) or at a results file's estimates (vis_est_poses.py).
 """
 from __future__ import annotations
 
@@ -32,36 +41,59 @@ class MeshSet:
     """Triangle meshes by object id, uploaded once: ``vertices`` float32 [V,3] and ``faces`` int32 [F,3] (indices relative to
     the mesh's first vertex) shared by all, ``ranges[obj_id] = (vertex_first, vertex_count, face_first, face_count)``.
     ``meshes``: {obj_id: mesh.Mesh or a PLY path}; ``scale`` multiplies the vertices on load (BOP models are in millimetres:
-    0.001 brings them to metres)."""
+    0.001 brings them to metres).  Paths are read with ply_io.read_ply_model (any BOP model file).
 
-    def __init__(self, meshes: dict, device="cuda", scale: float = 1.0, diameters: Optional[dict] = None):
+    ``normals`` and ``colors``: float32 [V,3] device tensors, None when no mesh of the set has them (a mesh object offers them
+    as attributes of those names).  Where only some have colours the others get 0.5; colours above 1 are divided by 255.  Where
+    only some have normals (or with ``compute_normals``, where none has) the others get ``vertex_normals``."""
+
+    def __init__(self, meshes: dict, device="cuda", scale: float = 1.0, diameters: Optional[dict] = None,
+                 compute_normals: bool = False):
         import torch
-        from .ply_io import read_ply_mesh
-        vs, fs, self.ranges = [], [], {}
+        from .ply_io import read_ply_model
+        vs, fs, ns, cs, self.ranges = [], [], [], [], {}
         v0 = f0 = 0
         for obj_id in sorted(meshes):
             m = meshes[obj_id]
-            v, f = read_ply_mesh(m) if isinstance(m, (str, Path)) else (m.vertices, m.faces)
+            if isinstance(m, (str, Path)):
+                model = read_ply_model(m)
+                v, f, n, c = model["pts"], model["faces"], model.get("normals"), model.get("colors")
+            else:
+                v, f, n, c = m.vertices, m.faces, getattr(m, "normals", None), getattr(m, "colors", None)
             v = np.ascontiguousarray(v, np.float32).reshape(-1, 3)
             f = np.ascontiguousarray(f, np.int32).reshape(-1, 3)
             if scale != 1.0:
                 v = (v.astype(np.float64) * scale).astype(np.float32)
             if len(f) and (f.min() < 0 or f.max() >= len(v)):
                 raise ValueError(f"object {obj_id}: a face names a vertex outside 0..{len(v) - 1}")
+            for name, a in (("normals", n), ("colors", c)):
+                if a is not None and np.asarray(a).reshape(-1, 3).shape[0] != len(v):
+                    raise ValueError(f"object {obj_id}: {name} must be [V,3]")
+            if c is not None:
+                c = np.asarray(c, np.float64).reshape(-1, 3)
+                c = (c / 255.0 if c.size and c.max() > 1.0 else c).astype(np.float32)          # as the toolkit's renderers do
             self.ranges[int(obj_id)] = (v0, len(v), f0, len(f))
             vs.append(v); fs.append(f)
+            ns.append(None if n is None else np.asarray(n, np.float64).reshape(-1, 3).astype(np.float32)); cs.append(c)
             v0 += len(v); f0 += len(f)
         self.vertices = torch.from_numpy(np.concatenate(vs) if vs else np.zeros((0, 3), np.float32)).to(device)
         self.faces = torch.from_numpy(np.concatenate(fs) if fs else np.zeros((0, 3), np.int32)).to(device)
+        self.normals = self.colors = None
+        if compute_normals or any(n is not None for n in ns):
+            ns = [vertex_normals(v, f).astype(np.float32) if n is None else n for v, f, n in zip(vs, fs, ns)]
+            self.normals = torch.from_numpy(np.concatenate(ns) if ns else np.zeros((0, 3), np.float32)).to(device)
+        if any(c is not None for c in cs):
+            cs = [np.full((len(v), 3), 0.5, np.float32) if c is None else c for v, c in zip(vs, cs)]
+            self.colors = torch.from_numpy(np.concatenate(cs)).to(device)
         self.diameters = {int(k): float(v) for k, v in (diameters or {}).items()}
         self.device = self.vertices.device
 
     @classmethod
-    def from_dir(cls, models_dir, device="cuda", scale: float = 1.0) -> "MeshSet":
+    def from_dir(cls, models_dir, device="cuda", scale: float = 1.0, compute_normals: bool = False) -> "MeshSet":
         """Every ``obj_NNNNNN.ply`` of a BOP models directory, diameters from its ``models_info.json`` (scaled alike)."""
         files = BD.model_files(models_dir)
         diam = {int(k): v["diameter"] * scale for k, v in BD.read_models_info(models_dir).items()}
-        return cls(files, device=device, scale=scale, diameters=diam)
+        return cls(files, device=device, scale=scale, diameters=diam, compute_normals=compute_normals)
 
     def mesh(self, obj_id: int):
         """(vertices, faces) of one object as host arrays."""
@@ -121,6 +153,290 @@ def render_depth(meshes: MeshSet, jobs: Sequence, K, size, margin=(0, 0), near: 
                   _lib.ptr(count), _lib.ptr(ws), ws.numel())
         straddle += count
     return (out, straddle) if return_straddle else out
+
+
+# ---- shaded renders: visibility buffer and resolve --------------------------------------------------------------------
+RENDER_OUTPUTS = {"rgb": ("float32", 3), "depth": ("float32", 0), "xyz": ("float32", 3), "normal": ("float32", 3),
+                  "face_id": ("int32", 0), "job_id": ("int32", 0)}
+DEFAULT_SURF_COLOR = (0.5, 0.5, 0.5)             # the toolkit renderers' grey
+
+
+def vertex_normals(vertices, faces) -> np.ndarray:
+    """Per-vertex normals float64 [V,3] by open3d's compute_vertex_normals rule: the unit normals of the faces, summed per
+    vertex in face order, normalised; all in float64 on the host.  A vertex of no face (or of degenerate faces only) gets 0."""
+    v = np.asarray(vertices, np.float64).reshape(-1, 3)
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    fn = np.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]])
+    length = np.linalg.norm(fn, axis=1, keepdims=True)
+    fn = np.divide(fn, length, out=np.zeros_like(fn), where=length > 0)
+    out = np.zeros_like(v)
+    for c in range(3):
+        np.add.at(out, f[:, c], fn)
+    length = np.linalg.norm(out, axis=1, keepdims=True)
+    return np.divide(out, length, out=np.zeros_like(out), where=length > 0)
+
+
+def _slot_chunks(slots, per_call_slots: int):
+    """Calls of a render: jobs that share a slot stay in one call (the visibility pass composites them), a call holds at
+    most PGR_MESH_VISIBILITY_MAX_JOBS jobs and ``per_call_slots`` slots.  Yields (job indices in order, slot ids)."""
+    by_slot = {}
+    for k, s in enumerate(slots):
+        by_slot.setdefault(int(s), []).append(k)
+    jobs, ids = [], []
+    for s, ks in by_slot.items():
+        if len(ks) > _lib.PGR_MESH_VISIBILITY_MAX_JOBS:
+            raise ValueError(f"slot {s} holds {len(ks)} jobs; one slot takes at most {_lib.PGR_MESH_VISIBILITY_MAX_JOBS}")
+        if jobs and (len(jobs) + len(ks) > _lib.PGR_MESH_VISIBILITY_MAX_JOBS or len(ids) >= per_call_slots):
+            yield sorted(jobs), ids
+            jobs, ids = [], []
+        jobs += ks; ids.append(s)
+    if jobs:
+        yield sorted(jobs), ids
+
+
+def render(meshes: MeshSet, jobs: Sequence, K, size, outputs=("rgb", "depth"), shading: str = "phong", ambient: float = 0.5,
+           light=(0.0, 0.0, 0.0), surf_colors=None, bg=(0.0, 0.0, 0.0), margin=(0, 0), near: float = DEFAULT_NEAR,
+           slots: Optional[Sequence[int]] = None, budget_bytes: int = DEFAULT_BUDGET, return_straddle: bool = False) -> dict:
+    """Shaded renders of ``jobs`` = [(obj_id, R, t), ...] as the toolkit's renderers shade them (one light, ambient plus
+    diffuse), and the dense maps only a mesh gives.  Returns {name: device tensor} for every name in ``outputs``:
+
+        rgb      float32 [S,Hc,Wc,3]  min(ambient + max(dot(L, n), 0), 1) * colour; ``bg`` where nothing is hit
+        depth    float32 [S,Hc,Wc]    camera z of the nearest surface (the bytes of render_depth), 0 where nothing is hit
+        xyz      float32 [S,Hc,Wc,3]  model coordinates of the surface point, 0 where nothing is hit
+        normal   float32 [S,Hc,Wc,3]  unit normal in the camera frame, 0 where nothing is hit
+        face_id, job_id  int32 [S,Hc,Wc]  the face (index in its mesh) and the job (index in ``jobs``), -1 where nothing is hit
+
+    ``slots``: the canvas of each job (default: one each, S = len(jobs)); jobs that share a slot are composited nearest-first
+    by the visibility pass itself (at equal depth the earlier job wins).  ``shading``: "phong" interpolates the set's vertex
+    normals (a set without normals raises), "flat" takes the face's own.  The colour is the set's vertex colours; without
+    them, or with ``surf_colors`` ([3] or one [3] per job) given, the surf colour (default the toolkit's 0.5 grey).  ``light``
+    is in the camera frame (the toolkit's default: the camera centre).  ``size``, ``margin``, ``K``, ``near`` as render_depth.
+    The rule is pinned above mesh_shade_kernel in csrc/meshraster.hip.h; calls are chunked by the library's 1024 jobs per call and
+    by ``budget_bytes`` of canvases."""
+    import torch
+    W, H = int(size[0]), int(size[1])
+    mx, my = int(margin[0]), int(margin[1])
+    Wc, Hc = W + 2 * mx, H + 2 * my
+    if not (1 <= Wc <= MAX_CANVAS and 1 <= Hc <= MAX_CANVAS) or mx < 0 or my < 0:
+        raise ValueError(f"canvas {Wc} x {Hc}: each side must be 1..{MAX_CANVAS}")
+    outputs = tuple(outputs)
+    unknown = [o for o in outputs if o not in RENDER_OUTPUTS]
+    if unknown or not outputs:
+        raise ValueError(f"outputs must be a non-empty choice of {sorted(RENDER_OUTPUTS)}, got {outputs!r}")
+    if shading not in ("phong", "flat"):
+        raise ValueError(f"shading must be 'phong' or 'flat', got {shading!r}")
+    if shading == "phong" and meshes.normals is None and ("rgb" in outputs or "normal" in outputs):
+        raise ValueError("shading='phong' needs a mesh set with normals (MeshSet(..., compute_normals=True), or shading='flat')")
+    device = meshes.device
+    if device.type != "cuda":
+        raise RuntimeError("render needs a mesh set on a HIP device; there is no CPU path")
+    J = len(jobs)
+    slots = list(range(J)) if slots is None else [int(s) for s in slots]
+    if len(slots) != J or any(s < 0 for s in slots):
+        raise ValueError("slots must name one canvas >= 0 per job")
+    S = max(slots) + 1 if slots else 0
+    Ks = broadcast_K(K, J)
+    surf = None
+    if surf_colors is not None:
+        surf = np.ascontiguousarray(np.broadcast_to(np.asarray(surf_colors, np.float32), (J, 3)))
+    colors = meshes.colors if surf is None else None
+    normals = meshes.normals if shading == "phong" else None
+    bg32 = np.asarray(bg, np.float32).reshape(3)
+    out = {}
+    for name in outputs:
+        dt, ch = RENDER_OUTPUTS[name]
+        shape = (S, Hc, Wc) + ((ch,) if ch else ())
+        if name == "rgb":
+            out[name] = torch.from_numpy(bg32).to(device).expand(shape).contiguous()
+        else:
+            out[name] = torch.full(shape, -1 if dt == "int32" else 0, dtype=getattr(torch, dt), device=device)
+    straddle = torch.zeros(1, dtype=torch.int32, device=device)
+    per_pixel = 8 + sum(4 * max(RENDER_OUTPUTS[n][1], 1) for n in outputs)
+    per_call = max(1, int(budget_bytes) // (per_pixel * Hc * Wc))
+    for ks, ids in _slot_chunks(slots, per_call):
+        local = {s: q for q, s in enumerate(ids)}
+        chunk = [jobs[k] for k in ks]
+        arr = mesh_jobs(meshes, chunk, Ks[ks], (mx, my), slots=[local[slots[k]] for k in ks])
+        n, ns = len(chunk), len(ids)
+        keys = torch.empty((ns, Hc, Wc), dtype=torch.int64, device=device)
+        count = torch.zeros(1, dtype=torch.int32, device=device)
+        ws = _lib.workspace("pgr_mesh_visibility", device, n, arr)
+        _lib.call("pgr_mesh_visibility", device, _lib.ptr(meshes.vertices), meshes.vertices.shape[0], _lib.ptr(meshes.faces),
+                  meshes.faces.shape[0], n, arr, Wc, Hc, float(near), _lib.ptr(keys), ns, _lib.ptr(count), _lib.ptr(ws), ws.numel())
+        straddle += count
+        part = {name: torch.empty((ns,) + tuple(out[name].shape[1:]), dtype=out[name].dtype, device=device) for name in outputs}
+        sub = None if surf is None else np.ascontiguousarray(surf[ks])
+        shade = _lib.PgrMeshShade(normals=_lib.ptr(normals), colors=_lib.ptr(colors),
+                                  surf_colors=None if sub is None else sub.ctypes.data_as(C.POINTER(C.c_float)),
+                                  light=(C.c_float * 3)(*np.asarray(light, np.float32).reshape(3).tolist()), ambient=float(ambient),
+                                  bg=(C.c_float * 3)(*bg32.tolist()), **{name: _lib.ptr(t) for name, t in part.items()})
+        ws2 = _lib.workspace("pgr_mesh_shade", device, n, arr)
+        _lib.call("pgr_mesh_shade", device, _lib.ptr(meshes.vertices), meshes.vertices.shape[0], _lib.ptr(meshes.faces),
+                  meshes.faces.shape[0], n, arr, Wc, Hc, float(near), _lib.ptr(keys), ns, C.byref(shade), _lib.ptr(ws2), ws2.numel())
+        index = torch.as_tensor(ids, device=device)
+        for name, t in part.items():
+            if name == "job_id":                                     # the index in the call -> the index in ``jobs``
+                lut = torch.as_tensor(ks + [-1], dtype=torch.int32, device=device)
+                t = lut[t.long()]
+            out[name][index] = t
+    if return_straddle:
+        out["straddle"] = straddle
+    return out
+
+
+class Renderer:
+    """The toolkit renderer's calls (renderer.create_renderer(width, height, ...): add_object, remove_object, render_object,
+    set_light_cam_pos, set_light_ambient_weight) on ``render``: code of the toolkit that is handed a renderer takes this one.
+    Models and translations share their unit (the toolkit's: millimetres)."""
+
+    def __init__(self, width: int, height: int, mode: str = "rgb+depth", shading: str = "phong", bg_color=(0.0, 0.0, 0.0, 0.0),
+                 device="cuda", near: float = DEFAULT_NEAR):
+        if mode not in ("rgb+depth", "rgb", "depth"):
+            raise ValueError(f"mode must be 'rgb+depth', 'rgb' or 'depth', got {mode!r}")
+        if shading not in ("phong", "flat"):
+            raise ValueError(f"shading must be 'phong' or 'flat', got {shading!r}")
+        self.width, self.height, self.mode, self.shading = int(width), int(height), mode, shading
+        self.bg_color = tuple(float(c) for c in bg_color)[:3]
+        self.device, self.near = device, float(near)
+        self.light_cam_pos, self.light_ambient_weight = (0.0, 0.0, 0.0), 0.5
+        self.model_paths, self.surf_colors, self._meshes = {}, {}, None
+
+    def set_light_cam_pos(self, light_cam_pos):
+        self.light_cam_pos = tuple(float(x) for x in np.asarray(light_cam_pos, np.float64).reshape(3))
+
+    def set_light_ambient_weight(self, light_ambient_weight):
+        self.light_ambient_weight = float(light_ambient_weight)
+
+    def add_object(self, obj_id, model_path, surf_color=None, **kwargs):
+        """``surf_color``: a colour (r, g, b in [0,1]) used instead of the model's vertex colours.  Other keywords of the
+        toolkit's renderers are accepted and ignored."""
+        self.model_paths[int(obj_id)] = model_path
+        self.surf_colors[int(obj_id)] = surf_color
+        self._meshes = None
+
+    def remove_object(self, obj_id):
+        self.model_paths.pop(int(obj_id), None)
+        self.surf_colors.pop(int(obj_id), None)
+        self._meshes = None
+
+    @property
+    def meshes(self) -> MeshSet:
+        if self._meshes is None:
+            self._meshes = MeshSet(dict(self.model_paths), device=self.device, compute_normals=self.shading == "phong")
+        return self._meshes
+
+    def render_object(self, obj_id, R, t, fx, fy, cx, cy) -> dict:
+        """{'rgb': uint8 [H,W,3], 'depth': float32 [H,W]} (what the mode names) as host arrays; rgb = rint(255 clip(rgb, 0, 1))."""
+        K = np.array([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]], np.float64)
+        outputs = tuple(o for o in ("rgb", "depth") if o in self.mode.split("+"))
+        surf = self.surf_colors.get(int(obj_id))
+        got = render(self.meshes, [(int(obj_id), np.asarray(R, np.float64).reshape(3, 3), np.asarray(t, np.float64).reshape(3))],
+                     K, (self.width, self.height), outputs=outputs, shading=self.shading, ambient=self.light_ambient_weight,
+                     light=self.light_cam_pos, surf_colors=None if surf is None else [surf], bg=self.bg_color, near=self.near)
+        out = {}
+        if "rgb" in got:
+            out["rgb"] = rgb_to_uint8(got["rgb"][0]).cpu().numpy()
+        if "depth" in got:
+            out["depth"] = got["depth"][0].cpu().numpy()
+        return out
+
+
+def rgb_to_uint8(rgb):
+    """rint(255 clip(rgb, 0, 1)) as uint8, in float32 (torch.round is round-half-even, as rint)."""
+    import torch
+    return torch.round(rgb.clamp(0.0, 1.0) * 255.0).to(torch.uint8)
+
+
+BBOX_GREY = int(0.3 * 255)                       # visualization.vis_object_poses: bbox_color = (0.3, 0.3, 0.3)
+
+
+def draw_rect(im: np.ndarray, rect, value: int = BBOX_GREY) -> np.ndarray:
+    """visualization.draw_rect without PIL: the one-pixel outline of [x, y, w, h] (corners (x, y) and (x + w, y + h), both
+    drawn), clipped to the image, set to ``value`` in every channel; in place."""
+    x0, y0, x1, y1 = int(rect[0]), int(rect[1]), int(rect[0] + rect[2]), int(rect[1] + rect[3])
+    H, W = im.shape[:2]
+    xs, ys = slice(max(x0, 0), min(x1, W - 1) + 1), slice(max(y0, 0), min(y1, H - 1) + 1)
+    for y in (y0, y1):
+        if 0 <= y < H:
+            im[y, xs] = value
+    for x in (x0, x1):
+        if 0 <= x < W:
+            im[ys, x] = value
+    return im
+
+
+def depth_for_vis(depth, valid_start=0.2, valid_end=1.0):
+    """visualization.depth_for_vis: the positive values of ``depth`` brought to [valid_start, valid_end], float64."""
+    mask = depth > 0
+    d = depth.astype(np.float64)
+    if mask.any():
+        d[mask] -= d[mask].min()
+        top = d[mask].max()
+        if top > 0:
+            d[mask] /= top / (valid_end - valid_start)
+        d[mask] += valid_start
+    return d
+
+
+def vis_object_poses(poses, K, meshes: MeshSet, rgb=None, depth=None, vis_rgb_path=None, vis_depth_diff_path=None,
+                     vis_rgb_resolve_visib: bool = False, shading: str = "phong", near: float = DEFAULT_NEAR) -> dict:
+    """visualization.vis_object_poses with the renderer replaced by the mesh set: the models of ``poses`` = [{'obj_id', 'R',
+    't'}, ...] shaded and blended over ``rgb`` (uint8 [H,W,3]), and their depth against ``depth`` [H,W] (the poses' unit).
+
+    With ``vis_rgb_resolve_visib`` all poses share one canvas (the nearest surface shows); otherwise each is rendered in its
+    own and the images are summed, saturating at 255.  The RGB visualisation is 0.5 rgb + 0.5 render plus the grey box
+    (misc.calc_2d_bbox of each object's own pixels), clipped at 255; the depth-difference image follows the toolkit's
+    (valid = depth > 0 and rendered > 0, difference = valid (rendered - depth), red where it is below the VSD delta of 15).
+    No text labels.  Images are written as PNG; returned: {'vis_rgb', 'depth_diff', 'depth_diff_vis', 'ren_depth'} (those asked for)."""
+    vis_rgb, vis_diff = vis_rgb_path is not None, vis_depth_diff_path is not None
+    if vis_rgb and rgb is None:
+        raise ValueError("RGB visualization triggered but RGB image not provided.")
+    if vis_diff and depth is None:
+        raise ValueError("Depth visualization triggered but D image not provided.")
+    ref = rgb if rgb is not None else depth
+    if ref is None:
+        raise ValueError("an rgb or a depth image is needed for the image size")
+    H, W = ref.shape[:2]
+    if rgb is not None and depth is not None and depth.shape[:2] != (H, W):
+        raise ValueError("The RGB and D images must have the same size.")
+    jobs = [(int(p["obj_id"]), np.asarray(p["R"], np.float64).reshape(3, 3), np.asarray(p["t"], np.float64).reshape(3))
+            for p in poses]
+    out = {}
+    shared = None
+    if jobs and (vis_diff or (vis_rgb and vis_rgb_resolve_visib)):
+        shared = render(meshes, jobs, K, (W, H), outputs=("rgb", "depth") if vis_rgb else ("depth",), shading=shading, near=near,
+                        slots=[0] * len(jobs))
+    if vis_rgb:
+        ren = np.zeros((H, W, 3), np.uint8)
+        info = np.zeros((H, W, 3), np.uint8)
+        if jobs:
+            own = rgb_to_uint8(render(meshes, jobs, K, (W, H), outputs=("rgb",), shading=shading, near=near)["rgb"]).cpu().numpy()
+            if vis_rgb_resolve_visib:
+                ren = rgb_to_uint8(shared["rgb"][0]).cpu().numpy()
+            else:
+                ren = np.minimum(own.astype(np.int64).sum(0), 255).astype(np.uint8)
+            for m in own:
+                ys, xs = (m > 0).any(2).nonzero()
+                if len(ys):
+                    draw_rect(info, [xs.min(), ys.min(), xs.max() - xs.min(), ys.max() - ys.min()])
+        vis = 0.5 * np.asarray(rgb).astype(np.float32) + 0.5 * ren.astype(np.float32) + 1.0 * info.astype(np.float32)
+        vis[vis > 255] = 255
+        out["vis_rgb"] = vis.astype(np.uint8)
+        Path(vis_rgb_path).parent.mkdir(parents=True, exist_ok=True)
+        Path(vis_rgb_path).write_bytes(BD.encode_png(out["vis_rgb"]))
+    if vis_diff:
+        ren_depth = shared["depth"][0].cpu().numpy() if shared is not None else np.zeros((H, W), np.float32)
+        d = np.asarray(depth)
+        valid = (d > 0) * (ren_depth > 0)
+        diff = valid * (ren_depth.astype(np.float32) - d)
+        below = (255 * (valid * (diff < 15))).astype(np.uint8)
+        grey = 255 * depth_for_vis(diff - diff.min())
+        image = np.dstack([below, grey, grey]).astype(np.uint8)
+        image[np.logical_not(valid)] = 0
+        out.update(depth_diff=diff, depth_diff_vis=image, ren_depth=ren_depth)
+        Path(vis_depth_diff_path).parent.mkdir(parents=True, exist_ok=True)
+        Path(vis_depth_diff_path).write_bytes(BD.encode_png(image))
+    return out
 
 
 # ---- ground truth ---------------------------------------------------------------------------------------------------
@@ -339,6 +655,35 @@ def recompute_dataset(dataset_dir, models_dir, delta: float = 15.0, translation_
     return scenes
 
 
+def visualize_dataset(dataset_dir, models_dir, out_dir, results=None, resolve_visib: bool = False, shading: str = "phong",
+                      translation_scale: float = 1.0, device="cuda") -> int:
+    """The toolkit's vis_gt_poses.py (or, with ``results`` = a BOP results file, vis_est_poses.py): for every image of every
+    scene under <dataset>/train the models at the ground-truth poses (or at the file's estimates for that scene and image)
+    shaded over the photograph, written to <out>/<scene>/<image>.png.  Returns the number of images written."""
+    unit = BD.unit_of(translation_scale)
+    meshes = MeshSet.from_dir(models_dir, device=device, scale=unit, compute_normals=shading == "phong")
+    ests = None
+    if results is not None:
+        from .pose_eval import read_results
+        ests = {}
+        for e in read_results(results):
+            ests.setdefault((e["scene_id"], e["im_id"]), []).append(dict(obj_id=e["obj_id"], R=e["R"], t=e["t"] * unit))
+    written = 0
+    for scene in map(BD.BopScene, BD.scene_dirs(dataset_dir, "train")):
+        for i in scene.image_ids:
+            if ests is None:
+                poses = [dict(obj_id=int(e["obj_id"]), R=BD.pose_of(e)[0], t=BD.pose_of(e)[1]) for e in scene.gt[i]]
+            else:
+                poses = ests.get((int(scene.path.name), int(i)), []) if scene.path.name.isdigit() else []
+            rgb = scene.read_png("rgb", i)
+            if rgb.ndim == 2:
+                rgb = np.repeat(rgb[:, :, None], 3, 2)
+            vis_object_poses(poses, BD.cam_K(scene.camera[i]), meshes, rgb=rgb, vis_rgb_path=Path(out_dir) / scene.path.name / BD.image_name(i),
+                             vis_rgb_resolve_visib=resolve_visib, shading=shading)
+            written += 1
+    return written
+
+
 def main(argv: Optional[Sequence[str]] = None) -> int:
     p = argparse.ArgumentParser(prog="python -m pegasus_amd.mesh_render", description=__doc__.split("\n\n")[0])
     p.add_argument("--dataset", required=True)
@@ -347,7 +692,16 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     p.add_argument("--translation_scale", type=float, default=1.0,
                    help="what scene_gt's translations were written with: 1 = metres, 1000 = millimetres")
     p.add_argument("--batch", type=int, default=8)
+    p.add_argument("--vis", metavar="DIR", help="instead, write <DIR>/<scene>/<image>.png: the models shaded over every photograph "
+                                               "at the ground-truth poses (the toolkit's vis_gt_poses.py)")
+    p.add_argument("--results", help="with --vis: a BOP results file whose estimates are drawn instead (vis_est_poses.py)")
+    p.add_argument("--resolve_visib", action="store_true", help="with --vis: only the nearest object shows at each pixel")
+    p.add_argument("--shading", choices=("flat", "phong"), default="phong", help="with --vis")
     a = p.parse_args(argv)
+    if a.vis:
+        n = visualize_dataset(a.dataset, a.models, a.vis, a.results, a.resolve_visib, a.shading, a.translation_scale)
+        print(f"wrote {n} visualisation(s) under {a.vis}")
+        return 0
     scenes = recompute_dataset(a.dataset, a.models, a.delta, a.translation_scale, a.batch)
     print(f"recomputed mask/, mask_visib/ and scene_gt_info.json of {len(scenes)} scene(s)")
     return 0

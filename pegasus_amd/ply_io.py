@@ -1,6 +1,8 @@
 """Minimal PLY reader/writer for 3DGS point clouds (the data format on the input side of the render path:
 /root/reference/src/gs/gaussian_model.py:231-288 reads it with ``plyfile``, which is not available here).
-Supports ``binary_little_endian`` and ``ascii`` vertex elements with scalar properties."""
+Supports ``binary_little_endian`` and ``ascii`` vertex elements with scalar properties.  Triangle meshes: ``write_ply_mesh`` /
+``read_ply_mesh`` for the layout the project writes, ``read_ply_model`` / ``write_ply_model`` for BOP object model files (normals,
+colours, texture coordinates skipped) as the toolkit's ``inout.load_ply`` / ``save_ply`` read and write them."""
 from __future__ import annotations
 
 from pathlib import Path
@@ -97,3 +99,152 @@ def read_ply_mesh(path):
     if nf and not (rows["n"] == 3).all():
         raise ValueError("faces must be triangles")
     return v.astype(np.float32), rows["idx"].astype(np.int32)
+
+
+# ---- BOP object models ------------------------------------------------------------------------------------------------
+_INDEX_TYPES = ("int", "uint", "int32", "uint32")
+_COUNT_TYPES = ("uchar", "uint8")
+
+
+def _model_header(data: bytes):
+    """(format, [(element, count, [property tokens])], offset of the body) of a PLY file."""
+    at = data.find(b"end_header")
+    if not data.startswith(b"ply") or at < 0:
+        raise ValueError("not a PLY file")
+    end = data.find(b"\n", at)
+    if end < 0:
+        raise ValueError("PLY header is not terminated")
+    fmt, elements = None, []
+    for line in data[:at].decode("ascii", "replace").splitlines()[1:]:
+        tok = line.split()
+        if not tok or tok[0] == "comment":
+            continue
+        if tok[0] == "format":
+            fmt = tok[1]
+        elif tok[0] == "element":
+            elements.append((tok[1], int(tok[2]), []))
+        elif tok[0] == "property" and elements:
+            elements[-1][2].append(tok[1:])
+    if fmt not in ("binary_little_endian", "ascii"):
+        raise ValueError(f"unsupported PLY format {fmt}")
+    return fmt, elements, end + 1
+
+
+def read_ply_model(path) -> dict:
+    """A BOP object model as the toolkit's inout.load_ply returns it: {'pts' float64 [V,3], 'faces' int64 [F,3]} plus
+    'normals' float64 [V,3] (nx ny nz) and 'colors' [V,3] (red green blue, as stored: uint8 or float) when present.  ASCII and
+    binary little-endian; any scalar vertex properties in any order (texture_u / texture_v and unknown ones are skipped); the
+    face list is ``list uchar|uint8 int|uint|int32|uint32 vertex_indices|vertex_index``; other elements and other face
+    properties are not supported in front of or between them.  Faces that are not triangles, a file that ends early and a face
+    index outside the vertices raise ValueError."""
+    data = Path(path).read_bytes()
+    fmt, elements, off = _model_header(data)
+    text = None
+    if fmt == "ascii":
+        text = data[off:].decode("ascii", "replace").split("\n")
+        line = 0
+    vert, faces = None, None
+    for name, count, props in elements:
+        if name == "vertex":
+            if any(p[0] == "list" for p in props):
+                raise ValueError("list properties in the vertex element are not supported")
+            if any(p[0] not in _TYPES for p in props):
+                raise ValueError(f"unknown vertex property type in {[p[0] for p in props]}")
+            dt = np.dtype([(p[1], "<" + _TYPES[p[0]]) for p in props])
+            if fmt == "ascii":
+                if line + count > len(text):
+                    raise ValueError("PLY file ends inside the vertex element")
+                rows = [text[line + r].split() for r in range(count)]
+                if any(len(r) < len(props) for r in rows):
+                    raise ValueError("PLY file ends inside the vertex element")
+                vert = np.zeros(count, dt)
+                for c, p in enumerate(props):
+                    col = [r[c] for r in rows]
+                    vert[p[1]] = np.array(col, np.float64).astype(dt[p[1]]) if count else []
+                line += count
+            else:
+                if off + count * dt.itemsize > len(data):
+                    raise ValueError("PLY file ends inside the vertex element")
+                vert = np.frombuffer(data, dt, count, off)
+                off += count * dt.itemsize
+        elif name == "face":
+            lists = [p for p in props if p[0] == "list"]
+            if len(props) != 1 or len(lists) != 1 or lists[0][1] not in _COUNT_TYPES or lists[0][2] not in _INDEX_TYPES or \
+                    lists[0][3] not in ("vertex_indices", "vertex_index"):
+                raise ValueError(f"unsupported face properties {props}: one list uchar int vertex_indices expected")
+            it = _TYPES[lists[0][2]]
+            if fmt == "ascii":
+                if line + count > len(text):
+                    raise ValueError("PLY file ends inside the face element")
+                rows = [text[line + r].split() for r in range(count)]
+                if any(not r for r in rows):
+                    raise ValueError("PLY file ends inside the face element")
+                if any(r[0] != "3" or len(r) != 4 for r in rows):
+                    raise ValueError("faces must be triangles")
+                faces = np.array([r[1:] for r in rows], np.int64).reshape(count, 3)
+                line += count
+            else:
+                dt = np.dtype([("n", "u1"), ("idx", "<" + it, (3,))])
+                have = min(count, max(0, len(data) - off) // dt.itemsize)
+                rows = np.frombuffer(data, dt, have, off)
+                if (rows["n"] != 3).any():
+                    raise ValueError("faces must be triangles")
+                if have < count:
+                    raise ValueError("PLY file ends inside the face element")
+                faces = rows["idx"].astype(np.int64)
+                off += count * dt.itemsize
+        elif count:
+            raise ValueError(f"unsupported PLY element {name}")
+    if vert is None or not {"x", "y", "z"} <= set(vert.dtype.names):
+        raise ValueError("no vertex element with x, y, z")
+    cols = lambda names, dt=np.float64: np.stack([vert[n] for n in names], 1).astype(dt) if len(vert) else np.zeros((0, 3), dt)
+    model = {"pts": cols("xyz"), "faces": np.zeros((0, 3), np.int64) if faces is None else faces}
+    if len(model["faces"]) and (model["faces"].min() < 0 or model["faces"].max() >= len(vert)):
+        raise ValueError(f"a face names a vertex outside 0..{len(vert) - 1}")
+    if {"nx", "ny", "nz"} <= set(vert.dtype.names):
+        model["normals"] = cols(("nx", "ny", "nz"))
+    if {"red", "green", "blue"} <= set(vert.dtype.names):
+        model["colors"] = cols(("red", "green", "blue"), np.result_type(*(vert.dtype[n] for n in ("red", "green", "blue"))))
+    return model
+
+
+def write_ply_model(path, pts, faces, normals=None, colors=None, ascii: bool = False):
+    """A BOP object model in the property order of the toolkit's inout.save_ply: x y z, nx ny nz, red green blue (uchar; float
+    colours are written as float), then ``list uchar int vertex_indices``.  Binary little-endian, or ASCII with ``ascii``
+    (floats with 9 significant digits: a float32 survives the round trip)."""
+    pts = np.asarray(pts, np.float32).reshape(-1, 3)
+    faces = np.asarray(faces, np.int32).reshape(-1, 3)
+    fields, cols = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")], [pts]
+    if normals is not None:
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        cols.append(np.asarray(normals, np.float32).reshape(len(pts), 3))
+    if colors is not None:
+        colors = np.asarray(colors).reshape(len(pts), 3)
+        ct = "u1" if colors.dtype.kind in "ui" else "<f4"
+        fields += [("red", ct), ("green", ct), ("blue", ct)]
+        cols.append(colors.astype(ct))
+    names = {"<f4": "float", "u1": "uchar"}
+    header = "ply\nformat %s 1.0\nelement vertex %d\n" % ("ascii" if ascii else "binary_little_endian", len(pts))
+    header += "".join(f"property {names[t]} {n}\n" for n, t in fields)
+    header += "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % len(faces)
+    Path(path).parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        if ascii:
+            fmt = lambda a: [str(int(x)) for x in a] if a.dtype.kind in "ui" else ["%.9g" % x for x in a]
+            for r in range(len(pts)):
+                fh.write((" ".join(sum((fmt(c[r]) for c in cols), [])) + "\n").encode("ascii"))
+            for f in faces:
+                fh.write(("3 %d %d %d\n" % tuple(f)).encode("ascii"))
+        else:
+            arr = np.empty(len(pts), np.dtype(fields))
+            at = 0
+            for c in cols:
+                for k in range(3):
+                    arr[fields[at + k][0]] = c[:, k]
+                at += 3
+            rows = np.empty(len(faces), np.dtype([("n", "u1"), ("idx", "<i4", (3,))]))
+            rows["n"] = 3
+            rows["idx"] = faces
+            fh.write(arr.tobytes())
+            fh.write(rows.tobytes())
