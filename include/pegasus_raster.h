@@ -1013,6 +1013,43 @@ int32_t pgr_mesh_cluster_emit(int32_t n_vertices, const float *vertices, int32_t
                               size_t workspace_bytes, int64_t n_clusters, int64_t n_out_faces, double *out_vertices,
                               int32_t *out_faces, int32_t *cluster_of_vertex, uint8_t *used_quadric, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Per-vertex normals and colours of an extracted mesh (pegasus_amd/mesh.py; the rules stand at the top of
+ * pegasus_amd/csrc/meshattr.hip.h and in DESIGN.md section 21).  `vertices` is a device float32 [n_vertices,3], `faces` a
+ * device int32 [n_faces,3].  Both entries run on `stream`, allocate nothing, wait for nothing, and return the same bytes from
+ * call to call.  Every argument check comes before any launch and gives PGR_ERR_INVALID_ARGUMENT.
+ *
+ * pgr_mesh_vertex_normals: the unit normals of the faces summed per vertex and normalised (the rule of open3d's
+ * compute_vertex_normals), `normals` device float32 [n_vertices,3].  Per face, in float32, each operation rounded on its own:
+ *   e1 = b - a, e2 = c - a, m = e1 x e2, len = sqrtf((m.x m.x + m.y m.y) + m.z m.z); the face adds nothing unless 0 < len < inf
+ *   q = (int64) rintf((m / len) * 2^30), added to the sums of the face's three vertices with 64-bit integer atomics
+ * and per vertex, in float64: s = (double) sum, normal = (float)(s / sqrt((s.x s.x + s.y s.y) + s.z s.z)), 0 where the length
+ * is not > 0.  A face with an index outside [0, n_vertices) is never dereferenced and adds nothing.  Workspace:
+ * pgr_mesh_vertex_normals_workspace_bytes(n_vertices) = 24 n_vertices device bytes, 8-byte aligned, zeroed by the entry (a
+ * host-only function; 0 for n_vertices < 1); a shorter or missing one is an invalid argument.  n_vertices == 0 does nothing;
+ * n_faces == 0 writes zeros.
+ *
+ * pgr_mesh_vertex_colors: every vertex projected into every view, averaged over the views that see it.  `cameras`, `depth`
+ * (PGR_DEPTH_NORMALIZED) and `final_T` as pgr_tsdf_integrate takes them (n_views 1..256, all of one size; each camera's
+ * viewmatrix, tanfovx/y and campos are read); `color` device float32 [n_views,3,H,W], rendered over a ZERO background;
+ * `normals` device float32 [n_vertices,3] or NULL; `fill` HOST float32 [3], read during the call.  Per vertex p (normal n) and
+ * view in order, in float32:
+ *   (x,y,z) = viewmatrix . p; skipped when z <= 0.2
+ *   pixel = floor((x/z) * W/(2 tanfovx) + (W-1)/2 + 0.5), likewise y; skipped outside the image
+ *   alpha = 1 - final_T; skipped when alpha < alpha_min; skipped unless |depth - z| <= depth_tol (a NaN depth fails)
+ *   with normals: e = campos - p, cs = (n . e) / |e|; skipped unless cs > cos_min; w = cs * cs.  Without: w = 1
+ *   acc += w * (color / alpha) per channel, wsum += w, seen += 1
+ * colors (device float32 [n_vertices,3]) = clamp(acc / wsum, 0, 1) where seen > 0, else fill; `seen` (device int32
+ * [n_vertices], may be NULL) the number of views used.  Invalid: a needed NULL, n_views outside 1..256, views of mixed sizes,
+ * alpha_min not > 0, depth_tol negative or NaN, cos_min NaN.  n_vertices == 0 does nothing. */
+size_t pgr_mesh_vertex_normals_workspace_bytes(int32_t n_vertices);
+int32_t pgr_mesh_vertex_normals(int32_t n_vertices, const float *vertices, int32_t n_faces, const int32_t *faces,
+                                float *normals, void *workspace, size_t workspace_bytes, void *stream);
+int32_t pgr_mesh_vertex_colors(int32_t n_vertices, const float *vertices, const float *normals, int32_t n_views,
+                               const PgrCamera *cameras, const float *color, const float *depth, const float *final_T,
+                               float depth_tol, float alpha_min, float cos_min, const float *fill, float *colors,
+                               int32_t *seen, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

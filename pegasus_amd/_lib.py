@@ -334,6 +334,12 @@ SYMBOLS = {
     "pgr_mesh_cluster_emit": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_double,
                                           C.c_double, C.c_int32, C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pgr_mesh_vertex_normals_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "pgr_mesh_vertex_normals": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                            C.c_void_p]),
+    "pgr_mesh_vertex_colors": (C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(PgrCamera), C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float),
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -22,6 +22,7 @@
 #include "cocorle.hip.h"
 #include "knn.hip.h"
 #include "mesh.hip.h"
+#include "meshattr.hip.h"
 #include "meshraster.hip.h"
 #include "obb.hip.h"
 #include "compose.hip.h"
@@ -2551,4 +2552,73 @@ int32_t pgr_mesh_cluster_emit(int32_t n_vertices, const float* vertices, int32_t
         dec_position_kernel<<<(unsigned)((n_clusters + DEC_WAVES - 1) / DEC_WAVES), DEC_BLOCK, 0, stream>>>(a);
     }
     return hip_ok(hipGetLastError(), "mesh_cluster_emit launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+// ---- vertex normals and colours of an extracted mesh (meshattr.hip.h) ------------------------------------------------------
+namespace {
+unsigned attr_blocks(int32_t n) { return (unsigned)(((int64_t)n + MESHATTR_THREADS - 1) / MESHATTR_THREADS); }
+}  // namespace
+
+size_t pgr_mesh_vertex_normals_workspace_bytes(int32_t n_vertices) {
+    return n_vertices < 1 ? 0 : (size_t)n_vertices * 3 * sizeof(int64_t);
+}
+
+int32_t pgr_mesh_vertex_normals(int32_t n_vertices, const float* vertices, int32_t n_faces, const int32_t* faces, float* normals,
+                                void* workspace, size_t workspace_bytes, void* stream_v) {
+    if (n_vertices < 0 || n_faces < 0 || (n_faces > 0 && !faces)) return PGR_ERR_INVALID_ARGUMENT;
+    if (n_vertices == 0) return PGR_OK;                                     // (no vertex: nothing to write, no face is kept)
+    if (!vertices || !normals || !workspace || reinterpret_cast<uintptr_t>(workspace) % sizeof(int64_t) != 0 ||
+        workspace_bytes < pgr_mesh_vertex_normals_workspace_bytes(n_vertices))
+        return PGR_ERR_INVALID_ARGUMENT;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    auto* sums = static_cast<long long*>(workspace);
+    if (!hip_ok(hipMemsetAsync(sums, 0, pgr_mesh_vertex_normals_workspace_bytes(n_vertices), stream), "memset normal sums"))
+        return PGR_ERR_LAUNCH_FAILURE;
+    if (n_faces > 0)
+        vertex_normals_accumulate_kernel<<<attr_blocks(n_faces), MESHATTR_THREADS, 0, stream>>>(n_vertices, vertices, n_faces, faces,
+                                                                                               sums);
+    vertex_normals_finalize_kernel<<<attr_blocks(n_vertices), MESHATTR_THREADS, 0, stream>>>(n_vertices, sums, normals);
+    return hip_ok(hipGetLastError(), "mesh_vertex_normals launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+int32_t pgr_mesh_vertex_colors(int32_t n_vertices, const float* vertices, const float* normals, int32_t n_views,
+                               const PgrCamera* cameras, const float* color, const float* depth, const float* final_T,
+                               float depth_tol, float alpha_min, float cos_min, const float* fill, float* colors, int32_t* seen,
+                               void* stream_v) {
+    if (n_vertices < 0 || n_views < 1 || n_views > TSDF_MAX_VIEWS || !cameras || !color || !depth || !final_T || !fill)
+        return PGR_ERR_INVALID_ARGUMENT;
+    if (!(alpha_min > 0.f) || !(depth_tol >= 0.f) || std::isnan(cos_min)) return PGR_ERR_INVALID_ARGUMENT;
+    if (n_vertices > 0 && (!vertices || !colors)) return PGR_ERR_INVALID_ARGUMENT;
+    const int32_t W = cameras[0].image_width, H = cameras[0].image_height;
+    if (W <= 0 || H <= 0 || (int64_t)W * H > (int64_t)1 << 28) return PGR_ERR_INVALID_ARGUMENT;
+    VertexColorArgs a{};
+    for (int32_t v = 0; v < n_views; ++v) {
+        const PgrCamera& c = cameras[v];
+        if (c.image_width != W || c.image_height != H || !c.viewmatrix || !c.campos || !(c.tanfovx > 0.f) || !(c.tanfovy > 0.f))
+            return PGR_ERR_INVALID_ARGUMENT;
+        a.view[v] = c.viewmatrix;
+        a.campos[v] = c.campos;
+        a.fx[v] = (float)((double)W / (2.0 * (double)c.tanfovx));
+        a.fy[v] = (float)((double)H / (2.0 * (double)c.tanfovy));
+    }
+    if (n_vertices == 0) return PGR_OK;
+    a.n_vertices = n_vertices;
+    a.n_views = n_views;
+    a.width = W;
+    a.height = H;
+    a.cx = (float)(W - 1) * 0.5f;
+    a.cy = (float)(H - 1) * 0.5f;
+    a.depth_tol = depth_tol;
+    a.alpha_min = alpha_min;
+    a.cos_min = cos_min;
+    for (int k = 0; k < 3; ++k) a.fill[k] = fill[k];
+    a.vertices = vertices;
+    a.normals = normals;
+    a.color = color;
+    a.depth = depth;
+    a.final_T = final_T;
+    a.colors = colors;
+    a.seen = seen;
+    vertex_colors_kernel<<<attr_blocks(n_vertices), MESHATTR_THREADS, 0, static_cast<hipStream_t>(stream_v)>>>(a);
+    return hip_ok(hipGetLastError(), "mesh_vertex_colors launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
 }

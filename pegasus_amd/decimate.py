@@ -9,7 +9,7 @@ result need NOT be closed or manifold: removing duplicates breaks the cycle prop
 tensors keep coming from the full mesh.  Parity with open3d is not pinned.
 
     python -m pegasus_amd.decimate --models <dir> [--out <dir>] [--ratio r | --faces n | --voxel v]
-                                   [--contraction average|quadric]
+                                   [--contraction average|quadric] [--normals]
 
 writes ``<models>/../models_eval`` (the directory the BOP toolkit evaluates on: every ``obj_NNNNNN.ply`` at 2.5 % of its
 faces by default, the toolkit's ``TargetPerc``, with a recomputed ``models_info.json`` that keeps the symmetries).
@@ -156,12 +156,15 @@ def simplify_to(mesh: Mesh, target_faces: int, contraction: str = "quadric", dev
 
 
 def write_models_eval(models_dir, out_dir=None, ratio: Optional[float] = 0.025, faces: Optional[int] = None,
-                      voxel: Optional[float] = None, contraction: str = "quadric", device="cuda") -> dict:
+                      voxel: Optional[float] = None, contraction: str = "quadric", device="cuda",
+                      normals: bool = False) -> dict:
     """For every ``obj_NNNNNN.ply`` under ``models_dir`` a decimated PLY under ``out_dir`` (default
     ``<models_dir>/../models_eval``) and a ``models_info.json`` there: diameter and box recomputed on the decimated mesh, the
     symmetries copied from the source.  The size is set by ``voxel`` (a cell edge), else ``faces`` (a face count), else
-    ``ratio`` (of the source's faces; default the toolkit's TargetPerc).  Returns {obj_id: (faces before, faces after, voxel)}."""
-    from .mesh import models_info
+    ``ratio`` (of the source's faces; default the toolkit's TargetPerc).  ``normals``: every decimated mesh is written with
+    vertex normals recomputed on it (mesh.vertex_normals), as the toolkit's remeshing script does.  Returns {obj_id: (faces
+    before, faces after, voxel)}."""
+    from .mesh import models_info, vertex_normals, write_ply
     from .ply_io import read_ply_mesh, write_ply_mesh
     models_dir = Path(models_dir)
     out_dir = Path(out_dir) if out_dir is not None else models_dir.parent / "models_eval"
@@ -177,7 +180,11 @@ def write_models_eval(models_dir, out_dir=None, ratio: Optional[float] = 0.025, 
         else:
             target = int(faces) if faces is not None else int(math.floor(float(ratio) * len(f)))
             small, used_voxel = simplify_to(full, target, contraction, device)
-        write_ply_mesh(out_dir / f"{BD.model_stem(obj_id)}.ply", small.vertices, small.faces)
+        if normals:
+            write_ply(out_dir / f"{BD.model_stem(obj_id)}.ply", Mesh(small.vertices, small.faces,
+                                                                     normals=vertex_normals(small, device=device)))
+        else:
+            write_ply_mesh(out_dir / f"{BD.model_stem(obj_id)}.ply", small.vertices, small.faces)
         src = source_info.get(str(obj_id), {})
         info[str(obj_id)] = models_info(small, src.get("symmetries_discrete"), src.get("symmetries_continuous"))
         report[obj_id] = (len(f), len(small.faces), used_voxel)
@@ -195,9 +202,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     size.add_argument("--faces", type=int, default=None, help="faces kept at the most")
     size.add_argument("--voxel", type=float, default=None, help="the cell edge, in the models' units")
     p.add_argument("--contraction", choices=sorted(CONTRACTIONS), default="quadric")
+    p.add_argument("--normals", action="store_true", help="write nx ny nz, recomputed on every decimated mesh")
     a = p.parse_args(argv)
     ratio = a.ratio if a.ratio is not None else 0.025
-    report = write_models_eval(a.models, a.out, ratio=ratio, faces=a.faces, voxel=a.voxel, contraction=a.contraction)
+    report = write_models_eval(a.models, a.out, ratio=ratio, faces=a.faces, voxel=a.voxel, contraction=a.contraction,
+                               normals=a.normals)
     for obj_id, (before, after, used_voxel) in sorted(report.items()):
         print(f"{BD.model_stem(obj_id)}: {before} -> {after} faces at voxel {used_voxel:.6g}")
     return 0

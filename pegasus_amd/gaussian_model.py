@@ -132,7 +132,9 @@ class GaussianModel:
         f_dc = np.stack([v["f_dc_0"], v["f_dc_1"], v["f_dc_2"]], axis=1)[:, None, :]           # [N,1,3]
         extra = sorted((n for n in names if n.startswith("f_rest_")), key=lambda s: int(s.split("_")[-1]))
         assert len(extra) == 3 * (self.max_sh_degree + 1) ** 2 - 3
-        f_extra = np.stack([v[n] for n in extra], axis=1).reshape(len(v), 3, -1).transpose(0, 2, 1)   # [N,15,3]
+        # [N,15,3]; a degree-0 model has no f_rest_ columns at all (np.stack refuses an empty list)
+        f_extra = (np.stack([v[n] for n in extra], axis=1) if extra else np.zeros((len(v), 0), np.float32)
+                   ).reshape(len(v), 3, -1).transpose(0, 2, 1)
         scales = np.stack([v[n] for n in sorted((n for n in names if n.startswith("scale_")),
                                                 key=lambda s: int(s.split("_")[-1]))], axis=1)
         rots = np.stack([v[n] for n in sorted((n for n in names if n.startswith("rot")),

@@ -7,9 +7,11 @@ the closed outer surface (``pgr_march_count`` / ``pgr_march_emit``).  A density 
 3DGS object is a shell of surface Gaussians, and its level set is two nested surfaces.
 
     python -m pegasus_amd.mesh -m <model dir> --out <dir> --obj_id N [--scale 1000] [--mass 0.1] [--resolution 256]
-                               [--collision_faces N]
+                               [--collision_faces N] [--vertex_colors]
 
-writes ``<out>/models/obj_NNNNNN.ply`` (scaled: BOP models are in mm) with its ``models_info.json`` entry, and
+writes ``<out>/models/obj_NNNNNN.ply`` (scaled: BOP models are in mm; with ``--vertex_colors`` also ``nx ny nz red green
+blue`` per vertex, from the views the mesh is fused from: ``pgr_mesh_vertex_normals`` / ``pgr_mesh_vertex_colors``,
+DESIGN.md section 21) with its ``models_info.json`` entry, and
 ``<out>/urdf/obj_NNNNNN.{obj,urdf}`` in the model's own units for pybullet; with ``--collision_faces`` also
 ``<out>/urdf/obj_NNNNNN_collision.obj``, the mesh decimated by vertex clustering (``pegasus_amd.decimate``), as the URDF's
 collision geometry.
@@ -29,7 +31,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib, bop_dataset as BD
-from .ply_io import write_ply_mesh
+from .ply_io import write_ply_mesh, write_ply_model
 
 NEAR_Z = 0.2                 # pgr_common.h: the renderer culls everything closer than this
 MAX_AXIS = 1024
@@ -69,6 +71,8 @@ class Grid:
 class Mesh:
     vertices: np.ndarray         # float32 [V,3]
     faces: np.ndarray            # int32 [F,3], outward winding
+    normals: Optional[np.ndarray] = None     # float32 [V,3], unit length or 0 (vertex_normals)
+    colors: Optional[np.ndarray] = None      # float32 [V,3] in 0..1 (vertex_colors)
 
     def _tets(self):
         v = self.vertices.astype(np.float64)[self.faces]                  # [F,3,3]: tetrahedra (0, a, b, c)
@@ -109,10 +113,13 @@ class Mesh:
         used = np.zeros(nv, bool)
         used[f[keep].ravel()] = True
         remap = np.cumsum(used) - 1
-        return Mesh(self.vertices[used], remap[f[keep]].astype(np.int32))
+        return Mesh(self.vertices[used], remap[f[keep]].astype(np.int32),
+                    normals=None if self.normals is None else self.normals[used],
+                    colors=None if self.colors is None else self.colors[used])
 
     def scaled(self, scale: float) -> "Mesh":
-        return Mesh((self.vertices.astype(np.float64) * scale).astype(np.float32), self.faces)
+        return Mesh((self.vertices.astype(np.float64) * scale).astype(np.float32), self.faces, normals=self.normals,
+                    colors=self.colors)
 
 
 # ---- the two GPU stages ---------------------------------------------------------------------------------------------
@@ -178,6 +185,117 @@ def march(sdf, grid: Grid, stage_ms: Optional[dict] = None) -> Mesh:
     return out
 
 
+# ---- vertex attributes ----------------------------------------------------------------------------------------------
+def _device_mesh(mesh_or_arrays, device):
+    """(vertices float32 [V,3], faces int32 [F,3]) of a Mesh or a (vertices, faces) pair as contiguous tensors on
+    ``device``; tensors are used where they are, and a host tensor is refused."""
+    import torch
+    v, f = (mesh_or_arrays.vertices, mesh_or_arrays.faces) if hasattr(mesh_or_arrays, "vertices") else mesh_or_arrays
+    out = []
+    for a, dt in ((v, torch.float32), (f, torch.int32)):
+        if isinstance(a, torch.Tensor):
+            if a.device.type != "cuda":
+                raise RuntimeError("vertex attributes need tensors on a HIP device; there is no CPU path")
+            out.append(a.to(dt).reshape(-1, 3).contiguous())
+        else:
+            if torch.device(device).type != "cuda":
+                raise RuntimeError("vertex attributes need a HIP device; there is no CPU path")
+            a = np.ascontiguousarray(a, np.float32 if dt == torch.float32 else np.int32).reshape(-1, 3)
+            out.append(torch.from_numpy(a).to(device))
+    return out
+
+
+def vertex_normals_device(vertices, faces):
+    """pgr_mesh_vertex_normals on device tensors: float32 [V,3] on the same device, enqueued on the current stream."""
+    import torch
+    if vertices.device.type != "cuda" or faces.device.type != "cuda":
+        raise RuntimeError("vertex_normals needs tensors on a HIP device; there is no CPU path")
+    V, F = int(vertices.shape[0]), int(faces.shape[0])
+    normals = torch.empty((V, 3), dtype=torch.float32, device=vertices.device)
+    if V == 0:
+        return normals
+    ws = _lib.workspace("pgr_mesh_vertex_normals", vertices.device, V)
+    _lib.call("pgr_mesh_vertex_normals", vertices.device, V, _lib.ptr(vertices), F, _lib.ptr(faces), _lib.ptr(normals),
+              _lib.ptr(ws), ws.numel())
+    return normals
+
+
+def vertex_normals(mesh_or_arrays, device="cuda") -> np.ndarray:
+    """Per-vertex normals float32 [V,3] of a Mesh or a (vertices, faces) pair by the rule of mesh_render.vertex_normals
+    (the faces' unit normals summed per vertex, normalised), on the GPU and identical from run to run: the sums are
+    64-bit integers of 2^-30 (pgr_mesh_vertex_normals).  A vertex of no face gets 0."""
+    v, f = _device_mesh(mesh_or_arrays, device)
+    return vertex_normals_device(v, f).cpu().numpy()
+
+
+def vertex_colors(mesh, color, depth, final_T, views, *, depth_tol: float, alpha_min: float = 0.5, cos_min: float = 0.3,
+                  fill=(0.5, 0.5, 0.5)):
+    """(colors float32 [V,3] in 0..1, seen int32 [V]) of ``mesh`` from rendered views (pgr_mesh_vertex_colors).  ``color``
+    [V,3,H,W] (rendered over a ZERO background), ``depth`` (normalised, depth mode 1) and ``final_T`` [V,H,W] are device
+    tensors of ``views``.  A view counts for a vertex when the vertex projects into it, the pixel is opaque (alpha >=
+    ``alpha_min``), its depth lies within ``depth_tol`` of the vertex's and, when the mesh has normals, the vertex faces
+    the camera (cosine > ``cos_min``); the views that count are averaged with weight cosine^2.  ``seen`` is the number of
+    views that counted; a vertex no view sees gets ``fill``."""
+    import torch
+    from .rasterizer import camera_structs
+    if not (1 <= len(views) <= MAX_VIEWS):
+        raise ValueError(f"vertex_colors takes 1..{MAX_VIEWS} views, got {len(views)}")
+    device = depth.device
+    if device.type != "cuda" or color.device.type != "cuda" or final_T.device.type != "cuda":
+        raise RuntimeError("vertex_colors needs tensors on a HIP device; there is no CPU path")
+    n = len(views)
+    H, W = int(views[0].image_height), int(views[0].image_width)
+    color = color.reshape(n, 3, *color.shape[-2:]).float().contiguous()
+    depth = depth.reshape(n, *depth.shape[-2:]).float().contiguous()
+    final_T = final_T.reshape(n, *final_T.shape[-2:]).float().contiguous()
+    if tuple(depth.shape) != (n, H, W) or final_T.shape != depth.shape or tuple(color.shape) != (n, 3, H, W):
+        raise ValueError("color must be [V,3,H,W], depth and final_T [V,H,W], of the views' image size")
+    vert = torch.from_numpy(np.ascontiguousarray(mesh.vertices, np.float32).reshape(-1, 3)).to(device)
+    normals = getattr(mesh, "normals", None)
+    if normals is not None:
+        normals = torch.from_numpy(np.ascontiguousarray(normals, np.float32).reshape(-1, 3)).to(device)
+        if normals.shape != vert.shape:
+            raise ValueError("normals must be [V,3]")
+    V = int(vert.shape[0])
+    cams, keep = camera_structs(views, device)
+    out = torch.empty((V, 3), dtype=torch.float32, device=device)
+    seen = torch.empty((V,), dtype=torch.int32, device=device)
+    fill_c = (C.c_float * 3)(*[float(x) for x in fill])
+    _lib.call("pgr_mesh_vertex_colors", device, V, _lib.ptr(vert), _lib.ptr(normals), n, cams, _lib.ptr(color),
+              _lib.ptr(depth), _lib.ptr(final_T), float(depth_tol), float(alpha_min), float(cos_min), fill_c, _lib.ptr(out),
+              _lib.ptr(seen))
+    result = out.cpu().numpy(), seen.cpu().numpy()
+    del keep
+    return result
+
+
+def fill_unseen(mesh, colors, seen) -> np.ndarray:
+    """``colors`` with every unseen vertex (``seen`` == 0) given the mean of its already-coloured edge neighbours, again and
+    again until none is left or nothing changes (host plumbing: a sparse adjacency product in float64).  What stays
+    unreachable keeps its colour."""
+    from scipy.sparse import coo_matrix
+    colors = np.asarray(colors, np.float32).reshape(-1, 3)
+    nv = len(colors)
+    known = np.asarray(seen).reshape(-1) > 0
+    if known.all() or not known.any() or len(mesh.faces) == 0:
+        return colors.copy()
+    f = np.asarray(mesh.faces, np.int64).reshape(-1, 3)
+    a, b = np.r_[f[:, 0], f[:, 1], f[:, 2]], np.r_[f[:, 1], f[:, 2], f[:, 0]]
+    adj = coo_matrix((np.ones(2 * len(a)), (np.r_[a, b], np.r_[b, a])), shape=(nv, nv)).tocsr()
+    adj.data[:] = 1.0                                                   # an edge counts once, however many faces share it
+    out = colors.astype(np.float64)
+    while not known.all():
+        k = known.astype(np.float64)
+        count = adj @ k
+        reach = ~known & (count > 0)
+        if not reach.any():
+            break
+        total = adj @ (out * k[:, None])
+        out[reach] = total[reach] / count[reach, None]
+        known = known | reach
+    return out.astype(np.float32)
+
+
 # ---- from a Gaussian model ------------------------------------------------------------------------------------------
 def default_bounds(xyz: np.ndarray, opacity: np.ndarray):
     """Per axis the 0.5-99.5 percentile of the means of Gaussians with opacity >= 0.1, padded on every side by 10 % of
@@ -210,8 +328,10 @@ def sphere_views(center, half_diag: float, n_views: int, image_size: int):
     return specs, r, fov
 
 
-def render_views(gaussians, views, stage_ms: Optional[dict] = None):
-    """Normalised depth and final_T [V,H,W] of ``views``, rendered in batches sized to the free device memory."""
+def render_views(gaussians, views, stage_ms: Optional[dict] = None, want_color: bool = False):
+    """Normalised depth and final_T [V,H,W] of ``views``, rendered in batches sized to the free device memory.
+    ``want_color``: also the colour images [V,3,H,W] of the same renders, as a third value (over the views' background:
+    sphere_views renders over zero, which vertex_colors needs)."""
     import torch
     from .rasterizer import forward_views
     xyz = gaussians.get_xyz.detach()
@@ -222,6 +342,7 @@ def render_views(gaussians, views, stage_ms: Optional[dict] = None):
     batch = int(max(1, min(32, len(views), (free // 4) // max(per_view, 1))))
     depth = torch.empty((len(views), H, W), dtype=torch.float32, device=xyz.device)
     final_T = torch.empty_like(depth)
+    color = torch.empty((len(views), 3, H, W), dtype=torch.float32, device=xyz.device) if want_color else None
     kw = dict(shs=gaussians.get_features.detach(), scales=gaussians.get_scaling.detach(),
               rotations=gaussians.get_rotation.detach(), sh_degree=int(gaussians.active_sh_degree))
     opac = gaussians.get_opacity.detach()
@@ -233,30 +354,71 @@ def render_views(gaussians, views, stage_ms: Optional[dict] = None):
         for k, r in enumerate(outs):
             depth[b + k] = r["depth"][0]
             final_T[b + k] = r["final_T"]
+            if want_color:
+                color[b + k] = r["color"]
     if start:
         end = torch.cuda.Event(enable_timing=True)
         end.record()
         end.synchronize()
         stage_ms["render"] = start.elapsed_time(end)
-    return depth, final_T
+    return (depth, final_T, color) if want_color else (depth, final_T)
+
+
+def _model_bounds(gaussians, bounds):
+    if bounds is None:
+        bounds = default_bounds(gaussians.get_xyz.detach().cpu().numpy(), gaussians.get_opacity.detach().cpu().numpy())
+    return tuple(np.asarray(b, np.float64) for b in bounds)
+
+
+def _attributes(mesh: Mesh, color, depth, final_T, views, depth_tol: float, alpha_min: float, cos_min: float,
+                stage_ms: Optional[dict] = None, info: Optional[dict] = None) -> Mesh:
+    """``mesh`` with normals (vertex_normals) and colours (vertex_colors, then fill_unseen) from the rendered views."""
+    import torch
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if stage_ms is not None else None
+    if ev:
+        ev[0].record()
+    normals = vertex_normals(mesh, device=depth.device)
+    if ev:
+        ev[1].record()
+    with_normals = Mesh(mesh.vertices, mesh.faces, normals=normals)
+    colors, seen = vertex_colors(with_normals, color, depth, final_T, views, depth_tol=depth_tol, alpha_min=alpha_min,
+                                 cos_min=cos_min)
+    if ev:
+        ev[2].record()
+        ev[2].synchronize()
+        stage_ms["normals"] = ev[0].elapsed_time(ev[1])
+        stage_ms["colors"] = ev[1].elapsed_time(ev[2])
+    if info is not None:
+        info["unseen"] = int((seen == 0).sum())
+        info["vertices"] = int(len(seen))
+    with_normals.colors = fill_unseen(mesh, colors, seen)
+    return with_normals
 
 
 def extract_mesh(gaussians, *, resolution: int = 256, n_views: int = 96, image_size: int = 512, alpha_min: float = 0.5,
-                 truncation_voxels: float = 4.0, bounds=None, stage_ms: Optional[dict] = None) -> Mesh:
+                 truncation_voxels: float = 4.0, bounds=None, stage_ms: Optional[dict] = None, colors: bool = False,
+                 depth_tol_voxels: float = 2.0, cos_min: float = 0.3, info: Optional[dict] = None) -> Mesh:
     """The closed outer surface of a GaussianModel (read through its activated getters), in the model's units.
     ``bounds``: (lo[3], hi[3]) of the grid, default default_bounds().  ``resolution``: grid points on the longest axis.
-    ``stage_ms``: a dict that receives the GPU milliseconds of the render, integrate, count and emit stages."""
+    ``stage_ms``: a dict that receives the GPU milliseconds of the render, integrate, count and emit stages (and of the
+    normals and colors stages with ``colors``).
+    ``colors``: the mesh also carries ``normals`` and ``colors``, taken from the same renders (the views are rendered once):
+    a view colours a vertex when its depth there lies within ``depth_tol_voxels`` voxels of the vertex and the vertex faces
+    it by more than ``cos_min``; vertices no view sees take their neighbours' colours (fill_unseen).  Vertices and faces are
+    the same either way.  ``info``: a dict that receives the number of ``vertices`` and of those ``unseen`` before the fill."""
     import torch
     if not (2 <= resolution <= MAX_AXIS):
         raise ValueError(f"resolution must be 2..{MAX_AXIS}")
-    if bounds is None:
-        bounds = default_bounds(gaussians.get_xyz.detach().cpu().numpy(), gaussians.get_opacity.detach().cpu().numpy())
-    lo, hi = (np.asarray(b, np.float64) for b in bounds)
+    lo, hi = _model_bounds(gaussians, bounds)
     grid = Grid.around(lo, hi, resolution)
     views, _r, _fov = sphere_views(0.5 * (lo + hi), 0.5 * float(np.linalg.norm(hi - lo)), n_views, image_size)
     if len(views) > MAX_VIEWS:
         raise ValueError(f"n_views: at most {MAX_VIEWS} views are fused")
-    depth, final_T = render_views(gaussians, views, stage_ms)
+    color = None
+    if colors:
+        depth, final_T, color = render_views(gaussians, views, stage_ms, want_color=True)
+    else:
+        depth, final_T = render_views(gaussians, views, stage_ms)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if stage_ms is not None else None
     if ev:
         ev[0].record()
@@ -268,13 +430,42 @@ def extract_mesh(gaussians, *, resolution: int = 256, n_views: int = 96, image_s
         stage_ms["integrate"] = ev[0].elapsed_time(ev[1])
     # a trained shell has gaps: rays through them carve pockets inside, and an unseen speck may stay outside; the body
     # is the largest closed piece
-    return mesh.largest_component()
+    mesh = mesh.largest_component()
+    if colors:
+        mesh = _attributes(mesh, color, depth, final_T, views, depth_tol_voxels * grid.voxel, alpha_min, cos_min, stage_ms,
+                           info)
+    return mesh
+
+
+def colorize(gaussians, mesh: Mesh, *, n_views: int = 96, image_size: int = 512, alpha_min: float = 0.5,
+             depth_tol: Optional[float] = None, cos_min: float = 0.3, bounds=None, stage_ms: Optional[dict] = None,
+             info: Optional[dict] = None) -> Mesh:
+    """``mesh`` (in the model's frame: an extracted mesh, or one decimated from it) with normals and colours from renders of
+    ``gaussians`` on the sphere of views extract_mesh uses.  ``depth_tol``: how far a view's depth may lie from a vertex, in
+    the model's units; default 2 voxels of extract_mesh's default grid (the longest side of the bounds / 255)."""
+    lo, hi = _model_bounds(gaussians, bounds)
+    if depth_tol is None:
+        depth_tol = 2.0 * float((hi - lo).max()) / 255.0
+    views, _r, _fov = sphere_views(0.5 * (lo + hi), 0.5 * float(np.linalg.norm(hi - lo)), n_views, image_size)
+    if len(views) > MAX_VIEWS:
+        raise ValueError(f"n_views: at most {MAX_VIEWS} views are used")
+    depth, final_T, color = render_views(gaussians, views, stage_ms, want_color=True)
+    return _attributes(Mesh(mesh.vertices, mesh.faces), color, depth, final_T, views, depth_tol, alpha_min, cos_min, stage_ms,
+                       info)
 
 
 # ---- files ----------------------------------------------------------------------------------------------------------
 def write_ply(path, mesh: Mesh, scale: float = 1.0):
-    """Binary PLY with vertex and face elements; vertices multiplied by ``scale`` (1000: metres -> BOP millimetres)."""
-    write_ply_mesh(path, mesh.scaled(scale).vertices, mesh.faces)
+    """Binary PLY with vertex and face elements; vertices multiplied by ``scale`` (1000: metres -> BOP millimetres).  A mesh
+    with normals or colours is written in the property order of a BOP model file (ply_io.write_ply_model): normals as
+    float, colours as uchar = rint(255 c)."""
+    if mesh.normals is None and mesh.colors is None:
+        write_ply_mesh(path, mesh.scaled(scale).vertices, mesh.faces)
+        return
+    colors = mesh.colors
+    if colors is not None:
+        colors = np.rint(255.0 * np.clip(np.asarray(colors, np.float64), 0.0, 1.0)).astype(np.uint8)
+    write_ply_model(path, mesh.scaled(scale).vertices, mesh.faces, normals=mesh.normals, colors=colors)
 
 
 def write_obj(path, mesh: Mesh):
@@ -399,6 +590,8 @@ def _parser():
     p.add_argument("--collision_faces", type=int, default=None, metavar="N",
                    help="also write urdf/<name>_collision.obj, the mesh decimated to at most N faces by vertex clustering "
                         "(pegasus_amd.decimate.simplify_to), and name it in the URDF's <collision> element")
+    p.add_argument("--vertex_colors", action="store_true",
+                   help="models/<name>.ply also carries nx ny nz red green blue, from the views the mesh is fused from")
     p.add_argument("--sym_continuous", type=float, nargs=6, action="append", metavar=("AX", "AY", "AZ", "OX", "OY", "OZ"),
                    help="a continuous rotational symmetry: axis and a point on it, in model units (repeatable)")
     p.add_argument("--sym_discrete", type=float, nargs=16, action="append", metavar="M",
@@ -420,7 +613,7 @@ def scaled_symmetries(sym_discrete, sym_continuous, scale: float):
 def main(argv: Optional[Sequence[str]] = None) -> int:
     a = _parser().parse_args(argv)
     mesh = extract_mesh(load_model(a.model_path, a.iteration, a.clean_pcd), resolution=a.resolution, n_views=a.n_views,
-                        image_size=a.image_size)
+                        image_size=a.image_size, colors=a.vertex_colors)
     name = BD.model_stem(a.obj_id)
     out = Path(a.out)
     write_ply(out / "models" / f"{name}.ply", mesh, scale=a.scale)
