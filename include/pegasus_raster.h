@@ -1050,6 +1050,59 @@ int32_t pgr_mesh_vertex_colors(int32_t n_vertices, const float *vertices, const 
                                float depth_tol, float alpha_min, float cos_min, const float *fill, float *colors,
                                int32_t *seen, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Collision geometry: signed distance fields of triangle meshes and distance / sweep queries between posed bodies
+ * (pegasus_amd/collision.py; the rules stand at the top of pegasus_amd/csrc/meshsdf.hip.h and in DESIGN.md section 22).  All
+ * three entries run on `stream`, allocate nothing, wait for nothing, use no floating-point atomic and return the same bytes
+ * from call to call.  Every argument check comes before any launch and gives PGR_ERR_INVALID_ARGUMENT.  Positive is outside.
+ *
+ * pgr_mesh_sdf: `vertices` device float32 [n_vertices,3], `faces` device int32 [n_faces,3], `grid` as above; `sdf` device
+ * float32 [nz,ny,nx]: at every grid point the exact distance to the nearest triangle (a zero-area face counts as its segment
+ * or point), negative where the generalized winding number (the faces' signed solid angles over 4 pi) is >= 0.5; `winding`
+ * (device float32 [nz,ny,nx], may be NULL) receives that number.  n_faces == 0 writes +inf (and winding 0).  A face with an
+ * index outside [0, n_vertices) is never dereferenced and adds nothing.  Brute force, points x faces, PGR_SDF_FACE_TILE faces
+ * per pass through LDS: meant for collision meshes of a few 10^4 faces.  Invalid: a bad grid, a negative count, a needed NULL.
+ *
+ * pgr_sdf_sample: `points` device float32 [n_points,3]; `values` device float32 [n_points]: the trilinear field value;
+ * `gradients` (device float32 [n_points,3], may be NULL): the analytic derivative of the trilinear cell.  Outside the grid the
+ * value is sqrt(r^2 + max(field, 0)^2) with r the distance to the grid's box and the field taken at the clamped point (a lower
+ * bound of the distance to the surface while the grid encloses the mesh), the gradient that of the clamped point.
+ * n_points == 0 does nothing.
+ *
+ * pgr_sdf_sweep: `bodies` and `jobs` are HOST tables, read during the call and handed to the kernels by value.  A body is a
+ * grid with its field (device, may be NULL for a body that is never a target), shell points (device float32 [n_shell,3], body
+ * frame) and a pose (R row-major, t).  A job moves the shell of body `mover` along the unit vector `dir` against body
+ * `target`, or against the plane n.x = d (`plane` = n, d; n a unit vector) when target == PGR_SWEEP_PLANE.  Per shell point:
+ * phi0, the target's field at the point (pgr_sdf_sample's rule in the target's frame; n.x - d for the plane), and s, the free
+ * travel by sphere tracing: the point steps by the sampled field while field > tol, s < max_travel and fewer than max_steps
+ * steps were taken (closed form for the plane).  out (device uint64 [n_jobs,2]): word 0 the minimum of phi0, word 1 the
+ * minimum of s over the job's points, each as (order-preserving bits of the float) << 32 | point index: bits ^ 0x80000000
+ * for a float with a clear sign bit, ~bits otherwise.  Equal floats resolve to the lowest index; a job whose mover has no shell
+ * points keeps all bits set.  Invalid: a needed NULL, a negative count, a job naming a body outside the table or itself, a
+ * target without a field or with a bad grid, a direction or plane normal that is not finite and of unit length within 1e-4,
+ * tol or max_travel that is NaN or negative, max_steps < 0.  n_jobs == 0 does nothing. */
+#define PGR_SDF_FACE_TILE 256
+#define PGR_SWEEP_PLANE (-1)
+typedef struct PgrSdfBody {
+    PgrGrid grid;
+    const float *sdf;
+    const float *shell;
+    int32_t n_shell;
+    float R[9];
+    float t[3];
+} PgrSdfBody;
+typedef struct PgrSweepJob {
+    int32_t mover, target;
+    float dir[3];
+    float plane[4];
+} PgrSweepJob;
+int32_t pgr_mesh_sdf(int32_t n_vertices, const float *vertices, int32_t n_faces, const int32_t *faces, const PgrGrid *grid,
+                     float *sdf, float *winding, void *stream);
+int32_t pgr_sdf_sample(const PgrGrid *grid, const float *sdf, int64_t n_points, const float *points, float *values,
+                       float *gradients, void *stream);
+int32_t pgr_sdf_sweep(int32_t n_bodies, const PgrSdfBody *bodies, int32_t n_jobs, const PgrSweepJob *jobs, float tol,
+                      float max_travel, int32_t max_steps, uint64_t *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -188,6 +188,20 @@ PGR_COCO_CHUNK, PGR_COCO_LDS_RUNS, PGR_COCO_MAX_LANES, PGR_COCO_MAX_MAXDETS = 25
 PGR_PLANE_SUMS, PGR_PLANE_TILE = 12, 2048
 
 
+class PgrSdfBody(C.Structure):
+    _fields_ = [("grid", PgrGrid), ("sdf", C.c_void_p), ("shell", C.c_void_p), ("n_shell", C.c_int32), ("R", C.c_float * 9),
+                ("t", C.c_float * 3)]
+
+
+class PgrSweepJob(C.Structure):
+    _fields_ = [("mover", C.c_int32), ("target", C.c_int32), ("dir", C.c_float * 3), ("plane", C.c_float * 4)]
+
+
+# include/pegasus_raster.h: the faces of one pass of pgr_mesh_sdf through LDS (tests/collision_cases.py is built around it) and
+# the target index that names the plane
+PGR_SDF_FACE_TILE, PGR_SWEEP_PLANE = 256, -1
+
+
 class PgrCocoGroup(C.Structure):
     _fields_ = [("dt_begin", C.c_int32), ("dt_count", C.c_int32), ("gt_begin", C.c_int32), ("gt_count", C.c_int32),
                 ("iou_offset", C.c_int64)]
@@ -340,6 +354,11 @@ SYMBOLS = {
     "pgr_mesh_vertex_colors": (C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(PgrCamera), C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float),
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pgr_mesh_sdf": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(PgrGrid), C.c_void_p, C.c_void_p,
+                                 C.c_void_p]),
+    "pgr_sdf_sample": (C.c_int32, [C.POINTER(PgrGrid), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pgr_sdf_sweep": (C.c_int32, [C.c_int32, C.POINTER(PgrSdfBody), C.c_int32, C.POINTER(PgrSweepJob), C.c_float, C.c_float,
+                                  C.c_int32, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

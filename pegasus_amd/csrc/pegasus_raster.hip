@@ -24,6 +24,7 @@
 #include "mesh.hip.h"
 #include "meshattr.hip.h"
 #include "meshraster.hip.h"
+#include "meshsdf.hip.h"
 #include "obb.hip.h"
 #include "compose.hip.h"
 #include "composite.hip.h"
@@ -2621,4 +2622,88 @@ int32_t pgr_mesh_vertex_colors(int32_t n_vertices, const float* vertices, const 
     a.seen = seen;
     vertex_colors_kernel<<<attr_blocks(n_vertices), MESHATTR_THREADS, 0, static_cast<hipStream_t>(stream_v)>>>(a);
     return hip_ok(hipGetLastError(), "mesh_vertex_colors launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+// ---- collision geometry: mesh distance fields, samples and sweeps (meshsdf.hip.h) ----------------------------------------
+namespace {
+bool unit_vector(const float* v) {
+    if (!std::isfinite(v[0]) || !std::isfinite(v[1]) || !std::isfinite(v[2])) return false;
+    const double n2 = (double)v[0] * v[0] + (double)v[1] * v[1] + (double)v[2] * v[2];
+    return std::fabs(std::sqrt(n2) - 1.0) <= 1e-4;
+}
+}  // namespace
+
+int32_t pgr_mesh_sdf(int32_t n_vertices, const float* vertices, int32_t n_faces, const int32_t* faces, const PgrGrid* grid,
+                     float* sdf, float* winding, void* stream_v) {
+    if (!grid_ok(grid) || n_vertices < 0 || n_faces < 0 || !sdf) return PGR_ERR_INVALID_ARGUMENT;
+    if (n_faces > 0 && (!faces || (n_vertices > 0 && !vertices))) return PGR_ERR_INVALID_ARGUMENT;
+    const size_t n = grid_points(grid);
+    mesh_sdf_kernel<<<(uint32_t)((n + SDF_THREADS - 1) / SDF_THREADS), SDF_THREADS, 0, static_cast<hipStream_t>(stream_v)>>>(
+        mesh_grid(grid), vertices, n_vertices, faces, n_faces, sdf, winding);
+    return hip_ok(hipGetLastError(), "mesh_sdf launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+int32_t pgr_sdf_sample(const PgrGrid* grid, const float* sdf, int64_t n_points, const float* points, float* values,
+                       float* gradients, void* stream_v) {
+    if (!grid_ok(grid) || !sdf || n_points < 0 || n_points > ((int64_t)1 << 38)) return PGR_ERR_INVALID_ARGUMENT;
+    if (n_points > 0 && (!points || !values)) return PGR_ERR_INVALID_ARGUMENT;
+    if (n_points == 0) return PGR_OK;
+    sdf_sample_kernel<<<(uint32_t)((n_points + 255) / 256), 256, 0, static_cast<hipStream_t>(stream_v)>>>(
+        mesh_grid(grid), sdf, (long long)n_points, points, values, gradients);
+    return hip_ok(hipGetLastError(), "sdf_sample launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
+}
+
+int32_t pgr_sdf_sweep(int32_t n_bodies, const PgrSdfBody* bodies, int32_t n_jobs, const PgrSweepJob* jobs, float tol,
+                      float max_travel, int32_t max_steps, uint64_t* out, void* stream_v) {
+    if (n_bodies < 0 || n_jobs < 0 || max_steps < 0 || !(tol >= 0.f) || !(max_travel >= 0.f)) return PGR_ERR_INVALID_ARGUMENT;
+    if ((n_bodies > 0 && !bodies) || (n_jobs > 0 && (!jobs || !out))) return PGR_ERR_INVALID_ARGUMENT;
+    for (int32_t b = 0; b < n_bodies; ++b)
+        if (bodies[b].n_shell < 0 || (bodies[b].n_shell > 0 && !bodies[b].shell)) return PGR_ERR_INVALID_ARGUMENT;
+    for (int32_t k = 0; k < n_jobs; ++k) {
+        const PgrSweepJob& j = jobs[k];
+        if (j.mover < 0 || j.mover >= n_bodies || j.target < PGR_SWEEP_PLANE || j.target >= n_bodies || j.target == j.mover)
+            return PGR_ERR_INVALID_ARGUMENT;
+        if (!unit_vector(j.dir)) return PGR_ERR_INVALID_ARGUMENT;
+        if (j.target == PGR_SWEEP_PLANE) {
+            if (!unit_vector(j.plane) || !std::isfinite(j.plane[3])) return PGR_ERR_INVALID_ARGUMENT;
+        } else if (!grid_ok(&bodies[j.target].grid) || !bodies[j.target].sdf) {
+            return PGR_ERR_INVALID_ARGUMENT;
+        }
+    }
+    if (n_jobs == 0) return PGR_OK;
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    sdf_sweep_init_kernel<<<(2 * n_jobs + 255) / 256, 256, 0, stream>>>(out, 2 * n_jobs);
+    for (int32_t k0 = 0; k0 < n_jobs; k0 += SWEEP_JOBS_PER_LAUNCH) {
+        SweepJobTable T{};
+        T.count = std::min(SWEEP_JOBS_PER_LAUNCH, n_jobs - k0);
+        T.first = k0;
+        T.tol = tol;
+        T.max_travel = max_travel;
+        T.max_steps = max_steps;
+        uint32_t blocks = 0;
+        for (int32_t k = 0; k < T.count; ++k) {
+            const PgrSweepJob& j = jobs[k0 + k];
+            const PgrSdfBody& a = bodies[j.mover];
+            SweepJobDev& d = T.job[k];
+            d.shell = a.shell;
+            d.n_shell = a.n_shell;
+            std::memcpy(d.Ra, a.R, sizeof(d.Ra));
+            std::memcpy(d.ta, a.t, sizeof(d.ta));
+            std::memcpy(d.dir, j.dir, sizeof(d.dir));
+            d.is_plane = j.target == PGR_SWEEP_PLANE;
+            if (d.is_plane) {
+                std::memcpy(d.plane, j.plane, sizeof(d.plane));
+            } else {
+                const PgrSdfBody& b = bodies[j.target];
+                d.sdf = b.sdf;
+                d.g = mesh_grid(&b.grid);
+                std::memcpy(d.Rb, b.R, sizeof(d.Rb));
+                std::memcpy(d.tb, b.t, sizeof(d.tb));
+            }
+            d.block0 = blocks;
+            blocks += (uint32_t)(((int64_t)a.n_shell + SWEEP_THREADS - 1) / SWEEP_THREADS);
+        }
+        if (blocks > 0) sdf_sweep_kernel<<<blocks, SWEEP_THREADS, 0, stream>>>(T, out);
+    }
+    return hip_ok(hipGetLastError(), "sdf_sweep launch") ? PGR_OK : PGR_ERR_LAUNCH_FAILURE;
 }
