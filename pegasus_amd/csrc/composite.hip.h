@@ -84,6 +84,46 @@ __device__ __forceinline__ void pixel_masks(float r, float g, float b, const flo
     }
 }
 
+// pixel_masks for a pixel value that is THE SAME IN EVERY LANE (a quarter of the fused kernel without object entries: the
+// background), all colours [0, k): the k verdicts are wave-uniform, so instead of every lane walking the k colours, lane c
+// takes colour c -- through pixel_masks' expression tree, bit for bit; its wave-wide shortcut is per lane here, which skips
+// the same work for the same reason -- a ballot turns the verdicts into scalar bits, and every plane's byte is stored from
+// its bit (same stores as pixel_masks: one byte per plane and pixel, one record byte per eight planes).
+__device__ __forceinline__ void uniform_pixel_masks(float r, float g, float b, const float* __restrict__ colors, int k, float thr,
+                                                    uint8_t* __restrict__ masks, size_t P, size_t pix, bool inside,
+                                                    uint8_t* __restrict__ rec_masks) {
+    const float far = thr * 1.000001f;
+    const int bytes = (k + 7) >> 3;
+    for (int c0 = 0; c0 < k; c0 += WAVE) {
+        const int c = c0 + (int)threadIdx.x;
+        bool m = false;
+        if (c < k) {
+            const float d0 = r - gload(colors + 3 * c), d1 = g - gload(colors + 3 * c + 1), d2 = b - gload(colors + 3 * c + 2);
+            const bool surely_out = fabsf(d0) > far || fabsf(d1) > far || fabsf(d2) > far;
+            if (!surely_out) {
+                const float dist = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
+                m = dist <= thr;
+            }
+        }
+        const unsigned long long bits = __ballot(m);          // bit j: colour c0 + j (0 beyond k)
+        const int nc = min(WAVE, k - c0);
+        if (inside) {
+            // (not unrolled: the unrolled loops rebuilt every plane's address with 64-bit multiplies, more vector work than
+            // the verdicts they store)
+            if (masks) {
+                uint8_t* plane = masks + (size_t)c0 * P + pix;
+#pragma unroll 1
+                for (int j = 0; j < nc; ++j, plane += P) gstore(plane, (uint8_t)((bits >> j) & 1ull));
+            }
+            if (rec_masks) {
+                uint8_t* byte = rec_masks + pix * (size_t)bytes + (size_t)(c0 >> 3);
+#pragma unroll 1
+                for (int j = 0; j < nc; j += 8, ++byte) gstore(byte, (uint8_t)((bits >> j) & 0xffull));
+            }
+        }
+    }
+}
+
 // the two casts of a frame record (pack_records_kernel's, bit for bit): uint8(v * 255) wrapping, uint16(d * 1000) wrapping
 __device__ __forceinline__ uint8_t quant_u8(float v) {
     v = fminf(fmaxf(v * 255.0f, -2147483520.0f), 2147483520.0f);
@@ -122,9 +162,16 @@ constexpr int PAIR_UNROLL = PGR_PAIR_UNROLL;   // entry pairs per trip of the co
 //
 //  * The tile's sorted list is consumed in batches of 64: lane j gathers entry j's 48-B record into registers one
 //    batch AHEAD (the loads land while the current batch is composited).
-//  * Skip + compact: lane j decides whether ITS entry can reach alpha >= 1/255 anywhere in this wave's 8x8 pixels
-//    (the binning's conservative predicate, on the quarter).  Entries that cannot are no-ops for every lane, so only
-//    the live ones are parked in LDS, compacted in list order (ballot + mbcnt).
+//  * Skip + compact: lane j decides whether ITS entry can reach alpha >= 1/255 anywhere in this wave's 8x8 pixels.
+//    Entries that cannot are no-ops for every lane, so only the live ones are parked in LDS, compacted in list order
+//    (ballot + mbcnt).  The test is the compositor's OWN (quarter_may_contribute, cull.hip.h), not the binning
+//    predicate: that one decides what the lists HOLD and reproduces the oracle's decisions bit for bit; this one only
+//    decides what is parked, and a parked entry that reaches no pixel blends with weight 0 (fma(c, 0, C) == C) and
+//    never becomes `last`.  What it CAN change is which pair loop a batch takes and when `pure` ends (a parked
+//    environment entry that reaches nothing turns RIDE into GENERAL, and a batch of such entries ends `pure`): both are
+//    shortcuts whose result is bitwise the general path's (see `pure` below), so any conservative test gives the same
+//    bits in every output.  This one is built for few instructions (it runs 64 lanes wide once per 64-entry batch: a
+//    quarter of the kernel's vector instructions sat in this prologue).
 //  * The parked batch is laid out for PAIRS of consecutive entries: the geometry of a pair (dx, dy, conic form, exp,
 //    opacity) is evaluated with packed fp32 -- one v_pk_* per two entries -- and arrives from LDS already as packed
 //    register pairs; the two colour accumulators are packed too ((r,g) and (b,depth)).  Per entry and pixel the
@@ -221,8 +268,6 @@ __device__ __forceinline__ void composite_quarter(const ViewEntry& ve, uint32_t 
     };
     fetch_record(0, fetch_index(0));
     uint32_t g_next = fetch_index(WAVE_BATCH);
-    const float rx0 = (float)qx0, ry0 = (float)qy0;
-    const float rx1 = fminf(rx0 + 7.0f, (float)(W - 1)), ry1 = fminf(ry0 + 7.0f, (float)(H - 1));
 
     for (int base = 0; base < n; base += WAVE_BATCH) {
         if (alive == 0ull && (sem_alive == 0ull || base >= n_sem)) break;
@@ -233,8 +278,10 @@ __device__ __forceinline__ void composite_quarter(const ViewEntry& ve, uint32_t 
         unsigned int cols = (unsigned int)(any | (any >> 32));
         cols |= cols >> 16; cols |= cols >> 8; cols &= 0xffu;
         const int ax0 = __builtin_ctz(cols), ax1 = 31 - __builtin_clz(cols);
-        const float bx0 = rx0 + (float)ax0, by0 = ry0 + (float)ay0;
-        const float bx1 = fminf(rx0 + (float)ax1, rx1), by1 = fminf(ry0 + (float)ay1, ry1);
+        // Formed as integers (wave-uniform), one conversion each: exact either way (pixel coordinates), and alive
+        // lanes are inside the image, so the box needs no clip against the last column and row.
+        const float bx0 = (float)(qx0 + ax0), by0 = (float)(qy0 + ay0);
+        const float bx1 = (float)(qx0 + ax1), by1 = (float)(qy0 + ay1);
         // with the scene pixels saturated only object entries are still of interest
         // the quads are taken as they arrive, HERE: without this the compiler forms the packed operands of the staging
         // arithmetic right behind the loads, in the previous iteration, and waits for the loads there
@@ -254,7 +301,7 @@ __device__ __forceinline__ void composite_quarter(const ViewEntry& ve, uint32_t 
             }
         }
         const bool live = have && (alive != 0ull || cs.w != 0.0f) &&
-                          rect_may_contribute(make_cull_splat(p, co, q1.z, q1.w), bx0, by0, bx1, by1);
+                          quarter_may_contribute(p.x, p.y, co.x, co.y, co.z, co.w, q1.z, q1.w, bx0, by0, bx1, by1);
         const unsigned long long mask = __ballot(live);
         const int cnt = __popcll(mask);
         const int pos = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
@@ -269,11 +316,10 @@ __device__ __forceinline__ void composite_quarter(const ViewEntry& ve, uint32_t 
             if (AUX) s_i[pos] = (uint32_t)(base + lane + 1);
         }
         if (lane == 0 && (cnt & 1)) {             // null entry (opacity 0: never valid) completes the last pair
+            // All six geometry words: a stale NaN among them would make alpha NaN, and v_min_f32 turns that into 0.99.
+            // Its colour, semantic colour and list position are only ever read for a valid entry (objbits stops at cnt).
             float* gq = s_gf + 12 * (cnt >> 1) + 1;
             gq[0] = 0.f; gq[2] = 0.f; gq[4] = 0.f; gq[6] = 0.f; gq[8] = 0.f; gq[10] = 0.f;
-            s_c[cnt] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (FUSED) s_s[cnt] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (AUX) s_i[cnt] = 0u;
         }
         __syncthreads();
         // which of the parked entries are objects': one bit per compacted position, kept in an SGPR pair
@@ -447,9 +493,14 @@ __device__ __forceinline__ void composite_quarter(const ViewEntry& ve, uint32_t 
             if (ve.sem_depth) gstore(ve.sem_depth + pix, want_sem ? depth_out(Sbd.y, Ts) : 0.0f);
         }
         // the K masks of that pixel, from the registers that hold it (round 3: a separate pass re-read 12 P bytes per view)
-        if ((ve.sem_masks || rec) && sem.mask_colors)
-            pixel_masks(sr, sg, sb, sem.mask_colors, 0, sem.k, sem.mask_thr, ve.sem_masks, P, pix, inside,
-                        rec ? rec + rec_masks : nullptr);
+        if ((ve.sem_masks || rec) && sem.mask_colors) {
+            if (want_sem)
+                pixel_masks(sr, sg, sb, sem.mask_colors, 0, sem.k, sem.mask_thr, ve.sem_masks, P, pix, inside,
+                            rec ? rec + rec_masks : nullptr);
+            else          // background only: the pixel is wave-uniform
+                uniform_pixel_masks(sr, sg, sb, sem.mask_colors, sem.k, sem.mask_thr, ve.sem_masks, P, pix, inside,
+                                    rec ? rec + rec_masks : nullptr);
+        }
     }
 }
 
