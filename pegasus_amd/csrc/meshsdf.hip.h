@@ -58,9 +58,9 @@
 //               wave and word at agent scope; the init kernel of the same call sets all bits.  Integer minima do not depend on
 //               arrival order; equal floats resolve to the lowest point index.  A job without shell points keeps all bits set.
 #pragma once
+#include "job_table.hip.h"       // pose_job_of_block
 #include "mesh.hip.h"
 #include "pgr_common.h"
-#include "poseerr.hip.h"
 
 namespace pgr {
 

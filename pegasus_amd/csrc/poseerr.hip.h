@@ -47,8 +47,9 @@
 //               order, into one partial; a second kernel adds a job's partials in order, divides by the vertex count and
 //               rounds to float32.
 #pragma once
-#include "blockcull.hip.h"
+#include "job_table.hip.h"       // pose_job_of_block
 #include "pgr_common.h"
+#include "wave_ops.hip.h"        // wave_max_f
 
 namespace pgr {
 
@@ -96,14 +97,6 @@ __device__ __forceinline__ double pose_wave_sum(double v) {
 #pragma unroll
     for (int d = 1; d < WAVE; d <<= 1) v += __shfl_xor(v, d, WAVE);
     return v;
-}
-
-template <typename Table>
-__device__ __forceinline__ int pose_job_of_block(const Table& T, uint32_t block) {
-    int k = 0;
-    for (int q = 1; q < T.count; ++q)
-        if (block >= T.job[q].block0) k = q;
-    return k;
 }
 
 // errors [n_jobs,6]: mssd and mspd start at +inf, the rest at 0

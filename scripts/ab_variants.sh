@@ -15,7 +15,7 @@ case "$mode" in
     mkdir -p build_variants
     for v in $1; do
       tag=${v%%:*}; fl=""; [ "$v" != "$tag" ] && fl=${v#*:}
-      ( cd pegasus_amd/csrc && hipcc $FL $fl -o ../../build_variants/lib_$tag.so pegasus_raster.hip ) &
+      ( cd pegasus_amd/csrc && hipcc $FL $fl -o ../../build_variants/lib_$tag.so *.hip ) &      # every translation unit: build.sources()
     done
     wait; ls -la build_variants ;;
   run)

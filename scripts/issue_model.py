@@ -139,13 +139,13 @@ def kernel_isa(asm_text):
 
 def main(pmc_files):
     cost = kind_costs(ROOT / "profiles" / "r06_valu_classes.txt")
-    from pegasus_amd.build import FLAGS
+    from pegasus_amd.build import FLAGS, sources
     with tempfile.TemporaryDirectory() as td:
         import os
         extra = os.environ.get("ISSUE_MODEL_HIPCC_FLAGS", "").split()      # (e.g. the -D switches of the build that was profiled)
-        subprocess.run(["hipcc", *FLAGS, *extra, "--save-temps", "-o", f"{td}/x.so", str(ROOT / "pegasus_amd/csrc/pegasus_raster.hip")],
+        subprocess.run(["hipcc", *FLAGS, *extra, "--save-temps", "-o", f"{td}/x.so", *map(str, sources()[0])],
                        cwd=td, check=True, capture_output=True)
-        asm = next(Path(td).glob("*gfx950*.s")).read_text()
+        asm = "".join(p.read_text() for p in sorted(Path(td).glob("*gfx950*.s")))      # one per translation unit
     isa = kernel_isa(asm)
     lines = [l.rstrip() for l in __doc__.strip().splitlines()[:1]]
     lines += ["", "# issue cost by kind (shader cycles per wave64 instruction, 8 waves per SIMD; profiles/r06_valu_classes.txt):",

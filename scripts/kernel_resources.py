@@ -8,10 +8,10 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
-from pegasus_amd.build import FLAGS  # noqa: E402
+from pegasus_amd.build import FLAGS, sources  # noqa: E402
 
 cmd = ["hipcc", *FLAGS, "-Rpass-analysis=kernel-resource-usage", "-o", "/tmp/pgr_resources.so",
-       str(ROOT / "pegasus_amd/csrc/pegasus_raster.hip"), *sys.argv[1:]]
+       *map(str, sources()[0]), *sys.argv[1:]]
 txt = subprocess.run(cmd, capture_output=True, text=True).stderr
 for b in re.split(r"remark: [^\n]*Function Name: ", txt)[1:]:
     name = b.split("\n")[0].strip(" []")
