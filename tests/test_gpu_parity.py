@@ -716,6 +716,7 @@ def test_hip_agrees_with_independent_dense_float64_renderer(gpu_device):
     would show here."""
     from helpers import gpu_forward
     from oracle.dense_ref import dense_forward
+    import raster_reference as RR
     for seed, deg, bg in ((21, 3, (0.1, 0.3, 0.5)), (22, 1, (0.0, 0.0, 0.0))):
         cloud, views = scenes.scene_c1(seed=seed, n=1500)
         v = scenes.make_view(views[0].R_c2w.T, views[0].t_w2c, 96, 80, fovx=views[0].fovx, fovy=views[0].fovy)
@@ -726,6 +727,19 @@ def test_hip_agrees_with_independent_dense_float64_renderer(gpu_device):
         dc, dd = np.abs(g["color"] - c64), np.abs(g["out_depth"][0] - d64)
         assert np.quantile(dc, 0.999) < 5e-5 and np.quantile(dd, 0.999) < 5e-5, (seed, dc.max(), dd.max())
         assert (dc > 1e-3).mean() < 1e-3 and (g["radii"] > 0).sum() > 500
+        # per pixel: within the bound any float32 evaluation of the model obeys, wherever float64 can decide the pixel's path
+        # (tests/raster_reference.py; the lists and decisions of these scenes are held in tests/test_raster_decisions_gpu.py)
+        pre, img = RR.forward(**act, sh_degree=deg, **v.raster_kwargs(bg))
+        ok = img["decided"]
+        assert (~ok).mean() <= 5e-4, (seed, (~ok).mean(), img["und_kinds"])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rc = np.where(dc == 0, 0.0, dc / img["color"].e)[:, ok].max()
+            rd = np.where(dd == 0, 0.0, dd / img["depth"].e)[ok].max()
+            rt = np.where(g["final_T"] == img["final_T"].v, 0.0, np.abs(g["final_T"] - img["final_T"].v) / img["final_T"].e)[ok].max()
+        print(f"seed {seed}: worst err / bound colour {rc:.3g} depth {rd:.3g} final_T {rt:.3g}")
+        assert rc <= 1.0 and rd <= 1.0 and rt <= 1.0, (seed, rc, rd, rt)
+        assert np.array_equal(g["radii"][pre["dec"]["radius"] & pre["dec"]["member"]] > 0,
+                              pre["projected"][pre["dec"]["radius"] & pre["dec"]["member"]])
 
 
 def test_layered_silhouettes_equal_per_object_passes(gpu_device):
