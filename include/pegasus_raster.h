@@ -1103,6 +1103,68 @@ int32_t pgr_sdf_sample(const PgrGrid *grid, const float *sdf, int64_t n_points, 
 int32_t pgr_sdf_sweep(int32_t n_bodies, const PgrSdfBody *bodies, int32_t n_jobs, const PgrSweepJob *jobs, float tol,
                       float max_travel, int32_t max_steps, uint64_t *out, void *stream);
 
+/* ---- PNG files of device images (pegasus_amd/png.py; csrc/png.hip.h, csrc/png_codes.h) ----------------------------------
+ * bop_dataset.encode_png on the device: deflate, checksums and chunk framing of a batch of images that lie in device memory.
+ * THE FILE.  A file is the PNG signature, IHDR, ONE IDAT, IEND.  Colour type / bit depth are 0/8 (kind 0, gray8), 2/8 (kind 1,
+ * rgb8) and 0/16 (kind 2, gray16: little-endian 16-bit storage, written as big-endian samples); no interlace; every row has
+ * filter type 0.  The IDAT payload is one zlib stream: the header 78 01, deflate data, the big-endian Adler-32 of the filtered
+ * raw stream (height rows of 1 + row_bytes bytes).  The raw stream is cut into segments of PGR_PNG_SEGMENT_BYTES; one workgroup
+ * encodes one segment independently of all others and no match reaches in front of its segment.  A segment becomes ONE deflate
+ * block of the cheapest of three forms -- stored, fixed Huffman, dynamic Huffman, by the bytes the segment takes, ties to the
+ * earlier in that order.  A Huffman-coded segment that is not the file's last is followed by an empty stored block (000, pad to
+ * a byte, 00 00 FF FF) so that segments join at byte boundaries, as pigz joins its blocks; a stored block ends on a byte
+ * boundary by itself and is followed by nothing.  The last block carries BFINAL and is padded to a byte.  So a segment never
+ * takes more than its raw length + 5 bytes and a file never more than 63 + raw_bytes + 5 * n_segments (pgr_png_max_bytes).
+ * Tokens: level 0 codes literals only.  Level 1 gives every position candidates from a hash table of the 3-byte strings at
+ * earlier positions of the segment (filled one sub-block of PGR_PNG_SUBBLOCK positions after the other, the highest position
+ * of a bucket wins: an integer maximum, so the table does not depend on the order of execution; a position sees the sub-blocks
+ * in front of its own) and from the fixed distances 1, 2, 3, 6 and 1 + row_bytes; a candidate is extended to at most 258 bytes
+ * inside the segment, the longest wins, ties go to the smaller distance, a match has at least 3 bytes; the parse is greedy from
+ * the segment's first byte.  Code lengths are length-limited (15, and 7 for the code-length alphabet) by the one builder behind
+ * pgr_png_code_lengths; codes are canonical (RFC 1951 3.2.2); runs of zero code lengths are sent as symbols 17 / 18, symbol 16 is not used.
+ * Everything is integer work and every shared update is an integer atomic whose result does not depend on order: two runs give
+ * equal bytes.  Nothing of a file is computed on the host.
+ *
+ * A job names one image where it lies: `pixels` (device) is the first sample of the first row, row y starts row_stride bytes
+ * behind row y - 1 and pixel x pixel_stride bytes behind pixel x - 1 (>= 1, 3, 2 bytes for kind 0, 1, 2; row_stride >=
+ * (width - 1) * pixel_stride + that), so a view into a frame record or a plane of a stack is read without a copy.  width and
+ * height are 1..16384.  `scale` is 1 or 255 (kind 0 only): the sample is multiplied by it, which writes a 0/1 mask as 0/255.
+ *
+ * Two calls, as pgr_mask_rle_count / pgr_mask_rle_emit.  pgr_png_encode compresses every segment into `workspace`
+ * (pgr_png_workspace_bytes: about the raw bytes of the jobs; 0 for n_jobs <= 0 or a job outside the domain above; device
+ * memory, 16-byte aligned), combines the checksums and writes sizes int64 [n_jobs] (device), the bytes of each file.  The caller
+ * forms offsets int64 [n_jobs + 1] (device), the exclusive sum of the sizes, allocates files uint8 [capacity] and calls
+ * pgr_png_emit with the SAME jobs and workspace, untouched in between: file k goes to files[offsets[k] .. offsets[k+1]).
+ * `total` is offsets[n_jobs] as the caller computed it; capacity < total is refused on the host and no store leaves
+ * files[offsets[k] .. min(offsets[k+1], total)) whatever the device-side offsets hold.  level is 0 or 1.  The job table is
+ * copied to the device before the call returns. */
+#define PGR_PNG_SEGMENT_BYTES 8192   /* raw bytes per segment (one workgroup, one deflate block) */
+#define PGR_PNG_SUBBLOCK 512         /* positions per hash sub-block */
+#define PGR_PNG_GRAY8 0
+#define PGR_PNG_RGB8 1
+#define PGR_PNG_GRAY16 2
+typedef struct PgrPngJob {
+    const void *pixels;
+    int32_t width, height;
+    int32_t kind;
+    int64_t row_stride;
+    int32_t pixel_stride;
+    int32_t scale;
+} PgrPngJob;
+size_t pgr_png_workspace_bytes(int32_t n_jobs, const PgrPngJob *jobs);
+int32_t pgr_png_encode(const PgrPngJob *jobs, int32_t n_jobs, int32_t level, int64_t *sizes, void *workspace,
+                       size_t workspace_bytes, void *stream);
+int32_t pgr_png_emit(const PgrPngJob *jobs, int32_t n_jobs, const int64_t *offsets, int64_t total, uint8_t *files,
+                     int64_t capacity, const void *workspace, size_t workspace_bytes, void *stream);
+/* 63 + raw_bytes + 5 * n_segments: what no file of that shape exceeds; 0 outside the domain.  Host only. */
+int64_t pgr_png_max_bytes(int32_t width, int32_t height, int32_t kind);
+/* The code builder of the encoder on host arrays (the same __host__ __device__ function, csrc/png_codes.h): lengths uint8 [n]
+ * of a prefix code for the symbols with freq != 0, none longer than `limit`, 0 for unused symbols; a single used symbol gets
+ * length 1, two or more get a COMPLETE code (Kraft sum exactly 1) that costs no more than giving every used symbol
+ * ceil(log2(used)) bits.  n is 1..288, limit 1..15 with n <= 2^limit, every freq <= 2^22.  Host only. */
+int32_t pgr_png_code_lengths(const uint32_t *freq, int32_t n, int32_t limit, uint8_t *lengths);
+
+
 #ifdef __cplusplus
 }
 #endif

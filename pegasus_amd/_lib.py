@@ -207,6 +207,16 @@ class PgrCocoGroup(C.Structure):
                 ("iou_offset", C.c_int64)]
 
 
+class PgrPngJob(C.Structure):
+    _fields_ = [("pixels", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("kind", C.c_int32),
+                ("row_stride", C.c_int64), ("pixel_stride", C.c_int32), ("scale", C.c_int32)]
+
+
+# include/pegasus_raster.h: the raw bytes of one deflate segment, the positions of one hash sub-block, the image kinds
+PGR_PNG_SEGMENT_BYTES, PGR_PNG_SUBBLOCK = 8192, 512
+PGR_PNG_GRAY8, PGR_PNG_RGB8, PGR_PNG_GRAY16 = 0, 1, 2
+
+
 # every symbol include/pegasus_raster.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "pgr_abi_version": (C.c_int32, []),
@@ -359,6 +369,12 @@ SYMBOLS = {
     "pgr_sdf_sample": (C.c_int32, [C.POINTER(PgrGrid), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pgr_sdf_sweep": (C.c_int32, [C.c_int32, C.POINTER(PgrSdfBody), C.c_int32, C.POINTER(PgrSweepJob), C.c_float, C.c_float,
                                   C.c_int32, C.c_void_p, C.c_void_p]),
+    "pgr_png_workspace_bytes": (C.c_size_t, [C.c_int32, C.POINTER(PgrPngJob)]),
+    "pgr_png_encode": (C.c_int32, [C.POINTER(PgrPngJob), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pgr_png_emit": (C.c_int32, [C.POINTER(PgrPngJob), C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                 C.c_size_t, C.c_void_p]),
+    "pgr_png_max_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "pgr_png_code_lengths": (C.c_int32, [C.POINTER(C.c_uint32), C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
 }
 
 _lib = None

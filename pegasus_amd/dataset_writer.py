@@ -23,9 +23,16 @@ class BopSceneWriter:
     (2.9 s for 64 frames that render in 26 ms).  Like the reference, which starts a thread per frame for its writers
     (/root/reference/pegasus.py:346-358), the encoder runs beside the renderer: `add_batch` quantises on the GPU, copies
     the 8/16-bit images to the host once per batch and hands one task per PNG to a thread pool (zlib releases the GIL);
-    `close()` waits for them.  At most `max_pending` batches are in flight (bounded host memory)."""
+    `close()` waits for them.  At most `max_pending` batches are in flight (bounded host memory).
 
-    def __init__(self, out_dir, scene_id: int = 0, png_level: int = 1, workers: int = None, max_pending: int = 4):
+    ``encoder="gpu"`` encodes on the device instead (pegasus_amd.png): `add_batch` lists every image of
+    the batch where it lies -- rgb, depth, visible masks, silhouettes, the semantic image, with ``meshes=`` the mesh masks --
+    makes ONE ``png.encode_batch`` call, and the thread pool only writes slices of the one buffer that came back to their
+    paths.  Same directory, same file names, files that decode to the same arrays; the JSON records, scene_gt_info and the
+    COCO annotations do not depend on the encoder.  The default stays the host encoder."""
+
+    def __init__(self, out_dir, scene_id: int = 0, png_level: int = 1, workers: int = None, max_pending: int = 4,
+                 encoder: str = "host"):
         import os
         from concurrent.futures import ThreadPoolExecutor
         self.scene = BD.scene_dir(out_dir, "train", scene_id)
@@ -35,6 +42,10 @@ class BopSceneWriter:
         self.scene_gt_coco, self.coco_bbox_type, self.coco_size = {}, None, None      # per frame: annotations without ids
         self.dataset_name = Path(out_dir).resolve().name
         self.n_frames, self.level = 0, png_level
+        if encoder not in ("host", "gpu"):
+            raise ValueError(f"encoder={encoder!r}: 'host' or 'gpu'")
+        self.encoder = encoder
+        self._gpu_jobs = []                                  # encoder="gpu": (device image, scale, path) of the batch being added
         self.workers = max(1, min(32, os.cpu_count() or 1) if workers is None else int(workers))
         self._pool = ThreadPoolExecutor(max_workers=self.workers) if self.workers > 1 else None
         self._pending, self._max_pending = [], max(1, int(max_pending))
@@ -42,12 +53,29 @@ class BopSceneWriter:
     def _write(self, path, image):
         path.write_bytes(encode_png(image, self.level))
 
-    def _submit(self, batch_futures, image, kind, i, k=None):
+    def _submit(self, batch_futures, image, kind, i, k=None, scale=1):
+        """``image``: a host array (encoder="host"), or a device tensor whose samples times ``scale`` are what is written."""
         path = self.files.image_path(kind, i, k)
-        if self._pool is None:
+        if self.encoder == "gpu":
+            self._gpu_jobs.append((image, scale, path))
+        elif self._pool is None:
             self._write(path, image)
         else:
             batch_futures.append(self._pool.submit(self._write, path, image))
+
+    def _encode_gpu_jobs(self, batch_futures):
+        """One device encode for everything `_submit` listed; the pool (or this thread) writes the slices."""
+        from . import png
+        jobs, self._gpu_jobs = self._gpu_jobs, []
+        if not jobs:
+            return
+        files, offsets = png.encode_batch([j[0] for j in jobs], level=1 if self.level else 0, scale=[j[1] for j in jobs])
+        for k, (_, _, path) in enumerate(jobs):
+            data = files[offsets[k]:offsets[k + 1]]
+            if self._pool is None:
+                path.write_bytes(data)
+            else:
+                batch_futures.append(self._pool.submit(path.write_bytes, data))
 
     def add_batch(self, frames: dict, scene_gt: dict, scene_camera: dict, n: int = None, silhouettes=None, frame_ids=None,
                   record_shape=None, meshes=None, delta: float = 15.0, translation_scale: float = 1.0, coco=False):
@@ -71,14 +99,15 @@ class BopSceneWriter:
             if self.coco_bbox_type not in (None, bbox_type):
                 raise ValueError(f"this scene's annotations are {self.coco_bbox_type}; one file holds one box type")
         masks_dev = frames.get("masks")
+        gpu = self.encoder == "gpu"
         if "color" in frames:
             n = frames["color"].shape[0] if n is None else n
             # GPU: uint8 HWC / uint16 millimetres for the whole batch in one launch (pgr_pack_frames), then ONE
             # device->host copy per kind and batch
             packed = M.pack_frames(color=frames["color"][:n], depth=frames["depth"][:n])
             depth_mm_dev = packed["depth_mm"]
-            rgb8 = packed["rgb"].cpu().numpy()
-            mm = depth_mm_dev.cpu().numpy().view(np.uint16)
+            rgb8 = packed["rgb"] if gpu else packed["rgb"].cpu().numpy()
+            mm = depth_mm_dev if gpu else depth_mm_dev.cpu().numpy().view(np.uint16)
         else:
             # a records-only frame set (FrameRenderer.alloc_frames(images=False | "seg")): the compositor's epilogue wrote the
             # casts already -- the record IS what the writers take
@@ -88,8 +117,9 @@ class BopSceneWriter:
             H, W, K = (int(v) for v in record_shape)
             rv = M.record_views(frames["records"][:n], H, W, K)
             depth_mm_dev = rv["depth_mm"]
-            rgb8 = rv["rgb"].cpu().numpy()
-            mm = depth_mm_dev.cpu().numpy().view(np.uint16)
+            # encoder="gpu": the record's own RGB and depth planes are the encoder's input, read where they lie
+            rgb8 = rv["rgb"] if gpu else rv["rgb"].cpu().numpy()
+            mm = depth_mm_dev if gpu else depth_mm_dev.cpu().numpy().view(np.uint16)
             masks_dev = M.unpack_mask_bits(rv["mask_bits"], K) if K else None
         if silhouettes is None:
             silhouettes = frames.get("sil")
@@ -105,9 +135,16 @@ class BopSceneWriter:
             if n_entries:
                 coco_enc = CO.encode_stack(masks_dev[:n].flatten(0, 1),
                                            silhouettes[:n].flatten(0, 1) if bbox_type == "amodal" else None)
-        mk = (masks_dev[:n] * 255).cpu().numpy() if masks_dev is not None else None
-        sem8 = M.pack_frames(color=frames["seg"][:n])["rgb"].cpu().numpy() if "seg" in frames else None
-        sil = (silhouettes[:n] * 255).cpu().numpy() if silhouettes is not None else None
+        if gpu:
+            # 0 / 1 planes as they lie: the encoder writes them as 0 / 255 (scale)
+            mk = masks_dev[:n] if masks_dev is not None else None
+            sem8 = M.pack_frames(color=frames["seg"][:n])["rgb"] if "seg" in frames else None
+            sil = silhouettes[:n] if silhouettes is not None else None
+        else:
+            mk = (masks_dev[:n] * 255).cpu().numpy() if masks_dev is not None else None
+            sem8 = M.pack_frames(color=frames["seg"][:n])["rgb"].cpu().numpy() if "seg" in frames else None
+            sil = (silhouettes[:n] * 255).cpu().numpy() if silhouettes is not None else None
+        mask_scale = 255 if gpu else 1
         info = None
         if silhouettes is not None and masks_dev is not None:
             # BOP's scene_gt_info from the masks the batch already holds, counted on the GPU (a few hundred numbers per batch)
@@ -145,25 +182,27 @@ class BopSceneWriter:
                 self.coco_bbox_type, self.coco_size = bbox_type, (int(W), int(H))
             if mesh_gt is not None:
                 for name, stack in (("mask", mesh_gt[0][i]), ("mask_visib", mesh_gt[1][i])):
-                    for k, image in enumerate((stack * 255).cpu().numpy()):
-                        self._submit(futures, image, name, fid, k)
+                    for k, image in enumerate(stack if gpu else (stack * 255).cpu().numpy()):
+                        self._submit(futures, image, name, fid, k, mask_scale)
                 self.scene_gt_info[str(fid)] = mesh_gt[2][i]
             self._submit(futures, rgb8[i], "rgb", fid)
             self._submit(futures, mm[i], "depth", fid)
             if mk is not None:
                 for k in range(mk.shape[1]):
-                    self._submit(futures, mk[i, k], "mask_visib", fid, k)
+                    self._submit(futures, mk[i, k], "mask_visib", fid, k, mask_scale)
             if sem8 is not None:
                 self._submit(futures, sem8[i], "sem_mask", fid)
             if sil is not None:
                 for k in range(sil.shape[1]):
-                    self._submit(futures, sil[i, k], "mask", fid, k)
+                    self._submit(futures, sil[i, k], "mask", fid, k, mask_scale)
             self.scene_gt[str(fid)] = scene_gt[str(i)]
             self.scene_camera[str(fid)] = scene_camera[str(i)]
             if info is not None:
                 from . import bop_pose
                 self.scene_gt_info[str(fid)] = bop_pose.scene_gt_info_entry(info, i)
             self.n_frames += 1
+        if gpu:
+            self._encode_gpu_jobs(futures)
         if futures:
             self._pending.append(futures)
             while len(self._pending) > self._max_pending:

@@ -10,7 +10,8 @@ link: the PNG encoders of all ranks run in parallel, which is what bounds a real
 
 What PEGASUS's generate_dataset loop does per frame (/root/reference/pegasus.py:247-395: merge, 3+K renders, numpy
 masks, PNG + JSON writers), in batches of cameras on the GPU; PNG encoding is the only per-frame host work and runs on
-a thread pool beside the renderer (the reference starts a writer thread per frame, pegasus.py:346-358)."""
+a thread pool beside the renderer (the reference starts a writer thread per frame, pegasus.py:346-358).  ``--png gpu`` moves
+the encoding to the device as well (pegasus_amd.png): the host then only writes the files."""
 from __future__ import annotations
 
 import argparse
@@ -29,6 +30,9 @@ def main(argv=None):
     ap.add_argument("--size", type=int, default=800)
     ap.add_argument("--dynamic", action="store_true", help="every frame a time step with its own object poses")
     ap.add_argument("--writers", type=int, default=None, help="PNG encoder threads (default: host cores, at most 32)")
+    ap.add_argument("--png", default="host", choices=["host", "gpu"],
+                    help="where the PNG files are encoded: on the host thread pool (zlib), or on the GPU (pegasus_amd.png: one "
+                         "encode call per batch, the threads only write the files)")
     ap.add_argument("--gt-from-meshes", default=None, metavar="MODELS_DIR",
                     help="take mask/, mask_visib/ and scene_gt_info.json from the depth renders of the obj_NNNNNN.ply meshes "
                          "(millimetres, as pegasus_amd.mesh writes them) of this directory, as the BOP toolkit does")
@@ -75,7 +79,7 @@ def main(argv=None):
     writers = args.writers
     if writers is None and world > 1:        # N ranks share the host's cores: their encoder pools must not add up to N x 32
         writers = max(1, min(32, (os.cpu_count() or 1) // world))
-    w = BopSceneWriter(args.out, workers=writers)
+    w = BopSceneWriter(args.out, workers=writers, encoder=args.png)
     meshes = None
     if args.gt_from_meshes:
         from .mesh_render import MeshSet
@@ -131,7 +135,8 @@ def main(argv=None):
     if rank == 0:
         print(f"{args.frames} frames ({cloud.n} Gaussians, {fr.K} objects) on {world} rank(s) -> {scene}: rank 0 rendered "
               f"{w.n_frames} of them in {t_gpu * 1e3:.1f} ms, total {dt:.2f} s ({args.frames / dt:.1f} frames/s with PNG "
-              f"encoding on {w.workers} host thread(s) per rank)")
+              + (f"encoding on the GPU and {w.workers} writer thread(s) per rank)" if args.png == "gpu" else
+                 f"encoding on {w.workers} host thread(s) per rank)"))
 
 
 if __name__ == "__main__":
