@@ -1103,6 +1103,71 @@ int32_t pgr_sdf_sample(const PgrGrid *grid, const float *sdf, int64_t n_points, 
 int32_t pgr_sdf_sweep(int32_t n_bodies, const PgrSdfBody *bodies, int32_t n_jobs, const PgrSweepJob *jobs, float tol,
                       float max_travel, int32_t max_steps, uint64_t *out, void *stream);
 
+/* ---- Rigid-body drops (pegasus_amd/dynamics.py; the rule stands at the top of pegasus_amd/csrc/rigid.hip.h and in DESIGN.md
+ * section 24): S independent worlds of B <= PGR_RIGID_MAX_BODIES slots fall onto the plane n.x = d and onto each other.
+ * Contacts come from the bodies' distance fields and shell points (pgr_mesh_sdf, pgr_sdf_sample's rule), a sequential-impulse
+ * solver with friction steps them.  Both entries run on `stream`, allocate nothing, wait for nothing, use no floating-point
+ * atomic and return the same bytes from call to call.  Every argument check comes before any launch and gives
+ * PGR_ERR_INVALID_ARGUMENT.
+ *
+ * `types` is a HOST table of n_types <= PGR_RIGID_MAX_TYPES body types, read during the call and handed to the kernels by
+ * value: geometry as in PgrSdfBody (shell points in the mesh frame), mass, centre of mass `com` (mesh frame), inverse inertia
+ * about it (mesh frame, row-major), friction, and the bounding radius max |shell - com|.  `type` is device int32 [S,B]: the
+ * type of every slot; a value outside [0, n_types) is an empty slot.  `state` is device float32 [S,B,PGR_RIGID_STATE]: centre
+ * of mass x, unit quaternion q (x, y, z, w), v, omega, all in the world.
+ *
+ * pgr_rigid_contacts: `words` device uint64 [S, B*B, PGR_RIGID_WORDS].  Pair slot a*B + b is mover a against target b, slot
+ * a*B + a mover a against the plane.  Word 0 is the minimum of the field value over the mover's shell points with value <=
+ * params->margin, words 1..6 the minima of +x, -x, +y, -y, +z, -z of (point - x_a) over the same points, each packed as in
+ * pgr_sdf_sweep; a pair without such a point (or out of bounding-sphere range, or with an empty slot) keeps all bits set.
+ *
+ * pgr_rigid_simulate: advances `state` by n_steps steps in place and enqueues all of them.  After every record_every-th step
+ * the mesh-frame pose (t = x - R com, q) of every slot goes to `trajectory`, device float32 [S, n_steps / record_every, B, 7]
+ * (may be NULL when that count is 0).  rest_step (device int32 [S]): the step at which the world fell asleep, -1 if never.
+ * status (device int32 [S]): 1 where a state stopped being finite; such a world stays at its last finite state.  Both entries
+ * take a `workspace` of pgr_rigid_workspace_bytes(S, B) bytes (0: arguments refused), 16-byte aligned.
+ *
+ * Invalid: a needed NULL, S < 0 or > 2^20, B < 0 or > PGR_RIGID_MAX_BODIES, n_types < 0 or > PGR_RIGID_MAX_TYPES (or 0 while
+ * there are slots), a type with n_shell < 0, a missing shell, a field that is missing or has a bad grid while B > 1, a mass,
+ * friction or radius that is not finite, mass <= 0, friction or radius < 0, a com or inertia entry that is not finite; h or
+ * iterations <= 0 or not finite, a plane normal that is not of unit length within 1e-4, any other parameter that is not finite,
+ * damping outside [0, 1), beta, slop, margin or a sleep threshold < 0, n_steps < 0, record_every < 1, a workspace that is too
+ * small (PGR_ERR_WORKSPACE_TOO_SMALL).  S == 0 or B == 0 (and n_steps == 0) do nothing. */
+#define PGR_RIGID_MAX_BODIES 8
+#define PGR_RIGID_MAX_TYPES 16
+#define PGR_RIGID_WORDS 7
+#define PGR_RIGID_STATE 13
+typedef struct PgrRigidType {
+    PgrGrid grid;
+    const float *sdf;
+    const float *shell;
+    int32_t n_shell;
+    float mass;
+    float com[3];
+    float inv_inertia[9];
+    float friction;
+    float radius;
+} PgrRigidType;
+typedef struct PgrRigidParams {
+    float h;
+    float gravity[3];
+    float plane[4];
+    float plane_friction;
+    float lin_damp, ang_damp;
+    int32_t iterations;
+    float beta, slop, margin;
+    float v_sleep, w_sleep;
+    int32_t sleep_steps;
+} PgrRigidParams;
+size_t pgr_rigid_workspace_bytes(int32_t n_worlds, int32_t n_slots);
+int32_t pgr_rigid_contacts(const PgrRigidParams *params, int32_t n_types, const PgrRigidType *types, int32_t n_worlds,
+                           int32_t n_slots, const int32_t *type, const float *state, uint64_t *words, void *workspace,
+                           size_t workspace_bytes, void *stream);
+int32_t pgr_rigid_simulate(const PgrRigidParams *params, int32_t n_types, const PgrRigidType *types, int32_t n_worlds,
+                           int32_t n_slots, const int32_t *type, float *state, int32_t n_steps, int32_t record_every,
+                           float *trajectory, int32_t *rest_step, int32_t *status, void *workspace, size_t workspace_bytes,
+                           void *stream);
+
 /* ---- PNG files of device images (pegasus_amd/png.py; csrc/png.hip.h, csrc/png_codes.h) ----------------------------------
  * bop_dataset.encode_png on the device: deflate, checksums and chunk framing of a batch of images that lie in device memory.
  * THE FILE.  A file is the PNG signature, IHDR, ONE IDAT, IEND.  Colour type / bit depth are 0/8 (kind 0, gray8), 2/8 (kind 1,

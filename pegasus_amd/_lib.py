@@ -202,6 +202,22 @@ class PgrSweepJob(C.Structure):
 PGR_SDF_FACE_TILE, PGR_SWEEP_PLANE = 256, -1
 
 
+class PgrRigidType(C.Structure):
+    _fields_ = [("grid", PgrGrid), ("sdf", C.c_void_p), ("shell", C.c_void_p), ("n_shell", C.c_int32), ("mass", C.c_float),
+                ("com", C.c_float * 3), ("inv_inertia", C.c_float * 9), ("friction", C.c_float), ("radius", C.c_float)]
+
+
+class PgrRigidParams(C.Structure):
+    _fields_ = [("h", C.c_float), ("gravity", C.c_float * 3), ("plane", C.c_float * 4), ("plane_friction", C.c_float),
+                ("lin_damp", C.c_float), ("ang_damp", C.c_float), ("iterations", C.c_int32), ("beta", C.c_float),
+                ("slop", C.c_float), ("margin", C.c_float), ("v_sleep", C.c_float), ("w_sleep", C.c_float),
+                ("sleep_steps", C.c_int32)]
+
+
+# include/pegasus_raster.h: the slots of a world, the types of a table, the words of a pair, the floats of a body's state
+PGR_RIGID_MAX_BODIES, PGR_RIGID_MAX_TYPES, PGR_RIGID_WORDS, PGR_RIGID_STATE = 8, 16, 7, 13
+
+
 class PgrCocoGroup(C.Structure):
     _fields_ = [("dt_begin", C.c_int32), ("dt_count", C.c_int32), ("gt_begin", C.c_int32), ("gt_count", C.c_int32),
                 ("iou_offset", C.c_int64)]
@@ -369,6 +385,12 @@ SYMBOLS = {
     "pgr_sdf_sample": (C.c_int32, [C.POINTER(PgrGrid), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pgr_sdf_sweep": (C.c_int32, [C.c_int32, C.POINTER(PgrSdfBody), C.c_int32, C.POINTER(PgrSweepJob), C.c_float, C.c_float,
                                   C.c_int32, C.c_void_p, C.c_void_p]),
+    "pgr_rigid_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "pgr_rigid_contacts": (C.c_int32, [C.POINTER(PgrRigidParams), C.c_int32, C.POINTER(PgrRigidType), C.c_int32, C.c_int32,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pgr_rigid_simulate": (C.c_int32, [C.POINTER(PgrRigidParams), C.c_int32, C.POINTER(PgrRigidType), C.c_int32, C.c_int32,
+                                       C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_size_t, C.c_void_p]),
     "pgr_png_workspace_bytes": (C.c_size_t, [C.c_int32, C.POINTER(PgrPngJob)]),
     "pgr_png_encode": (C.c_int32, [C.POINTER(PgrPngJob), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pgr_png_emit": (C.c_int32, [C.POINTER(PgrPngJob), C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,

@@ -1,5 +1,5 @@
 // mesh.hip -- host side of the object-mesh entries of libpegasus_raster.so: TSDF fusion and marching tetrahedra, the mesh
-// depth / visibility / shade renderers and BOP ground truth, vertex clustering, vertex attributes, distance fields and sweeps.
+// depth / visibility / shade renderers and BOP ground truth, vertex clustering, vertex attributes, distance fields and sweeps, rigid-body drops.
 // Owns its kernel headers: no other translation unit includes them (DESIGN.md "Source layout").
 #include <hip/hip_runtime.h>
 
@@ -13,6 +13,7 @@
 #include "meshattr.hip.h"
 #include "meshraster.hip.h"
 #include "meshsdf.hip.h"
+#include "rigid.hip.h"
 
 using namespace pgr;
 
@@ -661,4 +662,151 @@ int32_t pgr_sdf_sweep(int32_t n_bodies, const PgrSdfBody* bodies, int32_t n_jobs
         if (blocks > 0) sdf_sweep_kernel<<<blocks, SWEEP_THREADS, 0, stream>>>(T, out);
     }
     return launch_status("sdf_sweep launch");
+}
+
+// ---- rigid-body drops: field contacts and the batched impulse solver (rigid.hip.h) ------------------------------------------
+namespace {
+constexpr int32_t RIGID_MAX_WORLDS = 1 << 20;
+struct RigidLayout { size_t table, words, halt, rest_count, rows, total; };
+RigidLayout rigid_layout(int32_t S, int32_t B) {
+    RigidLayout L{};
+    if (S < 0 || S > RIGID_MAX_WORLDS || B < 0 || B > RIGID_MAX_BODIES) return L;
+    const size_t pairs = (size_t)S * B * B;
+    Carver c;
+    L.table = c.take(sizeof(RigidTable));
+    L.words = c.take(pairs * RIGID_WORDS * sizeof(uint64_t));
+    L.halt = c.take((size_t)S * sizeof(int32_t));
+    L.rest_count = c.take((size_t)S * sizeof(int32_t));
+    L.rows = c.take(pairs * RIGID_WORDS * RIGID_ROW_FIELDS * sizeof(float));
+    L.total = c.off;
+    return L;
+}
+bool all_finite(const float* v, int n) {
+    for (int k = 0; k < n; ++k)
+        if (!std::isfinite(v[k])) return false;
+    return true;
+}
+// the checks both rigid entries share; fills the kernels' copies of the table and the parameters
+bool rigid_args(const PgrRigidParams* p, int32_t n_types, const PgrRigidType* types, int32_t S, int32_t B, const int32_t* type,
+                const float* state, RigidTable& T, RigidParamsDev& P) {
+    if (!p || S < 0 || S > RIGID_MAX_WORLDS || B < 0 || B > RIGID_MAX_BODIES || n_types < 0 || n_types > RIGID_MAX_TYPES) return false;
+    if (n_types > 0 && !types) return false;
+    const bool slots = S > 0 && B > 0;
+    if (slots && (!type || !state || n_types == 0)) return false;
+    if (!std::isfinite(p->h) || !(p->h > 0.f) || p->iterations <= 0 || !all_finite(p->gravity, 3)) return false;
+    if (!unit_vector(p->plane) || !std::isfinite(p->plane[3])) return false;
+    for (float v : {p->plane_friction, p->beta, p->slop, p->margin, p->v_sleep, p->w_sleep})
+        if (!std::isfinite(v) || v < 0.f) return false;
+    for (float v : {p->lin_damp, p->ang_damp})
+        if (!std::isfinite(v) || v < 0.f || !(v < 1.f)) return false;
+    T = RigidTable{};
+    for (int32_t k = 0; k < n_types; ++k) {
+        const PgrRigidType& t = types[k];
+        if (t.n_shell < 0 || (t.n_shell > 0 && !t.shell)) return false;
+        if (B > 1 && (!t.sdf || !grid_ok(&t.grid))) return false;
+        if (!std::isfinite(t.mass) || !(t.mass > 0.f) || !std::isfinite(t.friction) || t.friction < 0.f) return false;
+        if (!std::isfinite(t.radius) || t.radius < 0.f || !all_finite(t.com, 3) || !all_finite(t.inv_inertia, 9)) return false;
+        RigidTypeDev& d = T.t[k];
+        if (t.sdf && grid_ok(&t.grid)) {
+            d.g = mesh_grid(&t.grid);
+            d.sdf = t.sdf;
+        }
+        d.mass = t.mass;
+        d.shell = t.shell;
+        d.n_shell = t.n_shell;
+        d.friction = t.friction;
+        d.radius = t.radius;
+        std::memcpy(d.com, t.com, sizeof(d.com));
+        std::memcpy(d.iinv, t.inv_inertia, sizeof(d.iinv));
+    }
+    P = RigidParamsDev{};
+    P.h = p->h;
+    P.gx = p->gravity[0];
+    P.gy = p->gravity[1];
+    P.gz = p->gravity[2];
+    P.nx = p->plane[0];
+    P.ny = p->plane[1];
+    P.nz = p->plane[2];
+    P.d = p->plane[3];
+    P.plane_friction = p->plane_friction;
+    P.lin_factor = (float)std::pow(1.0 - (double)p->lin_damp, (double)p->h);
+    P.ang_factor = (float)std::pow(1.0 - (double)p->ang_damp, (double)p->h);
+    P.beta = p->beta;
+    P.slop = p->slop;
+    P.margin = p->margin;
+    P.v_sleep = p->v_sleep;
+    P.w_sleep = p->w_sleep;
+    P.iterations = p->iterations;
+    P.sleep_steps = p->sleep_steps;
+    P.n_types = n_types;
+    return true;
+}
+// one pass of rigid_contacts_kernel over every (world, pair, point block); halt may be NULL
+void rigid_launch_contacts(const RigidTable& T, const RigidTypeDev* table, const RigidParamsDev& P, int32_t n_types, int32_t S, int32_t B, const int32_t* type,
+                           const float* state, const int32_t* halt, uint64_t* words, hipStream_t stream) {
+    int32_t most = 0;
+    for (int32_t k = 0; k < n_types; ++k) most = std::max(most, T.t[k].n_shell);
+    const uint32_t point_blocks = (uint32_t)(((int64_t)most + RIGID_CONTACT_THREADS - 1) / RIGID_CONTACT_THREADS);
+    if (point_blocks == 0) return;
+    rigid_contacts_kernel<<<dim3((uint32_t)S, (uint32_t)(B * B), point_blocks), RIGID_CONTACT_THREADS, 0, stream>>>(
+        table, P, B, type, state, halt, words);
+}
+}  // namespace
+
+size_t pgr_rigid_workspace_bytes(int32_t n_worlds, int32_t n_slots) { return rigid_layout(n_worlds, n_slots).total; }
+
+int32_t pgr_rigid_contacts(const PgrRigidParams* params, int32_t n_types, const PgrRigidType* types, int32_t S, int32_t B,
+                           const int32_t* type, const float* state, uint64_t* words, void* workspace, size_t workspace_bytes,
+                           void* stream_v) {
+    RigidTable T;
+    RigidParamsDev P;
+    if (!rigid_args(params, n_types, types, S, B, type, state, T, P)) return PGR_ERR_INVALID_ARGUMENT;
+    if (S == 0 || B == 0) return PGR_OK;
+    if (!words || !workspace || !workspace_aligned_16(workspace)) return PGR_ERR_INVALID_ARGUMENT;
+    const RigidLayout L = rigid_layout(S, B);
+    if (workspace_bytes < L.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    for (int32_t k = 0; k < n_types; ++k)
+        if ((int64_t)T.t[k].n_shell > (int64_t)65535 * RIGID_CONTACT_THREADS) return PGR_ERR_INVALID_ARGUMENT;
+    hipStream_t stream = as_stream(stream_v);
+    const long long n_words = (long long)S * B * B * RIGID_WORDS;
+    RigidTypeDev* table = ws_at<RigidTypeDev>(workspace, L.table);
+    rigid_table_kernel<<<1, WAVE, 0, stream>>>(T, table);
+    rigid_init_kernel<<<(uint32_t)((n_words + 255) / 256), 256, 0, stream>>>(words, n_words, nullptr, nullptr, nullptr, nullptr, 0);
+    rigid_launch_contacts(T, table, P, n_types, S, B, type, state, nullptr, words, stream);
+    return launch_status("rigid_contacts launch");
+}
+
+int32_t pgr_rigid_simulate(const PgrRigidParams* params, int32_t n_types, const PgrRigidType* types, int32_t S, int32_t B,
+                           const int32_t* type, float* state, int32_t n_steps, int32_t record_every, float* trajectory,
+                           int32_t* rest_step, int32_t* status, void* workspace, size_t workspace_bytes, void* stream_v) {
+    RigidTable T;
+    RigidParamsDev P;
+    if (!rigid_args(params, n_types, types, S, B, type, state, T, P)) return PGR_ERR_INVALID_ARGUMENT;
+    if (n_steps < 0 || record_every < 1) return PGR_ERR_INVALID_ARGUMENT;
+    if (S == 0 || B == 0) return PGR_OK;
+    const int32_t n_records = n_steps / record_every;
+    if (!rest_step || !status || !workspace || (n_records > 0 && !trajectory)) return PGR_ERR_INVALID_ARGUMENT;
+    if (!workspace_aligned_16(workspace)) return PGR_ERR_INVALID_ARGUMENT;
+    for (int32_t k = 0; k < n_types; ++k)
+        if ((int64_t)T.t[k].n_shell > (int64_t)65535 * RIGID_CONTACT_THREADS) return PGR_ERR_INVALID_ARGUMENT;
+    const RigidLayout L = rigid_layout(S, B);
+    if (workspace_bytes < L.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    hipStream_t stream = as_stream(stream_v);
+    uint64_t* words = ws_at<uint64_t>(workspace, L.words);
+    int32_t* halt = ws_at<int32_t>(workspace, L.halt);
+    int32_t* rest_count = ws_at<int32_t>(workspace, L.rest_count);
+    float* rows = ws_at<float>(workspace, L.rows);
+    RigidTypeDev* table = ws_at<RigidTypeDev>(workspace, L.table);
+    rigid_table_kernel<<<1, WAVE, 0, stream>>>(T, table);
+    const long long n_words = (long long)S * B * B * RIGID_WORDS;
+    const long long n_init = std::max<long long>(n_words, S);
+    rigid_init_kernel<<<(uint32_t)((n_init + 255) / 256), 256, 0, stream>>>(words, n_words, halt, rest_count, rest_step, status, S);
+    const uint32_t solve_blocks = (uint32_t)((S + RIGID_SOLVE_THREADS - 1) / RIGID_SOLVE_THREADS);
+    for (int32_t k = 0; k < n_steps; ++k) {
+        rigid_launch_contacts(T, table, P, n_types, S, B, type, state, halt, words, stream);
+        const int32_t record = (k + 1) % record_every == 0 ? (k + 1) / record_every - 1 : -1;
+        rigid_solve_kernel<<<solve_blocks, RIGID_SOLVE_THREADS, 0, stream>>>(table, P, S, B, type, state, words, rows, halt, rest_count, k,
+                                                                            record, n_records, trajectory, rest_step, status);
+    }
+    return launch_status("rigid_simulate launch");
 }

@@ -1,6 +1,6 @@
 """End-to-end example of the batch path: a synthetic merged scene -> frames -> BOP-layout dataset on disk.
 
-    python -m pegasus_amd.generate --out /tmp/pegasus_ds --frames 64 [--workload c3 --scale 0.1] [--dynamic]
+    python -m pegasus_amd.generate --out /tmp/pegasus_ds --frames 64 [--workload c3 --scale 0.1] [--dynamic [--trajectory simulation_steps.json]]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m pegasus_amd.generate --out ... --frames 4096
 
 Under torchrun the frames shard over the ranks (frame f -> rank f mod world; scene replicated, one GPU
@@ -29,6 +29,9 @@ def main(argv=None):
     ap.add_argument("--scale", type=float, default=0.1, help="fraction of the workload's Gaussian counts")
     ap.add_argument("--size", type=int, default=800)
     ap.add_argument("--dynamic", action="store_true", help="every frame a time step with its own object poses")
+    ap.add_argument("--trajectory", default=None, metavar="JSON",
+                    help="--dynamic: a simulation_steps.json (python -m pegasus_amd.dynamics, or the reference's) whose bodies "
+                         "the objects follow, every object its own body's motion, instead of the recorded fixture")
     ap.add_argument("--writers", type=int, default=None, help="PNG encoder threads (default: host cores, at most 32)")
     ap.add_argument("--png", default="host", choices=["host", "gpu"],
                     help="where the PNG files are encoded: on the host thread pool (zlib), or on the GPU (pegasus_amd.png: one "
@@ -44,6 +47,8 @@ def main(argv=None):
                     help="the box fields of scene_gt: the axis-aligned box of the object's Gaussians, or the minimal oriented "
                          "box of its mesh in NDDS corner order as the reference writes it (needs --gt-from-meshes)")
     args = ap.parse_args(argv)
+    if args.trajectory and not args.dynamic:
+        ap.error("--trajectory gives the object poses of --dynamic")
     if args.boxes == "oriented" and not args.gt_from_meshes:
         ap.error("--boxes oriented takes the boxes from the meshes: it requires --gt-from-meshes MODELS_DIR")
 
@@ -101,7 +106,11 @@ def main(argv=None):
         if args.dynamic and fr.K:
             # time step s of the recorded drop (the reference's trajectory fixture, pegasus_amd/trajectory.py)
             from . import trajectory as TJ
-            if seq_tables is None:
+            if seq_tables is None and args.trajectory:
+                sim = TJ.load_simulation(args.trajectory)
+                # 200 time steps spread over the drop up to where it comes to rest, so that the sequence ends there
+                seq_tables, seq_motion = TJ.simulation_poses(sim, centers, 200, stride=max(1, -(-(TJ.rest_index(sim) + 1) // 200)))
+            elif seq_tables is None:
                 seq_tables, seq_motion = TJ.sequence_poses(TJ.load_fixture(), centers, 200)
             idx = [f % 200 for f in ids]
             poses, m2w = seq_tables[idx], [seq_motion[i] for i in idx]

@@ -102,3 +102,54 @@ def sequence_poses(traj: np.ndarray, centers: Sequence, n_steps: int, phase: int
         tables[s] = pose_table(pairs)
         motions.append(mot)
     return tables, motions
+
+
+def load_simulation(path) -> np.ndarray:
+    """[B, S, 7] float64 of a ``simulation_steps.json`` (the reference's, ``collision.write_simulation_steps``' or
+    ``dynamics.write_trajectory``'s): t (3) and q (x, y, z, w) of bodies 1 .. B (body 0 is the ground) for steps 0 .. S-1, bodies
+    in the order of their bullet ids."""
+    import json
+    doc = json.loads(Path(path).read_text())["trajectory"]
+    ids = sorted(int(k) for k in doc if int(k) > 0)
+    if not ids:
+        raise ValueError(f"{path}: no body besides the ground")
+    rows = []
+    for i in ids:
+        steps = doc[str(i)]
+        order = sorted(steps, key=int)
+        rows.append([list(steps[s]["t"]) + list(steps[s]["q"]) for s in order])
+    if len({len(r) for r in rows}) != 1:
+        raise ValueError(f"{path}: the bodies have different numbers of steps")
+    return np.asarray(rows, np.float64).reshape(len(ids), -1, 7)
+
+
+def rest_index(sim: np.ndarray) -> int:
+    """The first step of ``sim`` [B, S, 7] from which every body keeps its last pose: where the drop has come to rest (S - 1 if
+    it moves to the end)."""
+    moving = np.flatnonzero((sim != sim[:, -1:]).any(axis=(0, 2)))
+    return int(moving[-1]) + 1 if len(moving) else 0
+
+
+def simulation_poses(sim: np.ndarray, centers: Sequence, n_steps: int, first_step: int = 0, stride: int = 1
+                     ) -> Tuple[np.ndarray, List[Dict[int, np.ndarray]]]:
+    """``sequence_poses`` for a simulated scene: object k (1-based) follows body ((k-1) mod B) of ``sim`` [B, S, 7]
+    (``load_simulation``), its own motion, relative to that body's last sample: time step s shows sample
+    min(S-1, first_step + s * stride).  Returns the same pair as ``sequence_poses``."""
+    from .compose import pose_table
+    B, S = sim.shape[0], sim.shape[1]
+    K = len(centers)
+    tables = np.zeros((n_steps, K, 20), np.float32)
+    motions: List[Dict[int, np.ndarray]] = []
+    for s in range(n_steps):
+        idx = min(S - 1, first_step + s * stride)
+        pairs, mot = [], {}
+        for k in range(K):
+            T = relative_to_rest(sim[k % B], idx)
+            c = np.asarray(centers[k], dtype=np.float64)
+            pairs.append((T, c))
+            Cp, Cm = np.eye(4), np.eye(4)
+            Cp[:3, 3], Cm[:3, 3] = c, -c
+            mot[k + 1] = Cp @ T @ Cm
+        tables[s] = pose_table(pairs)
+        motions.append(mot)
+    return tables, motions
