@@ -469,6 +469,23 @@ typedef struct PgrGrid {
 int32_t pgr_tsdf_integrate(const PgrGrid *grid, int32_t n_views, const PgrCamera *cameras, const float *depth,
                            const float *final_T, float truncation, float alpha_min, float *sdf, void *stream);
 
+/* The environment as a distance field (pegasus_amd/environment.py; the rule stands at the top of
+ * pegasus_amd/csrc/envfield.hip.h and in DESIGN.md section 25): a signed distance field over the whole grid from a carved
+ * volume, which is +-1 a few voxels from the surface and useless for sphere tracing.  `tsdf`, `sdf` and `dist2` (may be NULL)
+ * are device [nz,ny,nx]; `sdf` must not be `tsdf`.  inside(p) <=> tsdf(p) < 0 (a NaN is outside).  dist2(p) is the exact squared
+ * distance, in voxels, to the nearest grid point of the other sign, -1 where there is none.  A point with a 6-neighbour of the
+ * other sign (taken in the order -x, +x, -y, +y, -z, +z) is a band point: beta = min a / (a + b), a = |tsdf(p)|, b = |tsdf(n)|
+ * (1 for a value that is not finite), where pgr_march_emit puts its vertex on that edge.  sdf = s voxel beta for a band point,
+ * s voxel (sqrtf((float)dist2) - 0.5f) for other points, s voxel (float)(nx + ny + nz) without a point of the other sign; s = -1
+ * inside, +1 outside.  float32, every operation rounded on its own; integer minima only: two runs give equal bytes.  The field
+ * differs from the distance to the surface by less than a voxel and is not 1-Lipschitz.  Workspace:
+ * pgr_sdf_from_tsdf_workspace_bytes(nx, ny, nz) device bytes (0 for a bad grid; host-only), 16-byte aligned.  Invalid
+ * (PGR_ERR_INVALID_ARGUMENT, before any launch): a bad grid, a NULL tsdf, sdf or workspace, sdf == tsdf, a workspace that is too
+ * small or not aligned. */
+size_t pgr_sdf_from_tsdf_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+int32_t pgr_sdf_from_tsdf(const PgrGrid *grid, const float *tsdf, float *sdf, int32_t *dist2, void *workspace,
+                          size_t workspace_bytes, void *stream);
+
 /* Marching tetrahedra over `sdf` (inside: sdf < 0).  Every cell splits into the 6 tetrahedra around its
  * (0,0,0)-(1,1,1) diagonal; the mesh is closed and manifold, its triangles face positive sdf.  Each grid point owns the
  * edges +x, +y, +z, +x+y, +x+z, +y+z, +x+y+z (in that order) and emits one vertex per crossed edge, at
@@ -1167,6 +1184,25 @@ int32_t pgr_rigid_simulate(const PgrRigidParams *params, int32_t n_types, const 
                            int32_t n_slots, const int32_t *type, float *state, int32_t n_steps, int32_t record_every,
                            float *trajectory, int32_t *rest_step, int32_t *status, void *workspace, size_t workspace_bytes,
                            void *stream);
+/* The same two entries with the ground as a static field in world coordinates (pgr_sdf_from_tsdf writes one): with `ground`
+ * NULL they give the bytes of the entries above.  With a ground, pair slot a*B + a holds mover a against the field instead of
+ * the plane: no contacts where (field at x_a) - radius_a - 2 ground voxels > margin; per shell point the value and gradient by
+ * pgr_sdf_sample's rule at the world point (outside rule included), the unit gradient as the normal (a point whose gradient is
+ * shorter than 1e-6 is no candidate); the ground's friction in place of plane_friction; the rows are the plane's rows and the
+ * ground does not move.  params->plane is checked as before and not used.  Also invalid: a ground with a NULL field or a bad
+ * grid, a friction that is negative or not finite. */
+typedef struct PgrRigidGround {
+    PgrGrid grid;
+    const float *sdf;
+    float friction;
+} PgrRigidGround;
+int32_t pgr_rigid_contacts_ground(const PgrRigidParams *params, const PgrRigidGround *ground, int32_t n_types,
+                                  const PgrRigidType *types, int32_t n_worlds, int32_t n_slots, const int32_t *type,
+                                  const float *state, uint64_t *words, void *workspace, size_t workspace_bytes, void *stream);
+int32_t pgr_rigid_simulate_ground(const PgrRigidParams *params, const PgrRigidGround *ground, int32_t n_types,
+                                  const PgrRigidType *types, int32_t n_worlds, int32_t n_slots, const int32_t *type, float *state,
+                                  int32_t n_steps, int32_t record_every, float *trajectory, int32_t *rest_step, int32_t *status,
+                                  void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- PNG files of device images (pegasus_amd/png.py; csrc/png.hip.h, csrc/png_codes.h) ----------------------------------
  * bop_dataset.encode_png on the device: deflate, checksums and chunk framing of a batch of images that lie in device memory.

@@ -214,6 +214,10 @@ class PgrRigidParams(C.Structure):
                 ("sleep_steps", C.c_int32)]
 
 
+class PgrRigidGround(C.Structure):
+    _fields_ = [("grid", PgrGrid), ("sdf", C.c_void_p), ("friction", C.c_float)]
+
+
 # include/pegasus_raster.h: the slots of a world, the types of a table, the words of a pair, the floats of a body's state
 PGR_RIGID_MAX_BODIES, PGR_RIGID_MAX_TYPES, PGR_RIGID_WORDS, PGR_RIGID_STATE = 8, 16, 7, 13
 
@@ -312,6 +316,8 @@ SYMBOLS = {
                                       C.c_void_p]),
     "pgr_tsdf_integrate": (C.c_int32, [C.POINTER(PgrGrid), C.c_int32, C.POINTER(PgrCamera), C.c_void_p, C.c_void_p,
                                        C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "pgr_sdf_from_tsdf_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "pgr_sdf_from_tsdf": (C.c_int32, [C.POINTER(PgrGrid), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pgr_march_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "pgr_march_count": (C.c_int32, [C.POINTER(PgrGrid), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "pgr_march_emit": (C.c_int32, [C.POINTER(PgrGrid), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
@@ -391,6 +397,12 @@ SYMBOLS = {
     "pgr_rigid_simulate": (C.c_int32, [C.POINTER(PgrRigidParams), C.c_int32, C.POINTER(PgrRigidType), C.c_int32, C.c_int32,
                                        C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pgr_rigid_contacts_ground": (C.c_int32, [C.POINTER(PgrRigidParams), C.POINTER(PgrRigidGround), C.c_int32,
+                                              C.POINTER(PgrRigidType), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pgr_rigid_simulate_ground": (C.c_int32, [C.POINTER(PgrRigidParams), C.POINTER(PgrRigidGround), C.c_int32,
+                                              C.POINTER(PgrRigidType), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                              C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pgr_png_workspace_bytes": (C.c_size_t, [C.c_int32, C.POINTER(PgrPngJob)]),
     "pgr_png_encode": (C.c_int32, [C.POINTER(PgrPngJob), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pgr_png_emit": (C.c_int32, [C.POINTER(PgrPngJob), C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,

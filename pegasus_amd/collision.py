@@ -273,16 +273,30 @@ def decode_words(words):
     return value, index
 
 
-def min_distances(bodies: Sequence[CollisionBody], poses, plane=None) -> np.ndarray:
+def _with_environment(bodies, poses, environment, environment_pose=None):
+    """(bodies, poses) with the environment (an ``environment.EnvironmentField``) as one more body without shell points, at the
+    identity pose unless one is given; unchanged without an environment."""
+    poses = np.asarray(poses, np.float64).reshape(-1, 4, 4)
+    if environment is None:
+        return list(bodies), poses
+    T = np.eye(4) if environment_pose is None else np.asarray(environment_pose, np.float64).reshape(4, 4)
+    return list(bodies) + [environment.as_collision_body()], np.concatenate([poses, T[None]])
+
+
+def min_distances(bodies: Sequence[CollisionBody], poses, plane=None, environment=None, environment_pose=None) -> np.ndarray:
     """float32 [B, B+1]: entry [a, b] is the smallest value of body b's field over body a's shell points at these poses (the
     deepest interpenetration where negative), column B the same against the plane n.x = d (+inf without one); the diagonal is
-    +inf.  One ``pgr_sdf_sweep`` call with max_steps = 0."""
+    +inf.  One ``pgr_sdf_sweep`` call with max_steps = 0.  With an ``environment`` (an ``environment.EnvironmentField``, at the
+    identity pose unless ``environment_pose`` gives one) the result is [B, B+2] and column B+1 holds the same against its field."""
     B = len(bodies)
-    out = np.full((B, B + 1), np.inf, np.float32)
+    out = np.full((B, B + (1 if environment is None else 2)), np.inf, np.float32)
     if B == 0:
         return out
     down = (0.0, 0.0, -1.0)
     jobs = [(a, b, down) for a in range(B) for b in range(B) if a != b]
+    if environment is not None:
+        bodies, poses = _with_environment(bodies, poses, environment, environment_pose)
+        jobs += [(a, B, down) for a in range(B)]
     if plane is not None:
         plane = unit_plane(plane)
         jobs += [(a, PLANE, down) for a in range(B)]
@@ -290,7 +304,7 @@ def min_distances(bodies: Sequence[CollisionBody], poses, plane=None) -> np.ndar
         return out
     value, _ = decode_words(sweep_words(bodies, poses, jobs, plane, 0.0, 0.0, 0).cpu().numpy())
     for (a, b, _d), phi in zip(jobs, value[:, 0]):
-        out[a, B if b == PLANE else b] = phi
+        out[a, B if b == PLANE else (B + 1 if b == B else b)] = phi
     return out
 
 
@@ -313,18 +327,22 @@ def _unsigned_min(words):
 
 
 def sweep(bodies: Sequence[CollisionBody], poses, mover: int, direction, others: Optional[Sequence[int]] = None, plane=None,
-          tol: float = 1e-4, max_travel: float = 10.0, max_steps: int = 128) -> dict:
+          tol: float = 1e-4, max_travel: float = 10.0, max_steps: int = 128, environment=None) -> dict:
     """How far body ``mover`` can travel along ``direction`` before one of its shell points comes within ``tol`` of another
     body's field or of the plane (forward jobs), or another body's shell point within ``tol`` of its own field (reverse jobs: the
     other's shell moved by -direction).  Returns {"travel", "phi0": the deepest field value at the start, "jobs", "travels",
     "phi0s", "points"}: per job the minimum and the shell point that gives it.  The travel is conservative: every step of the
-    sphere tracing was at most the sampled free distance."""
+    sphere tracing was at most the sampled free distance.  ``environment``: an ``environment.EnvironmentField`` whose field the
+    mover is also traced against (a forward job whose target is the index len(bodies))."""
     direction = np.asarray(direction, np.float64).reshape(3)
     direction = direction / np.linalg.norm(direction)
     others = [b for b in range(len(bodies)) if b != mover] if others is None else [int(b) for b in others]
     if plane is not None:
         plane = unit_plane(plane)
     jobs = _sweep_jobs(int(mover), others, direction, plane is not None)
+    if environment is not None:
+        jobs.append((int(mover), len(bodies), tuple(float(x) for x in direction)))
+        bodies, poses = _with_environment(bodies, poses, environment)
     if not jobs:
         return dict(travel=float(max_travel), phi0=float("inf"), jobs=[], travels=np.zeros(0, np.float32),
                     phi0s=np.zeros(0, np.float32), points=np.zeros((0, 2), np.int64))
@@ -425,9 +443,17 @@ def start_height(vertices, R, placed_tops, n, margin: float) -> float:
     return max([0.0] + list(placed_tops)) + margin - below
 
 
+def environment_start_height(environment, vertices, R, at, margin: float) -> float:
+    """The z of a body's origin, over the point ``at``, at which its lowest point is ``margin`` above the environment's highest
+    solid grid point under its footprint (the bounding rectangle of its vertices); -inf where nothing solid is under it."""
+    w = np.asarray(vertices, np.float64) @ np.asarray(R, np.float64).T
+    top = environment.top_under(w[:, :2].min(0) + np.asarray(at, np.float64)[:2], w[:, :2].max(0) + np.asarray(at, np.float64)[:2])
+    return top + environment.voxel + margin - float(w[:, 2].min())
+
+
 def drop(bodies: Sequence[CollisionBody], order: Optional[Sequence[int]] = None, orientations=None, xy=None,
          plane=(0.0, 0.0, 1.0, 0.0), radius: Optional[float] = None, seed: int = 0, tol: float = 1e-4, max_rounds: int = 8,
-         max_steps: int = 128):
+         max_steps: int = 128, environment=None):
     """Places the bodies one after the other on the plane n.x = d and on each other.  Body k takes an orientation
     (``orientations[k]`` [3,3], or one of its ``resting_orientations`` drawn by weight with a random turn about n, from the
     generator seeded with ``seed``), a position over the plane (``xy[k]`` in the plane's (u, v) frame, or drawn uniformly from the
@@ -437,7 +463,10 @@ def drop(bodies: Sequence[CollisionBody], order: Optional[Sequence[int]] = None,
 
     Returns (poses float64 [B,4,4] indexed like ``bodies``, reports: per body {"order", "rounds", "settled", "travel",
     "touches": the bodies ("plane" for the plane) whose field -- or whose shell, in the body's own field -- is within 2 tol at the
-    end, "phi0": the smallest field value at the end}).  Orientation and lateral position are never changed by the lowering."""
+    end, "phi0": the smallest field value at the end}).  Orientation and lateral position are never changed by the lowering.
+
+    ``environment``: an ``environment.EnvironmentField`` (the plane must then be z = d) that every body is also traced against;
+    a body starts above the environment's highest solid point under its footprint, and "environment" is named in its touches."""
     B = len(bodies)
     order = list(range(B)) if order is None else [int(k) for k in order]
     if sorted(order) != list(range(B)):
@@ -449,7 +478,9 @@ def drop(bodies: Sequence[CollisionBody], order: Optional[Sequence[int]] = None,
     sizes = [float(np.linalg.norm(np.ptp(b.mesh.vertices.astype(np.float64), axis=0))) for b in bodies]
     if radius is None:
         radius = 0.5 * max(sizes, default=0.0)
-    margin = 2.0 * max((b.voxel for b in bodies), default=0.0) + 2.0 * tol
+    margin = 2.0 * max([b.voxel for b in bodies] + ([environment.voxel] if environment is not None else []), default=0.0) + 2.0 * tol
+    if environment is not None and not np.allclose(n, (0.0, 0.0, 1.0)):
+        raise ValueError("with an environment the plane must be z = d")
     poses = np.tile(np.eye(4), (B, 1, 1))
     reports = [None] * B
     placed, tops = [], []
@@ -466,6 +497,8 @@ def drop(bodies: Sequence[CollisionBody], order: Optional[Sequence[int]] = None,
             r, phi = radius * np.sqrt(rng.uniform()), rng.uniform(0.0, 2.0 * np.pi)
             a, b2 = r * np.cos(phi), r * np.sin(phi)
         h = start_height(body.mesh.vertices, R, tops, n, margin)
+        if environment is not None:
+            h = max(h, environment_start_height(environment, body.mesh.vertices, R, d * n + a * u + b2 * v, margin) - d)
         T = np.eye(4)
         T[:3, :3] = R
         T[:3, 3] = d * n + a * u + b2 * v + h * n
@@ -473,24 +506,31 @@ def drop(bodies: Sequence[CollisionBody], order: Optional[Sequence[int]] = None,
         active = placed + [k]
         sub = [bodies[i] for i in active]
         jobs = _sweep_jobs(len(active) - 1, range(len(placed)), -n, True)
+        if environment is not None:
+            jobs.append((len(active) - 1, len(active), tuple(float(x) for x in -n)))
+            sub = sub + [environment.as_collision_body()]
         max_travel = h + sizes[k] + margin
         rounds, settled, travel = 0, False, float("inf")
         while rounds < max_rounds:
-            words = sweep_words(sub, poses[active], jobs, p, tol, max_travel, max_steps)
+            words = sweep_words(sub, _active_poses(poses, active, environment), jobs, p, tol, max_travel, max_steps)
             travel = float(decode_words(_unsigned_min(words).cpu().numpy())[0][1])          # 16 bytes
             rounds += 1
             if travel <= tol:
                 settled = True
                 break
             poses[k, :3, 3] -= travel * n
-        value, _ = decode_words(sweep_words(sub, poses[active], jobs, p, tol, 0.0, 0).cpu().numpy())
-        touches = sorted({"plane" if b == PLANE else active[b if a == len(active) - 1 else a]
+        value, _ = decode_words(sweep_words(sub, _active_poses(poses, active, environment), jobs, p, tol, 0.0, 0).cpu().numpy())
+        touches = sorted({"plane" if b == PLANE else "environment" if b == len(active) else active[b if a == len(active) - 1 else a]
                           for (a, b, _), phi in zip(jobs, value[:, 0]) if phi <= 2.0 * tol}, key=str)
         reports[k] = dict(order=rank, rounds=rounds, settled=settled, travel=travel, touches=touches, phi0=float(value[:, 0].min()))
         placed.append(k)
         world = body.mesh.vertices.astype(np.float64) @ poses[k, :3, :3].T + poses[k, :3, 3]
         tops.append(float((world @ n).max()) - d)
     return poses, reports
+
+
+def _active_poses(poses, active, environment):
+    return poses[active] if environment is None else np.concatenate([poses[active], np.eye(4)[None]])
 
 
 # ---- files ------------------------------------------------------------------------------------------------------------
@@ -544,9 +584,17 @@ def read_simulation_steps(path, step: int = -1):
 
 
 def check_dataset(dataset_dir, models_dir, translation_scale: float = 1.0, split: str = "train", resolution: int = 96,
-                  device="cuda") -> dict:
+                  device="cuda", environment=None) -> dict:
     """{scene path: {image id: the deepest interpenetration of the image's scene_gt poses}}: the smallest entry of
-    ``min_distances`` between its objects (model-to-camera poses, so no plane), in scene_gt's unit; +inf for fewer than two."""
+    ``min_distances`` between its objects (model-to-camera poses, so no plane), in scene_gt's unit; +inf for fewer than two.
+    ``environment``: an ``environment.EnvironmentField`` in metres and world coordinates; the objects are then also held against
+    its field, placed by the image's cam_R_w2c / cam_t_w2c of scene_camera.json (an image without them is an error)."""
+    if environment is not None:
+        from .environment import EnvironmentField
+        from .mesh import Grid
+        g, k = environment.grid, float(translation_scale)
+        environment = EnvironmentField(environment.field * k, Grid(g.nx, g.ny, g.nz, tuple(float(o) * k for o in g.origin), g.voxel * k),
+                                       environment.friction)
     scenes = BD.scene_dirs(dataset_dir, split)
     cache, out = {}, {}
     unit = BD.unit_of(translation_scale)
@@ -562,7 +610,16 @@ def check_dataset(dataset_dir, models_dir, translation_scale: float = 1.0, split
                 T = np.eye(4)
                 T[:3, :3], T[:3, 3] = BD.pose_of(e)
                 poses.append(T)
-            D = min_distances([cache[i] for i in ids], np.asarray(poses).reshape(-1, 4, 4))
+            env_pose = None
+            if environment is not None:
+                cam = scene.camera[str(image)]
+                if "cam_R_w2c" not in cam or "cam_t_w2c" not in cam:
+                    raise ValueError(f"{scene.path} image {image}: scene_camera.json has no cam_R_w2c / cam_t_w2c to place the environment")
+                env_pose = np.eye(4)
+                env_pose[:3, :3] = np.asarray(cam["cam_R_w2c"], np.float64).reshape(3, 3)
+                env_pose[:3, 3] = np.asarray(cam["cam_t_w2c"], np.float64).reshape(3)
+            D = min_distances([cache[i] for i in ids], np.asarray(poses).reshape(-1, 4, 4), environment=environment,
+                              environment_pose=env_pose)
             per_image[str(image)] = float(D.min()) if D.size else float("inf")
         out[str(scene.path)] = per_image
     return out
@@ -585,15 +642,24 @@ def _parser():
     p.add_argument("--out", default=None, help="the simulation_steps.json to write")
     p.add_argument("--check", default=None, metavar="DATASET", help="report the deepest interpenetration of every image's "
                                                                     "scene_gt poses instead of placing anything")
+    p.add_argument("--environment", default=None, metavar="NPZ", help="the environment's field (python -m pegasus_amd.environment): "
+                                                                      "objects are placed on it, or with --check held against it")
     p.add_argument("--translation_scale", type=float, default=1.0,
                    help="--check: what scene_gt's translations were written with: 1 = metres, 1000 = millimetres")
     return p
 
 
+def _load_environment(a):
+    if not a.environment:
+        return None
+    from .environment import EnvironmentField
+    return EnvironmentField.load(a.environment)
+
+
 def main(argv: Optional[Sequence[str]] = None) -> int:
     a = _parser().parse_args(argv)
     if a.check:
-        report = check_dataset(a.check, a.models, a.translation_scale, resolution=a.resolution)
+        report = check_dataset(a.check, a.models, a.translation_scale, resolution=a.resolution, environment=_load_environment(a))
         for scene, images in report.items():
             for image, depth in images.items():
                 print(f"{scene} {image}: {depth:.6g}")
@@ -605,7 +671,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     by_id = bodies_from_dir(a.models, a.scale, a.objects, a.resolution)
     ids = [i for i in by_id for _ in range(max(1, a.count))]
     bodies = [by_id[i] for i in ids]
-    poses, reports = drop(bodies, radius=a.radius, seed=a.seed, tol=a.tol)
+    poses, reports = drop(bodies, radius=a.radius, seed=a.seed, tol=a.tol, environment=_load_environment(a))
     centers = [b.mesh.vertices.astype(np.float64).mean(0) for b in bodies]
     names = [BD.model_stem(i) for i in ids]
     write_simulation_steps(a.out, names, names, ids, poses, centers, a.steps)

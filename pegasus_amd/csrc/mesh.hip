@@ -1,5 +1,5 @@
 // mesh.hip -- host side of the object-mesh entries of libpegasus_raster.so: TSDF fusion and marching tetrahedra, the mesh
-// depth / visibility / shade renderers and BOP ground truth, vertex clustering, vertex attributes, distance fields and sweeps, rigid-body drops.
+// the environment field, depth / visibility / shade renderers and BOP ground truth, vertex clustering, vertex attributes, distance fields and sweeps, rigid-body drops.
 // Owns its kernel headers: no other translation unit includes them (DESIGN.md "Source layout").
 #include <hip/hip_runtime.h>
 
@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "decimate.hip.h"
+#include "envfield.hip.h"
 #include "host_common.h"
 #include "mesh.hip.h"
 #include "meshattr.hip.h"
@@ -85,6 +86,53 @@ int32_t pgr_tsdf_integrate(const PgrGrid* grid, int32_t n_views, const PgrCamera
     const dim3 blocks((grid->nx + TSDF_BX - 1) / TSDF_BX, (grid->ny + TSDF_BY - 1) / TSDF_BY, (grid->nz + TSDF_BZ - 1) / TSDF_BZ);
     tsdf_integrate_kernel<<<blocks, block, 0, as_stream(stream_v)>>>(a);
     return launch_status("tsdf_integrate launch");
+}
+
+// ---- the environment as a distance field (envfield.hip.h) ---------------------------------------------------------------------
+namespace {
+struct EnvLayout { size_t near_in, near_out, total; };
+EnvLayout env_layout(size_t n) {
+    EnvLayout L{};
+    Carver c;
+    L.near_in = c.take(n * sizeof(uint32_t));
+    L.near_out = c.take(n * sizeof(uint32_t));
+    L.total = c.off;
+    return L;
+}
+int32_t env_columns(int32_t n) { return n <= 256 ? 64 : (n <= 512 ? 32 : 16); }   // n * columns <= ENV_LINE_WORDS
+}  // namespace
+
+size_t pgr_sdf_from_tsdf_workspace_bytes(int32_t nx, int32_t ny, int32_t nz) {
+    const PgrGrid g{nx, ny, nz, {0.f, 0.f, 0.f}, 1.f};
+    return grid_ok(&g) ? env_layout(grid_points(&g)).total : 0;
+}
+
+int32_t pgr_sdf_from_tsdf(const PgrGrid* grid, const float* tsdf, float* sdf, int32_t* dist2, void* workspace,
+                          size_t workspace_bytes, void* stream_v) {
+    static_assert(MESH_MAX_AXIS == ENV_MAX_AXIS && ENV_MAX_AXIS * 16 <= ENV_LINE_WORDS, "line tiles of env_line_kernel");
+    if (!grid_ok(grid) || !tsdf || !sdf || sdf == tsdf || !workspace || !workspace_aligned_16(workspace))
+        return PGR_ERR_INVALID_ARGUMENT;
+    const size_t n = grid_points(grid);
+    const EnvLayout L = env_layout(n);
+    if (workspace_bytes < L.total) return PGR_ERR_INVALID_ARGUMENT;
+    hipStream_t stream = as_stream(stream_v);
+    auto* near_in = ws_at<uint32_t>(workspace, L.near_in);
+    auto* near_out = ws_at<uint32_t>(workspace, L.near_out);
+    const int32_t nx = grid->nx, ny = grid->ny, nz = grid->nz;
+    const int32_t lines_per_block = std::max(1, ENV_THREADS / nx);
+    const long long lines = (long long)ny * nz;
+    env_x_kernel<<<(uint32_t)((lines + lines_per_block - 1) / lines_per_block), ENV_THREADS, 0, stream>>>(
+        nx, (long long)n, lines_per_block, tsdf, near_in, near_out);
+    const long long slab = (long long)nx * ny;
+    int32_t tx = env_columns(ny);
+    env_line_kernel<<<dim3((uint32_t)((nx + tx - 1) / tx), (uint32_t)nz, 2), ENV_THREADS, (size_t)ny * tx * sizeof(uint32_t), stream>>>(
+        nx, ny, (long long)nx, slab, tx, near_in, near_out);
+    tx = env_columns(nz);
+    env_line_kernel<<<dim3((uint32_t)((nx + tx - 1) / tx), (uint32_t)ny, 2), ENV_THREADS, (size_t)nz * tx * sizeof(uint32_t), stream>>>(
+        nx, nz, slab, (long long)nx, tx, near_in, near_out);
+    env_value_kernel<<<(uint32_t)((n + ENV_THREADS - 1) / ENV_THREADS), ENV_THREADS, 0, stream>>>(mesh_grid(grid), tsdf, near_in,
+                                                                                                 near_out, sdf, dist2);
+    return launch_status("sdf_from_tsdf launch");
 }
 
 size_t pgr_march_workspace_bytes(int32_t nx, int32_t ny, int32_t nz) {
@@ -741,15 +789,29 @@ bool rigid_args(const PgrRigidParams* p, int32_t n_types, const PgrRigidType* ty
     P.n_types = n_types;
     return true;
 }
+// the ground of the *_ground entries: NULL is the plane (G.sdf stays NULL)
+bool rigid_ground(const PgrRigidGround* ground, RigidGroundDev& G) {
+    G = RigidGroundDev{};
+    if (!ground) return true;
+    if (!ground->sdf || !grid_ok(&ground->grid) || !std::isfinite(ground->friction) || ground->friction < 0.f) return false;
+    G.g = mesh_grid(&ground->grid);
+    G.sdf = ground->sdf;
+    G.friction = ground->friction;
+    return true;
+}
 // one pass of rigid_contacts_kernel over every (world, pair, point block); halt may be NULL
-void rigid_launch_contacts(const RigidTable& T, const RigidTypeDev* table, const RigidParamsDev& P, int32_t n_types, int32_t S, int32_t B, const int32_t* type,
+void rigid_launch_contacts(const RigidTable& T, const RigidTypeDev* table, const RigidParamsDev& P, const RigidGroundDev& G,
+                           int32_t n_types, int32_t S, int32_t B, const int32_t* type,
                            const float* state, const int32_t* halt, uint64_t* words, hipStream_t stream) {
     int32_t most = 0;
     for (int32_t k = 0; k < n_types; ++k) most = std::max(most, T.t[k].n_shell);
     const uint32_t point_blocks = (uint32_t)(((int64_t)most + RIGID_CONTACT_THREADS - 1) / RIGID_CONTACT_THREADS);
     if (point_blocks == 0) return;
-    rigid_contacts_kernel<<<dim3((uint32_t)S, (uint32_t)(B * B), point_blocks), RIGID_CONTACT_THREADS, 0, stream>>>(
-        table, P, B, type, state, halt, words);
+    const dim3 blocks((uint32_t)S, (uint32_t)(B * B), point_blocks);
+    if (G.sdf)
+        rigid_contacts_kernel<true><<<blocks, RIGID_CONTACT_THREADS, 0, stream>>>(table, P, G, B, type, state, halt, words);
+    else
+        rigid_contacts_kernel<false><<<blocks, RIGID_CONTACT_THREADS, 0, stream>>>(table, P, G, B, type, state, halt, words);
 }
 }  // namespace
 
@@ -758,9 +820,16 @@ size_t pgr_rigid_workspace_bytes(int32_t n_worlds, int32_t n_slots) { return rig
 int32_t pgr_rigid_contacts(const PgrRigidParams* params, int32_t n_types, const PgrRigidType* types, int32_t S, int32_t B,
                            const int32_t* type, const float* state, uint64_t* words, void* workspace, size_t workspace_bytes,
                            void* stream_v) {
+    return pgr_rigid_contacts_ground(params, nullptr, n_types, types, S, B, type, state, words, workspace, workspace_bytes, stream_v);
+}
+
+int32_t pgr_rigid_contacts_ground(const PgrRigidParams* params, const PgrRigidGround* ground, int32_t n_types,
+                                  const PgrRigidType* types, int32_t S, int32_t B, const int32_t* type, const float* state,
+                                  uint64_t* words, void* workspace, size_t workspace_bytes, void* stream_v) {
     RigidTable T;
     RigidParamsDev P;
-    if (!rigid_args(params, n_types, types, S, B, type, state, T, P)) return PGR_ERR_INVALID_ARGUMENT;
+    RigidGroundDev G;
+    if (!rigid_args(params, n_types, types, S, B, type, state, T, P) || !rigid_ground(ground, G)) return PGR_ERR_INVALID_ARGUMENT;
     if (S == 0 || B == 0) return PGR_OK;
     if (!words || !workspace || !workspace_aligned_16(workspace)) return PGR_ERR_INVALID_ARGUMENT;
     const RigidLayout L = rigid_layout(S, B);
@@ -772,16 +841,25 @@ int32_t pgr_rigid_contacts(const PgrRigidParams* params, int32_t n_types, const 
     RigidTypeDev* table = ws_at<RigidTypeDev>(workspace, L.table);
     rigid_table_kernel<<<1, WAVE, 0, stream>>>(T, table);
     rigid_init_kernel<<<(uint32_t)((n_words + 255) / 256), 256, 0, stream>>>(words, n_words, nullptr, nullptr, nullptr, nullptr, 0);
-    rigid_launch_contacts(T, table, P, n_types, S, B, type, state, nullptr, words, stream);
+    rigid_launch_contacts(T, table, P, G, n_types, S, B, type, state, nullptr, words, stream);
     return launch_status("rigid_contacts launch");
 }
 
 int32_t pgr_rigid_simulate(const PgrRigidParams* params, int32_t n_types, const PgrRigidType* types, int32_t S, int32_t B,
                            const int32_t* type, float* state, int32_t n_steps, int32_t record_every, float* trajectory,
                            int32_t* rest_step, int32_t* status, void* workspace, size_t workspace_bytes, void* stream_v) {
+    return pgr_rigid_simulate_ground(params, nullptr, n_types, types, S, B, type, state, n_steps, record_every, trajectory, rest_step,
+                                     status, workspace, workspace_bytes, stream_v);
+}
+
+int32_t pgr_rigid_simulate_ground(const PgrRigidParams* params, const PgrRigidGround* ground, int32_t n_types,
+                                  const PgrRigidType* types, int32_t S, int32_t B, const int32_t* type, float* state, int32_t n_steps,
+                                  int32_t record_every, float* trajectory, int32_t* rest_step, int32_t* status, void* workspace,
+                                  size_t workspace_bytes, void* stream_v) {
     RigidTable T;
     RigidParamsDev P;
-    if (!rigid_args(params, n_types, types, S, B, type, state, T, P)) return PGR_ERR_INVALID_ARGUMENT;
+    RigidGroundDev G;
+    if (!rigid_args(params, n_types, types, S, B, type, state, T, P) || !rigid_ground(ground, G)) return PGR_ERR_INVALID_ARGUMENT;
     if (n_steps < 0 || record_every < 1) return PGR_ERR_INVALID_ARGUMENT;
     if (S == 0 || B == 0) return PGR_OK;
     const int32_t n_records = n_steps / record_every;
@@ -803,10 +881,14 @@ int32_t pgr_rigid_simulate(const PgrRigidParams* params, int32_t n_types, const 
     rigid_init_kernel<<<(uint32_t)((n_init + 255) / 256), 256, 0, stream>>>(words, n_words, halt, rest_count, rest_step, status, S);
     const uint32_t solve_blocks = (uint32_t)((S + RIGID_SOLVE_THREADS - 1) / RIGID_SOLVE_THREADS);
     for (int32_t k = 0; k < n_steps; ++k) {
-        rigid_launch_contacts(T, table, P, n_types, S, B, type, state, halt, words, stream);
+        rigid_launch_contacts(T, table, P, G, n_types, S, B, type, state, halt, words, stream);
         const int32_t record = (k + 1) % record_every == 0 ? (k + 1) / record_every - 1 : -1;
-        rigid_solve_kernel<<<solve_blocks, RIGID_SOLVE_THREADS, 0, stream>>>(table, P, S, B, type, state, words, rows, halt, rest_count, k,
-                                                                            record, n_records, trajectory, rest_step, status);
+        if (G.sdf)
+            rigid_solve_kernel<true><<<solve_blocks, RIGID_SOLVE_THREADS, 0, stream>>>(
+                table, P, G, S, B, type, state, words, rows, halt, rest_count, k, record, n_records, trajectory, rest_step, status);
+        else
+            rigid_solve_kernel<false><<<solve_blocks, RIGID_SOLVE_THREADS, 0, stream>>>(
+                table, P, G, S, B, type, state, words, rows, halt, rest_count, k, record, n_records, trajectory, rest_step, status);
     }
     return launch_status("rigid_simulate launch");
 }

@@ -10,7 +10,11 @@
 //   outside [0, n_types) is an empty slot.  State per (world, slot) is float32[13]: x (centre of mass, world), q (x, y, z, w;
 //   unit), v, omega (world).  R(q) = [1 - 2(yy + zz), 2(xy - zw), 2(xz + yw); 2(xy + zw), 1 - 2(xx + zz), 2(yz - xw);
 //   2(xz - yw), 2(yz + xw), 1 - 2(xx + yy)];  T = x - R c per axis ((R0 c.x + R1 c.y) + R2 c.z subtracted from x).  The ground is
-//   the plane n.x = d.
+//   the plane n.x = d, or (the *_ground entries, kernels instantiated with GROUND) a static field in world coordinates, as
+//   pgr_sdf_from_tsdf writes it: then pair slot a B + a holds mover a against that field.  Spheres: sdf_eval(ground, x_a) -
+//   radius_a - 2 voxel_g > margin: no contacts.  Point: (phi, grad) = pgr_sdf_sample's rule at the world point p, outside rule
+//   included; a point without gn >= 1e-6 is no candidate; normal = grad / gn per component, no rotation.  mu_b is the ground's
+//   friction; the rows are the plane's rows, the ground has no velocity; the plane of the parameters is checked and not used.
 //
 // One step (step h, gravity g), in this order:
 //   1 Gravity and damping.  v <- (v + h g) fl,  omega <- omega fa  with  fl = (float) pow(1 - lin_damp, h),  fa likewise, taken
@@ -95,6 +99,12 @@ struct RigidParamsDev {
     int32_t iterations, sleep_steps, n_types, pad;
 };
 
+struct RigidGroundDev {                              // the ground as a field in world coordinates (GROUND kernels only)
+    MeshGrid g;
+    const float* sdf;
+    float friction;
+};
+
 struct RigidFrame {                                  // a body's pose: R(q) row-major and T = x - R c
     float R[9], T[3];
 };
@@ -120,14 +130,26 @@ __device__ __forceinline__ RigidFrame rigid_frame(const float* x, const float* q
 }
 
 // shell point s of a mover at frame A against the plane (`plane`) or against the field of `target` at frame Bf:
-// the point p, the field value phi and the unit normal in the world.  false: the gradient gives no normal.
+// the point p, the field value phi and the unit normal in the world.  false: the gradient gives no normal.  GROUND: the
+// plane's place is taken by the field G, sampled at p itself; its gradient is the normal, with no rotation.
+template <bool GROUND>
 __device__ __forceinline__ bool rigid_point(const RigidFrame& A, float sx, float sy, float sz, const RigidParamsDev& P,
-                                            bool plane, const RigidTypeDev& target, const RigidFrame& Bf, float* p, float& phi,
-                                            float* n) {
+                                            const RigidGroundDev& G, bool plane, const RigidTypeDev& target, const RigidFrame& Bf,
+                                            float* p, float& phi, float* n) {
     p[0] = ((A.R[0] * sx + A.R[1] * sy) + A.R[2] * sz) + A.T[0];
     p[1] = ((A.R[3] * sx + A.R[4] * sy) + A.R[5] * sz) + A.T[1];
     p[2] = ((A.R[6] * sx + A.R[7] * sy) + A.R[8] * sz) + A.T[2];
     if (plane) {
+        if constexpr (GROUND) {
+            float g[3];
+            phi = sdf_eval(G.g, G.sdf, p[0], p[1], p[2], g);
+            const float gn = sqrtf(sdf_dot(g[0], g[1], g[2], g[0], g[1], g[2]));
+            if (!(gn >= 1e-6f)) return false;
+            n[0] = g[0] / gn;
+            n[1] = g[1] / gn;
+            n[2] = g[2] / gn;
+            return true;
+        }
         phi = sdf_dot(P.nx, P.ny, P.nz, p[0], p[1], p[2]) - P.d;
         n[0] = P.nx;
         n[1] = P.ny;
@@ -173,8 +195,10 @@ __global__ __launch_bounds__(256) void rigid_init_kernel(uint64_t* __restrict__ 
     }
 }
 
+template <bool GROUND>
 __global__ __launch_bounds__(RIGID_CONTACT_THREADS) void rigid_contacts_kernel(const RigidTypeDev* __restrict__ table,
-                                                                               const RigidParamsDev P, int32_t B,
+                                                                               const RigidParamsDev P, const RigidGroundDev G,
+                                                                               int32_t B,
                                                                                const int32_t* __restrict__ type,
                                                                                const float* __restrict__ state,
                                                                                const int32_t* __restrict__ halt,
@@ -194,7 +218,11 @@ __global__ __launch_bounds__(RIGID_CONTACT_THREADS) void rigid_contacts_kernel(c
     RigidTypeDev Bt{};
     RigidFrame Fb{};
     if (plane) {
-        if ((sdf_dot(P.nx, P.ny, P.nz, xa[0], xa[1], xa[2]) - P.d) - A.radius > P.margin) return;
+        if constexpr (GROUND) {                          // two voxels: the field's error and slope
+            if ((sdf_eval(G.g, G.sdf, xa[0], xa[1], xa[2], nullptr) - A.radius) - 2.f * G.g.voxel > P.margin) return;
+        } else {
+            if ((sdf_dot(P.nx, P.ny, P.nz, xa[0], xa[1], xa[2]) - P.d) - A.radius > P.margin) return;
+        }
     } else {
         const int tb = __builtin_amdgcn_readfirstlane(rigid_type_of(type, (size_t)w * B + b, P.n_types));
         if (tb < 0) return;
@@ -215,7 +243,7 @@ __global__ __launch_bounds__(RIGID_CONTACT_THREADS) void rigid_contacts_kernel(c
     if (pi < A.n_shell) {
         const float* s = A.shell + 3 * (size_t)pi;
         float p[3], n[3], phi;
-        if (rigid_point(Fa, gload(s), gload(s + 1), gload(s + 2), P, plane, Bt, Fb, p, phi, n) && phi <= P.margin) {
+        if (rigid_point<GROUND>(Fa, gload(s), gload(s + 1), gload(s + 2), P, G, plane, Bt, Fb, p, phi, n) && phi <= P.margin) {
             const float rx = p[0] - xa[0], ry = p[1] - xa[1], rz = p[2] - xa[2];
             const float value[RIGID_WORDS] = {phi, rx, -rx, ry, -ry, rz, -rz};
 #pragma unroll
@@ -259,8 +287,10 @@ __device__ __forceinline__ void rigid_apply_iinv(const float* R, const float* I,
     W[2] = (R[6] * mx + R[7] * my) + R[8] * mz;
 }
 
+template <bool GROUND>
 __global__ __launch_bounds__(RIGID_SOLVE_THREADS) void rigid_solve_kernel(
-    const RigidTypeDev* __restrict__ table, const RigidParamsDev P, int32_t S, int32_t B, const int32_t* __restrict__ type,
+    const RigidTypeDev* __restrict__ table, const RigidParamsDev P, const RigidGroundDev G, int32_t S, int32_t B,
+    const int32_t* __restrict__ type,
     float* __restrict__ state,
     uint64_t* __restrict__ words, float* __restrict__ rows, int32_t* __restrict__ halt, int32_t* __restrict__ rest_count,
     int32_t step, int32_t record, int32_t n_records, float* __restrict__ trajectory, int32_t* __restrict__ rest_step,
@@ -316,7 +346,7 @@ __global__ __launch_bounds__(RIGID_SOLVE_THREADS) void rigid_solve_kernel(
                 RigidTypeDev Bt{};
                 if (!plane) Bt = table[tb];
                 RigidFrame Fb{};
-                float xb[3] = {0.f, 0.f, 0.f}, imb = 0.f, mu = A.friction * P.plane_friction;
+                float xb[3] = {0.f, 0.f, 0.f}, imb = 0.f, mu = A.friction * (GROUND ? G.friction : P.plane_friction);
                 if (!plane) {
                     xb[0] = RIGID_ST(b, 0);
                     xb[1] = RIGID_ST(b, 1);
@@ -336,7 +366,7 @@ __global__ __launch_bounds__(RIGID_SOLVE_THREADS) void rigid_solve_kernel(
                     last = m;
                     const float* s = A.shell + 3 * (size_t)m;
                     float p[3], n[3], phi;
-                    if (!rigid_point(Fa, gload(s), gload(s + 1), gload(s + 2), P, plane, Bt, Fb, p, phi, n)) continue;
+                    if (!rigid_point<GROUND>(Fa, gload(s), gload(s + 1), gload(s + 2), P, G, plane, Bt, Fb, p, phi, n)) continue;
                     float* row = rows + ((size_t)nc * RIGID_ROW_FIELDS) * S_ + (size_t)w;
                     const float ra[3] = {p[0] - xa[0], p[1] - xa[1], p[2] - xa[2]};
                     const float rb[3] = {p[0] - xb[0], p[1] - xb[1], p[2] - xb[2]};

@@ -145,9 +145,18 @@ def _device_of(bodies):
     return bodies[0].body.sdf.field.device
 
 
-def contacts(bodies: Sequence[RigidBody], types, state, params: Optional[Params] = None):
+def _ground_arg(ground):
+    """(the PgrRigidGround pointer the *_ground entries take, what keeps it alive); NULL for no ground."""
+    if ground is None:
+        return None, None
+    g = ground.struct()
+    return C.byref(g), (g, ground)
+
+
+def contacts(bodies: Sequence[RigidBody], types, state, params: Optional[Params] = None, ground=None):
     """``pgr_rigid_contacts``: the contact words int64 [S, B*B, 7] (device; ``collision.decode_words`` reads them on the host)
-    of a state [S,B,13]."""
+    of a state [S,B,13].  ``ground``: an ``environment.EnvironmentField`` that takes the plane's place
+    (``pgr_rigid_contacts_ground``)."""
     import torch
     params = params or Params()
     t = _types(types, len(bodies))
@@ -160,18 +169,21 @@ def contacts(bodies: Sequence[RigidBody], types, state, params: Optional[Params]
         return words
     ws = _lib.workspace("pgr_rigid", device, S, B)
     p = params.struct(bodies)
-    _lib.call("pgr_rigid_contacts", device, C.byref(p), len(bodies), _table(bodies), S, B, _lib.ptr(d_type), _lib.ptr(d_state),
-              _lib.ptr(words), _lib.ptr(ws), ws.numel())
+    g, keep = _ground_arg(ground)
+    _lib.call("pgr_rigid_contacts_ground", device, C.byref(p), g, len(bodies), _table(bodies), S, B, _lib.ptr(d_type),
+              _lib.ptr(d_state), _lib.ptr(words), _lib.ptr(ws), ws.numel())
+    del keep
     return words
 
 
 def simulate(bodies: Sequence[RigidBody], types, poses0=None, steps: int = 1000, params: Optional[Params] = None,
-             record_every: int = 1, velocities=None, state=None, return_state: bool = False):
+             record_every: int = 1, velocities=None, state=None, return_state: bool = False, ground=None):
     """``pgr_rigid_simulate``: S worlds of B slots (``types`` [S,B], -1 = empty) from mesh-frame poses ``poses0`` [S,B,7] (or a
     full ``state`` [S,B,13]) for ``steps`` steps, all enqueued on the current stream.  Returns device tensors: trajectory float32
     [S, steps // record_every, B, 7] (mesh-frame t, q in x,y,z,w after every record_every-th step), rest_step int32 [S] (-1: never
     came to rest), status int32 [S] (1: the state stopped being finite; the world stays at its last finite state); with
-    ``return_state`` also the final state [S,B,13]."""
+    ``return_state`` also the final state [S,B,13].  ``ground``: an ``environment.EnvironmentField`` the bodies fall onto instead
+    of the plane (``pgr_rigid_simulate_ground``); outside its grid box nothing is below a body."""
     import torch
     params = params or Params()
     if steps < 0 or record_every < 1:
@@ -192,9 +204,11 @@ def simulate(bodies: Sequence[RigidBody], types, poses0=None, steps: int = 1000,
     if S and B:
         ws = _lib.workspace("pgr_rigid", device, S, B)
         p = params.struct(bodies)
-        _lib.call("pgr_rigid_simulate", device, C.byref(p), len(bodies), _table(bodies), S, B, _lib.ptr(d_type), _lib.ptr(d_state),
-                  int(steps), int(record_every), _lib.ptr(traj) if n_records else None, _lib.ptr(rest), _lib.ptr(status),
-                  _lib.ptr(ws), ws.numel())
+        g, keep = _ground_arg(ground)
+        _lib.call("pgr_rigid_simulate_ground", device, C.byref(p), g, len(bodies), _table(bodies), S, B, _lib.ptr(d_type),
+                  _lib.ptr(d_state), int(steps), int(record_every), _lib.ptr(traj) if n_records else None, _lib.ptr(rest),
+                  _lib.ptr(status), _lib.ptr(ws), ws.numel())
+        del keep
     return (traj, rest, status, d_state) if return_state else (traj, rest, status)
 
 
@@ -208,11 +222,12 @@ def start_quaternion(rng) -> np.ndarray:
 
 
 def start_states(bodies: Sequence[RigidBody], types, seed: int, radius: Optional[float] = None, gap: Optional[float] = None,
-                 plane=(0.0, 0.0, 1.0, 0.0)) -> np.ndarray:
+                 plane=(0.0, 0.0, 1.0, 0.0), ground=None) -> np.ndarray:
     """Mesh-frame start poses float64 [S,B,7] from the generator seeded with ``seed``: per slot the reference's start orientation,
     a position in the disc of ``radius`` (default: the largest body's half diagonal) over the plane, and a height
     (``collision.start_height``) that puts its lowest point ``gap`` (default: two of the largest voxel) above everything placed
-    before it in its world."""
+    before it in its world.  With a ``ground`` (an ``environment.EnvironmentField``; the plane must be z = d) also above the
+    ground's highest solid point under the body's footprint."""
     t = _types(types, len(bodies))
     p = COL.unit_plane(plane)
     n, d = p[:3], float(p[3])
@@ -234,17 +249,21 @@ def start_states(bodies: Sequence[RigidBody], types, seed: int, radius: Optional
             R = _rotation(q)
             r, phi = radius * np.sqrt(rng.uniform()), rng.uniform(0.0, 2.0 * np.pi)
             h = COL.start_height(verts[t[w, k]], R, tops, n, gap)
-            poses[w, k, :3] = d * n + r * np.cos(phi) * u + r * np.sin(phi) * v + h * n
+            at = d * n + r * np.cos(phi) * u + r * np.sin(phi) * v
+            if ground is not None:
+                h = max(h, COL.environment_start_height(ground, verts[t[w, k]], R, at, gap) - d)
+            poses[w, k, :3] = at + h * n
             poses[w, k, 3:] = q
             tops.append(float((verts[t[w, k]] @ R.T @ n).max()) + h)
     return poses
 
 
 # ---- files ------------------------------------------------------------------------------------------------------------------
-def write_trajectory(path, names, class_names, object_ids, trajectory, centers=None) -> dict:
+def write_trajectory(path, names, class_names, object_ids, trajectory, centers=None, environment: Optional[str] = None) -> dict:
     """``collision.write_simulation_steps``' layout with a pose per step: ``trajectory`` [n_steps, B, 7] holds mesh-frame poses
     (t, q in x,y,z,w); body k gets bullet id k + 1 and its ``t`` is converted by ``collision.reference_translation`` about
-    ``centers[k]`` (default: the origin).  Returns the document."""
+    ``centers[k]`` (default: the origin).  ``environment``: the name body 0 gets in ``asset_infos.environment`` instead of the
+    plane's.  Returns the document."""
     traj = np.asarray(trajectory, np.float64)
     if traj.ndim != 3 or traj.shape[2] != 7 or traj.shape[0] < 1:
         raise ValueError("trajectory must be [n_steps >= 1, B, 7]")
@@ -267,20 +286,28 @@ def write_trajectory(path, names, class_names, object_ids, trajectory, centers=N
             T[:3, :3], T[:3, 3] = R[s], traj[s, k, :3]
             steps[str(s)] = {"t": COL.reference_translation(T, centers[k]).tolist(), "q": traj[s, k, 3:].tolist()}
         doc_traj[str(k + 1)] = steps
-    doc = {"asset_infos": {"environment": {"plane": {"bullet_id": [0], "class_name": "plane"}}, "object": objects},
-           "trajectory": doc_traj}
+    env = {"plane": {"bullet_id": [0], "class_name": "plane"}} if environment is None else \
+        {str(environment): {"bullet_id": [0], "class_name": "environment"}}
+    doc = {"asset_infos": {"environment": env, "object": objects}, "trajectory": doc_traj}
     path = Path(path)
     path.parent.mkdir(parents=True, exist_ok=True)
     path.write_text(json.dumps(doc))
     return doc
 
 
+def outside_ground(ground, poses) -> np.ndarray:
+    """bool [...]: the mesh-frame poses [...,7] whose origin lies outside the ground's grid box, where nothing is below a body."""
+    lo, hi = ground.box()
+    t = np.asarray(poses, np.float64)[..., :3]
+    return ((t < lo) | (t > hi)).any(axis=-1)
+
+
 @dataclass
 class Engine:
     """The surface of the reference's ``PybulletEngine``: ``add_object(object_instance, start_pos, start_orientation_euler)``
     and ``simulate()``, which writes ``output_path_json`` in the reference's layout.  ``bodies``: {object id: RigidBody}.  An
-    object instance has ``TYPE`` ('environment': the ground plane, recorded as body 0; 'object'), and for an object ``ID`` and
-    optionally ``urdf_file_name``.  As in the reference the Euler angles are not used: an object starts in four uniform(0, 1)
+    object instance has ``TYPE`` ('environment': the ground, recorded as body 0 -- the plane, or the instance's ``field``, an
+    ``environment.EnvironmentField``, where it has one; 'object'), and for an object ``ID`` and optionally ``urdf_file_name``.  As in the reference the Euler angles are not used: an object starts in four uniform(0, 1)
     draws, normalised -- here from the generator seeded with ``seed``."""
     bodies: dict
     output_path_json: str = "simulation_steps.json"
@@ -288,6 +315,8 @@ class Engine:
     seed: int = 0
     params: Params = field(default_factory=Params)
     record_every: int = 1
+    ground: object = None
+    environment_name: Optional[str] = None
 
     def __post_init__(self):
         if self.simulation_steps < 1 or self.record_every < 1 or self.simulation_steps // self.record_every < 1:
@@ -298,6 +327,9 @@ class Engine:
     def add_object(self, object_instance, start_pos=(0.0, 0.0, 0.0), start_orientation_euler=(0.0, 0.0, 0.0)):
         kind = getattr(object_instance, "TYPE", None)
         if kind == "environment":
+            if getattr(object_instance, "field", None) is not None:
+                self.ground = object_instance.field
+                self.environment_name = str(getattr(object_instance, "urdf_file_name", "environment")).split(".")[0]
             return
         if kind != "object":
             raise ValueError(f"Wrong entity - {kind}")
@@ -323,11 +355,12 @@ class Engine:
         types = [[ids.index(o[2]) for o in self._objects]]
         # start_pos is where pybullet puts the link frame's origin, which is the mesh frame's here
         poses = np.stack([o[3] for o in self._objects])[None]
-        traj, rest, status = simulate(table, types, poses, self.simulation_steps, self.params, self.record_every)
+        traj, rest, status = simulate(table, types, poses, self.simulation_steps, self.params, self.record_every, ground=self.ground)
         traj = traj[0].cpu().numpy()
         centers = [self.bodies[o[2]].body.mesh.vertices.astype(np.float64).mean(0) for o in self._objects]
         write_trajectory(self.output_path_json, [o[0] for o in self._objects], [o[1] for o in self._objects],
-                         [o[2] for o in self._objects], traj, centers)
+                         [o[2] for o in self._objects], traj, centers,
+                         environment=(self.environment_name or "environment") if self.ground is not None else None)
         return traj, int(rest[0]), int(status[0])
 
 
@@ -353,6 +386,8 @@ def _parser():
     p.add_argument("--radius", type=float, default=None, help="radius of the disc the objects start over")
     p.add_argument("--mass", type=float, default=1.0)
     p.add_argument("--friction", type=float, default=0.5)
+    p.add_argument("--environment", default=None, metavar="NPZ", help="the ground as a field (python -m pegasus_amd.environment) "
+                                                                      "instead of the plane z = 0")
     p.add_argument("--out", required=True, help="directory: scene_NNNNNN/simulation_steps.json per scene")
     return p
 
@@ -369,15 +404,22 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     by_id = bodies_from_dir(a.models, a.scale, ids, a.resolution, a.mass, a.friction)
     table = [by_id[i] for i in ids]
     types = np.tile(np.array([ids.index(i) for i in a.objects], np.int32), (a.scenes, 1))
-    poses = start_states(table, types, a.seed, a.radius)
-    traj, rest, status = simulate(table, types, poses, a.steps, record_every=a.record_every)
+    ground = None
+    if a.environment:
+        from .environment import EnvironmentField
+        ground = EnvironmentField.load(a.environment)
+    poses = start_states(table, types, a.seed, a.radius, ground=ground)
+    traj, rest, status = simulate(table, types, poses, a.steps, record_every=a.record_every, ground=ground)
     traj, rest, status = traj.cpu().numpy(), rest.cpu().numpy(), status.cpu().numpy()
     names = [BD.model_stem(i) for i in a.objects]
     centers = [by_id[i].body.mesh.vertices.astype(np.float64).mean(0) for i in a.objects]
     for w in range(a.scenes):
         path = Path(a.out) / f"scene_{w:06d}" / "simulation_steps.json"
-        write_trajectory(path, names, names, a.objects, traj[w], centers)
+        write_trajectory(path, names, names, a.objects, traj[w], centers,
+                         environment=Path(a.environment).stem if ground is not None else None)
         state = "not finite, frozen" if status[w] else (f"at rest after step {rest[w]}" if rest[w] >= 0 else "still moving")
+        if ground is not None and outside_ground(ground, traj[w, -1]).any():
+            state += "; a body left the environment's grid box (nothing is below it there)"
         print(f"scene {w}: {state} -> {path}")
     return 0
 
