@@ -208,8 +208,131 @@ def word_exemptions(types, type_row, state, p):
     return words, exempt
 
 
+# ---- edges: shells beyond one point block, a tie across blocks, a crowded world, the guard's triggers ---------------------------
+POINT_BLOCK = 256                            # rigid_contacts_kernel's points per workgroup
+SHELL_CASES = ((257, 513, 256), (300, 700, 64))        # shell sizes of (cube, L prism, small cube): see scattered_shell
+MIN_HIGH_INDEX_WORDS = 20
+
+
+@functools.lru_cache(maxsize=None)
+def scattered_shell(name, n, seed):
+    """float32 [n,3]: the mesh's vertices and n - len(vertices) random points on its faces -- area-weighted over the triangles,
+    uniform in each -- shuffled as a whole, all from the generator seeded with ``seed`` (an int or a tuple of ints).  Random
+    points tie far less often on a flat face than a lattice does, and any block of 256 holds points of every face."""
+    v, f = mesh(name)
+    rng = np.random.default_rng(list(seed) if isinstance(seed, tuple) else seed)
+    tri = v.astype(np.float64)[f]
+    m = n - len(v)
+    if m < 0:
+        raise ValueError("fewer points than vertices")
+    area = 0.5 * np.linalg.norm(np.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]), axis=1)
+    t = tri[rng.choice(len(tri), size=m, p=area / area.sum())]
+    a, b = rng.uniform(size=m), rng.uniform(size=m)
+    flip = a + b > 1.0
+    a, b = np.where(flip, 1.0 - a, a), np.where(flip, 1.0 - b, b)
+    p = np.concatenate([v.astype(np.float64), t[:, 0] + a[:, None] * (t[:, 1] - t[:, 0]) + b[:, None] * (t[:, 2] - t[:, 0])])
+    out = p[rng.permutation(n)].astype(np.float32)
+    out.setflags(write=False)
+    return out
+
+
+def case_shells(case):
+    """The scattered shells of the column's three bodies for one of SHELL_CASES: body k's from the generator seeded [k, n]."""
+    return [scattered_shell(name, n, (k, n)) for k, (name, n) in enumerate(zip(SCENES["column"], case))]
+
+
+def with_shell(t, points):
+    """The reference's type ``t`` with another shell (the radius follows the shell, as RigidBody.from_collision's does)."""
+    return DR.RefType(t.field, t.grid, points, t.mass, t.com, t.iinv, t.friction)
+
+
+TIE_POINTS = 600
+
+
+@functools.lru_cache(maxsize=None)
+def tie_shell():
+    """float32 [600,3]: a scattered shell of the cube without the side points a margin above the bottom face (the flat cube's
+    candidates are then its bottom points alone, all with the same phi and r.z), ordered so that no bottom point (z = -0.5) has
+    an index below 256, the lowest bottom index lies in point block 1 and further bottom points lie in block 2."""
+    p = scattered_shell("cube", 800, 5)
+    p = p[~((p[:, 2] > -0.5) & (p[:, 2] < -0.3))][:TIE_POINTS]
+    bottom, other = np.flatnonzero(p[:, 2] == -0.5), np.flatnonzero(p[:, 2] != -0.5)
+    half = len(bottom) // 2
+    out = p[np.concatenate([other[:300], bottom[:half], other[300:], bottom[half:]])].copy()
+    out.setflags(write=False)
+    return out
+
+
+def flat_cube_state(types):
+    """[1,13]: the cube flat on the plane, as test_contact_ties_empty_slots_and_a_single_body puts it."""
+    return state_of(types[:1], np.array([[0.0, 0.0, 0.5, 0, 0, 0, 1.0]]))
+
+
+CROWD_SPACING, CROWD_CENTER = 0.58, (0.0, 0.0, 1.2)
+
+
+def crowd(types):
+    """[8,13] float64 of float32 numbers: eight small cubes (side 0.6, ``types`` = [the small cube's type]) at the corners of a
+    2x2x2 lattice of spacing 0.58, so every neighbour overlaps by 0.02 and all 56 ordered pairs are in sphere range; each slightly
+    tilted and moving.  The bottom cubes' spheres end 0.39 above the plane: no plane contact."""
+    rng = np.random.default_rng(8)
+    half = 0.5 * CROWD_SPACING
+    corners = np.array([[x, y, z] for z in (-half, half) for y in (-half, half) for x in (-half, half)]) + np.asarray(CROWD_CENTER)
+    poses = np.array([np.concatenate([c, small_tilt(rng, 0.03)]) for c in corners])
+    state = state_of([types[0]] * 8, poses)
+    state[:, 7:10] = DR.f32(rng.uniform(-0.5, 0.5, (8, 3)))
+    state[:, 10:13] = DR.f32(rng.uniform(-1.0, 1.0, (8, 3)))
+    return state
+
+
+EMBEDDED_ROW = (-1, 0, -1, -1, 1, -1, -1, 2)            # the column in slots 1, 4 and 7 of eight
+FULL_ROW = (2, 0, 1, 0, 1, 2, 0, 2)                     # .. and five flyers in the other slots
+COLUMN_SLOTS, FLYER_SLOTS = (1, 4, 7), (0, 2, 3, 5, 6)
+
+
+def flyers(types, type_row=FULL_ROW, slots=FLYER_SLOTS):
+    """{slot: [13]}: bodies at rest, tens of units up and apart: 40 + 15 k above the plane and 15 k along x.  In 60 steps of free
+    fall (|g| = 500, h = 1e-3) a body drops 0.92, so each stays out of sphere range of the plane and of everything else."""
+    out = {}
+    for k, a in enumerate(slots):
+        out[a] = state_of([types[type_row[a]]], np.array([[15.0 * (k + 1), -20.0, 40.0 + 15.0 * k, 0, 0, 0, 1.0]]))[0]
+    return out
+
+
+# The guard's triggers.  A: a zero quaternion, whose normalisation divides 0 by 0 in the first step.  B: a lone body so far up and
+# so fast that x.z = 3.394e38 + k h v passes float32's largest number 3.402823e38 in the third step (index 2) and in no earlier
+# one: 3.397e38, 3.400e38 (2.8e35 below it), 3.403e38 (1.8e34 above it); |x_a - x_b|^2 overflows to +inf, which is out of sphere
+# range, so nothing is NaN before the guard.
+GUARD_STEP = {"A": 0, "B": 2}
+FAR_Z, FAR_VZ = 3.394e38, 3e38
+
+
+def far_body():
+    """[13]: trigger B's body, at rest in everything but z."""
+    s = np.zeros(13)
+    s[2], s[6], s[9] = FAR_Z, 1.0, FAR_VZ
+    return DR.f32(s)
+
+
+def guard_state(column_state, trigger):
+    """[4,13]: a world of the column's three bodies (``column_state`` [3,13]) and a fourth slot: empty for no trigger (None), with
+    a zero quaternion in body 1 for trigger A, with the far body in slot 3 for trigger B."""
+    s = np.zeros((4, 13))
+    s[3, 6] = 1.0
+    s[:3] = column_state
+    if trigger == "A":
+        s[1, 3:7] = 0.0
+    elif trigger == "B":
+        s[3] = far_body()
+    return s
+
+
+def guard_types(trigger):
+    return [0, 1, 2, 0 if trigger == "B" else -1]
+
+
 # ---- friction -------------------------------------------------------------------------------------------------------------------
-TILT = np.deg2rad(20.0)
+TILT =np.deg2rad(20.0)
 FRICTION_STEPS = 500
 FRICTION_CASES = {"sticks": 1.0, "slides": 0.2}        # the cube's friction; the plane's is 0.5: mu = 0.5 and 0.1 (tan 20 deg = 0.364)
 

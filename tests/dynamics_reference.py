@@ -301,7 +301,9 @@ def simulate(types, type_row, state0, n_steps, params, record_every=1, snapshots
             n_rows[k] = len(rows)
             if rows:
                 deepest[k] = min(r["phi"] for r in rows)
-            if not np.isfinite(new).all():
+            with np.errstate(over="ignore"):
+                finite = np.isfinite(new.astype(np.float32)).all()                # rule 7 judges the float32 state the device holds
+            if not finite:
                 status, halted = 1, True
             else:
                 state = new
