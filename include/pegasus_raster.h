@@ -1265,6 +1265,41 @@ int64_t pgr_png_max_bytes(int32_t width, int32_t height, int32_t kind);
  * ceil(log2(used)) bits.  n is 1..288, limit 1..15 with n <= 2^limit, every freq <= 2^22.  Host only. */
 int32_t pgr_png_code_lengths(const uint32_t *freq, int32_t n, int32_t limit, uint8_t *lengths);
 
+/* ---- Undistortion of COLMAP projects (pegasus_amd/undistort.py; csrc/undistort.hip.h) --------------
+ * The camera models, their inverse, the remap of images to a pinhole camera and the box pyramid, all in float64; the rule is
+ * written out at the top of csrc/undistort.hip.h.  A camera is a COLMAP model id with its parameters in COLMAP's order (host
+ * memory): 0 SIMPLE_PINHOLE, 1 PINHOLE, 2 SIMPLE_RADIAL, 3 RADIAL, 4 OPENCV, 5 OPENCV_FISHEYE, 6 FULL_OPENCV; every other id, a
+ * parameter that is not finite or a focal length of 0 is PGR_ERR_INVALID_ARGUMENT.  Pixel (x, y) has its centre at (x + 0.5,
+ * y + 0.5).
+ *
+ * pgr_undistort_points: xy double [n,2] (device) image points -> uv double [n,2] normalised points, ok uint8 [n] (may be NULL).
+ * A point the inverse does not reach is NaN, NaN with ok 0.  pgr_distort_points is the forward direction, uv -> xy.
+ *
+ * A PgrUndistortJob names a source and a destination image where they lie (device, uint8, `channels` = 1, 3 or 4 interleaved,
+ * row y starts stride bytes behind row y - 1, stride >= width * channels, sides 1..32768), the source camera and the output
+ * pinhole fx, fy, cx, cy.  pgr_undistort_images fills every destination pixel: bilinear from the source where the four taps
+ * lie inside it, 0 elsewhere.  Jobs are grouped by model and channel count, a launch takes 16 of a group.
+ * pgr_image_box_downscale reads only the images of a job: dst = factor x factor integer box means of src, (sum + f f / 2) /
+ * (f f); factor is 2, 4 or 8 and dst_width * factor <= src_width, dst_height * factor <= src_height.
+ * n = 0 / n_jobs = 0 is PGR_OK without a launch; the tables are read before the call returns. */
+typedef struct PgrUndistortJob {
+    const void *src;
+    int32_t src_width, src_height;
+    int32_t channels;
+    int32_t model;
+    int64_t src_stride;
+    void *dst;
+    int32_t dst_width, dst_height;
+    int64_t dst_stride;
+    double params[12];
+    double pinhole[4];
+} PgrUndistortJob;
+int32_t pgr_undistort_points(int32_t model, const double *params, int64_t n, const double *xy, double *uv, uint8_t *ok,
+                             void *stream);
+int32_t pgr_distort_points(int32_t model, const double *params, int64_t n, const double *uv, double *xy, void *stream);
+int32_t pgr_undistort_images(const PgrUndistortJob *jobs, int32_t n_jobs, void *stream);
+int32_t pgr_image_box_downscale(const PgrUndistortJob *jobs, int32_t n_jobs, int32_t factor, void *stream);
+
 
 #ifdef __cplusplus
 }

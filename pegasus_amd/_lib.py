@@ -237,6 +237,12 @@ PGR_PNG_SEGMENT_BYTES, PGR_PNG_SUBBLOCK = 8192, 512
 PGR_PNG_GRAY8, PGR_PNG_RGB8, PGR_PNG_GRAY16 = 0, 1, 2
 
 
+class PgrUndistortJob(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("src_width", C.c_int32), ("src_height", C.c_int32), ("channels", C.c_int32),
+                ("model", C.c_int32), ("src_stride", C.c_int64), ("dst", C.c_void_p), ("dst_width", C.c_int32),
+                ("dst_height", C.c_int32), ("dst_stride", C.c_int64), ("params", C.c_double * 12), ("pinhole", C.c_double * 4)]
+
+
 # every symbol include/pegasus_raster.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "pgr_abi_version": (C.c_int32, []),
@@ -409,6 +415,11 @@ SYMBOLS = {
                                  C.c_size_t, C.c_void_p]),
     "pgr_png_max_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "pgr_png_code_lengths": (C.c_int32, [C.POINTER(C.c_uint32), C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
+    "pgr_undistort_points": (C.c_int32, [C.c_int32, C.POINTER(C.c_double), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    "pgr_distort_points": (C.c_int32, [C.c_int32, C.POINTER(C.c_double), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pgr_undistort_images": (C.c_int32, [C.POINTER(PgrUndistortJob), C.c_int32, C.c_void_p]),
+    "pgr_image_box_downscale": (C.c_int32, [C.POINTER(PgrUndistortJob), C.c_int32, C.c_int32, C.c_void_p]),
 }
 
 _lib = None

@@ -5,7 +5,9 @@ conventions, written for this package (no plyfile / cv2: PLY through ply_io, ima
 Conventions (the ones pegasus_amd.cameras.Camera uses):
   R = qvec2rotmat(qvec)^T   (camera-to-world rotation),   T = tvec   (world-to-camera translation)
   FoVx = focal2fov(fx, width), FoVy = focal2fov(fy, height)
-Only PINHOLE and SIMPLE_PINHOLE cameras are supported: the rasterizer has no distortion model."""
+Only PINHOLE and SIMPLE_PINHOLE cameras are supported: the rasterizer has no distortion model.  pegasus_amd.undistort turns
+a project with distorted cameras into one of these; for it the readers take ``distorted=True`` (no model check) and carry the
+2D observations and the tracks, which they skip otherwise."""
 from __future__ import annotations
 
 import os
@@ -23,6 +25,8 @@ CAMERA_MODELS = {0: ("SIMPLE_PINHOLE", 3), 1: ("PINHOLE", 4), 2: ("SIMPLE_RADIAL
                  4: ("OPENCV", 8), 5: ("OPENCV_FISHEYE", 8), 6: ("FULL_OPENCV", 12), 7: ("FOV", 5),
                  8: ("SIMPLE_RADIAL_FISHEYE", 4), 9: ("RADIAL_FISHEYE", 5), 10: ("THIN_PRISM_FISHEYE", 12)}
 SUPPORTED_MODELS = ("PINHOLE", "SIMPLE_PINHOLE")
+ONE_FOCAL_MODELS = ("SIMPLE_PINHOLE", "SIMPLE_RADIAL", "RADIAL", "SIMPLE_RADIAL_FISHEYE", "RADIAL_FISHEYE")
+TWO_FOCAL_MODELS = ("PINHOLE", "OPENCV", "OPENCV_FISHEYE", "FULL_OPENCV", "FOV", "THIN_PRISM_FISHEYE")
 LLFF_HOLD = 8                                   # eval: every 8th image (sorted by name) is a test camera
 
 
@@ -48,6 +52,22 @@ class ColmapCamera:
         raise UnsupportedCameraModel(f"COLMAP camera {self.id}: model {self.model} is not supported (only "
                                      f"{' / '.join(SUPPORTED_MODELS)}: undistort the images first)")
 
+    @property
+    def distorted_focal(self):
+        """(fx, fy) of any model whose parameters start with one focal length (f, cx, cy, ...) or two (fx, fy, cx, cy, ...)"""
+        if self.model in ONE_FOCAL_MODELS:
+            return float(self.params[0]), float(self.params[0])
+        if self.model in TWO_FOCAL_MODELS:
+            return float(self.params[0]), float(self.params[1])
+        raise UnsupportedCameraModel(f"COLMAP camera {self.id}: model {self.model} has no focal lengths this package knows")
+
+    @property
+    def principal_point(self):
+        """(cx, cy) of the models ``distorted_focal`` knows"""
+        first = 1 if self.model in ONE_FOCAL_MODELS else 2
+        self.distorted_focal
+        return float(self.params[first]), float(self.params[first + 1])
+
 
 @dataclass
 class ColmapImage:
@@ -56,6 +76,8 @@ class ColmapImage:
     tvec: np.ndarray
     camera_id: int
     name: str
+    xys: np.ndarray = None                      # [n,2] float64 2D observations (readers: points2D=True)
+    point3D_ids: np.ndarray = None              # [n] int64, -1 for an observation without a 3D point
 
 
 def qvec2rotmat(q):
@@ -100,16 +122,18 @@ def _lines(path):
 
 
 # ---- text -----------------------------------------------------------------------------------------------------------------
-def read_cameras_text(path) -> dict:
+def read_cameras_text(path, distorted=False) -> dict:
+    """``distorted``: any camera model is read (pegasus_amd.undistort); otherwise a distorted one raises."""
     cams = {}
     for line in _lines(path):
         tok = line.split()
         cam = ColmapCamera(int(tok[0]), tok[1], int(tok[2]), int(tok[3]), np.array([float(v) for v in tok[4:]]))
-        cams[cam.id] = _check_model(cam)
+        cams[cam.id] = cam if distorted else _check_model(cam)
     return cams
 
 
-def read_images_text(path) -> dict:
+def read_images_text(path, points2D=False) -> dict:
+    """``points2D``: every image carries its observations (xys, point3D_ids)."""
     imgs = {}
     raw = [ln.strip() for ln in Path(path).read_text().splitlines() if not ln.strip().startswith("#")]
     # two lines per image: the pose line and the (possibly empty) 2D point line
@@ -121,19 +145,29 @@ def read_images_text(path) -> dict:
         tok = raw[i].split()
         img = ColmapImage(int(tok[0]), np.array([float(v) for v in tok[1:5]]), np.array([float(v) for v in tok[5:8]]),
                           int(tok[8]), " ".join(tok[9:]))
+        if points2D:
+            obs = raw[i + 1].split() if i + 1 < len(raw) else []
+            img.xys = np.array([float(v) for k, v in enumerate(obs) if k % 3 != 2], dtype=np.float64).reshape(-1, 2)
+            img.point3D_ids = np.array([int(v) for v in obs[2::3]], dtype=np.int64)
         imgs[img.id] = img
         i += 2
     return imgs
 
 
-def read_points3D_text(path):
-    """(xyz [N,3] float64, rgb [N,3] uint8)"""
-    xyz, rgb = [], []
+def read_points3D_text(path, tracks=False):
+    """(xyz [N,3] float64, rgb [N,3] uint8); with ``tracks`` also errors [N] float64, the tracks (a list of int32 [L,2]
+    arrays of (image id, index of the 2D point)) and the point ids [N] int64."""
+    xyz, rgb, err, trk, ids = [], [], [], [], []
     for line in _lines(path):
         tok = line.split()
         xyz.append([float(v) for v in tok[1:4]])
         rgb.append([int(v) for v in tok[4:7]])
-    return np.array(xyz, dtype=np.float64).reshape(-1, 3), np.array(rgb, dtype=np.uint8).reshape(-1, 3)
+        if tracks:
+            ids.append(int(tok[0]))
+            err.append(float(tok[7]))
+            trk.append(np.array([int(v) for v in tok[8:]], dtype=np.int32).reshape(-1, 2))
+    out = np.array(xyz, dtype=np.float64).reshape(-1, 3), np.array(rgb, dtype=np.uint8).reshape(-1, 3)
+    return out + (np.array(err, dtype=np.float64), trk, np.array(ids, dtype=np.int64)) if tracks else out
 
 
 # ---- binary (little endian) -----------------------------------------------------------------------------------------------
@@ -153,7 +187,7 @@ class _Reader:
         return s
 
 
-def read_cameras_binary(path) -> dict:
+def read_cameras_binary(path, distorted=False) -> dict:
     r, cams = _Reader(path), {}
     (n,) = r.read("Q")
     for _ in range(n):
@@ -162,43 +196,64 @@ def read_cameras_binary(path) -> dict:
             raise UnsupportedCameraModel(f"COLMAP camera {cam_id}: unknown model id {model_id}")
         name, n_params = CAMERA_MODELS[model_id]
         params = np.array(r.read("d" * n_params))
-        cams[cam_id] = _check_model(ColmapCamera(cam_id, name, int(w), int(h), params))
+        cam = ColmapCamera(cam_id, name, int(w), int(h), params)
+        cams[cam_id] = cam if distorted else _check_model(cam)
     return cams
 
 
-def read_images_binary(path) -> dict:
+def read_images_binary(path, points2D=False) -> dict:
     r, imgs = _Reader(path), {}
     (n,) = r.read("Q")
     for _ in range(n):
         vals = r.read("idddddddi")
         name = r.cstring()
         (n2d,) = r.read("Q")
-        r.off += n2d * 24                        # (x, y, point3D_id) per 2D point: not needed here
-        imgs[vals[0]] = ColmapImage(vals[0], np.array(vals[1:5]), np.array(vals[5:8]), vals[8], name)
+        img = ColmapImage(vals[0], np.array(vals[1:5]), np.array(vals[5:8]), vals[8], name)
+        if points2D:                             # (x, y, point3D_id) per 2D point, 24 bytes
+            obs = np.frombuffer(r.data, dtype=np.dtype([("xy", "<f8", 2), ("id", "<i8")]), count=n2d, offset=r.off)
+            img.xys, img.point3D_ids = obs["xy"].astype(np.float64), obs["id"].astype(np.int64)
+        r.off += n2d * 24
+        imgs[vals[0]] = img
     return imgs
 
 
-def read_points3D_binary(path):
+def read_points3D_binary(path, tracks=False):
+    """As read_points3D_text."""
     r = _Reader(path)
     (n,) = r.read("Q")
     xyz, rgb = np.empty((n, 3)), np.empty((n, 3), dtype=np.uint8)
+    err, trk, ids = np.empty(n), [], np.empty(n, dtype=np.int64)
     for i in range(n):
         vals = r.read("QdddBBBd")
         xyz[i], rgb[i] = vals[1:4], vals[4:7]
+        ids[i], err[i] = vals[0], vals[7]
         (track,) = r.read("Q")
+        if tracks:
+            trk.append(np.frombuffer(r.data, dtype="<i4", count=2 * track, offset=r.off).astype(np.int32).reshape(-1, 2))
         r.off += track * 8
-    return xyz, rgb
+    return (xyz, rgb, err, trk, ids) if tracks else (xyz, rgb)
 
 
 # ---- writers (test fixtures, synthetic datasets) --------------------------------------------------------------------------
 _MODEL_IDS = {name: mid for mid, (name, _) in CAMERA_MODELS.items()}
 
 
-def write_colmap_model(sparse_dir, cameras, images, xyz, rgb, binary=True) -> None:
+def write_colmap_model(sparse_dir, cameras, images, xyz, rgb, binary=True, errors=None, tracks=None, point_ids=None) -> None:
     """Writes cameras / images / points3D (.bin or .txt).  cameras: {id: ColmapCamera}; images: {id: ColmapImage};
-    xyz [N,3], rgb [N,3] uint8.  2D points and tracks are written empty."""
+    xyz [N,3], rgb [N,3] uint8.  An image that carries observations (xys, point3D_ids) has them written, one without has
+    none; ``errors`` [N], ``tracks`` (a list of [L,2] (image id, 2D point index) arrays) and ``point_ids`` [N] are what
+    read_points3D_*(tracks=True) returns and default to error 0, empty tracks and the ids 1..N."""
     d = Path(sparse_dir)
     d.mkdir(parents=True, exist_ok=True)
+    n = len(xyz)
+    errors = [0.0] * n if errors is None else [float(e) for e in errors]
+    tracks = [np.zeros((0, 2), np.int32)] * n if tracks is None else [np.asarray(t, dtype=np.int32).reshape(-1, 2) for t in tracks]
+    point_ids = list(range(1, n + 1)) if point_ids is None else [int(i) for i in point_ids]
+
+    def observations(im):
+        if im.xys is None:
+            return np.zeros((0, 2)), np.zeros(0, np.int64)
+        return np.asarray(im.xys, dtype=np.float64).reshape(-1, 2), np.asarray(im.point3D_ids, dtype=np.int64).reshape(-1)
     if binary:
         b = struct.pack("<Q", len(cameras))
         for c in cameras.values():
@@ -208,11 +263,15 @@ def write_colmap_model(sparse_dir, cameras, images, xyz, rgb, binary=True) -> No
         b = struct.pack("<Q", len(images))
         for im in images.values():
             b += struct.pack("<idddddddi", im.id, *map(float, im.qvec), *map(float, im.tvec), im.camera_id)
-            b += im.name.encode("utf-8") + b"\x00" + struct.pack("<Q", 0)
+            xys, ids = observations(im)
+            obs = np.zeros(len(ids), dtype=np.dtype([("xy", "<f8", 2), ("id", "<i8")]))
+            obs["xy"], obs["id"] = xys, ids
+            b += im.name.encode("utf-8") + b"\x00" + struct.pack("<Q", len(ids)) + obs.tobytes()
         (d / "images.bin").write_bytes(b)
         b = struct.pack("<Q", len(xyz))
         for i, (p, c) in enumerate(zip(np.asarray(xyz, dtype=np.float64), np.asarray(rgb, dtype=np.uint8))):
-            b += struct.pack("<QdddBBBdQ", i + 1, *map(float, p), *map(int, c), 0.0, 0)
+            b += struct.pack("<QdddBBBdQ", point_ids[i], *map(float, p), *map(int, c), errors[i], len(tracks[i]))
+            b += tracks[i].astype("<i4").tobytes()
         (d / "points3D.bin").write_bytes(b)
     else:
         (d / "cameras.txt").write_text("# Camera list\n" + "".join(
@@ -220,9 +279,11 @@ def write_colmap_model(sparse_dir, cameras, images, xyz, rgb, binary=True) -> No
             for c in cameras.values()))
         (d / "images.txt").write_text("# Image list\n" + "".join(
             f"{im.id} {' '.join(repr(float(v)) for v in im.qvec)} {' '.join(repr(float(v)) for v in im.tvec)} "
-            f"{im.camera_id} {im.name}\n\n" for im in images.values()))
+            f"{im.camera_id} {im.name}\n" + " ".join(f"{float(x)!r} {float(y)!r} {int(k)}" for (x, y), k in zip(*observations(im)))
+            + "\n" for im in images.values()))
         (d / "points3D.txt").write_text("# 3D point list\n" + "".join(
-            f"{i + 1} {' '.join(repr(float(v)) for v in p)} {' '.join(str(int(v)) for v in c)} 0.0\n"
+            f"{point_ids[i]} {' '.join(repr(float(v)) for v in p)} {' '.join(str(int(v)) for v in c)} {errors[i]!r}"
+            f"{''.join(f' {int(a)} {int(b)}' for a, b in tracks[i])}\n"
             for i, (p, c) in enumerate(zip(np.asarray(xyz, dtype=np.float64), np.asarray(rgb, dtype=np.uint8)))))
 
 
@@ -232,13 +293,13 @@ def _sparse_dir(source_path) -> Path:
     return d if d.is_dir() else Path(source_path) / "sparse"
 
 
-def read_model(source_path):
-    """(cameras, images) of ``source_path``'s sparse model, binary preferred."""
+def read_model(source_path, distorted=False, points2D=False):
+    """(cameras, images) of ``source_path``'s sparse model, binary preferred.  ``distorted`` / ``points2D``: as the readers."""
     d = _sparse_dir(source_path)
     if (d / "images.bin").exists() and (d / "cameras.bin").exists():
-        return read_cameras_binary(d / "cameras.bin"), read_images_binary(d / "images.bin")
+        return read_cameras_binary(d / "cameras.bin", distorted), read_images_binary(d / "images.bin", points2D)
     if (d / "images.txt").exists() and (d / "cameras.txt").exists():
-        return read_cameras_text(d / "cameras.txt"), read_images_text(d / "images.txt")
+        return read_cameras_text(d / "cameras.txt", distorted), read_images_text(d / "images.txt", points2D)
     raise FileNotFoundError(f"no COLMAP model (cameras / images .bin or .txt) under {d}")
 
 

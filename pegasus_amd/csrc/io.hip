@@ -1,11 +1,15 @@
-// io.hip -- host side of the file-format entries of libpegasus_raster.so: PNG files of device images.
-// Owns its kernel header: no other translation unit includes it (DESIGN.md "Source layout").
+// io.hip -- host side of the image-file entries of libpegasus_raster.so: PNG files of device images, undistortion of a
+// COLMAP project's images and points.
+// Owns its kernel headers: no other translation unit includes them (DESIGN.md "Source layout").
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "host_common.h"
 #include "png.hip.h"
+#include "undistort.hip.h"
 
 using namespace pgr;
 
@@ -119,4 +123,171 @@ int32_t pgr_png_emit(const PgrPngJob* jobs, int32_t n_jobs, const int64_t* offse
         ws_at<const PngFileInfo>(workspace, L.files), ws_at<const uint8_t>(workspace, L.slots),
         reinterpret_cast<const long long*>(offsets), (long long)total, files);
     return launch_status("png_emit launch");
+}
+
+// ---- undistortion (undistort.hip.h) ---------------------------------------------------------------------------------------------
+namespace {
+constexpr int32_t UND_MAX_SIDE = 32768;
+
+// a COLMAP model id and its parameters in COLMAP's order as the kernels' camera; false for a model outside the rule or
+// focal lengths that do not divide
+bool und_camera(int32_t model, const double* p, UndCam& c, int& kind) {
+    if (!p) return false;
+    c = UndCam{};
+    int n_k = 0, first_k = 0;
+    switch (model) {
+        case 0: kind = UND_PINHOLE; c.fx = c.fy = p[0]; c.cx = p[1]; c.cy = p[2]; break;
+        case 1: kind = UND_PINHOLE; c.fx = p[0]; c.fy = p[1]; c.cx = p[2]; c.cy = p[3]; break;
+        case 2: kind = UND_SIMPLE_RADIAL; c.fx = c.fy = p[0]; c.cx = p[1]; c.cy = p[2]; first_k = 3; n_k = 1; break;
+        case 3: kind = UND_RADIAL; c.fx = c.fy = p[0]; c.cx = p[1]; c.cy = p[2]; first_k = 3; n_k = 2; break;
+        case 4: kind = UND_OPENCV; c.fx = p[0]; c.fy = p[1]; c.cx = p[2]; c.cy = p[3]; first_k = 4; n_k = 4; break;
+        case 5: kind = UND_FISHEYE; c.fx = p[0]; c.fy = p[1]; c.cx = p[2]; c.cy = p[3]; first_k = 4; n_k = 4; break;
+        case 6: kind = UND_FULL_OPENCV; c.fx = p[0]; c.fy = p[1]; c.cx = p[2]; c.cy = p[3]; first_k = 4; n_k = 8; break;
+        default: return false;
+    }
+    for (int i = 0; i < n_k; ++i) c.k[i] = p[first_k + i];
+    for (int i = 0; i < n_k; ++i)
+        if (!std::isfinite(c.k[i])) return false;
+    return std::isfinite(c.fx) && std::isfinite(c.fy) && c.fx != 0.0 && c.fy != 0.0 && std::isfinite(c.cx) && std::isfinite(c.cy);
+}
+
+int und_channel_slot(int32_t channels) { return channels == 1 ? 0 : channels == 3 ? 1 : channels == 4 ? 2 : -1; }
+
+// what both image entries ask of a job: two images that lie inside their strides
+bool und_images_ok(const PgrUndistortJob& j) {
+    const int32_t c = j.channels;
+    return j.src && j.dst && und_channel_slot(c) >= 0 && j.src_width >= 1 && j.src_width <= UND_MAX_SIDE && j.src_height >= 1 &&
+           j.src_height <= UND_MAX_SIDE && j.dst_width >= 1 && j.dst_width <= UND_MAX_SIDE && j.dst_height >= 1 &&
+           j.dst_height <= UND_MAX_SIDE && j.src_stride >= (int64_t)j.src_width * c && j.dst_stride >= (int64_t)j.dst_width * c;
+}
+
+void und_job_images(const PgrUndistortJob& j, UndJobDev& d, uint32_t& blocks) {
+    d.src = static_cast<const uint8_t*>(j.src); d.dst = static_cast<uint8_t*>(j.dst);
+    d.src_stride = j.src_stride; d.dst_stride = j.dst_stride;
+    d.sw = j.src_width; d.sh = j.src_height; d.dw = j.dst_width; d.dh = j.dst_height;
+    d.block0 = blocks;
+    d.blocks_x = (uint32_t)((j.dst_width + UND_BLOCK_W - 1) / UND_BLOCK_W);
+    blocks += d.blocks_x * (uint32_t)((j.dst_height + UND_ROWS - 1) / UND_ROWS);
+}
+
+using UndImageKernel = void (*)(const UndJobTable);
+template <int M> constexpr UndImageKernel und_remap_row(int slot) {
+    return slot == 0 ? und_remap_kernel<M, 1> : slot == 1 ? und_remap_kernel<M, 3> : und_remap_kernel<M, 4>;
+}
+UndImageKernel und_remap_fn(int kind, int slot) {
+    switch (kind) {
+        case UND_PINHOLE: return und_remap_row<UND_PINHOLE>(slot);
+        case UND_SIMPLE_RADIAL: return und_remap_row<UND_SIMPLE_RADIAL>(slot);
+        case UND_RADIAL: return und_remap_row<UND_RADIAL>(slot);
+        case UND_OPENCV: return und_remap_row<UND_OPENCV>(slot);
+        case UND_FULL_OPENCV: return und_remap_row<UND_FULL_OPENCV>(slot);
+        default: return und_remap_row<UND_FISHEYE>(slot);
+    }
+}
+
+// the launches of one group of jobs (those of `pick`): a table of at most UND_JOBS_PER_LAUNCH jobs per launch
+template <typename Pick, typename Fill>
+void und_launch_group(UndImageKernel fn, int32_t n_jobs, const PgrUndistortJob* jobs, int32_t factor, Pick pick, Fill fill,
+                      hipStream_t stream) {
+    UndJobTable T{};
+    T.factor = factor;
+    uint32_t blocks = 0;
+    for (int32_t k = 0; k <= n_jobs; ++k) {
+        if (k < n_jobs && pick(k)) {
+            UndJobDev& d = T.job[T.count++];
+            und_job_images(jobs[k], d, blocks);
+            fill(k, d);
+        }
+        if (T.count == UND_JOBS_PER_LAUNCH || (k == n_jobs && T.count > 0)) {
+            fn<<<blocks, UND_THREADS, 0, stream>>>(T);
+            T.count = 0;
+            blocks = 0;
+        }
+    }
+}
+}  // namespace
+
+int32_t pgr_undistort_points(int32_t model, const double* params, int64_t n, const double* xy, double* uv, uint8_t* ok,
+                             void* stream_v) {
+    UndCam c;
+    int kind = 0;
+    if (n < 0 || !und_camera(model, params, c, kind) || (n > 0 && (!xy || !uv)) || (n + UND_THREADS - 1) / UND_THREADS > MAX_GRID_BLOCKS)
+        return PGR_ERR_INVALID_ARGUMENT;
+    if (n == 0) return PGR_OK;
+    const unsigned blocks = (unsigned)((n + UND_THREADS - 1) / UND_THREADS);
+    hipStream_t stream = as_stream(stream_v);
+    switch (kind) {
+        case UND_PINHOLE: und_points_kernel<UND_PINHOLE><<<blocks, UND_THREADS, 0, stream>>>(c, n, xy, uv, ok); break;
+        case UND_SIMPLE_RADIAL: und_points_kernel<UND_SIMPLE_RADIAL><<<blocks, UND_THREADS, 0, stream>>>(c, n, xy, uv, ok); break;
+        case UND_RADIAL: und_points_kernel<UND_RADIAL><<<blocks, UND_THREADS, 0, stream>>>(c, n, xy, uv, ok); break;
+        case UND_OPENCV: und_points_kernel<UND_OPENCV><<<blocks, UND_THREADS, 0, stream>>>(c, n, xy, uv, ok); break;
+        case UND_FULL_OPENCV: und_points_kernel<UND_FULL_OPENCV><<<blocks, UND_THREADS, 0, stream>>>(c, n, xy, uv, ok); break;
+        default: und_points_kernel<UND_FISHEYE><<<blocks, UND_THREADS, 0, stream>>>(c, n, xy, uv, ok); break;
+    }
+    return launch_status("undistort_points launch");
+}
+
+int32_t pgr_distort_points(int32_t model, const double* params, int64_t n, const double* uv, double* xy, void* stream_v) {
+    UndCam c;
+    int kind = 0;
+    if (n < 0 || !und_camera(model, params, c, kind) || (n > 0 && (!uv || !xy)) || (n + UND_THREADS - 1) / UND_THREADS > MAX_GRID_BLOCKS)
+        return PGR_ERR_INVALID_ARGUMENT;
+    if (n == 0) return PGR_OK;
+    const unsigned blocks = (unsigned)((n + UND_THREADS - 1) / UND_THREADS);
+    hipStream_t stream = as_stream(stream_v);
+    switch (kind) {
+        case UND_PINHOLE: und_distort_kernel<UND_PINHOLE><<<blocks, UND_THREADS, 0, stream>>>(c, n, uv, xy); break;
+        case UND_SIMPLE_RADIAL: und_distort_kernel<UND_SIMPLE_RADIAL><<<blocks, UND_THREADS, 0, stream>>>(c, n, uv, xy); break;
+        case UND_RADIAL: und_distort_kernel<UND_RADIAL><<<blocks, UND_THREADS, 0, stream>>>(c, n, uv, xy); break;
+        case UND_OPENCV: und_distort_kernel<UND_OPENCV><<<blocks, UND_THREADS, 0, stream>>>(c, n, uv, xy); break;
+        case UND_FULL_OPENCV: und_distort_kernel<UND_FULL_OPENCV><<<blocks, UND_THREADS, 0, stream>>>(c, n, uv, xy); break;
+        default: und_distort_kernel<UND_FISHEYE><<<blocks, UND_THREADS, 0, stream>>>(c, n, uv, xy); break;
+    }
+    return launch_status("distort_points launch");
+}
+
+int32_t pgr_undistort_images(const PgrUndistortJob* jobs, int32_t n_jobs, void* stream_v) {
+    if (n_jobs < 0 || (n_jobs > 0 && !jobs)) return PGR_ERR_INVALID_ARGUMENT;
+    std::vector<UndCam> cams((size_t)n_jobs);
+    std::vector<int> group((size_t)n_jobs);                   // model kind * 3 + channel slot
+    bool present[UND_MODELS * 3] = {};
+    for (int32_t k = 0; k < n_jobs; ++k) {
+        const PgrUndistortJob& j = jobs[k];
+        int kind = 0;
+        if (!und_images_ok(j) || !und_camera(j.model, j.params, cams[(size_t)k], kind)) return PGR_ERR_INVALID_ARGUMENT;
+        for (int i = 0; i < 4; ++i)
+            if (!std::isfinite(j.pinhole[i])) return PGR_ERR_INVALID_ARGUMENT;
+        if (j.pinhole[0] == 0.0 || j.pinhole[1] == 0.0) return PGR_ERR_INVALID_ARGUMENT;
+        group[(size_t)k] = kind * 3 + und_channel_slot(j.channels);
+        present[group[(size_t)k]] = true;
+    }
+    hipStream_t stream = as_stream(stream_v);
+    for (int g = 0; g < UND_MODELS * 3; ++g) {
+        if (!present[g]) continue;
+        und_launch_group(und_remap_fn(g / 3, g % 3), n_jobs, jobs, 0, [&](int32_t k) { return group[(size_t)k] == g; },
+                         [&](int32_t k, UndJobDev& d) {
+                             d.cam = cams[(size_t)k];
+                             d.pfx = jobs[k].pinhole[0]; d.pfy = jobs[k].pinhole[1]; d.pcx = jobs[k].pinhole[2]; d.pcy = jobs[k].pinhole[3];
+                         }, stream);
+    }
+    return n_jobs == 0 ? PGR_OK : launch_status("undistort_images launch");
+}
+
+int32_t pgr_image_box_downscale(const PgrUndistortJob* jobs, int32_t n_jobs, int32_t factor, void* stream_v) {
+    if (n_jobs < 0 || (n_jobs > 0 && !jobs) || (factor != 2 && factor != 4 && factor != 8)) return PGR_ERR_INVALID_ARGUMENT;
+    bool present[3] = {};
+    for (int32_t k = 0; k < n_jobs; ++k) {
+        const PgrUndistortJob& j = jobs[k];
+        if (!und_images_ok(j) || (int64_t)j.dst_width * factor > j.src_width || (int64_t)j.dst_height * factor > j.src_height)
+            return PGR_ERR_INVALID_ARGUMENT;
+        present[und_channel_slot(j.channels)] = true;
+    }
+    hipStream_t stream = as_stream(stream_v);
+    const UndImageKernel fns[3] = {und_box_kernel<1>, und_box_kernel<3>, und_box_kernel<4>};
+    for (int s = 0; s < 3; ++s) {
+        if (!present[s]) continue;
+        und_launch_group(fns[s], n_jobs, jobs, factor, [&](int32_t k) { return und_channel_slot(jobs[k].channels) == s; },
+                         [](int32_t, UndJobDev&) {}, stream);
+    }
+    return n_jobs == 0 ? PGR_OK : launch_status("image_box_downscale launch");
 }
