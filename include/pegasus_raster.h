@@ -1265,6 +1265,50 @@ int64_t pgr_png_max_bytes(int32_t width, int32_t height, int32_t kind);
  * ceil(log2(used)) bits.  n is 1..288, limit 1..15 with n <= 2^limit, every freq <= 2^22.  Host only. */
 int32_t pgr_png_code_lengths(const uint32_t *freq, int32_t n, int32_t limit, uint8_t *lengths);
 
+/* ---- JPEG files of device images (pegasus_amd/jpeg.py; csrc/jpeg.hip.h) ----------------------------
+ * Baseline sequential JPEG (8-bit, Huffman, one interleaved scan) of a batch of images that lie in device memory: SOI, APP0
+ * JFIF 1.01, DQT, SOF0, DHT, DRI, SOS, entropy data, EOI.  Gray images have one component; RGB images become full-range YCbCr
+ * at 4:4:4 or 4:2:0.  Quantisation tables follow the IJG rule on the Annex K tables (pgr_jpeg_quant_tables), the Huffman
+ * tables are built per file on the device from the file's own symbol counts with the builder behind pgr_png_code_lengths
+ * (limit 16), restart intervals are PGR_JPEG_RESTART_MCUS MCUs.  The arithmetic is integer throughout and written out at the
+ * top of csrc/jpeg.hip.h: two runs give equal bytes, and tests/jpeg_reference.py restates it in NumPy.
+ *
+ * A job names one image where it lies, as a PgrPngJob does: kind PGR_JPEG_GRAY8 (pixel_stride >= 1) or PGR_JPEG_RGB8 (three
+ * adjacent bytes R, G, B; pixel_stride >= 3), row_stride >= (width - 1) * pixel_stride + that, width and height 1..16384,
+ * quality 1..100, subsampling PGR_JPEG_444 or PGR_JPEG_420 (gray: PGR_JPEG_444 only).
+ *
+ * Two calls with PNG's contract.  pgr_jpeg_encode transforms, counts, builds the tables and sizes every interval into
+ * `workspace` (pgr_jpeg_workspace_bytes: two bytes a coefficient and small records; 0 for n_jobs <= 0 or a job outside the
+ * domain; device memory, 16-byte aligned) and writes sizes int64 [n_jobs] (device).  The caller forms offsets int64 [n_jobs + 1]
+ * (device), their exclusive sum, and calls pgr_jpeg_emit with the SAME jobs and workspace: file k goes to files[offsets[k] ..
+ * offsets[k+1]).  capacity < total is refused on the host and no store leaves files[offsets[k] .. min(offsets[k+1], total))
+ * whatever the device-side offsets hold.  Every misuse is PGR_ERR_INVALID_ARGUMENT before any launch. */
+#define PGR_JPEG_RESTART_MCUS 16     /* MCUs per restart interval (one workgroup), whatever the width */
+#define PGR_JPEG_GRAY8 0
+#define PGR_JPEG_RGB8 1
+#define PGR_JPEG_444 0
+#define PGR_JPEG_420 1
+typedef struct PgrJpegJob {
+    const void *pixels;
+    int32_t width, height;
+    int32_t kind;
+    int64_t row_stride;
+    int32_t pixel_stride;
+    int32_t quality;
+    int32_t subsampling;
+} PgrJpegJob;
+size_t pgr_jpeg_workspace_bytes(int32_t n_jobs, const PgrJpegJob *jobs);
+int32_t pgr_jpeg_encode(const PgrJpegJob *jobs, int32_t n_jobs, int64_t *sizes, void *workspace, size_t workspace_bytes,
+                        void *stream);
+int32_t pgr_jpeg_emit(const PgrJpegJob *jobs, int32_t n_jobs, const int64_t *offsets, int64_t total, uint8_t *files,
+                      int64_t capacity, const void *workspace, size_t workspace_bytes, void *stream);
+/* What no file of that shape exceeds: the longest header (330 bytes gray, 613 colour), 418 bytes a block (1665 bits, every
+ * byte stuffed) and 2 bytes a restart interval; 0 outside the domain.  Host only. */
+int64_t pgr_jpeg_max_bytes(int32_t width, int32_t height, int32_t kind, int32_t subsampling);
+/* The IJG rule: s = 5000 / q below 50, else 200 - 2 q; Q = clamp((base * s + 50) / 100, 1, 255), integer division, on the
+ * Annex K tables.  lum and chroma are uint8 [64] in natural (row-major) order.  Host only. */
+int32_t pgr_jpeg_quant_tables(int32_t quality, uint8_t *lum, uint8_t *chroma);
+
 /* ---- Undistortion of COLMAP projects (pegasus_amd/undistort.py; csrc/undistort.hip.h) --------------
  * The camera models, their inverse, the remap of images to a pinhole camera and the box pyramid, all in float64; the rule is
  * written out at the top of csrc/undistort.hip.h.  A camera is a COLMAP model id with its parameters in COLMAP's order (host

@@ -237,6 +237,17 @@ PGR_PNG_SEGMENT_BYTES, PGR_PNG_SUBBLOCK = 8192, 512
 PGR_PNG_GRAY8, PGR_PNG_RGB8, PGR_PNG_GRAY16 = 0, 1, 2
 
 
+class PgrJpegJob(C.Structure):
+    _fields_ = [("pixels", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("kind", C.c_int32),
+                ("row_stride", C.c_int64), ("pixel_stride", C.c_int32), ("quality", C.c_int32), ("subsampling", C.c_int32)]
+
+
+# include/pegasus_raster.h: the MCUs of one restart interval, the image kinds, the chroma subsamplings
+PGR_JPEG_RESTART_MCUS = 16
+PGR_JPEG_GRAY8, PGR_JPEG_RGB8 = 0, 1
+PGR_JPEG_444, PGR_JPEG_420 = 0, 1
+
+
 class PgrUndistortJob(C.Structure):
     _fields_ = [("src", C.c_void_p), ("src_width", C.c_int32), ("src_height", C.c_int32), ("channels", C.c_int32),
                 ("model", C.c_int32), ("src_stride", C.c_int64), ("dst", C.c_void_p), ("dst_width", C.c_int32),
@@ -415,6 +426,12 @@ SYMBOLS = {
                                  C.c_size_t, C.c_void_p]),
     "pgr_png_max_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "pgr_png_code_lengths": (C.c_int32, [C.POINTER(C.c_uint32), C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
+    "pgr_jpeg_workspace_bytes": (C.c_size_t, [C.c_int32, C.POINTER(PgrJpegJob)]),
+    "pgr_jpeg_encode": (C.c_int32, [C.POINTER(PgrJpegJob), C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pgr_jpeg_emit": (C.c_int32, [C.POINTER(PgrJpegJob), C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                  C.c_size_t, C.c_void_p]),
+    "pgr_jpeg_max_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "pgr_jpeg_quant_tables": (C.c_int32, [C.c_int32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     "pgr_undistort_points": (C.c_int32, [C.c_int32, C.POINTER(C.c_double), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
     "pgr_distort_points": (C.c_int32, [C.c_int32, C.POINTER(C.c_double), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),

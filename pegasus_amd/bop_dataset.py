@@ -29,12 +29,13 @@ import numpy as np
 
 SCENE_GT, SCENE_CAMERA, SCENE_GT_INFO, MODELS_INFO = "scene_gt.json", "scene_camera.json", "scene_gt_info.json", "models_info.json"
 IMAGE_KINDS = ("rgb", "depth", "mask_visib", "mask", "sem_mask")
+JPEG_EXTENSIONS = (".jpg", ".jpeg")
 
 
 # ---- names and discovery ----------------------------------------------------------------------------------------------
-def image_name(i, k=None) -> str:
-    """The PNG of frame ``i``; with ``k`` the mask of its k-th entry."""
-    return f"{int(i):06d}.png" if k is None else f"{int(i):06d}_{int(k):06d}.png"
+def image_name(i, k=None, ext: str = "png") -> str:
+    """The PNG of frame ``i``; with ``k`` the mask of its k-th entry.  ``ext``: "jpg" for the colour image of a JPEG scene."""
+    return f"{int(i):06d}.{ext}" if k is None else f"{int(i):06d}_{int(k):06d}.{ext}"
 
 
 def scene_name(scene_id) -> str:
@@ -95,24 +96,37 @@ class BopScene:
             (self.path / kind).mkdir(parents=True, exist_ok=True)
 
     def image_path(self, kind: str, i, k=None) -> Path:
-        """rgb/, depth/ or sem_mask/ of frame ``i``; with ``k``, mask/ or mask_visib/ of its k-th entry."""
-        return self.path / kind / image_name(i, k)
+        """rgb/, depth/ or sem_mask/ of frame ``i``; with ``k``, mask/ or mask_visib/ of its k-th entry.  The colour image of
+        a scene that stores rgb/ as JPEG (BOP's train_pbr splits): the .png when it exists, else an existing .jpg / .jpeg,
+        else the .png path."""
+        png = self.path / kind / image_name(i, k)
+        if kind == "rgb" and k is None and not png.exists():
+            for ext in JPEG_EXTENSIONS:
+                if (jpg := png.with_suffix(ext)).exists():
+                    return jpg
+        return png
 
     def read_png(self, kind: str, i, k=None) -> np.ndarray:
         return decode_png(self.image_path(kind, i, k).read_bytes())
 
+    def read_image(self, kind: str, i, k=None) -> np.ndarray:
+        """``read_png`` that also opens the JPEG of a scene whose rgb/ is stored as JPEG."""
+        return read_image(self.image_path(kind, i, k))
+
     def image_size(self, i):
-        """(W, H) of frame ``i`` from the header of its rgb PNG, else of its first visible mask, else (0, 0)."""
+        """(W, H) of frame ``i`` from the header of its rgb PNG or JPEG, else of its first visible mask, else (0, 0)."""
         return _first_size([self.image_path("rgb", i)] + sorted((self.path / "mask_visib").glob(f"{int(i):06d}_*.png"))) or (0, 0)
 
     def first_image_size(self):
-        """(W, H) of the scene's first rgb (else depth) PNG; None when it has neither."""
-        return _first_size(p for kind in ("rgb", "depth") for p in sorted((self.path / kind).glob("*.png")))
+        """(W, H) of the scene's first rgb (else depth) PNG or JPEG; None when it has neither."""
+        return _first_size(p for kind in ("rgb", "depth") for p in sorted((self.path / kind).glob("*"))
+                           if p.suffix in (".png",) + JPEG_EXTENSIONS)
 
 
 def _first_size(files):
-    """png_size of the first of ``files`` that exists and is a PNG, else None."""
-    return next((s for p in files if p.exists() and (s := png_size(p)) is not None), None)
+    """The size of the first of ``files`` that exists and is a PNG or a JPEG, else None."""
+    return next((s for p in files if p.exists() and
+                 (s := jpeg_size(p) if p.suffix in JPEG_EXTENSIONS else png_size(p)) is not None), None)
 
 
 # ---- record fields ----------------------------------------------------------------------------------------------------
@@ -197,3 +211,40 @@ def png_size(path):
     """(W, H) from the IHDR of a PNG file; None when its first chunk is not one."""
     head = Path(path).read_bytes()[:24]
     return struct.unpack(">II", head[16:24]) if head[12:16] == b"IHDR" else None
+
+
+# ---- JPEG -------------------------------------------------------------------------------------------------------------
+def jpeg_size(path):
+    """(W, H) from the SOF0 / SOF2 segment of a JPEG file, without decoding; None when the file has none."""
+    data = Path(path).read_bytes()
+    if data[:2] != b"\xff\xd8":
+        return None
+    pos = 2
+    while pos + 4 <= len(data) and data[pos] == 0xFF:
+        marker = data[pos + 1]
+        if marker == 0xFF:                                   # a fill byte
+            pos += 1
+            continue
+        n = struct.unpack(">H", data[pos + 2:pos + 4])[0]
+        if marker in (0xC0, 0xC2) and pos + 9 <= len(data):
+            h, w = struct.unpack(">HH", data[pos + 5:pos + 9])
+            return w, h
+        if marker == 0xDA:                                   # the scan: no frame header in front of it
+            return None
+        pos += 2 + n
+    return None
+
+
+def read_image(path) -> np.ndarray:
+    """uint8 [H,W] / [H,W,3] or uint16 [H,W] of a PNG (``decode_png``) or a JPEG (PIL, imported when first needed)."""
+    path = Path(path)
+    if path.suffix.lower() not in JPEG_EXTENSIONS:
+        return decode_png(path.read_bytes())
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise ImportError(f"{path} is a JPEG: reading it needs PIL (pip install pillow); this package only encodes JPEG") from e
+    with Image.open(path) as im:
+        if im.mode not in ("L", "RGB"):
+            im = im.convert("RGB")
+        return np.asarray(im).copy()

@@ -340,7 +340,7 @@ def recompute_dataset(dataset_dir, bbox_type: str = "amodal", backend=None, batc
                 per_image[int(i)] = annotations_from_encoded(*enc, size, [int(e["obj_id"]) for e in gt[i]], fract, int(i),
                                                              bbox_type, at)
                 at += K
-        images = [(int(i), f"rgb/{BD.image_name(i)}", list(scene.image_size(i))) for i in ids]
+        images = [(int(i), f"rgb/{scene.image_path('rgb', i).name}", list(scene.image_size(i))) for i in ids]
         scene.write_json(coco_file_name(bbox_type), scene_coco(images, per_image, scene_obj_ids(gt), dataset_dir.resolve().name))
     return scenes
 

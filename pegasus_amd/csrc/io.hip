@@ -1,5 +1,5 @@
-// io.hip -- host side of the image-file entries of libpegasus_raster.so: PNG files of device images, undistortion of a
-// COLMAP project's images and points.
+// io.hip -- host side of the image-file entries of libpegasus_raster.so: PNG and JPEG files of device images, undistortion
+// of a COLMAP project's images and points.
 // Owns its kernel headers: no other translation unit includes them (DESIGN.md "Source layout").
 #include <hip/hip_runtime.h>
 
@@ -9,6 +9,7 @@
 
 #include "host_common.h"
 #include "png.hip.h"
+#include "jpeg.hip.h"
 #include "undistort.hip.h"
 
 using namespace pgr;
@@ -123,6 +124,152 @@ int32_t pgr_png_emit(const PgrPngJob* jobs, int32_t n_jobs, const int64_t* offse
         ws_at<const PngFileInfo>(workspace, L.files), ws_at<const uint8_t>(workspace, L.slots),
         reinterpret_cast<const long long*>(offsets), (long long)total, files);
     return launch_status("png_emit launch");
+}
+
+// ---- JPEG encoding (jpeg.hip.h) -----------------------------------------------------------------------------------------------
+namespace {
+constexpr int32_t JPEG_MAX_SIDE = 16384;
+constexpr int64_t JPEG_BLOCK_BYTES = 2 * ((JPEG_BLOCK_BITS + 7) / 8);      // every byte of a block's bits stuffed
+constexpr int64_t JPEG_MIN_BYTES = 120;                                     // less than any header and its EOI
+
+// ITU-T T.81 Annex K, tables K.1 and K.2, in natural order: what PIL writes at quality 50 --
+//   python -c "from PIL import Image; Image.new('RGB', (8, 8)).save('q50.jpg', quality=50); print(Image.open('q50.jpg').quantization)"
+constexpr uint8_t JPEG_BASE_LUM[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,
+                                       14, 13, 16, 24, 40,  57,  69,  56,  14, 17, 22, 29, 51,  87,  80,  62,
+                                       18, 22, 37, 56, 68,  109, 103, 77,  24, 35, 55, 64, 81,  104, 113, 92,
+                                       49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+constexpr uint8_t JPEG_BASE_CHROMA[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99,
+                                          99, 99, 47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
+                                          99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+int jpeg_quant(int base, int quality) {
+    const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    return std::min(255, std::max(1, (base * s + 50) / 100));
+}
+
+bool jpeg_shape_ok(int32_t width, int32_t height, int32_t kind, int32_t sub) {
+    return width >= 1 && width <= JPEG_MAX_SIDE && height >= 1 && height <= JPEG_MAX_SIDE &&
+           ((kind == PGR_JPEG_GRAY8 && sub == PGR_JPEG_444) || (kind == PGR_JPEG_RGB8 && (sub == PGR_JPEG_444 || sub == PGR_JPEG_420)));
+}
+bool jpeg_job_ok(const PgrJpegJob& j) {
+    if (!jpeg_shape_ok(j.width, j.height, j.kind, j.subsampling) || j.quality < 1 || j.quality > 100) return false;
+    const int bpp = j.kind == PGR_JPEG_GRAY8 ? 1 : 3;
+    return j.pixel_stride >= bpp && j.row_stride >= (int64_t)(j.width - 1) * j.pixel_stride + bpp;
+}
+// MCUs a row, MCUs, restart intervals and blocks of a shape inside the domain
+struct JpegShape { int64_t mcu_w, n_mcu, n_iv, bpm, n_y; };
+JpegShape jpeg_shape(int32_t width, int32_t height, int32_t kind, int32_t sub) {
+    const int side = sub == PGR_JPEG_420 ? 16 : 8;
+    JpegShape s;
+    s.mcu_w = (width + side - 1) / side;
+    s.n_mcu = s.mcu_w * ((height + side - 1) / side);
+    s.n_iv = (s.n_mcu + JPEG_R - 1) / JPEG_R;
+    s.n_y = sub == PGR_JPEG_420 ? 4 : 1;
+    s.bpm = kind == PGR_JPEG_GRAY8 ? 1 : s.n_y + 2;
+    return s;
+}
+
+// the encoder's workspace: the job table, one record per file and per interval, the coefficients
+struct JpegLayout { size_t jobs, files, info, coefs, total; int64_t n_iv; };
+JpegLayout jpeg_layout(int32_t n_jobs, const PgrJpegJob* jobs) {
+    JpegLayout L{};
+    if (n_jobs <= 0 || !jobs) return L;
+    int64_t ivs = 0, blocks = 0;
+    for (int32_t k = 0; k < n_jobs; ++k) {
+        if (!jpeg_job_ok(jobs[k])) return L;
+        const JpegShape s = jpeg_shape(jobs[k].width, jobs[k].height, jobs[k].kind, jobs[k].subsampling);
+        ivs += s.n_iv;
+        blocks += s.n_mcu * s.bpm;
+    }
+    if (ivs > MAX_GRID_BLOCKS) return L;
+    Carver c;
+    L.jobs = c.take((size_t)n_jobs * sizeof(JpegJobDev));
+    L.files = c.take((size_t)n_jobs * sizeof(JpegFileInfo));
+    L.info = c.take((size_t)ivs * sizeof(JpegIvInfo));
+    L.coefs = c.take((size_t)blocks * 64 * sizeof(int16_t));
+    L.total = c.off;
+    L.n_iv = ivs;
+    return L;
+}
+}  // namespace
+
+size_t pgr_jpeg_workspace_bytes(int32_t n_jobs, const PgrJpegJob* jobs) { return jpeg_layout(n_jobs, jobs).total; }
+
+int64_t pgr_jpeg_max_bytes(int32_t width, int32_t height, int32_t kind, int32_t subsampling) {
+    if (!jpeg_shape_ok(width, height, kind, subsampling)) return 0;
+    const JpegShape s = jpeg_shape(width, height, kind, subsampling);
+    return (kind == PGR_JPEG_GRAY8 ? 330 : 613) + JPEG_BLOCK_BYTES * s.n_mcu * s.bpm + 2 * s.n_iv;
+}
+
+int32_t pgr_jpeg_quant_tables(int32_t quality, uint8_t* lum, uint8_t* chroma) {
+    if (quality < 1 || quality > 100 || !lum || !chroma) return PGR_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < 64; ++i) {
+        lum[i] = (uint8_t)jpeg_quant(JPEG_BASE_LUM[i], quality);
+        chroma[i] = (uint8_t)jpeg_quant(JPEG_BASE_CHROMA[i], quality);
+    }
+    return PGR_OK;
+}
+
+int32_t pgr_jpeg_encode(const PgrJpegJob* jobs, int32_t n_jobs, int64_t* sizes, void* workspace, size_t workspace_bytes, void* stream_v) {
+    if (n_jobs < 0) return PGR_ERR_INVALID_ARGUMENT;
+    if (n_jobs == 0) return PGR_OK;
+    const JpegLayout L = jpeg_layout(n_jobs, jobs);
+    if (!L.total || !sizes || !workspace || !workspace_aligned_16(workspace)) return PGR_ERR_INVALID_ARGUMENT;
+    for (int32_t k = 0; k < n_jobs; ++k)
+        if (!jobs[k].pixels) return PGR_ERR_INVALID_ARGUMENT;
+    if (workspace_bytes < L.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    std::vector<JpegJobDev> table((size_t)n_jobs);
+    uint32_t iv = 0;
+    uint64_t block = 0;
+    for (int32_t k = 0; k < n_jobs; ++k) {
+        const PgrJpegJob& j = jobs[k];
+        const JpegShape s = jpeg_shape(j.width, j.height, j.kind, j.subsampling);
+        JpegJobDev& d = table[(size_t)k];
+        d.pixels = static_cast<const uint8_t*>(j.pixels);
+        d.row_stride = j.row_stride;
+        d.coef_first = block;
+        d.pixel_stride = j.pixel_stride; d.width = j.width; d.height = j.height; d.kind = j.kind; d.sub = j.subsampling;
+        d.mcu_w = (uint32_t)s.mcu_w; d.n_mcu = (uint32_t)s.n_mcu; d.iv_first = iv; d.n_iv = (uint32_t)s.n_iv;
+        d.bpm = (uint32_t)s.bpm; d.n_y = (uint32_t)s.n_y;
+        for (int i = 0; i < 64; ++i) {
+            d.q[0][i] = (uint16_t)jpeg_quant(JPEG_BASE_LUM[i], j.quality);
+            d.q[1][i] = (uint16_t)jpeg_quant(JPEG_BASE_CHROMA[i], j.quality);
+        }
+        iv += d.n_iv;
+        block += (uint64_t)(s.n_mcu * s.bpm);
+    }
+    hipStream_t stream = as_stream(stream_v);
+    auto* jobs_dev = ws_at<JpegJobDev>(workspace, L.jobs);
+    auto* files = ws_at<JpegFileInfo>(workspace, L.files);
+    auto* info = ws_at<JpegIvInfo>(workspace, L.info);
+    auto* coefs = ws_at<int16_t>(workspace, L.coefs);
+    // in stream order, and read when this returns: the caller may free its table after the call
+    if (!hip_ok(hipMemcpyWithStream(jobs_dev, table.data(), table.size() * sizeof(JpegJobDev), hipMemcpyHostToDevice, stream),
+                "memcpy jpeg jobs") ||
+        !hip_ok(hipMemsetAsync(files, 0, (size_t)n_jobs * sizeof(JpegFileInfo), stream), "memset jpeg histograms"))
+        return PGR_ERR_LAUNCH_FAILURE;
+    jpeg_blocks_kernel<<<(unsigned)L.n_iv, JPEG_THREADS, 0, stream>>>(jobs_dev, n_jobs, files, coefs);
+    jpeg_tables_kernel<<<(unsigned)n_jobs, JPEG_THREADS, 0, stream>>>(jobs_dev, files);
+    jpeg_scan_kernel<false><<<(unsigned)L.n_iv, JPEG_THREADS, 0, stream>>>(jobs_dev, n_jobs, files, info, coefs, nullptr, 0, nullptr);
+    jpeg_finish_kernel<<<(unsigned)n_jobs, JPEG_THREADS, 0, stream>>>(jobs_dev, info, files, reinterpret_cast<long long*>(sizes));
+    return launch_status("jpeg_encode launch");
+}
+
+int32_t pgr_jpeg_emit(const PgrJpegJob* jobs, int32_t n_jobs, const int64_t* offsets, int64_t total, uint8_t* files, int64_t capacity,
+                      const void* workspace, size_t workspace_bytes, void* stream_v) {
+    if (n_jobs < 0) return PGR_ERR_INVALID_ARGUMENT;
+    if (n_jobs == 0) return PGR_OK;
+    const JpegLayout L = jpeg_layout(n_jobs, jobs);
+    if (!L.total || !offsets || !files || !workspace || !workspace_aligned_16(workspace)) return PGR_ERR_INVALID_ARGUMENT;
+    int64_t most = 0;
+    for (int32_t k = 0; k < n_jobs; ++k) most += pgr_jpeg_max_bytes(jobs[k].width, jobs[k].height, jobs[k].kind, jobs[k].subsampling);
+    if (total <= JPEG_MIN_BYTES * n_jobs || total > most || capacity < total) return PGR_ERR_INVALID_ARGUMENT;
+    if (workspace_bytes < L.total) return PGR_ERR_WORKSPACE_TOO_SMALL;
+    // the scan kernel only reads the workspace when it emits
+    jpeg_scan_kernel<true><<<(unsigned)L.n_iv, JPEG_THREADS, 0, as_stream(stream_v)>>>(
+        ws_at<const JpegJobDev>(workspace, L.jobs), n_jobs, ws_at<const JpegFileInfo>(workspace, L.files),
+        const_cast<JpegIvInfo*>(ws_at<const JpegIvInfo>(workspace, L.info)), ws_at<const int16_t>(workspace, L.coefs),
+        reinterpret_cast<const long long*>(offsets), (long long)total, files);
+    return launch_status("jpeg_emit launch");
 }
 
 // ---- undistortion (undistort.hip.h) ---------------------------------------------------------------------------------------------

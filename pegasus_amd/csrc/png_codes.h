@@ -10,7 +10,7 @@ namespace pgr {
 constexpr int PNG_CODE_MAX_SYMBOLS = 288;            // the largest alphabet the builder takes
 constexpr uint32_t PNG_CODE_MAX_FREQ = 1u << 22;     // and the largest count: 288 of them still sum below 2^31
 // uint32 words of scratch the builder needs for an alphabet of n symbols
-constexpr int png_code_scratch_words(int n) { return 2 * n + 16; }
+constexpr int png_code_scratch_words(int n) { return 2 * n + 17; }
 
 // Code lengths of a prefix code for the symbols with freq != 0, none longer than `limit`; 0 for unused symbols.
 //   no used symbol   -> all 0 (the caller sends one zero length: HDIST = 0)
@@ -22,7 +22,8 @@ constexpr int png_code_scratch_words(int n) { return 2 * n + 16; }
 // the lengths are handed out again in order of the counts, the rarest symbol the longest.  If that costs more than the flat
 // complete code (2^L - used symbols at L - 1 bits, the rest at L = ceil(log2(used)) bits), the flat code is taken: the result
 // never costs more than ceil(log2(used)) bits for every used symbol.  Ties between equal counts go by symbol index, so host
-// and device build the same code.  Preconditions (the callers check them): 1 <= n <= 288, 1 <= limit <= 15, n <= 2^limit,
+// and device build the same code.  Preconditions (the callers check them): 1 <= n <= 288, 1 <= limit <= 16 (deflate's callers
+// pass 15 and 7, the JPEG encoder 16), n <= 2^limit,
 // freq[s] <= 2^22.  `scratch`: png_code_scratch_words(n) words (LDS on the device: the function keeps no array of its own).
 __host__ __device__ inline void png_code_lengths(const uint32_t* freq, int n, int limit, uint8_t* lengths, uint32_t* scratch) {
     uint32_t* w = scratch;             // sorted keys, then weights / parents, then depths
@@ -70,7 +71,7 @@ __host__ __device__ inline void png_code_lengths(const uint32_t* freq, int n, in
         used = 0;
     }
     // the limit
-    for (int l = 0; l < 16; ++l) num[l] = 0;
+    for (int l = 0; l <= 16; ++l) num[l] = 0;
     for (int i = 0; i < m; ++i) num[w[i] < (uint32_t)limit ? w[i] : (uint32_t)limit]++;
     uint32_t kraft = 0;                                        // in units of 2^-limit
     for (int l = 1; l <= limit; ++l) kraft += num[l] << (limit - l);

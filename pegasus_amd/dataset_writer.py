@@ -29,10 +29,15 @@ class BopSceneWriter:
     the batch where it lies -- rgb, depth, visible masks, silhouettes, the semantic image, with ``meshes=`` the mesh masks --
     makes ONE ``png.encode_batch`` call, and the thread pool only writes slices of the one buffer that came back to their
     paths.  Same directory, same file names, files that decode to the same arrays; the JSON records, scene_gt_info and the
-    COCO annotations do not depend on the encoder.  The default stays the host encoder."""
+    COCO annotations do not depend on the encoder.  The default stays the host encoder.
+
+    ``rgb_format="jpg"`` writes the colour images as ``rgb/<id>.jpg``, as BOP's own train_pbr splits store them: ONE
+    ``jpeg.encode_batch`` call per batch on the device (pegasus_amd.jpeg) at ``jpeg_quality`` and
+    ``jpeg_subsampling`` ('4:4:4' or '4:2:0'), whatever ``encoder`` is; every other kind follows ``encoder`` as before and
+    scene_gt_coco.json names the .jpg.  The default stays "png"."""
 
     def __init__(self, out_dir, scene_id: int = 0, png_level: int = 1, workers: int = None, max_pending: int = 4,
-                 encoder: str = "host"):
+                 encoder: str = "host", rgb_format: str = "png", jpeg_quality: int = 95, jpeg_subsampling: str = "4:4:4"):
         import os
         from concurrent.futures import ThreadPoolExecutor
         self.scene = BD.scene_dir(out_dir, "train", scene_id)
@@ -45,6 +50,15 @@ class BopSceneWriter:
         if encoder not in ("host", "gpu"):
             raise ValueError(f"encoder={encoder!r}: 'host' or 'gpu'")
         self.encoder = encoder
+        if rgb_format not in ("png", "jpg"):
+            raise ValueError(f"rgb_format={rgb_format!r}: 'png' or 'jpg'")
+        if rgb_format == "jpg":
+            from . import jpeg
+            jpeg.subsampling_code(jpeg_subsampling)          # raises on anything but 4:4:4 / 4:2:0
+            if not 1 <= int(jpeg_quality) <= 100:
+                raise ValueError(f"jpeg_quality={jpeg_quality!r}: 1..100")
+        self.rgb_format, self.jpeg_quality, self.jpeg_subsampling = rgb_format, int(jpeg_quality), jpeg_subsampling
+        self._jpeg_jobs = []                                 # rgb_format="jpg": (device image, path) of the batch being added
         self._gpu_jobs = []                                  # encoder="gpu": (device image, scale, path) of the batch being added
         self.workers = max(1, min(32, os.cpu_count() or 1) if workers is None else int(workers))
         self._pool = ThreadPoolExecutor(max_workers=self.workers) if self.workers > 1 else None
@@ -77,6 +91,20 @@ class BopSceneWriter:
             else:
                 batch_futures.append(self._pool.submit(path.write_bytes, data))
 
+    def _encode_jpeg_jobs(self, batch_futures):
+        """One device encode for the batch's colour images; the pool (or this thread) writes the slices."""
+        from . import jpeg
+        jobs, self._jpeg_jobs = self._jpeg_jobs, []
+        if not jobs:
+            return
+        files, offsets = jpeg.encode_batch([j[0] for j in jobs], self.jpeg_quality, self.jpeg_subsampling)
+        for k, (_, path) in enumerate(jobs):
+            data = files[offsets[k]:offsets[k + 1]]
+            if self._pool is None:
+                path.write_bytes(data)
+            else:
+                batch_futures.append(self._pool.submit(path.write_bytes, data))
+
     def add_batch(self, frames: dict, scene_gt: dict, scene_camera: dict, n: int = None, silhouettes=None, frame_ids=None,
                   record_shape=None, meshes=None, delta: float = 15.0, translation_scale: float = 1.0, coco=False):
         """``frames``: FrameRenderer output (color, depth, and with masks: seg, masks); ``silhouettes``: uint8 [B,K,H,W]
@@ -100,13 +128,14 @@ class BopSceneWriter:
                 raise ValueError(f"this scene's annotations are {self.coco_bbox_type}; one file holds one box type")
         masks_dev = frames.get("masks")
         gpu = self.encoder == "gpu"
+        jpg = self.rgb_format == "jpg"
         if "color" in frames:
             n = frames["color"].shape[0] if n is None else n
             # GPU: uint8 HWC / uint16 millimetres for the whole batch in one launch (pgr_pack_frames), then ONE
             # device->host copy per kind and batch
             packed = M.pack_frames(color=frames["color"][:n], depth=frames["depth"][:n])
             depth_mm_dev = packed["depth_mm"]
-            rgb8 = packed["rgb"] if gpu else packed["rgb"].cpu().numpy()
+            rgb8 = packed["rgb"] if gpu or jpg else packed["rgb"].cpu().numpy()
             mm = depth_mm_dev if gpu else depth_mm_dev.cpu().numpy().view(np.uint16)
         else:
             # a records-only frame set (FrameRenderer.alloc_frames(images=False | "seg")): the compositor's epilogue wrote the
@@ -118,7 +147,7 @@ class BopSceneWriter:
             rv = M.record_views(frames["records"][:n], H, W, K)
             depth_mm_dev = rv["depth_mm"]
             # encoder="gpu": the record's own RGB and depth planes are the encoder's input, read where they lie
-            rgb8 = rv["rgb"] if gpu else rv["rgb"].cpu().numpy()
+            rgb8 = rv["rgb"] if gpu or jpg else rv["rgb"].cpu().numpy()
             mm = depth_mm_dev if gpu else depth_mm_dev.cpu().numpy().view(np.uint16)
             masks_dev = M.unpack_mask_bits(rv["mask_bits"], K) if K else None
         if silhouettes is None:
@@ -185,7 +214,10 @@ class BopSceneWriter:
                     for k, image in enumerate(stack if gpu else (stack * 255).cpu().numpy()):
                         self._submit(futures, image, name, fid, k, mask_scale)
                 self.scene_gt_info[str(fid)] = mesh_gt[2][i]
-            self._submit(futures, rgb8[i], "rgb", fid)
+            if jpg:
+                self._jpeg_jobs.append((rgb8[i], self.files.path / "rgb" / BD.image_name(fid, ext="jpg")))
+            else:
+                self._submit(futures, rgb8[i], "rgb", fid)
             self._submit(futures, mm[i], "depth", fid)
             if mk is not None:
                 for k in range(mk.shape[1]):
@@ -203,6 +235,8 @@ class BopSceneWriter:
             self.n_frames += 1
         if gpu:
             self._encode_gpu_jobs(futures)
+        if jpg:
+            self._encode_jpeg_jobs(futures)
         if futures:
             self._pending.append(futures)
             while len(self._pending) > self._max_pending:
@@ -254,6 +288,6 @@ class BopSceneWriter:
             self.files.write_json(BD.SCENE_GT_INFO, BD.by_frame(self.scene_gt_info))
         if self.coco_bbox_type is not None:
             from . import coco as CO
-            images = [(int(k), f"rgb/{BD.image_name(k)}", list(self.coco_size)) for k in self.scene_gt_coco]
+            images = [(int(k), f"rgb/{BD.image_name(k, ext=self.rgb_format)}", list(self.coco_size)) for k in self.scene_gt_coco]
             doc = CO.scene_coco(images, self.scene_gt_coco, CO.scene_obj_ids(self.scene_gt), self.dataset_name)
             self.files.write_json(CO.coco_file_name(self.coco_bbox_type), doc)

@@ -36,6 +36,11 @@ def main(argv=None):
     ap.add_argument("--png", default="host", choices=["host", "gpu"],
                     help="where the PNG files are encoded: on the host thread pool (zlib), or on the GPU (pegasus_amd.png: one "
                          "encode call per batch, the threads only write the files)")
+    ap.add_argument("--rgb", default="png", choices=["png", "jpg"],
+                    help="the format of rgb/: PNG, or baseline JPEG as BOP's train_pbr splits store it, encoded on the GPU "
+                         "(pegasus_amd.jpeg: one encode call per batch) whatever --png says")
+    ap.add_argument("--jpeg-quality", type=int, default=95, help="--rgb jpg: quality 1..100 (the IJG scale)")
+    ap.add_argument("--jpeg-subsampling", default="444", choices=["444", "420"], help="--rgb jpg: chroma subsampling")
     ap.add_argument("--gt-from-meshes", default=None, metavar="MODELS_DIR",
                     help="take mask/, mask_visib/ and scene_gt_info.json from the depth renders of the obj_NNNNNN.ply meshes "
                          "(millimetres, as pegasus_amd.mesh writes them) of this directory, as the BOP toolkit does")
@@ -49,6 +54,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.trajectory and not args.dynamic:
         ap.error("--trajectory gives the object poses of --dynamic")
+    if not 1 <= args.jpeg_quality <= 100:
+        ap.error("--jpeg-quality is 1..100")
     if args.boxes == "oriented" and not args.gt_from_meshes:
         ap.error("--boxes oriented takes the boxes from the meshes: it requires --gt-from-meshes MODELS_DIR")
 
@@ -84,7 +91,8 @@ def main(argv=None):
     writers = args.writers
     if writers is None and world > 1:        # N ranks share the host's cores: their encoder pools must not add up to N x 32
         writers = max(1, min(32, (os.cpu_count() or 1) // world))
-    w = BopSceneWriter(args.out, workers=writers, encoder=args.png)
+    w = BopSceneWriter(args.out, workers=writers, encoder=args.png, rgb_format=args.rgb, jpeg_quality=args.jpeg_quality,
+                       jpeg_subsampling=args.jpeg_subsampling)
     meshes = None
     if args.gt_from_meshes:
         from .mesh_render import MeshSet

@@ -675,7 +675,7 @@ def visualize_dataset(dataset_dir, models_dir, out_dir, results=None, resolve_vi
                 poses = [dict(obj_id=int(e["obj_id"]), R=BD.pose_of(e)[0], t=BD.pose_of(e)[1]) for e in scene.gt[i]]
             else:
                 poses = ests.get((int(scene.path.name), int(i)), []) if scene.path.name.isdigit() else []
-            rgb = scene.read_png("rgb", i)
+            rgb = scene.read_image("rgb", i)
             if rgb.ndim == 2:
                 rgb = np.repeat(rgb[:, :, None], 3, 2)
             vis_object_poses(poses, BD.cam_K(scene.camera[i]), meshes, rgb=rgb, vis_rgb_path=Path(out_dir) / scene.path.name / BD.image_name(i),

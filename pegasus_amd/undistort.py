@@ -301,14 +301,24 @@ def _encode(path, array):
         Image.fromarray(array).save(path)
 
 
-def _write_batch(pool, backend, png, paths, images):
-    """The files of a batch of images that lie with the backend: PNG on the device where asked and possible, else on the host"""
-    device = png == "gpu" and backend.device_png                 # pegasus_amd.png writes gray and RGB; the rest goes to the host
-    on_device = [device and p.suffix.lower() == ".png" and (im.dim() == 2 or im.shape[2] == 3) for p, im in zip(paths, images)]
-    if any(on_device):
-        from . import png as device_png
-        pick = [k for k, d in enumerate(on_device) if d]
-        for k, data in zip(pick, device_png.encode_batch_bytes([images[k] for k in pick])):
+def _write_batch(pool, backend, png, jpeg, paths, images):
+    """The files of a batch of images that lie with the backend: PNG and JPEG on the device where asked and possible, else on the
+    host"""
+    # pegasus_amd.png and pegasus_amd.jpeg write gray and RGB; the rest (RGBA, other formats) goes to the host
+    encoders = {".png": "png" if png == "gpu" and backend.device_png else None}
+    encoders[".jpg"] = encoders[".jpeg"] = "jpeg" if jpeg == "gpu" and backend.device_png else None
+    on_device = [(e := encoders.get(p.suffix.lower())) and (im.dim() == 2 or im.shape[2] == 3) and e for p, im in zip(paths, images)]
+    for name in ("png", "jpeg"):
+        pick = [k for k, d in enumerate(on_device) if d == name]
+        if not pick:
+            continue
+        if name == "png":
+            from . import png as device_png
+            files = device_png.encode_batch_bytes([images[k] for k in pick])
+        else:
+            from . import jpeg as device_jpeg                    # quality 95 at 4:2:0: what _encode asks of PIL
+            files = device_jpeg.encode_batch_bytes([images[k] for k in pick], quality=95, subsampling="4:2:0")
+        for k, data in zip(pick, files):
             paths[k].parent.mkdir(parents=True, exist_ok=True)
             paths[k].write_bytes(data)
     rest = [k for k, d in enumerate(on_device) if not d]
@@ -317,16 +327,18 @@ def _write_batch(pool, backend, png, paths, images):
 
 
 def undistort_project(image_path, input_path, output_path, *, blank_pixels=0.0, min_scale=0.2, max_scale=2.0, max_image_size=-1,
-                      principal_point="center", masks=None, resize=False, png="host", batch=8, backend=None) -> dict:
+                      principal_point="center", masks=None, resize=False, png="host", jpeg="host", batch=8, backend=None) -> dict:
     """Undistorts the COLMAP project ``input_path`` (a sparse model, .bin or .txt) with images under ``image_path`` into
     ``output_path``: ``images/<same name>`` (PNG through the host or, ``png="gpu"``, pegasus_amd.png; JPEG through PIL at quality
-    95), ``sparse/0`` in the input's format (PINHOLE cameras, moved 2D observations, points3D copied verbatim),
+    95 or, ``jpeg="gpu"``, gray and RGB ones through pegasus_amd.jpeg at quality 95, 4:2:0 -- PIL's default), ``sparse/0`` in the input's format (PINHOLE cameras, moved 2D observations, points3D copied verbatim),
     ``masks/<mask file>`` of each image with ``masks=<dir>``, the pyramid ``images_2``, ``images_4``, ``images_8`` with
     ``resize`` (box means; the undistorted size is then a multiple of 8, so the fields of view hold at every level) and
     ``undistort.json`` (the options and both cameras per camera id).  Returns the seconds spent decoding, on the device and
     encoding, and the output cameras."""
     if png not in ("host", "gpu"):
         raise ValueError(f"png is 'host' or 'gpu', not {png!r}")
+    if jpeg not in ("host", "gpu"):
+        raise ValueError(f"jpeg is 'host' or 'gpu', not {jpeg!r}")
     backend = backend or _Device()
     image_path, input_path, output_path = Path(image_path), Path(input_path), Path(output_path)
     binary = (input_path / "cameras.bin").exists() and (input_path / "images.bin").exists()
@@ -389,7 +401,7 @@ def undistort_project(image_path, input_path, output_path, *, blank_pixels=0.0, 
             t2 = time.perf_counter()
             for f, level in levels.items():
                 paths = [output_path / (c[2] if f == 1 else Path(f"{c[2].parts[0]}_{f}", *c[2].parts[1:])) for c in chunk]
-                _write_batch(pool, backend, png, paths, level)
+                _write_batch(pool, backend, png, jpeg, paths, level)
             t3 = time.perf_counter()
             seconds["decode"] += t1 - t0
             seconds["device"] += t2 - t1
@@ -399,7 +411,7 @@ def undistort_project(image_path, input_path, output_path, *, blank_pixels=0.0, 
         return dict(model=c.model, width=int(c.width), height=int(c.height), params=[float(v) for v in c.params])
     output_path.mkdir(parents=True, exist_ok=True)
     (output_path / "undistort.json").write_text(json.dumps(dict(
-        options=dict(options, masks=str(masks) if masks else None, resize=bool(resize), png=png),
+        options=dict(options, masks=str(masks) if masks else None, resize=bool(resize), png=png, jpeg=jpeg),
         cameras={str(cid): dict(source=as_json(cameras[cid]), undistorted=as_json(out_cameras[cid])) for cid in cameras}),
         indent=1) + "\n")
     return dict(seconds=seconds, cameras=out_cameras, n_images=len(images))
@@ -420,6 +432,8 @@ def main(argv=None) -> int:
     ap.add_argument("--resize", action="store_true", help="also write images_2, images_4, images_8")
     ap.add_argument("--masks", default=None, help="a directory with one mask per image, undistorted into <out>/masks")
     ap.add_argument("--png", choices=("host", "gpu"), default="host")
+    ap.add_argument("--jpeg", choices=("host", "gpu"), default="host",
+                    help="where gray and RGB JPEG files are encoded: PIL on the host, or pegasus_amd.jpeg on the GPU")
     args = ap.parse_args(argv)
     if args.source_path:
         src = Path(args.source_path)
@@ -431,7 +445,7 @@ def main(argv=None) -> int:
     t0 = time.perf_counter()
     res = undistort_project(image_path, input_path, output_path, blank_pixels=args.blank_pixels, min_scale=args.min_scale,
                             max_scale=args.max_scale, max_image_size=args.max_image_size, principal_point=args.principal_point,
-                            masks=args.masks, resize=args.resize, png=args.png)
+                            masks=args.masks, resize=args.resize, png=args.png, jpeg=args.jpeg)
     s = res["seconds"]
     print(f"undistorted {res['n_images']} images in {time.perf_counter() - t0:.2f} s (decode {s['decode']:.2f} s, device "
           f"{s['device']:.2f} s, encode {s['encode']:.2f} s) -> {output_path}")
