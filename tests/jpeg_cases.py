@@ -76,6 +76,112 @@ def reference_files(mode: str):
     return {(name, q): JR.encode(im, q, sub) for name, im in equality_images(mode).items() for q in QUALITIES}
 
 
+# ---- edges: tokens no ordinary image codes, the code-length limit, files past one pass of the finish kernel -----------------------
+def single_coefficient_block(k: int, v: int, Q) -> np.ndarray:
+    """uint8 [8,8]: the float inverse DCT of v * Q[k] at zigzag position k, plus 128, rounded.  At quality 50 the restatement
+    quantises it back to exactly that coefficient (tests/test_jpeg_host.py asserts it for every block used here)."""
+    X = np.zeros(64)
+    X[JR.NAT_OF_ZZ[k]] = v * int(Q[JR.NAT_OF_ZZ[k]])
+    u, x = np.arange(8)[:, None], np.arange(8)[None, :]
+    c = np.where(u == 0, np.sqrt(1.0 / 8.0), 0.5) * np.cos((2 * x + 1) * u * np.pi / 16)
+    return np.rint(128.0 + c.T @ X.reshape(8, 8) @ c).astype(np.uint8)
+
+
+TOKEN_KS = (17, 33, 49, 62, 63)            # one, two, three ZRLs; three and a run of 13; three, a run of 14 and no EOB
+
+
+def grid_of_blocks(blocks, across: int) -> np.ndarray:
+    blocks = np.asarray(blocks)
+    return blocks.reshape(-1, across, *blocks.shape[1:]).transpose(0, 2, 1, 3).reshape(-1, across * blocks.shape[2])
+
+
+def token_image(mode: str) -> np.ndarray:
+    """Single-coefficient blocks of TOKEN_KS with v = 1 and -2 and a flat block: gray; or, at 4:2:0, as luminance (a gray RGB
+    image: Y is the sample, the chroma 128) next to a half that carries them in Cb and Cr at constant luminance."""
+    ql, qc = JR.quant_tables(50)
+    luma = grid_of_blocks([single_coefficient_block(k, v, ql) for v in (1, -2) for k in TOKEN_KS] + [np.full((8, 8), 128, np.uint8)] * 2, 6)
+    if mode == "gray":
+        return luma
+    y = np.concatenate([luma, np.full_like(luma, 128)], axis=1).astype(np.float64)
+    chroma = grid_of_blocks([single_coefficient_block(k, v, qc) for v in (1, -2) for k in TOKEN_KS] + [np.full((8, 8), 128, np.uint8)] * 2, 6)
+    chroma = np.kron(chroma.astype(np.float64) - 128.0, np.ones((2, 2)))                       # a chroma sample covers 2 x 2 pixels
+    y = np.concatenate([y, np.full((chroma.shape[0] - y.shape[0], y.shape[1]), 128.0)], axis=0)
+    y = np.concatenate([y, np.full((y.shape[0], 2 * chroma.shape[1] - y.shape[1]), 128.0)], axis=1)
+    cb = np.concatenate([np.zeros_like(chroma), chroma], axis=1)
+    cr = np.concatenate([np.zeros_like(chroma), np.roll(chroma, 16, axis=0)], axis=1)              # the two rows of blocks swapped
+    rgb = np.stack([y + 1.402 * cr, y - 0.344136 * cb - 0.714136 * cr, y + 1.772 * cb], -1)
+    return np.clip(np.rint(rgb), 0, 255).astype(np.uint8)
+
+
+def dc11_image(mode: str) -> np.ndarray:
+    """Black and white blocks in both orders: at quality 100 the DC difference is +-2040, category 11."""
+    side = 16 if mode == "420" else 8
+    g = np.kron(np.array([[0, 255, 255, 0, 255], [255, 0, 0, 255, 0]], np.uint8), np.ones((side, side), np.uint8))
+    return g if mode == "gray" else np.stack([g, g, g], -1)
+
+
+FIBONACCI_COUNTS = (1, 2, 3, 5, 8, 13, 21, 34, 55, 89, 144, 233, 377, 610, 987, 1597)        # F(2) .. F(17): 4179 blocks
+
+
+def fibonacci_image() -> np.ndarray:
+    """Gray, 528 x 512 = 66 x 64 blocks = 264 intervals: FIBONACCI_COUNTS[k - 1] blocks whose one coefficient is a 1 at zigzag
+    position k (symbol (k - 1) << 4 | 1), shuffled, and 45 flat blocks.  With the end-of-block symbol of every block and the
+    pseudo-symbol the AC table's counts are 1, 1, 2, 3, 5, ..., 1597, 4224: every merge of a Huffman code of them takes the
+    accumulated subtree and the next count, whatever the tie-break, so the unlimited code is 17 deep."""
+    ql, _ = JR.quant_tables(50)
+    kinds = [single_coefficient_block(k, 1, ql) for k in range(1, 17)] + [np.full((8, 8), 128, np.uint8)]
+    which = np.repeat(np.arange(17), FIBONACCI_COUNTS + (66 * 64 - sum(FIBONACCI_COUNTS),))
+    np.random.default_rng(23).shuffle(which)
+    return grid_of_blocks(np.array(kinds)[which], 66)
+
+
+def shallowest_huffman_depth(counts) -> int:
+    """Depth of a Huffman code of ``counts`` when every tie goes to the shallower subtree."""
+    import heapq
+    heap = [(int(f), 0) for f in counts]
+    heapq.heapify(heap)
+    while len(heap) > 1:
+        a, b = heapq.heappop(heap), heapq.heappop(heap)
+        heapq.heappush(heap, (a[0] + b[0], max(a[1], b[1]) + 1))
+    return heap[0][1]
+
+
+def past_one_pass_shapes():
+    """name -> (mode, MCUs across, MCUs down): 256, 257 and 513 intervals of gray, 260 of 4:2:0.  One row of 256 R MCUs would be
+    32768 pixels wide, outside the encoder's domain (sides to 16384) and, at 512 R + 1, outside what a JPEG header can say
+    (65535): the same MCU counts are laid out in rows instead, intervals being counted in raster order whatever the width --
+    256 R = 64 x 64, 256 R + 1 = 4097 = 241 x 17 (a last interval of one MCU), and, 512 R + 1 = 8193 = 3 x 2731 having no
+    shape inside the domain, 512 R + 2 = 8194 = 241 x 34 (a last interval of two)."""
+    assert R == 16
+    return {"256 intervals": ("gray", 64, 64), "257 intervals": ("gray", 241, 17), "513 intervals": ("gray", 241, 34),
+            "260 intervals 420": ("420", 64, 65)}
+
+
+def past_one_pass_image(name: str) -> np.ndarray:
+    mode, across, down = past_one_pass_shapes()[name]
+    side = 16 if mode == "420" else 8
+    h, w = down * side, across * side
+    return ramp(h, w, mode != "gray") ^ (noise(h, w, mode != "gray", seed=across + down) >> 5)
+
+
+def edge_cases():
+    """name -> (mode, image, quality)."""
+    out = {}
+    for mode in ("gray", "420"):
+        out[f"tokens {mode}"] = (mode, token_image(mode), 50)
+        out[f"dc 11 {mode}"] = (mode, dc11_image(mode), 100)
+    out["fibonacci"] = ("gray", fibonacci_image(), 50)
+    for name, (mode, _, _) in past_one_pass_shapes().items():
+        out[name] = (mode, past_one_pass_image(name), 50)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def edge_reference_files():
+    """{name: bytes} of the restatement, computed once."""
+    return {name: JR.encode(im, q, MODES[mode][1]) for name, (mode, im, q) in edge_cases().items()}
+
+
 COMPARE_CASES = [(mode, q, h, w) for mode in MODES for q in (50, 75, 95) for h, w in ((48, 64), (64, 48), (90, 120))]
 
 

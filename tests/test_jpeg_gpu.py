@@ -45,6 +45,31 @@ def test_bytes_equal_the_restatement(gpu_device, mode):
     assert JR.read_jpeg(got[keys.index((f"ramp+noise {8 * JC.R + 1} MCUs", 50))], 50)["n_intervals"] == 9
 
 
+@pytest.mark.parametrize("group", ["tokens and tables", "past one pass"])
+def test_edge_cases_equal_the_restatement(gpu_device, group):
+    """jpeg_cases.edge_cases in one batch a group: blocks that code one, two and three ZRLs and end without an EOB, DC
+    differences of category 11, a table whose unlimited code is 17 deep (limit 16 on the device, in a file of 264
+    intervals); and files of 256, 257, 513 and 260 intervals, where the finish kernel takes more than one pass.  Every file is
+    the restatement's (tests/test_jpeg_host.py judges those alone) and the strict reader reports the intervals."""
+    from pegasus_amd import jpeg
+    cases, want = JC.edge_cases(), JC.edge_reference_files()
+    past = set(JC.past_one_pass_shapes())
+    names = [n for n in cases if (n in past) == (group == "past one pass")]
+    assert len(names) == (4 if group == "past one pass" else 5)
+    got = jpeg.encode_batch_bytes([dev(cases[n][1], gpu_device) for n in names], quality=[cases[n][2] for n in names],
+                                  subsampling=[JC.MODES[cases[n][0]][1] for n in names])
+    wrong = [(n, len(g), len(want[n])) for n, g in zip(names, got) if g != want[n]]
+    assert not wrong, wrong
+    for n, data in zip(names, got):
+        mode, image, q = cases[n]
+        info = JR.read_jpeg(data, q)
+        assert (info["width"], info["height"]) == image.shape[1::-1]
+        assert info["n_intervals"] == -(-np.prod(JR.shape(image.shape[1], image.shape[0], *JC.MODES[mode])[:2]) // JC.R)
+        if n in past or n == "fibonacci":
+            assert info["n_intervals"] >= 256
+            assert n == "fibonacci" or info["n_intervals"] == int(n.split()[0])
+
+
 def test_one_batch_mixes_kinds_sizes_qualities_and_subsamplings(gpu_device):
     from pegasus_amd import jpeg
     jobs = [("gray", "noise 17x17", 95), ("420", "rendered-like", 50), ("444", "ramp", 100), ("gray", "ramp", 1),

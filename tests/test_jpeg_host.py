@@ -135,6 +135,114 @@ def test_the_device_builder_and_the_restatement_build_the_same_lengths():
         assert png.code_lengths(freq, 15).tolist() == JR.code_lengths(freq.tolist(), 15)
 
 
+# ---- the edge cases of jpeg_cases.edge_cases, judged on the restatement alone ------------------------------------------------------
+def _tokens_of(name):
+    """[(component, [(table offset, symbol, size, extra)])] of every block of an edge case, DC predictors as the scan has them."""
+    mode, image, q = JC.edge_cases()[name]
+    blocks, bpm = JR.scan_blocks(image, q, JC.MODES[mode][1])
+    out = []
+    for first in range(0, len(blocks), JC.R * bpm):
+        pred = [0, 0, 0]
+        for comp, zz in blocks[first:first + JC.R * bpm]:
+            out.append((comp, JR.block_tokens(zz, pred[comp])))
+            pred[comp] = int(zz[0])
+    return out
+
+
+def _reader_gives_back_the_coefficients(name):
+    mode, image, q = JC.edge_cases()[name]
+    sub = JC.MODES[mode][1]
+    ql, qc = JR.quant_tables(q)
+    want = [JR.quantise(s, ql if i == 0 else qc)[..., JR.NAT_OF_ZZ] for i, s in enumerate(JR.component_blocks(image, sub))]
+    info = JR.read_jpeg(JC.edge_reference_files()[name], q)
+    for a, b in zip(want, info["coefficients"]):
+        np.testing.assert_array_equal(a, b)
+    return info
+
+
+def _dht_bits(data):
+    """bits[1..16] of every table of a file's DHT, as lists of 17."""
+    at = data.index(b"\xff\xc4")
+    body = data[at + 4:at + 2 + int.from_bytes(data[at + 2:at + 4], "big")]
+    out, pos = [], 0
+    while pos < len(body):
+        bits = [0] + list(body[pos + 1:pos + 17])
+        out.append(bits)
+        pos += 17 + sum(bits)
+    return out
+
+
+@pytest.mark.parametrize("mode", ["gray", "420"])
+def test_single_coefficient_blocks_code_up_to_three_zrls_and_no_eob(mode):
+    """Every block of the token image quantises to the one coefficient it was built from (or to none), in luminance and, at
+    4:2:0, in both chroma components; one, two and three ZRLs in a row are coded in each AC table, and the blocks whose
+    coefficient 63 is not zero end without an EOB."""
+    name = f"tokens {mode}"
+    _, image, q = JC.edge_cases()[name]
+    info = _reader_gives_back_the_coefficients(name)
+    for comp, grid in enumerate(info["coefficients"]):
+        found = sorted((int(k), int(zz[k])) for zz in grid.reshape(-1, 64) for k in np.flatnonzero(zz))
+        assert (grid.reshape(-1, 64) != 0).sum(axis=1).max() == 1 and not grid[..., 0].any()
+        assert found == sorted((k, v) for k in JC.TOKEN_KS for v in (1, -2)), (comp, found)
+    for table in ((1,) if mode == "gray" else (1, 3)):
+        zrls, no_eob = set(), 0
+        for comp, tokens in _tokens_of(name):
+            ac = [s for t, s, _, _ in tokens if t == 1]
+            if 2 * min(comp, 1) + 1 != table or ac == [0x00]:
+                continue
+            zrls.add(ac.count(0xF0))
+            assert ac[:ac.count(0xF0)] == [0xF0] * ac.count(0xF0)                 # in a row, in front of the coefficient's symbol
+            no_eob += ac[-1] != 0x00
+        assert zrls == {1, 2, 3} and no_eob == 2 * (1 if mode == "gray" or table == 1 else 2), (table, zrls, no_eob)
+    from PIL import Image
+    with Image.open(io.BytesIO(JC.edge_reference_files()[name])) as im:
+        assert im.size == image.shape[1::-1]
+        im.load()
+
+
+@pytest.mark.parametrize("mode", ["gray", "420"])
+def test_black_and_white_blocks_code_dc_category_11(mode):
+    name = f"dc 11 {mode}"
+    _reader_gives_back_the_coefficients(name)
+    dc = [(size, extra) for comp, tokens in _tokens_of(name) for t, s, size, extra in tokens if t == 0 and comp == 0]
+    assert {s for s, _ in dc} >= {11} and max(s for s, _ in dc) == 11
+    # both signs: +2040 is 11111111000, -2040 its complement (a first block of black codes -1024: 01111111111)
+    assert {e for s, e in dc if s == 11} >= {2040, 2047 - 2040}
+
+
+def test_the_fibonacci_blocks_need_the_limit_of_16():
+    """On the restatement alone: the counts are what the case promises, their unlimited code is deeper than 16, the limited
+    table has a 16-bit code in the DHT, the file has 264 intervals, the reader gives back the coefficients and PIL decodes it."""
+    from PIL import Image
+    _, image, q = JC.edge_cases()["fibonacci"]
+    counts = [0] * 256
+    for comp, tokens in _tokens_of("fibonacci"):
+        for t, s, _, _ in tokens:
+            if t == 1:
+                counts[s] += 1
+    assert [counts[((k - 1) << 4) | 1] for k in range(1, 17)] == list(JC.FIBONACCI_COUNTS) and counts[0] == 66 * 64
+    assert sum(1 for c in counts if c) == 17
+    depth = JC.shallowest_huffman_depth([c for c in counts if c] + [1])
+    bits = _dht_bits(JC.edge_reference_files()["fibonacci"])[1]
+    print("fibonacci: shallowest unlimited depth", depth, "AC bits", bits[1:])
+    assert depth == 17 > 16
+    assert bits[16] >= 1 and sum(bits) == 17
+    assert bits[1:] == JR.huffman_table(counts)[0][1:]
+    info = _reader_gives_back_the_coefficients("fibonacci")
+    assert info["n_intervals"] == 264 > 256
+    with Image.open(io.BytesIO(JC.edge_reference_files()["fibonacci"])) as im:
+        decoded = np.asarray(im).astype(np.int64)
+    print("fibonacci: PIL's decode is within", int(np.abs(decoded - image).max()), "of the source")
+    assert decoded.shape == image.shape
+
+
+def test_files_past_one_pass_have_the_intervals_they_are_named_for():
+    for name, (mode, across, down) in JC.past_one_pass_shapes().items():
+        _, image, q = JC.edge_cases()[name]
+        info = JR.read_jpeg(JC.edge_reference_files()[name], q)
+        assert info["n_intervals"] == int(name.split()[0]) == -(-across * down // JC.R) and max(image.shape[:2]) <= 16384
+
+
 # ---- bop_dataset -------------------------------------------------------------------------------------------------------------
 def _scene(root, ext, gray=False):
     from PIL import Image

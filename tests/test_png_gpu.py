@@ -10,90 +10,13 @@ import heapq
 import numpy as np
 import pytest
 
+import png_cases as PC
 import png_reference as PR
 
 pytestmark = pytest.mark.gpu
 
-S = PR.segment_bytes()
-BPP = (1, 3, 2)
-KIND_NAMES = ("gray8", "rgb8", "gray16")
-
-
-def shape_with_raw(target: int, kind: int):
-    """(W, H) whose raw stream, H rows of 1 + W * bpp bytes, has exactly ``target`` bytes; None when no shape has."""
-    bpp = BPP[kind]
-    for h in range(1, target + 1):
-        if target % h == 0 and (target // h - 1) >= bpp and (target // h - 1) % bpp == 0:
-            return (target // h - 1) // bpp, h
-    return None
-
-
-def sizes_of(kind: int):
-    """name -> (W, H): 1 x 1, one row, one column, a raw stream of S - 1, S, S + 1 bytes where the kind's row length allows
-    it (a 16-bit row has an odd length, so no 16-bit image has a power of two of raw bytes), a row across a segment edge,
-    three segments."""
-    bpp = BPP[kind]
-    out = {"1x1": (1, 1), "row": (37, 1), "column": (1, 53)}
-    for name, target in (("S-1", S - 1), ("S", S), ("S+1", S + 1)):
-        shape = shape_with_raw(target, kind)
-        if shape is not None:
-            out[name] = shape
-    w = (S // 3 - 50) // bpp                                   # row 3 starts in front of byte S and ends behind it
-    assert 3 * (1 + w * bpp) < S < 4 * (1 + w * bpp)
-    out["straddle"] = (w, 7)
-    out["3 segments"] = (100, -(-(2 * S + 1) // (1 + 100 * bpp)))
-    assert 2 * S < PR.raw_bytes(*out["3 segments"], kind) <= 3 * S
-    return out
-
-
-def ellipse(h, w):
-    y, x = np.mgrid[0:h, 0:w]
-    return ((((x - (w - 1) / 2) / max(w * 0.37, 0.6)) ** 2 + ((y - (h - 1) / 2) / max(h * 0.41, 0.6)) ** 2) <= 1).astype(np.uint8)
-
-
-def contents_of(kind: int, w: int, h: int, rng):
-    """name -> (array as stored, scale, array the file must hold)."""
-    dtype = np.uint16 if kind == PR.GRAY16 else np.uint8
-    shape = (h, w, 3) if kind == PR.RGB8 else (h, w)
-    top = np.iinfo(dtype).max
-    out = {"zero": np.zeros(shape, dtype), "all ones": np.full(shape, top, dtype),
-           "random": rng.integers(0, int(top) + 1, shape, dtype=dtype)}
-    out = {k: (v, 1, v) for k, v in out.items()}
-    if kind == PR.GRAY8:
-        m = ellipse(h, w)
-        out["ellipse mask"] = (m, 255, m * np.uint8(255))
-    if kind == PR.GRAY16:
-        y, x = np.mgrid[0:h, 0:w]
-        ramp = (700.0 + 3.25 * x + 11.5 * y + 40.0 * np.sin(x / 9.0)).astype(np.uint16)          # millimetres of a tilted plane
-        out["depth ramp"] = (ramp, 1, ramp)
-    if kind == PR.RGB8:
-        y, x = np.mgrid[0:h, 0:w]
-        palette = np.array([[0, 0, 0], [214, 92, 92], [92, 214, 133], [92, 133, 214]], np.uint8)
-        sem = palette[((x // 11 + y // 5) % 4) * (ellipse(h, w) > 0)]
-        out["semantic"] = (sem, 1, sem)
-    return out
-
-
-def place(array, mode: int, device):
-    """The array on the device: packed (0), as a crop of a wider tensor (1: the row stride differs), or with a pixel stride of
-    its own (2: every other gray sample, the first three of four channels)."""
-    import torch
-    a = np.ascontiguousarray(array)
-    store = a.view(np.int16) if a.dtype == np.uint16 else a                    # int16 storage of uint16, as pack_frames has it
-    t = torch.from_numpy(store.copy())
-    if mode == 1:
-        wide = torch.full((t.shape[0], t.shape[1] + 5) + tuple(t.shape[2:]), 77, dtype=t.dtype)
-        wide[:, 2:2 + t.shape[1]] = t
-        return wide.to(device)[:, 2:2 + t.shape[1]]
-    if mode == 2 and t.dim() == 2:
-        wide = torch.full((t.shape[0], t.shape[1], 2), 77, dtype=t.dtype)
-        wide[:, :, 1] = t
-        return wide.to(device)[:, :, 1]
-    if mode == 2:
-        wide = torch.full((t.shape[0], t.shape[1], 4), 77, dtype=t.dtype)
-        wide[:, :, 1:] = t
-        return wide.to(device)[:, :, 1:]
-    return t.to(device)
+S, BPP, KIND_NAMES = PC.S, PC.BPP, PC.KIND_NAMES
+shape_with_raw, sizes_of, ellipse, contents_of, place = PC.shape_with_raw, PC.sizes_of, PC.ellipse, PC.contents_of, PC.place
 
 
 def check_file(data, expected, kind):
