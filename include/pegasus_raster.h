@@ -577,6 +577,48 @@ int32_t pgr_mesh_shade(const float *vertices, int64_t n_vertices, const int32_t 
                        const PgrMeshJob *jobs, int32_t width, int32_t height, float near_z, const uint64_t *keys,
                        int32_t n_slots, const PgrMeshShade *shade, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Textured object models (BOP's obj_NNNNNN.ply with texture coordinates and a PNG beside it; the toolkit's renderers draw them
+ * with texture2D(u_texture, v_texcoord)).  pgr_mesh_shade_textured takes every argument of pgr_mesh_shade, resolves the same
+ * `keys`, and reads the colour of a textured job from its texture.  Rule (pinned above mesh_shade_kernel in
+ * pegasus_amd/csrc/meshraster.hip.h, restated in tests/mesh_texture_reference.py, which the outputs equal bit for bit; float32,
+ * no contraction, correctly rounded division):
+ *   uv        the attribute rule of pgr_mesh_shade on corner_uv[face][a, b, c] (b's and c's values swapped when the face was
+ *             flipped): perspective-correct.  The optional output `uv` receives it for every covered pixel, 0 where empty
+ *   texture   width x height texels of 3 bytes (RGB), rows tightly packed, at `offset` bytes into `texels`; stored row 0 is the
+ *             image's top row and v = 0 is its BOTTOM row (stored row = height - 1 - j); clamp to edge:
+ *             clamp(x, n) = x >= 0 ? (x < n ? (int)x : n - 1) : 0, so a NaN gives index 0
+ *   nearest   i = clamp(floorf(u * width), width), j = clamp(floorf(v * height), height), colour = (float)texel / 255.0f
+ *   bilinear  x = u * width - 0.5f, x0 = floorf(x), fx = x - x0 (0 when that is a NaN), i0 = clamp(x0), i1 = clamp(x0 + 1); y
+ *             alike; top = (1 - fx) c00 + fx c10, bot = (1 - fx) c01 + fx c11, colour = (1 - fy) top + fy bot
+ *   rgb       light_w * colour, light_w as in pgr_mesh_shade.  A job whose job_texture is -1 is untextured: it follows
+ *             pgr_mesh_shade's colour rule, and every output of it equals pgr_mesh_shade's bit for bit
+ * No alignment is asked of `texels` or of an offset.  Workspace (the job table and one texture row per job):
+ * pgr_mesh_shade_textured_workspace_bytes(n_jobs, jobs), host-only, 0 for bad arguments; 8-byte aligned.  Invalid
+ * (PGR_ERR_INVALID_ARGUMENT, before any launch): whatever pgr_mesh_shade refuses, a NULL `textures`, n_textures < 0, a NULL
+ * table with n_textures > 0, a NULL job_texture, a job_texture outside [-1, n_textures), a texture side outside 1..8192, an
+ * offset plus 3 width height beyond texel_bytes, an unknown filter, and a NULL corner_uv or texels when a job is textured. */
+#define PGR_TEXTURE_NEAREST 0
+#define PGR_TEXTURE_BILINEAR 1
+typedef struct PgrMeshTexture {
+    int64_t offset;            /* bytes from `texels` to the texture's top-left texel */
+    int32_t width, height;     /* texels, each 1..8192 */
+} PgrMeshTexture;
+typedef struct PgrMeshTextures {
+    const float *corner_uv;          /* device float32 [n_faces,3,2]: (u, v) per face corner in the order of `faces`; NULL: no uv */
+    const uint8_t *texels;           /* device uint8: every texture, RGB */
+    int64_t texel_bytes;
+    int32_t n_textures;
+    const PgrMeshTexture *textures;  /* HOST [n_textures] */
+    const int32_t *job_texture;      /* HOST int32 [n_jobs]: a texture index, or -1 for an untextured job */
+    int32_t filter;                  /* PGR_TEXTURE_NEAREST or PGR_TEXTURE_BILINEAR */
+    float *uv;                       /* output, device float32 [n_slots,height,width,2], may be NULL */
+} PgrMeshTextures;
+size_t pgr_mesh_shade_textured_workspace_bytes(int32_t n_jobs, const PgrMeshJob *jobs);
+int32_t pgr_mesh_shade_textured(const float *vertices, int64_t n_vertices, const int32_t *faces, int64_t n_faces, int32_t n_jobs,
+                                const PgrMeshJob *jobs, int32_t width, int32_t height, float near_z, const uint64_t *keys,
+                                int32_t n_slots, const PgrMeshShade *shade, const PgrMeshTextures *textures, void *workspace,
+                                size_t workspace_bytes, void *stream);
+
 /* BOP ground truth of n_jobs (object, image) pairs from depth canvases, the sequence of the toolkit's
  * scripts/calc_gt_info.py:117-177.  Job k reads canvas `slot` of `canvases` [n_slots,canvas_height,canvas_width] (as
  * pgr_mesh_depth leaves it) and image `frame` of `scene_depth` [n_frames,height,width] (same unit, 0 = missing); the image
@@ -1066,6 +1108,35 @@ int32_t pgr_mesh_vertex_colors(int32_t n_vertices, const float *vertices, const 
                                const PgrCamera *cameras, const float *color, const float *depth, const float *final_T,
                                float depth_tol, float alpha_min, float cos_min, const float *fill, float *colors,
                                int32_t *seen, void *stream);
+
+/* A texture for a mesh: a per-face atlas baked from the same views (pegasus_amd/mesh.py bake_texture).  The rules are pinned in
+ * pegasus_amd/csrc/meshattr.hip.h and restated in tests/mesh_texture_reference.py, which the outputs equal bit for bit.
+ * Layout: cell side `cell` = s >= 4 texels, leg L = s - 3, cells = ceil(n_faces / 2), cols = the smallest integer with
+ * cols^2 >= cells, rows = ceil(cells / cols); `width` = cols s and `height` = rows s, each at most 8192, must be handed in as
+ * such (pegasus_amd.mesh.texture_atlas_layout).  Face f lies in cell f >> 1, half f & 1; the cell's origin is ((c % cols) s,
+ * (c / cols) s) from the top-left; texel (i, j) of a cell belongs to half 0 when i + j <= s - 1; in texel-centre coordinates half
+ * 0 has its corners at (0.5, 0.5), (0.5 + L, 0.5), (0.5, 0.5 + L) and half 1 is its mirror image through the cell's centre.
+ *
+ * pgr_mesh_atlas_points: one lane per texel writes `points` and `normals` (device float32 [height*width,3]) and `face_of_texel`
+ * (device int32 [height*width]): the owning face, or -1 (with zeros) where the half has no face, a face index is outside
+ * [0, n_vertices) or the face normal's length is zero or not finite.  (di, dj) = (i, j) in half 0, (s - 1 - i, s - 1 - j) in half
+ * 1; p = (A + (di / L) (B - A)) + (dj / L) (C - A) in float32, every operation rounded on its own; the normal is
+ * cross(B - A, C - A) normalised (pgr_mesh_shade's flat rule in the model frame, no flip).  The colours of the points come from
+ * pgr_mesh_vertex_colors, unchanged.
+ *
+ * pgr_mesh_atlas_pack: `colors` (device float32 [height*width,3], in [0,1]) and `seen` (device int32 [height*width]) to
+ * `texture` (device uint8 [height,width,3]).  A texel of a face with seen > 0 gets (uint8)rintf(255 c) (a NaN gives 0); the face's
+ * other texels get the mean of those, (2 sum + cnt) / (2 cnt) in integers, or, when it has none, row f of `face_fill` (device
+ * uint8 [n_faces,3]; NULL: `fill`); texels of no face get `fill` (HOST uint8 [3]).  `face_seen` (device int32 [n_faces], may be
+ * NULL) receives cnt.  One wave per cell, integer reductions: two runs give equal bytes.
+ * Invalid (PGR_ERR_INVALID_ARGUMENT, before any launch): n_faces < 1, cell < 4, a size that is not the layout's or beyond 8192, a
+ * NULL among the pointers not marked optional. */
+int32_t pgr_mesh_atlas_points(int32_t n_vertices, const float *vertices, int32_t n_faces, const int32_t *faces, int32_t cell,
+                              int32_t width, int32_t height, float *points, float *normals, int32_t *face_of_texel,
+                              void *stream);
+int32_t pgr_mesh_atlas_pack(int32_t n_faces, int32_t cell, int32_t width, int32_t height, const int32_t *face_of_texel,
+                            const float *colors, const int32_t *seen, const uint8_t *face_fill, const uint8_t *fill,
+                            uint8_t *texture, int32_t *face_seen, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------------
  * Collision geometry: signed distance fields of triangle meshes and distance / sweep queries between posed bodies

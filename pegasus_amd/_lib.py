@@ -151,6 +151,19 @@ class PgrMeshShade(C.Structure):
 PGR_MESH_VISIBILITY_MAX_JOBS = 1024      # include/pegasus_raster.h
 
 
+class PgrMeshTexture(C.Structure):
+    _fields_ = [("offset", C.c_int64), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+class PgrMeshTextures(C.Structure):
+    _fields_ = [("corner_uv", C.c_void_p), ("texels", C.c_void_p), ("texel_bytes", C.c_int64), ("n_textures", C.c_int32),
+                ("textures", C.POINTER(PgrMeshTexture)), ("job_texture", C.POINTER(C.c_int32)), ("filter", C.c_int32),
+                ("uv", C.c_void_p)]
+
+
+PGR_TEXTURE_NEAREST, PGR_TEXTURE_BILINEAR = 0, 1
+
+
 class PgrGtInfoJob(C.Structure):
     _fields_ = [("slot", C.c_int32), ("frame", C.c_int32), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double),
                 ("cy", C.c_double)]
@@ -351,6 +364,10 @@ SYMBOLS = {
     "pgr_mesh_shade": (C.c_int32, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(PgrMeshJob), C.c_int32,
                                    C.c_int32, C.c_float, C.c_void_p, C.c_int32, C.POINTER(PgrMeshShade), C.c_void_p,
                                    C.c_size_t, C.c_void_p]),
+    "pgr_mesh_shade_textured_workspace_bytes": (C.c_size_t, [C.c_int32, C.POINTER(PgrMeshJob)]),
+    "pgr_mesh_shade_textured": (C.c_int32, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(PgrMeshJob),
+                                            C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_int32, C.POINTER(PgrMeshShade),
+                                            C.POINTER(PgrMeshTextures), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pgr_bop_gt_info": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                     C.c_int32, C.c_int32, C.c_int32, C.POINTER(PgrGtInfoJob), C.c_float, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -403,6 +420,10 @@ SYMBOLS = {
     "pgr_mesh_vertex_colors": (C.c_int32, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(PgrCamera), C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float),
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pgr_mesh_atlas_points": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pgr_mesh_atlas_pack": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.POINTER(C.c_uint8), C.c_void_p, C.c_void_p, C.c_void_p]),
     "pgr_mesh_sdf": (C.c_int32, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(PgrGrid), C.c_void_p, C.c_void_p,
                                  C.c_void_p]),
     "pgr_sdf_sample": (C.c_int32, [C.POINTER(PgrGrid), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -316,17 +316,56 @@ size_t pgr_mesh_shade_workspace_bytes(int32_t n_jobs, const PgrMeshJob* jobs) {
     return align_up((size_t)n_jobs * sizeof(MeshShadeJobDev), 256);
 }
 
-int32_t pgr_mesh_shade(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int32_t n_jobs,
-                       const PgrMeshJob* jobs, int32_t width, int32_t height, float near_z, const uint64_t* keys,
-                       int32_t n_slots, const PgrMeshShade* shade, void* workspace, size_t workspace_bytes, void* stream_v) {
+// pgr_mesh_shade_textured's workspace: the job table, then one MeshJobTexDev per job
+size_t pgr_mesh_shade_textured_workspace_bytes(int32_t n_jobs, const PgrMeshJob* jobs) {
+    const size_t table = pgr_mesh_shade_workspace_bytes(n_jobs, jobs);
+    return table ? table + align_up((size_t)n_jobs * sizeof(MeshJobTexDev), 256) : 0;
+}
+
+namespace {
+// what pgr_mesh_shade_textured asks of its textures beyond pgr_mesh_shade's arguments
+bool mesh_textures_ok(const PgrMeshTextures* tex, int32_t n_jobs) {
+    if (!tex || tex->n_textures < 0 || tex->texel_bytes < 0 || (tex->n_textures > 0 && !tex->textures) || (n_jobs > 0 && !tex->job_texture) ||
+        (tex->filter != PGR_TEXTURE_NEAREST && tex->filter != PGR_TEXTURE_BILINEAR))
+        return false;
+    for (int32_t q = 0; q < tex->n_textures; ++q) {
+        const PgrMeshTexture& t = tex->textures[q];
+        if (t.width < 1 || t.width > MESHR_MAX_CANVAS || t.height < 1 || t.height > MESHR_MAX_CANVAS || t.offset < 0 ||
+            t.offset > tex->texel_bytes || (int64_t)t.width * t.height * 3 > tex->texel_bytes - t.offset)
+            return false;
+    }
+    bool any = false;
+    for (int32_t k = 0; k < n_jobs; ++k) {
+        if (tex->job_texture[k] < -1 || tex->job_texture[k] >= tex->n_textures) return false;
+        any = any || tex->job_texture[k] >= 0;
+    }
+    return !any || (tex->corner_uv && tex->texels);
+}
+
+// pgr_mesh_shade (tex == NULL) and pgr_mesh_shade_textured: the job table through the workspace, then one launch
+int32_t mesh_shade_run(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int32_t n_jobs,
+                       const PgrMeshJob* jobs, int32_t width, int32_t height, float near_z, const uint64_t* keys, int32_t n_slots,
+                       const PgrMeshShade* shade, const PgrMeshTextures* tex, void* workspace, size_t workspace_bytes, void* stream_v) {
     if (n_jobs > MESHV_MAX_JOBS || !keys || !shade || std::isnan(shade->ambient) || reinterpret_cast<uintptr_t>(keys) % sizeof(uint64_t) ||
-        reinterpret_cast<uintptr_t>(workspace) % alignof(MeshShadeJobDev) ||
-        !mesh_call_ok(vertices, n_vertices, faces, n_faces, n_jobs, jobs, width, height, near_z, n_slots))
+        reinterpret_cast<uintptr_t>(workspace) % (tex ? alignof(MeshJobTexDev) : alignof(MeshShadeJobDev)) ||
+        !mesh_call_ok(vertices, n_vertices, faces, n_faces, n_jobs, jobs, width, height, near_z, n_slots) ||
+        (tex && !mesh_textures_ok(tex, n_jobs)))
         return PGR_ERR_INVALID_ARGUMENT;
-    const size_t need = pgr_mesh_shade_workspace_bytes(n_jobs, jobs);
+    const size_t need = tex ? pgr_mesh_shade_textured_workspace_bytes(n_jobs, jobs) : pgr_mesh_shade_workspace_bytes(n_jobs, jobs);
     if (n_jobs > 0 && (!need || !workspace || workspace_bytes < need)) return PGR_ERR_WORKSPACE_TOO_SMALL;
     hipStream_t stream = as_stream(stream_v);
     auto* table = static_cast<MeshShadeJobDev*>(workspace);
+    auto* tex_table = tex && n_jobs > 0 ? ws_at<MeshJobTexDev>(workspace, pgr_mesh_shade_workspace_bytes(n_jobs, jobs)) : nullptr;
+    for (int32_t k0 = 0; tex && k0 < n_jobs; k0 += MESHR_JOBS_PER_LAUNCH) {
+        MeshTexTable T{};
+        T.count = std::min(MESHR_JOBS_PER_LAUNCH, n_jobs - k0);
+        T.first = k0;
+        for (int32_t k = 0; k < T.count; ++k) {
+            const int32_t q = tex->job_texture[k0 + k];
+            if (q >= 0) T.tex[k] = MeshJobTexDev{(unsigned long long)tex->textures[q].offset, tex->textures[q].width, tex->textures[q].height};
+        }
+        mesh_tex_table_kernel<<<1, 64, 0, stream>>>(T, tex_table);
+    }
     for (int32_t k0 = 0; k0 < n_jobs; k0 += MESHR_JOBS_PER_LAUNCH) {
         MeshShadeTable T{};
         T.count = std::min(MESHR_JOBS_PER_LAUNCH, n_jobs - k0);
@@ -349,8 +388,33 @@ int32_t pgr_mesh_shade(const float* vertices, int64_t n_vertices, const int32_t*
     const dim3 grid((unsigned)((width + MESHS_TILE_W - 1) / MESHS_TILE_W),
                     (unsigned)((height + MESHS_TILE_H * (MESHS_THREADS / WAVE) - 1) / (MESHS_TILE_H * (MESHS_THREADS / WAVE))),
                     (unsigned)std::min(n_slots, 65535));
-    mesh_shade_kernel<<<grid, MESHS_THREADS, 0, stream>>>(A);
-    return launch_status("mesh_shade launch");
+    if (!tex) {
+        mesh_shade_kernel<false><<<grid, MESHS_THREADS, 0, stream>>>(A, MeshTextureArgs{});
+        return launch_status("mesh_shade launch");
+    }
+    MeshTextureArgs X{};
+    X.corner_uv = tex->corner_uv; X.texels = tex->texels; X.job_tex = tex_table;
+    X.bilinear = tex->filter == PGR_TEXTURE_BILINEAR ? 1 : 0;
+    X.uv = tex->uv;
+    mesh_shade_kernel<true><<<grid, MESHS_THREADS, 0, stream>>>(A, X);
+    return launch_status("mesh_shade_textured launch");
+}
+}  // namespace
+
+int32_t pgr_mesh_shade(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int32_t n_jobs,
+                       const PgrMeshJob* jobs, int32_t width, int32_t height, float near_z, const uint64_t* keys,
+                       int32_t n_slots, const PgrMeshShade* shade, void* workspace, size_t workspace_bytes, void* stream_v) {
+    return mesh_shade_run(vertices, n_vertices, faces, n_faces, n_jobs, jobs, width, height, near_z, keys, n_slots, shade, nullptr,
+                          workspace, workspace_bytes, stream_v);
+}
+
+int32_t pgr_mesh_shade_textured(const float* vertices, int64_t n_vertices, const int32_t* faces, int64_t n_faces, int32_t n_jobs,
+                                const PgrMeshJob* jobs, int32_t width, int32_t height, float near_z, const uint64_t* keys,
+                                int32_t n_slots, const PgrMeshShade* shade, const PgrMeshTextures* textures, void* workspace,
+                                size_t workspace_bytes, void* stream_v) {
+    if (!textures) return PGR_ERR_INVALID_ARGUMENT;
+    return mesh_shade_run(vertices, n_vertices, faces, n_faces, n_jobs, jobs, width, height, near_z, keys, n_slots, shade, textures,
+                          workspace, workspace_bytes, stream_v);
 }
 
 int32_t pgr_bop_gt_info(const float* canvases, int32_t n_slots, int32_t canvas_width, int32_t canvas_height, int32_t margin_x,
@@ -626,6 +690,55 @@ int32_t pgr_mesh_vertex_colors(int32_t n_vertices, const float* vertices, const 
     a.seen = seen;
     vertex_colors_kernel<<<attr_blocks(n_vertices), MESHATTR_THREADS, 0, as_stream(stream_v)>>>(a);
     return launch_status("mesh_vertex_colors launch");
+}
+
+namespace {
+// the per-face atlas of meshattr.hip.h; width == 0: refused
+struct AtlasLayout { int32_t cols, rows, width, height; };
+AtlasLayout atlas_layout(int32_t n_faces, int32_t cell) {
+    AtlasLayout L{};
+    if (n_faces < 1 || cell < 4 || cell > ATLAS_MAX_SIDE) return L;
+    const int64_t cells = ((int64_t)n_faces + 1) / 2;
+    int64_t cols = (int64_t)std::sqrt((double)cells);
+    while (cols * cols < cells) ++cols;
+    while (cols > 1 && (cols - 1) * (cols - 1) >= cells) --cols;
+    const int64_t rows = (cells + cols - 1) / cols;
+    if (cols * cell > ATLAS_MAX_SIDE || rows * cell > ATLAS_MAX_SIDE) return L;
+    L.cols = (int32_t)cols; L.rows = (int32_t)rows; L.width = (int32_t)(cols * cell); L.height = (int32_t)(rows * cell);
+    return L;
+}
+}  // namespace
+
+int32_t pgr_mesh_atlas_points(int32_t n_vertices, const float* vertices, int32_t n_faces, const int32_t* faces, int32_t cell,
+                              int32_t width, int32_t height, float* points, float* normals, int32_t* face_of_texel, void* stream_v) {
+    const AtlasLayout L = atlas_layout(n_faces, cell);
+    if (n_vertices < 0 || !L.width || width != L.width || height != L.height || !faces || (n_vertices > 0 && !vertices) || !points ||
+        !normals || !face_of_texel)
+        return PGR_ERR_INVALID_ARGUMENT;
+    AtlasArgs a{};
+    a.n_vertices = n_vertices; a.n_faces = n_faces; a.cell = cell; a.cols = L.cols; a.width = width; a.height = height;
+    a.vertices = vertices; a.faces = faces;
+    const size_t texels = (size_t)width * (size_t)height;
+    atlas_points_kernel<<<(unsigned)((texels + MESHATTR_THREADS - 1) / MESHATTR_THREADS), MESHATTR_THREADS, 0, as_stream(stream_v)>>>(
+        a, points, normals, face_of_texel);
+    return launch_status("mesh_atlas_points launch");
+}
+
+int32_t pgr_mesh_atlas_pack(int32_t n_faces, int32_t cell, int32_t width, int32_t height, const int32_t* face_of_texel,
+                            const float* colors, const int32_t* seen, const uint8_t* face_fill, const uint8_t* fill, uint8_t* texture,
+                            int32_t* face_seen, void* stream_v) {
+    const AtlasLayout L = atlas_layout(n_faces, cell);
+    if (!L.width || width != L.width || height != L.height || !face_of_texel || !colors || !seen || !fill || !texture)
+        return PGR_ERR_INVALID_ARGUMENT;
+    AtlasPackArgs a{};
+    a.n_faces = n_faces; a.cell = cell; a.cols = L.cols; a.width = width; a.height = height;
+    a.n_cells = (long long)L.cols * L.rows;
+    for (int d = 0; d < 3; ++d) a.fill[d] = fill[d];
+    a.face_of_texel = face_of_texel; a.colors = colors; a.seen = seen; a.face_fill = face_fill;
+    a.texture = texture; a.face_seen = face_seen;
+    constexpr int per_block = ATLAS_PACK_THREADS / WAVE;
+    atlas_pack_kernel<<<(unsigned)((a.n_cells + per_block - 1) / per_block), ATLAS_PACK_THREADS, 0, as_stream(stream_v)>>>(a);
+    return launch_status("mesh_atlas_pack launch");
 }
 
 // ---- collision geometry: mesh distance fields, samples and sweeps (meshsdf.hip.h) ----------------------------------------

@@ -157,4 +157,144 @@ __global__ __launch_bounds__(MESHATTR_THREADS) void vertex_colors_kernel(const V
     if (a.seen) a.seen[i] = seen;
 }
 
+// ---- a per-face texture atlas: pgr_mesh_atlas_points, pgr_mesh_atlas_pack ---------------------------------------------------
+// Layout (pegasus_amd.mesh.texture_atlas_layout computes it on the host; the entries check the size they are handed against
+// it).  Cell side s >= 4 texels, leg L = s - 3.  cells = ceil(F / 2), cols = the smallest integer with cols^2 >= cells,
+// rows = ceil(cells / cols); the atlas is cols s wide and rows s high, each at most 8192.  Face f lies in cell c = f >> 1, half
+// f & 1; the cell's origin is ((c % cols) s, (c / cols) s) from the image's top-left.  In cell-local texel-centre coordinates
+// (x right, y down, the centre of texel (i, j) at (i + 0.5, j + 0.5)) half 0 has corner a at (0.5, 0.5), b at (0.5 + L, 0.5),
+// c at (0.5, 0.5 + L); half 1 is its mirror image through the cell's centre: a at (s - 0.5, s - 0.5), b at (s - 0.5 - L,
+// s - 0.5), c at (s - 0.5, s - 0.5 - L).  Texel (i, j) belongs to half 0 when i + j <= s - 1, else to half 1.  In exact
+// arithmetic a sample inside half 0's triangle reads, with non-zero weight, only texels with i + j <= s - 2 and one inside half
+// 1's only texels with i + j >= s, under the nearest and the bilinear filter: the antidiagonal i + j = s - 1 between them takes
+// what float32 rounding of u and of u W adds (tests/test_mesh_texture_host.py checks both).
+//
+// pgr_mesh_atlas_points: one lane per atlas texel.  Its face f = 2 c + half; face_of_texel = -1 (and point = normal = 0) when
+// f >= F, when one of the face's indices is outside [0, V) (never dereferenced), or when the face normal's length is zero or
+// not finite.  Else, float32, every operation rounded on its own:
+//   (di, dj) = (i, j) in half 0, (s - 1 - i, s - 1 - j) in half 1;   beta = (float)di / (float)L,  gamma = (float)dj / (float)L
+//   p = (A + beta (B - A)) + gamma (C - A) per component (texels whose centre lies outside the triangle extrapolate)
+//   normal = m / sqrtf((m.x m.x + m.y m.y) + m.z m.z),  m = (B - A) x (C - A) as pgr_mesh_shade's flat rule, model frame, no flip
+//
+// pgr_mesh_atlas_pack: one wave per cell, the texels of the cell in strides of 64.  A texel counts as its face's when
+// face_of_texel names that face.  Per owned texel with seen > 0:  q = (uint8)rintf(255 c) per channel (a NaN gives 0; c is
+// clamped by pgr_mesh_vertex_colors).  Per face, in integers:  cnt = its seen texels,  sum = the per-channel sum of their q
+// (wave reductions over 64-bit integers: no float atomics, equal bytes from run to run).  Its unseen texels get
+// (2 sum + cnt) / (2 cnt) (the mean rounded half up); with cnt == 0 row f of face_fill (uint8 [F,3]), or `fill` without
+// face_fill.  Texels of no face get `fill`.  face_seen[f] = cnt.
+constexpr int ATLAS_MAX_SIDE = 8192;
+constexpr int ATLAS_PACK_THREADS = 256;                    // four waves: four cells
+
+struct AtlasArgs {
+    int32_t n_vertices, n_faces, cell, cols, width, height;
+    const float* vertices;
+    const int32_t* faces;
+};
+
+__global__ __launch_bounds__(MESHATTR_THREADS) void atlas_points_kernel(const AtlasArgs a, float* __restrict__ points,
+                                                                        float* __restrict__ normals,
+                                                                        int32_t* __restrict__ face_of_texel) {
+    const size_t t = (size_t)blockIdx.x * MESHATTR_THREADS + threadIdx.x;
+    if (t >= (size_t)a.width * (size_t)a.height) return;
+    const int X = (int)(t % (size_t)a.width), Y = (int)(t / (size_t)a.width);
+    const int s = a.cell, L = s - 3;
+    const int cx = X / s, cy = Y / s;
+    const int i = X - cx * s, j = Y - cy * s;
+    const int half = i + j <= s - 1 ? 0 : 1;
+    const long long f = 2ll * ((long long)cy * a.cols + cx) + half;
+    float p[3] = {0.f, 0.f, 0.f}, n[3] = {0.f, 0.f, 0.f};
+    int32_t owner = -1;
+    if (f < (long long)a.n_faces) {
+        const int32_t ia = a.faces[3 * f], ib = a.faces[3 * f + 1], ic = a.faces[3 * f + 2];
+        if ((uint32_t)ia < (uint32_t)a.n_vertices && (uint32_t)ib < (uint32_t)a.n_vertices && (uint32_t)ic < (uint32_t)a.n_vertices) {
+            const float* A = a.vertices + 3 * (size_t)ia;
+            const float* B = a.vertices + 3 * (size_t)ib;
+            const float* C = a.vertices + 3 * (size_t)ic;
+            float e1[3], e2[3];
+#pragma unroll
+            for (int d = 0; d < 3; ++d) { e1[d] = B[d] - A[d]; e2[d] = C[d] - A[d]; }
+            const float mx = e1[1] * e2[2] - e1[2] * e2[1];
+            const float my = e1[2] * e2[0] - e1[0] * e2[2];
+            const float mz = e1[0] * e2[1] - e1[1] * e2[0];
+            const float len = sqrtf((mx * mx + my * my) + mz * mz);
+            if (len > 0.f && len < INFINITY) {
+                owner = (int32_t)f;
+                const int di = half ? s - 1 - i : i, dj = half ? s - 1 - j : j;
+                const float beta = (float)di / (float)L, gamma = (float)dj / (float)L;
+#pragma unroll
+                for (int d = 0; d < 3; ++d) p[d] = (A[d] + beta * e1[d]) + gamma * e2[d];
+                n[0] = mx / len; n[1] = my / len; n[2] = mz / len;
+            }
+        }
+    }
+#pragma unroll
+    for (int d = 0; d < 3; ++d) { points[3 * t + d] = p[d]; normals[3 * t + d] = n[d]; }
+    face_of_texel[t] = owner;
+}
+
+__device__ __forceinline__ unsigned long long atlas_wave_sum(unsigned long long v) {
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) v += __shfl_xor(v, d, WAVE);
+    return v;
+}
+
+__device__ __forceinline__ uint32_t atlas_quantise(float c) {
+    const float v = 255.0f * c;
+    return v == v ? (uint32_t)min(max((int)rintf(v), 0), 255) : 0u;
+}
+
+struct AtlasPackArgs {
+    int32_t n_faces, cell, cols, width, height;
+    long long n_cells;
+    uint8_t fill[3];
+    const int32_t* face_of_texel;
+    const float* colors;                           // [height*width,3]
+    const int32_t* seen;                           // [height*width]
+    const uint8_t* face_fill;                      // [F,3] or NULL
+    uint8_t* texture;                              // [height,width,3]
+    int32_t* face_seen;                            // [F] or NULL
+};
+
+__global__ __launch_bounds__(ATLAS_PACK_THREADS) void atlas_pack_kernel(const AtlasPackArgs a) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const long long c = (long long)blockIdx.x * (ATLAS_PACK_THREADS / WAVE) + threadIdx.x / WAVE;     // wave-uniform
+    if (c >= a.n_cells) return;
+    const int s = a.cell, n = s * s;
+    const size_t x0 = (size_t)(c % a.cols) * s, y0 = (size_t)(c / a.cols) * s;
+    unsigned long long cnt[2] = {0, 0}, sum[2][3] = {{0, 0, 0}, {0, 0, 0}};
+    for (int e = lane; e < n; e += WAVE) {
+        const int j = e / s, i = e - j * s;
+        const int half = i + j <= s - 1 ? 0 : 1;
+        const size_t t = (y0 + j) * (size_t)a.width + x0 + i;
+        if ((long long)a.face_of_texel[t] == 2 * c + half && a.seen[t] > 0) {
+            cnt[half] += 1;
+#pragma unroll
+            for (int d = 0; d < 3; ++d) sum[half][d] += atlas_quantise(a.colors[3 * t + d]);
+        }
+    }
+    uint8_t mean[2][3];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        cnt[h] = atlas_wave_sum(cnt[h]);
+        const long long f = 2 * c + h;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            sum[h][d] = atlas_wave_sum(sum[h][d]);
+            if (cnt[h] > 0) mean[h][d] = (uint8_t)((2 * sum[h][d] + cnt[h]) / (2 * cnt[h]));
+            else mean[h][d] = (a.face_fill && f < a.n_faces) ? a.face_fill[3 * f + d] : a.fill[d];
+        }
+        if (a.face_seen && lane == 0 && f < a.n_faces) a.face_seen[f] = (int32_t)cnt[h];
+    }
+    for (int e = lane; e < n; e += WAVE) {
+        const int j = e / s, i = e - j * s;
+        const int half = i + j <= s - 1 ? 0 : 1;
+        const size_t t = (y0 + j) * (size_t)a.width + x0 + i;
+        const bool owned = (long long)a.face_of_texel[t] == 2 * c + half;
+        const bool seen = owned && a.seen[t] > 0;
+#pragma unroll
+        for (int d = 0; d < 3; ++d)
+            a.texture[3 * t + d] = seen ? (uint8_t)atlas_quantise(a.colors[3 * t + d]) : owned ? mean[half][d] : a.fill[d];
+    }
+}
+
 }  // namespace pgr

@@ -42,6 +42,8 @@
 // bit, what pgr_mesh_depth writes for the same call.
 //
 // pgr_mesh_shade: one lane per canvas pixel turns a key into per-pixel quantities, see the rule above mesh_shade_kernel.
+// pgr_mesh_shade_textured: the same kernel's second instantiation reads a textured job's colour from its texture, see the second
+// rule above mesh_shade_kernel.
 //
 // pgr_bop_gt_info: per canvas pixel the sequence of the toolkit's calc_gt_info.py, see the kernel.
 #pragma once
@@ -94,6 +96,7 @@ struct MeshTri {
 struct MeshCorners {
     int32_t vi[3];
     float P[3][3];
+    int32_t flipped;                                 // b and c were swapped: per-corner attributes swap with them
 };
 
 __device__ __forceinline__ int32_t mesh_snap(float u) {
@@ -148,6 +151,7 @@ __device__ __forceinline__ int mesh_setup(const MeshJobDev& J, const float* __re
     T.area2 = area2;
     if constexpr (CORNERS) {
         const int order[3] = {0, b, c};
+        corners->flipped = b == 2 ? 1 : 0;
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
             corners->vi[q] = vid[order[q]];
@@ -380,7 +384,79 @@ __device__ __forceinline__ void mesh_store3(float* out, size_t p, float x, float
     out[3 * p + 0] = x; out[3 * p + 1] = y; out[3 * p + 2] = z;
 }
 
-__global__ __launch_bounds__(MESHS_THREADS) void mesh_shade_kernel(const MeshShadeArgs A) {
+// ---- pgr_mesh_shade_textured: the same resolve, the colour read from a texture ------------------------------------------
+// The second instantiation of mesh_shade_kernel.  Everything above holds unchanged; in addition (float32, no contraction,
+// correctly rounded division; tests/mesh_texture_reference.py restates it in NumPy):
+//
+//   uv          (u, v) = the attribute rule on the face's three corner values corner_uv[face][a, b, c], b's and c's swapped
+//               when the face was flipped: perspective-correct, like xyz.  Written for every covered pixel when corner_uv
+//               is given (whatever the job's texture), 0 where empty or without corner_uv.
+//   Texture.    W x H texels of 3 bytes, rows tightly packed at a byte offset of the texel buffer; stored row 0 is the
+//               image's top row.  v = 0 is the image's BOTTOM row (the toolkit flips the image before OpenGL sees it):
+//               texel (i, j) is stored at row H - 1 - j.  Clamp to edge:
+//                   clamp(x, n) = x >= 0 ? (x < n ? (int)x : n - 1) : 0          (so a NaN gives index 0)
+//   nearest     i = clamp(floorf(u * W), W),  j = clamp(floorf(v * H), H),  colour = (float)texel / 255.0f.
+//   bilinear    x = u * W - 0.5f,  x0 = floorf(x),  fx = x - x0 (0 when that is a NaN: a NaN or infinite coordinate),
+//               i0 = clamp(x0, W),  i1 = clamp(x0 + 1, W);  y, y0, fy, j0, j1 alike from v and H.  With c = (float)texel / 255.0f:
+//                   top = (1 - fx) c(i0, j0) + fx c(i1, j0),   bot = (1 - fx) c(i0, j1) + fx c(i1, j1),
+//                   colour = (1 - fy) top + fy bot             every operation rounded on its own.
+//   rgb         light_w * colour with light_w as above.  A job whose texture index is -1 follows the colour rule above
+//               (vertex colours or its surf colour): all its outputs are pgr_mesh_shade's, bit for bit.
+// Plain byte loads: gfx950 has no image-sampling path for HIP, and the result is pinned bit for bit anyway.
+struct MeshJobTexDev {
+    unsigned long long offset;                       // of the texture's first byte in the texel buffer
+    int32_t w, h;                                    // w == 0: the job is untextured
+};
+
+struct MeshTexTable {
+    int32_t count, first;
+    MeshJobTexDev tex[MESHR_JOBS_PER_LAUNCH];
+};
+
+struct MeshTextureArgs {
+    const float* corner_uv;
+    const uint8_t* texels;
+    const MeshJobTexDev* job_tex;
+    int32_t bilinear;
+    float* uv;
+};
+
+__global__ __launch_bounds__(64) void mesh_tex_table_kernel(const MeshTexTable T, MeshJobTexDev* __restrict__ table) {
+    if ((int)threadIdx.x < T.count) table[T.first + threadIdx.x] = T.tex[threadIdx.x];
+}
+
+__device__ __forceinline__ int mesh_tex_clamp(float x, int n) { return x >= 0.f ? (x < (float)n ? (int)x : n - 1) : 0; }
+
+// channel d of texel (i, j), j counted from the image's bottom row
+__device__ __forceinline__ float mesh_texel(const uint8_t* __restrict__ tex, int w, int h, int i, int j, int d) {
+    return (float)tex[((size_t)(h - 1 - j) * (size_t)w + (size_t)i) * 3 + d] / 255.0f;
+}
+
+__device__ __forceinline__ void mesh_tex_sample(const uint8_t* __restrict__ tex, int w, int h, float u, float v, bool bilinear,
+                                                float col[3]) {
+    if (!bilinear) {
+        const int i = mesh_tex_clamp(floorf(u * (float)w), w), j = mesh_tex_clamp(floorf(v * (float)h), h);
+#pragma unroll
+        for (int d = 0; d < 3; ++d) col[d] = mesh_texel(tex, w, h, i, j, d);
+        return;
+    }
+    const float x = u * (float)w - 0.5f, y = v * (float)h - 0.5f;
+    const float x0 = floorf(x), y0 = floorf(y);
+    float fx = x - x0, fy = y - y0;
+    if (fx != fx) fx = 0.f;
+    if (fy != fy) fy = 0.f;
+    const int i0 = mesh_tex_clamp(x0, w), i1 = mesh_tex_clamp(x0 + 1.0f, w);
+    const int j0 = mesh_tex_clamp(y0, h), j1 = mesh_tex_clamp(y0 + 1.0f, h);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const float top = (1.0f - fx) * mesh_texel(tex, w, h, i0, j0, d) + fx * mesh_texel(tex, w, h, i1, j0, d);
+        const float bot = (1.0f - fx) * mesh_texel(tex, w, h, i0, j1, d) + fx * mesh_texel(tex, w, h, i1, j1, d);
+        col[d] = (1.0f - fy) * top + fy * bot;
+    }
+}
+
+template <bool TEXTURED>
+__global__ __launch_bounds__(MESHS_THREADS) void mesh_shade_kernel(const MeshShadeArgs A, const MeshTextureArgs X) {
     const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
     const int i = blockIdx.x * MESHS_TILE_W + (lane & (MESHS_TILE_W - 1));
     const int j = (blockIdx.y * (MESHS_THREADS / WAVE) + wave) * MESHS_TILE_H + lane / MESHS_TILE_W;
@@ -390,6 +466,7 @@ __global__ __launch_bounds__(MESHS_THREADS) void mesh_shade_kernel(const MeshSha
         const size_t p = (size_t)slot * plane + (size_t)j * A.width + i;
         const uint64_t key = A.keys[p];
         float depth = 0.f, x[3] = {0.f, 0.f, 0.f}, n[3] = {0.f, 0.f, 0.f}, rgb[3] = {A.bg[0], A.bg[1], A.bg[2]};
+        float uv[2] = {0.f, 0.f};
         int32_t fid = -1, jid = -1;
         const int job = (int)((uint32_t)key >> MESHV_FACE_BITS), face = (int)((uint32_t)key & ((1u << MESHV_FACE_BITS) - 1u));
         MeshTri tri;
@@ -449,7 +526,24 @@ __global__ __launch_bounds__(MESHS_THREADS) void mesh_shade_kernel(const MeshSha
                 diffuse = fmaxf((L[0] * n[0] + L[1] * n[1]) + L[2] * n[2], 0.f);
             }
             const float light_w = fminf(A.ambient + diffuse, 1.f);
-            if (A.rgb) {
+            bool textured = false;
+            if constexpr (TEXTURED) {
+                if (X.corner_uv) {
+                    const float* c = X.corner_uv + 6 * ((size_t)J.f0 + (size_t)face);
+                    const int qb = cor.flipped ? 2 : 1, qc = cor.flipped ? 1 : 2;
+#pragma unroll
+                    for (int d = 0; d < 2; ++d) uv[d] = mesh_attr(la, lb, lc, den, c[d], c[2 * qb + d], c[2 * qc + d]);
+                    const MeshJobTexDev tex = X.job_tex[job];
+                    if (A.rgb && tex.w > 0) {
+                        textured = true;
+                        float col[3];
+                        mesh_tex_sample(X.texels + tex.offset, tex.w, tex.h, uv[0], uv[1], X.bilinear != 0, col);
+#pragma unroll
+                        for (int d = 0; d < 3; ++d) rgb[d] = light_w * col[d];
+                    }
+                }
+            }
+            if (A.rgb && !textured) {
                 float col[3] = {S.surf[0], S.surf[1], S.surf[2]};
                 if (A.colors) {
                     const float* ca = A.colors + 3 * ((size_t)J.v0 + (size_t)cor.vi[0]);
@@ -468,6 +562,9 @@ __global__ __launch_bounds__(MESHS_THREADS) void mesh_shade_kernel(const MeshSha
         mesh_store3(A.xyz, p, x[0], x[1], x[2]);
         mesh_store3(A.normal, p, n[0], n[1], n[2]);
         mesh_store3(A.rgb, p, rgb[0], rgb[1], rgb[2]);
+        if constexpr (TEXTURED) {
+            if (X.uv) { X.uv[2 * p + 0] = uv[0]; X.uv[2 * p + 1] = uv[1]; }
+        }
     }
 }
 

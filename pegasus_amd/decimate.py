@@ -10,9 +10,13 @@ tensors keep coming from the full mesh.  Parity with open3d is not pinned.
 
     python -m pegasus_amd.decimate --models <dir> [--out <dir>] [--ratio r | --faces n | --voxel v]
                                    [--contraction average|quadric] [--normals]
+                                   [--texture -m <model dir> [--obj_id N] [--texel_cell 16] [--scale 1000]]
 
 writes ``<models>/../models_eval`` (the directory the BOP toolkit evaluates on: every ``obj_NNNNNN.ply`` at 2.5 % of its
-faces by default, the toolkit's ``TargetPerc``, with a recomputed ``models_info.json`` that keeps the symmetries).
+faces by default, the toolkit's ``TargetPerc``, with a recomputed ``models_info.json`` that keeps the symmetries).  With
+``--texture`` the decimated mesh of the object a trained Gaussian model shows gets a texture baked from that model
+(``mesh.bake_texture``: a per-face atlas): the PLY carries ``texcoord`` lists and names ``obj_NNNNNN.png``
+beside it.
 """
 from __future__ import annotations
 
@@ -157,14 +161,17 @@ def simplify_to(mesh: Mesh, target_faces: int, contraction: str = "quadric", dev
 
 def write_models_eval(models_dir, out_dir=None, ratio: Optional[float] = 0.025, faces: Optional[int] = None,
                       voxel: Optional[float] = None, contraction: str = "quadric", device="cuda",
-                      normals: bool = False) -> dict:
+                      normals: bool = False, texture_model=None, texture_obj_id: Optional[int] = None, texel_cell: int = 16,
+                      model_scale: float = 1000.0, n_views: int = 96, image_size: int = 512) -> dict:
     """For every ``obj_NNNNNN.ply`` under ``models_dir`` a decimated PLY under ``out_dir`` (default
     ``<models_dir>/../models_eval``) and a ``models_info.json`` there: diameter and box recomputed on the decimated mesh, the
     symmetries copied from the source.  The size is set by ``voxel`` (a cell edge), else ``faces`` (a face count), else
     ``ratio`` (of the source's faces; default the toolkit's TargetPerc).  ``normals``: every decimated mesh is written with
-    vertex normals recomputed on it (mesh.vertex_normals), as the toolkit's remeshing script does.  Returns {obj_id: (faces
-    before, faces after, voxel)}."""
-    from .mesh import models_info, vertex_normals, write_ply
+    vertex normals recomputed on it (mesh.vertex_normals), as the toolkit's remeshing script does.  ``texture_model``: a
+    GaussianModel of object ``texture_obj_id`` (default: the directory's only object) in units ``model_scale`` times smaller
+    than the files' (1000: metres against millimetres); that object's decimated mesh is written textured (mesh.bake_texture
+    with ``texel_cell``, ``n_views``, ``image_size``).  Returns {obj_id: (faces before, faces after, voxel)}."""
+    from .mesh import bake_texture, models_info, vertex_normals, write_ply
     from .ply_io import read_ply_mesh, write_ply_mesh
     models_dir = Path(models_dir)
     out_dir = Path(out_dir) if out_dir is not None else models_dir.parent / "models_eval"
@@ -172,7 +179,14 @@ def write_models_eval(models_dir, out_dir=None, ratio: Optional[float] = 0.025, 
         raise ValueError("ratio must lie in (0, 1]")
     source_info = BD.read_models_info(models_dir)
     info, report = {}, {}
-    for obj_id, path in BD.model_files(models_dir).items():
+    files = BD.model_files(models_dir)
+    if texture_model is not None:
+        if texture_obj_id is None and len(files) != 1:
+            raise ValueError(f"{models_dir} holds {len(files)} objects: name the one the Gaussian model shows (obj_id)")
+        texture_obj_id = int(next(iter(files)) if texture_obj_id is None else texture_obj_id)
+        if texture_obj_id not in {int(k) for k in files}:
+            raise ValueError(f"object {texture_obj_id} is not in {models_dir}")
+    for obj_id, path in files.items():
         v, f = read_ply_mesh(path)
         full = Mesh(v, f)
         if voxel is not None:
@@ -180,9 +194,13 @@ def write_models_eval(models_dir, out_dir=None, ratio: Optional[float] = 0.025, 
         else:
             target = int(faces) if faces is not None else int(math.floor(float(ratio) * len(f)))
             small, used_voxel = simplify_to(full, target, contraction, device)
-        if normals:
-            write_ply(out_dir / f"{BD.model_stem(obj_id)}.ply", Mesh(small.vertices, small.faces,
-                                                                     normals=vertex_normals(small, device=device)))
+        small_normals = vertex_normals(small, device=device) if normals else None
+        if texture_model is not None and int(obj_id) == texture_obj_id:
+            baked = bake_texture(texture_model, small.scaled(1.0 / model_scale), cell=texel_cell, n_views=n_views, image_size=image_size)
+            write_ply(out_dir / f"{BD.model_stem(obj_id)}.ply", Mesh(small.vertices, small.faces, normals=small_normals,
+                                                                     corner_uv=baked.corner_uv, texture=baked.texture))
+        elif normals:
+            write_ply(out_dir / f"{BD.model_stem(obj_id)}.ply", Mesh(small.vertices, small.faces, normals=small_normals))
         else:
             write_ply_mesh(out_dir / f"{BD.model_stem(obj_id)}.ply", small.vertices, small.faces)
         src = source_info.get(str(obj_id), {})
@@ -203,10 +221,25 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     size.add_argument("--voxel", type=float, default=None, help="the cell edge, in the models' units")
     p.add_argument("--contraction", choices=sorted(CONTRACTIONS), default="quadric")
     p.add_argument("--normals", action="store_true", help="write nx ny nz, recomputed on every decimated mesh")
+    p.add_argument("--texture", action="store_true", help="bake a texture for the decimated mesh from the Gaussian model of -m")
+    p.add_argument("-m", "--model_path", default=None, help="with --texture: the trained model directory of the object")
+    p.add_argument("--iteration", type=int, default=-1)
+    p.add_argument("--obj_id", type=int, default=None, help="with --texture: the object the model shows (default: the only one)")
+    p.add_argument("--texel_cell", type=int, default=16, help="texels on the side of the atlas cell two faces share")
+    p.add_argument("--scale", type=float, default=1000.0, help="model units -> the files' units (default: m -> mm)")
+    p.add_argument("--n_views", type=int, default=96)
+    p.add_argument("--image_size", type=int, default=512)
     a = p.parse_args(argv)
     ratio = a.ratio if a.ratio is not None else 0.025
+    gaussians = None
+    if a.texture:
+        if a.model_path is None:
+            p.error("--texture needs -m <model dir>")
+        from .mesh import load_model
+        gaussians = load_model(a.model_path, a.iteration)
     report = write_models_eval(a.models, a.out, ratio=ratio, faces=a.faces, voxel=a.voxel, contraction=a.contraction,
-                               normals=a.normals)
+                               normals=a.normals, texture_model=gaussians, texture_obj_id=a.obj_id, texel_cell=a.texel_cell,
+                               model_scale=a.scale, n_views=a.n_views, image_size=a.image_size)
     for obj_id, (before, after, used_voxel) in sorted(report.items()):
         print(f"{BD.model_stem(obj_id)}: {before} -> {after} faces at voxel {used_voxel:.6g}")
     return 0

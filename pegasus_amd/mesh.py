@@ -7,14 +7,16 @@ the closed outer surface (``pgr_march_count`` / ``pgr_march_emit``).  A density 
 3DGS object is a shell of surface Gaussians, and its level set is two nested surfaces.
 
     python -m pegasus_amd.mesh -m <model dir> --out <dir> --obj_id N [--scale 1000] [--mass 0.1] [--resolution 256]
-                               [--collision_faces N] [--vertex_colors]
+                               [--collision_faces N [--texture [--texel_cell 16]]] [--vertex_colors]
 
 writes ``<out>/models/obj_NNNNNN.ply`` (scaled: BOP models are in mm; with ``--vertex_colors`` also ``nx ny nz red green
 blue`` per vertex, from the views the mesh is fused from: ``pgr_mesh_vertex_normals`` / ``pgr_mesh_vertex_colors``,
 DESIGN.md section 21) with its ``models_info.json`` entry, and
 ``<out>/urdf/obj_NNNNNN.{obj,urdf}`` in the model's own units for pybullet; with ``--collision_faces`` also
 ``<out>/urdf/obj_NNNNNN_collision.obj``, the mesh decimated by vertex clustering (``pegasus_amd.decimate``), as the URDF's
-collision geometry.
+collision geometry; with ``--texture`` that mesh also gets a texture baked from the same sphere of views (``bake_texture``: a
+per-face atlas, ``pgr_mesh_atlas_points`` / ``pgr_mesh_atlas_pack``), written as
+``<out>/urdf/obj_NNNNNN_textured.{obj,mtl,png}`` and named in the URDF's ``<visual>``.
 """
 from __future__ import annotations
 
@@ -73,6 +75,8 @@ class Mesh:
     faces: np.ndarray            # int32 [F,3], outward winding
     normals: Optional[np.ndarray] = None     # float32 [V,3], unit length or 0 (vertex_normals)
     colors: Optional[np.ndarray] = None      # float32 [V,3] in 0..1 (vertex_colors)
+    corner_uv: Optional[np.ndarray] = None   # float32 [F,3,2]: (u, v) per face corner, v = 0 at the image's bottom row
+    texture: Optional[np.ndarray] = None     # uint8 [H,W,3] (bake_texture)
 
     def _tets(self):
         v = self.vertices.astype(np.float64)[self.faces]                  # [F,3,3]: tetrahedra (0, a, b, c)
@@ -119,7 +123,7 @@ class Mesh:
 
     def scaled(self, scale: float) -> "Mesh":
         return Mesh((self.vertices.astype(np.float64) * scale).astype(np.float32), self.faces, normals=self.normals,
-                    colors=self.colors)
+                    colors=self.colors, corner_uv=self.corner_uv, texture=self.texture)
 
 
 # ---- the two GPU stages ---------------------------------------------------------------------------------------------
@@ -229,8 +233,10 @@ def vertex_normals(mesh_or_arrays, device="cuda") -> np.ndarray:
 
 
 def vertex_colors(mesh, color, depth, final_T, views, *, depth_tol: float, alpha_min: float = 0.5, cos_min: float = 0.3,
-                  fill=(0.5, 0.5, 0.5)):
-    """(colors float32 [V,3] in 0..1, seen int32 [V]) of ``mesh`` from rendered views (pgr_mesh_vertex_colors).  ``color``
+                  fill=(0.5, 0.5, 0.5), on_device: bool = False):
+    """(colors float32 [V,3] in 0..1, seen int32 [V]) of ``mesh`` from rendered views (pgr_mesh_vertex_colors); host arrays, or
+    with ``on_device`` the device tensors (``mesh`` is anything with ``vertices`` and optionally ``normals``, arrays or
+    tensors: bake_texture hands in the atlas' texel points).  ``color``
     [V,3,H,W] (rendered over a ZERO background), ``depth`` (normalised, depth mode 1) and ``final_T`` [V,H,W] are device
     tensors of ``views``.  A view counts for a vertex when the vertex projects into it, the pixel is opaque (alpha >=
     ``alpha_min``), its depth lies within ``depth_tol`` of the vertex's and, when the mesh has normals, the vertex faces
@@ -250,10 +256,12 @@ def vertex_colors(mesh, color, depth, final_T, views, *, depth_tol: float, alpha
     final_T = final_T.reshape(n, *final_T.shape[-2:]).float().contiguous()
     if tuple(depth.shape) != (n, H, W) or final_T.shape != depth.shape or tuple(color.shape) != (n, 3, H, W):
         raise ValueError("color must be [V,3,H,W], depth and final_T [V,H,W], of the views' image size")
-    vert = torch.from_numpy(np.ascontiguousarray(mesh.vertices, np.float32).reshape(-1, 3)).to(device)
+    to_device = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, np.float32))) \
+        .to(device=device, dtype=torch.float32).reshape(-1, 3).contiguous()
+    vert = to_device(mesh.vertices)
     normals = getattr(mesh, "normals", None)
     if normals is not None:
-        normals = torch.from_numpy(np.ascontiguousarray(normals, np.float32).reshape(-1, 3)).to(device)
+        normals = to_device(normals)
         if normals.shape != vert.shape:
             raise ValueError("normals must be [V,3]")
     V = int(vert.shape[0])
@@ -264,7 +272,7 @@ def vertex_colors(mesh, color, depth, final_T, views, *, depth_tol: float, alpha
     _lib.call("pgr_mesh_vertex_colors", device, V, _lib.ptr(vert), _lib.ptr(normals), n, cams, _lib.ptr(color),
               _lib.ptr(depth), _lib.ptr(final_T), float(depth_tol), float(alpha_min), float(cos_min), fill_c, _lib.ptr(out),
               _lib.ptr(seen))
-    result = out.cpu().numpy(), seen.cpu().numpy()
+    result = (out, seen) if on_device else (out.cpu().numpy(), seen.cpu().numpy())
     del keep
     return result
 
@@ -454,18 +462,180 @@ def colorize(gaussians, mesh: Mesh, *, n_views: int = 96, image_size: int = 512,
                        info)
 
 
+# ---- a texture for a (decimated) mesh: a per-face atlas baked from the views ---------------------------------------------
+MAX_ATLAS_SIDE = 8192
+MIN_ATLAS_CELL = 4
+
+
+def texture_atlas_layout(n_faces: int, cell: int):
+    """(width, height, cols, rows, corner_uv float32 [F,3,2]) of the per-face atlas (the layout pinned in csrc/meshattr.hip.h;
+    this is the one place it is computed, the library checks the size it is handed against its own).  Two faces share a cell
+    of ``cell`` x ``cell`` texels as two right triangles with legs of ``cell`` - 3 texels; face f lies in cell f >> 1, half
+    f & 1.  Corner UVs are u = X / width, v = 1 - Y / height of the corners' texel-centre coordinates (X right, Y down from the
+    top-left), computed in float64 and rounded once."""
+    F, s = int(n_faces), int(cell)
+    if F < 1:
+        raise ValueError("a texture atlas needs at least one face")
+    if s < MIN_ATLAS_CELL:
+        raise ValueError(f"cell must be at least {MIN_ATLAS_CELL} texels, got {s}")
+    cells = (F + 1) // 2
+    cols = math.isqrt(cells - 1) + 1
+    rows = -(-cells // cols)
+    if cols * s > MAX_ATLAS_SIDE:
+        raise ValueError(f"{F} faces at cell {s} need an atlas {cols * s} texels wide; at most {MAX_ATLAS_SIDE}: the largest "
+                         f"cell that fits is {MAX_ATLAS_SIDE // cols}" + ("" if MAX_ATLAS_SIDE // cols >= MIN_ATLAS_CELL else
+                                                                          f" (below {MIN_ATLAS_CELL}: decimate the mesh first)"))
+    width, height, L = cols * s, rows * s, s - 3
+    f = np.arange(F)
+    c, half = f >> 1, (f & 1)[:, None]
+    origin = np.stack([(c % cols) * s, (c // cols) * s], 1).astype(np.float64)                      # [F,2]
+    local0 = np.array([[0.5, 0.5], [0.5 + L, 0.5], [0.5, 0.5 + L]])
+    local = np.where(half[:, :, None] == 0, local0[None], s - local0[None])                          # [F,3,2]
+    xy = origin[:, None, :] + local
+    corner_uv = np.stack([xy[..., 0] / width, 1.0 - xy[..., 1] / height], -1).astype(np.float32)
+    return width, height, cols, rows, corner_uv
+
+
+def atlas_points(vertices, faces, cell: int):
+    """pgr_mesh_atlas_points on device tensors (vertices float32 [V,3], faces int32 [F,3]): (points float32 [H*W,3], normals
+    float32 [H*W,3], face_of_texel int32 [H*W]) of every atlas texel, on the same device, and (width, height)."""
+    import torch
+    if vertices.device.type != "cuda" or faces.device.type != "cuda":
+        raise RuntimeError("atlas_points needs tensors on a HIP device; there is no CPU path")
+    width, height = texture_atlas_layout(int(faces.shape[0]), cell)[:2]
+    n = width * height
+    points = torch.empty((n, 3), dtype=torch.float32, device=vertices.device)
+    normals = torch.empty_like(points)
+    owner = torch.empty((n,), dtype=torch.int32, device=vertices.device)
+    _lib.call("pgr_mesh_atlas_points", vertices.device, int(vertices.shape[0]), _lib.ptr(vertices), int(faces.shape[0]), _lib.ptr(faces),
+              int(cell), width, height, _lib.ptr(points), _lib.ptr(normals), _lib.ptr(owner))
+    return points, normals, owner, (width, height)
+
+
+def atlas_pack(n_faces: int, cell: int, face_of_texel, colors, seen, face_fill=None, fill=(128, 128, 128)):
+    """pgr_mesh_atlas_pack on device tensors: (texture uint8 [H,W,3], face_seen int32 [F]) on the same device.  ``face_fill``:
+    uint8 [F,3] (array or tensor) for the faces no view sees, else ``fill``."""
+    import torch
+    device = colors.device
+    if device.type != "cuda":
+        raise RuntimeError("atlas_pack needs tensors on a HIP device; there is no CPU path")
+    width, height = texture_atlas_layout(n_faces, cell)[:2]
+    colors = colors.to(torch.float32).reshape(-1, 3).contiguous()
+    seen = seen.to(torch.int32).reshape(-1).contiguous()
+    face_of_texel = face_of_texel.to(torch.int32).reshape(-1).contiguous()
+    if not (colors.shape[0] == seen.shape[0] == face_of_texel.shape[0] == width * height):
+        raise ValueError(f"colors, seen and face_of_texel must hold the atlas' {width} x {height} texels")
+    if face_fill is not None:
+        face_fill = torch.as_tensor(np.ascontiguousarray(face_fill, np.uint8) if not isinstance(face_fill, torch.Tensor) else face_fill)
+        face_fill = face_fill.to(device=device, dtype=torch.uint8).reshape(-1, 3).contiguous()
+        if face_fill.shape[0] != n_faces:
+            raise ValueError("face_fill must be [F,3]")
+    texture = torch.empty((height, width, 3), dtype=torch.uint8, device=device)
+    face_seen = torch.empty((n_faces,), dtype=torch.int32, device=device)
+    fill_c = (C.c_uint8 * 3)(*[int(x) for x in fill])
+    _lib.call("pgr_mesh_atlas_pack", device, int(n_faces), int(cell), width, height, _lib.ptr(face_of_texel), _lib.ptr(colors),
+              _lib.ptr(seen), _lib.ptr(face_fill), fill_c, _lib.ptr(texture), _lib.ptr(face_seen))
+    return texture, face_seen
+
+
+def bake_views(mesh: Mesh, color, depth, final_T, views, *, cell: int = 16, depth_tol: float, alpha_min: float = 0.5,
+               cos_min: float = 0.3, stage_ms: Optional[dict] = None, info: Optional[dict] = None) -> Mesh:
+    """``mesh`` with ``corner_uv`` and ``texture`` baked from rendered views (the tensors vertex_colors takes): the texels'
+    surface points (pgr_mesh_atlas_points), coloured by the per-point rule of the vertex colours (pgr_mesh_vertex_colors,
+    unchanged: same views, tolerances and weights), quantised and filled per face (pgr_mesh_atlas_pack).  Faces no view sees
+    take the mean of the mesh's own vertex colours when it has them, else mid grey.  ``info`` receives ``face_seen`` (int32
+    [F]: the seen texels of every face) and ``atlas`` = (width, height); ``stage_ms`` the milliseconds of the three stages."""
+    import torch
+    from types import SimpleNamespace
+    device = depth.device
+    vert, faces = _device_mesh(mesh, device)
+    F = int(faces.shape[0])
+    corner_uv = texture_atlas_layout(F, cell)[4]
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if stage_ms is not None else None
+    if ev:
+        ev[0].record()
+    points, normals, owner, _size = atlas_points(vert, faces, cell)
+    if ev:
+        ev[1].record()
+    colors, seen = vertex_colors(SimpleNamespace(vertices=points, normals=normals), color, depth, final_T, views, depth_tol=depth_tol,
+                                 alpha_min=alpha_min, cos_min=cos_min, on_device=True)
+    if ev:
+        ev[2].record()
+    face_fill = None
+    if mesh.colors is not None:
+        mean = np.asarray(mesh.colors, np.float64).reshape(-1, 3)[np.asarray(mesh.faces, np.int64)].mean(1)
+        face_fill = np.rint(255.0 * np.clip(mean, 0.0, 1.0)).astype(np.uint8)
+    texture, face_seen = atlas_pack(F, cell, owner, colors, seen, face_fill)
+    if ev:
+        ev[3].record()
+        ev[3].synchronize()
+        for k, name in enumerate(("atlas_points", "atlas_colors", "atlas_pack")):
+            stage_ms[name] = ev[k].elapsed_time(ev[k + 1])
+    texture = texture.cpu().numpy()
+    if info is not None:
+        info["face_seen"] = face_seen.cpu().numpy()
+        info["atlas"] = (int(texture.shape[1]), int(texture.shape[0]))
+    return Mesh(mesh.vertices, mesh.faces, normals=mesh.normals, colors=mesh.colors, corner_uv=corner_uv, texture=texture)
+
+
+def bake_texture(gaussians, mesh: Mesh, *, cell: int = 16, n_views: int = 96, image_size: int = 512, alpha_min: float = 0.5,
+                 depth_tol: Optional[float] = None, cos_min: float = 0.3, bounds=None, stage_ms: Optional[dict] = None,
+                 info: Optional[dict] = None) -> Mesh:
+    """``mesh`` (in the model's frame; typically decimated) with a texture baked from renders of ``gaussians``: colorize's
+    arguments, sphere of views and default ``depth_tol``, but the appearance goes into ``cell`` x ``cell`` texels per pair of
+    faces (bake_views) instead of one colour per vertex.  Returns the mesh with ``corner_uv`` [F,3,2] and ``texture`` uint8
+    [H,W,3]; ``info`` receives ``face_seen``."""
+    texture_atlas_layout(len(mesh.faces), cell)                         # refuse an atlas that cannot be built before rendering
+    lo, hi = _model_bounds(gaussians, bounds)
+    if depth_tol is None:
+        depth_tol = 2.0 * float((hi - lo).max()) / 255.0
+    views, _r, _fov = sphere_views(0.5 * (lo + hi), 0.5 * float(np.linalg.norm(hi - lo)), n_views, image_size)
+    if len(views) > MAX_VIEWS:
+        raise ValueError(f"n_views: at most {MAX_VIEWS} views are used")
+    depth, final_T, color = render_views(gaussians, views, stage_ms, want_color=True)
+    return bake_views(mesh, color, depth, final_T, views, cell=cell, depth_tol=depth_tol, alpha_min=alpha_min, cos_min=cos_min,
+                      stage_ms=stage_ms, info=info)
+
+
 # ---- files ----------------------------------------------------------------------------------------------------------
 def write_ply(path, mesh: Mesh, scale: float = 1.0):
     """Binary PLY with vertex and face elements; vertices multiplied by ``scale`` (1000: metres -> BOP millimetres).  A mesh
     with normals or colours is written in the property order of a BOP model file (ply_io.write_ply_model): normals as
-    float, colours as uchar = rint(255 c)."""
-    if mesh.normals is None and mesh.colors is None:
+    float, colours as uchar = rint(255 c).  A mesh that carries a texture is written with its corner UVs as the face
+    element's ``texcoord`` list, a ``comment TextureFile <stem>.png`` line, and the image as ``<stem>.png`` beside the file."""
+    textured = getattr(mesh, "texture", None) is not None and getattr(mesh, "corner_uv", None) is not None
+    if mesh.normals is None and mesh.colors is None and not textured:
         write_ply_mesh(path, mesh.scaled(scale).vertices, mesh.faces)
         return
     colors = mesh.colors
     if colors is not None:
         colors = np.rint(255.0 * np.clip(np.asarray(colors, np.float64), 0.0, 1.0)).astype(np.uint8)
-    write_ply_model(path, mesh.scaled(scale).vertices, mesh.faces, normals=mesh.normals, colors=colors)
+    if not textured:
+        write_ply_model(path, mesh.scaled(scale).vertices, mesh.faces, normals=mesh.normals, colors=colors)
+        return
+    path = Path(path)
+    write_ply_model(path, mesh.scaled(scale).vertices, mesh.faces, normals=mesh.normals, colors=colors,
+                    texture_uv_face=np.asarray(mesh.corner_uv, np.float32).reshape(-1, 6), texture_file=path.stem + ".png")
+    path.with_suffix(".png").write_bytes(BD.encode_png(np.ascontiguousarray(mesh.texture, np.uint8)))
+
+
+def write_obj_textured(path, mesh: Mesh, texture_name: str):
+    """Wavefront OBJ with texture coordinates: ``v``, one ``vt`` per face corner, ``f a/ta b/tb c/tc``, and ``<stem>.mtl``
+    beside it whose ``map_Kd`` names ``texture_name`` (relative to the OBJ).  The image itself is neither read nor written
+    here: whoever passes the name puts it there."""
+    if getattr(mesh, "corner_uv", None) is None:
+        raise ValueError("write_obj_textured needs a mesh with corner_uv")
+    path = Path(path)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    uv = np.asarray(mesh.corner_uv, np.float32).reshape(-1, 2)
+    f = np.asarray(mesh.faces, np.int64).reshape(-1, 3) + 1
+    t = np.arange(1, 3 * len(f) + 1).reshape(-1, 3)
+    with open(path, "w") as fh:
+        fh.write(f"# closed mesh extracted from a Gaussian model, textured\nmtllib {path.stem}.mtl\nusemtl material_0\n")
+        np.savetxt(fh, mesh.vertices, fmt="v %.9g %.9g %.9g")
+        np.savetxt(fh, uv, fmt="vt %.9g %.9g")
+        np.savetxt(fh, np.stack([f, t], 2).reshape(-1, 6), fmt="f %d/%d %d/%d %d/%d")
+    path.with_suffix(".mtl").write_text(f"newmtl material_0\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {texture_name}\n")
 
 
 def write_obj(path, mesh: Mesh):
@@ -477,10 +647,12 @@ def write_obj(path, mesh: Mesh):
         np.savetxt(f, mesh.faces.astype(np.int64) + 1, fmt="f %d %d %d")
 
 
-def write_urdf(path, mesh_filename: str, mesh: Mesh, mass: float, collision_filename: Optional[str] = None):
+def write_urdf(path, mesh_filename: str, mesh: Mesh, mass: float, collision_filename: Optional[str] = None,
+               visual_filename: Optional[str] = None):
     """One link: visual and collision are the mesh file, the inertial block holds the mesh's centre of mass, ``mass``
     and inertia about the centre of mass at uniform density.  ``collision_filename``: another (coarser) mesh file for the
-    ``<collision>`` element only; the inertial block still comes from ``mesh``."""
+    ``<collision>`` element only; ``visual_filename``: another (textured) one for ``<visual>`` only; the inertial block
+    still comes from ``mesh``."""
     c = mesh.center_of_mass()
     I = mesh.inertia(mass)
     robot = ET.Element("robot", name=Path(mesh_filename).stem)
@@ -494,6 +666,8 @@ def write_urdf(path, mesh_filename: str, mesh: Mesh, mass: float, collision_file
         e = ET.SubElement(link, tag)
         ET.SubElement(e, "origin", xyz="0 0 0", rpy="0 0 0")
         filename = collision_filename if tag == "collision" and collision_filename is not None else mesh_filename
+        if tag == "visual" and visual_filename is not None:
+            filename = visual_filename
         ET.SubElement(ET.SubElement(e, "geometry"), "mesh", filename=str(filename), scale="1 1 1")
     ET.indent(robot)
     path = Path(path)
@@ -592,6 +766,10 @@ def _parser():
                         "(pegasus_amd.decimate.simplify_to), and name it in the URDF's <collision> element")
     p.add_argument("--vertex_colors", action="store_true",
                    help="models/<name>.ply also carries nx ny nz red green blue, from the views the mesh is fused from")
+    p.add_argument("--texture", action="store_true",
+                   help="with --collision_faces: bake a texture for the decimated mesh from the same sphere of views (bake_texture) and "
+                        "write urdf/<name>_textured.{obj,mtl,png}, named in the URDF's <visual> element")
+    p.add_argument("--texel_cell", type=int, default=16, help="with --texture: texels on the side of the atlas cell two faces share")
     p.add_argument("--sym_continuous", type=float, nargs=6, action="append", metavar=("AX", "AY", "AZ", "OX", "OY", "OZ"),
                    help="a continuous rotational symmetry: axis and a point on it, in model units (repeatable)")
     p.add_argument("--sym_discrete", type=float, nargs=16, action="append", metavar="M",
@@ -611,9 +789,12 @@ def scaled_symmetries(sym_discrete, sym_continuous, scale: float):
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:
-    a = _parser().parse_args(argv)
-    mesh = extract_mesh(load_model(a.model_path, a.iteration, a.clean_pcd), resolution=a.resolution, n_views=a.n_views,
-                        image_size=a.image_size, colors=a.vertex_colors)
+    parser = _parser()
+    a = parser.parse_args(argv)
+    if a.texture and a.collision_faces is None:
+        parser.error("--texture textures the decimated mesh: it needs --collision_faces")
+    gaussians = load_model(a.model_path, a.iteration, a.clean_pcd)
+    mesh = extract_mesh(gaussians, resolution=a.resolution, n_views=a.n_views, image_size=a.image_size, colors=a.vertex_colors)
     name = BD.model_stem(a.obj_id)
     out = Path(a.out)
     write_ply(out / "models" / f"{name}.ply", mesh, scale=a.scale)
@@ -628,7 +809,13 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         coarse, _voxel = simplify_to(mesh, a.collision_faces)
         collision = f"{name}_collision.obj"
         write_obj(out / "urdf" / collision, coarse)
-    write_urdf(out / "urdf" / f"{name}.urdf", f"{name}.obj", mesh, a.mass, collision_filename=collision)
+    visual = None
+    if a.texture:
+        baked = bake_texture(gaussians, coarse, cell=a.texel_cell, n_views=a.n_views, image_size=a.image_size)
+        visual = f"{name}_textured.obj"
+        write_obj_textured(out / "urdf" / visual, baked, f"{name}_textured.png")
+        (out / "urdf" / f"{name}_textured.png").write_bytes(BD.encode_png(baked.texture))
+    write_urdf(out / "urdf" / f"{name}.urdf", f"{name}.obj", mesh, a.mass, collision_filename=collision, visual_filename=visual)
     print(f"{name}: {len(mesh.vertices)} vertices, {len(mesh.faces)} faces, volume {mesh.volume():.6g}, "
           f"written under {out}")
     return 0

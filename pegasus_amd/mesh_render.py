@@ -14,7 +14,7 @@ Shaded renders (``render``, ``Renderer``, ``vis_object_poses``) come from a visi
 (depth, job, face) per pixel, ``pgr_mesh_shade`` resolves it to rgb, depth, model coordinates, normals and ids.
 
     python -m pegasus_amd.mesh_render --dataset <dir> --models <dir> --vis <out dir> [--results <bop csv>] [--resolve_visib]
-                                      [--shading flat|phong]
+                                      [--shading flat|phong] [--textures] [--texture_filter nearest|bilinear]
 
 writes ``<out>/<scene>/<image>.png`` instead: the models over the photographs at the ground-truth poses (the toolkit's
 vis_gt_poses.py) or at a results file's estimates (vis_est_poses.py).
@@ -45,21 +45,40 @@ class MeshSet:
 
     ``normals`` and ``colors``: float32 [V,3] device tensors, None when no mesh of the set has them (a mesh object offers them
     as attributes of those names).  Where only some have colours the others get 0.5; colours above 1 are divided by 255.  Where
-    only some have normals (or with ``compute_normals``, where none has) the others get ``vertex_normals``."""
+    only some have normals (or with ``compute_normals``, where none has) the others get ``vertex_normals``.
+
+    ``textures`` (default off: every file loads as it always did): paths are read with their texture coordinates and the image
+    their ``comment TextureFile`` line names, opened relative to the PLY (8-bit; RGBA drops alpha, grey is replicated); a mesh
+    object offers ``corner_uv`` [F,3,2] and ``texture`` (uint8 [H,W,3]).  Per-vertex UVs are expanded to face corners
+    (uv[faces]); per-face ones are taken as they are and win when a file has both.  Then ``corner_uv`` is a float32 [F,3,2]
+    device tensor (zeros for meshes without UVs; None when no mesh has any), ``texels`` the uint8 device buffer of every image,
+    ``texture_table`` its (byte offset, width, height) rows and ``texture_of[obj_id]`` a row index or -1; ``render`` then
+    textures these objects as the toolkit's renderers do (v = 0 is the image's bottom row)."""
 
     def __init__(self, meshes: dict, device="cuda", scale: float = 1.0, diameters: Optional[dict] = None,
-                 compute_normals: bool = False):
+                 compute_normals: bool = False, textures: bool = False):
         import torch
         from .ply_io import read_ply_model
-        vs, fs, ns, cs, self.ranges = [], [], [], [], {}
+        vs, fs, ns, cs, uvs, images, self.ranges = [], [], [], [], [], [], {}
+        self.texture_of, self.texture_table = {}, []
         v0 = f0 = 0
         for obj_id in sorted(meshes):
             m = meshes[obj_id]
+            uv = image = None
             if isinstance(m, (str, Path)):
-                model = read_ply_model(m)
+                model = read_ply_model(m, texture=True) if textures else read_ply_model(m)
                 v, f, n, c = model["pts"], model["faces"], model.get("normals"), model.get("colors")
+                if "texture_uv_face" in model:
+                    uv = model["texture_uv_face"].reshape(-1, 3, 2)
+                elif "texture_uv" in model:
+                    uv = model["texture_uv"][np.asarray(f, np.int64).reshape(-1, 3)]
+                if uv is not None and "texture_file" in model:
+                    image = load_texture(Path(m).parent / model["texture_file"], m)
             else:
                 v, f, n, c = m.vertices, m.faces, getattr(m, "normals", None), getattr(m, "colors", None)
+                if textures:
+                    uv, image = getattr(m, "corner_uv", None), getattr(m, "texture", None)
+                    image = None if uv is None else image
             v = np.ascontiguousarray(v, np.float32).reshape(-1, 3)
             f = np.ascontiguousarray(f, np.int32).reshape(-1, 3)
             if scale != 1.0:
@@ -72,6 +91,19 @@ class MeshSet:
             if c is not None:
                 c = np.asarray(c, np.float64).reshape(-1, 3)
                 c = (c / 255.0 if c.size and c.max() > 1.0 else c).astype(np.float32)          # as the toolkit's renderers do
+            if uv is not None:
+                uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 3, 2)
+                if len(uv) != len(f):
+                    raise ValueError(f"object {obj_id}: corner_uv must be [F,3,2]")
+            if image is not None:
+                image = np.ascontiguousarray(image)
+                if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3 or not (1 <= image.shape[0] <= MAX_CANVAS and
+                                                                                               1 <= image.shape[1] <= MAX_CANVAS):
+                    raise ValueError(f"object {obj_id}: a texture must be uint8 [H,W,3] with sides 1..{MAX_CANVAS}")
+            self.texture_of[int(obj_id)] = len(images) if image is not None else -1
+            if image is not None:
+                images.append(image)
+            uvs.append(uv)
             self.ranges[int(obj_id)] = (v0, len(v), f0, len(f))
             vs.append(v); fs.append(f)
             ns.append(None if n is None else np.asarray(n, np.float64).reshape(-1, 3).astype(np.float32)); cs.append(c)
@@ -85,20 +117,43 @@ class MeshSet:
         if any(c is not None for c in cs):
             cs = [np.full((len(v), 3), 0.5, np.float32) if c is None else c for v, c in zip(vs, cs)]
             self.colors = torch.from_numpy(np.concatenate(cs)).to(device)
+        self.corner_uv = self.texels = None
+        if any(uv is not None for uv in uvs):
+            uvs = [np.zeros((len(f), 3, 2), np.float32) if uv is None else uv for f, uv in zip(fs, uvs)]
+            self.corner_uv = torch.from_numpy(np.concatenate(uvs)).to(device)
+        if images:
+            at = 0
+            for image in images:
+                self.texture_table.append((at, int(image.shape[1]), int(image.shape[0])))
+                at += image.size
+            self.texels = torch.from_numpy(np.concatenate([image.reshape(-1) for image in images])).to(device)
         self.diameters = {int(k): float(v) for k, v in (diameters or {}).items()}
         self.device = self.vertices.device
 
     @classmethod
-    def from_dir(cls, models_dir, device="cuda", scale: float = 1.0, compute_normals: bool = False) -> "MeshSet":
+    def from_dir(cls, models_dir, device="cuda", scale: float = 1.0, compute_normals: bool = False, textures: bool = False) -> "MeshSet":
         """Every ``obj_NNNNNN.ply`` of a BOP models directory, diameters from its ``models_info.json`` (scaled alike)."""
         files = BD.model_files(models_dir)
         diam = {int(k): v["diameter"] * scale for k, v in BD.read_models_info(models_dir).items()}
-        return cls(files, device=device, scale=scale, diameters=diam, compute_normals=compute_normals)
+        return cls(files, device=device, scale=scale, diameters=diam, compute_normals=compute_normals, textures=textures)
 
     def mesh(self, obj_id: int):
         """(vertices, faces) of one object as host arrays."""
         v0, nv, f0, nf = self.ranges[int(obj_id)]
         return self.vertices[v0:v0 + nv].cpu().numpy(), self.faces[f0:f0 + nf].cpu().numpy()
+
+
+def load_texture(path, model_path=None) -> np.ndarray:
+    """The image of a model's ``comment TextureFile`` line as uint8 [H,W,3], as stored (row 0 is the top row): RGBA drops
+    alpha, grey is replicated; 16-bit images are refused.  A missing file raises FileNotFoundError naming it and the model."""
+    path = Path(path)
+    if not path.is_file():
+        raise FileNotFoundError(f"texture {path} named by {model_path if model_path is not None else 'the model'} does not exist")
+    from PIL import Image
+    with Image.open(path) as im:
+        if im.mode in ("I;16", "I;16B", "I;16L", "I", "F"):
+            raise ValueError(f"texture {path}: 16-bit images (mode {im.mode}) are not supported; convert it to 8 bits per channel")
+        return np.ascontiguousarray(np.asarray(im.convert("RGB"), np.uint8))
 
 
 def mesh_jobs(meshes: MeshSet, jobs: Sequence, K, margin=(0, 0), slots: Optional[Sequence[int]] = None):
@@ -157,7 +212,8 @@ def render_depth(meshes: MeshSet, jobs: Sequence, K, size, margin=(0, 0), near: 
 
 # ---- shaded renders: visibility buffer and resolve --------------------------------------------------------------------
 RENDER_OUTPUTS = {"rgb": ("float32", 3), "depth": ("float32", 0), "xyz": ("float32", 3), "normal": ("float32", 3),
-                  "face_id": ("int32", 0), "job_id": ("int32", 0)}
+                  "face_id": ("int32", 0), "job_id": ("int32", 0), "uv": ("float32", 2)}
+TEXTURE_FILTERS = {"nearest": _lib.PGR_TEXTURE_NEAREST, "bilinear": _lib.PGR_TEXTURE_BILINEAR}
 DEFAULT_SURF_COLOR = (0.5, 0.5, 0.5)             # the toolkit renderers' grey
 
 
@@ -196,7 +252,8 @@ def _slot_chunks(slots, per_call_slots: int):
 
 def render(meshes: MeshSet, jobs: Sequence, K, size, outputs=("rgb", "depth"), shading: str = "phong", ambient: float = 0.5,
            light=(0.0, 0.0, 0.0), surf_colors=None, bg=(0.0, 0.0, 0.0), margin=(0, 0), near: float = DEFAULT_NEAR,
-           slots: Optional[Sequence[int]] = None, budget_bytes: int = DEFAULT_BUDGET, return_straddle: bool = False) -> dict:
+           slots: Optional[Sequence[int]] = None, budget_bytes: int = DEFAULT_BUDGET, return_straddle: bool = False,
+           texture_filter: str = "nearest") -> dict:
     """Shaded renders of ``jobs`` = [(obj_id, R, t), ...] as the toolkit's renderers shade them (one light, ambient plus
     diffuse), and the dense maps only a mesh gives.  Returns {name: device tensor} for every name in ``outputs``:
 
@@ -205,12 +262,17 @@ def render(meshes: MeshSet, jobs: Sequence, K, size, outputs=("rgb", "depth"), s
         xyz      float32 [S,Hc,Wc,3]  model coordinates of the surface point, 0 where nothing is hit
         normal   float32 [S,Hc,Wc,3]  unit normal in the camera frame, 0 where nothing is hit
         face_id, job_id  int32 [S,Hc,Wc]  the face (index in its mesh) and the job (index in ``jobs``), -1 where nothing is hit
+        uv       float32 [S,Hc,Wc,2]  texture coordinates of the surface point, perspective-correct (a set loaded with
+                                      ``textures=True`` whose meshes have UVs), 0 where nothing is hit
 
     ``slots``: the canvas of each job (default: one each, S = len(jobs)); jobs that share a slot are composited nearest-first
     by the visibility pass itself (at equal depth the earlier job wins).  ``shading``: "phong" interpolates the set's vertex
     normals (a set without normals raises), "flat" takes the face's own.  The colour is the set's vertex colours; without
     them, or with ``surf_colors`` ([3] or one [3] per job) given, the surf colour (default the toolkit's 0.5 grey).  ``light``
     is in the camera frame (the toolkit's default: the camera centre).  ``size``, ``margin``, ``K``, ``near`` as render_depth.
+    In a set loaded with ``textures=True`` an object with a texture takes its colour from it (``pgr_mesh_shade_textured``;
+    ``texture_filter``: "nearest", what the toolkit's renderers get from vispy / glumpy by default, or "bilinear"; clamp to
+    edge), unless ``surf_colors`` is given, as in the toolkit; parity with an OpenGL render is not pinned.
     The rule is pinned above mesh_shade_kernel in csrc/meshraster.hip.h; calls are chunked by the library's 1024 jobs per call and
     by ``budget_bytes`` of canvases."""
     import torch
@@ -225,6 +287,10 @@ def render(meshes: MeshSet, jobs: Sequence, K, size, outputs=("rgb", "depth"), s
         raise ValueError(f"outputs must be a non-empty choice of {sorted(RENDER_OUTPUTS)}, got {outputs!r}")
     if shading not in ("phong", "flat"):
         raise ValueError(f"shading must be 'phong' or 'flat', got {shading!r}")
+    if texture_filter not in TEXTURE_FILTERS:
+        raise ValueError(f"texture_filter must be one of {sorted(TEXTURE_FILTERS)}, got {texture_filter!r}")
+    if "uv" in outputs and getattr(meshes, "corner_uv", None) is None:
+        raise ValueError("the 'uv' output needs a mesh set with texture coordinates (MeshSet(..., textures=True))")
     if shading == "phong" and meshes.normals is None and ("rgb" in outputs or "normal" in outputs):
         raise ValueError("shading='phong' needs a mesh set with normals (MeshSet(..., compute_normals=True), or shading='flat')")
     device = meshes.device
@@ -240,6 +306,9 @@ def render(meshes: MeshSet, jobs: Sequence, K, size, outputs=("rgb", "depth"), s
     if surf_colors is not None:
         surf = np.ascontiguousarray(np.broadcast_to(np.asarray(surf_colors, np.float32), (J, 3)))
     colors = meshes.colors if surf is None else None
+    corner_uv = getattr(meshes, "corner_uv", None)
+    texels = getattr(meshes, "texels", None) if surf is None else None
+    textured = corner_uv is not None and (texels is not None or "uv" in outputs)
     normals = meshes.normals if shading == "phong" else None
     bg32 = np.asarray(bg, np.float32).reshape(3)
     out = {}
@@ -266,13 +335,27 @@ def render(meshes: MeshSet, jobs: Sequence, K, size, outputs=("rgb", "depth"), s
         straddle += count
         part = {name: torch.empty((ns,) + tuple(out[name].shape[1:]), dtype=out[name].dtype, device=device) for name in outputs}
         sub = None if surf is None else np.ascontiguousarray(surf[ks])
+        uv_part = part.pop("uv", None)
         shade = _lib.PgrMeshShade(normals=_lib.ptr(normals), colors=_lib.ptr(colors),
                                   surf_colors=None if sub is None else sub.ctypes.data_as(C.POINTER(C.c_float)),
                                   light=(C.c_float * 3)(*np.asarray(light, np.float32).reshape(3).tolist()), ambient=float(ambient),
                                   bg=(C.c_float * 3)(*bg32.tolist()), **{name: _lib.ptr(t) for name, t in part.items()})
-        ws2 = _lib.workspace("pgr_mesh_shade", device, n, arr)
-        _lib.call("pgr_mesh_shade", device, _lib.ptr(meshes.vertices), meshes.vertices.shape[0], _lib.ptr(meshes.faces),
-                  meshes.faces.shape[0], n, arr, Wc, Hc, float(near), _lib.ptr(keys), ns, C.byref(shade), _lib.ptr(ws2), ws2.numel())
+        mesh_args = (_lib.ptr(meshes.vertices), meshes.vertices.shape[0], _lib.ptr(meshes.faces), meshes.faces.shape[0], n, arr, Wc, Hc,
+                     float(near), _lib.ptr(keys), ns, C.byref(shade))
+        if textured:
+            table = (_lib.PgrMeshTexture * max(len(meshes.texture_table), 1))(*[_lib.PgrMeshTexture(offset=o, width=w, height=h)
+                                                                                for o, w, h in meshes.texture_table])
+            which = (C.c_int32 * n)(*[meshes.texture_of[int(job[0])] if texels is not None else -1 for job in chunk])
+            tex = _lib.PgrMeshTextures(corner_uv=_lib.ptr(corner_uv), texels=_lib.ptr(texels), texel_bytes=0 if texels is None else texels.numel(),
+                                       n_textures=len(meshes.texture_table) if texels is not None else 0, textures=table, job_texture=which,
+                                       filter=TEXTURE_FILTERS[texture_filter], uv=_lib.ptr(uv_part))
+            ws2 = _lib.workspace("pgr_mesh_shade_textured", device, n, arr)
+            _lib.call("pgr_mesh_shade_textured", device, *mesh_args, C.byref(tex), _lib.ptr(ws2), ws2.numel())
+        else:
+            ws2 = _lib.workspace("pgr_mesh_shade", device, n, arr)
+            _lib.call("pgr_mesh_shade", device, *mesh_args, _lib.ptr(ws2), ws2.numel())
+        if uv_part is not None:
+            part["uv"] = uv_part
         index = torch.as_tensor(ids, device=device)
         for name, t in part.items():
             if name == "job_id":                                     # the index in the call -> the index in ``jobs``
@@ -290,7 +373,10 @@ class Renderer:
     Models and translations share their unit (the toolkit's: millimetres)."""
 
     def __init__(self, width: int, height: int, mode: str = "rgb+depth", shading: str = "phong", bg_color=(0.0, 0.0, 0.0, 0.0),
-                 device="cuda", near: float = DEFAULT_NEAR):
+                 device="cuda", near: float = DEFAULT_NEAR, texture_filter: str = "nearest"):
+        if texture_filter not in TEXTURE_FILTERS:
+            raise ValueError(f"texture_filter must be one of {sorted(TEXTURE_FILTERS)}, got {texture_filter!r}")
+        self.texture_filter = texture_filter
         if mode not in ("rgb+depth", "rgb", "depth"):
             raise ValueError(f"mode must be 'rgb+depth', 'rgb' or 'depth', got {mode!r}")
         if shading not in ("phong", "flat"):
@@ -308,8 +394,9 @@ class Renderer:
         self.light_ambient_weight = float(light_ambient_weight)
 
     def add_object(self, obj_id, model_path, surf_color=None, **kwargs):
-        """``surf_color``: a colour (r, g, b in [0,1]) used instead of the model's vertex colours.  Other keywords of the
-        toolkit's renderers are accepted and ignored."""
+        """``surf_color``: a colour (r, g, b in [0,1]) used instead of the model's texture or vertex colours.  A model whose
+        file names a texture (``comment TextureFile``) and has texture coordinates is drawn with it, else with its vertex
+        colours, else grey: the toolkit's order.  Other keywords of the toolkit's renderers are accepted and ignored."""
         self.model_paths[int(obj_id)] = model_path
         self.surf_colors[int(obj_id)] = surf_color
         self._meshes = None
@@ -322,7 +409,7 @@ class Renderer:
     @property
     def meshes(self) -> MeshSet:
         if self._meshes is None:
-            self._meshes = MeshSet(dict(self.model_paths), device=self.device, compute_normals=self.shading == "phong")
+            self._meshes = MeshSet(dict(self.model_paths), device=self.device, compute_normals=self.shading == "phong", textures=True)
         return self._meshes
 
     def render_object(self, obj_id, R, t, fx, fy, cx, cy) -> dict:
@@ -332,7 +419,8 @@ class Renderer:
         surf = self.surf_colors.get(int(obj_id))
         got = render(self.meshes, [(int(obj_id), np.asarray(R, np.float64).reshape(3, 3), np.asarray(t, np.float64).reshape(3))],
                      K, (self.width, self.height), outputs=outputs, shading=self.shading, ambient=self.light_ambient_weight,
-                     light=self.light_cam_pos, surf_colors=None if surf is None else [surf], bg=self.bg_color, near=self.near)
+                     light=self.light_cam_pos, surf_colors=None if surf is None else [surf], bg=self.bg_color, near=self.near,
+                     texture_filter=self.texture_filter)
         out = {}
         if "rgb" in got:
             out["rgb"] = rgb_to_uint8(got["rgb"][0]).cpu().numpy()
@@ -379,7 +467,8 @@ def depth_for_vis(depth, valid_start=0.2, valid_end=1.0):
 
 
 def vis_object_poses(poses, K, meshes: MeshSet, rgb=None, depth=None, vis_rgb_path=None, vis_depth_diff_path=None,
-                     vis_rgb_resolve_visib: bool = False, shading: str = "phong", near: float = DEFAULT_NEAR) -> dict:
+                     vis_rgb_resolve_visib: bool = False, shading: str = "phong", near: float = DEFAULT_NEAR,
+                     texture_filter: str = "nearest") -> dict:
     """visualization.vis_object_poses with the renderer replaced by the mesh set: the models of ``poses`` = [{'obj_id', 'R',
     't'}, ...] shaded and blended over ``rgb`` (uint8 [H,W,3]), and their depth against ``depth`` [H,W] (the poses' unit).
 
@@ -387,6 +476,7 @@ def vis_object_poses(poses, K, meshes: MeshSet, rgb=None, depth=None, vis_rgb_pa
     own and the images are summed, saturating at 255.  The RGB visualisation is 0.5 rgb + 0.5 render plus the grey box
     (misc.calc_2d_bbox of each object's own pixels), clipped at 255; the depth-difference image follows the toolkit's
     (valid = depth > 0 and rendered > 0, difference = valid (rendered - depth), red where it is below the VSD delta of 15).
+    A mesh set loaded with ``textures=True`` shows its textured objects textured (``texture_filter`` as in render).
     No text labels.  Images are written as PNG; returned: {'vis_rgb', 'depth_diff', 'depth_diff_vis', 'ren_depth'} (those asked for)."""
     vis_rgb, vis_diff = vis_rgb_path is not None, vis_depth_diff_path is not None
     if vis_rgb and rgb is None:
@@ -405,12 +495,13 @@ def vis_object_poses(poses, K, meshes: MeshSet, rgb=None, depth=None, vis_rgb_pa
     shared = None
     if jobs and (vis_diff or (vis_rgb and vis_rgb_resolve_visib)):
         shared = render(meshes, jobs, K, (W, H), outputs=("rgb", "depth") if vis_rgb else ("depth",), shading=shading, near=near,
-                        slots=[0] * len(jobs))
+                        slots=[0] * len(jobs), texture_filter=texture_filter)
     if vis_rgb:
         ren = np.zeros((H, W, 3), np.uint8)
         info = np.zeros((H, W, 3), np.uint8)
         if jobs:
-            own = rgb_to_uint8(render(meshes, jobs, K, (W, H), outputs=("rgb",), shading=shading, near=near)["rgb"]).cpu().numpy()
+            own = rgb_to_uint8(render(meshes, jobs, K, (W, H), outputs=("rgb",), shading=shading, near=near,
+                                      texture_filter=texture_filter)["rgb"]).cpu().numpy()
             if vis_rgb_resolve_visib:
                 ren = rgb_to_uint8(shared["rgb"][0]).cpu().numpy()
             else:
@@ -656,12 +747,13 @@ def recompute_dataset(dataset_dir, models_dir, delta: float = 15.0, translation_
 
 
 def visualize_dataset(dataset_dir, models_dir, out_dir, results=None, resolve_visib: bool = False, shading: str = "phong",
-                      translation_scale: float = 1.0, device="cuda") -> int:
+                      translation_scale: float = 1.0, device="cuda", textures: bool = False, texture_filter: str = "nearest") -> int:
     """The toolkit's vis_gt_poses.py (or, with ``results`` = a BOP results file, vis_est_poses.py): for every image of every
     scene under <dataset>/train the models at the ground-truth poses (or at the file's estimates for that scene and image)
-    shaded over the photograph, written to <out>/<scene>/<image>.png.  Returns the number of images written."""
+    shaded over the photograph, written to <out>/<scene>/<image>.png.  ``textures``: models that name a texture are drawn with
+    it.  Returns the number of images written."""
     unit = BD.unit_of(translation_scale)
-    meshes = MeshSet.from_dir(models_dir, device=device, scale=unit, compute_normals=shading == "phong")
+    meshes = MeshSet.from_dir(models_dir, device=device, scale=unit, compute_normals=shading == "phong", textures=textures)
     ests = None
     if results is not None:
         from .pose_eval import read_results
@@ -679,7 +771,7 @@ def visualize_dataset(dataset_dir, models_dir, out_dir, results=None, resolve_vi
             if rgb.ndim == 2:
                 rgb = np.repeat(rgb[:, :, None], 3, 2)
             vis_object_poses(poses, BD.cam_K(scene.camera[i]), meshes, rgb=rgb, vis_rgb_path=Path(out_dir) / scene.path.name / BD.image_name(i),
-                             vis_rgb_resolve_visib=resolve_visib, shading=shading)
+                             vis_rgb_resolve_visib=resolve_visib, shading=shading, texture_filter=texture_filter)
             written += 1
     return written
 
@@ -697,9 +789,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     p.add_argument("--results", help="with --vis: a BOP results file whose estimates are drawn instead (vis_est_poses.py)")
     p.add_argument("--resolve_visib", action="store_true", help="with --vis: only the nearest object shows at each pixel")
     p.add_argument("--shading", choices=("flat", "phong"), default="phong", help="with --vis")
+    p.add_argument("--textures", action="store_true", help="with --vis: models whose PLY names a texture image are drawn with it")
+    p.add_argument("--texture_filter", choices=sorted(TEXTURE_FILTERS), default="nearest", help="with --vis --textures")
     a = p.parse_args(argv)
     if a.vis:
-        n = visualize_dataset(a.dataset, a.models, a.vis, a.results, a.resolve_visib, a.shading, a.translation_scale)
+        n = visualize_dataset(a.dataset, a.models, a.vis, a.results, a.resolve_visib, a.shading, a.translation_scale,
+                              textures=a.textures, texture_filter=a.texture_filter)
         print(f"wrote {n} visualisation(s) under {a.vis}")
         return 0
     scenes = recompute_dataset(a.dataset, a.models, a.delta, a.translation_scale, a.batch)

@@ -2,7 +2,8 @@
 /root/reference/src/gs/gaussian_model.py:231-288 reads it with ``plyfile``, which is not available here).
 Supports ``binary_little_endian`` and ``ascii`` vertex elements with scalar properties.  Triangle meshes: ``write_ply_mesh`` /
 ``read_ply_mesh`` for the layout the project writes, ``read_ply_model`` / ``write_ply_model`` for BOP object model files (normals,
-colours, texture coordinates skipped) as the toolkit's ``inout.load_ply`` / ``save_ply`` read and write them."""
+colours; texture coordinates and the texture file's name on request) as the toolkit's ``inout.load_ply`` / ``save_ply`` read and
+write them."""
 from __future__ import annotations
 
 from pathlib import Path
@@ -130,20 +131,38 @@ def _model_header(data: bytes):
     return fmt, elements, end + 1
 
 
-def read_ply_model(path) -> dict:
+_UV_TYPES = ("float", "float32")
+
+
+def _texture_file(data: bytes):
+    """The name in the header line ``comment TextureFile <name>`` (the last one, its last word, as the toolkit reads it), or None."""
+    name = None
+    for line in data[:data.find(b"end_header")].decode("ascii", "replace").splitlines():
+        if line.startswith("comment TextureFile") and len(line.split()) > 2:
+            name = line.split()[-1]
+    return name
+
+
+def read_ply_model(path, texture: bool = False) -> dict:
     """A BOP object model as the toolkit's inout.load_ply returns it: {'pts' float64 [V,3], 'faces' int64 [F,3]} plus
     'normals' float64 [V,3] (nx ny nz) and 'colors' [V,3] (red green blue, as stored: uint8 or float) when present.  ASCII and
     binary little-endian; any scalar vertex properties in any order (texture_u / texture_v and unknown ones are skipped); the
     face list is ``list uchar|uint8 int|uint|int32|uint32 vertex_indices|vertex_index``; other elements and other face
     properties are not supported in front of or between them.  Faces that are not triangles, a file that ends early and a face
-    index outside the vertices raise ValueError."""
+    index outside the vertices raise ValueError.
+
+    With ``texture`` also what the toolkit's renderers texture a model with: 'texture_uv' float64 [V,2] when the vertex element
+    has texture_u and texture_v, 'texture_uv_face' float64 [F,6] (u_a v_a u_b v_b u_c v_c) when the face element has a second
+    property ``list uchar|uint8 float|float32 texcoord`` (before or after the index list; a count other than 6 raises
+    ValueError), and 'texture_file' (str) from a header line ``comment TextureFile <name>``.  Without ``texture`` such a face
+    element is refused, as before."""
     data = Path(path).read_bytes()
     fmt, elements, off = _model_header(data)
     text = None
     if fmt == "ascii":
         text = data[off:].decode("ascii", "replace").split("\n")
         line = 0
-    vert, faces = None, None
+    vert, faces, uv_face = None, None, None
     for name, count, props in elements:
         if name == "vertex":
             if any(p[0] == "list" for p in props):
@@ -168,6 +187,11 @@ def read_ply_model(path) -> dict:
                 vert = np.frombuffer(data, dt, count, off)
                 off += count * dt.itemsize
         elif name == "face":
+            tex = [p for p in props if texture and p[0] == "list" and len(p) > 3 and p[3] == "texcoord"]
+            if len(tex) > 1 or (tex and (tex[0][1] not in _COUNT_TYPES or tex[0][2] not in _UV_TYPES)):
+                raise ValueError(f"unsupported face properties {props}: one list uchar float texcoord expected")
+            index_first = not tex or props[0] is not tex[0]
+            props = [p for p in props if not (tex and p is tex[0])]
             lists = [p for p in props if p[0] == "list"]
             if len(props) != 1 or len(lists) != 1 or lists[0][1] not in _COUNT_TYPES or lists[0][2] not in _INDEX_TYPES or \
                     lists[0][3] not in ("vertex_indices", "vertex_index"):
@@ -179,15 +203,45 @@ def read_ply_model(path) -> dict:
                 rows = [text[line + r].split() for r in range(count)]
                 if any(not r for r in rows):
                     raise ValueError("PLY file ends inside the face element")
+                if tex:
+                    # the two lists in the header's order: 3 a b c | 6 u_a v_a u_b v_b u_c v_c
+                    at_i, at_t = (0, 4) if index_first else (7, 0)
+                    if any(len(r) <= at_i or r[at_i] != "3" for r in rows):
+                        raise ValueError("faces must be triangles")
+                    if any(len(r) <= at_t or r[at_t] != "6" for r in rows):
+                        raise ValueError("a texcoord list must hold 6 values (u, v of three corners)")
+                    if any(len(r) != 11 for r in rows):
+                        raise ValueError("PLY file ends inside the face element")
+                    uv_face = np.array([r[at_t + 1:at_t + 7] for r in rows], np.float64).reshape(count, 6)
+                    rows = [r[at_i:at_i + 4] for r in rows]
                 if any(r[0] != "3" or len(r) != 4 for r in rows):
                     raise ValueError("faces must be triangles")
                 faces = np.array([r[1:] for r in rows], np.int64).reshape(count, 3)
                 line += count
             else:
-                dt = np.dtype([("n", "u1"), ("idx", "<" + it, (3,))])
+                fields = [("n", "u1"), ("idx", "<" + it, (3,))]
+                if tex:
+                    uv_fields = [("tn", "u1"), ("uv", "<f4", (6,))]
+                    fields = fields + uv_fields if index_first else uv_fields + fields
+                dt = np.dtype(fields)
+                if tex and count:
+                    # the first record's two counts, read where they stand even when a short list leaves less than a whole
+                    # record: the second one only when the first is right (else it is not where it is looked for)
+                    at_n, at_t = (0, dt.fields["tn"][1]) if index_first else (dt.fields["n"][1], 0)
+                    for at, want, what in sorted([(at_n, 3, "faces must be triangles"),
+                                                  (at_t, 6, "a texcoord list must hold 6 values (u, v of three corners)")]):
+                        if off + at < len(data) and data[off + at] != want:
+                            raise ValueError(what)
                 have = min(count, max(0, len(data) - off) // dt.itemsize)
                 rows = np.frombuffer(data, dt, have, off)
-                if (rows["n"] != 3).any():
+                first_bad = rows["n"] != 3
+                if tex:
+                    # a wrong count in the first list shifts what follows: report the one that comes first in the record
+                    tex_bad = rows["tn"] != 6
+                    if (tex_bad & ~first_bad).any() if index_first else tex_bad.any():
+                        raise ValueError("a texcoord list must hold 6 values (u, v of three corners)")
+                    uv_face = rows["uv"].astype(np.float64)
+                if first_bad.any():
                     raise ValueError("faces must be triangles")
                 if have < count:
                     raise ValueError("PLY file ends inside the face element")
@@ -205,13 +259,26 @@ def read_ply_model(path) -> dict:
         model["normals"] = cols(("nx", "ny", "nz"))
     if {"red", "green", "blue"} <= set(vert.dtype.names):
         model["colors"] = cols(("red", "green", "blue"), np.result_type(*(vert.dtype[n] for n in ("red", "green", "blue"))))
+    if texture:
+        if {"texture_u", "texture_v"} <= set(vert.dtype.names):
+            model["texture_uv"] = np.stack([vert["texture_u"], vert["texture_v"]], 1).astype(np.float64) if len(vert) else np.zeros((0, 2))
+        if uv_face is not None:
+            model["texture_uv_face"] = uv_face
+        name = _texture_file(data)
+        if name is not None:
+            model["texture_file"] = name
     return model
 
 
-def write_ply_model(path, pts, faces, normals=None, colors=None, ascii: bool = False):
+def write_ply_model(path, pts, faces, normals=None, colors=None, ascii: bool = False, texture_uv=None, texture_uv_face=None,
+                    texture_file=None):
     """A BOP object model in the property order of the toolkit's inout.save_ply: x y z, nx ny nz, red green blue (uchar; float
     colours are written as float), then ``list uchar int vertex_indices``.  Binary little-endian, or ASCII with ``ascii``
-    (floats with 9 significant digits: a float32 survives the round trip)."""
+    (floats with 9 significant digits: a float32 survives the round trip).
+
+    Texture (each optional; with none the bytes are those of a call without them), in save_ply2's order: ``texture_uv`` [V,2] as
+    ``texture_u texture_v`` behind the colours, ``texture_uv_face`` [F,6] as ``list uchar float texcoord`` behind the index list,
+    ``texture_file`` as ``comment TextureFile <name>`` directly after the format line.  Coordinates are written as float32."""
     pts = np.asarray(pts, np.float32).reshape(-1, 3)
     faces = np.asarray(faces, np.int32).reshape(-1, 3)
     fields, cols = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")], [pts]
@@ -223,10 +290,21 @@ def write_ply_model(path, pts, faces, normals=None, colors=None, ascii: bool = F
         ct = "u1" if colors.dtype.kind in "ui" else "<f4"
         fields += [("red", ct), ("green", ct), ("blue", ct)]
         cols.append(colors.astype(ct))
+    if texture_uv is not None:
+        fields += [("texture_u", "<f4"), ("texture_v", "<f4")]
+        cols.append(np.asarray(texture_uv, np.float32).reshape(len(pts), 2))
+    if texture_uv_face is not None:
+        texture_uv_face = np.asarray(texture_uv_face, np.float32).reshape(len(faces), 6)
     names = {"<f4": "float", "u1": "uchar"}
-    header = "ply\nformat %s 1.0\nelement vertex %d\n" % ("ascii" if ascii else "binary_little_endian", len(pts))
+    header = "ply\nformat %s 1.0\n" % ("ascii" if ascii else "binary_little_endian")
+    if texture_file is not None:
+        header += f"comment TextureFile {texture_file}\n"
+    header += "element vertex %d\n" % len(pts)
     header += "".join(f"property {names[t]} {n}\n" for n, t in fields)
-    header += "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % len(faces)
+    header += "element face %d\nproperty list uchar int vertex_indices\n" % len(faces)
+    if texture_uv_face is not None:
+        header += "property list uchar float texcoord\n"
+    header += "end_header\n"
     Path(path).parent.mkdir(parents=True, exist_ok=True)
     with open(path, "wb") as fh:
         fh.write(header.encode("ascii"))
@@ -234,17 +312,22 @@ def write_ply_model(path, pts, faces, normals=None, colors=None, ascii: bool = F
             fmt = lambda a: [str(int(x)) for x in a] if a.dtype.kind in "ui" else ["%.9g" % x for x in a]
             for r in range(len(pts)):
                 fh.write((" ".join(sum((fmt(c[r]) for c in cols), [])) + "\n").encode("ascii"))
-            for f in faces:
-                fh.write(("3 %d %d %d\n" % tuple(f)).encode("ascii"))
+            for k, f in enumerate(faces):
+                tail = "" if texture_uv_face is None else " 6 " + " ".join(fmt(texture_uv_face[k]))
+                fh.write(("3 %d %d %d%s\n" % (*f, tail)).encode("ascii"))
         else:
             arr = np.empty(len(pts), np.dtype(fields))
             at = 0
             for c in cols:
-                for k in range(3):
+                for k in range(c.shape[1]):
                     arr[fields[at + k][0]] = c[:, k]
-                at += 3
-            rows = np.empty(len(faces), np.dtype([("n", "u1"), ("idx", "<i4", (3,))]))
+                at += c.shape[1]
+            face_fields = [("n", "u1"), ("idx", "<i4", (3,))] + ([] if texture_uv_face is None else [("tn", "u1"), ("uv", "<f4", (6,))])
+            rows = np.empty(len(faces), np.dtype(face_fields))
             rows["n"] = 3
             rows["idx"] = faces
+            if texture_uv_face is not None:
+                rows["tn"] = 6
+                rows["uv"] = texture_uv_face
             fh.write(arr.tobytes())
             fh.write(rows.tobytes())
